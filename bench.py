@@ -236,6 +236,36 @@ def valu_note(counters):
                     "vector lane-issue capacity doing work — the limit that binds these kernels (the tree is cache-resident)"}
 
 
+DUMP_BUDGET = 64_000_000  # bytes, all files of --dump-outputs together
+DUMP_SEED = 20240611
+
+
+def dump_outputs(r, out_dir, aovs):
+    """--dump-outputs: what the timed path computed in its last step — the images a caller reads back (read_image) — as
+    float32 .npy files.  The accumulated colour image is written whole when it fits in the budget beside the others; larger
+    images, and the albedo / normal AOVs, as a fixed seeded sample of pixels (row-major pixel indices in pixel_index.npy, float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = r.width * r.height
+    k = min(n, 524_288)
+    idx = np.sort(np.random.RandomState(DUMP_SEED).choice(n, size=k, replace=False))
+    names = {r.ACCUM: "accum", r.ALBEDO: "albedo", r.NORMAL: "normal"}
+    room = DUMP_BUDGET - (len(aovs) - 1) * k * 16 - k * 8  # what the samples and their indices leave for the whole image
+    written = {}
+    for which in aovs:
+        img = r.read_image(which)  # (H, W, 4) float32
+        if which == r.ACCUM and img.nbytes <= room:
+            arr, name = img, names[which]
+        else:
+            arr, name = img.reshape(n, 4)[idx], names[which] + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+        written[name] = list(arr.shape)
+    if any(name.endswith("_sample") for name in written):
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+        written["pixel_index"] = [k]
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -243,7 +273,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the images of the last timed step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python3 bench.py --gpus N` from a bare shell: start the N ranks ourselves, exactly as the driver would (one process per GPU
@@ -296,6 +330,10 @@ def main():
     # (two timed frames from 8 steps on, else exactly one: any `p` consecutive updates hold one multiple of `p`)
     period = int(os.environ.get("BENCH_TIMING_PERIOD", str(args.steps // 2 if args.steps >= 8 else max(1, args.steps))))
     dt, s0, s1 = run.measure(args.steps, args.warmup, timing_period=period, fusion=2)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before the extra frames below render again: the last timed step's images (the fence above finished its all-gather, if any)
+        dumped = dump_outputs(run.r, args.dump_outputs, (run.r.ACCUM,) if world > 1 else (run.r.ACCUM, run.r.ALBEDO, run.r.NORMAL))
     rays_local = s1.rays_total - s0.rays_total
     t_local = torch.tensor([dt, float(rays_local)], dtype=torch.float64, device=f"cuda:{local_rank}")
     if dist is not None:
@@ -381,6 +419,8 @@ def main():
                        "scaling_note": "N = 1 renders configs[3] (1920x1080); N > 1 renders configs[4] (3840x2160) strong-scaled; the single-GPU time of the 4K frame is under secondary.configs4_on_1_gpu"},
             "roofline": roof,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     run.close()
 
     if rank == 0 and world == 1:
