@@ -41,6 +41,9 @@ def load_library():
         _lib = _C.CDLL(LIB_PATH)
         _lib.hala_last_error_message.restype = _C.c_char_p
         _lib.hala_version.restype = _C.c_char_p
+        for name, (argtypes, restype) in _abi.PROTOTYPES.items():
+            fn = getattr(_lib, name)
+            fn.argtypes, fn.restype = argtypes, restype
     return _lib
 
 
@@ -53,7 +56,7 @@ def check(status: int):
         raise HalaRendererError(last_error())
 
 
-from .renderer import HalaRenderer  # noqa: E402,F401
+from .renderer import HalaRenderer, denoise_images, denoise_default_params  # noqa: E402,F401
 from .raytracing_program import (HalaRayTracingProgram, HalaRayTracingProgramDesc,  # noqa: E402,F401
                                  HalaRayTracingHitShaderDesc)
 

@@ -178,6 +178,23 @@ class RtProgDescInfo(C.Structure):
                 ("binding_count", C.c_uint32), ("ray_recursion_depth", C.c_uint32)]
 
 
+class DenoiseParams(C.Structure):  # hala_denoise_params, 32 B (docs/RENDER_SPEC.md 10)
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_albedo", C.c_float),
+                ("normal_power", C.c_uint32), ("demodulate", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+# argtypes / restype of the denoise entry points (load_library installs them)
+PROTOTYPES = {
+    "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
+    "hala_rt_denoise": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_read_denoised": ([C.c_void_p, C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_get_denoised_buffer": ([C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)], C.c_int),
+    "hala_rt_save_denoised": ([C.c_void_p, C.c_char_p], C.c_int),
+    "hala_denoise_images": ([C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
+                             C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
+}
+
+
 # numpy dtypes of the batch records
 import numpy as _np
 
@@ -208,4 +225,6 @@ EXPORTS = [
     "hala_rt_comm_unique_id", "hala_rt_comm_init_rank", "hala_rt_comm_attach", "hala_rt_comm_destroy",
     "hala_rt_tile_allgather", "hala_rt_tile_allgather_begin", "hala_rt_tile_allgather_finish", "hala_rt_get_gathered_buffer",
     "hala_rt_tile_allgather_begin_external", "hala_rt_get_exchange_buffers",
+    "hala_denoise_default_params", "hala_rt_denoise", "hala_rt_read_denoised", "hala_rt_get_denoised_buffer", "hala_rt_save_denoised",
+    "hala_denoise_images",
 ]

@@ -13,6 +13,7 @@
 #include <sys/stat.h>
 #include <vector>
 
+#include "denoise.h"
 #include "dyn_api.h"
 #include "hala_types.h"
 #include "host_image.h"
@@ -187,6 +188,8 @@ struct hala_rt_renderer {
   DeviceArray<float4> img_local[4];  // accum, albedo, normal, final (slot order)
   DeviceArray<float4> img_full[4];   // row-major, only after scatter_gathered_tiles (world > 1)
   bool full_valid[4] = {false, false, false, false};
+  DenoiseBuffers denoise;      // RENDER_SPEC 10: allocated by the first hala_rt_denoise
+  bool denoised = false;       // denoise.out holds a result
   DeviceArray<P3> ps_lr, ps_le, ps_alb, ps_nrm;
   DeviceArray<hala_ray> q_rays[2];
   DeviceArray<float4> q_state[2];
@@ -1217,6 +1220,65 @@ int hala_rt_reset_accumulation(hala_rt_renderer* r) {
   r->reset_accumulation();
   return HALA_OK;
 }
+
+// ---- denoising (RENDER_SPEC 10) -----------------------------------------------------------------------------------------------
+int hala_rt_denoise(hala_rt_renderer* r, const hala_denoise_params* p, float* gpu_ms) {
+  RtRange range("halart::denoise");
+  const std::string bad = denoise_check_params(p);  // first: the CPU tier pins it without a renderer
+  if (!bad.empty()) RT_FAIL(bad);
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (r->total_frames == 0) RT_FAIL("Nothing to denoise: no sample has been accumulated since the renderer was created or its accumulation reset.");
+  if (r->world > 1 && !(r->full_valid[0] && r->full_valid[1] && r->full_valid[2]))
+    RT_FAIL("The frame is sharded across ranks: gather AOVs 0, 1 and 2 (accum, albedo, normal) before denoising.");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  DeviceArray<float4>* img = r->world > 1 ? r->img_full : r->img_local;
+  RT_HIP(r->denoise.ensure(r->width, r->height));
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  if (gpu_ms) {
+    RT_HIP(hipEventCreate(&ev[0]));
+    if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipEventDestroy(ev[0]); RT_FAIL("hipEventCreate failed."); }
+  }
+  hipError_t e = gpu_ms ? hipEventRecord(ev[0], r->stream) : hipSuccess;
+  if (e == hipSuccess) e = denoise_enqueue(r->denoise, img[0].ptr, img[1].ptr, img[2].ptr, *p, r->stream);
+  if (e == hipSuccess && gpu_ms) e = hipEventRecord(ev[1], r->stream);
+  if (e == hipSuccess && gpu_ms) e = hipEventSynchronize(ev[1]);
+  if (e == hipSuccess && gpu_ms) e = hipEventElapsedTime(gpu_ms, ev[0], ev[1]);
+  for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+  if (e != hipSuccess) RT_FAIL(std::string("hala_rt_denoise: ") + hipGetErrorString(e));
+  r->denoised = true;
+  return HALA_OK;
+}
+int hala_rt_read_denoised(hala_rt_renderer* r, float* dst) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!dst) RT_FAIL("Invalid argument.");
+  if (!r->denoised) RT_FAIL("Nothing has been denoised yet (hala_rt_denoise).");
+  RT_HIP(hipStreamSynchronize(r->stream));
+  RT_HIP(hipMemcpy(dst, r->denoise.out.ptr, (size_t)r->denoise.width * r->denoise.height * sizeof(float4), hipMemcpyDeviceToHost));
+  return HALA_OK;
+}
+int hala_rt_get_denoised_buffer(hala_rt_renderer* r, void** d_ptr, size_t* bytes) {
+  if (!r || !d_ptr || !bytes) RT_FAIL("Invalid argument.");
+  if (!r->denoised) RT_FAIL("Nothing has been denoised yet (hala_rt_denoise).");
+  *d_ptr = r->denoise.out.ptr;
+  *bytes = (size_t)r->denoise.width * r->denoise.height * sizeof(float4);
+  return HALA_OK;
+}
+int hala_rt_save_denoised(hala_rt_renderer* r, const char* path) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!path || !*path) RT_FAIL("The file name is none!");
+  if (!r->denoised) RT_FAIL("Nothing has been denoised yet (hala_rt_denoise).");
+  std::string p(path);
+  const size_t slash = p.find_last_of("/\\");
+  const std::string dir = slash == std::string::npos ? "" : p.substr(0, slash + 1);
+  const size_t n = (size_t)r->denoise.width * r->denoise.height;
+  std::vector<float> px(n * 4);
+  if (hala_rt_read_denoised(r, px.data()) != HALA_OK) return HALA_ERR;
+  tonemap_pixels(px.data(), n, r->enable_tonemap, r->enable_aces, r->use_simple_aces);  // as save_images treats _color.pfm
+  const std::string e = write_pfm((dir + file_stem(path) + "_denoised.pfm").c_str(), px.data(), r->denoise.width, r->denoise.height);
+  if (!e.empty()) RT_FAIL(e);
+  return HALA_OK;
+}
+
 int hala_rt_set_launch_timing_period(hala_rt_renderer* r, uint32_t period) {
   if (!r) RT_FAIL("The renderer handle is null!");
   r->launch_event_period = period;

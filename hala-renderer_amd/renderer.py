@@ -185,6 +185,31 @@ class HalaRenderer:
         self._check(self._lib.hala_rt_read_image(self._h, C.c_int(which), out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    # -- denoising (docs/RENDER_SPEC.md 10; include/halart.h "hala_rt_denoise") -----------------------------------
+    def denoise(self, iterations=None, sigma_color=None, sigma_albedo=None, normal_power=None, demodulate=True, timed=False):
+        """filter accum / albedo / normal into the denoised image (stream-ordered; None: the library's default).  timed: wait and
+        return the GPU milliseconds of the filter's launches"""
+        p = denoise_default_params(iterations=iterations, sigma_color=sigma_color, sigma_albedo=sigma_albedo,
+                                   normal_power=normal_power, demodulate=demodulate)
+        ms = C.c_float(0.0)
+        self._check(self._lib.hala_rt_denoise(self._h, C.byref(p), C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
+    def read_denoised(self) -> np.ndarray:
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self._lib.hala_rt_read_denoised(self._h, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def denoised_buffer(self):
+        """-> (device address, bytes) of the denoised RGBA32F image (zero-copy; wrap it on the renderer's stream)"""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._lib.hala_rt_get_denoised_buffer(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def save_denoised(self, path):
+        """<stem>_denoised.pfm, tonemapped on the host like save_images' <stem>_color.pfm"""
+        self._check(self._lib.hala_rt_save_denoised(self._h, os.fsencode(path)))
+
     def global_uniform(self) -> A.GlobalUniform:
         u = A.GlobalUniform()
         self._check(self._lib.hala_rt_get_global_uniform(self._h, C.byref(u)))
@@ -348,3 +373,38 @@ class HalaRenderer:
     def scatter_gathered_tiles(self, which, d_gathered: int, nbytes: int, stream: int = 0):
         """de-interleave a gathered buffer into this renderer's row-major image; stream = a hipStream_t of the caller's (0: the renderer's)"""
         self._check(self._lib.hala_rt_scatter_gathered_tiles_on_stream(self._h, C.c_int(which), C.c_void_p(d_gathered), C.c_size_t(nbytes), C.c_void_p(stream or None)))
+
+
+def denoise_default_params(**overrides) -> A.DenoiseParams:
+    """hala_denoise_default_params with the fields given (not None) replaced"""
+    from . import load_library
+    p = A.DenoiseParams()
+    load_library().hala_denoise_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if v is not None:
+            setattr(p, k, int(bool(v)) if k == "demodulate" else v)
+    return p
+
+
+def denoise_images(color, albedo, normal, device_ordinal=0, **params) -> np.ndarray:
+    """hala_denoise_images: the RENDER_SPEC 10 filter on host images [H, W, 3 or 4] (e.g. the PFM trio of save_images); returns the
+    denoised RGBA32F [H, W, 4].  params: iterations, sigma_color, sigma_albedo, normal_power, demodulate."""
+    from . import check, load_library
+
+    def rgba(x):
+        x = np.asarray(x, dtype=np.float32)
+        if x.ndim != 3 or x.shape[2] not in (3, 4):
+            raise ValueError("expected an image of shape [H, W, 3] or [H, W, 4]")
+        if x.shape[2] == 3:
+            x = np.concatenate([x, np.ones(x.shape[:2] + (1,), np.float32)], axis=2)
+        return np.ascontiguousarray(x)
+
+    c, a, n = rgba(color), rgba(albedo), rgba(normal)
+    if not (c.shape == a.shape == n.shape):
+        raise ValueError("color, albedo and normal must have the same size")
+    h, w = c.shape[:2]
+    p = denoise_default_params(**params)
+    out = np.empty((h, w, 4), dtype=np.float32)
+    fp = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    check(load_library().hala_denoise_images(device_ordinal, fp(c), fp(a), fp(n), w, h, C.byref(p), fp(out)))
+    return out

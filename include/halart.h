@@ -596,6 +596,37 @@ int hala_rt_update_material(hala_rt_renderer* r, uint32_t material_index, const 
 int hala_rt_refit(hala_rt_renderer* r);
 
 /* ------------------------------------------------------------------------------------------------
+ * Denoising (docs/RENDER_SPEC.md 10; no reference equivalent): an edge-avoiding a-trous wavelet filter over the running
+ * means, guided by the first-hit albedo and normal AOVs.  Opt-in: nothing is allocated for a renderer that never denoises.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hala_denoise_params {
+  uint32_t iterations;   /* N, 1..8: pass i gathers 5 x 5 taps 2^i pixels apart */
+  float sigma_color;     /* colour tolerance of pass 0 (halves with each pass), in [1e-6, 1e6] */
+  float sigma_albedo;    /* albedo tolerance, in [1e-6, 1e6] */
+  uint32_t normal_power; /* exponent of the normal weight: a power of two, 1..128 */
+  uint32_t demodulate;   /* 1: filter radiance / albedo and multiply the albedo back; 0: filter the radiance itself */
+  uint32_t reserved[3];  /* must be zero */
+} hala_denoise_params;   /* 32 B */
+/* the defaults (DESIGN.md "Denoising" records the measurements behind them) */
+void hala_denoise_default_params(hala_denoise_params* out);
+/* Filters the renderer's accum / albedo / normal into its denoised image (RGBA32F, alpha 1).  Stream-ordered on the renderer's
+ * stream behind the updates enqueued so far; returns without waiting when gpu_ms is NULL, else times its own launches with HIP
+ * events, waits and stores the milliseconds.  Writes none of the four images.  Refused: no sample accumulated since creation,
+ * hala_rt_reset_accumulation or hala_rt_set_tile_shard; a sharded renderer (world > 1) whose AOVs 0, 1 and 2 have not all been
+ * gathered since the last update (then the gathered frame is filtered).  Parameters are validated before any device call. */
+int hala_rt_denoise(hala_rt_renderer* r, const hala_denoise_params* p, float* gpu_ms);
+/* the last denoised image: W*H*4 floats, linear, row 0 = top */
+int hala_rt_read_denoised(hala_rt_renderer* r, float* dst_rgba32f);
+/* zero-copy: its device address and byte size (valid until the next hala_rt_denoise that changes the size, or destroy) */
+int hala_rt_get_denoised_buffer(hala_rt_renderer* r, void** d_ptr, size_t* bytes);
+/* <stem>_denoised.pfm beside what save_images writes, tonemapped on the host like <stem>_color.pfm */
+int hala_rt_save_denoised(hala_rt_renderer* r, const char* path);
+/* the same filter on host images (e.g. the PFM trio of save_images, as hala_load_float_image reads it, widened to RGBA32F):
+ * color / albedo / normal / dst are W*H*4 floats, row 0 = top.  Parameters are validated before any device call. */
+int hala_denoise_images(int device_ordinal, const float* color, const float* albedo, const float* normal, uint32_t width,
+                        uint32_t height, const hala_denoise_params* p, float* dst);
+
+/* ------------------------------------------------------------------------------------------------
  * Stand-alone pieces of the path (usable without a renderer)
  * ---------------------------------------------------------------------------------------------- */
 /* EnvMap::build_distribution_maps (src/envmap.rs:239-388) on the GPU. pixels: RGBA32F host, W*H*4. */

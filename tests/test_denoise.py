@@ -1,0 +1,370 @@
+"""The a-trous denoiser (docs/RENDER_SPEC.md 10): ABI surface and parameter checks on the CPU tier; on the GPU tier the HIP kernels
+bit for bit against the numpy twin (tests/denoise_ref.py), through the renderer, sharded, and what the filter does to images."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import denoise_ref as R
+import hala_renderer_amd as H
+from conftest import ROOT
+from hala_renderer_amd import _abi as A
+from hala_renderer_amd import scenes
+
+f32 = np.float32
+gpu = pytest.mark.gpu
+NEW_FUNCTIONS = ["hala_denoise_default_params", "hala_rt_denoise", "hala_rt_read_denoised", "hala_rt_get_denoised_buffer",
+                 "hala_rt_save_denoised", "hala_denoise_images"]
+
+
+def fp(x):
+    return x.ctypes.data_as(C.POINTER(C.c_float))
+
+
+# ---- CPU tier ---------------------------------------------------------------------------------------------------------------------------
+def test_header_declares_and_library_exports_the_denoiser(halart):
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "halart.h")).read(), flags=re.S)
+    lib = C.CDLL(halart.LIB_PATH)
+    for name in NEW_FUNCTIONS:
+        assert re.search(rf"\b{name}\s*\(", text), name
+        assert name in A.EXPORTS, name
+        assert hasattr(lib, name), name
+
+
+def test_denoise_params_layout():
+    assert C.sizeof(A.DenoiseParams) == 32
+    offsets = {f: getattr(A.DenoiseParams, f).offset for f, _ in A.DenoiseParams._fields_}
+    assert offsets == {"iterations": 0, "sigma_color": 4, "sigma_albedo": 8, "normal_power": 12, "demodulate": 16, "reserved": 20}
+    assert re.search(r"\}\s*hala_denoise_params;\s*/\*\s*32 B", open(os.path.join(ROOT, "include", "halart.h")).read())
+
+
+def test_default_params(halart):
+    p = halart.denoise_default_params()
+    assert (p.iterations, p.normal_power, p.demodulate, list(p.reserved)) == (5, 32, 1, [0, 0, 0])
+    assert p.sigma_color > 0 and p.sigma_albedo > 0
+
+
+BAD_PARAMS = [
+    ("iterations", 0, "iterations"), ("iterations", 9, "iterations"),
+    ("normal_power", 3, "normal_power"), ("normal_power", 0, "normal_power"), ("normal_power", 256, "normal_power"),
+    ("sigma_color", 0.0, "sigma_color"), ("sigma_color", -1.0, "sigma_color"), ("sigma_color", math.nan, "sigma_color"),
+    ("sigma_color", math.inf, "sigma_color"),
+    ("sigma_albedo", 0.0, "sigma_albedo"), ("sigma_albedo", -0.5, "sigma_albedo"), ("sigma_albedo", math.nan, "sigma_albedo"),
+    ("demodulate", 2, "demodulate"),
+]
+
+
+@pytest.mark.parametrize("field,value,word", BAD_PARAMS)
+def test_invalid_params_are_refused_before_any_device_call(halart, field, value, word):
+    lib = halart.load_library()
+    img = np.zeros((2, 3, 4), f32)
+    p = halart.denoise_default_params()
+    setattr(p, field, value)
+    assert lib.hala_denoise_images(0, fp(img), fp(img), fp(img), 3, 2, C.byref(p), fp(img)) == 1
+    assert word in halart.last_error()
+    assert lib.hala_rt_denoise(None, C.byref(p), None) == 1  # validated before the renderer handle is looked at
+    assert word in halart.last_error()
+    if field != "demodulate":  # the Python wrapper takes demodulate as a bool
+        with pytest.raises(halart.HalaRendererError, match=word):
+            halart.denoise_images(img, img, img, **{field: value})
+
+
+def test_invalid_arguments_are_refused_before_any_device_call(halart):
+    lib = halart.load_library()
+    img = np.zeros((2, 3, 4), f32)
+    p = halart.denoise_default_params()
+    p.reserved[1] = 7
+    assert lib.hala_denoise_images(0, fp(img), fp(img), fp(img), 3, 2, C.byref(p), fp(img)) == 1 and "reserved" in halart.last_error()
+    assert lib.hala_denoise_images(0, fp(img), fp(img), fp(img), 3, 2, None, fp(img)) == 1 and "null" in halart.last_error()
+    p = halart.denoise_default_params()
+    for w, h in ((0, 2), (3, 0)):
+        assert lib.hala_denoise_images(0, fp(img), fp(img), fp(img), w, h, C.byref(p), fp(img)) == 1
+        assert "size" in halart.last_error()
+    for k in range(4):
+        args = [fp(img)] * 4
+        args[k] = None
+        assert lib.hala_denoise_images(0, args[0], args[1], args[2], 3, 2, C.byref(p), args[3]) == 1
+        assert "null" in halart.last_error()
+    assert lib.hala_rt_denoise(None, C.byref(p), None) == 1 and "null" in halart.last_error()
+    with pytest.raises(halart.HalaRendererError, match="size"):
+        halart.denoise_images(np.zeros((0, 3, 3)), np.zeros((0, 3, 3)), np.zeros((0, 3, 3)))
+
+
+def random_aovs(w, h, seed):
+    """AOV-like inputs: running means of radiance (HDR spikes to 1e4), albedo (zeros and values above 1), normals (averaged unit
+    vectors, zero for misses and lights)"""
+    rng = np.random.default_rng(seed)
+    color = rng.exponential(0.4, (h, w, 3)).astype(f32)
+    spikes = rng.random((h, w)) < 0.02
+    color[spikes] *= f32(1e4) * rng.random((int(spikes.sum()), 1)).astype(f32)
+    albedo = rng.uniform(0.0, 1.3, (h, w, 3)).astype(f32)
+    albedo[rng.random((h, w)) < 0.05] = 0.0
+    n = rng.normal(size=(h, w, 3))
+    n /= np.linalg.norm(n, axis=2, keepdims=True)
+    n *= rng.uniform(0.6, 1.0, (h, w, 1))
+    n[rng.random((h, w)) < 0.1] = 0.0
+    one = np.ones((h, w, 1), f32)
+    return [np.concatenate([x.astype(f32), one], axis=2) for x in (color, albedo, n)]
+
+
+def test_twin_preserves_a_constant_image():
+    c, a, n = random_aovs(40, 30, 1)
+    for demod in (False, True):
+        color = np.full_like(c, 0.7)
+        color[..., :3] *= np.maximum(a[..., :3], f32(1 / 256)) if demod else 1
+        out = R.denoise(color, a, n, iterations=5, sigma_color=0.3, sigma_albedo=0.2, normal_power=8, demodulate=demod)
+        np.testing.assert_allclose(out[..., :3], color[..., :3], rtol=1e-6)
+        assert (out[..., 3] == 1).all()
+
+
+def test_twin_with_identical_guides_is_the_b3_blur():
+    rng = np.random.default_rng(2)
+    h, w = 23, 31
+    color = rng.uniform(0, 2, (h, w, 4)).astype(f32)
+    albedo = np.full((h, w, 4), 0.5, f32)
+    normal = np.zeros((h, w, 4), f32)
+    normal[..., 2] = 1
+    out = R.denoise(color, albedo, normal, iterations=1, sigma_color=1e6, sigma_albedo=1e6, normal_power=128, demodulate=False)
+    np.testing.assert_allclose(out[..., :3], R.b3_blur(color[..., :3]), rtol=2e-6)
+
+
+# ---- GPU tier: bit-exact against the twin -----------------------------------------------------------------------------------------
+POWERS = [1, 2, 4, 8, 16, 32, 64, 128]
+SIZES = [(1, 1), (7, 300), (96, 64), (333, 187), (517, 530)]  # 517 x 530: above 512 both ways, not a multiple of the 16 x 16 tile
+
+
+def params(k, iterations, demod):
+    return dict(iterations=iterations, sigma_color=[0.5, 0.1, 2.0][k % 3], sigma_albedo=[0.1, 0.35][k % 2],
+                normal_power=POWERS[k % len(POWERS)], demodulate=demod)
+
+
+@gpu
+@pytest.mark.parametrize("w,h", SIZES)
+def test_bit_exact_against_the_twin(halart, w, h):
+    c, a, n = random_aovs(w, h, w * 1000 + h)
+    k = 0
+    for iterations in (1, 5, 8):
+        for demod in (True, False):
+            p = params(k + w, iterations, demod)
+            k += 1
+            got = halart.denoise_images(c, a, n, **p)
+            want = R.denoise(c, a, n, **p)
+            assert got.tobytes() == want.tobytes(), (p, int((got != want).sum()))
+
+
+@gpu
+@pytest.mark.parametrize("power", POWERS)
+def test_bit_exact_every_normal_power(halart, power):
+    c, a, n = random_aovs(61, 47, power)
+    for demod in (True, False):
+        p = dict(iterations=3, sigma_color=0.4, sigma_albedo=0.2, normal_power=power, demodulate=demod)
+        assert halart.denoise_images(c, a, n, **p).tobytes() == R.denoise(c, a, n, **p).tobytes(), p
+
+
+@gpu
+def test_rgb_inputs_and_defaults(halart):
+    """[H, W, 3] inputs (the PFM trio as hala_load_float_image reads it) and the library's defaults"""
+    c, a, n = random_aovs(50, 40, 5)
+    d = halart.denoise_default_params()
+    want = R.denoise(c, a, n, iterations=d.iterations, sigma_color=d.sigma_color, sigma_albedo=d.sigma_albedo,
+                     normal_power=d.normal_power, demodulate=bool(d.demodulate))
+    assert halart.denoise_images(c[..., :3], a[..., :3], n[..., :3]).tobytes() == want.tobytes()
+
+
+# ---- GPU tier: through the renderer ----------------------------------------------------------------------------------------------
+def cornell(halart, w, h, tonemap=(False, False, False)):
+    r = halart.HalaRenderer("denoise", w, h, 5, 3, *tonemap, 0)
+    r.set_scene(scenes.cornell_box(aspect=w / h))
+    r.commit()
+    return r
+
+
+def twin_of(r, **p):
+    d = H.denoise_default_params(**p)
+    return R.denoise(r.read_image(0), r.read_image(1), r.read_image(2), iterations=d.iterations, sigma_color=d.sigma_color,
+                     sigma_albedo=d.sigma_albedo, normal_power=d.normal_power, demodulate=bool(d.demodulate))
+
+
+@gpu
+def test_renderer_denoise_matches_the_twin(halart):
+    r = cornell(halart, 96, 64)
+    r.update_batch(2)
+    ms = r.denoise(timed=True)
+    assert ms > 0
+    assert r.read_denoised().tobytes() == twin_of(r).tobytes()
+    for p in (dict(iterations=8, normal_power=1, demodulate=False), dict(iterations=2, sigma_color=0.05, sigma_albedo=1.0)):
+        r.denoise(**p)
+        assert r.read_denoised().tobytes() == twin_of(r, **p).tobytes(), p
+    ptr, nbytes = r.denoised_buffer()
+    assert ptr and nbytes == 96 * 64 * 16
+    r.close()
+
+
+@gpu
+def test_denoise_has_no_side_effects(halart, oracle):
+    s = scenes.cornell_box(aspect=96 / 64)
+    images = []
+    for denoise in (True, False):
+        r = cornell(halart, 96, 64)
+        r.update(); r.update(); r.render()
+        if denoise:
+            r.denoise()
+        r.update(); r.update(); r.render()
+        images.append([r.read_image(k).tobytes() for k in range(4)])
+        r.close()
+    assert images[0] == images[1]
+    want, _ = oracle.OracleScene(s).render(96, 64, frames=4)
+    assert images[0] == [x.tobytes() for x in want]
+
+
+@gpu
+def test_denoise_refusals_and_new_accumulation(halart):
+    r = cornell(halart, 64, 48)
+    with pytest.raises(halart.HalaRendererError, match="no sample"):
+        r.denoise()
+    with pytest.raises(halart.HalaRendererError, match="denoised"):
+        r.read_denoised()
+    r.update()
+    r.denoise()
+    first = r.read_denoised()
+    r.reset_accumulation()
+    with pytest.raises(halart.HalaRendererError, match="no sample"):
+        r.denoise()
+    assert r.read_denoised().tobytes() == first.tobytes()  # the last result stays readable
+    r.set_tile_shard(0, 1, 32)  # reallocates the frame buffers and restarts the accumulation
+    with pytest.raises(halart.HalaRendererError, match="no sample"):
+        r.denoise()
+    r.update_batch(3)
+    r.denoise(iterations=4)
+    assert r.read_denoised().tobytes() == twin_of(r, iterations=4).tobytes()
+    r.close()
+
+
+@gpu
+def test_sharded_denoise_after_gather(halart):
+    """three emulated ranks (test_gpu_parity's style): refused until AOVs 0, 1 and 2 are gathered, then byte-equal to denoising the
+    unsharded frame"""
+    import torch
+
+    from hala_renderer_amd import dist
+    w, h, world, ts = 96, 64, 3, 16
+    ref = cornell(halart, w, h)
+    ref.update_batch(2)
+    ref.denoise()
+    want = ref.read_denoised()
+    ref.close()
+    parts, last = {k: [] for k in range(3)}, None
+    for rank in range(world):
+        r = halart.HalaRenderer("shard", w, h, 5, 3, False, False, False, 0)
+        r.set_tile_shard(rank, world, ts)
+        r.set_scene(scenes.cornell_box(aspect=w / h)); r.commit()
+        r.update_batch(2); r.render(); r.wait_idle()
+        for k in range(3):
+            ptr, nbytes = r.tile_buffer(k)
+            parts[k].append(torch.as_tensor(dist._DeviceView(ptr, nbytes // 4), device="cuda:0").clone())
+        if last is not None:
+            last.close()
+        last = r
+    with pytest.raises(halart.HalaRendererError, match="gather"):
+        last.denoise()
+    gathered = {k: torch.cat(parts[k]).contiguous() for k in range(3)}
+    for k in (0, 1):
+        last.scatter_gathered_tiles(k, gathered[k].data_ptr(), gathered[k].numel() * 4)
+    with pytest.raises(halart.HalaRendererError, match="gather"):
+        last.denoise()
+    last.scatter_gathered_tiles(2, gathered[2].data_ptr(), gathered[2].numel() * 4)
+    last.denoise()
+    assert last.read_denoised().tobytes() == want.tobytes()
+    last.close()
+
+
+@gpu
+def test_determinism_and_save_denoised(halart, tmp_path):
+    r = cornell(halart, 80, 60, tonemap=(True, True, False))
+    r.update_batch(2)
+    r.denoise()
+    a = r.read_denoised()
+    r.denoise()
+    b = r.read_denoised()
+    assert a.tobytes() == b.tobytes()
+    r.save_denoised(str(tmp_path / "shot.pfm"))
+    lib = halart.load_library()
+    w, hh, ch = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    out = np.empty(80 * 60 * 4, f32)
+    halart.check(lib.hala_load_float_image(str(tmp_path / "shot_denoised.pfm").encode(), C.byref(w), C.byref(hh), C.byref(ch), fp(out),
+                                           C.c_size_t(out.size)))
+    assert (w.value, hh.value) == (80, 60)
+    got = out[: 80 * 60 * ch.value].reshape(60, 80, ch.value)
+    tm = np.ascontiguousarray(a.copy())
+    lib.hala_tonemap_pixels(fp(tm), C.c_size_t(80 * 60), 1, 1, 0)
+    assert got[..., :3].tobytes() == np.ascontiguousarray(tm[..., :3]).tobytes()
+    r.close()
+
+
+# ---- GPU tier: what the filter does ------------------------------------------------------------------------------------------------
+def g_space(x):
+    x = np.asarray(x, np.float64)[..., :3]
+    lum = 0.212671 * x[..., 0] + 0.715160 * x[..., 1] + 0.072169 * x[..., 2]
+    return x / (1.0 + lum)[..., None]
+
+
+# measured on an MI355X with the default parameters: MSE 4.296e-3 (4 spp) -> 2.909e-4 (denoised), 14.8x; the bound keeps 2x margin
+QUALITY_MSE_MAX = 5.8e-4
+
+
+@gpu
+def test_quality_against_a_converged_render(halart):
+    """Cornell box 256 x 256: the 4-spp frame filtered with the defaults against a 1024-spp render of the same scene, in g-space
+    (x / (1 + lum x)).  Measured on an MI355X: the MSE drops from 4.296e-3 to 2.909e-4, a ratio of 14.8 (DESIGN.md "Denoising");
+    the bound is twice the measured denoised MSE."""
+    r = cornell(halart, 256, 256)
+    r.update_batch(1024)
+    converged = r.read_image(0)
+    r.reset_accumulation()
+    r.update_batch(4)
+    noisy = r.read_image(0)
+    r.denoise()
+    den = r.read_denoised()
+    r.close()
+    mse_noisy = float(((g_space(noisy) - g_space(converged)) ** 2).mean())
+    mse_den = float(((g_space(den) - g_space(converged)) ** 2).mean())
+    print(f"quality: mse noisy {mse_noisy:.6g} denoised {mse_den:.6g} ratio {mse_noisy / mse_den:.3f}")
+    assert mse_den < QUALITY_MSE_MAX and mse_den * 7.0 < mse_noisy
+
+
+@gpu
+def test_normal_edge_is_preserved(halart):
+    """a step in the normal at column 32 with independent noise on each side: the columns next to it keep their own side's mean"""
+    rng = np.random.default_rng(11)
+    h, w, edge = 64, 64, 32
+    one = np.ones((h, w, 1), f32)
+    normal = np.zeros((h, w, 3), f32)
+    normal[:, :edge, 0] = 1
+    normal[:, edge:, 2] = 1
+    base = np.where(np.arange(w) < edge, 0.2, 0.8).astype(f32)[None, :, None]
+    color = (base * rng.uniform(0.5, 1.5, (h, w, 3))).astype(f32)
+    albedo = np.full((h, w, 3), 0.5, f32)
+    out = halart.denoise_images(color, albedo, normal)
+    left, right = out[:, edge - 1, :3].mean(), out[:, edge, :3].mean()
+    assert abs(left - 0.2) < 0.02 and abs(right - 0.8) < 0.02, (left, right)
+    # the noise inside each side is smoothed
+    assert out[:, 4:edge - 4, :3].std() < 0.5 * color[:, 4:edge - 4].std()
+
+
+@gpu
+def test_albedo_checker_survives_demodulation(halart):
+    """a checkerboard albedo (0.2 / 0.8, 8 x 8 cells) over a constant, noisy irradiance: with demodulate = 1 the contrast survives"""
+    rng = np.random.default_rng(12)
+    h, w = 64, 64
+    yy, xx = np.mgrid[0:h, 0:w]
+    bright = ((yy // 8 + xx // 8) % 2 == 0)
+    albedo = np.where(bright, 0.8, 0.2).astype(f32)[..., None].repeat(3, axis=2)
+    color = (albedo * rng.uniform(0.4, 1.6, (h, w, 3))).astype(f32)
+    normal = np.zeros((h, w, 3), f32)
+    normal[..., 2] = 1
+    out = halart.denoise_images(color, albedo, normal, demodulate=True)
+    ratio = out[bright][:, :3].mean() / out[~bright][:, :3].mean()
+    assert abs(ratio - 4.0) < 0.2, ratio
