@@ -550,11 +550,6 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
     slot = i;
     real = primary_ray(fc, sv, slot, &o, &d, &rng);
     if (fc.u.env_type == 1u) ps.radiance_env[slot] = P3{0.0f, 0.0f, 0.0f};
-    if (!real) {  // resolve reads every slot of the rank's tile buffer
-      ps.radiance[slot] = P3{0.0f, 0.0f, 0.0f};
-      ps.albedo[slot] = P3{0.0f, 0.0f, 0.0f};
-      ps.normal[slot] = P3{0.0f, 0.0f, 0.0f};
-    }
   }
   if (real) {
     // L: what this bounce adds to the path's radiance (at most one term: light hit | environment | emission)
@@ -766,14 +761,13 @@ __global__ void __launch_bounds__(256) k_resolve(FrameConst fc, PathState ps, fl
                                                   float4* __restrict__ normal, float4* __restrict__ final_img) {
   const uint32_t pslot = blockIdx.x * blockDim.x + threadIdx.x;
   if (pslot >= fc.pixel_slots) return;
+  // padding slots (of a border block, of a padding tile, or outside the frame in a border tile) are never written: they keep the zeros
+  // the images were allocated with (RENDER_SPEC §9)
+  uint32_t px, py;
+  if (!slot_to_pixel(fc, pslot, &px, &py)) return;
   // where the pixel of this slot lives in the images: sharded ranks keep their tile buffers in slot order (RENDER_SPEC §9), an unsharded
   // frame is row-major whatever the slot order
-  uint32_t at = pslot;
-  if (fc.world <= 1u) {
-    uint32_t px, py;
-    if (!slot_to_pixel(fc, pslot, &px, &py)) return;  // padding slot of a border block
-    at = py * fc.width + px;
-  }
+  const uint32_t at = fc.world <= 1u ? py * fc.width + px : pslot;
   // the running means; a batch that starts an accumulation (frame_index 0) never looks at them (fold_mean)
   float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, n = a;
   if (fc.u.frame_index != 0u) { a = accum[at]; b = albedo[at]; n = normal[at]; }

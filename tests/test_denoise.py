@@ -133,7 +133,10 @@ def test_twin_with_identical_guides_is_the_b3_blur():
 
 # ---- GPU tier: bit-exact against the twin -----------------------------------------------------------------------------------------
 POWERS = [1, 2, 4, 8, 16, 32, 64, 128]
-SIZES = [(1, 1), (7, 300), (96, 64), (333, 187), (517, 530)]  # 517 x 530: above 512 both ways, not a multiple of the 16 x 16 tile
+SIZES = [(1, 1), (7, 300), (96, 64), (333, 187), (517, 530),  # 517 x 530: above 512 both ways, not a multiple of the 16 x 16 tile
+         # wide frames shorter than one tile (grid.y == 1: every vertical tap of the long steps is out of the frame) and their transposes;
+         # exactly one tile and one pixel past it
+         (300, 7), (4099, 3), (32, 1), (1, 33), (16, 16), (17, 17)]
 
 
 def params(k, iterations, demod):
@@ -243,14 +246,10 @@ def test_denoise_refusals_and_new_accumulation(halart):
     r.close()
 
 
-@gpu
-def test_sharded_denoise_after_gather(halart):
-    """three emulated ranks (test_gpu_parity's style): refused until AOVs 0, 1 and 2 are gathered, then byte-equal to denoising the
-    unsharded frame"""
+def sharded_denoise_after_gather(halart, w, h, world, ts):
     import torch
 
     from hala_renderer_amd import dist
-    w, h, world, ts = 96, 64, 3, 16
     ref = cornell(halart, w, h)
     ref.update_batch(2)
     ref.denoise()
@@ -265,12 +264,14 @@ def test_sharded_denoise_after_gather(halart):
         for k in range(3):
             ptr, nbytes = r.tile_buffer(k)
             parts[k].append(torch.as_tensor(dist._DeviceView(ptr, nbytes // 4), device="cuda:0").clone())
+        torch.cuda.synchronize()  # the copies run on torch's stream
         if last is not None:
             last.close()
         last = r
     with pytest.raises(halart.HalaRendererError, match="gather"):
         last.denoise()
     gathered = {k: torch.cat(parts[k]).contiguous() for k in range(3)}
+    torch.cuda.synchronize()  # complete before the renderer's stream reads them
     for k in (0, 1):
         last.scatter_gathered_tiles(k, gathered[k].data_ptr(), gathered[k].numel() * 4)
     with pytest.raises(halart.HalaRendererError, match="gather"):
@@ -279,6 +280,21 @@ def test_sharded_denoise_after_gather(halart):
     last.denoise()
     assert last.read_denoised().tobytes() == want.tobytes()
     last.close()
+
+
+@gpu
+def test_sharded_denoise_after_gather(halart):
+    """three emulated ranks (test_gpu_parity's style): refused until AOVs 0, 1 and 2 are gathered, then byte-equal to denoising the
+    unsharded frame"""
+    sharded_denoise_after_gather(halart, 96, 64, 3, 16)
+
+
+@gpu
+@pytest.mark.parametrize("w,h,world,ts", [(61, 37, 5, 12), (40, 24, 8, 16)], ids=["ts12-row-major-in-tile", "world8-more-ranks-than-tiles"])
+def test_sharded_denoise_after_gather_odd_layouts(halart, w, h, world, ts):
+    """the same at a shard with row-major order inside the tiles, and at one where ranks 6 and 7 own no tile (rank 7, whose buffers
+    are one padding tile, is the one that gathers and denoises)"""
+    sharded_denoise_after_gather(halart, w, h, world, ts)
 
 
 @gpu

@@ -11,21 +11,68 @@ from hala_renderer_amd import scenes
 from hala_renderer_amd.dist import TileLayout
 
 
-@pytest.mark.parametrize("w,h,world,ts", [(1920, 1080, 8, 32), (1920, 1080, 2, 32), (100, 70, 4, 16), (64, 64, 8, 32), (3840, 2160, 8, 32)])
+# (w, h, world, ts) at the edges of the layout (tests/test_frame_edges.py renders them on the GPU): in-tile row-major order (ts % 8 != 0)
+# with partial border tiles, a multiple of 8 that is not a power of two, ts = 1, one tile larger than the frame, more ranks than tiles
+EDGE_LAYOUTS = [(61, 37, 3, 7), (61, 37, 5, 12), (200, 120, 3, 40), (23, 17, 4, 1), (100, 70, 3, 256), (40, 24, 8, 16), (1, 1, 2, 32),
+                (33, 17, 8, 8)]
+
+
+@pytest.mark.parametrize("w,h,world,ts", [(1920, 1080, 8, 32), (1920, 1080, 2, 32), (100, 70, 4, 16), (64, 64, 8, 32), (3840, 2160, 8, 32)]
+                         + EDGE_LAYOUTS)
 def test_tile_layout_matches_oracle(oracle, w, h, world, ts):
     L = TileLayout(w, h, world, ts)
     owner, slot = oracle.tile_assignment(L.tiles_x, L.tiles_y, world)
     assert np.array_equal(owner, L.owner) and np.array_equal(slot, L.slot)
     counts = np.bincount(L.owner, minlength=world)
     assert counts.max() - counts.min() <= 1
+    # rank k % world holds dealing position k as its (k // world)-th tile: every position is dealt once, within tiles_per_rank
+    assert np.array_equal(np.sort(L.slot * world + L.owner), np.arange(L.n_tiles))
+    assert L.tiles_per_rank == -(-L.n_tiles // world) and counts.max() == L.tiles_per_rank
+
+
+def spec_rank_pixel_map(w, h, world, ts, rank):
+    """RENDER_SPEC §9 read literally, one slot at a time: slot -> (tile slot, position in the tile) -> dealing position -> tile -> pixel;
+    (-1, -1) for padding tiles and out-of-frame pixels"""
+    tx_n, ty_n = -(-w // ts), -(-h // ts)
+    n = tx_n * ty_n
+    a = max(0x9E3779B1 % n, 1)
+    while np.gcd(a, n) != 1:
+        a += 1
+    tile_at = {(t * a + 7) % n: t for t in range(n)}
+    out = []
+    for s in range(-(-n // world) * ts * ts):
+        lt, j = divmod(s, ts * ts)
+        if ts % 8 == 0:
+            blk, i = divmod(j, 64)
+            ly, lx = (blk // (ts // 8)) * 8 + i // 8, (blk % (ts // 8)) * 8 + i % 8
+        else:
+            ly, lx = divmod(j, ts)
+        k = lt * world + rank
+        if k >= n:
+            out.append((-1, -1))
+            continue
+        ty, tx = divmod(tile_at[k], tx_n)
+        py, px = ty * ts + ly, tx * ts + lx
+        out.append((py, px) if py < h and px < w else (-1, -1))
+    return np.array(out, dtype=np.int64).reshape(-1, 2)
+
+
+@pytest.mark.parametrize("w,h,world,ts", [(100, 70, 4, 16), (64, 48, 3, 32)] + EDGE_LAYOUTS)
+def test_rank_pixel_map_is_the_spec(w, h, world, ts):
+    """TileLayout.rank_pixel_map (the host statement of slot_to_pixel) against §9 evaluated slot by slot, which pins the in-tile order:
+    8 x 8 blocks when ts is a multiple of 8, plain row-major otherwise"""
+    L = TileLayout(w, h, world, ts)
+    for r in range(world):
+        assert np.array_equal(L.rank_pixel_map(r), spec_rank_pixel_map(w, h, world, ts, r)), r
 
 
 def test_shard_unshard_roundtrip():
     rng = np.random.RandomState(0)
-    for w, h, world, ts in [(100, 70, 4, 16), (64, 48, 3, 32), (33, 17, 8, 8)]:
+    for w, h, world, ts in [(100, 70, 4, 16), (64, 48, 3, 32), (33, 17, 8, 8)] + EDGE_LAYOUTS:
         L = TileLayout(w, h, world, ts)
         img = rng.rand(h, w, 4).astype(np.float32)
         gathered = np.concatenate([L.shard(img, r) for r in range(world)])
+        assert gathered.shape == (world * L.pixels_per_rank, 4) and L.pixels_per_rank == L.tiles_per_rank * ts * ts
         assert np.array_equal(L.unshard(gathered), img)
         # every real pixel is owned exactly once
         seen = np.zeros((h, w), dtype=np.int32)
@@ -33,6 +80,11 @@ def test_shard_unshard_roundtrip():
             m = L.rank_pixel_map(r)
             ok = m[:, 0] >= 0
             np.add.at(seen, (m[ok, 0], m[ok, 1]), 1)
+            # what a rank owns is its tiles clipped to the frame (compute_tiling's real_pixels); padding slots carry zeros
+            tiles = np.nonzero(L.owner == r)[0]
+            real = sum(min(ts, w - (t % L.tiles_x) * ts) * min(ts, h - (t // L.tiles_x) * ts) for t in tiles)
+            assert int(ok.sum()) == real, (w, h, world, ts, r)
+            assert not L.shard(img, r)[~ok].any()
         assert np.all(seen == 1)
 
 
@@ -276,15 +328,16 @@ def test_sharded_render_equals_unsharded(halart, world):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world", [2, 8])
-def test_emulated_ranks_through_the_librarys_own_exchange_pipeline(halart, world):
+@pytest.mark.parametrize("w,h,ts,world", [pytest.param(200, 120, 32, 2, id="2"), pytest.param(200, 120, 32, 8, id="8"),
+                                          pytest.param(61, 37, 12, 5, id="61x37-ts12-world5"),    # in-tile row-major order
+                                          pytest.param(40, 24, 16, 8, id="40x24-ts16-world8")])   # 6 tiles: ranks 6 and 7 own none
+def test_emulated_ranks_through_the_librarys_own_exchange_pipeline(halart, w, h, ts, world):
     """the world > 1 leg of hala_rt_tile_allgather_begin / _finish on a one-GPU box: every emulated rank renders its share; on ONE of
     them the library's own pipeline runs — begin_external (stream-ordered snapshot into the staging buffer, receive buffer sized
     world x n), the exchange done by the test (device-to-device copies of every rank's staging buffer into the receive buffer, on the
     library's exchange stream), finish() (de-interleave of the receive buffer by k_scatter_tiles on that stream, full_valid, the
     renderer's stream waits) — pipelined: the next frame is enqueued before finish().  read_image must equal the unsharded frame."""
     import torch
-    w, h, ts = 200, 120, 32
     scene = scenes.cornell_box(aspect=w / h)
     ref = halart.HalaRenderer("ref", w, h, 5, 3, False, False, False, 0)
     ref.set_scene(scene); ref.commit()
