@@ -6,7 +6,7 @@
 //             single-level traversal needs no per-instance ray transform)
 //   build     binary hierarchy: >= 4096 triangles: top-down full-sweep SAH, one tree level per round (three centroid orders kept through
 //             every partition, segmented box scans with rocPRIM; sah_hierarchy) | below: 60-bit Morton codes -> rocPRIM radix sort ->
-//             Karras 2012 LBVH | HALART_BUILDER=ploc: PLOC over the Morton order, the fast large-scene build ->
+//             Karras 2012 LBVH | hala_rt_build_options::builder = 2: PLOC over the Morton order, the fast large-scene build ->
 //             fitted AABBs -> subtrees of <= leaf_max triangles become leaves ->
 //             top-down collapse into 4-wide nodes, breadth-first, by surface area -> 64-B compressed nodes
 //             (8-bit child boxes quantised conservatively against the node's own box, RENDER_SPEC §4.1b)
@@ -190,7 +190,7 @@ RT_DI unsigned long long spread21(uint32_t v) {  // 21 bits -> every third bit
   return x;
 }
 __global__ void __launch_bounds__(256) k_morton(const Box6* __restrict__ tri_box, uint32_t n, const uint32_t* __restrict__ scene_ord,
-                                                 unsigned long long* __restrict__ keys, uint32_t* __restrict__ ids, uint32_t size_classes) {
+                                                 unsigned long long* __restrict__ keys, uint32_t* __restrict__ ids) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= n) return;
   const Box6 b = tri_box[g];
@@ -212,8 +212,7 @@ __global__ void __launch_bounds__(256) k_morton(const Box6* __restrict__ tri_box
   // hierarchy splits by class first: big triangles form their own shallow subtrees next to the well-formed rest.
   // class 0: box diagonal > 1/8 of the scene's, 1: > 1/32, 2: > 1/128, 3: the rest.
   const float ratio2 = scene_d2 > 0.0f ? tri_d2 / scene_d2 : 0.0f;
-  uint32_t cls = ratio2 > (1.0f / 64.0f) ? 0u : (ratio2 > (1.0f / 1024.0f) ? 1u : (ratio2 > (1.0f / 16384.0f) ? 2u : 3u));
-  if (!size_classes) cls = 0u;
+  const uint32_t cls = ratio2 > (1.0f / 64.0f) ? 0u : (ratio2 > (1.0f / 1024.0f) ? 1u : (ratio2 > (1.0f / 16384.0f) ? 2u : 3u));
   keys[g] = ((unsigned long long)cls << 60) | (spread21(q[0]) << 2) | (spread21(q[1]) << 1) | spread21(q[2]);
   ids[g] = g;
 }
@@ -386,8 +385,7 @@ RT_DI float half_area(const Box6& b) {
 __global__ void __launch_bounds__(256) k_collapse_level(const uint32_t* __restrict__ root_of, const uint32_t* __restrict__ level, uint32_t bound,
                                                          const uint32_t* __restrict__ left, const uint32_t* __restrict__ right,
                                                          const uint32_t* __restrict__ keep, const Box6* __restrict__ node_box,
-                                                         uint4* __restrict__ refs4, uint32_t* __restrict__ cnt,
-                                                         const uint32_t* __restrict__ first, const uint32_t* __restrict__ last, int order_mode) {
+                                                         uint4* __restrict__ refs4, uint32_t* __restrict__ cnt) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= bound) return;
   const uint32_t base = level[0], size = level[1];
@@ -413,22 +411,20 @@ __global__ void __launch_bounds__(256) k_collapse_level(const uint32_t* __restri
       ++n;
     }
   }
-  // Slot order = the order in which an any-hit ray of a large tree takes the inner children (RENDER_SPEC 4.4c); every other ray sorts
-  // the children by distance (the slot only breaks ties)
-  if (order_mode != 0) {
-    float w[4];
-    for (int k = 0; k < n; ++k) {
-      const uint32_t r = c[k];
-      if ((r & kLeafBit) || !keep[r]) { w[k] = -1.0f; continue; }
-      const float a = half_area(node_box[r]), cntf = (float)(last[r] - first[r] + 1u);
-      w[k] = order_mode == 1 ? a : (order_mode == 2 ? 1.0f / (a + 1e-30f) : (order_mode == 3 ? cntf : (order_mode == 4 ? cntf / (a + 1e-30f) : (a + 1e-30f) / cntf)));
-    }
-    for (int a = 1; a < n; ++a)  // insertion sort, descending weight, stable
-      for (int b = a; b > 0 && w[b] > w[b - 1]; --b) {
-        const float tw = w[b]; w[b] = w[b - 1]; w[b - 1] = tw;
-        const uint32_t tc = c[b]; c[b] = c[b - 1]; c[b - 1] = tc;
-      }
+  // Slot order = the order in which an any-hit ray of a large tree takes the inner children (RENDER_SPEC 4.4c): the kept inner children
+  // by descending surface area, then the leaves in the order the opening left them.  configs[3]: 9.09 instead of 9.40 node visits per
+  // connection ray (in-order slots), 3.40 instead of 3.45 ms per frame in the shadow passes; ascending area / triangle count / density:
+  // 9.60 / 9.48 / 9.36.  Every other ray sorts the children by distance (the slot only breaks ties).
+  float w[4];
+  for (int k = 0; k < n; ++k) {
+    const uint32_t r = c[k];
+    w[k] = (r & kLeafBit) || !keep[r] ? -1.0f : half_area(node_box[r]);
   }
+  for (int a = 1; a < n; ++a)  // insertion sort, descending weight, stable
+    for (int b = a; b > 0 && w[b] > w[b - 1]; --b) {
+      const float tw = w[b]; w[b] = w[b - 1]; w[b - 1] = tw;
+      const uint32_t tc = c[b]; c[b] = c[b - 1]; c[b - 1] = tc;
+    }
   refs4[base + j] = make_uint4(c[0], c[1], c[2], c[3]);
   uint32_t inner = 0;
   for (int k = 0; k < n; ++k) inner += (!(c[k] & kLeafBit) && keep[c[k]]) ? 1u : 0u;
@@ -1011,10 +1007,6 @@ static std::string fit_and_emit(BvhBuffers& b, BvhTopology& t, hipStream_t s) {
     constexpr uint32_t kMaxLevels = 96;
     uint32_t look_every = 8;
     if (b.opt.collapse_look_every) look_every = b.opt.collapse_look_every;
-    // slots by descending surface area of the inner children: configs[3] 9.09 instead of 9.40 node visits per connection ray (in-order
-    // slots), 3.40 instead of 3.45 ms per frame in the shadow passes; ascending area / triangle count / density: 9.60 / 9.48 / 9.36
-    int order_mode = 1;
-    if (const char* ev = tune_env("HALART_CHILD_ORDER")) order_mode = atoi(ev);
     DevBuf level, bases;
     if (!(e = level.alloc(16)).empty()) return e;
     if (!(e = bases.alloc(kMaxLevels * 4)).empty()) return e;
@@ -1026,8 +1018,7 @@ static std::string fit_and_emit(BvhBuffers& b, BvhTopology& t, hipStream_t s) {
       for (uint32_t k = 0; k < look_every; ++k) {
         const uint32_t bd = (uint32_t)std::min<unsigned long long>(bound, ni);
         hipLaunchKernelGGL(k_collapse_level, dim3(nblk(bd)), dim3(256), 0, s, t.root_of.as<uint32_t>(), level.as<uint32_t>(), bd, t.left.as<uint32_t>(),
-                           t.right.as<uint32_t>(), t.keep.as<uint32_t>(), t.node_box.as<Box6>(), t.refs4.as<uint4>(), t.cnt.as<uint32_t>(),
-                           t.first.as<uint32_t>(), t.last.as<uint32_t>(), order_mode);
+                           t.right.as<uint32_t>(), t.keep.as<uint32_t>(), t.node_box.as<Box6>(), t.refs4.as<uint4>(), t.cnt.as<uint32_t>());
         size_t tb = tmp_bytes;
         HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, t.cnt.as<uint32_t>(), t.off.as<uint32_t>(), 0u, bd, rocprim::plus<uint32_t>(), s));
         hipLaunchKernelGGL(k_scatter_level, dim3(nblk(bd)), dim3(256), 0, s, t.root_of.as<uint32_t>(), level.as<uint32_t>(), t.refs4.as<uint4>(),
@@ -1076,8 +1067,7 @@ static std::string ploc_hierarchy(BvhBuffers& b, BvhTopology& t, hipStream_t s) 
                      box[0].as<Box6>());
   uint32_t m = n, created = 0;
   int cur = 0;
-  uint32_t radius = kPlocRadius;
-  if (const char* ev = tune_env("HALART_PLOC_RADIUS")) radius = (uint32_t)std::max(1, atoi(ev));
+  const uint32_t radius = kPlocRadius;
   bool tail = true;
   if (b.opt.ploc_tail == 2u) tail = false;  // every round as separate launches
   // rounds between two looks at the device's counters: a look is a host round trip (~50 us, as long as a late round itself); the
@@ -1170,8 +1160,7 @@ static std::string sah_hierarchy(BvhBuffers& b, BvhTopology& t, hipStream_t s) {
   hipLaunchKernelGGL(k_sah_init, dim3(nblk(n)), dim3(256), 0, s, n, node_of.as<uint32_t>(), t.first.as<uint32_t>(), t.last.as<uint32_t>(),
                      t.node_parent.as<uint32_t>(), act[0].as<uint32_t>(), best.as<unsigned long long>());
   const float pad = box_pad(b);
-  uint32_t quant = (uint32_t)kSahQuant;  // = the leaf slots of the cooperative pass (traverse.h: RT_LEAF_SLOTS)
-  if (const char* ev = tune_env("HALART_SAH_QUANT")) quant = (uint32_t)std::max(1, atoi(ev));
+  const uint32_t quant = (uint32_t)kSahQuant;  // = the leaf slots of the cooperative pass (traverse.h: RT_LEAF_SLOTS)
   uint32_t open = 1, next_id = 1, round = 0;
   int cur = 0, ac = 0;
   constexpr uint32_t kSweepRounds = 64;  // below that depth every node is halved instead: at most 28 more rounds
@@ -1267,10 +1256,8 @@ std::string bvh_build(BvhBuffers& b, uint32_t leaf_max, hipStream_t s) {
       if (!(e = keys_in.alloc((size_t)n * 8)).empty()) return e;
       if (!(e = keys_out.alloc((size_t)n * 8)).empty()) return e;
       if (!(e = ids_in.alloc((size_t)n * 4)).empty()) return e;
-      uint32_t size_classes = 1;
-      if (const char* ev = tune_env("HALART_SIZE_CLASSES")) size_classes = (uint32_t)atoi(ev);
       hipLaunchKernelGGL(k_morton, dim3(nblk(n)), dim3(256), 0, s, t.tri_box.as<Box6>(), n, t.scene_ord.as<uint32_t>(),
-                         keys_in.as<unsigned long long>(), ids_in.as<uint32_t>(), size_classes);
+                         keys_in.as<unsigned long long>(), ids_in.as<uint32_t>());
       size_t tmp_bytes = 0;
       HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_in.as<unsigned long long>(), keys_out.as<unsigned long long>(),
                                         ids_in.as<uint32_t>(), t.sorted_ids.as<uint32_t>(), n, 0, 64, s));

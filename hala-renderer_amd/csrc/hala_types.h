@@ -235,13 +235,13 @@ struct WorkCounters {
   uint32_t c[kWorkShards * kWorkStride];
   unsigned long long dry[kWorkStride / 2];  // dry[0]: bit s set once shard s has handed out all of its batches (own 128-B line)
 };
-struct Control {
+// The two parts of the control block the host reads back after an update, each in one copy (renderer.hip: TraceEvents)
+struct QueueSizes {
   uint32_t n_active[kMaxDepth + 1];  // ray-queue size entering bounce d
   uint32_t n_shadow[2][kMaxDepth];   // connections produced by bounce d: [0] light, [1] environment
-  uint32_t pad[3];
-  WorkCounters work_closest;    // re-zeroed by the shade kernel of every bounce (it runs between two uses)
-  WorkCounters work_shadow[2];
-  unsigned long long rays_closest, rays_shadow;  // totals of this update
+};
+struct Totals {  // of this update
+  unsigned long long rays_closest, rays_shadow;
   // only filled by counting launches: steps[kind] = {nodes visited, triangles tested}; kind 0 closest-hit
   // kernel, kind 1 shadow / any-hit kernel
   unsigned long long steps[2][2];
@@ -250,6 +250,18 @@ struct Control {
   unsigned long long probe[2][3];
   unsigned long long primary_steps[2];  // counting launches: steps[0] as it stood after the depth-0 launch (camera rays only)
 };
+struct Control {
+  QueueSizes sizes;
+  uint32_t pad[3];
+  WorkCounters work_closest;    // re-zeroed by the shade kernel of every bounce (it runs between two uses)
+  WorkCounters work_shadow[2];
+  Totals totals;
+};
+// the layout the fields had before they were grouped (WorkCounters grows with RT_WORK_SHARDS: 2176 B at the default 16 shards)
+static_assert(offsetof(Control, sizes) == 0 && offsetof(Control, sizes.n_shadow) == 260 && offsetof(Control, work_closest) == 784 &&
+              offsetof(Control, work_shadow) == 784 + sizeof(WorkCounters) && offsetof(Control, totals) == 784 + 3 * sizeof(WorkCounters) &&
+              offsetof(Control, totals.primary_steps) == offsetof(Control, totals) + 96 && sizeof(Control) == offsetof(Control, totals) + sizeof(Totals) &&
+              sizeof(Totals) == 14 * sizeof(unsigned long long), "control block layout");
 
 // per-path records indexed by path slot (everything a live path needs from bounce to bounce travels in its queue entry)
 struct P3 { float x, y, z; };  // 12-B per-path record: one dwordx3 load / store, no padding word to move

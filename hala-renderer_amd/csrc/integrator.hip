@@ -8,21 +8,18 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "kernels.h"
 #include "shading.h"
 #include "traverse.h"
 
 namespace rt {
-// Streaming stores (queue entries, hit records; RT_PLAIN_STORES restores ordinary ones): written once, read by the next launch at the
-// earliest — nontemporal stores keep them from displacing what the traversal and shading gathers want in L2 (+1.4 ... 2.2 % on the
-// headline).  The 12-B per-path records stay ordinary stores: three scalar nontemporal stores each measured slower.
+// Streaming stores (queue entries, hit records): written once, read by the next launch at the earliest — nontemporal stores keep
+// them from displacing what the traversal and shading gathers want in L2 (+1.4 ... 2.2 % on the headline).  The 12-B per-path
+// records stay ordinary stores: three scalar nontemporal stores each measured slower.
 typedef float v4f_nt __attribute__((ext_vector_type(4)));
-#ifndef RT_PLAIN_STORES
 RT_DI void st4(float4* p, float4 v) { __builtin_nontemporal_store(v4f_nt{v.x, v.y, v.z, v.w}, reinterpret_cast<v4f_nt*>(p)); }
-#else
-RT_DI void st4(float4* p, float4 v) { *p = v; }
-#endif
 
 // wave64 helpers ------------------------------------------------------------------------------------------
 RT_DI uint32_t lane_id() { return threadIdx.x & 63u; }
@@ -150,14 +147,6 @@ RT_DI void persistent_trace(const SceneView& sv, const TraverseLds& lds, uint2* 
   // between leave in ONE store instruction — whole 1-KB runs for the whole-wave batches of the LDS-staged kernels (64 consecutive
   // queue entries: full lines for the nontemporal stores) — instead of one divergent store per lane and step.
   bool fin = false;
-  // Occluder cache (-DRT_OCCLUDER_CACHE; connection launches of large one-level trees): the triangle that blocked the lane's previous
-  // connection is tested first against its next one — consecutive rays of a lane are queue neighbours, i.e. connections of nearby surface
-  // points towards the same light or the same part of the sky; 23 % of the light and 58 % of the environment connections of configs[3] are
-  // blocked, often by the same large triangles (walls).  A hit inside (0, tmax) on a fully blocking triangle IS an any-hit result: the
-  // connection is dropped without a traversal; otherwise the ray is traced as before.  Images cannot depend on it (the suite passes with
-  // it).  It does not pay: the extra 48-B gather and triangle test of EVERY connection cost more than the traversals the hits save.
-  constexpr bool kCache = ANY && !STAGED && !INST && Source::kOccluderCache;
-  uint32_t last_occ = kAbsent;
   for (;;) {
     const unsigned long long idle = __ballot(!has);
     if (more && idle) {
@@ -183,19 +172,8 @@ RT_DI void persistent_trace(const SceneView& sv, const TraverseLds& lds, uint2* 
             idx = base + rank;
             f3 o, d; float tmin, tmax; uint32_t key = 0u;
             if (src.load(idx, &o, &d, &tmin, &tmax, &key, &pay)) {  // false: the source had no ray for this entry and has dealt with it
-              bool blocked = false;
-              if (kCache && last_occ != kAbsent) {
-                const float4* tp = reinterpret_cast<const float4*>(sv.tris) + (size_t)last_occ * 3;
-                const float4 a = tp[0], b = tp[1], c = tp[2];
-                float tt, tu, tv, det;
-                if (COUNT) sc.tris++;
-                // flag 0: blocks every ray (a translucent triangle or a medium boundary decides per ray: RENDER_SPEC 7.1d / 7.1g — not cached)
-                blocked = tri_test_od(o, d, a, b, c, &tt, &tu, &tv, &det) && tt > maxf(tmin, 0.0f) && tt < tmax && __float_as_uint(b.w) == 0u;
-              }
-              if (!blocked) {
-                trav_begin(t, make_ray(o, d, tmin), tmax, key);
-                has = true;
-              }  // else: occluded — a connection that is blocked leaves nothing behind (ShadowSource::done does nothing for it)
+              trav_begin(t, make_ray(o, d, tmin), tmax, key);
+              has = true;
             }
           }
         }
@@ -205,14 +183,7 @@ RT_DI void persistent_trace(const SceneView& sv, const TraverseLds& lds, uint2* 
     for (;;) {
       if (COUNT && lane_id() == 0u) sc.wave_steps++;  // lane 0 runs every iteration of this wave-uniform loop
       // every lane calls it: the large-scene variant deals the wave's leaf work out over all 64 lanes (traverse.h)
-#ifdef RT_NO_DEFER
-      if (trav_step<ANY, COUNT, STAGED, ALPHA, INST>(sv, lds, spill, t, has, sc)) { src.done(idx, t, pay); has = false; }
-#else
-      if (trav_step<ANY, COUNT, STAGED, ALPHA, INST>(sv, lds, spill, t, has, sc)) {
-        fin = true; has = false;
-        if (kCache && t.best.prim != kAbsent) last_occ = t.best.prim;
-      }
-#endif
+      if (trav_step<ANY, COUNT, STAGED, ALPHA, INST>(sv, lds, spill, t, has, sc)) { fin = true; has = false; }
       const uint32_t nidle = (uint32_t)__popcll(__ballot(!has));
       if (nidle == 64u || (more && nidle >= refill)) break;
     }
@@ -221,7 +192,6 @@ RT_DI void persistent_trace(const SceneView& sv, const TraverseLds& lds, uint2* 
 }
 
 struct BatchSource {
-  static constexpr bool kOccluderCache = false;  // a caller's batch: traced ray by ray as the spec says (step counts are pinned to the oracle's)
   struct Payload {};
   const hala_ray* rays;
   hala_hit* hits;
@@ -261,7 +231,6 @@ RT_DI bool primary_ray(const FrameConst& fc, const SceneView& sv, uint32_t slot,
   return true;
 }
 struct CameraSource {
-  static constexpr bool kOccluderCache = false;
   struct Payload {};
   const FrameConst& fc;
   const SceneView& sv;
@@ -281,16 +250,8 @@ struct CameraSource {
     else reinterpret_cast<float4*>(hits)[i] = out;
   }
 };
-#ifndef RT_SHADOW_PREFETCH
-#define RT_SHADOW_PREFETCH 1  // large scenes too: 84 of the 102 VGPRs of 5 waves per SIMD are in use, the three words fit (shadow 4.06 -> 3.99 ms, configs[3])
-#endif
-template <bool PREFETCH, bool ALPHA>
+template <bool ALPHA>
 struct ShadowSource {
-#ifdef RT_OCCLUDER_CACHE  // measured: configs[3] shadow 3.95 -> 4.05 ms per frame with it (profiles/r03_experiments.txt): off
-  static constexpr bool kOccluderCache = true;
-#else
-  static constexpr bool kOccluderCache = false;
-#endif
   // contribution.xyz | pixel slot, fetched with the ray (one coalesced 48-B record), and the path's radiance as it stands
   struct Payload { float4 cs; float lx, ly, lz; };
   const ShadowEntry* entries;
@@ -299,17 +260,13 @@ struct ShadowSource {
   // path's radiance during the launch: it is fetched here, behind the entry (the load is in flight while the ray is traced), and
   // an unoccluded ray stores radiance + contribution — one IEEE add per component, no ordering freedom.  (Three memory-side float
   // atomics per unoccluded ray did the same and cost 57 of the launch's 160 us on the headline config: profiles/r01_h_experiments.txt.)
-  // PREFETCH = false (kept for register-starved variants): the add is done by fire-and-forget float atomics instead — at most one per
-  // radiance word per launch, so exactly the same single IEEE add.  (The two connection kinds of a bounce share a launch but not an
-  // array: light connections add to L, environment connections to Le.)
+  // The two connection kinds of a bounce share a launch but not an array: light connections add to L, environment connections to Le.
   RT_DI bool load(uint32_t i, f3* o, f3* d, float* tmin, float* tmax, uint32_t* key, Payload* p) const {
     const float4* e = reinterpret_cast<const float4*>(entries + i);
     const float4 ro = e[0], rd = e[1];
     p->cs = e[2];
-    if (PREFETCH) {
-      const float* l = reinterpret_cast<const float*>(radiance + __float_as_uint(p->cs.w));
-      p->lx = l[0]; p->ly = l[1]; p->lz = l[2];
-    }
+    const float* l = reinterpret_cast<const float*>(radiance + __float_as_uint(p->cs.w));
+    p->lx = l[0]; p->ly = l[1]; p->lz = l[2];
     // a connection starts at its origin (tmin = 0): the field carries its any-hit key (RENDER_SPEC 7.1d)
     *o = mk3(ro.x, ro.y, ro.z); *d = mk3(rd.x, rd.y, rd.z); *tmin = 0.0f; *tmax = rd.w; *key = __float_as_uint(ro.w);
     return true;
@@ -322,8 +279,7 @@ struct ShadowSource {
       if (tr.x != 1.0f || tr.y != 1.0f || tr.z != 1.0f) { cx = cx * tr.x; cy = cy * tr.y; cz = cz * tr.z; }
     }
     float* l = reinterpret_cast<float*>(radiance + __float_as_uint(p.cs.w));
-    if (PREFETCH) { l[0] = p.lx + cx; l[1] = p.ly + cy; l[2] = p.lz + cz; }
-    else { atomicAdd(l + 0, cx); atomicAdd(l + 1, cy); atomicAdd(l + 2, cz); }
+    l[0] = p.lx + cx; l[1] = p.ly + cy; l[2] = p.lz + cz;
   }
 };
 
@@ -333,9 +289,9 @@ extern __shared__ __attribute__((aligned(16))) unsigned char g_smem[];
 RT_DI void flush_counters(Control* ctl, int kind, const StepCounters& sc) {
   const uint32_t v[5] = {wave_sum(sc.nodes), wave_sum(sc.tris), wave_sum(sc.wave_steps), wave_sum(sc.leaf_passes), wave_sum(sc.leaf_lanes)};
   if (lane_id() != 0u) return;
-  atomicAdd(&ctl->steps[kind][0], (unsigned long long)v[0]); atomicAdd(&ctl->steps[kind][1], (unsigned long long)v[1]);
-  atomicAdd(&ctl->probe[kind][0], (unsigned long long)v[2]); atomicAdd(&ctl->probe[kind][1], (unsigned long long)v[3]);
-  atomicAdd(&ctl->probe[kind][2], (unsigned long long)v[4]);
+  atomicAdd(&ctl->totals.steps[kind][0], (unsigned long long)v[0]); atomicAdd(&ctl->totals.steps[kind][1], (unsigned long long)v[1]);
+  atomicAdd(&ctl->totals.probe[kind][0], (unsigned long long)v[2]); atomicAdd(&ctl->totals.probe[kind][1], (unsigned long long)v[3]);
+  atomicAdd(&ctl->totals.probe[kind][2], (unsigned long long)v[4]);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -351,7 +307,7 @@ k_trace_batch(SceneView sv, const hala_ray* __restrict__ rays, hala_hit* __restr
   uint2* spill = spill_base ? spill_base + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * kStackSpill : nullptr;
   StepCounters sc;
   if (account && blockIdx.x == 0 && threadIdx.x == 0) {
-    if (ANY) ctl->rays_shadow += n; else ctl->rays_closest += n;
+    if (ANY) ctl->totals.rays_shadow += n; else ctl->totals.rays_closest += n;
   }
   BatchSource src{rays, hits, ANY, account != 0, STAGED && refill == 64u};
   persistent_trace<ANY, COUNT, STAGED, ALPHA, INST>(sv, lds, spill, work, n, refill, src, sc);
@@ -367,7 +323,7 @@ k_trace_primary(SceneView sv, FrameConst fc, hala_hit* __restrict__ hits, WorkCo
   const TraverseLds lds = stage_bvh<STAGED, INST>(sv, g_smem);
   uint2* spill = spill_base ? spill_base + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * kStackSpill : nullptr;
   StepCounters sc;
-  if (blockIdx.x == 0 && threadIdx.x == 0) ctl->rays_closest += n_account;
+  if (blockIdx.x == 0 && threadIdx.x == 0) ctl->totals.rays_closest += n_account;
   CameraSource src{fc, sv, hits, STAGED && refill == 64u};
   persistent_trace<false, COUNT, STAGED, false, INST>(sv, lds, spill, work, fc.slot_count, refill, src, sc);
   if (COUNT) flush_counters(ctl, 0, sc);
@@ -382,10 +338,10 @@ __global__ void __launch_bounds__(kTraverseThreads, STAGED ? kTraverseWavesPerSi
 k_trace_shadow(SceneView sv, Queues q, PathState ps, Control* __restrict__ ctl, uint32_t depth, uint32_t kind, uint2* __restrict__ spill_base,
                uint32_t refill) {
   const TraverseLds lds = stage_bvh<STAGED, INST>(sv, g_smem);
-  const uint32_t n = ctl->n_shadow[kind][depth];
+  const uint32_t n = ctl->sizes.n_shadow[kind][depth];
   uint2* spill = spill_base ? spill_base + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * kStackSpill : nullptr;
   StepCounters sc;
-  ShadowSource<(STAGED || RT_SHADOW_PREFETCH), ALPHA> src{q.shadow[kind], kind ? ps.radiance_env : ps.radiance};
+  ShadowSource<ALPHA> src{q.shadow[kind], kind ? ps.radiance_env : ps.radiance};
   persistent_trace<true, COUNT, STAGED, ALPHA, INST>(sv, lds, spill, &ctl->work_shadow[kind], n, refill, src, sc);
   if (COUNT) flush_counters(ctl, 1, sc);
 }
@@ -411,13 +367,13 @@ k_trace_shadow_then_batch(SceneView sv, const Tri* __restrict__ tris_any, Queues
     sva.tris = tris_any;  // RENDER_SPEC 7.1d (STAGED: the launcher only fuses when both passes traverse the same triangles)
     for (uint32_t kind = 0; kind < 2u; ++kind) {  // bit 0: light connections, bit 1: environment connections
       if (!((kinds >> kind) & 1u)) continue;
-      ShadowSource<(STAGED || RT_SHADOW_PREFETCH), ALPHA> src{q.shadow[kind], kind ? ps.radiance_env : ps.radiance};
-      persistent_trace<true, false, STAGED, ALPHA, INST>(sva, lds, spill, &ctl->work_shadow[kind], ctl->n_shadow[kind][depth], refill, src, sc);
+      ShadowSource<ALPHA> src{q.shadow[kind], kind ? ps.radiance_env : ps.radiance};
+      persistent_trace<true, false, STAGED, ALPHA, INST>(sva, lds, spill, &ctl->work_shadow[kind], ctl->sizes.n_shadow[kind][depth], refill, src, sc);
     }
   }
   if (rays == nullptr) return;  // the last bounce: its two shadow passes share the launch, no closest-hit pass follows
-  const uint32_t n = ctl->n_active[depth + 1u];
-  if (blockIdx.x == 0 && threadIdx.x == 0) ctl->rays_closest += n;
+  const uint32_t n = ctl->sizes.n_active[depth + 1u];
+  if (blockIdx.x == 0 && threadIdx.x == 0) ctl->totals.rays_closest += n;
   BatchSource src{rays, hits, false, true, STAGED && refill == 64u};
   persistent_trace<false, false, STAGED, false, INST>(sv, lds, spill, &ctl->work_closest, n, refill, src, sc);
 }
@@ -450,7 +406,7 @@ k_trace_shadow_then_batch(SceneView sv, const Tri* __restrict__ tris_any, Queues
 constexpr uint32_t kSortThreads = RT_SORT_THREADS, kSortRounds = RT_SORT_ROUNDS, kSortWindow = kSortThreads * kSortRounds;
 static_assert(kSortWindow <= 65536, "window-relative positions are 16-bit in LDS");
 __global__ void __launch_bounds__(kSortThreads) k_shade_sort(Queues q, const Control* __restrict__ ctl, uint32_t depth) {
-  const uint32_t n = ctl->n_active[depth];
+  const uint32_t n = ctl->sizes.n_active[depth];
   const uint32_t base = blockIdx.x * kSortWindow;
   if (base >= n) return;
   const uint32_t live = min(kSortWindow, n - base);
@@ -502,7 +458,7 @@ __global__ void __launch_bounds__(kSortThreads) k_shade_sort(Queues q, const Con
 template <bool PRIMARY, bool SIMPLE, bool SCATTER>
 __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric, SIMPLE ? RT_SHADE_WAVES_SIMPLE : RT_SHADE_WAVES) k_shade(FrameConst fc, SceneView sv, Queues q, PathState ps, Control* __restrict__ ctl, uint32_t depth) {
   __shared__ BlockCompact s_compact;
-  const uint32_t n = PRIMARY ? fc.slot_count : ctl->n_active[depth];
+  const uint32_t n = PRIMARY ? fc.slot_count : ctl->sizes.n_active[depth];
   // the traversal of this bounce is over and the next users (shadow pass of this bounce, closest-hit pass of the next)
   // have not started: re-arm their work counters here
   if (blockIdx.x == 0u && threadIdx.x < kWorkShards) {
@@ -512,7 +468,6 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
     if (threadIdx.x == 0u) { ctl->work_closest.dry[0] = 0ull; ctl->work_shadow[0].dry[0] = 0ull; ctl->work_shadow[1].dry[0] = 0ull; }
   }
   uint32_t blk = blockIdx.x;
-#if !defined(RT_SHADE_NOSORT) && !defined(RT_SHADE_NO_XCD_MAP)
   if (!PRIMARY && !SIMPLE && sv.shade_sort) {
     // The workgroups that share a sort window read the same lines of the ray / state / hit queues (each takes a kind-slice of the
     // window's paths).  Workgroups are dealt round-robin over the 8 XCDs (b and b + 8 share one, each XCD has its own L2): give every
@@ -521,7 +476,6 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
     const uint32_t wi = blk % kGroup;
     blk = blk - wi + (wi & 7u) * kBPW + (wi >> 3);
   }
-#endif
   if (blk * blockDim.x >= n) return;  // whole workgroup beyond the queue (uniform exit: barriers below)
   uint32_t i = blk * blockDim.x + threadIdx.x;
   // the texel decode table in LDS (shading.h::tex8_fetch); the barriers of the block compaction come long after every read of it
@@ -531,9 +485,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
     for (uint32_t k = threadIdx.x; k < kTexLutEntries; k += blockDim.x) s_tex_lut[k] = sv.tex_lut[k];
     __syncthreads();
   }
-#ifndef RT_SHADE_NOSORT
   if (!PRIMARY && !SIMPLE && sv.shade_sort && i < n) i = q.perm[i];  // kind order inside the window (k_shade_sort)
-#endif
   const uint32_t in = depth & 1u, out = in ^ 1u;
   {
   const bool active = i < n;
@@ -736,8 +688,8 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
   }
   // ballot compaction (block level) of the surviving paths and of the two kinds of NEE connections
   uint32_t pos[3];
-  uint32_t* const counters[3] = {&ctl->n_active[depth + 1u], &ctl->n_shadow[0][depth], &ctl->n_shadow[1][depth]};
-  block_compact3(s_compact, keep, counters, &ctl->rays_shadow, pos);
+  uint32_t* const counters[3] = {&ctl->sizes.n_active[depth + 1u], &ctl->sizes.n_shadow[0][depth], &ctl->sizes.n_shadow[1][depth]};
+  block_compact3(s_compact, keep, counters, &ctl->totals.rays_shadow, pos);
   if (keep[0]) {
     float4* rp = reinterpret_cast<float4*>(q.rays[out] + pos[0]);
     st4(rp, make_float4(no.x, no.y, no.z, __uint_as_float(slot)));
@@ -812,138 +764,104 @@ __global__ void __launch_bounds__(256) k_scatter_tiles(FrameConst fc, const floa
 // ---------------------------------------------------------------------------------------------------------
 static inline uint32_t blocks_for(uint32_t n, uint32_t per) { return (n + per - 1) / per; }
 
-// tree: 0 large one-level, 1 LDS-staged, 2 two-level (kernels.h: TreeKind)
-size_t traverse_fixed_lds_bytes(int tree) {  // per-lane stacks (+ the waves' leaf work lists and merge slots of the large-scene variants)
-  return tree == 1 ? (size_t)kStackLdsStaged * kTraverseThreads * 8
-                   : (size_t)(tree == 2 ? kStackLdsInst : kStackLdsGlobal) * kTraverseThreads * 8 + (kTraverseThreads / 64) * kCoopBytesPerWave;
+// The one place where launch-time flags become kernel template arguments: calls f with one std::integral_constant<bool, flag> argument
+// per runtime flag, in order.  The callers leave out with `if constexpr` the combinations no kernel is built for (no kernel is both
+// STAGED and INST, ALPHA only exists for any-hit rays, SIMPLE shading has no SCATTER variant).
+template <class F>
+static void with_flags(F&& f) { f(); }
+template <class F, class... Flags>
+static void with_flags(F&& f, bool flag, Flags... flags) {
+  if (flag) with_flags([&](auto... c) { f(std::true_type{}, c...); }, flags...);
+  else with_flags([&](auto... c) { f(std::false_type{}, c...); }, flags...);
 }
-uint32_t traverse_stack_lds_levels(int tree) { return tree == 1 ? kStackLdsStaged : (tree == 2 ? kStackLdsInst : kStackLdsGlobal); }
+
+uint32_t traverse_stack_lds_levels(TreeForm tree) {
+  return tree == TreeForm::Staged ? kStackLdsStaged : (tree == TreeForm::TwoLevel ? kStackLdsInst : kStackLdsGlobal);
+}
+size_t traverse_fixed_lds_bytes(TreeForm tree) {  // per-lane stacks (+ the waves' leaf work lists and merge slots of the large-scene variants)
+  const size_t stacks = (size_t)traverse_stack_lds_levels(tree) * kTraverseThreads * 8;
+  return tree == TreeForm::Staged ? stacks : stacks + (kTraverseThreads / 64) * kCoopBytesPerWave;
+}
 uint32_t traverse_stack_spill_levels() { return kStackSpill; }
-uint32_t traverse_max_leaf(bool staged) { return staged ? 8u : (uint32_t)kLeafSlots; }
-uint32_t traverse_blocks_per_cu(size_t dynamic_lds_bytes, int tree) {
+uint32_t traverse_max_leaf(TreeForm tree) { return tree == TreeForm::Staged ? 8u : (uint32_t)kLeafSlots; }
+uint32_t traverse_blocks_per_cu(size_t dynamic_lds_bytes, TreeForm tree) {
   int a = 0, b = 0;
-  const hipError_t ea = tree == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_trace_batch<false, false, true, false, false>, kTraverseThreads, dynamic_lds_bytes)
-                      : tree == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_trace_batch<false, false, false, false, true>, kTraverseThreads, dynamic_lds_bytes)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_trace_batch<false, false, false, false, false>, kTraverseThreads, dynamic_lds_bytes);
-  const hipError_t eb = tree == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_trace_shadow<false, true, false, false>, kTraverseThreads, dynamic_lds_bytes)
-                      : tree == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_trace_shadow<false, false, false, true>, kTraverseThreads, dynamic_lds_bytes)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_trace_shadow<false, false, false, false>, kTraverseThreads, dynamic_lds_bytes);
+  hipError_t ea = hipSuccess, eb = hipSuccess;
+  with_flags([&](auto STAGED, auto INST) {
+    if constexpr (!(STAGED && INST)) {
+      ea = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_trace_batch<false, false, STAGED, false, INST>, kTraverseThreads, dynamic_lds_bytes);
+      eb = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_trace_shadow<false, STAGED, false, INST>, kTraverseThreads, dynamic_lds_bytes);
+    }
+  }, tree == TreeForm::Staged, tree == TreeForm::TwoLevel);
   if (ea != hipSuccess || eb != hipSuccess) return 0;
   return (uint32_t)std::max(0, std::min(a, b));
 }
-static size_t traverse_smem(const SceneView& sv) {
-  return traverse_fixed_lds_bytes(sv.staged ? 1 : (sv.two_level ? 2 : 0)) + (sv.staged ? (size_t)sv.lds_nodes * 64 + (size_t)sv.lds_tris * 48 : 0);
-}
 
-// the traversal kernels are compiled per (any-hit, counting, BVH staged in LDS); all three are launch-time constants
-template <bool ANY, bool COUNT, bool STAGED, bool ALPHA, bool INST>
-static void launch_trace_batch_t(const LaunchCfg& lc, const SceneView& sv, const hala_ray* rays, hala_hit* hits, const uint32_t* n_ptr,
-                                 uint32_t n_imm, WorkCounters* work, Control* ctl, int acc, size_t smem, hipStream_t s) {
-  hipLaunchKernelGGL((k_trace_batch<ANY, COUNT, STAGED, ALPHA, INST>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), smem, s, sv, rays, hits, n_ptr, n_imm,
-                     work, lc.spill, ctl, acc, lc.refill);
-}
-// the traversal kernels are compiled per (any-hit, counting, BVH staged in LDS | tree with instance levels) and, for the any-hit ones, per
-// "the scene has translucent materials" (RENDER_SPEC 7.1d: the ALPHA variants carry the texture fetch that decides whether a flagged
-// triangle blocks); all launch-time constants
+// The traversal kernels are compiled per (any-hit, counting, tree form) and, for the any-hit ones, per "the scene has translucent
+// materials" (RENDER_SPEC 7.1d: the ALPHA variants carry the texture fetch that decides whether a flagged triangle blocks); all
+// launch-time constants
 void launch_trace_batch(const LaunchCfg& lc, const SceneView& sv, const hala_ray* rays, hala_hit* hits, const uint32_t* n_ptr,
                         uint32_t n_imm, WorkCounters* work, Control* ctl, bool any, bool count, bool account, hipStream_t s) {
-  const int acc = account ? 1 : 0;
-  using Fn = void (*)(const LaunchCfg&, const SceneView&, const hala_ray*, hala_hit*, const uint32_t*, uint32_t, WorkCounters*, Control*, int, size_t,
-                      hipStream_t);
-  // index: tree (0 large one-level, 1 LDS-staged, 2 two-level) + 3 * (count + 2 * ray kind (0 closest, 1 any, 2 any with ALPHA))
-  static const Fn table[18] = {
-      launch_trace_batch_t<false, false, false, false, false>, launch_trace_batch_t<false, false, true, false, false>, launch_trace_batch_t<false, false, false, false, true>,
-      launch_trace_batch_t<false, true, false, false, false>,  launch_trace_batch_t<false, true, true, false, false>,  launch_trace_batch_t<false, true, false, false, true>,
-      launch_trace_batch_t<true, false, false, false, false>,  launch_trace_batch_t<true, false, true, false, false>,  launch_trace_batch_t<true, false, false, false, true>,
-      launch_trace_batch_t<true, true, false, false, false>,   launch_trace_batch_t<true, true, true, false, false>,   launch_trace_batch_t<true, true, false, false, true>,
-      launch_trace_batch_t<true, false, false, true, false>,   launch_trace_batch_t<true, false, true, true, false>,   launch_trace_batch_t<true, false, false, true, true>,
-      launch_trace_batch_t<true, true, false, true, false>,    launch_trace_batch_t<true, true, true, true, false>,    launch_trace_batch_t<true, true, false, true, true>};
   SceneView sva = sv;
   if (any) sva.tris = sv.tris_any;  // RENDER_SPEC 7.1d
-  const int kind = any ? (sv.any_translucent ? 2 : 1) : 0;
-  const int tree = sv.staged ? 1 : (sv.two_level ? 2 : 0);
-  table[tree + 3 * ((count ? 1 : 0) + 2 * kind)](lc, sva, rays, hits, n_ptr, n_imm, work, ctl, acc, traverse_smem(sv), s);
+  const TreeForm tree = tree_form(sv);
+  with_flags([&](auto ANY, auto COUNT, auto ALPHA, auto STAGED, auto INST) {
+    if constexpr ((ANY || !ALPHA) && !(STAGED && INST))
+      hipLaunchKernelGGL((k_trace_batch<ANY, COUNT, STAGED, ALPHA, INST>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sva, rays,
+                         hits, n_ptr, n_imm, work, lc.spill, ctl, account ? 1 : 0, lc.refill);
+  }, any, count, any && sv.any_translucent, tree == TreeForm::Staged, tree == TreeForm::TwoLevel);
 }
 
-template <bool COUNT, bool STAGED, bool ALPHA, bool INST>
-static void launch_trace_shadow_t(const LaunchCfg& lc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, uint32_t kind,
-                                  size_t smem, hipStream_t s) {
-  hipLaunchKernelGGL((k_trace_shadow<COUNT, STAGED, ALPHA, INST>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), smem, s, sv, q, ps, ctl, depth, kind, lc.spill, lc.refill);
-}
 void launch_trace_shadow(const LaunchCfg& lc, const SceneView& sv0, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth,
                          uint32_t kind, bool count, hipStream_t s) {
   SceneView sv = sv0;
   sv.tris = sv0.tris_any;  // RENDER_SPEC 7.1d: shadow rays traverse the copy in which invisible surfaces are degenerate and translucent ones flagged
-  using Fn = void (*)(const LaunchCfg&, const SceneView&, const Queues&, const PathState&, Control*, uint32_t, uint32_t, size_t, hipStream_t);
-  // index: tree (0 large one-level, 1 LDS-staged, 2 two-level) + 3 * (count + 2 * alpha)
-  static const Fn table[12] = {launch_trace_shadow_t<false, false, false, false>, launch_trace_shadow_t<false, true, false, false>, launch_trace_shadow_t<false, false, false, true>,
-                               launch_trace_shadow_t<true, false, false, false>,  launch_trace_shadow_t<true, true, false, false>,  launch_trace_shadow_t<true, false, false, true>,
-                               launch_trace_shadow_t<false, false, true, false>,  launch_trace_shadow_t<false, true, true, false>,  launch_trace_shadow_t<false, false, true, true>,
-                               launch_trace_shadow_t<true, false, true, false>,   launch_trace_shadow_t<true, true, true, false>,   launch_trace_shadow_t<true, false, true, true>};
-  const int tree = sv.staged ? 1 : (sv.two_level ? 2 : 0);
-  table[tree + 3 * ((count ? 1 : 0) + 2 * (sv.any_translucent ? 1 : 0))](lc, sv, q, ps, ctl, depth, kind, traverse_smem(sv0), s);
+  const TreeForm tree = tree_form(sv);
+  with_flags([&](auto COUNT, auto ALPHA, auto STAGED, auto INST) {
+    if constexpr (!(STAGED && INST))
+      hipLaunchKernelGGL((k_trace_shadow<COUNT, STAGED, ALPHA, INST>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, q, ps, ctl,
+                         depth, kind, lc.spill, lc.refill);
+  }, count, sv.any_translucent != 0u, tree == TreeForm::Staged, tree == TreeForm::TwoLevel);
 }
 
 // the fused launch; false: the caller must issue the two launches separately (an LDS-staged scene whose any-hit rays traverse a
 // different triangle copy than its closest-hit rays: only one of them is staged)
 bool launch_trace_shadow_then_batch(const LaunchCfg& lc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth,
                                     uint32_t kinds, bool with_closest, hipStream_t s) {
-  if (sv.staged && sv.tris_any != sv.tris) return false;
-  const size_t smem = traverse_smem(sv);
-  const dim3 grid(lc.persistent_blocks), block(kTraverseThreads);
+  const TreeForm tree = tree_form(sv);
+  if (tree == TreeForm::Staged && sv.tris_any != sv.tris) return false;
   const hala_ray* rays = with_closest ? q.rays[(depth + 1u) & 1u] : nullptr;
-  if (sv.staged) {
-    if (sv.any_translucent) hipLaunchKernelGGL((k_trace_shadow_then_batch<true, true, false>), grid, block, smem, s, sv, sv.tris_any, q, ps, ctl, depth, kinds, rays, q.hits, lc.spill, lc.refill);
-    else hipLaunchKernelGGL((k_trace_shadow_then_batch<true, false, false>), grid, block, smem, s, sv, sv.tris_any, q, ps, ctl, depth, kinds, rays, q.hits, lc.spill, lc.refill);
-  } else if (sv.two_level) {
-    if (sv.any_translucent) hipLaunchKernelGGL((k_trace_shadow_then_batch<false, true, true>), grid, block, smem, s, sv, sv.tris_any, q, ps, ctl, depth, kinds, rays, q.hits, lc.spill, lc.refill);
-    else hipLaunchKernelGGL((k_trace_shadow_then_batch<false, false, true>), grid, block, smem, s, sv, sv.tris_any, q, ps, ctl, depth, kinds, rays, q.hits, lc.spill, lc.refill);
-  } else {
-    if (sv.any_translucent) hipLaunchKernelGGL((k_trace_shadow_then_batch<false, true, false>), grid, block, smem, s, sv, sv.tris_any, q, ps, ctl, depth, kinds, rays, q.hits, lc.spill, lc.refill);
-    else hipLaunchKernelGGL((k_trace_shadow_then_batch<false, false, false>), grid, block, smem, s, sv, sv.tris_any, q, ps, ctl, depth, kinds, rays, q.hits, lc.spill, lc.refill);
-  }
+  with_flags([&](auto ALPHA, auto STAGED, auto INST) {
+    if constexpr (!(STAGED && INST))
+      hipLaunchKernelGGL((k_trace_shadow_then_batch<STAGED, ALPHA, INST>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, sv.tris_any,
+                         q, ps, ctl, depth, kinds, rays, q.hits, lc.spill, lc.refill);
+  }, sv.any_translucent != 0u, tree == TreeForm::Staged, tree == TreeForm::TwoLevel);
   return true;
 }
 
 void launch_trace_primary(const LaunchCfg& lc, const SceneView& sv, const FrameConst& fc, hala_hit* hits, WorkCounters* work, Control* ctl,
                           uint32_t n_account, bool count, hipStream_t s) {
-  const size_t smem = traverse_smem(sv);
-  static const uint32_t refill_env = tune_env("HALART_REFILL_PRIMARY") ? (uint32_t)atoi(tune_env("HALART_REFILL_PRIMARY")) : 0u;
+  const TreeForm tree = tree_form(sv);
   // camera rays of neighbouring pixels are about equally long: larger refills (40 idle lanes instead of 24) keep the 8 x 8 pixel blocks together
-  const uint32_t refill = refill_env ? refill_env : (sv.staged ? lc.refill : std::max(lc.refill, 40u));
-  dim3 grid(lc.persistent_blocks), block(kTraverseThreads);
-  if (sv.staged) {
-    if (count) hipLaunchKernelGGL((k_trace_primary<true, true, false>), grid, block, smem, s, sv, fc, hits, work, lc.spill, ctl, n_account, refill);
-    else hipLaunchKernelGGL((k_trace_primary<false, true, false>), grid, block, smem, s, sv, fc, hits, work, lc.spill, ctl, n_account, refill);
-  } else if (sv.two_level) {
-    if (count) hipLaunchKernelGGL((k_trace_primary<true, false, true>), grid, block, smem, s, sv, fc, hits, work, lc.spill, ctl, n_account, refill);
-    else hipLaunchKernelGGL((k_trace_primary<false, false, true>), grid, block, smem, s, sv, fc, hits, work, lc.spill, ctl, n_account, refill);
-  } else {
-    if (count) hipLaunchKernelGGL((k_trace_primary<true, false, false>), grid, block, smem, s, sv, fc, hits, work, lc.spill, ctl, n_account, refill);
-    else hipLaunchKernelGGL((k_trace_primary<false, false, false>), grid, block, smem, s, sv, fc, hits, work, lc.spill, ctl, n_account, refill);
-  }
+  const uint32_t refill = tree == TreeForm::Staged ? lc.refill : std::max(lc.refill, 40u);
+  with_flags([&](auto COUNT, auto STAGED, auto INST) {
+    if constexpr (!(STAGED && INST))
+      hipLaunchKernelGGL((k_trace_primary<COUNT, STAGED, INST>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, fc, hits, work,
+                         lc.spill, ctl, n_account, refill);
+  }, count, tree == TreeForm::Staged, tree == TreeForm::TwoLevel);
 }
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s) {
   const uint32_t threads = sv.simple_materials ? (uint32_t)kShadeThreads : (uint32_t)kShadeThreadsGeneric;
   dim3 grid(blocks_for(fc.slot_count, threads)), block(threads);
-#ifndef RT_SHADE_NOSORT
   // bounce launches of multi-kind scenes shade their paths in kind order inside windows of the queue
   if (depth != 0u && !sv.simple_materials && sv.shade_sort) {
     hipLaunchKernelGGL(k_shade_sort, dim3(blocks_for(fc.slot_count, kSortWindow)), dim3(kSortThreads), 0, s, q, ctl, depth);
     const uint32_t group = 8u * (kSortWindow / threads);  // whole groups of 8 windows: k_shade's window -> XCD mapping permutes the blocks of a group
     grid.x = blocks_for(grid.x, group) * group;
   }
-#endif
-  if (sv.simple_materials) {
-    if (depth == 0u) hipLaunchKernelGGL((k_shade<true, true, false>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
-    else hipLaunchKernelGGL((k_shade<false, true, false>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
-  } else if (sv.scatter_media) {
-    if (depth == 0u) hipLaunchKernelGGL((k_shade<true, false, true>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
-    else hipLaunchKernelGGL((k_shade<false, false, true>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
-  } else {
-    if (depth == 0u) hipLaunchKernelGGL((k_shade<true, false, false>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
-    else hipLaunchKernelGGL((k_shade<false, false, false>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
-  }
+  with_flags([&](auto PRIMARY, auto SIMPLE, auto SCATTER) {
+    if constexpr (!(SIMPLE && SCATTER)) hipLaunchKernelGGL((k_shade<PRIMARY, SIMPLE, SCATTER>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
+  }, depth == 0u, sv.simple_materials != 0u, !sv.simple_materials && sv.scatter_media);
 }
 void launch_resolve(const FrameConst& fc, const PathState& ps, float4* accum, float4* albedo, float4* normal, float4* final_img, hipStream_t s) {
   hipLaunchKernelGGL(k_resolve, dim3(blocks_for(fc.pixel_slots, 256)), dim3(256), 0, s, fc, ps, accum, albedo, normal, final_img);

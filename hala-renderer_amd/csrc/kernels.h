@@ -2,7 +2,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -14,15 +13,20 @@ struct LaunchCfg {
   uint32_t persistent_blocks;  // grid of the persistent traversal kernels
   uint2* spill;                // global stack spill area or nullptr (stack need <= kStackLds)
   uint32_t refill;             // a wave refills its idle lanes once this many are idle (64 = whole-wave batches)
+  size_t smem;                 // dynamic LDS bytes of the traversal kernels: a staged BVH + traverse_fixed_lds_bytes
 };
 
+// The forms of tree the traversal kernels are built for, each with its own kernel variants: a large one-level tree, a one-level tree
+// staged whole in LDS, a two-level tree (RENDER_SPEC 4.5)
+enum class TreeForm { Large, Staged, TwoLevel };
+inline TreeForm tree_form(const SceneView& sv) { return sv.staged ? TreeForm::Staged : (sv.two_level ? TreeForm::TwoLevel : TreeForm::Large); }
+
 // integrator.hip
-// `tree`: 0 = a large one-level tree, 1 = a tree staged whole in LDS, 2 = a two-level tree (RENDER_SPEC 4.5): each has its kernel variants
-size_t traverse_fixed_lds_bytes(int tree);  // LDS bytes of one workgroup besides a staged BVH: per-lane stacks (+ leaf work lists)
-uint32_t traverse_stack_lds_levels(int tree);  // stack entries kept in LDS
-uint32_t traverse_max_leaf(bool staged);  // largest leaf (triangles) the traversal variant accepts
+size_t traverse_fixed_lds_bytes(TreeForm tree);  // LDS bytes of one workgroup besides a staged BVH: per-lane stacks (+ leaf work lists)
+uint32_t traverse_stack_lds_levels(TreeForm tree);  // stack entries kept in LDS
+uint32_t traverse_max_leaf(TreeForm tree);  // largest leaf (triangles) the traversal variant accepts
 uint32_t traverse_stack_spill_levels();  // deeper entries spilled to global scratch (8 B each, per lane)
-uint32_t traverse_blocks_per_cu(size_t dynamic_lds_bytes, int tree);  // resident workgroups per CU (occupancy query)
+uint32_t traverse_blocks_per_cu(size_t dynamic_lds_bytes, TreeForm tree);  // resident workgroups per CU (occupancy query)
 void launch_trace_batch(const LaunchCfg& lc, const SceneView& sv, const hala_ray* rays, hala_hit* hits, const uint32_t* n_ptr,
                         uint32_t n_imm, WorkCounters* work, Control* ctl, bool any, bool count, bool account, hipStream_t s);
 void launch_trace_shadow(const LaunchCfg& lc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth,
@@ -43,14 +47,6 @@ void launch_mip_downsample(const float4* src, uint32_t sw, uint32_t sh, float4* 
 void launch_tile8(const uint32_t* src, uint32_t w, uint32_t h, uint32_t* dst, hipStream_t s);
 void launch_mip_downsample8(const uint32_t* src, uint32_t sw, uint32_t sh, uint32_t* dst, uint32_t dw, uint32_t dh, uint32_t format, const float* lut,
                             const float* thr, hipStream_t s);
-
-// Tuning knobs read from the environment exist only in builds made with -DHALART_TUNING (scripts/variant_sweep.sh): the results and
-// the speed of the release library do not depend on the caller's environment.
-#ifdef HALART_TUNING
-inline const char* tune_env(const char* name) { return getenv(name); }
-#else
-inline const char* tune_env(const char*) { return nullptr; }
-#endif
 
 // bvh_build.hip — K1/K3/K4: flatten instances to world space, LBVH build, refit
 // How commit() builds the hierarchy (hala_rt_set_build_options; 0 = the default everywhere).  The driver fields only change HOW the

@@ -91,8 +91,8 @@ struct TraceEvents {
   // timed passes: bit d of fused_mask = the third bracket of depth d holds a fused launch (k_trace_shadow_then_batch); bit d of
   // traced_mask = the closest-hit pass of depth d ran inside depth d - 1's fused launch (its own bracket is empty)
   unsigned long long fused_mask = 0, traced_mask = 0;
-  uint32_t* host_queue_sizes = nullptr;  // pinned: the head of the control block (n_active | n_shadow) as the pass left it
-  unsigned long long* host_counts = nullptr;  // pinned: rays_closest, rays_shadow, steps[2][2], probe[2][3]
+  QueueSizes* host_sizes = nullptr;  // pinned copy of Control::sizes as the pass left it (timed passes only)
+  Totals* host_totals = nullptr;     // pinned copy of Control::totals
 };
 
 }  // namespace
@@ -239,8 +239,8 @@ struct hala_rt_renderer {
       for (auto e : t.ev) (void)hipEventDestroy(e);
       if (t.frame_begin) (void)hipEventDestroy(t.frame_begin);
       if (t.frame_end) (void)hipEventDestroy(t.frame_end);
-      if (t.host_counts) (void)hipHostFree(t.host_counts);
-      if (t.host_queue_sizes) (void)hipHostFree(t.host_queue_sizes);
+      if (t.host_totals) (void)hipHostFree(t.host_totals);
+      if (t.host_sizes) (void)hipHostFree(t.host_sizes);
     }
     if (batch_done) (void)hipEventDestroy(batch_done);
     if (gather_stream) { (void)hipStreamSynchronize(gather_stream); (void)hipStreamDestroy(gather_stream); }
@@ -304,22 +304,22 @@ struct hala_rt_renderer {
     // four events per depth: a | closest-hit launch | b | shade launch | c | shadow launch(es) or the fused launch | d
     double tr[3] = {0.0, 0.0, 0.0}, sh = 0.0;  // closest-hit launches, shadow launches, fused launches
     unsigned long long rays[3] = {0, 0, 0}, launches[3] = {0, 0, 0};
-    const uint32_t* qn = t.host_queue_sizes;  // Control::n_active[kMaxDepth + 1] | n_shadow[2][kMaxDepth] of this pass (timed passes only)
+    const QueueSizes* qs = t.host_sizes;
     for (size_t k = 0, depth = 0; k + 3 < t.used; k += 4, ++depth) {
       float m = 0.0f;
       const bool own_closest = depth == 0 || !((t.traced_mask >> depth) & 1ull);  // else: it ran inside the previous depth's fused launch
       if (own_closest && hipEventElapsedTime(&m, t.ev[k], t.ev[k + 1]) == hipSuccess) {
-        const unsigned long long n = depth == 0 ? (unsigned long long)real_pixels * t.samples : qn[depth];
+        const unsigned long long n = depth == 0 ? (unsigned long long)real_pixels * t.samples : qs->n_active[depth];
         tr[0] += m; rays[0] += n; launches[0] += 1;
         if (depth == 0) { stats.traverse_primary_ms_total += m; stats.traverse_primary_launches += 1; stats.rays_primary_timed += n; }  // k_trace_primary
       }
       if (hipEventElapsedTime(&m, t.ev[k + 1], t.ev[k + 2]) == hipSuccess) sh += m;
       if (hipEventElapsedTime(&m, t.ev[k + 2], t.ev[k + 3]) == hipSuccess) {
-        const unsigned long long ns = (unsigned long long)qn[kMaxDepth + 1 + depth] + qn[kMaxDepth + 1 + kMaxDepth + depth];
+        const unsigned long long ns = (unsigned long long)qs->n_shadow[0][depth] + qs->n_shadow[1][depth];
         if ((t.fused_mask >> depth) & 1ull) {
           tr[2] += m; launches[2] += 1;
           stats.rays_fused_shadow_timed += ns;
-          if ((t.traced_mask >> (depth + 1)) & 1ull) stats.rays_fused_closest_timed += qn[depth + 1];
+          if ((t.traced_mask >> (depth + 1)) & 1ull) stats.rays_fused_closest_timed += qs->n_active[depth + 1];
         } else { tr[1] += m; rays[1] += ns; }
       }
     }
@@ -334,20 +334,21 @@ struct hala_rt_renderer {
     stats.traverse_shadow_launches += t.used ? t.shadow_launches : 0;  // as issued: one per connection kind the scene has, per depth
     stats.rays_closest_timed += rays[0]; stats.rays_shadow_timed += rays[1];
     stats.updates_rendered += t.samples;
-    const unsigned long long rc = t.host_counts[0], rs = t.host_counts[1];
+    const Totals& tot = *t.host_totals;
+    const unsigned long long rc = tot.rays_closest, rs = tot.rays_shadow;
     stats.rays_last_update = rc + rs;
     stats.rays_total += rc + rs;
     stats.rays_closest_total += rc;
     stats.rays_primary_total += (unsigned long long)real_pixels * t.samples;
     stats.rays_shadow_total += rs;
     if (t.counted) {
-      stats.nodes_closest_total += t.host_counts[2]; stats.tris_closest_total += t.host_counts[3];
-      stats.nodes_shadow_total += t.host_counts[4]; stats.tris_shadow_total += t.host_counts[5];
+      stats.nodes_closest_total += tot.steps[0][0]; stats.tris_closest_total += tot.steps[0][1];
+      stats.nodes_shadow_total += tot.steps[1][0]; stats.tris_shadow_total += tot.steps[1][1];
       stats.rays_closest_counted += rc; stats.rays_shadow_counted += rs;
-      stats.wave_steps_closest_total += t.host_counts[6]; stats.leaf_passes_closest_total += t.host_counts[7]; stats.leaf_lanes_closest_total += t.host_counts[8];
-      stats.nodes_primary_total += t.host_counts[12]; stats.tris_primary_total += t.host_counts[13];
+      stats.wave_steps_closest_total += tot.probe[0][0]; stats.leaf_passes_closest_total += tot.probe[0][1]; stats.leaf_lanes_closest_total += tot.probe[0][2];
+      stats.nodes_primary_total += tot.primary_steps[0]; stats.tris_primary_total += tot.primary_steps[1];
       stats.rays_primary_counted += (unsigned long long)real_pixels * t.samples;
-      stats.wave_steps_shadow_total += t.host_counts[9]; stats.leaf_passes_shadow_total += t.host_counts[10]; stats.leaf_lanes_shadow_total += t.host_counts[11];
+      stats.wave_steps_shadow_total += tot.probe[1][0]; stats.leaf_passes_shadow_total += tot.probe[1][1]; stats.leaf_lanes_shadow_total += tot.probe[1][2];
     }
     t.pending = false;
   }
@@ -460,7 +461,6 @@ int upload_packed(hala_rt_renderer* r, bool geometry = true) {
     r->scatter_media = false;
     for (const auto& m : hs.gpu_materials) r->scatter_media = r->scatter_media || m.medium_type == 2u;
     r->simple_materials = seen == (1u << kShadeKindFirst);  // nothing but untextured opaque DIFFUSE: the SIMPLE shade kernels (configs[1])
-    if (tune_env("HALART_NO_SIMPLE_SHADE")) r->simple_materials = false;
   }
   RT_HIP(r->d_instances.upload(hs.instances.data(), hs.instances.size(), r->stream));
   RT_HIP(r->d_inst_first_tri.upload(hs.inst_first_tri.data(), hs.inst_first_tri.size(), r->stream));
@@ -533,24 +533,20 @@ int configure_traversal(hala_rt_renderer* r) {
   const size_t nb = (size_t)r->bvh.node_count * 64, tb = (size_t)r->bvh.tri_count * 48;
   // Whole BVH in LDS when it fits the budget (the STAGED kernel variants read it with ds_read only); otherwise nothing
   // is staged: a top-of-tree slice measured no gain (profiles/r01_h_experiments.txt), the caches already hold it.
-  size_t budget = kLdsStageBudget;
-  if (const char* e = tune_env("HALART_LDS_STAGE_BYTES")) budget = (size_t)strtoul(e, nullptr, 10);  // tuning knob
-  r->staged = !r->two_level && nb + tb <= budget;  // (the LDS-staged kernel variants know no instances)
+  r->staged = !r->two_level && nb + tb <= kLdsStageBudget;  // (the LDS-staged kernel variants know no instances)
   r->lds_nodes = r->staged ? r->bvh.node_count : 0u;
   r->lds_tris = r->staged ? r->bvh.tri_count : 0u;
-  if (r->leaf_max_built > traverse_max_leaf(r->staged)) RT_FAIL("The BVH was built with larger leaves than the traversal variant for its size accepts.");
-  const int tree = r->staged ? 1 : (r->two_level ? 2 : 0);
+  const TreeForm tree = tree_form(r->view());
+  if (r->leaf_max_built > traverse_max_leaf(tree)) RT_FAIL("The BVH was built with larger leaves than the traversal variant for its size accepts.");
   const size_t smem = (size_t)r->lds_nodes * 64 + (size_t)r->lds_tris * 48 + traverse_fixed_lds_bytes(tree);
-  uint32_t per_cu = traverse_blocks_per_cu(smem, tree);
+  const uint32_t per_cu = traverse_blocks_per_cu(smem, tree);
   if (per_cu == 0) RT_FAIL("The traversal kernel does not fit on a compute unit with the requested LDS staging.");
-  per_cu = std::min(per_cu, 8u);
-  if (const char* e = tune_env("HALART_BLOCKS_PER_CU")) per_cu = std::min(per_cu, std::max(1u, (uint32_t)atoi(e)));  // tuning knob
-  r->lcfg.persistent_blocks = r->cu_count * per_cu;
+  r->lcfg.persistent_blocks = r->cu_count * std::min(per_cu, 8u);
+  r->lcfg.smem = smem;
   r->lcfg.spill = nullptr;
   // measured (profiles/r01_c_refill_sweep.txt): whole-wave refills are best when the BVH lives in LDS (uniform, cheap rays);
   // refilling once half the wave is idle is best when node fetches go to L2 / Infinity Cache
   r->lcfg.refill = r->staged ? 64u : kRefillThreshold;
-  if (const char* e = tune_env("HALART_REFILL")) r->lcfg.refill = std::min(64u, std::max(1u, (uint32_t)strtoul(e, nullptr, 10)));  // tuning knob
   if (r->two_level || r->bvh.stack_need > traverse_stack_lds_levels(tree)) {
     if (r->two_level || r->bvh.stack_need > traverse_stack_lds_levels(tree) + traverse_stack_spill_levels()) {
       // 3 x levels is a loose bound (every node on the path deferring three siblings).  Before refusing the tree, take the exact
@@ -831,8 +827,7 @@ int build_bvh(hala_rt_renderer* r) {
   if (attach_any_triangles(r) != HALA_OK) return HALA_ERR;
   // a scene this small will be staged in LDS (configure_traversal: 48 B per triangle + at most ~32 B of nodes per triangle)
   uint32_t leaf_max = (size_t)n * 80 <= kLdsStageBudget ? kLeafMaxStaged : kLeafMax;
-  if (const char* ev = tune_env("HALART_LEAF_MAX")) leaf_max = std::min(8u, std::max(1u, (uint32_t)atoi(ev)));  // tuning knob
-  if ((size_t)n * 80 > kLdsStageBudget) leaf_max = std::min(leaf_max, traverse_max_leaf(false));  // one consumer lane per triangle of a leaf item
+  if ((size_t)n * 80 > kLdsStageBudget) leaf_max = std::min(leaf_max, traverse_max_leaf(TreeForm::Large));  // one consumer lane per triangle of a leaf item
   const std::string e = bvh_build(r->bvh, leaf_max, r->stream);
   if (!e.empty()) RT_FAIL(e);
   r->leaf_max_built = leaf_max;
@@ -899,7 +894,6 @@ int hala_rt_create(const char* name, uint32_t width, uint32_t height, int device
   if (device_ordinal < 0 || device_ordinal >= count) RT_FAIL("The requested device ordinal does not exist.");
   RT_HIP(hipSetDevice(device_ordinal));
   std::unique_ptr<hala_rt_renderer> r(new hala_rt_renderer());
-  if (const char* ev = tune_env("HALART_EVENT_PERIOD")) r->launch_event_period = (uint32_t)std::max(0, atoi(ev));  // tuning knob
   r->name = name ? name : "";
   r->width = width; r->height = height; r->device = device_ordinal;
   r->max_depth = max_depth; r->rr_depth = rr_depth;
@@ -909,7 +903,6 @@ int hala_rt_create(const char* name, uint32_t width, uint32_t height, int device
   RT_HIP(hipGetDeviceProperties(&prop, device_ordinal));
   r->cu_count = (uint32_t)prop.multiProcessorCount;
   RT_HIP(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-  if (const char* ev = tune_env("HALART_FUSE")) r->fuse_mode = (uint32_t)std::max(0, std::min(2, atoi(ev)));
   compute_tiling(r.get());
   // create_storage_images (src/rt_renderer.rs:818-917): final, accum, albedo, normal
   if (alloc_frame_buffers(r.get()) != HALA_OK) return HALA_ERR;
@@ -1079,7 +1072,7 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   TraceEvents& te = r->ring[r->ring_pos];
   r->ring_pos = (r->ring_pos + 1) % kStatRing;
   r->resolve_slot(te);
-  if (!te.frame_begin) { RT_HIP(hipEventCreate(&te.frame_begin)); RT_HIP(hipEventCreate(&te.frame_end)); RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&te.host_counts), 14 * sizeof(unsigned long long), hipHostMallocDefault)); }
+  if (!te.frame_begin) { RT_HIP(hipEventCreate(&te.frame_begin)); RT_HIP(hipEventCreate(&te.frame_end)); RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&te.host_totals), sizeof(Totals), hipHostMallocDefault)); }
   te.used = 0; te.counted = r->counting; te.shadow_launches = 0; te.fused_mask = 0; te.traced_mask = 0;
 
   te.samples = samples;
@@ -1100,17 +1093,16 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   // persistent launch (k_trace_shadow_then_batch: one tail of long rays instead of three).  Updates that carry per-launch timing events or
   // counting kernels keep one launch per pass, so that every measured launch is one kernel symbol with the chip to itself.
   const bool fuse = (r->fuse_mode == 2u || (r->fuse_mode == 1u && !timed)) && !r->counting && (u.num_of_lights > 0 || u.env_type == 1u);
-  constexpr size_t kQueueSizeWords = (kMaxDepth + 1) + 2 * kMaxDepth;
-  if (timed && !te.host_queue_sizes) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&te.host_queue_sizes), kQueueSizeWords * sizeof(uint32_t), hipHostMallocDefault));
+  if (timed && !te.host_sizes) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&te.host_sizes), sizeof(QueueSizes), hipHostMallocDefault));
   bool traced = false;  // the closest-hit pass of this depth already ran inside the previous depth's fused launch
   for (uint32_t depth = 0; depth < r->max_depth; ++depth) {
     if (timed) { hipEvent_t a = r->next_event(te); RT_HIP(hipEventRecord(a, s)); }
     // depth 0: the camera rays are generated inside the traversal kernel, there is no ray-generation pass
     if (depth == 0) {
       launch_trace_primary(r->lcfg, sv, fc, q.hits, &ctl->work_closest, ctl, r->real_pixels * samples, r->counting, s);
-      if (r->counting) RT_HIP(hipMemcpyAsync(ctl->primary_steps, ctl->steps[0], 16, hipMemcpyDeviceToDevice, s));
+      if (r->counting) RT_HIP(hipMemcpyAsync(ctl->totals.primary_steps, ctl->totals.steps[0], 16, hipMemcpyDeviceToDevice, s));
     }
-    else if (!traced) launch_trace_batch(r->lcfg, sv, q.rays[depth & 1u], q.hits, &ctl->n_active[depth], 0, &ctl->work_closest, ctl, false, r->counting, true, s);
+    else if (!traced) launch_trace_batch(r->lcfg, sv, q.rays[depth & 1u], q.hits, &ctl->sizes.n_active[depth], 0, &ctl->work_closest, ctl, false, r->counting, true, s);
     traced = false;
     if (timed) { hipEvent_t b = r->next_event(te); RT_HIP(hipEventRecord(b, s)); }
     launch_shade(fc, sv, q, ps, ctl, depth, s);
@@ -1132,8 +1124,8 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
     if (timed) { hipEvent_t d = r->next_event(te); RT_HIP(hipEventRecord(d, s)); }
   }
   launch_resolve(fc, ps, r->img_local[0].ptr, r->img_local[1].ptr, r->img_local[2].ptr, r->img_local[3].ptr, s);
-  RT_HIP(hipMemcpyAsync(te.host_counts, &ctl->rays_closest, 14 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  if (timed) RT_HIP(hipMemcpyAsync(te.host_queue_sizes, ctl->n_active, kQueueSizeWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  RT_HIP(hipMemcpyAsync(te.host_totals, &ctl->totals, sizeof(Totals), hipMemcpyDeviceToHost, s));
+  if (timed) RT_HIP(hipMemcpyAsync(te.host_sizes, &ctl->sizes, sizeof(QueueSizes), hipMemcpyDeviceToHost, s));
   RT_HIP(hipEventRecord(te.frame_end, s));
   r->scratch_event = te.frame_end; r->scratch_stream = s;
   RT_HIP(hipGetLastError());
@@ -1615,9 +1607,9 @@ int hala_rt_trace_rays(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_
   if (r->scratch_acquire(s) != HALA_OK) return HALA_ERR;  // stream-ordered behind the previous user of the renderer's scratch (include/halart.h)
   RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
   // counters: the kernel accumulates into the control block's 64-bit fields; copy them out if requested
-  if (d_counters) RT_HIP(hipMemsetAsync(&r->d_ctl.ptr->steps[mode][0], 0, 16, s));
+  if (d_counters) RT_HIP(hipMemsetAsync(&r->d_ctl.ptr->totals.steps[mode][0], 0, 16, s));
   launch_trace_batch(r->lcfg, r->view(), d_rays, d_hits, nullptr, count, r->d_batch_work.ptr, r->d_ctl.ptr, mode == 1, d_counters != nullptr, false, s);
-  if (d_counters) RT_HIP(hipMemcpyAsync(d_counters, &r->d_ctl.ptr->steps[mode][0], 16, hipMemcpyDeviceToDevice, s));
+  if (d_counters) RT_HIP(hipMemcpyAsync(d_counters, &r->d_ctl.ptr->totals.steps[mode][0], 16, hipMemcpyDeviceToDevice, s));
   if (!r->batch_done) RT_HIP(hipEventCreateWithFlags(&r->batch_done, hipEventDisableTiming));
   RT_HIP(hipEventRecord(r->batch_done, s));
   r->scratch_event = r->batch_done; r->scratch_stream = s;

@@ -497,8 +497,8 @@ RT_DI bool trav_step(const SceneView& sv, const TraverseLds& lds, uint2* spill, 
                     __hip_atomic_fetch_add(ot + 3, q[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                   }
                 }
-                // the owner's prim word leaves kAbsent: it becomes the BVH-order index of a blocker (which one of several does not matter) —
-                // the occluder cache of the connection launches tests that triangle first for the lane's next ray (integrator.hip)
+                // the owner's prim word leaves kAbsent: it becomes the BVH-order index of a blocker (which one of several does not matter),
+                // which the owner reads back below as its any-hit result (found, best.prim)
                 if (blocks) *(RT_LDS uint32_t*)okey = (leaf & 0x0fffffffu) + j;
               }
             }
