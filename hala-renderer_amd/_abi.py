@@ -183,7 +183,16 @@ class DenoiseParams(C.Structure):  # hala_denoise_params, 32 B (docs/RENDER_SPEC
                 ("normal_power", C.c_uint32), ("demodulate", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
-# argtypes / restype of the denoise entry points (load_library installs them)
+class AdaptiveParams(C.Structure):  # hala_adaptive_params, 32 B (docs/RENDER_SPEC.md 11)
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_uint32), ("interval", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class AdaptiveStatus(C.Structure):  # hala_adaptive_status, 32 B
+    _fields_ = [("enabled", C.c_uint32), ("active_blocks", C.c_uint32), ("total_blocks", C.c_uint32), ("active_pixels", C.c_uint32),
+                ("samples", C.c_uint32), ("last_snapshot", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+# argtypes / restype of the denoise and adaptive sampling entry points (load_library installs them)
 PROTOTYPES = {
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
     "hala_rt_denoise": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
@@ -192,6 +201,10 @@ PROTOTYPES = {
     "hala_rt_save_denoised": ([C.c_void_p, C.c_char_p], C.c_int),
     "hala_denoise_images": ([C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
                              C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
+    "hala_adaptive_default_params": ([C.POINTER(AdaptiveParams)], None),
+    "hala_rt_set_adaptive_sampling": ([C.c_void_p, C.POINTER(AdaptiveParams)], C.c_int),
+    "hala_rt_read_sample_counts": ([C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
+    "hala_rt_get_adaptive_status": ([C.c_void_p, C.POINTER(AdaptiveStatus)], C.c_int),
 }
 
 
@@ -227,4 +240,5 @@ EXPORTS = [
     "hala_rt_tile_allgather_begin_external", "hala_rt_get_exchange_buffers",
     "hala_denoise_default_params", "hala_rt_denoise", "hala_rt_read_denoised", "hala_rt_get_denoised_buffer", "hala_rt_save_denoised",
     "hala_denoise_images",
+    "hala_adaptive_default_params", "hala_rt_set_adaptive_sampling", "hala_rt_read_sample_counts", "hala_rt_get_adaptive_status",
 ]

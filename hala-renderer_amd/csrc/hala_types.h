@@ -216,6 +216,9 @@ struct FrameConst {
   // result is bit-identical to `samples` single-sample updates.
   uint32_t samples;
   uint32_t slot_count;  // pixel_slots * samples
+  // adaptive sampling (RENDER_SPEC §11; world == 1 only): the pixel blocks this update renders, in ascending order — pixel block j of the
+  // slot order is block_list[j], and pixel_slots = 64 x their count.  nullptr: every block (the feature is off)
+  const uint32_t* block_list;
 };
 
 // device control block: queue sizes and work counters of the wavefront loop.  One slot per bounce, so a single

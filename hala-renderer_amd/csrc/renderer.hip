@@ -13,6 +13,7 @@
 #include <sys/stat.h>
 #include <vector>
 
+#include "adaptive.h"
 #include "denoise.h"
 #include "dyn_api.h"
 #include "hala_types.h"
@@ -87,6 +88,7 @@ struct TraceEvents {
   hipEvent_t frame_begin = nullptr, frame_end = nullptr;
   bool pending = false, counted = false;
   uint32_t samples = 1;  // frames rendered by this wavefront pass
+  uint32_t primary_pixels = 0;  // pixels that traced a camera ray per frame (all real ones; the active blocks' under adaptive sampling)
   uint32_t shadow_launches = 0;  // k_trace_shadow launches inside the timed brackets of this pass (0, 1 or 2 per depth)
   // timed passes: bit d of fused_mask = the third bracket of depth d holds a fused launch (k_trace_shadow_then_batch); bit d of
   // traced_mask = the closest-hit pass of depth d ran inside depth d - 1's fused launch (its own bracket is empty)
@@ -190,6 +192,7 @@ struct hala_rt_renderer {
   bool full_valid[4] = {false, false, false, false};
   DenoiseBuffers denoise;      // RENDER_SPEC 10: allocated by the first hala_rt_denoise
   bool denoised = false;       // denoise.out holds a result
+  AdaptiveState adaptive;      // RENDER_SPEC 11: allocated by the first hala_rt_set_adaptive_sampling that enables it
   DeviceArray<P3> ps_lr, ps_le, ps_alb, ps_nrm;
   DeviceArray<hala_ray> q_rays[2];
   DeviceArray<float4> q_state[2];
@@ -287,13 +290,21 @@ struct hala_rt_renderer {
     fc.tile_size = tile_size; fc.tiles_x = tiles_x; fc.tiles_y = tiles_y; fc.world = world; fc.rank = rank; fc.blocks_x = blocks_x;
     fc.tiles_per_rank = tiles_per_rank; fc.perm_a = perm_a_inv; fc.perm_b = perm_b;
     fc.pixel_slots = slot_count; fc.samples = samples; fc.slot_count = slot_count * samples;
+    if (adaptive.enabled) {  // RENDER_SPEC 11: slots for the active blocks only
+      fc.block_list = adaptive.lists[adaptive.cur].ptr;
+      fc.pixel_slots = adaptive.active_blocks * kPixelBlock * kPixelBlock;
+      fc.slot_count = fc.pixel_slots * samples;
+    }
     return fc;
   }
 
   void reset_accumulation() {  // statistics.reset() of the device-lost path (src/rt_renderer.rs:557)
     total_frames = 0;
     for (bool& v : full_valid) v = false;
+    adaptive.restart(width * height);
   }
+  // frames folded into the pixels that are still traced (every pixel with adaptive sampling off)
+  uint32_t rendered_frames() const { return (uint32_t)std::min(total_frames, max_frames); }
 
   // resolve one ring slot's events into the totals (the slot's work must have completed)
   void resolve_slot(TraceEvents& t) {
@@ -309,7 +320,7 @@ struct hala_rt_renderer {
       float m = 0.0f;
       const bool own_closest = depth == 0 || !((t.traced_mask >> depth) & 1ull);  // else: it ran inside the previous depth's fused launch
       if (own_closest && hipEventElapsedTime(&m, t.ev[k], t.ev[k + 1]) == hipSuccess) {
-        const unsigned long long n = depth == 0 ? (unsigned long long)real_pixels * t.samples : qs->n_active[depth];
+        const unsigned long long n = depth == 0 ? (unsigned long long)t.primary_pixels * t.samples : qs->n_active[depth];
         tr[0] += m; rays[0] += n; launches[0] += 1;
         if (depth == 0) { stats.traverse_primary_ms_total += m; stats.traverse_primary_launches += 1; stats.rays_primary_timed += n; }  // k_trace_primary
       }
@@ -339,7 +350,7 @@ struct hala_rt_renderer {
     stats.rays_last_update = rc + rs;
     stats.rays_total += rc + rs;
     stats.rays_closest_total += rc;
-    stats.rays_primary_total += (unsigned long long)real_pixels * t.samples;
+    stats.rays_primary_total += (unsigned long long)t.primary_pixels * t.samples;
     stats.rays_shadow_total += rs;
     if (t.counted) {
       stats.nodes_closest_total += tot.steps[0][0]; stats.tris_closest_total += tot.steps[0][1];
@@ -347,7 +358,7 @@ struct hala_rt_renderer {
       stats.rays_closest_counted += rc; stats.rays_shadow_counted += rs;
       stats.wave_steps_closest_total += tot.probe[0][0]; stats.leaf_passes_closest_total += tot.probe[0][1]; stats.leaf_lanes_closest_total += tot.probe[0][2];
       stats.nodes_primary_total += tot.primary_steps[0]; stats.tris_primary_total += tot.primary_steps[1];
-      stats.rays_primary_counted += (unsigned long long)real_pixels * t.samples;
+      stats.rays_primary_counted += (unsigned long long)t.primary_pixels * t.samples;
       stats.wave_steps_shadow_total += tot.probe[1][0]; stats.leaf_passes_shadow_total += tot.probe[1][1]; stats.leaf_lanes_shadow_total += tot.probe[1][2];
     }
     t.pending = false;
@@ -1068,6 +1079,14 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   u.num_of_lights = (uint32_t)r->hs.lights.size();
   r->last_uniform = u;
   r->last_uniform.frame_index = (uint32_t)(first + samples - 1);  // what the last frame of the batch would have uploaded
+  AdaptiveState& ad = r->adaptive;
+  if (ad.enabled && first == 0 && adaptive_begin(ad, r->stream) != hipSuccess) RT_FAIL("hala_rt_update: the adaptive sampling state could not be reset.");
+  if (ad.enabled && ad.active_blocks == 0) {  // RENDER_SPEC 11: every block has converged; the frames count, nothing is launched
+    for (int k = 0; k < kStatRing; ++k) r->resolve_slot(r->ring[(r->ring_pos + k) % kStatRing]);  // done: the last check waited for them
+    r->stats.rays_last_update = 0;
+    return HALA_OK;
+  }
+  const uint32_t primary_pixels = ad.enabled ? ad.active_pixels : r->real_pixels;
 
   TraceEvents& te = r->ring[r->ring_pos];
   r->ring_pos = (r->ring_pos + 1) % kStatRing;
@@ -1076,6 +1095,7 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   te.used = 0; te.counted = r->counting; te.shadow_launches = 0; te.fused_mask = 0; te.traced_mask = 0;
 
   te.samples = samples;
+  te.primary_pixels = primary_pixels;
   const FrameConst fc = r->frame_const(u, samples);
   const SceneView sv = r->view();
   const Queues q = r->queues();
@@ -1099,7 +1119,7 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
     if (timed) { hipEvent_t a = r->next_event(te); RT_HIP(hipEventRecord(a, s)); }
     // depth 0: the camera rays are generated inside the traversal kernel, there is no ray-generation pass
     if (depth == 0) {
-      launch_trace_primary(r->lcfg, sv, fc, q.hits, &ctl->work_closest, ctl, r->real_pixels * samples, r->counting, s);
+      launch_trace_primary(r->lcfg, sv, fc, q.hits, &ctl->work_closest, ctl, primary_pixels * samples, r->counting, s);
       if (r->counting) RT_HIP(hipMemcpyAsync(ctl->totals.primary_steps, ctl->totals.steps[0], 16, hipMemcpyDeviceToDevice, s));
     }
     else if (!traced) launch_trace_batch(r->lcfg, sv, q.rays[depth & 1u], q.hits, &ctl->sizes.n_active[depth], 0, &ctl->work_closest, ctl, false, r->counting, true, s);
@@ -1131,6 +1151,17 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   RT_HIP(hipGetLastError());
   te.pending = true;
   for (bool& v : r->full_valid) v = false;
+  // RENDER_SPEC 11: hala_rt_update_batch ends its chunks on these frames, so n is the snapshot or check frame itself
+  const uint32_t n = (uint32_t)(first + samples);
+  if (ad.enabled && n == ad.p.min_samples / 2u) {
+    RT_HIP(hipMemcpyAsync(ad.snapshot.ptr, r->img_local[0].ptr, ad.snapshot.bytes(), hipMemcpyDeviceToDevice, s));
+    ad.last_snapshot = n;
+  }
+  if (ad.enabled && adaptive_is_check(ad.p, n)) {  // the one synchronising update: the next ones are sized by the two counts
+    RT_HIP(adaptive_enqueue_check(ad, r->img_local[0].ptr, r->width, r->height, r->blocks_x, r->exposure, n, s));
+    RT_HIP(hipStreamSynchronize(s));
+    adaptive_finish_check(ad, n);
+  }
   return HALA_OK;
 }
 
@@ -1139,7 +1170,9 @@ int hala_rt_update(hala_rt_renderer* r, double, uint32_t, uint32_t) { return upd
 int hala_rt_update_batch(hala_rt_renderer* r, uint32_t frames) {
   if (!r) RT_FAIL("The renderer handle is null!");
   while (frames > 0) {
-    const uint32_t chunk = std::min(frames, kMaxSampleBatch);
+    uint32_t chunk = std::min(frames, kMaxSampleBatch);
+    if (r->adaptive.enabled && r->total_frames < r->max_frames)  // a chunk ends on the next snapshot or check frame (RENDER_SPEC 11)
+      chunk = (uint32_t)std::min<uint64_t>(chunk, adaptive_frames_to_event(r->adaptive.p, r->total_frames));
     if (update_impl(r, chunk) != HALA_OK) return HALA_ERR;
     frames -= chunk;
   }
@@ -1210,6 +1243,64 @@ int hala_rt_get_statistics(hala_rt_renderer* r, hala_rt_statistics* out) {
 int hala_rt_reset_accumulation(hala_rt_renderer* r) {
   if (!r) RT_FAIL("The renderer handle is null!");
   r->reset_accumulation();
+  return HALA_OK;
+}
+
+// ---- adaptive sampling (RENDER_SPEC 11) -------------------------------------------------------------------------------------
+int hala_rt_set_adaptive_sampling(hala_rt_renderer* r, const hala_adaptive_params* p) {
+  if (p) {
+    const std::string bad = adaptive_check_params(p);  // first: the CPU tier pins it without a renderer
+    if (!bad.empty()) RT_FAIL(bad);
+  }
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  AdaptiveState& ad = r->adaptive;
+  if (p) {
+    if (kPixelBlock != 8u) RT_FAIL("Adaptive sampling needs the 8 x 8 pixel blocks of RENDER_SPEC 9 (this build has RT_PIXEL_BLOCK = " + std::to_string(kPixelBlock) + ").");
+    if (r->world > 1) RT_FAIL("Adaptive sampling is not available on a sharded renderer (world > 1).");
+    if (!ad.enabled) {
+      RT_HIP(hipStreamSynchronize(r->stream));
+      const uint32_t blocks = r->blocks_x * ((r->height + kPixelBlock - 1) / kPixelBlock);
+      RT_HIP(ad.ensure(blocks, (size_t)r->width * r->height));
+    }
+    ad.p = *p;
+    ad.enabled = true;
+  } else if (ad.enabled) {
+    RT_HIP(hipStreamSynchronize(r->stream));
+    ad.release();
+    ad.enabled = false;
+  }
+  r->reset_accumulation();
+  return HALA_OK;
+}
+int hala_rt_read_sample_counts(hala_rt_renderer* r, uint32_t* dst) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!dst) RT_FAIL("The output pointer is null!");
+  const uint32_t n = r->rendered_frames();
+  const size_t pixels = (size_t)r->width * r->height;
+  const AdaptiveState& ad = r->adaptive;
+  if (!ad.enabled || n == 0) { std::fill(dst, dst + pixels, n); return HALA_OK; }
+  std::vector<uint32_t> c(ad.total_blocks);
+  RT_HIP(hipStreamSynchronize(r->stream));
+  RT_HIP(hipMemcpy(c.data(), ad.block_count.ptr, c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (uint32_t y = 0; y < r->height; ++y)
+    for (uint32_t x = 0; x < r->width; ++x) {
+      const uint32_t cb = c[(y / kPixelBlock) * r->blocks_x + x / kPixelBlock];
+      dst[(size_t)y * r->width + x] = cb ? cb : n;  // 0: still active
+    }
+  return HALA_OK;
+}
+int hala_rt_get_adaptive_status(hala_rt_renderer* r, hala_adaptive_status* out) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (!out) RT_FAIL("The output pointer is null!");
+  memset(out, 0, sizeof(*out));
+  const AdaptiveState& ad = r->adaptive;
+  const uint32_t bh = kPixelBlock ? (r->height + kPixelBlock - 1) / kPixelBlock : 0u;
+  out->enabled = ad.enabled ? 1u : 0u;
+  out->total_blocks = ad.enabled ? ad.total_blocks : r->blocks_x * bh;
+  out->active_blocks = ad.enabled ? ad.active_blocks : out->total_blocks;
+  out->active_pixels = ad.enabled ? ad.active_pixels : r->width * r->height;
+  out->samples = r->rendered_frames();
+  out->last_snapshot = ad.enabled ? ad.last_snapshot : 0u;
   return HALA_OK;
 }
 
@@ -1392,6 +1483,7 @@ int hala_rt_set_tile_shard(hala_rt_renderer* r, uint32_t rank, uint32_t world, u
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (world == 0 || rank >= world) RT_FAIL("Invalid rank / world size.");
   if (tile_size == 0 || tile_size > 256) RT_FAIL("Invalid tile size.");
+  if (world > 1 && r->adaptive.enabled) RT_FAIL("Adaptive sampling is on: a sharded frame cannot use it (hala_rt_set_adaptive_sampling(r, NULL) first).");
   // a collective in flight belongs to the old shard: complete it (its receive buffer is laid out for the old world size)
   if (r->gather_pending && hala_rt_tile_allgather_finish(r) != HALA_OK) return HALA_ERR;
   // a communicator is bound to (rank, world): gather_recv is sized by it and the de-interleave indexes it by the shard's world

@@ -21,7 +21,9 @@ RT_DI bool slot_to_pixel(const FrameConst& fc, uint32_t slot, uint32_t* px, uint
       return true;
     }
     constexpr uint32_t kB = kPixelBlock ? kPixelBlock : 1u, kB2 = kB * kB;
-    const uint32_t blk = slot / kB2, within = slot - blk * kB2;
+    uint32_t blk = slot / kB2;
+    const uint32_t within = slot - blk * kB2;
+    if (fc.block_list) blk = fc.block_list[blk];  // adaptive sampling (RENDER_SPEC §11): only the active blocks have slots
     const uint32_t ly = within / kB, lx = within - ly * kB;
     const uint32_t by = blk / fc.blocks_x, bx = blk - by * fc.blocks_x;
     *px = bx * kB + lx;

@@ -210,6 +210,27 @@ class HalaRenderer:
         """<stem>_denoised.pfm, tonemapped on the host like save_images' <stem>_color.pfm"""
         self._check(self._lib.hala_rt_save_denoised(self._h, os.fsencode(path)))
 
+    # -- adaptive sampling (docs/RENDER_SPEC.md 11; include/halart.h "hala_rt_set_adaptive_sampling") -------------------------------
+    def set_adaptive_sampling(self, threshold, min_samples=None, interval=None):
+        """stop tracing the 8 x 8 pixel blocks whose error estimate fell below `threshold` (None: turn the feature off); None for
+        min_samples / interval: the library's default.  Restarts the accumulation either way."""
+        if threshold is None:
+            self._check(self._lib.hala_rt_set_adaptive_sampling(self._h, None))
+            return
+        p = adaptive_default_params(threshold=threshold, min_samples=min_samples, interval=interval)
+        self._check(self._lib.hala_rt_set_adaptive_sampling(self._h, C.byref(p)))
+
+    def read_sample_counts(self) -> np.ndarray:
+        """[H, W] uint32: the samples folded into each pixel"""
+        out = np.empty((self.height, self.width), dtype=np.uint32)
+        self._check(self._lib.hala_rt_read_sample_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def adaptive_status(self) -> A.AdaptiveStatus:
+        s = A.AdaptiveStatus()
+        self._check(self._lib.hala_rt_get_adaptive_status(self._h, C.byref(s)))
+        return s
+
     def global_uniform(self) -> A.GlobalUniform:
         u = A.GlobalUniform()
         self._check(self._lib.hala_rt_get_global_uniform(self._h, C.byref(u)))
@@ -383,6 +404,17 @@ def denoise_default_params(**overrides) -> A.DenoiseParams:
     for k, v in overrides.items():
         if v is not None:
             setattr(p, k, int(bool(v)) if k == "demodulate" else v)
+    return p
+
+
+def adaptive_default_params(**overrides) -> A.AdaptiveParams:
+    """hala_adaptive_default_params with the fields given (not None) replaced"""
+    from . import load_library
+    p = A.AdaptiveParams()
+    load_library().hala_adaptive_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if v is not None:
+            setattr(p, k, v)
     return p
 
 

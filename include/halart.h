@@ -470,7 +470,8 @@ int hala_rt_sample_texture_host(hala_rt_renderer* r, uint32_t texture, const flo
  * hala_rt_tile_buffer gives its device address + byte size (per AOV) for the RCCL all-gather, and
  * hala_rt_scatter_gathered_tiles de-interleaves the gathered [world][tiles_per_rank][ts*ts][4] buffer (inside a tile the pixels
  * come in 8 x 8 blocks when ts is a multiple of 8: docs/RENDER_SPEC.md 9) into the row-major images of this renderer.  The renderer works on its own HIP stream: wait (hala_rt_wait_idle, or a stream
- * dependency on hala_rt_get_stream) before another stream reads the tile buffer — hala_rt_render does not flush. */
+ * dependency on hala_rt_get_stream) before another stream reads the tile buffer — hala_rt_render does not flush.
+ * world > 1 is refused while adaptive sampling is on (hala_rt_set_adaptive_sampling). */
 int hala_rt_set_tile_shard(hala_rt_renderer* r, uint32_t rank, uint32_t world, uint32_t tile_size);
 int hala_rt_tile_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_t* bytes);
 /* the hipStream_t every launch of this renderer goes to (for stream-ordered hand-overs: hipStreamWaitEvent both ways) */
@@ -625,6 +626,34 @@ int hala_rt_save_denoised(hala_rt_renderer* r, const char* path);
  * color / albedo / normal / dst are W*H*4 floats, row 0 = top.  Parameters are validated before any device call. */
 int hala_denoise_images(int device_ordinal, const float* color, const float* albedo, const float* normal, uint32_t width,
                         uint32_t height, const hala_denoise_params* p, float* dst);
+
+/* ------------------------------------------------------------------------------------------------
+ * Adaptive sampling (docs/RENDER_SPEC.md 11; no reference equivalent): the 8 x 8 pixel blocks whose running mean has converged stop
+ * being traced until the accumulation restarts.  Opt-in: nothing is allocated and no image changes for a renderer that never enables it.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hala_adaptive_status {
+  uint32_t enabled, active_blocks, total_blocks, active_pixels;
+  uint32_t samples;       /* n: frames folded into the active blocks */
+  uint32_t last_snapshot; /* s */
+  uint32_t reserved[2];
+} hala_adaptive_status;   /* 32 B */
+typedef struct hala_adaptive_params {
+  float threshold;        /* finite, > 0: a block converges when every pixel's error estimate is below it */
+  uint32_t min_samples;   /* 2 ... 65536: the first check (the snapshot is taken at min_samples / 2) */
+  uint32_t interval;      /* 1 ... 65536: samples between two checks */
+  uint32_t reserved[5];   /* 0 */
+} hala_adaptive_params;   /* 32 B */
+/* the defaults (DESIGN.md "Adaptive sampling" records the measurements behind them) */
+void hala_adaptive_default_params(hala_adaptive_params* out);
+/* p: enable with these parameters; NULL: off.  Either way the accumulation restarts.  Refused, with the renderer left as it was:
+ * invalid parameters (checked before the handle is looked at), a sharded renderer (world > 1), a build with another pixel block size.
+ * The first call that enables allocates the snapshot image and the block lists.  An update that ends on a check frame
+ * (n = min_samples + j * interval) waits for the check and reads two counts back; every other update stays asynchronous. */
+int hala_rt_set_adaptive_sampling(hala_rt_renderer* r, const hala_adaptive_params* p);
+/* W*H uint32, row-major: the samples folded into each pixel (with the feature off: the frames rendered since the accumulation started) */
+int hala_rt_read_sample_counts(hala_rt_renderer* r, uint32_t* dst);
+/* active / total blocks, active in-frame pixels, n and s */
+int hala_rt_get_adaptive_status(hala_rt_renderer* r, hala_adaptive_status* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Stand-alone pieces of the path (usable without a renderer)
