@@ -234,10 +234,26 @@ struct hala_rt_renderer {
     if (scratch_event && scratch_stream != s) RT_HIP(hipStreamWaitEvent(s, scratch_event, 0));
     return HALA_OK;
   }
+  // The tail of an untimed update — the last bounce's shadow launch(es), k_resolve and the read-back of the totals — runs on tail_stream,
+  // beside the next update's k_trace_primary, which needs none of it.  The tail uses the update's own control block
+  // (d_ctl holds two, updates alternate) and its own stack spill area.  While tail_open the renderer's stream has not waited for it:
+  // every entry point joins it first (ensure_device), except update — after its camera-ray launch — and render.
+  hipStream_t tail_stream = nullptr;
+  hipEvent_t ev_shaded = nullptr;  // the last k_shade of an untimed update: where its tail starts
+  hipEvent_t tail_done = nullptr;  // not owned: the frame_end of that update, recorded on tail_stream
+  bool tail_open = false;
+  uint32_t ctl_pos = 0;            // control block of the next update
+  DeviceArray<uint2> d_spill_tail;
+  int join_tail() {
+    if (tail_open) RT_HIP(hipStreamWaitEvent(stream, tail_done, 0));
+    tail_open = false;
+    return HALA_OK;
+  }
 
   ~hala_rt_renderer() {
     if (device >= 0) (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
+    if (tail_stream) (void)hipStreamSynchronize(tail_stream);
     for (auto& t : ring) {
       for (auto e : t.ev) (void)hipEventDestroy(e);
       if (t.frame_begin) (void)hipEventDestroy(t.frame_begin);
@@ -254,6 +270,8 @@ struct hala_rt_renderer {
     for (auto& i : img_full) i.release();
     if (bvh.topology) bvh_free_topology(bvh.topology);
     blas.clear();
+    if (ev_shaded) (void)hipEventDestroy(ev_shaded);
+    if (tail_stream) (void)hipStreamDestroy(tail_stream);
     if (stream) (void)hipStreamDestroy(stream);
   }
 
@@ -371,9 +389,11 @@ struct hala_rt_renderer {
 
 namespace {
 
-int ensure_device(hala_rt_renderer* r) {
+// join = false: update and render only, which leave the tail of the last update running (hala_rt_renderer::tail_stream)
+int ensure_device(hala_rt_renderer* r, bool join = true) {
   if (!r) RT_FAIL("The renderer handle is null!");
   RT_HIP(hipSetDevice(r->device));
+  if (join && r->join_tail() != HALA_OK) return HALA_ERR;
   return HALA_OK;
 }
 
@@ -426,8 +446,8 @@ int alloc_frame_buffers(hala_rt_renderer* r) {
   const size_t n = r->slot_count;
   for (auto& i : r->img_local) { RT_HIP(i.resize(n)); RT_HIP(hipMemsetAsync(i.ptr, 0, n * sizeof(float4), r->stream)); }
   if (alloc_wavefront(r, 1) != HALA_OK) return HALA_ERR;
-  RT_HIP(r->d_ctl.resize(1));
-  RT_HIP(hipMemsetAsync(r->d_ctl.ptr, 0, sizeof(Control), r->stream));
+  RT_HIP(r->d_ctl.resize(2));  // updates alternate between the two: a tail still running accounts into its own
+  RT_HIP(hipMemsetAsync(r->d_ctl.ptr, 0, 2 * sizeof(Control), r->stream));
   RT_HIP(r->d_batch_work.resize(1));
   return HALA_OK;
 }
@@ -587,6 +607,7 @@ int configure_traversal(hala_rt_renderer* r) {
     if (r->bvh.stack_need > traverse_stack_lds_levels(tree) + traverse_stack_spill_levels())
       RT_FAIL("The BVH is deeper than the traversal stack supports (" + std::to_string(r->bvh.max_depth) + " levels, " + std::to_string(r->bvh.stack_need) + " stack entries).");
     RT_HIP(r->d_spill.resize((size_t)r->lcfg.persistent_blocks * 256 * traverse_stack_spill_levels()));
+    RT_HIP(r->d_spill_tail.resize(r->d_spill.count));  // the launches of an update's tail, which run beside the next camera-ray launch
     r->lcfg.spill = r->d_spill.ptr;
   }
   const float ex = r->bvh.scene_max[0] - r->bvh.scene_min[0], ey = r->bvh.scene_max[1] - r->bvh.scene_min[1], ez = r->bvh.scene_max[2] - r->bvh.scene_min[2];
@@ -914,6 +935,8 @@ int hala_rt_create(const char* name, uint32_t width, uint32_t height, int device
   RT_HIP(hipGetDeviceProperties(&prop, device_ordinal));
   r->cu_count = (uint32_t)prop.multiProcessorCount;
   RT_HIP(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+  RT_HIP(hipStreamCreateWithFlags(&r->tail_stream, hipStreamNonBlocking));
+  RT_HIP(hipEventCreateWithFlags(&r->ev_shaded, hipEventDisableTiming));
   compute_tiling(r.get());
   // create_storage_images (src/rt_renderer.rs:818-917): final, accum, albedo, normal
   if (alloc_frame_buffers(r.get()) != HALA_OK) return HALA_ERR;
@@ -1054,13 +1077,14 @@ int hala_rt_set_build_options(hala_rt_renderer* r, const hala_rt_build_options* 
 // (src/rt_renderer.rs:394-396); the frames that do render share one kernel sequence with `samples` paths per pixel.
 static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   RtRange range("halart::update");
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (ensure_device(r, false) != HALA_OK) return HALA_ERR;
   if (!r->committed) RT_FAIL("The pipeline is none!");  // src/rt_renderer.rs:443
   const uint64_t first = r->total_frames;  // frame_index of the first frame of this batch = total_frames - 1 after its increment
   r->total_frames += frames;
   if (first >= r->max_frames) return HALA_OK;
   const uint32_t samples = (uint32_t)std::min<uint64_t>(frames, r->max_frames - first);
   if (samples > r->batch_capacity) {
+    if (r->join_tail() != HALA_OK) return HALA_ERR;
     RT_HIP(hipStreamSynchronize(r->stream));
     if (alloc_wavefront(r, samples) != HALA_OK) return HALA_ERR;
   }
@@ -1080,7 +1104,7 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   r->last_uniform = u;
   r->last_uniform.frame_index = (uint32_t)(first + samples - 1);  // what the last frame of the batch would have uploaded
   AdaptiveState& ad = r->adaptive;
-  if (ad.enabled && first == 0 && adaptive_begin(ad, r->stream) != hipSuccess) RT_FAIL("hala_rt_update: the adaptive sampling state could not be reset.");
+  if (ad.enabled && first == 0 && (r->join_tail() != HALA_OK || adaptive_begin(ad, r->stream) != hipSuccess)) RT_FAIL("hala_rt_update: the adaptive sampling state could not be reset.");
   if (ad.enabled && ad.active_blocks == 0) {  // RENDER_SPEC 11: every block has converged; the frames count, nothing is launched
     for (int k = 0; k < kStatRing; ++k) r->resolve_slot(r->ring[(r->ring_pos + k) % kStatRing]);  // done: the last check waited for them
     r->stats.rays_last_update = 0;
@@ -1100,27 +1124,38 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   const SceneView sv = r->view();
   const Queues q = r->queues();
   const PathState ps = r->path_state();
-  Control* ctl = r->d_ctl.ptr;
-  hipStream_t s = r->stream;
-  if (r->scratch_acquire(s) != HALA_OK) return HALA_ERR;
-  RT_HIP(hipEventRecord(te.frame_begin, s));
-  RT_HIP(hipMemsetAsync(ctl, 0, sizeof(Control), s));
+  Control* ctl = r->d_ctl.ptr + r->ctl_pos;
+  r->ctl_pos ^= 1u;
+  const hipStream_t s = r->stream;
   // per-launch HIP events (statistics: traverse_*_ms_total) on every launch_event_period-th update; each record is a barrier
   // packet on the stream, i.e. a few microseconds between two launches
   const bool timed = r->launch_event_period == 1u || (r->launch_event_period > 1u && (r->update_counter % r->launch_event_period) == 0u);
   r->update_counter++;
+  // Untimed updates put their tail on tail_stream (hala_rt_renderer::tail_stream).  Updates that carry per-launch timing events or
+  // counting kernels keep the serial order on one stream, so that every measured launch has the chip to itself.
+  const bool split_tail = !timed && !r->counting;
+  if (!split_tail && r->join_tail() != HALA_OK) return HALA_ERR;
+  // an open tail is the last user of the scratch (external trace_rays calls join it), and it uses none of what this update's
+  // camera-ray launch uses: that launch starts beside it, the depth-0 shade waits for it
+  if (!r->tail_open && r->scratch_acquire(s) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipEventRecord(te.frame_begin, s));
+  RT_HIP(hipMemsetAsync(ctl, 0, sizeof(Control), s));
   // The shadow passes of bounce d and the closest-hit traversal of bounce d + 1 are independent: untimed updates issue them as ONE
   // persistent launch (k_trace_shadow_then_batch: one tail of long rays instead of three).  Updates that carry per-launch timing events or
   // counting kernels keep one launch per pass, so that every measured launch is one kernel symbol with the chip to itself.
   const bool fuse = (r->fuse_mode == 2u || (r->fuse_mode == 1u && !timed)) && !r->counting && (u.num_of_lights > 0 || u.env_type == 1u);
   if (timed && !te.host_sizes) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&te.host_sizes), sizeof(QueueSizes), hipHostMallocDefault));
   bool traced = false;  // the closest-hit pass of this depth already ran inside the previous depth's fused launch
+  hipStream_t ts = s;  // the stream of the shadow launches, then of the tail
+  LaunchCfg lc = r->lcfg;
   for (uint32_t depth = 0; depth < r->max_depth; ++depth) {
     if (timed) { hipEvent_t a = r->next_event(te); RT_HIP(hipEventRecord(a, s)); }
     // depth 0: the camera rays are generated inside the traversal kernel, there is no ray-generation pass
     if (depth == 0) {
       launch_trace_primary(r->lcfg, sv, fc, q.hits, &ctl->work_closest, ctl, primary_pixels * samples, r->counting, s);
       if (r->counting) RT_HIP(hipMemcpyAsync(ctl->totals.primary_steps, ctl->totals.steps[0], 16, hipMemcpyDeviceToDevice, s));
+      // the depth-0 shade resets the paths' radiance the previous tail still adds to, and rewrites the connection queues it reads
+      if (r->join_tail() != HALA_OK) return HALA_ERR;
     }
     else if (!traced) launch_trace_batch(r->lcfg, sv, q.rays[depth & 1u], q.hits, &ctl->sizes.n_active[depth], 0, &ctl->work_closest, ctl, false, r->counting, true, s);
     traced = false;
@@ -1131,28 +1166,37 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
     // other and of the next bounce's closest-hit pass
     const uint32_t kinds = (u.num_of_lights > 0 ? 1u : 0u) | (u.env_type == 1u ? 2u : 0u);
     const bool last = depth + 1u >= r->max_depth;  // no closest-hit pass follows: only worth one launch when there are two shadow passes
-    if (fuse && kinds && (!last || kinds == 3u) && launch_trace_shadow_then_batch(r->lcfg, sv, q, ps, ctl, depth, kinds, !last, s)) {
+    if (last && split_tail) {  // the tail: from here on everything goes to tail_stream, its traversal to the tail's spill area
+      RT_HIP(hipEventRecord(r->ev_shaded, s));
+      RT_HIP(hipStreamWaitEvent(r->tail_stream, r->ev_shaded, 0));
+      ts = r->tail_stream;
+      lc.spill = r->lcfg.spill ? r->d_spill_tail.ptr : nullptr;
+    }
+    if (fuse && kinds && (!last || kinds == 3u) && launch_trace_shadow_then_batch(lc, sv, q, ps, ctl, depth, kinds, !last, ts)) {
       traced = !last;
       if (timed) { te.fused_mask |= 1ull << depth; if (traced) te.traced_mask |= 1ull << (depth + 1u); }
     }
     else
       for (uint32_t kind = 0; kind < 2u; ++kind) {
         if (!((kinds >> kind) & 1u)) continue;
-        launch_trace_shadow(r->lcfg, sv, q, ps, ctl, depth, kind, r->counting, s);
+        launch_trace_shadow(lc, sv, q, ps, ctl, depth, kind, r->counting, ts);
         te.shadow_launches += timed ? 1u : 0u;
       }
     if (timed) { hipEvent_t d = r->next_event(te); RT_HIP(hipEventRecord(d, s)); }
   }
-  launch_resolve(fc, ps, r->img_local[0].ptr, r->img_local[1].ptr, r->img_local[2].ptr, r->img_local[3].ptr, s);
-  RT_HIP(hipMemcpyAsync(te.host_totals, &ctl->totals, sizeof(Totals), hipMemcpyDeviceToHost, s));
-  if (timed) RT_HIP(hipMemcpyAsync(te.host_sizes, &ctl->sizes, sizeof(QueueSizes), hipMemcpyDeviceToHost, s));
-  RT_HIP(hipEventRecord(te.frame_end, s));
-  r->scratch_event = te.frame_end; r->scratch_stream = s;
+  launch_resolve(fc, ps, r->img_local[0].ptr, r->img_local[1].ptr, r->img_local[2].ptr, r->img_local[3].ptr, ts);
+  RT_HIP(hipMemcpyAsync(te.host_totals, &ctl->totals, sizeof(Totals), hipMemcpyDeviceToHost, ts));
+  if (timed) RT_HIP(hipMemcpyAsync(te.host_sizes, &ctl->sizes, sizeof(QueueSizes), hipMemcpyDeviceToHost, ts));
+  // frame_begin -> frame_end spans the whole update, its tail included
+  RT_HIP(hipEventRecord(te.frame_end, ts));
+  r->scratch_event = te.frame_end; r->scratch_stream = ts;
+  r->tail_done = te.frame_end; r->tail_open = ts != s;
   RT_HIP(hipGetLastError());
   te.pending = true;
   for (bool& v : r->full_valid) v = false;
   // RENDER_SPEC 11: hala_rt_update_batch ends its chunks on these frames, so n is the snapshot or check frame itself
   const uint32_t n = (uint32_t)(first + samples);
+  if (ad.enabled && (n == ad.p.min_samples / 2u || adaptive_is_check(ad.p, n)) && r->join_tail() != HALA_OK) return HALA_ERR;  // they read the accumulation
   if (ad.enabled && n == ad.p.min_samples / 2u) {
     RT_HIP(hipMemcpyAsync(ad.snapshot.ptr, r->img_local[0].ptr, ad.snapshot.bytes(), hipMemcpyDeviceToDevice, s));
     ad.last_snapshot = n;
@@ -1180,7 +1224,7 @@ int hala_rt_update_batch(hala_rt_renderer* r, uint32_t frames) {
 }
 
 int hala_rt_render(hala_rt_renderer* r) {  // src/rt_renderer.rs:475-502: nothing to present; make the frame's work visible
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (ensure_device(r, false) != HALA_OK) return HALA_ERR;
   if (r->total_frames > r->max_frames) return HALA_OK;  // :484-486
   // submit_and_present_frame hands the frame to the queue and only blocks on the fence of the swapchain image it reuses: with no
   // swapchain here, render() bounds the updates in flight to two (it waits for the update before the latest), so the host can

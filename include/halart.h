@@ -474,7 +474,10 @@ int hala_rt_sample_texture_host(hala_rt_renderer* r, uint32_t texture, const flo
  * world > 1 is refused while adaptive sampling is on (hala_rt_set_adaptive_sampling). */
 int hala_rt_set_tile_shard(hala_rt_renderer* r, uint32_t rank, uint32_t world, uint32_t tile_size);
 int hala_rt_tile_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_t* bytes);
-/* the hipStream_t every launch of this renderer goes to (for stream-ordered hand-overs: hipStreamWaitEvent both ways) */
+/* the hipStream_t every launch of this renderer goes to (for stream-ordered hand-overs: hipStreamWaitEvent both ways).  Exception: the
+ * tail of an update without per-launch timing (its last shadow launches and the resolve) runs on a second stream beside the next update's
+ * camera-ray launch; every call into the library other than update and render first puts the renderer's stream behind it, this one
+ * included — fetch the stream after the updates a hand-over is to cover. */
 int hala_rt_get_stream(hala_rt_renderer* r, void** hip_stream);
 int hala_rt_scatter_gathered_tiles(hala_rt_renderer* r, int which, const void* d_gathered, size_t bytes);
 
