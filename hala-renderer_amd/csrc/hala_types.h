@@ -201,7 +201,16 @@ constexpr uint32_t kAnyKeyLight = 0xA511E9B3u, kAnyKeyEnv = 0x63D83595u, kAnyKey
 #define RT_PIXEL_BLOCK 8
 #endif
 constexpr uint32_t kPixelBlock = RT_PIXEL_BLOCK;  // 8: 64 pixels per block; 0: row-major slots (A/B)
-// per-update constants derived on the host from HalaGlobalUniform + camera 0 (RENDER_SPEC §5)
+// One view of a multi-view update (RENDER_SPEC §12): the packed camera it renders and that camera's §5 / §7.4 constants.  The table lives
+// in a small device buffer (FrameConst::view_table), so that a lane-varying view index never indexes the by-value kernel argument.
+constexpr uint32_t kMaxViews = HALA_MAX_CAMERA_COUNT;
+struct ViewConst {
+  uint32_t camera;
+  float tan_half, pixel_spread;
+  uint32_t pad;
+};
+static_assert(sizeof(ViewConst) == 16, "view record is 16 B");
+// per-update constants derived on the host from HalaGlobalUniform + the camera of view 0 (RENDER_SPEC §5)
 struct FrameConst {
   hala_global_uniform u;  // the 112-B record itself (src/rt_renderer.rs:408-427)
   float aspect, tan_half;
@@ -215,7 +224,12 @@ struct FrameConst {
   // together; path slot = sample * pixel_slots + pixel slot.  The resolve kernel folds them in frame order, so the
   // result is bit-identical to `samples` single-sample updates.
   uint32_t samples;
-  uint32_t slot_count;  // pixel_slots * samples
+  uint32_t slot_count;  // pixel_slots * samples * views
+  // views (RENDER_SPEC §12): path slot = (sample * views + view) * pixel_slots + pixel slot; the resolve writes view v's images at
+  // v * view_pixels.  views == 1: u.camera_index, tan_half and pixel_spread are view 0's and view_table is never read
+  uint32_t views;
+  uint32_t view_pixels;
+  const ViewConst* view_table;
   // adaptive sampling (RENDER_SPEC §11; world == 1 only): the pixel blocks this update renders, in ascending order — pixel block j of the
   // slot order is block_list[j], and pixel_slots = 64 x their count.  nullptr: every block (the feature is off)
   const uint32_t* block_list;

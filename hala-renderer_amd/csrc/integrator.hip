@@ -220,16 +220,33 @@ struct BatchSource {
 };
 // The camera ray of path slot `slot` (RENDER_SPEC §5) and the RNG state after it; false for the padding slots of a
 // sharded frame.  Primary rays are never stored: the depth-0 traversal and the depth-0 shading both evaluate this.
+// VIEWS (fc.views > 1, RENDER_SPEC §12): slot = (sample * views + view) * pixel_slots + pixel slot; the view picks the camera and its
+// tan_half, the RNG state is the single-view one (keyed by pixel and frame only).  A compile-time flag: the single-view code stays as it
+// was (a run-time merge of the two turned the camera index and tan_half into vector registers and added scratch to the traversal kernels).
+template <bool VIEWS>
 RT_DI bool primary_ray(const FrameConst& fc, const SceneView& sv, uint32_t slot, f3* o, f3* d, uint32_t* rng) {
-  const uint32_t sample = slot / fc.pixel_slots, pslot = slot - sample * fc.pixel_slots;
+  uint32_t sample = slot / fc.pixel_slots;
+  const uint32_t pslot = slot - sample * fc.pixel_slots;
+  uint32_t view = 0;
+  if (VIEWS) { const uint32_t q = sample; sample = q / fc.views; view = q - sample * fc.views; }
   uint32_t px = 0, py = 0;
   *o = splat3(0.0f); *d = mk3(0.0f, 0.0f, 1.0f); *rng = 0u;
   if (!slot_to_pixel(fc, pslot, &px, &py)) return false;
   uint32_t state = rng_init(py * fc.width + px, fc.u.frame_index + sample);
-  camera_ray(fc, sv.cameras[fc.u.camera_index], px, py, state, o, d);
+  if (VIEWS) {
+    const ViewConst vc = fc.view_table[view];
+    camera_ray(fc, sv.cameras[vc.camera], vc.tan_half, px, py, state, o, d);
+  } else camera_ray(fc, sv.cameras[fc.u.camera_index], fc.tan_half, px, py, state, o, d);
   *rng = state;
   return true;
 }
+
+// the texture-LOD spread of the view that path slot `slot` belongs to (RENDER_SPEC §7.4, §12); several views only
+RT_DI float view_pixel_spread(const FrameConst& fc, uint32_t slot) {
+  const uint32_t q = slot / fc.pixel_slots;
+  return fc.view_table[q % fc.views].pixel_spread;
+}
+template <bool VIEWS>
 struct CameraSource {
   struct Payload {};
   const FrameConst& fc;
@@ -239,7 +256,7 @@ struct CameraSource {
   RT_DI bool load(uint32_t i, f3* o, f3* d, float* tmin, float* tmax, uint32_t*, Payload*) const {
     uint32_t rng;
     *tmin = 0.0f; *tmax = kTMax;
-    if (primary_ray(fc, sv, i, o, d, &rng)) return true;
+    if (primary_ray<VIEWS>(fc, sv, i, o, d, &rng)) return true;
     reinterpret_cast<float4*>(hits)[i] = make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(kAbsent));  // padding slot: no ray
     return false;
   }
@@ -315,8 +332,8 @@ k_trace_batch(SceneView sv, const hala_ray* __restrict__ rays, hala_hit* __restr
 }
 
 // K5a at depth 0: the camera rays are generated in the lanes that trace them (RENDER_SPEC §5) — no ray-generation kernel,
-// no primary-ray queue in HBM; entry i of the hit queue belongs to path slot i.  `n_account` = real (non-padding) paths.
-template <bool COUNT, bool STAGED, bool INST>
+// no primary-ray queue in HBM; entry i of the hit queue belongs to path slot i.  `n_account` = real (non-padding) paths.  VIEWS: fc.views > 1.
+template <bool COUNT, bool STAGED, bool INST, bool VIEWS>
 __global__ void __launch_bounds__(kTraverseThreads, STAGED ? kTraverseWavesPerSimdStaged : kTraverseWavesPerSimd)
 k_trace_primary(SceneView sv, FrameConst fc, hala_hit* __restrict__ hits, WorkCounters* __restrict__ work, uint2* __restrict__ spill_base,
                 Control* __restrict__ ctl, uint32_t n_account, uint32_t refill) {
@@ -324,7 +341,7 @@ k_trace_primary(SceneView sv, FrameConst fc, hala_hit* __restrict__ hits, WorkCo
   uint2* spill = spill_base ? spill_base + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * kStackSpill : nullptr;
   StepCounters sc;
   if (blockIdx.x == 0 && threadIdx.x == 0) ctl->totals.rays_closest += n_account;
-  CameraSource src{fc, sv, hits, STAGED && refill == 64u};
+  CameraSource<VIEWS> src{fc, sv, hits, STAGED && refill == 64u};
   persistent_trace<false, COUNT, STAGED, false, INST>(sv, lds, spill, work, fc.slot_count, refill, src, sc);
   if (COUNT) flush_counters(ctl, 0, sc);
 }
@@ -500,7 +517,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
   bool real = active;  // false: padding slot of a sharded frame (depth 0 only; later queues hold real paths only)
   if (PRIMARY && active) {
     slot = i;
-    real = primary_ray(fc, sv, slot, &o, &d, &rng);
+    real = fc.views > 1u ? primary_ray<true>(fc, sv, slot, &o, &d, &rng) : primary_ray<false>(fc, sv, slot, &o, &d, &rng);  // wave-uniform
     if (fc.u.env_type == 1u) ps.radiance_env[slot] = P3{0.0f, 0.0f, 0.0f};
   }
   if (real) {
@@ -549,7 +566,10 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
         ps.normal[slot] = P3{0.0f, 0.0f, 0.0f};
       }
     } else {
-      const Surface sf = make_surface<SIMPLE>(sv, lut, fc.pixel_spread, o, d, hv.x, hv.y, hv.z, hit_prim);
+      // the LOD footprint of the path's own view at every depth (RENDER_SPEC §12); SIMPLE materials have no textures, one view keeps fc's
+      float spread = fc.pixel_spread;
+      if (!SIMPLE && fc.views > 1u) spread = view_pixel_spread(fc, slot);
+      const Surface sf = make_surface<SIMPLE>(sv, lut, spread, o, d, hv.x, hv.y, hv.z, hit_prim);
       if (PRIMARY) {
         ps.albedo[slot] = P3{sf.mat.base.x, sf.mat.base.y, sf.mat.base.z};
         ps.normal[slot] = P3{sf.ns.x, sf.ns.y, sf.ns.z};
@@ -709,22 +729,25 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
 // ---------------------------------------------------------------------------------------------------------
 // resolve: fold this sample into the running means and write the tonemapped final image (RENDER_SPEC §8)
 // ---------------------------------------------------------------------------------------------------------
+// Several views (RENDER_SPEC §12): thread t of views x pixel_slots resolves pixel slot t % pixel_slots of view t / pixel_slots into that
+// view's images (view_pixels float4s apart; view 0's are the renderer's usual images).
 __global__ void __launch_bounds__(256) k_resolve(FrameConst fc, PathState ps, float4* __restrict__ accum, float4* __restrict__ albedo,
                                                   float4* __restrict__ normal, float4* __restrict__ final_img) {
-  const uint32_t pslot = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pslot >= fc.pixel_slots) return;
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t view = t / fc.pixel_slots, pslot = t - view * fc.pixel_slots;
+  if (view >= fc.views) return;
   // padding slots (of a border block, of a padding tile, or outside the frame in a border tile) are never written: they keep the zeros
   // the images were allocated with (RENDER_SPEC §9)
   uint32_t px, py;
   if (!slot_to_pixel(fc, pslot, &px, &py)) return;
   // where the pixel of this slot lives in the images: sharded ranks keep their tile buffers in slot order (RENDER_SPEC §9), an unsharded
   // frame is row-major whatever the slot order
-  const uint32_t at = fc.world <= 1u ? py * fc.width + px : pslot;
+  const size_t at = (fc.world <= 1u ? py * fc.width + px : pslot) + (size_t)view * fc.view_pixels;
   // the running means; a batch that starts an accumulation (frame_index 0) never looks at them (fold_mean)
   float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, n = a;
   if (fc.u.frame_index != 0u) { a = accum[at]; b = albedo[at]; n = normal[at]; }
   for (uint32_t k = 0; k < fc.samples; ++k) {  // the batch's samples, folded in frame order
-    const uint32_t slot = k * fc.pixel_slots + pslot;
+    const uint32_t slot = (k * fc.views + view) * fc.pixel_slots + pslot;
     const P3 lr = ps.radiance[slot];
     f3 L = mk3(lr.x, lr.y, lr.z);
     if (fc.u.env_type == 1u) { const P3 le = ps.radiance_env[slot]; L = L + mk3(le.x, le.y, le.z); }  // RENDER_SPEC §6: L + Le
@@ -844,11 +867,11 @@ void launch_trace_primary(const LaunchCfg& lc, const SceneView& sv, const FrameC
   const TreeForm tree = tree_form(sv);
   // camera rays of neighbouring pixels are about equally long: larger refills (40 idle lanes instead of 24) keep the 8 x 8 pixel blocks together
   const uint32_t refill = tree == TreeForm::Staged ? lc.refill : std::max(lc.refill, 40u);
-  with_flags([&](auto COUNT, auto STAGED, auto INST) {
+  with_flags([&](auto COUNT, auto STAGED, auto INST, auto VIEWS) {
     if constexpr (!(STAGED && INST))
-      hipLaunchKernelGGL((k_trace_primary<COUNT, STAGED, INST>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, fc, hits, work,
+      hipLaunchKernelGGL((k_trace_primary<COUNT, STAGED, INST, VIEWS>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, fc, hits, work,
                          lc.spill, ctl, n_account, refill);
-  }, count, tree == TreeForm::Staged, tree == TreeForm::TwoLevel);
+  }, count, tree == TreeForm::Staged, tree == TreeForm::TwoLevel, fc.views > 1u);
 }
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s) {
   const uint32_t threads = sv.simple_materials ? (uint32_t)kShadeThreads : (uint32_t)kShadeThreadsGeneric;
@@ -864,7 +887,7 @@ void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, co
   }, depth == 0u, sv.simple_materials != 0u, !sv.simple_materials && sv.scatter_media);
 }
 void launch_resolve(const FrameConst& fc, const PathState& ps, float4* accum, float4* albedo, float4* normal, float4* final_img, hipStream_t s) {
-  hipLaunchKernelGGL(k_resolve, dim3(blocks_for(fc.pixel_slots, 256)), dim3(256), 0, s, fc, ps, accum, albedo, normal, final_img);
+  hipLaunchKernelGGL(k_resolve, dim3(blocks_for(fc.pixel_slots * fc.views, 256)), dim3(256), 0, s, fc, ps, accum, albedo, normal, final_img);
 }
 void launch_sample_texture(const SceneView& sv, uint32_t tex, const float* uvl, uint32_t n, float4* out, hipStream_t s) {
   hipLaunchKernelGGL(k_sample_texture, dim3(blocks_for(n, 256)), dim3(256), 0, s, sv, tex, uvl, n, out);

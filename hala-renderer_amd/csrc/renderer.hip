@@ -185,7 +185,13 @@ struct hala_rt_renderer {
   uint32_t blocks_x = 0;        // world == 1: 8 x 8 pixel blocks per row of blocks (hala_types.h: kPixelBlock)
   // pixels of this rank's image buffers: its tile slots when sharded, the row-major frame otherwise (whose path slots may hold padding)
   size_t image_pixels() const { return world <= 1 ? (size_t)width * height : (size_t)slot_count; }
-  uint32_t batch_capacity = 1;  // samples the wavefront buffers can hold in flight (hala_rt_update_batch)
+  uint32_t batch_capacity = 1;  // paths per pixel slot the wavefront buffers can hold in flight: samples x views (hala_rt_update_batch)
+  // views (RENDER_SPEC §12): the packed camera of each; view v's images follow view 0's in img_local, image_pixels() apart
+  std::vector<uint32_t> views{0u};
+  DeviceArray<ViewConst> d_views;  // what the kernels read when views.size() > 1 (rebuilt when a camera's yfov changes)
+  std::vector<ViewConst> views_uploaded;
+  uint32_t view_count() const { return (uint32_t)views.size(); }
+  size_t image_alloc() const { return (size_t)slot_count + (size_t)(view_count() - 1) * image_pixels(); }  // view 0 keeps its slot_count
 
   DeviceArray<float4> img_local[4];  // accum, albedo, normal, final (slot order)
   DeviceArray<float4> img_full[4];   // row-major, only after scatter_gathered_tiles (world > 1)
@@ -296,19 +302,31 @@ struct hala_rt_renderer {
   }
   PathState path_state() const { return PathState{ps_lr.ptr, ps_le.ptr, ps_alb.ptr, ps_nrm.ptr}; }
 
+  // RENDER_SPEC §5 / §7.4 for packed camera `cam`: tan(yfov / 2) and the angular size of one pixel
+  ViewConst view_const(uint32_t cam, float height) const {
+    ViewConst v{};
+    float sn = 0.0f, cs = 1.0f;
+    if (cam < hs.cameras.size()) h_sincos_rad(0.5f * hs.cameras[cam].yfov, &sn, &cs);
+    v.camera = cam;
+    v.tan_half = sn / cs;
+    v.pixel_spread = 2.0f * v.tan_half / height;
+    return v;
+  }
   FrameConst frame_const(const hala_global_uniform& u, uint32_t samples = 1) const {
     FrameConst fc{};
     fc.u = u;
     fc.aspect = u.resolution[0] / u.resolution[1];
-    float sn = 0.0f, cs = 1.0f;
-    if (!hs.cameras.empty()) h_sincos_rad(0.5f * hs.cameras[0].yfov, &sn, &cs);
-    fc.tan_half = sn / cs;
-    fc.pixel_spread = 2.0f * fc.tan_half / u.resolution[1];
+    const ViewConst v0 = view_const(views[0], u.resolution[1]);
+    fc.tan_half = v0.tan_half;
+    fc.pixel_spread = v0.pixel_spread;
+    fc.views = view_count();
+    fc.view_pixels = (uint32_t)image_pixels();
+    fc.view_table = fc.views > 1u ? d_views.ptr : nullptr;
     fc.width = width; fc.height = height;
     fc.tile_size = tile_size; fc.tiles_x = tiles_x; fc.tiles_y = tiles_y; fc.world = world; fc.rank = rank; fc.blocks_x = blocks_x;
     fc.tiles_per_rank = tiles_per_rank; fc.perm_a = perm_a_inv; fc.perm_b = perm_b;
-    fc.pixel_slots = slot_count; fc.samples = samples; fc.slot_count = slot_count * samples;
-    if (adaptive.enabled) {  // RENDER_SPEC 11: slots for the active blocks only
+    fc.pixel_slots = slot_count; fc.samples = samples; fc.slot_count = slot_count * samples * fc.views;
+    if (adaptive.enabled) {  // RENDER_SPEC 11: slots for the active blocks only (one view)
       fc.block_list = adaptive.lists[adaptive.cur].ptr;
       fc.pixel_slots = adaptive.active_blocks * kPixelBlock * kPixelBlock;
       fc.slot_count = fc.pixel_slots * samples;
@@ -431,19 +449,19 @@ void compute_tiling(hala_rt_renderer* r) {
   r->real_pixels = (uint32_t)real;
 }
 
-// wavefront state for `samples` frames in flight (hala_rt_update_batch): everything indexed by path slot
-int alloc_wavefront(hala_rt_renderer* r, uint32_t samples) {
-  const size_t n = (size_t)r->slot_count * samples;
+// wavefront state for `paths` paths per pixel slot in flight (samples x views, hala_rt_update_batch): everything indexed by path slot
+int alloc_wavefront(hala_rt_renderer* r, uint32_t paths) {
+  const size_t n = (size_t)r->slot_count * paths;
   if (n > 0xfffffff0ull) RT_FAIL("The sample batch is too large for 32-bit path slots.");
   RT_HIP(r->ps_lr.resize(n)); RT_HIP(r->ps_le.resize(n)); RT_HIP(r->ps_alb.resize(n)); RT_HIP(r->ps_nrm.resize(n));
   RT_HIP(r->q_rays[0].resize(n)); RT_HIP(r->q_rays[1].resize(n)); RT_HIP(r->q_state[0].resize(n)); RT_HIP(r->q_state[1].resize(n));
   RT_HIP(r->q_hits.resize(n)); RT_HIP(r->q_perm.resize(n)); RT_HIP(r->q_shadow[0].resize(n)); RT_HIP(r->q_shadow[1].resize(n));
-  r->batch_capacity = samples;
+  r->batch_capacity = paths;
   return HALA_OK;
 }
 
 int alloc_frame_buffers(hala_rt_renderer* r) {
-  const size_t n = r->slot_count;
+  const size_t n = r->image_alloc();
   for (auto& i : r->img_local) { RT_HIP(i.resize(n)); RT_HIP(hipMemsetAsync(i.ptr, 0, n * sizeof(float4), r->stream)); }
   if (alloc_wavefront(r, 1) != HALA_OK) return HALA_ERR;
   RT_HIP(r->d_ctl.resize(2));  // updates alternate between the two: a tail still running accounts into its own
@@ -1079,21 +1097,37 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   RtRange range("halart::update");
   if (ensure_device(r, false) != HALA_OK) return HALA_ERR;
   if (!r->committed) RT_FAIL("The pipeline is none!");  // src/rt_renderer.rs:443
+  const uint32_t V = r->view_count();
+  for (uint32_t v = 0; v < V; ++v)  // RENDER_SPEC §12: a scene set or committed after hala_rt_set_views may have fewer cameras
+    if (r->views[v] >= r->hs.cameras.size())
+      RT_FAIL("hala_rt_update: view " + std::to_string(v) + " renders camera " + std::to_string(r->views[v]) + ", but the committed scene has " +
+              std::to_string(r->hs.cameras.size()) + " camera(s) (hala_rt_set_views).");
   const uint64_t first = r->total_frames;  // frame_index of the first frame of this batch = total_frames - 1 after its increment
   r->total_frames += frames;
   if (first >= r->max_frames) return HALA_OK;
   const uint32_t samples = (uint32_t)std::min<uint64_t>(frames, r->max_frames - first);
-  if (samples > r->batch_capacity) {
+  if (samples * V > r->batch_capacity) {
     if (r->join_tail() != HALA_OK) return HALA_ERR;
     RT_HIP(hipStreamSynchronize(r->stream));
-    if (alloc_wavefront(r, samples) != HALA_OK) return HALA_ERR;
+    if (alloc_wavefront(r, samples * V) != HALA_OK) return HALA_ERR;
+  }
+  if (V > 1u) {  // the view table: tan_half / pixel_spread follow the cameras' yfov, which a new scene may change
+    std::vector<ViewConst> table(V);
+    for (uint32_t v = 0; v < V; ++v) table[v] = r->view_const(r->views[v], (float)r->height);
+    if (table.size() != r->views_uploaded.size() || memcmp(table.data(), r->views_uploaded.data(), V * sizeof(ViewConst)) != 0) {
+      if (r->join_tail() != HALA_OK) return HALA_ERR;
+      RT_HIP(hipStreamSynchronize(r->stream));  // no update in flight reads the old table
+      RT_HIP(r->d_views.upload(table.data(), V, r->stream));
+      RT_HIP(hipStreamSynchronize(r->stream));
+      r->views_uploaded = table;
+    }
   }
   hala_global_uniform u{};                                 // :408-427
   memcpy(u.ground_color, r->ground, 16); memcpy(u.sky_color, r->sky, 16);
   u.resolution[0] = (float)r->width; u.resolution[1] = (float)r->height;
   u.max_depth = r->max_depth; u.rr_depth = r->rr_depth;
   u.frame_index = (uint32_t)first;  // == total_frames - 1 for a single-frame update (:414)
-  u.camera_index = 0;
+  u.camera_index = r->views[0];  // RENDER_SPEC §12: view 0's camera (0 unless hala_rt_set_views chose another)
   u.env_type = r->has_env ? 1u : 0u;
   u.env_map_width = r->has_env ? r->env_w : 0; u.env_map_height = r->has_env ? r->env_h : 0;
   u.env_total_sum = r->has_env ? r->env_total_sum : 0.0f;
@@ -1110,7 +1144,7 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
     r->stats.rays_last_update = 0;
     return HALA_OK;
   }
-  const uint32_t primary_pixels = ad.enabled ? ad.active_pixels : r->real_pixels;
+  const uint32_t primary_pixels = (ad.enabled ? ad.active_pixels : r->real_pixels) * V;  // camera rays per frame, all views
 
   TraceEvents& te = r->ring[r->ring_pos];
   r->ring_pos = (r->ring_pos + 1) % kStatRing;
@@ -1213,8 +1247,10 @@ int hala_rt_update(hala_rt_renderer* r, double, uint32_t, uint32_t) { return upd
 
 int hala_rt_update_batch(hala_rt_renderer* r, uint32_t frames) {
   if (!r) RT_FAIL("The renderer handle is null!");
+  // several views multiply the paths per pixel slot: a chunk keeps them at kMaxSampleBatch at most (RENDER_SPEC §12)
+  const uint32_t max_chunk = std::max(1u, kMaxSampleBatch / r->view_count());
   while (frames > 0) {
-    uint32_t chunk = std::min(frames, kMaxSampleBatch);
+    uint32_t chunk = std::min(frames, max_chunk);
     if (r->adaptive.enabled && r->total_frames < r->max_frames)  // a chunk ends on the next snapshot or check frame (RENDER_SPEC 11)
       chunk = (uint32_t)std::min<uint64_t>(chunk, adaptive_frames_to_event(r->adaptive.p, r->total_frames));
     if (update_impl(r, chunk) != HALA_OK) return HALA_ERR;
@@ -1248,6 +1284,53 @@ int hala_rt_read_image(hala_rt_renderer* r, int which, float* dst) {
   if (r->world <= 1) { RT_HIP(hipMemcpy(dst, r->img_local[which].ptr, bytes, hipMemcpyDeviceToHost)); return HALA_OK; }
   if (!r->full_valid[which]) RT_FAIL("The frame is sharded across ranks: gather the tiles (hala_rt_scatter_gathered_tiles) before reading the image.");
   RT_HIP(hipMemcpy(dst, r->img_full[which].ptr, bytes, hipMemcpyDeviceToHost));
+  return HALA_OK;
+}
+
+int hala_rt_read_view_image(hala_rt_renderer* r, uint32_t view, int which, float* dst) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (view >= r->view_count()) RT_FAIL("The view does not exist (hala_rt_set_views set " + std::to_string(r->view_count()) + ").");
+  if (view == 0u) return hala_rt_read_image(r, which, dst);
+  if (which < 0 || which > 3 || !dst) RT_FAIL("Invalid image selector.");
+  RT_HIP(hipStreamSynchronize(r->stream));
+  const size_t px = r->image_pixels();  // several views: never sharded, the row-major frame
+  RT_HIP(hipMemcpy(dst, r->img_local[which].ptr + view * px, px * sizeof(float4), hipMemcpyDeviceToHost));
+  return HALA_OK;
+}
+
+// ---- views (RENDER_SPEC 12) ---------------------------------------------------------------------------------------------
+int hala_rt_set_views(hala_rt_renderer* r, const uint32_t* camera_indices, uint32_t count) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (!camera_indices) RT_FAIL("hala_rt_set_views: the camera list is null.");
+  if (count == 0 || count > kMaxViews) RT_FAIL("hala_rt_set_views: the view count must be in 1.." + std::to_string(kMaxViews) + ".");
+  for (uint32_t v = 0; v < count; ++v)
+    if (camera_indices[v] >= HALA_MAX_CAMERA_COUNT)
+      RT_FAIL("hala_rt_set_views: camera index " + std::to_string(camera_indices[v]) + " is out of range (< " + std::to_string(HALA_MAX_CAMERA_COUNT) + ").");
+  if (count > 1u && r->world > 1u) RT_FAIL("hala_rt_set_views: several views are not available on a sharded renderer (world > 1).");
+  if (count > 1u && r->adaptive.enabled) RT_FAIL("hala_rt_set_views: several views are not available with adaptive sampling on.");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins an open tail
+  RT_HIP(hipStreamSynchronize(r->stream));
+  const size_t old_n = r->image_alloc();
+  std::vector<uint32_t> old_views = r->views;
+  r->views.assign(camera_indices, camera_indices + count);
+  const size_t n = r->image_alloc();
+  // the images hold V views now: view 0 (and every view both lists have) keeps its pixels, new views start at zero.  Buffers only
+  // ever grow, so that a failure half-way leaves every one large enough for either list.
+  const size_t keep = std::min(old_n, n);
+  for (auto& img : r->img_local) {
+    hipError_t e = hipSuccess;
+    if (img.count < n) {
+      DeviceArray<float4> grown;
+      e = grown.resize(n);
+      if (e == hipSuccess) e = hipMemcpyAsync(grown.ptr, img.ptr, keep * sizeof(float4), hipMemcpyDeviceToDevice, r->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+      if (e == hipSuccess) { std::swap(img.ptr, grown.ptr); std::swap(img.count, grown.count); }
+    }
+    if (e == hipSuccess && n > keep) e = hipMemsetAsync(img.ptr + keep, 0, (n - keep) * sizeof(float4), r->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    if (e != hipSuccess) { r->views = old_views; RT_HIP(e); }
+  }
+  r->reset_accumulation();
   return HALA_OK;
 }
 
@@ -1301,6 +1384,7 @@ int hala_rt_set_adaptive_sampling(hala_rt_renderer* r, const hala_adaptive_param
   if (p) {
     if (kPixelBlock != 8u) RT_FAIL("Adaptive sampling needs the 8 x 8 pixel blocks of RENDER_SPEC 9 (this build has RT_PIXEL_BLOCK = " + std::to_string(kPixelBlock) + ").");
     if (r->world > 1) RT_FAIL("Adaptive sampling is not available on a sharded renderer (world > 1).");
+    if (r->view_count() > 1u) RT_FAIL("Adaptive sampling is not available with several views (hala_rt_set_views with one camera first).");
     if (!ad.enabled) {
       RT_HIP(hipStreamSynchronize(r->stream));
       const uint32_t blocks = r->blocks_x * ((r->height + kPixelBlock - 1) / kPixelBlock);
@@ -1528,6 +1612,7 @@ int hala_rt_set_tile_shard(hala_rt_renderer* r, uint32_t rank, uint32_t world, u
   if (world == 0 || rank >= world) RT_FAIL("Invalid rank / world size.");
   if (tile_size == 0 || tile_size > 256) RT_FAIL("Invalid tile size.");
   if (world > 1 && r->adaptive.enabled) RT_FAIL("Adaptive sampling is on: a sharded frame cannot use it (hala_rt_set_adaptive_sampling(r, NULL) first).");
+  if (world > 1 && r->view_count() > 1u) RT_FAIL("The renderer has several views: a sharded frame renders one (hala_rt_set_views with one camera first).");
   // a collective in flight belongs to the old shard: complete it (its receive buffer is laid out for the old world size)
   if (r->gather_pending && hala_rt_tile_allgather_finish(r) != HALA_OK) return HALA_ERR;
   // a communicator is bound to (rank, world): gather_recv is sized by it and the de-interleave indexes it by the shard's world

@@ -52,7 +52,8 @@ RT_DI bool slot_to_pixel(const FrameConst& fc, uint32_t slot, uint32_t* px, uint
 }
 
 // ---- §5 camera ---------------------------------------------------------------------------------------------
-RT_DI void camera_ray(const FrameConst& fc, const hala_gpu_camera& cam, uint32_t px, uint32_t py, uint32_t& rng, f3* o, f3* d) {
+// tan_half: the camera's own tan(yfov / 2) (fc.tan_half for a single view, the view table's entry otherwise: RENDER_SPEC §12)
+RT_DI void camera_ray(const FrameConst& fc, const hala_gpu_camera& cam, float tan_half, uint32_t px, uint32_t py, uint32_t& rng, f3* o, f3* d) {
   float r1 = rng_next(rng), r2 = rng_next(rng), r3 = rng_next(rng), r4 = rng_next(rng);
   float fx = ((float)px + r1) / fc.u.resolution[0];
   float fy = ((float)py + r2) / fc.u.resolution[1];
@@ -60,8 +61,8 @@ RT_DI void camera_ray(const FrameConst& fc, const hala_gpu_camera& cam, uint32_t
   float ndc_y = 1.0f - fy * 2.0f;
   f3 pos = ld3(cam.position), right = ld3(cam.right), up = ld3(cam.up), fwd = ld3(cam.forward);
   if (cam.type == 0u) {
-    float dx = ndc_x * fc.aspect * fc.tan_half;
-    float dy = ndc_y * fc.tan_half;
+    float dx = ndc_x * fc.aspect * tan_half;
+    float dy = ndc_y * tan_half;
     f3 dir = normalize3(madd3(up, dy, madd3(right, dx, fwd)));
     float aperture = cam.aperture_or_ymag;
     if (aperture > 0.0f) {

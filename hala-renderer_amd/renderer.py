@@ -180,10 +180,23 @@ class HalaRenderer:
     # -- read-back used by tests and bench (what save_images downloads, :1239-1254) -------------------------------
     ACCUM, ALBEDO, NORMAL, FINAL = 0, 1, 2, 3
 
-    def read_image(self, which=0) -> np.ndarray:
+    def read_image(self, which=0, view=0) -> np.ndarray:
+        """one of the four images of `view` (an index into the list set_views gave; 0: the only view by default)"""
         out = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._check(self._lib.hala_rt_read_image(self._h, C.c_int(which), out.ctypes.data_as(C.POINTER(C.c_float))))
+        dst = out.ctypes.data_as(C.POINTER(C.c_float))
+        if view == 0:
+            self._check(self._lib.hala_rt_read_image(self._h, C.c_int(which), dst))
+        else:
+            self._check(self._lib.hala_rt_read_view_image(self._h, C.c_uint32(view), C.c_int(which), dst))
         return out
+
+    # -- views (docs/RENDER_SPEC.md 12; include/halart.h "hala_rt_set_views") ---------------------------------------
+    def set_views(self, cameras):
+        """render every camera index in `cameras` (1..8 entries, each < 8; duplicates allowed) in each update; view v of read_image
+        is cameras[v].  [0] is the default.  Restarts the accumulation."""
+        idx = [int(c) for c in cameras]
+        arr = (C.c_uint32 * max(len(idx), 1))(*idx)
+        self._check(self._lib.hala_rt_set_views(self._h, arr, C.c_uint32(len(idx))))
 
     # -- denoising (docs/RENDER_SPEC.md 10; include/halart.h "hala_rt_denoise") -----------------------------------
     def denoise(self, iterations=None, sigma_color=None, sigma_albedo=None, normal_power=None, demodulate=True, timed=False):

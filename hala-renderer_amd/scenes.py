@@ -8,7 +8,7 @@ import math
 import numpy as np
 
 from . import _abi as A
-from .scene import (HalaLight, HalaLightType, HalaMaterial, HalaMaterialType, HalaMesh, HalaNode,
+from .scene import (HalaLight, HalaLightType, HalaMaterial, HalaMaterialType, HalaMesh, HalaNode, HalaOrthographicCamera,
                     HalaPerspectiveCamera, HalaPrimitive, HalaScene)
 
 
@@ -48,6 +48,78 @@ def look_at_node_transform(eye, target, up=(0.0, 1.0, 0.0)):
     m = np.eye(4)
     m[:3, 0] = r; m[:3, 1] = u; m[:3, 2] = -f; m[:3, 3] = eye
     return m.astype(np.float32)
+
+
+def _node_world(scene, index):
+    m = np.eye(4)
+    while index is not None:
+        nd = scene.nodes[index]
+        m = np.asarray(nd.local_transform, dtype=np.float64) @ m
+        index = nd.parent
+    return m
+
+
+def with_extra_cameras(scene: HalaScene, count=7, orbit_deg=9.0) -> HalaScene:
+    """A copy of `scene` with `count` cameras (1..7) after its camera 0, for multi-view renders (docs/RENDER_SPEC.md 12): camera 1 is a
+    thin lens focused on the point camera 0 looks at, camera 2 orthographic, the rest perspective with their own yfov.  Each stands on a
+    circle around that point (the centre of the scene's instances, projected onto camera 0's view axis) a few degrees away from camera 0,
+    and looks at it.  Meshes, materials and lights are shared with `scene`."""
+    if not 1 <= count <= A.MAX_CAMERA_COUNT - 1:
+        raise ValueError("count must be in 1..7")
+    cam0 = scene.cameras[0]
+    node0 = next(i for i, nd in enumerate(scene.nodes) if nd.camera_index == 0)
+    w0 = _node_world(scene, node0)
+    eye, fwd = w0[:3, 3], -w0[:3, 2] / np.linalg.norm(w0[:3, 2])
+    centres = []
+    for i, nd in enumerate(scene.nodes):
+        if nd.mesh_index == A.INVALID_INDEX:
+            continue
+        w = _node_world(scene, i)
+        for p in scene.meshes[nd.mesh_index].primitives:
+            pos = p.vertices["position"].astype(np.float64)
+            c = 0.5 * (pos.min(axis=0) + pos.max(axis=0))
+            centres.append(w[:3, :3] @ c + w[:3, 3])
+    dist = max(float(np.dot(np.mean(centres, axis=0) - eye, fwd)), 1e-3)
+    target = eye + fwd * dist
+    yfov0 = cam0.yfov if isinstance(cam0, HalaPerspectiveCamera) else math.radians(45.0)
+    aspect = cam0.aspect if isinstance(cam0, HalaPerspectiveCamera) else 1.0
+    out = HalaScene(nodes=list(scene.nodes), meshes=scene.meshes, materials=scene.materials,
+                    texture2image_mapping=scene.texture2image_mapping, image2data_mapping=scene.image2data_mapping,
+                    image_data=scene.image_data, lights=scene.lights, cameras=list(scene.cameras[:1]))
+    for j in range(1, count + 1):
+        side = 1.0 if j % 2 else -1.0
+        ang = math.radians(orbit_deg) * ((j + 1) // 2) * side
+        rad = dist * (1.0 - 0.08 * ((j - 1) % 3))
+        c, sn = math.cos(ang), math.sin(ang)
+        off = -fwd * rad
+        rot = np.array([[c, 0.0, sn], [0.0, 1.0, 0.0], [-sn, 0.0, c]])  # about the world's up axis
+        pos = target + rot @ off + np.array([0.0, 0.04 * dist * ((j % 3) - 1), 0.0])
+        out.nodes.append(HalaNode(name=f"camera_{j}", camera_index=j, local_transform=look_at_node_transform(pos, target)))
+        if j == 1:
+            out.cameras.append(HalaPerspectiveCamera(aspect=aspect, yfov=yfov0, znear=cam0.znear if hasattr(cam0, "znear") else 0.1,
+                                                     focal_distance=rad, aperture=0.02 * rad))
+        elif j == 2:
+            ymag = rad * math.tan(0.5 * yfov0)
+            out.cameras.append(HalaOrthographicCamera(xmag=ymag * aspect, ymag=ymag))
+        else:
+            out.cameras.append(HalaPerspectiveCamera(aspect=aspect, yfov=yfov0 * (0.6 + 0.15 * (j - 3)), znear=0.1))
+    return out
+
+
+def swap_cameras(scene: HalaScene, k) -> HalaScene:
+    """A copy of `scene` whose camera 0 is `scene`'s camera k and whose camera k is its camera 0 (the nodes that carry them swap their
+    camera_index too): what a single-view render of camera k equals (docs/RENDER_SPEC.md 12)."""
+    cams = list(scene.cameras)
+    cams[0], cams[k] = cams[k], cams[0]
+    nodes = []
+    for nd in scene.nodes:
+        ci = nd.camera_index
+        if ci in (0, k):
+            nd = HalaNode(name=nd.name, parent=nd.parent, local_transform=nd.local_transform, mesh_index=nd.mesh_index,
+                          camera_index=k if ci == 0 else 0, light_index=nd.light_index)
+        nodes.append(nd)
+    return HalaScene(nodes=nodes, meshes=scene.meshes, materials=scene.materials, texture2image_mapping=scene.texture2image_mapping,
+                     image2data_mapping=scene.image2data_mapping, image_data=scene.image_data, lights=scene.lights, cameras=cams)
 
 
 # ---------------------------------------------------------------------------------------------------------

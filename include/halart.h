@@ -374,6 +374,21 @@ int hala_rt_save_images(hala_rt_renderer* r, const char* path);
  * (RGBA32F, 4*W*H floats, row 0 = top), 3 final (tonemapped RGBA32F the raygen stage writes, :688). */
 int hala_rt_read_image(hala_rt_renderer* r, int which, float* dst_rgba32f);
 
+/* Views (docs/RENDER_SPEC.md 12; no reference equivalent — the reference always renders camera 0, src/rt_renderer.rs:415).  Every
+ * update renders one sample per pixel for each of `count` (1..8) views; view v uses packed camera camera_indices[v] (< 8; duplicates
+ * render identical views) with that camera's own yfov.  The default is one view of camera 0.  The RNG is keyed by pixel and frame only,
+ * so view v equals a single-view render of its camera bit for bit and the noise of the views is correlated.  Refused, with the renderer
+ * left as it was: a null list, count 0 or > 8, an index >= 8, and count > 1 on a sharded renderer (world > 1) or with adaptive sampling
+ * on (hala_rt_set_tile_shard and hala_rt_set_adaptive_sampling refuse the other order).  A successful call joins the tail of the last
+ * update, sizes the images for count views (new views start at zero) and restarts the accumulation like hala_rt_commit.  An update
+ * whose views name a camera the committed scene does not have fails before any device work.  Chunks of hala_rt_update_batch hold at
+ * most 16 / count frames; statistics count every view (rays_primary_total grows by W*H*count per frame); camera_index of
+ * hala_rt_get_global_uniform is view 0's camera.  read_image, save_images, hala_rt_denoise and the tile entry points act on view 0. */
+int hala_rt_set_views(hala_rt_renderer* r, const uint32_t* camera_indices, uint32_t count);
+/* read_image for view `view` (< count of hala_rt_set_views): waits like hala_rt_read_image.  Another view's PFMs or denoised image come
+ * from hala_write_pfm and hala_denoise_images on what this returns. */
+int hala_rt_read_view_image(hala_rt_renderer* r, uint32_t view, int which, float* dst_rgba32f);
+
 /* info()/statistics() (src/renderer.rs:212-218, :135-207) */
 typedef struct hala_rt_info {
   uint32_t width;
@@ -471,7 +486,8 @@ int hala_rt_sample_texture_host(hala_rt_renderer* r, uint32_t texture, const flo
  * hala_rt_scatter_gathered_tiles de-interleaves the gathered [world][tiles_per_rank][ts*ts][4] buffer (inside a tile the pixels
  * come in 8 x 8 blocks when ts is a multiple of 8: docs/RENDER_SPEC.md 9) into the row-major images of this renderer.  The renderer works on its own HIP stream: wait (hala_rt_wait_idle, or a stream
  * dependency on hala_rt_get_stream) before another stream reads the tile buffer — hala_rt_render does not flush.
- * world > 1 is refused while adaptive sampling is on (hala_rt_set_adaptive_sampling). */
+ * world > 1 is refused while adaptive sampling is on (hala_rt_set_adaptive_sampling) or while the renderer has several views
+ * (hala_rt_set_views). */
 int hala_rt_set_tile_shard(hala_rt_renderer* r, uint32_t rank, uint32_t world, uint32_t tile_size);
 int hala_rt_tile_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_t* bytes);
 /* the hipStream_t every launch of this renderer goes to (for stream-ordered hand-overs: hipStreamWaitEvent both ways).  Exception: the
@@ -649,7 +665,8 @@ typedef struct hala_adaptive_params {
 /* the defaults (DESIGN.md "Adaptive sampling" records the measurements behind them) */
 void hala_adaptive_default_params(hala_adaptive_params* out);
 /* p: enable with these parameters; NULL: off.  Either way the accumulation restarts.  Refused, with the renderer left as it was:
- * invalid parameters (checked before the handle is looked at), a sharded renderer (world > 1), a build with another pixel block size.
+ * invalid parameters (checked before the handle is looked at), a sharded renderer (world > 1), a renderer with several views
+ * (hala_rt_set_views), a build with another pixel block size.
  * The first call that enables allocates the snapshot image and the block lists.  An update that ends on a check frame
  * (n = min_samples + j * interval) waits for the check and reads two counts back; every other update stays asynchronous. */
 int hala_rt_set_adaptive_sampling(hala_rt_renderer* r, const hala_adaptive_params* p);
