@@ -192,7 +192,7 @@ class AdaptiveStatus(C.Structure):  # hala_adaptive_status, 32 B
                 ("samples", C.c_uint32), ("last_snapshot", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
-# argtypes / restype of the denoise, adaptive sampling and view entry points (load_library installs them)
+# argtypes / restype of the denoise, adaptive sampling, view and AOV entry points (load_library installs them)
 PROTOTYPES = {
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
     "hala_rt_denoise": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
@@ -207,6 +207,7 @@ PROTOTYPES = {
     "hala_rt_get_adaptive_status": ([C.c_void_p, C.POINTER(AdaptiveStatus)], C.c_int),
     "hala_rt_set_views": ([C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32], C.c_int),
     "hala_rt_read_view_image": ([C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_set_aovs": ([C.c_void_p, C.c_uint32], C.c_int),
 }
 
 
@@ -243,5 +244,5 @@ EXPORTS = [
     "hala_denoise_default_params", "hala_rt_denoise", "hala_rt_read_denoised", "hala_rt_get_denoised_buffer", "hala_rt_save_denoised",
     "hala_denoise_images",
     "hala_adaptive_default_params", "hala_rt_set_adaptive_sampling", "hala_rt_read_sample_counts", "hala_rt_get_adaptive_status",
-    "hala_rt_set_views", "hala_rt_read_view_image",
+    "hala_rt_set_views", "hala_rt_read_view_image", "hala_rt_set_aovs",
 ]

@@ -289,6 +289,12 @@ struct PathState {
                            // passes of a bounce then never touch the same word and may share a launch)
   P3* albedo;              // first-hit AOVs of this sample
   P3* normal;
+  // first-hit position and ids of this sample (RENDER_SPEC §13; nullptr: that AOV is off): (P, hit) and (node, instance, material, id).
+  // Written by the AOV variant of the depth-0 shade only, which also reads the two node tables (per instance, per light)
+  float4* aov_pos;
+  uint4* aov_ids;
+  const uint32_t* inst_node;
+  const uint32_t* light_node;
 };
 
 struct ShadowEntry {  // 48 B: one NEE connection = shadow ray + the contribution it carries if unoccluded

@@ -183,8 +183,9 @@ std::string HostScene::pack() {
     cameras.push_back(g);
   }
   // ---- lights: gpu_uploader.rs:148-293 (iterates nodes; order = node order) -------------------------------
-  lights.clear(); light_aabbs.clear();
-  for (const auto& node : nodes) {
+  lights.clear(); light_aabbs.clear(); light_node.clear();
+  for (size_t k = 0; k < nodes.size(); ++k) {
+    const HostNode& node = nodes[k];
     if (node.light_index == HALA_INVALID_INDEX) continue;
     const hala_light_desc& l = lights_cpu[node.light_index];
     const float* X = node.world.m; const float* Y = X + 4; const float* Z = X + 8; const float* P = X + 12;
@@ -229,6 +230,7 @@ std::string HostScene::pack() {
     for (int i = 0; i < 3; ++i) { sorted.min[i] = std::min(bb.min[i], bb.max[i]); sorted.max[i] = std::max(bb.min[i], bb.max[i]); }
     lights.push_back(g);
     light_aabbs.push_back(sorted);
+    light_node.push_back((uint32_t)k);
     if (lights.size() >= HALA_MAX_LIGHT_COUNT) break;
   }
   // ---- materials: gpu_uploader.rs:306-331 ---------------------------------------------------------------------

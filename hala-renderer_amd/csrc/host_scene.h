@@ -55,6 +55,7 @@ struct HostScene {
   std::vector<hala_gpu_camera> cameras;
   std::vector<hala_gpu_light> lights;
   std::vector<hala_aabb> light_aabbs;
+  std::vector<uint32_t> light_node;  // per packed light: the node it came from (RENDER_SPEC §13 ids)
   std::vector<hala_gpu_material> gpu_materials;
   std::vector<hala_gpu_mesh_data> instances;  // `primitives` of gpu_uploader.rs:843-871 (addresses filled at upload)
   std::vector<float> instance_3x4;            // VkAccelerationStructureInstanceKHR transforms (:854-858)

@@ -472,7 +472,13 @@ __global__ void __launch_bounds__(kSortThreads) k_shade_sort(Queues q, const Con
   }
 }
 
-template <bool PRIMARY, bool SIMPLE, bool SCATTER>
+// AOV (PRIMARY only): the first-hit position / id AOVs of RENDER_SPEC §13 are on — this sample's (P, hit) and ids go to ps.aov_pos /
+// ps.aov_ids (each may be null).  A compile-time flag, like k_trace_primary's VIEWS: the variants without it compile exactly as before.
+RT_DI void first_hit_aovs(const PathState& ps, uint32_t slot, float4 pos, uint4 ids) {
+  if (ps.aov_pos) ps.aov_pos[slot] = pos;
+  if (ps.aov_ids) ps.aov_ids[slot] = ids;
+}
+template <bool PRIMARY, bool SIMPLE, bool SCATTER, bool AOV>
 __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric, SIMPLE ? RT_SHADE_WAVES_SIMPLE : RT_SHADE_WAVES) k_shade(FrameConst fc, SceneView sv, Queues q, PathState ps, Control* __restrict__ ctl, uint32_t depth) {
   __shared__ BlockCompact s_compact;
   const uint32_t n = PRIMARY ? fc.slot_count : ctl->sizes.n_active[depth];
@@ -552,6 +558,10 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
       if (PRIMARY) {
         ps.albedo[slot] = P3{minf(le.x, 1.0f), minf(le.y, 1.0f), minf(le.z, 1.0f)};
         ps.normal[slot] = P3{0.0f, 0.0f, 0.0f};
+        if (AOV) {
+          const f3 P = madd3(d, t_light, o);
+          first_hit_aovs(ps, slot, make_float4(P.x, P.y, P.z, 1.0f), make_uint4(ps.light_node[hit_light], kAbsent, kAbsent, 0x80000000u | (uint32_t)hit_light));
+        }
       }
     } else if (hit_prim == kAbsent) {
       f3 env;
@@ -564,6 +574,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
       if (PRIMARY) {
         ps.albedo[slot] = P3{minf(env.x, 1.0f), minf(env.y, 1.0f), minf(env.z, 1.0f)};
         ps.normal[slot] = P3{0.0f, 0.0f, 0.0f};
+        if (AOV) first_hit_aovs(ps, slot, make_float4(0.0f, 0.0f, 0.0f, 0.0f), make_uint4(kAbsent, kAbsent, kAbsent, kAbsent));
       }
     } else {
       // the LOD footprint of the path's own view at every depth (RENDER_SPEC §12); SIMPLE materials have no textures, one view keeps fc's
@@ -573,6 +584,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
       if (PRIMARY) {
         ps.albedo[slot] = P3{sf.mat.base.x, sf.mat.base.y, sf.mat.base.z};
         ps.normal[slot] = P3{sf.ns.x, sf.ns.y, sf.ns.z};
+        if (AOV) first_hit_aovs(ps, slot, make_float4(sf.P.x, sf.P.y, sf.P.z, 1.0f), make_uint4(ps.inst_node[sf.inst], sf.inst, sf.material, hit_prim));
       }
       // §7.1e: what the medium of an object just crossed did to the segment that ends here (identity for every other hit)
       if (sf.glow.x > 0.0f || sf.glow.y > 0.0f || sf.glow.z > 0.0f) {
@@ -731,8 +743,12 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
 // ---------------------------------------------------------------------------------------------------------
 // Several views (RENDER_SPEC §12): thread t of views x pixel_slots resolves pixel slot t % pixel_slots of view t / pixel_slots into that
 // view's images (view_pixels float4s apart; view 0's are the renderer's usual images).
+// AOV (RENDER_SPEC §13): `pos` (may be null) folds (P, hit) like the other means; `ids` (may be null) takes the ids of the sample of frame 0
+// of the accumulation and keeps them after that.  The variant without the flag never looks at the two images.
+template <bool AOV>
 __global__ void __launch_bounds__(256) k_resolve(FrameConst fc, PathState ps, float4* __restrict__ accum, float4* __restrict__ albedo,
-                                                  float4* __restrict__ normal, float4* __restrict__ final_img) {
+                                                  float4* __restrict__ normal, float4* __restrict__ final_img, float4* __restrict__ pos,
+                                                  uint4* __restrict__ ids) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t view = t / fc.pixel_slots, pslot = t - view * fc.pixel_slots;
   if (view >= fc.views) return;
@@ -746,6 +762,9 @@ __global__ void __launch_bounds__(256) k_resolve(FrameConst fc, PathState ps, fl
   // the running means; a batch that starts an accumulation (frame_index 0) never looks at them (fold_mean)
   float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, n = a;
   if (fc.u.frame_index != 0u) { a = accum[at]; b = albedo[at]; n = normal[at]; }
+  float4 p = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  uint4 id = make_uint4(kAbsent, kAbsent, kAbsent, kAbsent);
+  if (AOV && pos && fc.u.frame_index != 0u) p = pos[at];
   for (uint32_t k = 0; k < fc.samples; ++k) {  // the batch's samples, folded in frame order
     const uint32_t slot = (k * fc.views + view) * fc.pixel_slots + pslot;
     const P3 lr = ps.radiance[slot];
@@ -757,8 +776,15 @@ __global__ void __launch_bounds__(256) k_resolve(FrameConst fc, PathState ps, fl
     a = make_float4(fold_mean(a.x, L.x, fi), fold_mean(a.y, L.y, fi), fold_mean(a.z, L.z, fi), 1.0f);
     b = make_float4(fold_mean(b.x, sa.x, fi), fold_mean(b.y, sa.y, fi), fold_mean(b.z, sa.z, fi), 1.0f);
     n = make_float4(fold_mean(n.x, sn.x, fi), fold_mean(n.y, sn.y, fi), fold_mean(n.z, sn.z, fi), 1.0f);
+    if (AOV && pos) {
+      const float4 sp = ps.aov_pos[slot];
+      p = make_float4(fold_mean(p.x, sp.x, fi), fold_mean(p.y, sp.y, fi), fold_mean(p.z, sp.z, fi), fold_mean(p.w, sp.w, fi));
+    }
+    if (AOV && ids && fi == 0u) id = ps.aov_ids[slot];
   }
   accum[at] = a; albedo[at] = b; normal[at] = n;
+  if (AOV && pos) pos[at] = p;
+  if (AOV && ids && fc.u.frame_index == 0u) ids[at] = id;
   const f3 c = tonemap_select(mk3(a.x, a.y, a.z) * fc.u.exposure_value, fc.u.enable_tonemap, fc.u.enable_aces, fc.u.use_simple_aces);
   final_img[at] = make_float4(c.x, c.y, c.z, 1.0f);
 }
@@ -882,12 +908,16 @@ void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, co
     const uint32_t group = 8u * (kSortWindow / threads);  // whole groups of 8 windows: k_shade's window -> XCD mapping permutes the blocks of a group
     grid.x = blocks_for(grid.x, group) * group;
   }
-  with_flags([&](auto PRIMARY, auto SIMPLE, auto SCATTER) {
-    if constexpr (!(SIMPLE && SCATTER)) hipLaunchKernelGGL((k_shade<PRIMARY, SIMPLE, SCATTER>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
-  }, depth == 0u, sv.simple_materials != 0u, !sv.simple_materials && sv.scatter_media);
+  // the first-hit AOVs (RENDER_SPEC §13) are written by the depth-0 shade only
+  with_flags([&](auto PRIMARY, auto SIMPLE, auto SCATTER, auto AOV) {
+    if constexpr (!(SIMPLE && SCATTER) && (PRIMARY || !AOV)) hipLaunchKernelGGL((k_shade<PRIMARY, SIMPLE, SCATTER, AOV>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
+  }, depth == 0u, sv.simple_materials != 0u, !sv.simple_materials && sv.scatter_media, depth == 0u && (ps.aov_pos || ps.aov_ids));
 }
-void launch_resolve(const FrameConst& fc, const PathState& ps, float4* accum, float4* albedo, float4* normal, float4* final_img, hipStream_t s) {
-  hipLaunchKernelGGL(k_resolve, dim3(blocks_for(fc.pixel_slots * fc.views, 256)), dim3(256), 0, s, fc, ps, accum, albedo, normal, final_img);
+void launch_resolve(const FrameConst& fc, const PathState& ps, float4* accum, float4* albedo, float4* normal, float4* final_img, float4* pos,
+                    uint4* ids, hipStream_t s) {
+  with_flags([&](auto AOV) {
+    hipLaunchKernelGGL((k_resolve<AOV>), dim3(blocks_for(fc.pixel_slots * fc.views, 256)), dim3(256), 0, s, fc, ps, accum, albedo, normal, final_img, pos, ids);
+  }, pos != nullptr || ids != nullptr);
 }
 void launch_sample_texture(const SceneView& sv, uint32_t tex, const float* uvl, uint32_t n, float4* out, hipStream_t s) {
   hipLaunchKernelGGL(k_sample_texture, dim3(blocks_for(n, 256)), dim3(256), 0, s, sv, tex, uvl, n, out);

@@ -193,9 +193,15 @@ struct hala_rt_renderer {
   uint32_t view_count() const { return (uint32_t)views.size(); }
   size_t image_alloc() const { return (size_t)slot_count + (size_t)(view_count() - 1) * image_pixels(); }  // view 0 keeps its slot_count
 
-  DeviceArray<float4> img_local[4];  // accum, albedo, normal, final (slot order)
-  DeviceArray<float4> img_full[4];   // row-major, only after scatter_gathered_tiles (world > 1)
-  bool full_valid[4] = {false, false, false, false};
+  DeviceArray<float4> img_local[6];  // accum, albedo, normal, final, position, ids (slot order); 4 and 5 only while that AOV is on
+  DeviceArray<float4> img_full[6];   // row-major, only after scatter_gathered_tiles (world > 1)
+  bool full_valid[6] = {false, false, false, false, false, false};
+  // first-hit AOVs (RENDER_SPEC §13): bit 0 position (image 4), bit 1 ids (image 5); hala_rt_set_aovs
+  uint32_t aov_mask = 0;
+  bool has_image(int which) const { return which >= 0 && (which < 4 || (which < 6 && ((aov_mask >> (which - 4)) & 1u))); }
+  DeviceArray<float4> ps_aov_pos;
+  DeviceArray<uint4> ps_aov_ids;
+  DeviceArray<uint32_t> d_inst_node, d_light_node;  // per instance / per light: the scene node it came from
   DenoiseBuffers denoise;      // RENDER_SPEC 10: allocated by the first hala_rt_denoise
   bool denoised = false;       // denoise.out holds a result
   AdaptiveState adaptive;      // RENDER_SPEC 11: allocated by the first hala_rt_set_adaptive_sampling that enables it
@@ -233,7 +239,7 @@ struct hala_rt_renderer {
   bool comm_owned = false;
   int comm_rank = 0, comm_world = 1;
   hipStream_t gather_stream = nullptr;
-  DeviceArray<float4> gather_stage[4], gather_recv[4];
+  DeviceArray<float4> gather_stage[6], gather_recv[6];
   hipEvent_t ev_rendered = nullptr, ev_staged = nullptr, ev_gathered = nullptr;
   uint32_t gather_pending = 0;  // AOV mask of the collective in flight (hala_rt_tile_allgather_begin)
   int scratch_acquire(hipStream_t s) {
@@ -300,7 +306,10 @@ struct hala_rt_renderer {
     q.hits = q_hits.ptr; q.perm = q_perm.ptr; q.shadow[0] = q_shadow[0].ptr; q.shadow[1] = q_shadow[1].ptr;
     return q;
   }
-  PathState path_state() const { return PathState{ps_lr.ptr, ps_le.ptr, ps_alb.ptr, ps_nrm.ptr}; }
+  PathState path_state() const {
+    return PathState{ps_lr.ptr, ps_le.ptr, ps_alb.ptr, ps_nrm.ptr, (aov_mask & 1u) ? ps_aov_pos.ptr : nullptr, (aov_mask & 2u) ? ps_aov_ids.ptr : nullptr,
+                     d_inst_node.ptr, d_light_node.ptr};
+  }
 
   // RENDER_SPEC §5 / §7.4 for packed camera `cam`: tan(yfov / 2) and the angular size of one pixel
   ViewConst view_const(uint32_t cam, float height) const {
@@ -456,13 +465,20 @@ int alloc_wavefront(hala_rt_renderer* r, uint32_t paths) {
   RT_HIP(r->ps_lr.resize(n)); RT_HIP(r->ps_le.resize(n)); RT_HIP(r->ps_alb.resize(n)); RT_HIP(r->ps_nrm.resize(n));
   RT_HIP(r->q_rays[0].resize(n)); RT_HIP(r->q_rays[1].resize(n)); RT_HIP(r->q_state[0].resize(n)); RT_HIP(r->q_state[1].resize(n));
   RT_HIP(r->q_hits.resize(n)); RT_HIP(r->q_perm.resize(n)); RT_HIP(r->q_shadow[0].resize(n)); RT_HIP(r->q_shadow[1].resize(n));
+  // first-hit AOVs (RENDER_SPEC §13): 16 B per path slot each, only while on
+  if (r->aov_mask & 1u) RT_HIP(r->ps_aov_pos.resize(n)); else r->ps_aov_pos.release();
+  if (r->aov_mask & 2u) RT_HIP(r->ps_aov_ids.resize(n)); else r->ps_aov_ids.release();
   r->batch_capacity = paths;
   return HALA_OK;
 }
 
 int alloc_frame_buffers(hala_rt_renderer* r) {
   const size_t n = r->image_alloc();
-  for (auto& i : r->img_local) { RT_HIP(i.resize(n)); RT_HIP(hipMemsetAsync(i.ptr, 0, n * sizeof(float4), r->stream)); }
+  for (int k = 0; k < 6; ++k) {
+    DeviceArray<float4>& i = r->img_local[k];
+    if (!r->has_image(k)) { i.release(); continue; }
+    RT_HIP(i.resize(n)); RT_HIP(hipMemsetAsync(i.ptr, 0, n * sizeof(float4), r->stream));
+  }
   if (alloc_wavefront(r, 1) != HALA_OK) return HALA_ERR;
   RT_HIP(r->d_ctl.resize(2));  // updates alternate between the two: a tail still running accounts into its own
   RT_HIP(hipMemsetAsync(r->d_ctl.ptr, 0, 2 * sizeof(Control), r->stream));
@@ -513,6 +529,9 @@ int upload_packed(hala_rt_renderer* r, bool geometry = true) {
   }
   RT_HIP(r->d_instances.upload(hs.instances.data(), hs.instances.size(), r->stream));
   RT_HIP(r->d_inst_first_tri.upload(hs.inst_first_tri.data(), hs.inst_first_tri.size(), r->stream));
+  // RENDER_SPEC §13: the node each instance and each light came from (the ids AOV)
+  RT_HIP(r->d_inst_node.upload(hs.instance_node.data(), hs.instance_node.size(), r->stream));
+  RT_HIP(r->d_light_node.upload(hs.light_node.data(), hs.light_node.size(), r->stream));
   RT_HIP(hipStreamSynchronize(r->stream));
   return HALA_OK;
 }
@@ -1218,7 +1237,8 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
       }
     if (timed) { hipEvent_t d = r->next_event(te); RT_HIP(hipEventRecord(d, s)); }
   }
-  launch_resolve(fc, ps, r->img_local[0].ptr, r->img_local[1].ptr, r->img_local[2].ptr, r->img_local[3].ptr, ts);
+  launch_resolve(fc, ps, r->img_local[0].ptr, r->img_local[1].ptr, r->img_local[2].ptr, r->img_local[3].ptr, r->has_image(4) ? r->img_local[4].ptr : nullptr,
+                 r->has_image(5) ? reinterpret_cast<uint4*>(r->img_local[5].ptr) : nullptr, ts);
   RT_HIP(hipMemcpyAsync(te.host_totals, &ctl->totals, sizeof(Totals), hipMemcpyDeviceToHost, ts));
   if (timed) RT_HIP(hipMemcpyAsync(te.host_sizes, &ctl->sizes, sizeof(QueueSizes), hipMemcpyDeviceToHost, ts));
   // frame_begin -> frame_end spans the whole update, its tail included
@@ -1278,7 +1298,7 @@ int hala_rt_wait_idle(hala_rt_renderer* r) {
 
 int hala_rt_read_image(hala_rt_renderer* r, int which, float* dst) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
-  if (which < 0 || which > 3 || !dst) RT_FAIL("Invalid image selector.");
+  if (!r->has_image(which) || !dst) RT_FAIL("Invalid image selector.");
   RT_HIP(hipStreamSynchronize(r->stream));  // wait_idle (src/rt_renderer.rs:1242)
   const size_t bytes = (size_t)r->width * r->height * sizeof(float4);
   if (r->world <= 1) { RT_HIP(hipMemcpy(dst, r->img_local[which].ptr, bytes, hipMemcpyDeviceToHost)); return HALA_OK; }
@@ -1291,7 +1311,7 @@ int hala_rt_read_view_image(hala_rt_renderer* r, uint32_t view, int which, float
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (view >= r->view_count()) RT_FAIL("The view does not exist (hala_rt_set_views set " + std::to_string(r->view_count()) + ").");
   if (view == 0u) return hala_rt_read_image(r, which, dst);
-  if (which < 0 || which > 3 || !dst) RT_FAIL("Invalid image selector.");
+  if (!r->has_image(which) || !dst) RT_FAIL("Invalid image selector.");
   RT_HIP(hipStreamSynchronize(r->stream));
   const size_t px = r->image_pixels();  // several views: never sharded, the row-major frame
   RT_HIP(hipMemcpy(dst, r->img_local[which].ptr + view * px, px * sizeof(float4), hipMemcpyDeviceToHost));
@@ -1317,7 +1337,9 @@ int hala_rt_set_views(hala_rt_renderer* r, const uint32_t* camera_indices, uint3
   // the images hold V views now: view 0 (and every view both lists have) keeps its pixels, new views start at zero.  Buffers only
   // ever grow, so that a failure half-way leaves every one large enough for either list.
   const size_t keep = std::min(old_n, n);
-  for (auto& img : r->img_local) {
+  for (int k = 0; k < 6; ++k) {
+    if (!r->has_image(k)) continue;
+    DeviceArray<float4>& img = r->img_local[k];
     hipError_t e = hipSuccess;
     if (img.count < n) {
       DeviceArray<float4> grown;
@@ -1400,6 +1422,37 @@ int hala_rt_set_adaptive_sampling(hala_rt_renderer* r, const hala_adaptive_param
   r->reset_accumulation();
   return HALA_OK;
 }
+// ---- first-hit AOVs (RENDER_SPEC 13) ------------------------------------------------------------------------------------
+int hala_rt_set_aovs(hala_rt_renderer* r, uint32_t mask) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (mask > 3u) RT_FAIL("hala_rt_set_aovs: unknown AOV bits (bit 0: position, bit 1: ids).");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins an open tail
+  if (r->gather_pending && hala_rt_tile_allgather_finish(r) != HALA_OK) return HALA_ERR;  // an exchange in flight may stage images 4 and 5
+  RT_HIP(hipStreamSynchronize(r->stream));
+  if (r->gather_stream) RT_HIP(hipStreamSynchronize(r->gather_stream));
+  const uint32_t old = r->aov_mask;
+  r->aov_mask = mask;
+  hipError_t e = hipSuccess;
+  const size_t n = r->image_alloc(), paths = (size_t)r->slot_count * r->batch_capacity;
+  for (int k = 4; k < 6 && e == hipSuccess; ++k) {
+    if (!r->has_image(k)) { r->img_local[k].release(); r->img_full[k].release(); r->gather_stage[k].release(); r->gather_recv[k].release(); continue; }
+    if (r->img_local[k].count == n && ((old >> (k - 4)) & 1u)) continue;  // stays on: kept (the accumulation restarts below)
+    e = r->img_local[k].resize(n);
+    if (e == hipSuccess) e = hipMemsetAsync(r->img_local[k].ptr, 0, n * sizeof(float4), r->stream);
+  }
+  if (e == hipSuccess) { if (mask & 1u) e = r->ps_aov_pos.resize(paths); else r->ps_aov_pos.release(); }
+  if (e == hipSuccess) { if (mask & 2u) e = r->ps_aov_ids.resize(paths); else r->ps_aov_ids.release(); }
+  if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+  if (e != hipSuccess) {  // out of memory: the AOVs are off, the other images are untouched
+    r->aov_mask = 0;
+    for (int k = 4; k < 6; ++k) r->img_local[k].release();
+    r->ps_aov_pos.release(); r->ps_aov_ids.release();
+    RT_HIP(e);
+  }
+  r->reset_accumulation();
+  return HALA_OK;
+}
+
 int hala_rt_read_sample_counts(hala_rt_renderer* r, uint32_t* dst) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (!dst) RT_FAIL("The output pointer is null!");
@@ -1629,7 +1682,7 @@ int hala_rt_set_tile_shard(hala_rt_renderer* r, uint32_t rank, uint32_t world, u
   return HALA_OK;
 }
 int hala_rt_tile_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_t* bytes) {
-  if (!r || which < 0 || which > 3 || !d_ptr || !bytes) RT_FAIL("Invalid argument.");
+  if (!r || !r->has_image(which) || !d_ptr || !bytes) RT_FAIL("Invalid argument.");
   *d_ptr = r->img_local[which].ptr;
   *bytes = r->image_pixels() * sizeof(float4);
   return HALA_OK;
@@ -1642,7 +1695,7 @@ int hala_rt_get_stream(hala_rt_renderer* r, void** hip_stream) {
 }
 int hala_rt_scatter_gathered_tiles_on_stream(hala_rt_renderer* r, int which, const void* d_gathered, size_t bytes, void* hip_stream) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
-  if (which < 0 || which > 3 || !d_gathered) RT_FAIL("Invalid argument.");
+  if (!r->has_image(which) || !d_gathered) RT_FAIL("Invalid argument.");
   if (r->world <= 1) RT_FAIL("The renderer is not sharded.");
   if (bytes != r->image_pixels() * r->world * sizeof(float4)) RT_FAIL("The gathered buffer has the wrong size.");
   RT_HIP(r->img_full[which].resize((size_t)r->width * r->height));
@@ -1735,7 +1788,8 @@ int hala_rt_comm_destroy(hala_rt_renderer* r) {
 // tests that emulate the ranks) reads the staging buffer and fills the receive buffer on the exchange stream (hala_rt_get_exchange_buffers) —
 // everything else (staging copy, event order, de-interleave in finish) is this very code.
 static int allgather_begin(hala_rt_renderer* r, uint32_t aov_mask, bool external) {
-  if (aov_mask == 0u || aov_mask > 15u) RT_FAIL("Invalid AOV mask.");
+  // bits 4 and 5: the first-hit AOVs, while on (RENDER_SPEC §13)
+  if (aov_mask == 0u || aov_mask > 63u || ((aov_mask >> 4) & ~r->aov_mask)) RT_FAIL("Invalid AOV mask.");
   if (hala_rt_tile_allgather_finish(r) != HALA_OK) return HALA_ERR;
   if (ensure_gather_resources(r) != HALA_OK) return HALA_ERR;
   const uint32_t world = external ? r->world : (uint32_t)r->comm_world;
@@ -1744,7 +1798,7 @@ static int allgather_begin(hala_rt_renderer* r, uint32_t aov_mask, bool external
   hipStream_t g = r->gather_stream;
   RT_HIP(hipEventRecord(r->ev_rendered, r->stream));
   RT_HIP(hipStreamWaitEvent(g, r->ev_rendered, 0));
-  for (int which = 0; which < 4; ++which) {
+  for (int which = 0; which < 6; ++which) {
     if (!(aov_mask & (1u << which))) continue;
     RT_HIP(r->gather_stage[which].resize(n));
     RT_HIP(r->gather_recv[which].resize(n * (size_t)world));
@@ -1754,7 +1808,7 @@ static int allgather_begin(hala_rt_renderer* r, uint32_t aov_mask, bool external
   RT_HIP(hipStreamWaitEvent(r->stream, r->ev_staged, 0));
   if (!external) {
     RT_RCCL_API(api);
-    for (int which = 0; which < 4; ++which)
+    for (int which = 0; which < 6; ++which)
       if (aov_mask & (1u << which))
         RT_NCCL(api, api->AllGather(r->gather_stage[which].ptr, r->gather_recv[which].ptr, n * 4, ncclFloat, r->comm, g));
   }
@@ -1773,7 +1827,7 @@ int hala_rt_tile_allgather_begin_external(hala_rt_renderer* r, uint32_t aov_mask
   return allgather_begin(r, aov_mask, true);
 }
 int hala_rt_get_exchange_buffers(hala_rt_renderer* r, int which, void** d_staged, size_t* staged_bytes, void** d_receive, size_t* receive_bytes, void** hip_stream) {
-  if (!r || which < 0 || which > 3) RT_FAIL("Invalid argument.");
+  if (!r || !r->has_image(which)) RT_FAIL("Invalid argument.");
   if (!(r->gather_pending & (1u << which))) RT_FAIL("No exchange of this image is in flight: call hala_rt_tile_allgather_begin_external first.");
   if (d_staged) *d_staged = r->gather_stage[which].ptr;
   if (staged_bytes) *staged_bytes = r->gather_stage[which].bytes();
@@ -1793,7 +1847,7 @@ int hala_rt_tile_allgather_finish(hala_rt_renderer* r) {
   hipStream_t g = r->gather_stream;
   if (r->world > 1) {
     const FrameConst fc = r->frame_const(r->last_uniform);
-    for (int which = 0; which < 4; ++which) {
+    for (int which = 0; which < 6; ++which) {
       if (!(mask & (1u << which))) continue;
       if (r->gather_recv[which].count != r->image_pixels() * (size_t)r->world) RT_FAIL("The receive buffer does not match the tile shard.");
       RT_HIP(r->img_full[which].resize((size_t)r->width * r->height));
@@ -1811,7 +1865,7 @@ int hala_rt_tile_allgather(hala_rt_renderer* r, uint32_t aov_mask) {
   return hala_rt_tile_allgather_finish(r);
 }
 int hala_rt_get_gathered_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_t* bytes) {
-  if (!r || which < 0 || which > 3 || !d_ptr || !bytes) RT_FAIL("Invalid argument.");
+  if (!r || !r->has_image(which) || !d_ptr || !bytes) RT_FAIL("Invalid argument.");
   *d_ptr = r->gather_recv[which].ptr;
   *bytes = r->gather_recv[which].bytes();
   return HALA_OK;

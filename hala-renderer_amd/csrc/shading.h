@@ -624,6 +624,7 @@ struct Surface {
   f3 absorb, glow;  // §7.1e: transmittance / emitted radiance of the medium the segment that ends here ran through
   float sigma, hg;  // §7.1f: scattering coefficient (0: none) and Henyey-Greenstein g of that medium
   f3 scol;          //        its single-scattering albedo
+  uint32_t inst, material;  // instance (TLAS order) and material of the hit triangle (RENDER_SPEC §13)
 };
 RT_DI f3 transform_vector(const float* m, f3 p) {
   return mk3(__fmaf_rn(m[8], p.z, __fmaf_rn(m[4], p.y, m[0] * p.x)), __fmaf_rn(m[9], p.z, __fmaf_rn(m[5], p.y, m[1] * p.x)),
@@ -648,6 +649,7 @@ RT_DI Surface make_surface(const SceneView& sv, LUT lut, float pixel_spread, f3 
   const float4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
   const uint32_t inst = sv.two_level ? inst_tl : __float_as_uint(s0.w), material = __float_as_uint(s1.w);
   const hala_gpu_mesh_data& md = sv.primitives[inst];
+  sf.inst = inst; sf.material = material;
   float w0 = 1.0f - u - v;
   f3 nl = madd3(mk3(s3.x, s3.y, s3.z), v, madd3(mk3(s2.x, s2.y, s2.z), u, mk3(s1.x, s1.y, s1.z) * w0));
   sf.ns = normalize3(transform_normal(md.transform, nl));

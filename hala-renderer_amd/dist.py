@@ -105,6 +105,8 @@ class TileGather:
         import torch
         import torch.distributed as dist
         self.r, self.dist, self.group, self.torch, self.aovs = renderer, dist, group, torch, tuple(aovs)
+        if not self.aovs or any(a not in range(6) for a in self.aovs):  # 4 position, 5 ids: while on (HalaRenderer.set_aovs)
+            raise ValueError(f"TileGather: AOVs must be among 0..5, got {aovs}")
         self.device = f"cuda:{device_index}"
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)

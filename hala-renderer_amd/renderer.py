@@ -178,10 +178,14 @@ class HalaRenderer:
         self._check(self._lib.hala_rt_set_launch_timing_period(self._h, C.c_uint32(period)))
 
     # -- read-back used by tests and bench (what save_images downloads, :1239-1254) -------------------------------
-    ACCUM, ALBEDO, NORMAL, FINAL = 0, 1, 2, 3
+    ACCUM, ALBEDO, NORMAL, FINAL, POSITION, IDS = 0, 1, 2, 3, 4, 5
+    IMAGE_NAMES = ("accum", "albedo", "normal", "final", "position", "ids")
 
     def read_image(self, which=0, view=0) -> np.ndarray:
-        """one of the four images of `view` (an index into the list set_views gave; 0: the only view by default)"""
+        """one of the images of `view` (an index into the list set_views gave; 0: the only view by default); `which` is an index or a
+        name of IMAGE_NAMES.  4 / 5 only while set_aovs turned them on (5 comes back as float32 bits: read_ids)"""
+        if isinstance(which, str):
+            which = self.IMAGE_NAMES.index(which)
         out = np.empty((self.height, self.width, 4), dtype=np.float32)
         dst = out.ctypes.data_as(C.POINTER(C.c_float))
         if view == 0:
@@ -197,6 +201,16 @@ class HalaRenderer:
         idx = [int(c) for c in cameras]
         arr = (C.c_uint32 * max(len(idx), 1))(*idx)
         self._check(self._lib.hala_rt_set_views(self._h, arr, C.c_uint32(len(idx))))
+
+    # -- first-hit AOVs (docs/RENDER_SPEC.md 13; include/halart.h "hala_rt_set_aovs") -------------------------------------------
+    def set_aovs(self, position=False, ids=False):
+        """turn the first-hit position (image 4) and id (image 5) AOVs on or off.  Restarts the accumulation."""
+        self._check(self._lib.hala_rt_set_aovs(self._h, C.c_uint32((1 if position else 0) | (2 if ids else 0))))
+
+    def read_ids(self, view=0) -> np.ndarray:
+        """[H, W, 4] uint32: (node, instance, material, triangle id) of the first hit of frame 0's sample; lights: (node, ~0, ~0,
+        0x80000000 | light index); misses: all ~0"""
+        return self.read_image(self.IDS, view=view).view(np.uint32)
 
     # -- denoising (docs/RENDER_SPEC.md 10; include/halart.h "hala_rt_denoise") -----------------------------------
     def denoise(self, iterations=None, sigma_color=None, sigma_albedo=None, normal_power=None, demodulate=True, timed=False):
@@ -453,3 +467,17 @@ def denoise_images(color, albedo, normal, device_ordinal=0, **params) -> np.ndar
     fp = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
     check(load_library().hala_denoise_images(device_ordinal, fp(c), fp(a), fp(n), w, h, C.byref(p), fp(out)))
     return out
+
+
+def view_depth(position, camera):
+    """[H, W] float32 view-space depth along the camera's forward axis from a position AOV (read_image("position")) and a packed camera
+    (HalaRenderer.packed_cameras()[c]): dot(xyz / w - camera position, normalize(forward)) where w > 0, +inf where no sample hit.  Computed in
+    float64 and rounded once.  Depth is linear in P, so it is also the mean depth of the samples that hit."""
+    p = np.asarray(position, dtype=np.float64)
+    w = p[..., 3]
+    fwd = np.array(camera.forward[:3], dtype=np.float64)
+    fwd = fwd / np.linalg.norm(fwd)
+    eye = np.array(camera.position[:3], dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        depth = (p[..., :3] @ fwd - w * float(eye @ fwd)) / w
+    return np.where(w > 0.0, depth, np.inf).astype(np.float32)

@@ -389,6 +389,24 @@ int hala_rt_set_views(hala_rt_renderer* r, const uint32_t* camera_indices, uint3
  * from hala_write_pfm and hala_denoise_images on what this returns. */
 int hala_rt_read_view_image(hala_rt_renderer* r, uint32_t view, int which, float* dst_rgba32f);
 
+/* First-hit AOVs (docs/RENDER_SPEC.md 13; no reference equivalent — there an application writes its own closest-hit and raygen shaders,
+ * which this integrator validates and ignores).  mask bit 0 = image 4 `position`, bit 1 = image 5 `ids`; the default is 0.  The first
+ * hit of a sample is its camera ray's nearest triangle or hittable light (QUAD, SPHERE): the surface whose albedo and normal go to
+ * images 1 and 2.
+ *   4 position (RGBA32F): the running mean, in frame order, of (P.xyz, 1) on a hit and (0, 0, 0, 0) on a miss, P = madd(d, t, o) of the
+ *     camera ray.  .w is the pixel's coverage; xyz / w is the mean hit point of the samples that hit.
+ *   5 ids (4 x uint32 per pixel in the same 16-B slots; read with read_image and reinterpret): the first hit of the sample of frame 0 of
+ *     the accumulation, kept after that.  Triangle: (node, instance, material, global triangle id), the instance in the order of
+ *     hala_rt_get_packed_primitives and the node it came from.  Light: (node of the light, 0xFFFFFFFF, 0xFFFFFFFF, 0x80000000 | light
+ *     index).  Miss: all 0xFFFFFFFF.
+ * They follow the tile layout, the views, adaptive sampling and update_batch like images 0-3.  Bits above 1 are refused with the
+ * renderer left as it was.  A successful call joins the tail of the last update, allocates or frees images 4 / 5 of every view and
+ * 16 B per path slot each, and restarts the accumulation.  read_image, read_view_image, tile_buffer, the scatter and exchange entry
+ * points take `which` 4 / 5 and the all-gather masks bits 4 / 5 while that AOV is on, and refuse them while it is off.  Not built:
+ * save_images does not write them (hala_write_pfm does), no depth image (view depth follows from position and the camera), no
+ * per-sample (deep) ids, no motion vectors, no denoiser guided by position. */
+int hala_rt_set_aovs(hala_rt_renderer* r, uint32_t mask);
+
 /* info()/statistics() (src/renderer.rs:212-218, :135-207) */
 typedef struct hala_rt_info {
   uint32_t width;

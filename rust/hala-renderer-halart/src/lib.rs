@@ -119,6 +119,8 @@ pub mod sys {
     pub fn hala_rt_tile_allgather_begin_external(r: *mut hala_rt_renderer, aov_mask: u32) -> c_int;
     pub fn hala_rt_get_exchange_buffers(r: *mut hala_rt_renderer, which: c_int, d_staged: *mut *mut c_void, staged_bytes: *mut usize,
                                         d_receive: *mut *mut c_void, receive_bytes: *mut usize, hip_stream: *mut *mut c_void) -> c_int;
+    // first-hit AOVs (docs/RENDER_SPEC.md 13): mask bit 0 = image 4 position, bit 1 = image 5 ids
+    pub fn hala_rt_set_aovs(r: *mut hala_rt_renderer, mask: u32) -> c_int;
     // cpu::HalaScene::new inside the library (for hosts without the Rust `src/scene` module)
     pub fn hala_scene_load_gltf(path: *const c_char, out: *mut *mut hala_scene) -> c_int;
     pub fn hala_scene_get_desc(scene: *const hala_scene) -> *const hala_scene_desc;
