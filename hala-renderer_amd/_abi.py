@@ -192,6 +192,11 @@ class AdaptiveStatus(C.Structure):  # hala_adaptive_status, 32 B
                 ("samples", C.c_uint32), ("last_snapshot", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class LightGroups(C.Structure):  # hala_light_groups, 32 B (docs/RENDER_SPEC.md 14)
+    _fields_ = [("group_count", C.c_uint32), ("environment_group", C.c_uint32), ("light_count", C.c_uint32),
+                ("material_count", C.c_uint32), ("light_group", C.POINTER(C.c_uint32)), ("material_group", C.POINTER(C.c_uint32))]
+
+
 # argtypes / restype of the denoise, adaptive sampling, view and AOV entry points (load_library installs them)
 PROTOTYPES = {
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
@@ -208,6 +213,11 @@ PROTOTYPES = {
     "hala_rt_set_views": ([C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32], C.c_int),
     "hala_rt_read_view_image": ([C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_float)], C.c_int),
     "hala_rt_set_aovs": ([C.c_void_p, C.c_uint32], C.c_int),
+    "hala_rt_set_light_groups": ([C.c_void_p, C.POINTER(LightGroups)], C.c_int),
+    "hala_rt_read_light_group": ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_relight": ([C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_uint32], C.c_int),
+    "hala_rt_read_relit": ([C.c_void_p, C.c_int, C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_get_relit_buffer": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)], C.c_int),
 }
 
 
@@ -245,4 +255,5 @@ EXPORTS = [
     "hala_denoise_images",
     "hala_adaptive_default_params", "hala_rt_set_adaptive_sampling", "hala_rt_read_sample_counts", "hala_rt_get_adaptive_status",
     "hala_rt_set_views", "hala_rt_read_view_image", "hala_rt_set_aovs",
+    "hala_rt_set_light_groups", "hala_rt_read_light_group", "hala_rt_relight", "hala_rt_read_relit", "hala_rt_get_relit_buffer",
 ]

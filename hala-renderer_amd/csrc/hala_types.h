@@ -295,14 +295,25 @@ struct PathState {
   uint4* aov_ids;
   const uint32_t* inst_node;
   const uint32_t* light_node;
+  // light groups (RENDER_SPEC §14; nullptr / 0 while off): group_count radiance sums per path slot, group-major (group g of slot s at
+  // groups[g * group_stride + s]), and the group of every packed light, of every material and of the environment.  Read and written by
+  // the GROUPS kernel variants only
+  P3* groups;
+  const uint32_t* light_group;
+  const uint32_t* material_group;
+  uint32_t group_count, group_stride, env_group;
 };
+constexpr uint32_t kMaxLightGroups = 8;
 
 struct ShadowEntry {  // 48 B: one NEE connection = shadow ray + the contribution it carries if unoccluded
   hala_ray ray;
   float contrib[3];  // throughput * f * Le * cos * weight / pdf, already multiplied out (RENDER_SPEC §6.5-6.6)
-  uint32_t slot;     // pixel slot whose radiance receives it
+  uint32_t slot;     // pixel slot whose radiance receives it; light connections of the GROUPS variants: slot | light group << kGroupShift
 };
 static_assert(sizeof(ShadowEntry) == 48, "shadow entry is 48 B");
+// light groups on: path slots stay below 2^29 (the renderer refuses larger wavefronts), the group (< 8) rides in the top three bits
+constexpr uint32_t kGroupShift = 29, kGroupSlotMask = (1u << kGroupShift) - 1u;
+static_assert(kMaxLightGroups <= (1u << (32 - kGroupShift)), "the group fits the top bits of ShadowEntry::slot");
 
 struct Queues {
   hala_ray* rays[2];  // bounce rays; tmin / tmax are implied (0 / FLT_MAX): their fields carry the path slot / the RNG counter

@@ -267,12 +267,16 @@ struct CameraSource {
     else reinterpret_cast<float4*>(hits)[i] = out;
   }
 };
-template <bool ALPHA>
+template <bool ALPHA, bool GROUPS>
 struct ShadowSource {
   // contribution.xyz | pixel slot, fetched with the ray (one coalesced 48-B record), and the path's radiance as it stands
   struct Payload { float4 cs; float lx, ly, lz; };
   const ShadowEntry* entries;
   P3* radiance;
+  // GROUPS (RENDER_SPEC §14): the light connections' entries carry slot | group << kGroupShift, and an unoccluded one adds its contribution
+  // to that group's sum of the path too — the same owner rule, one IEEE add per component.  Null for the environment connections.
+  P3* groups;
+  uint32_t group_stride;
   // A path owns at most one connection per queue and the two queues add to different arrays, so nothing else touches this word of the
   // path's radiance during the launch: it is fetched here, behind the entry (the load is in flight while the ray is traced), and
   // an unoccluded ray stores radiance + contribution — one IEEE add per component, no ordering freedom.  (Three memory-side float
@@ -282,7 +286,8 @@ struct ShadowSource {
     const float4* e = reinterpret_cast<const float4*>(entries + i);
     const float4 ro = e[0], rd = e[1];
     p->cs = e[2];
-    const float* l = reinterpret_cast<const float*>(radiance + __float_as_uint(p->cs.w));
+    const uint32_t slot = GROUPS ? (__float_as_uint(p->cs.w) & kGroupSlotMask) : __float_as_uint(p->cs.w);
+    const float* l = reinterpret_cast<const float*>(radiance + slot);
     p->lx = l[0]; p->ly = l[1]; p->lz = l[2];
     // a connection starts at its origin (tmin = 0): the field carries its any-hit key (RENDER_SPEC 7.1d)
     *o = mk3(ro.x, ro.y, ro.z); *d = mk3(rd.x, rd.y, rd.z); *tmin = 0.0f; *tmax = rd.w; *key = __float_as_uint(ro.w);
@@ -295,8 +300,14 @@ struct ShadowSource {
       const f3 tr = any_transmittance(t.tau);
       if (tr.x != 1.0f || tr.y != 1.0f || tr.z != 1.0f) { cx = cx * tr.x; cy = cy * tr.y; cz = cz * tr.z; }
     }
-    float* l = reinterpret_cast<float*>(radiance + __float_as_uint(p.cs.w));
+    const uint32_t w = __float_as_uint(p.cs.w), slot = GROUPS ? (w & kGroupSlotMask) : w;
+    float* l = reinterpret_cast<float*>(radiance + slot);
     l[0] = p.lx + cx; l[1] = p.ly + cy; l[2] = p.lz + cz;
+    if (GROUPS && groups) {
+      P3* gp = groups + (size_t)(w >> kGroupShift) * group_stride + slot;
+      const P3 g = *gp;
+      *gp = P3{g.x + cx, g.y + cy, g.z + cz};
+    }
   }
 };
 
@@ -350,7 +361,7 @@ k_trace_primary(SceneView sv, FrameConst fc, hala_hit* __restrict__ hits, WorkCo
 // K5c: shadow traversal of the NEE connections of one bounce; unoccluded contributions are added to the
 // path's radiance in the fixed order light, environment (RENDER_SPEC §6)
 // ---------------------------------------------------------------------------------------------------------
-template <bool COUNT, bool STAGED, bool ALPHA, bool INST>
+template <bool COUNT, bool STAGED, bool ALPHA, bool INST, bool GROUPS>
 __global__ void __launch_bounds__(kTraverseThreads, STAGED ? kTraverseWavesPerSimdStaged : kTraverseWavesPerSimd)
 k_trace_shadow(SceneView sv, Queues q, PathState ps, Control* __restrict__ ctl, uint32_t depth, uint32_t kind, uint2* __restrict__ spill_base,
                uint32_t refill) {
@@ -358,7 +369,7 @@ k_trace_shadow(SceneView sv, Queues q, PathState ps, Control* __restrict__ ctl, 
   const uint32_t n = ctl->sizes.n_shadow[kind][depth];
   uint2* spill = spill_base ? spill_base + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * kStackSpill : nullptr;
   StepCounters sc;
-  ShadowSource<ALPHA> src{q.shadow[kind], kind ? ps.radiance_env : ps.radiance};
+  ShadowSource<ALPHA, GROUPS> src{q.shadow[kind], kind ? ps.radiance_env : ps.radiance, kind ? nullptr : ps.groups, ps.group_stride};
   persistent_trace<true, COUNT, STAGED, ALPHA, INST>(sv, lds, spill, &ctl->work_shadow[kind], n, refill, src, sc);
   if (COUNT) flush_counters(ctl, 1, sc);
 }
@@ -372,7 +383,7 @@ k_trace_shadow(SceneView sv, Queues q, PathState ps, Control* __restrict__ ctl, 
 // do not achieve this: each takes the chip from the other all the time, profiles/r02_experiments.txt.)  Not used by updates that carry
 // per-launch timing events or counting kernels.
 // ---------------------------------------------------------------------------------------------------------
-template <bool STAGED, bool ALPHA, bool INST>
+template <bool STAGED, bool ALPHA, bool INST, bool GROUPS>
 __global__ void __launch_bounds__(kTraverseThreads, STAGED ? kTraverseWavesPerSimdStaged : kTraverseWavesPerSimd)
 k_trace_shadow_then_batch(SceneView sv, const Tri* __restrict__ tris_any, Queues q, PathState ps, Control* __restrict__ ctl, uint32_t depth,
                           uint32_t kinds, const hala_ray* __restrict__ rays, hala_hit* __restrict__ hits, uint2* __restrict__ spill_base, uint32_t refill) {
@@ -384,7 +395,7 @@ k_trace_shadow_then_batch(SceneView sv, const Tri* __restrict__ tris_any, Queues
     sva.tris = tris_any;  // RENDER_SPEC 7.1d (STAGED: the launcher only fuses when both passes traverse the same triangles)
     for (uint32_t kind = 0; kind < 2u; ++kind) {  // bit 0: light connections, bit 1: environment connections
       if (!((kinds >> kind) & 1u)) continue;
-      ShadowSource<ALPHA> src{q.shadow[kind], kind ? ps.radiance_env : ps.radiance};
+      ShadowSource<ALPHA, GROUPS> src{q.shadow[kind], kind ? ps.radiance_env : ps.radiance, kind ? nullptr : ps.groups, ps.group_stride};
       persistent_trace<true, false, STAGED, ALPHA, INST>(sva, lds, spill, &ctl->work_shadow[kind], ctl->sizes.n_shadow[kind][depth], refill, src, sc);
     }
   }
@@ -478,7 +489,14 @@ RT_DI void first_hit_aovs(const PathState& ps, uint32_t slot, float4 pos, uint4 
   if (ps.aov_pos) ps.aov_pos[slot] = pos;
   if (ps.aov_ids) ps.aov_ids[slot] = ids;
 }
-template <bool PRIMARY, bool SIMPLE, bool SCATTER, bool AOV>
+// GROUPS: the light groups of RENDER_SPEC §14 are on — every term added to the path's radiance also goes to its source's group sum
+// (ps.groups), and light connections carry their light's group to the shadow pass.  A compile-time flag like AOV.
+RT_DI void group_add(const PathState& ps, uint32_t g, uint32_t slot, f3 x) {
+  P3* gp = ps.groups + (size_t)g * ps.group_stride + slot;
+  const P3 l = *gp;
+  *gp = P3{l.x + x.x, l.y + x.y, l.z + x.z};
+}
+template <bool PRIMARY, bool SIMPLE, bool SCATTER, bool AOV, bool GROUPS>
 __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric, SIMPLE ? RT_SHADE_WAVES_SIMPLE : RT_SHADE_WAVES) k_shade(FrameConst fc, SceneView sv, Queues q, PathState ps, Control* __restrict__ ctl, uint32_t depth) {
   __shared__ BlockCompact s_compact;
   const uint32_t n = PRIMARY ? fc.slot_count : ctl->sizes.n_active[depth];
@@ -529,6 +547,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
   if (real) {
     // L: what this bounce adds to the path's radiance (at most one term: light hit | environment | emission)
     f3 T = splat3(1.0f), L = splat3(0.0f);
+    uint32_t gL = 0;  // GROUPS: the light group of the source of L's term
     float prev_pdf = kNoNeePdf;  // no vertex has sampled a direction yet: an emitter reached through skipped (7.1d) surfaces counts in full
     if (!PRIMARY) {  // the whole state of a live path is its queue entry: coalesced reads, no gather by slot
       const float4* rp = reinterpret_cast<const float4*>(q.rays[in] + i);
@@ -555,6 +574,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
       float w = 1.0f;
       if (!PRIMARY) w = power_heuristic(prev_pdf, light_pdf * (1.0f / (float)nl));
       L = L + T * le * w;
+      if (GROUPS) gL = ps.light_group[hit_light];
       if (PRIMARY) {
         ps.albedo[slot] = P3{minf(le.x, 1.0f), minf(le.y, 1.0f), minf(le.z, 1.0f)};
         ps.normal[slot] = P3{0.0f, 0.0f, 0.0f};
@@ -571,6 +591,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
         if (!PRIMARY) w = power_heuristic(prev_pdf, env_map_pdf(fc, sv, d));
       } else env = sky_eval(fc, d);
       L = L + T * env * w;
+      if (GROUPS) gL = ps.env_group;
       if (PRIMARY) {
         ps.albedo[slot] = P3{minf(env.x, 1.0f), minf(env.y, 1.0f), minf(env.z, 1.0f)};
         ps.normal[slot] = P3{0.0f, 0.0f, 0.0f};
@@ -586,6 +607,8 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
         ps.normal[slot] = P3{sf.ns.x, sf.ns.y, sf.ns.z};
         if (AOV) first_hit_aovs(ps, slot, make_float4(sf.P.x, sf.P.y, sf.P.z, 1.0f), make_uint4(ps.inst_node[sf.inst], sf.inst, sf.material, hit_prim));
       }
+      // the glow and the emission of this hit both come from the hit triangle's material: one group
+      if (GROUPS) gL = ps.material_group[sf.material];
       // §7.1e: what the medium of an object just crossed did to the segment that ends here (identity for every other hit)
       if (sf.glow.x > 0.0f || sf.glow.y > 0.0f || sf.glow.z > 0.0f) {
         const f3 g = T * sf.glow;
@@ -593,6 +616,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
         else {  // a second term may follow in this bounce (emission): this one goes to the path's radiance right away, in order
           const P3 l = ps.radiance[slot];
           ps.radiance[slot] = P3{l.x + g.x, l.y + g.y, l.z + g.z};
+          if (GROUPS) group_add(ps, gL, slot, g);
         }
       }
       T = T * sf.absorb;
@@ -654,7 +678,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
             const f3 tc = T * contrib;
             conn[0][0] = make_float4(so.x, so.y, so.z, __uint_as_float(pcg_hash(rng ^ kAnyKeyLight)));  // tmin is 0: the field carries the any-hit key (7.1d)
             conn[0][1] = make_float4(ls.wi.x, ls.wi.y, ls.wi.z, tmax);
-            conn[0][2] = make_float4(tc.x, tc.y, tc.z, __uint_as_float(slot));
+            conn[0][2] = make_float4(tc.x, tc.y, tc.z, __uint_as_float(GROUPS ? slot | (ps.light_group[idx] << kGroupShift) : slot));
             keep[1] = true;
           }
         }
@@ -710,10 +734,14 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
       }
       }  // !through
     }
-    if (PRIMARY) ps.radiance[slot] = P3{L.x, L.y, L.z};
-    else if (L.x != 0.0f || L.y != 0.0f || L.z != 0.0f) {  // radiance += term (this launch touches the word once: a plain update)
+    if (PRIMARY) {
+      ps.radiance[slot] = P3{L.x, L.y, L.z};
+      if (GROUPS)  // every group sum of the slot starts here: the term's group holds L, the others 0
+        for (uint32_t g = 0; g < ps.group_count; ++g) ps.groups[(size_t)g * ps.group_stride + slot] = g == gL ? P3{L.x, L.y, L.z} : P3{0.0f, 0.0f, 0.0f};
+    } else if (L.x != 0.0f || L.y != 0.0f || L.z != 0.0f) {  // radiance += term (this launch touches the word once: a plain update)
       const P3 l = ps.radiance[slot];
       ps.radiance[slot] = P3{l.x + L.x, l.y + L.y, l.z + L.z};
+      if (GROUPS) group_add(ps, gL, slot, L);
     }
     rng_out = rng;
     state_out = make_float4(T.x, T.y, T.z, prev_pdf);
@@ -745,10 +773,12 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
 // view's images (view_pixels float4s apart; view 0's are the renderer's usual images).
 // AOV (RENDER_SPEC §13): `pos` (may be null) folds (P, hit) like the other means; `ids` (may be null) takes the ids of the sample of frame 0
 // of the accumulation and keeps them after that.  The variant without the flag never looks at the two images.
-template <bool AOV>
+// GROUPS (RENDER_SPEC §14): image g of the light groups (at gimg + g * gimg_stride, laid out like accum) folds S_g = L_g (+ Le for the
+// environment's group when env_type is MAP) in frame order, a non-finite S_g replaced by 0 on its own.
+template <bool AOV, bool GROUPS>
 __global__ void __launch_bounds__(256) k_resolve(FrameConst fc, PathState ps, float4* __restrict__ accum, float4* __restrict__ albedo,
                                                   float4* __restrict__ normal, float4* __restrict__ final_img, float4* __restrict__ pos,
-                                                  uint4* __restrict__ ids) {
+                                                  uint4* __restrict__ ids, float4* __restrict__ gimg, size_t gimg_stride) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t view = t / fc.pixel_slots, pslot = t - view * fc.pixel_slots;
   if (view >= fc.views) return;
@@ -784,9 +814,41 @@ __global__ void __launch_bounds__(256) k_resolve(FrameConst fc, PathState ps, fl
   }
   accum[at] = a; albedo[at] = b; normal[at] = n;
   if (AOV && pos) pos[at] = p;
+  if (GROUPS)
+    for (uint32_t g = 0; g < ps.group_count; ++g) {
+      float4* gi = gimg + g * gimg_stride + at;
+      float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (fc.u.frame_index != 0u) m = *gi;
+      for (uint32_t k = 0; k < fc.samples; ++k) {
+        const uint32_t slot = (k * fc.views + view) * fc.pixel_slots + pslot;
+        const P3 lr = ps.groups[(size_t)g * ps.group_stride + slot];
+        f3 S = mk3(lr.x, lr.y, lr.z);
+        if (fc.u.env_type == 1u && g == ps.env_group) { const P3 le = ps.radiance_env[slot]; S = S + mk3(le.x, le.y, le.z); }
+        if (!(isfinite(S.x) && isfinite(S.y) && isfinite(S.z))) S = splat3(0.0f);
+        const uint32_t fi = fc.u.frame_index + k;
+        m = make_float4(fold_mean(m.x, S.x, fi), fold_mean(m.y, S.y, fi), fold_mean(m.z, S.z, fi), 1.0f);
+      }
+      *gi = m;
+    }
   if (AOV && ids && fc.u.frame_index == 0u) ids[at] = id;
   const f3 c = tonemap_select(mk3(a.x, a.y, a.z) * fc.u.exposure_value, fc.u.enable_tonemap, fc.u.enable_aces, fc.u.use_simple_aces);
   final_img[at] = make_float4(c.x, c.y, c.z, 1.0f);
+}
+
+// relight (RENDER_SPEC §14): R = sum over g ascending of s_g * I_g, from 0, one IEEE multiply and add per channel and group; the linear
+// image and tonemap_select(R * exposure) exactly as k_resolve writes `final`.  One thread per pixel of one view.
+__global__ void __launch_bounds__(256) k_relight(const float4* __restrict__ gimg, size_t gimg_stride, uint32_t group_count, RelightScales sc,
+                                                 uint32_t n, hala_global_uniform u, float4* __restrict__ linear, float4* __restrict__ toned) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  f3 acc = splat3(0.0f);
+  for (uint32_t g = 0; g < group_count; ++g) {
+    const float4 v = gimg[g * gimg_stride + i];
+    acc = acc + mk3(sc.s[g][0], sc.s[g][1], sc.s[g][2]) * mk3(v.x, v.y, v.z);
+  }
+  linear[i] = make_float4(acc.x, acc.y, acc.z, 1.0f);
+  const f3 c = tonemap_select(acc * u.exposure_value, u.enable_tonemap, u.enable_aces, u.use_simple_aces);
+  toned[i] = make_float4(c.x, c.y, c.z, 1.0f);
 }
 
 // stand-alone texture fetch (tests): uvl = (u, v, lod) per sample
@@ -839,7 +901,7 @@ uint32_t traverse_blocks_per_cu(size_t dynamic_lds_bytes, TreeForm tree) {
   with_flags([&](auto STAGED, auto INST) {
     if constexpr (!(STAGED && INST)) {
       ea = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_trace_batch<false, false, STAGED, false, INST>, kTraverseThreads, dynamic_lds_bytes);
-      eb = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_trace_shadow<false, STAGED, false, INST>, kTraverseThreads, dynamic_lds_bytes);
+      eb = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_trace_shadow<false, STAGED, false, INST, false>, kTraverseThreads, dynamic_lds_bytes);
     }
   }, tree == TreeForm::Staged, tree == TreeForm::TwoLevel);
   if (ea != hipSuccess || eb != hipSuccess) return 0;
@@ -866,11 +928,12 @@ void launch_trace_shadow(const LaunchCfg& lc, const SceneView& sv0, const Queues
   SceneView sv = sv0;
   sv.tris = sv0.tris_any;  // RENDER_SPEC 7.1d: shadow rays traverse the copy in which invisible surfaces are degenerate and translucent ones flagged
   const TreeForm tree = tree_form(sv);
-  with_flags([&](auto COUNT, auto ALPHA, auto STAGED, auto INST) {
+  // light groups (RENDER_SPEC §14): only the light connections carry a group
+  with_flags([&](auto COUNT, auto ALPHA, auto STAGED, auto INST, auto GROUPS) {
     if constexpr (!(STAGED && INST))
-      hipLaunchKernelGGL((k_trace_shadow<COUNT, STAGED, ALPHA, INST>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, q, ps, ctl,
-                         depth, kind, lc.spill, lc.refill);
-  }, count, sv.any_translucent != 0u, tree == TreeForm::Staged, tree == TreeForm::TwoLevel);
+      hipLaunchKernelGGL((k_trace_shadow<COUNT, STAGED, ALPHA, INST, GROUPS>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, q, ps,
+                         ctl, depth, kind, lc.spill, lc.refill);
+  }, count, sv.any_translucent != 0u, tree == TreeForm::Staged, tree == TreeForm::TwoLevel, kind == 0u && ps.groups != nullptr);
 }
 
 // the fused launch; false: the caller must issue the two launches separately (an LDS-staged scene whose any-hit rays traverse a
@@ -880,11 +943,11 @@ bool launch_trace_shadow_then_batch(const LaunchCfg& lc, const SceneView& sv, co
   const TreeForm tree = tree_form(sv);
   if (tree == TreeForm::Staged && sv.tris_any != sv.tris) return false;
   const hala_ray* rays = with_closest ? q.rays[(depth + 1u) & 1u] : nullptr;
-  with_flags([&](auto ALPHA, auto STAGED, auto INST) {
+  with_flags([&](auto ALPHA, auto STAGED, auto INST, auto GROUPS) {
     if constexpr (!(STAGED && INST))
-      hipLaunchKernelGGL((k_trace_shadow_then_batch<STAGED, ALPHA, INST>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, sv.tris_any,
-                         q, ps, ctl, depth, kinds, rays, q.hits, lc.spill, lc.refill);
-  }, sv.any_translucent != 0u, tree == TreeForm::Staged, tree == TreeForm::TwoLevel);
+      hipLaunchKernelGGL((k_trace_shadow_then_batch<STAGED, ALPHA, INST, GROUPS>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv,
+                         sv.tris_any, q, ps, ctl, depth, kinds, rays, q.hits, lc.spill, lc.refill);
+  }, sv.any_translucent != 0u, tree == TreeForm::Staged, tree == TreeForm::TwoLevel, (kinds & 1u) != 0u && ps.groups != nullptr);
   return true;
 }
 
@@ -908,16 +971,22 @@ void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, co
     const uint32_t group = 8u * (kSortWindow / threads);  // whole groups of 8 windows: k_shade's window -> XCD mapping permutes the blocks of a group
     grid.x = blocks_for(grid.x, group) * group;
   }
-  // the first-hit AOVs (RENDER_SPEC §13) are written by the depth-0 shade only
-  with_flags([&](auto PRIMARY, auto SIMPLE, auto SCATTER, auto AOV) {
-    if constexpr (!(SIMPLE && SCATTER) && (PRIMARY || !AOV)) hipLaunchKernelGGL((k_shade<PRIMARY, SIMPLE, SCATTER, AOV>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
-  }, depth == 0u, sv.simple_materials != 0u, !sv.simple_materials && sv.scatter_media, depth == 0u && (ps.aov_pos || ps.aov_ids));
+  // the first-hit AOVs (RENDER_SPEC §13) are written by the depth-0 shade only; the light groups (§14) by every shade
+  with_flags([&](auto PRIMARY, auto SIMPLE, auto SCATTER, auto AOV, auto GROUPS) {
+    if constexpr (!(SIMPLE && SCATTER) && (PRIMARY || !AOV))
+      hipLaunchKernelGGL((k_shade<PRIMARY, SIMPLE, SCATTER, AOV, GROUPS>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
+  }, depth == 0u, sv.simple_materials != 0u, !sv.simple_materials && sv.scatter_media, depth == 0u && (ps.aov_pos || ps.aov_ids), ps.groups != nullptr);
 }
 void launch_resolve(const FrameConst& fc, const PathState& ps, float4* accum, float4* albedo, float4* normal, float4* final_img, float4* pos,
-                    uint4* ids, hipStream_t s) {
-  with_flags([&](auto AOV) {
-    hipLaunchKernelGGL((k_resolve<AOV>), dim3(blocks_for(fc.pixel_slots * fc.views, 256)), dim3(256), 0, s, fc, ps, accum, albedo, normal, final_img, pos, ids);
-  }, pos != nullptr || ids != nullptr);
+                    uint4* ids, float4* group_images, size_t group_stride, hipStream_t s) {
+  with_flags([&](auto AOV, auto GROUPS) {
+    hipLaunchKernelGGL((k_resolve<AOV, GROUPS>), dim3(blocks_for(fc.pixel_slots * fc.views, 256)), dim3(256), 0, s, fc, ps, accum, albedo, normal, final_img,
+                       pos, ids, group_images, group_stride);
+  }, pos != nullptr || ids != nullptr, ps.groups != nullptr);
+}
+void launch_relight(const hala_global_uniform& u, const float4* group_images, size_t group_stride, uint32_t group_count, const RelightScales& sc, uint32_t n,
+                    float4* linear, float4* toned, hipStream_t s) {
+  hipLaunchKernelGGL(k_relight, dim3(blocks_for(n, 256)), dim3(256), 0, s, group_images, group_stride, group_count, sc, n, u, linear, toned);
 }
 void launch_sample_texture(const SceneView& sv, uint32_t tex, const float* uvl, uint32_t n, float4* out, hipStream_t s) {
   hipLaunchKernelGGL(k_sample_texture, dim3(blocks_for(n, 256)), dim3(256), 0, s, sv, tex, uvl, n, out);

@@ -37,9 +37,14 @@ bool launch_trace_shadow_then_batch(const LaunchCfg& lc, const SceneView& sv, co
 void launch_trace_primary(const LaunchCfg& lc, const SceneView& sv, const FrameConst& fc, hala_hit* hits, WorkCounters* work, Control* ctl,
                           uint32_t n_account /* real paths among fc.slot_count */, bool count, hipStream_t s);
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s);
-// pos / ids: the first-hit AOV images of RENDER_SPEC §13 (nullptr: off; both off: the kernel variant without them)
+// pos / ids: the first-hit AOV images of RENDER_SPEC §13 (nullptr: off; both off: the kernel variant without them).  group_images: the
+// light-group images of §14, group g at group_images + g * group_stride (read only while ps.groups is set: the GROUPS variants)
 void launch_resolve(const FrameConst& fc, const PathState& ps, float4* accum, float4* albedo, float4* normal, float4* final_img, float4* pos,
-                    uint4* ids, hipStream_t s);
+                    uint4* ids, float4* group_images, size_t group_stride, hipStream_t s);
+// RENDER_SPEC §14 relight: n pixels of the group images (group g at group_images + g * group_stride) -> linear R and tonemapped R * exposure
+struct RelightScales { float s[kMaxLightGroups][3]; };
+void launch_relight(const hala_global_uniform& u, const float4* group_images, size_t group_stride, uint32_t group_count, const RelightScales& sc,
+                    uint32_t n, float4* linear, float4* toned, hipStream_t s);
 void launch_scatter_tiles(const FrameConst& fc, const float4* gathered, float4* full, hipStream_t s);
 void launch_sample_texture(const SceneView& sv, uint32_t tex, const float* uvl, uint32_t n, float4* out, hipStream_t s);
 

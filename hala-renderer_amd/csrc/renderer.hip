@@ -202,6 +202,15 @@ struct hala_rt_renderer {
   DeviceArray<float4> ps_aov_pos;
   DeviceArray<uint4> ps_aov_ids;
   DeviceArray<uint32_t> d_inst_node, d_light_node;  // per instance / per light: the scene node it came from
+  // light groups (RENDER_SPEC §14; hala_rt_set_light_groups): group_count 0 = off.  The tables as set (they may cover more lights /
+  // materials than the committed scene has); group_img holds group g of every view at g * image_alloc(), laid out like accum
+  uint32_t group_count = 0, env_group = 0;
+  std::vector<uint32_t> light_group, material_group;
+  DeviceArray<uint32_t> d_light_group, d_material_group;
+  DeviceArray<P3> ps_groups;    // group_count x path slots (slot_count x batch_capacity), group-major
+  DeviceArray<float4> group_img;
+  DeviceArray<float4> relit[2];  // hala_rt_relight: linear, tonemapped (W x H)
+  bool relit_valid = false;
   DenoiseBuffers denoise;      // RENDER_SPEC 10: allocated by the first hala_rt_denoise
   bool denoised = false;       // denoise.out holds a result
   AdaptiveState adaptive;      // RENDER_SPEC 11: allocated by the first hala_rt_set_adaptive_sampling that enables it
@@ -308,7 +317,9 @@ struct hala_rt_renderer {
   }
   PathState path_state() const {
     return PathState{ps_lr.ptr, ps_le.ptr, ps_alb.ptr, ps_nrm.ptr, (aov_mask & 1u) ? ps_aov_pos.ptr : nullptr, (aov_mask & 2u) ? ps_aov_ids.ptr : nullptr,
-                     d_inst_node.ptr, d_light_node.ptr};
+                     d_inst_node.ptr, d_light_node.ptr,
+                     group_count ? ps_groups.ptr : nullptr, group_count ? d_light_group.ptr : nullptr, group_count ? d_material_group.ptr : nullptr,
+                     group_count, group_count ? (uint32_t)((size_t)slot_count * batch_capacity) : 0u, env_group};
   }
 
   // RENDER_SPEC §5 / §7.4 for packed camera `cam`: tan(yfov / 2) and the angular size of one pixel
@@ -468,6 +479,11 @@ int alloc_wavefront(hala_rt_renderer* r, uint32_t paths) {
   // first-hit AOVs (RENDER_SPEC §13): 16 B per path slot each, only while on
   if (r->aov_mask & 1u) RT_HIP(r->ps_aov_pos.resize(n)); else r->ps_aov_pos.release();
   if (r->aov_mask & 2u) RT_HIP(r->ps_aov_ids.resize(n)); else r->ps_aov_ids.release();
+  // light groups (RENDER_SPEC §14): 12 B per path slot and group; light connections carry the group in the top bits of the slot word
+  if (r->group_count) {
+    if (n > kGroupSlotMask) RT_FAIL("Light groups need fewer than 2^29 path slots (pixels x samples x views).");
+    RT_HIP(r->ps_groups.resize(n * r->group_count));
+  } else r->ps_groups.release();
   r->batch_capacity = paths;
   return HALA_OK;
 }
@@ -479,6 +495,8 @@ int alloc_frame_buffers(hala_rt_renderer* r) {
     if (!r->has_image(k)) { i.release(); continue; }
     RT_HIP(i.resize(n)); RT_HIP(hipMemsetAsync(i.ptr, 0, n * sizeof(float4), r->stream));
   }
+  if (r->group_count) { RT_HIP(r->group_img.resize(n * r->group_count)); RT_HIP(hipMemsetAsync(r->group_img.ptr, 0, r->group_img.bytes(), r->stream)); }
+  r->relit_valid = false;
   if (alloc_wavefront(r, 1) != HALA_OK) return HALA_ERR;
   RT_HIP(r->d_ctl.resize(2));  // updates alternate between the two: a tail still running accounts into its own
   RT_HIP(hipMemsetAsync(r->d_ctl.ptr, 0, 2 * sizeof(Control), r->stream));
@@ -1121,6 +1139,10 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
     if (r->views[v] >= r->hs.cameras.size())
       RT_FAIL("hala_rt_update: view " + std::to_string(v) + " renders camera " + std::to_string(r->views[v]) + ", but the committed scene has " +
               std::to_string(r->hs.cameras.size()) + " camera(s) (hala_rt_set_views).");
+  if (r->group_count && (r->hs.lights.size() > r->light_group.size() || r->hs.gpu_materials.size() > r->material_group.size()))  // RENDER_SPEC §14
+    RT_FAIL("hala_rt_update: the light groups cover " + std::to_string(r->light_group.size()) + " light(s) and " + std::to_string(r->material_group.size()) +
+            " material(s), but the committed scene has " + std::to_string(r->hs.lights.size()) + " and " + std::to_string(r->hs.gpu_materials.size()) +
+            " (hala_rt_set_light_groups).");
   const uint64_t first = r->total_frames;  // frame_index of the first frame of this batch = total_frames - 1 after its increment
   r->total_frames += frames;
   if (first >= r->max_frames) return HALA_OK;
@@ -1238,7 +1260,7 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
     if (timed) { hipEvent_t d = r->next_event(te); RT_HIP(hipEventRecord(d, s)); }
   }
   launch_resolve(fc, ps, r->img_local[0].ptr, r->img_local[1].ptr, r->img_local[2].ptr, r->img_local[3].ptr, r->has_image(4) ? r->img_local[4].ptr : nullptr,
-                 r->has_image(5) ? reinterpret_cast<uint4*>(r->img_local[5].ptr) : nullptr, ts);
+                 r->has_image(5) ? reinterpret_cast<uint4*>(r->img_local[5].ptr) : nullptr, r->group_img.ptr, r->image_alloc(), ts);
   RT_HIP(hipMemcpyAsync(te.host_totals, &ctl->totals, sizeof(Totals), hipMemcpyDeviceToHost, ts));
   if (timed) RT_HIP(hipMemcpyAsync(te.host_sizes, &ctl->sizes, sizeof(QueueSizes), hipMemcpyDeviceToHost, ts));
   // frame_begin -> frame_end spans the whole update, its tail included
@@ -1352,6 +1374,13 @@ int hala_rt_set_views(hala_rt_renderer* r, const uint32_t* camera_indices, uint3
     if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
     if (e != hipSuccess) { r->views = old_views; RT_HIP(e); }
   }
+  if (r->group_count) {  // light groups (RENDER_SPEC §14): every view's images, zero until its first update
+    hipError_t e = r->group_img.count < n * r->group_count ? r->group_img.resize(n * r->group_count) : hipSuccess;
+    if (e == hipSuccess) e = hipMemsetAsync(r->group_img.ptr, 0, r->group_img.bytes(), r->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    if (e != hipSuccess) { r->views = old_views; RT_HIP(e); }
+  }
+  r->relit_valid = false;
   r->reset_accumulation();
   return HALA_OK;
 }
@@ -1450,6 +1479,107 @@ int hala_rt_set_aovs(hala_rt_renderer* r, uint32_t mask) {
     RT_HIP(e);
   }
   r->reset_accumulation();
+  return HALA_OK;
+}
+
+// ---- light groups (RENDER_SPEC 14) ------------------------------------------------------------------------------------------
+static std::string light_groups_check(const hala_light_groups* g) {
+  if (g->group_count == 0 || g->group_count > kMaxLightGroups)
+    return "hala_rt_set_light_groups: group_count must be in 1.." + std::to_string(kMaxLightGroups) + ".";
+  if ((g->light_count && !g->light_group) || (g->material_count && !g->material_group))
+    return "hala_rt_set_light_groups: a table is null but its count is not 0.";
+  if (g->environment_group >= g->group_count) return "hala_rt_set_light_groups: the environment's group is out of range (>= group_count).";
+  for (uint32_t k = 0; k < g->light_count; ++k)
+    if (g->light_group[k] >= g->group_count) return "hala_rt_set_light_groups: the group of light " + std::to_string(k) + " is out of range (>= group_count).";
+  for (uint32_t k = 0; k < g->material_count; ++k)
+    if (g->material_group[k] >= g->group_count)
+      return "hala_rt_set_light_groups: the group of material " + std::to_string(k) + " is out of range (>= group_count).";
+  return "";
+}
+int hala_rt_set_light_groups(hala_rt_renderer* r, const hala_light_groups* g) {
+  if (g) {
+    const std::string bad = light_groups_check(g);  // first: the CPU tier pins it without a renderer
+    if (!bad.empty()) RT_FAIL(bad);
+  }
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (g && r->world > 1) RT_FAIL("hala_rt_set_light_groups: light groups are not available on a sharded renderer (world > 1).");
+  if (g && (size_t)r->slot_count * r->batch_capacity > kGroupSlotMask)
+    RT_FAIL("hala_rt_set_light_groups: light groups need fewer than 2^29 path slots (pixels x samples x views).");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins an open tail
+  RT_HIP(hipStreamSynchronize(r->stream));
+  auto off = [r]() {
+    r->group_count = 0; r->env_group = 0;
+    r->light_group.clear(); r->material_group.clear();
+    r->d_light_group.release(); r->d_material_group.release(); r->ps_groups.release(); r->group_img.release();
+    r->relit[0].release(); r->relit[1].release(); r->relit_valid = false;
+  };
+  off();
+  if (g) {
+    const size_t G = g->group_count, paths = (size_t)r->slot_count * r->batch_capacity, n = r->image_alloc();
+    hipError_t e = r->ps_groups.resize(paths * G);
+    if (e == hipSuccess) e = r->group_img.resize(n * G);
+    if (e == hipSuccess) e = hipMemsetAsync(r->group_img.ptr, 0, r->group_img.bytes(), r->stream);
+    if (e == hipSuccess) e = r->d_light_group.upload(g->light_group, g->light_count, r->stream);
+    if (e == hipSuccess) e = r->d_material_group.upload(g->material_group, g->material_count, r->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    if (e != hipSuccess) { off(); RT_HIP(e); }  // out of memory: the groups are off, the other images are untouched
+    r->group_count = g->group_count; r->env_group = g->environment_group;
+    r->light_group.assign(g->light_group, g->light_group + g->light_count);
+    r->material_group.assign(g->material_group, g->material_group + g->material_count);
+  }
+  r->reset_accumulation();
+  return HALA_OK;
+}
+static int light_group_view_check(hala_rt_renderer* r, uint32_t view) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (!r->group_count) RT_FAIL("Light groups are off (hala_rt_set_light_groups).");
+  if (view >= r->view_count()) RT_FAIL("The view does not exist (hala_rt_set_views set " + std::to_string(r->view_count()) + ").");
+  return HALA_OK;
+}
+int hala_rt_read_light_group(hala_rt_renderer* r, uint32_t view, uint32_t group, float* dst) {
+  if (light_group_view_check(r, view) != HALA_OK) return HALA_ERR;
+  if (group >= r->group_count) RT_FAIL("The light group does not exist (hala_rt_set_light_groups set " + std::to_string(r->group_count) + ").");
+  if (!dst) RT_FAIL("The output pointer is null!");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipStreamSynchronize(r->stream));
+  const size_t px = r->image_pixels();  // never sharded: the row-major frame
+  RT_HIP(hipMemcpy(dst, r->group_img.ptr + group * r->image_alloc() + view * px, px * sizeof(float4), hipMemcpyDeviceToHost));
+  return HALA_OK;
+}
+int hala_rt_relight(hala_rt_renderer* r, uint32_t view, const float* rgb_scales, uint32_t group_count) {
+  if (light_group_view_check(r, view) != HALA_OK) return HALA_ERR;
+  if (group_count != r->group_count) RT_FAIL("hala_rt_relight: group_count must be the light groups' count (" + std::to_string(r->group_count) + ").");
+  if (!rgb_scales) RT_FAIL("hala_rt_relight: the scales are null.");
+  RelightScales sc{};
+  for (uint32_t k = 0; k < 3u * group_count; ++k) {
+    if (!std::isfinite(rgb_scales[k])) RT_FAIL("hala_rt_relight: the scales must be finite.");
+    sc.s[k / 3u][k % 3u] = rgb_scales[k];
+  }
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  const size_t px = r->image_pixels();
+  RT_HIP(r->relit[0].resize(px)); RT_HIP(r->relit[1].resize(px));
+  hala_global_uniform u{};  // the renderer's output settings, as an update would upload them
+  u.exposure_value = r->exposure; u.enable_tonemap = r->enable_tonemap; u.enable_aces = r->enable_aces; u.use_simple_aces = r->use_simple_aces;
+  launch_relight(u, r->group_img.ptr + view * px, r->image_alloc(), r->group_count, sc, (uint32_t)px, r->relit[0].ptr, r->relit[1].ptr, r->stream);
+  RT_HIP(hipGetLastError());
+  r->relit_valid = true;
+  return HALA_OK;
+}
+int hala_rt_read_relit(hala_rt_renderer* r, int which, float* dst) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (which < 0 || which > 1 || !dst) RT_FAIL("Invalid argument.");
+  if (!r->relit_valid) RT_FAIL("Nothing relit: call hala_rt_relight while light groups are on first.");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipStreamSynchronize(r->stream));
+  RT_HIP(hipMemcpy(dst, r->relit[which].ptr, r->relit[which].bytes(), hipMemcpyDeviceToHost));
+  return HALA_OK;
+}
+int hala_rt_get_relit_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_t* bytes) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (which < 0 || which > 1 || !d_ptr || !bytes) RT_FAIL("Invalid argument.");
+  if (!r->relit_valid) RT_FAIL("Nothing relit: call hala_rt_relight while light groups are on first.");
+  *d_ptr = r->relit[which].ptr;
+  *bytes = r->relit[which].bytes();
   return HALA_OK;
 }
 
@@ -1666,6 +1796,7 @@ int hala_rt_set_tile_shard(hala_rt_renderer* r, uint32_t rank, uint32_t world, u
   if (tile_size == 0 || tile_size > 256) RT_FAIL("Invalid tile size.");
   if (world > 1 && r->adaptive.enabled) RT_FAIL("Adaptive sampling is on: a sharded frame cannot use it (hala_rt_set_adaptive_sampling(r, NULL) first).");
   if (world > 1 && r->view_count() > 1u) RT_FAIL("The renderer has several views: a sharded frame renders one (hala_rt_set_views with one camera first).");
+  if (world > 1 && r->group_count) RT_FAIL("Light groups are on: a sharded frame cannot use them (hala_rt_set_light_groups(r, NULL) first).");
   // a collective in flight belongs to the old shard: complete it (its receive buffer is laid out for the old world size)
   if (r->gather_pending && hala_rt_tile_allgather_finish(r) != HALA_OK) return HALA_ERR;
   // a communicator is bound to (rank, world): gather_recv is sized by it and the de-interleave indexes it by the shard's world

@@ -85,6 +85,7 @@ class HalaRenderer:
             return
         holder = scene_in_cpu.to_desc()
         self._check(self._lib.hala_rt_set_scene(self._h, holder.ptr()))
+        self._scene = scene_in_cpu  # set_light_groups resolves light node names through it
 
     def set_envmap(self, path_or_pixels, rotation=0.0):
         """src/rt_renderer.rs:1184-1195. A str/PathLike goes through the library's decoder (.hdr / .pfm);
@@ -211,6 +212,70 @@ class HalaRenderer:
         """[H, W, 4] uint32: (node, instance, material, triangle id) of the first hit of frame 0's sample; lights: (node, ~0, ~0,
         0x80000000 | light index); misses: all ~0"""
         return self.read_image(self.IDS, view=view).view(np.uint32)
+
+    # -- light groups (docs/RENDER_SPEC.md 14; include/halart.h "hala_rt_set_light_groups") --------------------------------------
+    def set_light_groups(self, lights=None, environment=0, materials=None, group_count=None):
+        """split the beauty image by emitter.  lights: a list of groups indexed by packed light (the order of packed_lights()), or a dict
+        {light node name: group} (every other light: group 0); environment: the environment's group; materials: one group for every
+        material (an int), a list indexed by material, or None — then all materials share one group of their own, one past the largest
+        group the lights and the environment use.  group_count: None = one past the largest group used.  set_light_groups(None) or no
+        arguments at all turns the feature off.  Restarts the accumulation."""
+        if lights is None and materials is None and group_count is None and environment == 0:
+            self._check(self._lib.hala_rt_set_light_groups(self._h, None))
+            self.light_group_count = 0
+            return
+        n_lights = len(self.packed_lights()[0])
+        if isinstance(lights, dict):
+            scene = getattr(self, "_scene", None)
+            if scene is None or not hasattr(scene, "nodes"):
+                raise ValueError("set_light_groups: a dict of light node names needs the HalaScene given to set_scene")
+            from .scene import INVALID
+            names = [nd.name for nd in scene.nodes if nd.light_index != INVALID]  # packed light order (RENDER_SPEC 7.2)
+            unknown = set(lights) - set(names)
+            if unknown:
+                raise ValueError(f"set_light_groups: no light node named {sorted(unknown)}")
+            lg = [int(lights.get(nm, 0)) for nm in names[:n_lights]]
+        else:
+            lg = [int(x) for x in (lights if lights is not None else [0] * n_lights)]
+        used = max(lg + [int(environment)]) + 1
+        if materials is None or isinstance(materials, (int, np.integer)):
+            n_mat = len(self.packed_materials())
+            mg = [used if materials is None else int(materials)] * n_mat
+        else:
+            mg = [int(x) for x in materials]
+        g = A.LightGroups()
+        g.group_count = int(group_count) if group_count is not None else max(lg + mg + [int(environment)]) + 1
+        g.environment_group = int(environment)
+        la, ma = (C.c_uint32 * max(len(lg), 1))(*lg), (C.c_uint32 * max(len(mg), 1))(*mg)
+        g.light_count, g.material_count = len(lg), len(mg)
+        g.light_group = C.cast(la, C.POINTER(C.c_uint32))
+        g.material_group = C.cast(ma, C.POINTER(C.c_uint32))
+        self._check(self._lib.hala_rt_set_light_groups(self._h, C.byref(g)))
+        self.light_group_count = g.group_count
+
+    def read_light_group(self, group, view=0) -> np.ndarray:
+        """[H, W, 4] float32: the running mean of light group `group`'s share of the beauty image (alpha 1)"""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self._lib.hala_rt_read_light_group(self._h, C.c_uint32(view), C.c_uint32(group), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def relight(self, scales, view=0):
+        """-> (linear, tonemapped) [H, W, 4] float32: sum over the groups of scales[g] * read_light_group(g) on the GPU; scales: one
+        RGB triple (or one float) per group, finite, negative values allowed; tonemapped = the renderer's operators on linear * exposure"""
+        sc = np.array([np.broadcast_to(np.asarray(s, np.float32), (3,)) for s in scales], dtype=np.float32).reshape(-1)
+        self._check(self._lib.hala_rt_relight(self._h, C.c_uint32(view), sc.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(len(scales))))
+        out = []
+        for which in (0, 1):
+            img = np.empty((self.height, self.width, 4), dtype=np.float32)
+            self._check(self._lib.hala_rt_read_relit(self._h, C.c_int(which), img.ctypes.data_as(C.POINTER(C.c_float))))
+            out.append(img)
+        return tuple(out)
+
+    def relit_buffer(self, which=0):
+        """-> (device address, bytes) of the last relit image (0 linear, 1 tonemapped; zero-copy, on the renderer's stream)"""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._lib.hala_rt_get_relit_buffer(self._h, C.c_int(which), C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     # -- denoising (docs/RENDER_SPEC.md 10; include/halart.h "hala_rt_denoise") -----------------------------------
     def denoise(self, iterations=None, sigma_color=None, sigma_albedo=None, normal_power=None, demodulate=True, timed=False):

@@ -407,6 +407,47 @@ int hala_rt_read_view_image(hala_rt_renderer* r, uint32_t view, int which, float
  * per-sample (deep) ids, no motion vectors, no denoiser guided by position. */
 int hala_rt_set_aovs(hala_rt_renderer* r, uint32_t mask);
 
+/* Light groups (docs/RENDER_SPEC.md 14; no reference equivalent): the beauty image split by emitter, so that a converged frame can be
+ * relit without rendering it again.  The sources are each packed light k (the order of hala_rt_get_packed_lights), the environment (SKY
+ * or MAP) and each material m (its surface emission, emission map included, and the glow of its EMISSIVE medium).  The descriptor maps
+ * every source to one group 0 .. group_count-1 (group_count 1..8); NULL turns the feature off, the default.  Images 0-5, statistics
+ * and the RNG are the same with groups on or off.
+ * Image g of a view is the running mean (in frame order, RGBA32F, alpha 1, laid out like accum) of S_g: the terms of RENDER_SPEC 6
+ * whose source is in g, added in the order 6 adds them to L, plus Le (the environment connections) for the environment's group
+ * when an environment map is set.  A non-finite S_g is replaced by 0 on its own.  Image g equals the accum image of the same renderer
+ * on the isolated scene of g (every light outside g at intensity 0, env_intensity 0 unless the environment is in g, every material
+ * outside g with emission 0 and, if its medium is EMISSIVE, medium colour 0) bit for bit, except in samples where a zeroed term is
+ * non-finite (0 * inf).  The images follow the views, adaptive sampling (converged blocks keep theirs), update_batch (k frames equal k
+ * updates) and the tail overlap like accum.
+ * Refused, with the renderer left as it was and before any device work: group_count 0 or > 8, a group index >= group_count, a null
+ * table with a nonzero count (these are checked before the handle is looked at), a sharded renderer (world > 1; hala_rt_set_tile_shard
+ * refuses the other order), and more than 2^29 - 1 path slots (pixels x samples x views: light connections carry the group in the top
+ * bits of their slot word).  An update whose committed scene has more lights or materials than the tables cover fails before any
+ * device work.  A successful call joins the tail of the last update, allocates (12 B per path slot and group, 16 B per pixel, view
+ * and group) or frees the buffers and restarts the accumulation.  Not built: gathering the images across ranks, groups in save_images,
+ * light path expressions beyond the emitter. */
+typedef struct hala_light_groups {
+  uint32_t group_count;          /* 1..8 */
+  uint32_t environment_group;
+  uint32_t light_count;          /* entries of light_group: packed light index -> group */
+  uint32_t material_count;       /* entries of material_group: material index -> group */
+  const uint32_t* light_group;
+  const uint32_t* material_group;
+} hala_light_groups;             /* 32 B */
+int hala_rt_set_light_groups(hala_rt_renderer* r, const hala_light_groups* g);
+/* image `group` of view `view` (W*H*4 floats, row 0 = top); waits like hala_rt_read_image.  Refused while groups are off or for a
+ * view / group that does not exist. */
+int hala_rt_read_light_group(hala_rt_renderer* r, uint32_t view, uint32_t group, float* dst_rgba32f);
+/* Relight view `view`: R = sum over g ascending of s_g * I_g from 0, per channel acc = acc + s * I (no fma); rgb_scales holds
+ * 3 * group_count finite floats (negative ones accepted), group_count must equal the descriptor's.  Writes the linear R (alpha 1) and
+ * tonemap(R * exposure_value) with the renderer's operators, exactly as the final image is written.  Stream-ordered on the renderer's
+ * stream; refused while groups are off or for a view that does not exist. */
+int hala_rt_relight(hala_rt_renderer* r, uint32_t view, const float* rgb_scales, uint32_t group_count);
+/* the last relit image: which 0 linear, 1 tonemapped (W*H*4 floats); refused before the first hala_rt_relight */
+int hala_rt_read_relit(hala_rt_renderer* r, int which, float* dst_rgba32f);
+/* zero-copy: device address and byte size of a relit image (valid until the next hala_rt_set_light_groups, or destroy) */
+int hala_rt_get_relit_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_t* bytes);
+
 /* info()/statistics() (src/renderer.rs:212-218, :135-207) */
 typedef struct hala_rt_info {
   uint32_t width;

@@ -39,6 +39,11 @@ pub mod sys {
   #[repr(C)] pub struct hala_camera_desc {
     pub type_: u32, pub aspect: f32, pub yfov: f32, pub znear: f32, pub zfar: f32, pub focal_distance: f32, pub aperture: f32, pub xmag: f32, pub ymag: f32,
   }
+  /// docs/RENDER_SPEC.md 14 (32 B): packed light / material / environment -> light group
+  #[repr(C)] pub struct hala_light_groups {
+    pub group_count: u32, pub environment_group: u32, pub light_count: u32, pub material_count: u32,
+    pub light_group: *const u32, pub material_group: *const u32,
+  }
   #[repr(C)] pub struct hala_image_desc { pub format: u32, pub width: u32, pub height: u32, pub data: *const c_void, pub num_of_bytes: usize }
   #[repr(C)] pub struct hala_index_pair { pub key: u32, pub value: u32 }
   #[repr(C)] pub struct hala_scene_desc {
@@ -121,6 +126,12 @@ pub mod sys {
                                         d_receive: *mut *mut c_void, receive_bytes: *mut usize, hip_stream: *mut *mut c_void) -> c_int;
     // first-hit AOVs (docs/RENDER_SPEC.md 13): mask bit 0 = image 4 position, bit 1 = image 5 ids
     pub fn hala_rt_set_aovs(r: *mut hala_rt_renderer, mask: u32) -> c_int;
+    // light groups (docs/RENDER_SPEC.md 14): g = NULL turns them off; relight which 0 = linear, 1 = tonemapped
+    pub fn hala_rt_set_light_groups(r: *mut hala_rt_renderer, g: *const hala_light_groups) -> c_int;
+    pub fn hala_rt_read_light_group(r: *mut hala_rt_renderer, view: u32, group: u32, dst_rgba32f: *mut f32) -> c_int;
+    pub fn hala_rt_relight(r: *mut hala_rt_renderer, view: u32, rgb_scales: *const f32, group_count: u32) -> c_int;
+    pub fn hala_rt_read_relit(r: *mut hala_rt_renderer, which: c_int, dst_rgba32f: *mut f32) -> c_int;
+    pub fn hala_rt_get_relit_buffer(r: *mut hala_rt_renderer, which: c_int, d_ptr: *mut *mut c_void, bytes: *mut usize) -> c_int;
     // cpu::HalaScene::new inside the library (for hosts without the Rust `src/scene` module)
     pub fn hala_scene_load_gltf(path: *const c_char, out: *mut *mut hala_scene) -> c_int;
     pub fn hala_scene_get_desc(scene: *const hala_scene) -> *const hala_scene_desc;
