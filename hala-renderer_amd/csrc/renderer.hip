@@ -2082,7 +2082,8 @@ int hala_rt_download_instance_refs(hala_rt_renderer* r, void* refs_64B, uint32_t
 }
 int hala_rt_update_node_transform(hala_rt_renderer* r, uint32_t node_index, const float local_transform[16]) {
   if (!r || !local_transform) RT_FAIL("Invalid argument.");
-  if (!r->has_scene || node_index >= r->hs.nodes.size()) RT_FAIL("The node does not exist.");
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");  // commit builds from what set_scene packed: an edit before it would not reach it
+  if (node_index >= r->hs.nodes.size()) RT_FAIL("The node does not exist.");
   memcpy(r->hs.nodes[node_index].local.m, local_transform, 64);
   return HALA_OK;
 }
@@ -2106,7 +2107,8 @@ int hala_rt_update_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
 }
 int hala_rt_update_material(hala_rt_renderer* r, uint32_t material_index, const hala_material_desc* material) {
   if (!r || !material) RT_FAIL("Invalid argument.");
-  if (!r->has_scene || material_index >= r->hs.materials.size()) RT_FAIL("The material does not exist.");
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  if (material_index >= r->hs.materials.size()) RT_FAIL("The material does not exist.");
   if (material->type > 1u) RT_FAIL("Invalid material type.");  // cpu/material.rs:14
   if (r->hs.materials[material_index].opacity == 0.0f || material->opacity == 0.0f) r->materials_dirty_any = true;
   r->hs.materials[material_index] = *material;

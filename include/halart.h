@@ -658,7 +658,9 @@ int hala_rt_get_bvh_info(hala_rt_renderer* r, hala_bvh_info* out);
 int hala_rt_download_bvh(hala_rt_renderer* r, void* nodes_64B, void* triangles_48B);
 int hala_rt_download_instance_refs(hala_rt_renderer* r, void* refs_64B, uint32_t capacity, uint32_t* count);
 /* Refit after vertex/transform edits (north_star "BVH build/refit"; the reference rebuilds only):
- * re-flattens instances with the given node local transforms and refits AABBs bottom-up on the GPU. */
+ * re-flattens instances with the given node local transforms and refits AABBs bottom-up on the GPU.  The three hala_rt_update_* calls
+ * need a committed scene (before hala_rt_commit they are refused) and take effect at the next hala_rt_refit: until then updates render
+ * the scene as it was and keep accumulating.  A refused call changes nothing; the edits made before it still apply at the refit. */
 int hala_rt_update_node_transform(hala_rt_renderer* r, uint32_t node_index, const float local_transform[16]);
 /* Deforming geometry: replaces the vertices of primitive `primitive_index` of mesh `mesh_index` (indices into the scene handed
  * to hala_rt_set_scene, cpu/mesh.rs: HalaMesh::primitives).  The vertex count must be the primitive's own (the topology, i.e. the
@@ -671,7 +673,9 @@ int hala_rt_update_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
 int hala_rt_update_material(hala_rt_renderer* r, uint32_t material_index, const hala_material_desc* material);
 /* Applies the edits: node hierarchies, materials, camera / light / instance records, and — if an instance's transform or a primitive's vertices
  * changed — the tree (topology kept, boxes re-derived).  A move of camera or light nodes alone leaves the tree untouched.  The
- * accumulation restarts either way. */
+ * accumulation restarts either way (every adaptive-sampling block is active again); the views, the AOV switches, the light-group
+ * tables and the adaptive-sampling parameters are kept.  hala_rt_denoise is refused until new samples (and, sharded, a new gather)
+ * arrive; hala_rt_read_denoised keeps returning the last denoised frame. */
 int hala_rt_refit(hala_rt_renderer* r);
 
 /* ------------------------------------------------------------------------------------------------
