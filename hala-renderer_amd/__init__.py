@@ -56,7 +56,8 @@ def check(status: int):
         raise HalaRendererError(last_error())
 
 
-from .renderer import HalaRenderer, adaptive_default_params, denoise_images, denoise_default_params, view_depth  # noqa: E402,F401
+from .renderer import (HalaRenderer, adaptive_default_params, cryptomatte_matte, denoise_images, denoise_default_params,  # noqa: E402,F401
+                       view_depth)
 from .raytracing_program import (HalaRayTracingProgram, HalaRayTracingProgramDesc,  # noqa: E402,F401
                                  HalaRayTracingHitShaderDesc)
 

@@ -197,6 +197,11 @@ class LightGroups(C.Structure):  # hala_light_groups, 32 B (docs/RENDER_SPEC.md 
                 ("material_count", C.c_uint32), ("light_group", C.POINTER(C.c_uint32)), ("material_group", C.POINTER(C.c_uint32))]
 
 
+class CryptomatteDesc(C.Structure):  # hala_cryptomatte_desc, 24 B (docs/RENDER_SPEC.md 15)
+    _fields_ = [("layer_mask", C.c_uint32), ("material_name_count", C.c_uint32), ("material_names", C.POINTER(C.c_char_p)),
+                ("reserved", C.c_uint32 * 2)]
+
+
 # argtypes / restype of the denoise, adaptive sampling, view and AOV entry points (load_library installs them)
 PROTOTYPES = {
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
@@ -218,6 +223,14 @@ PROTOTYPES = {
     "hala_rt_relight": ([C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_uint32], C.c_int),
     "hala_rt_read_relit": ([C.c_void_p, C.c_int, C.POINTER(C.c_float)], C.c_int),
     "hala_rt_get_relit_buffer": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)], C.c_int),
+    "hala_rt_set_cryptomatte": ([C.c_void_p, C.POINTER(CryptomatteDesc)], C.c_int),
+    "hala_rt_read_cryptomatte": ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_read_cryptomatte_records": ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)], C.c_int),
+    "hala_rt_get_cryptomatte_manifest": ([C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)], C.c_int),
+    "hala_rt_save_cryptomatte": ([C.c_void_p, C.c_uint32, C.c_char_p], C.c_int),
+    "hala_cryptomatte_hash": ([C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], C.c_int),
+    "hala_write_exr": ([C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_float)), C.c_uint32,
+                        C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)], C.c_int),
 }
 
 
@@ -256,4 +269,6 @@ EXPORTS = [
     "hala_adaptive_default_params", "hala_rt_set_adaptive_sampling", "hala_rt_read_sample_counts", "hala_rt_get_adaptive_status",
     "hala_rt_set_views", "hala_rt_read_view_image", "hala_rt_set_aovs",
     "hala_rt_set_light_groups", "hala_rt_read_light_group", "hala_rt_relight", "hala_rt_read_relit", "hala_rt_get_relit_buffer",
+    "hala_rt_set_cryptomatte", "hala_rt_read_cryptomatte", "hala_rt_read_cryptomatte_records", "hala_rt_get_cryptomatte_manifest",
+    "hala_rt_save_cryptomatte", "hala_cryptomatte_hash", "hala_write_exr",
 ]

@@ -55,6 +55,7 @@ std::string HostScene::assign(const hala_scene_desc* d) {
   for (uint32_t i = 0; i < d->node_count; ++i) {
     const hala_node_desc& nd = d->nodes[i];
     HostNode n;
+    if (nd.name) n.name = nd.name;
     n.parent = nd.parent;
     if (nd.parent >= (int32_t)i) return "Node hierarchy is not in parent-before-child order (src/scene/cpu/scene.rs:102-109).";
     memcpy(n.local.m, nd.local_transform, 64);

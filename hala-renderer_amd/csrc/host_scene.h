@@ -19,6 +19,7 @@ struct Mat4 {
 };
 
 struct HostNode {
+  std::string name;  // hala_node_desc::name ("" for a null one): the Cryptomatte object name (RENDER_SPEC §15)
   int32_t parent = -1;
   Mat4 local = Mat4::identity(), world = Mat4::identity();
   uint32_t mesh_index = HALA_INVALID_INDEX, camera_index = HALA_INVALID_INDEX, light_index = HALA_INVALID_INDEX;

@@ -1,16 +1,20 @@
 // host_util.cpp — error channel, JSON reader, and the host half of save_images / set_envmap:
 // tonemap operators and PFM writer (src/rt_renderer.rs:1256-1334), Radiance .hdr / .pfm decoding for
-// EnvMap::new_with_file (src/envmap.rs:48-60; the reference decodes through the `image` crate).
+// EnvMap::new_with_file (src/envmap.rs:48-60; the reference decodes through the `image` crate); the Cryptomatte name hash and the
+// OpenEXR writer (docs/RENDER_SPEC.md 15).
 #include <zlib.h>
 
 #include "host_util.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <numeric>
 
+#include "cryptomatte.h"
 #include "hala_types.h"
 #include "host_image.h"
 
@@ -185,6 +189,154 @@ std::string write_pfm(const char* path, const float* rgba, uint32_t width, uint3
     if (fwrite(row.data(), 4, row.size(), f) != row.size()) { fclose(f); return std::string("Failed to write the image file: \"") + path + "\""; }
   }
   if (fclose(f) != 0) return std::string("Failed to flush the image file: \"") + path + "\"";
+  return "";
+}
+
+// ---- Cryptomatte (docs/RENDER_SPEC.md 15): name hash, JSON strings, the OpenEXR writer -----------------------------------------
+uint32_t murmur3_32(const void* data, size_t len, uint32_t seed) {
+  const uint8_t* p = static_cast<const uint8_t*>(data);
+  const uint32_t c1 = 0xcc9e2d51u, c2 = 0x1b873593u;
+  auto rotl = [](uint32_t x, int r) { return (x << r) | (x >> (32 - r)); };
+  uint32_t h = seed;
+  const size_t blocks = len / 4;
+  for (size_t i = 0; i < blocks; ++i) {
+    uint32_t k = (uint32_t)p[4 * i] | (uint32_t)p[4 * i + 1] << 8 | (uint32_t)p[4 * i + 2] << 16 | (uint32_t)p[4 * i + 3] << 24;
+    k *= c1; k = rotl(k, 15); k *= c2;
+    h ^= k; h = rotl(h, 13); h = h * 5u + 0xe6546b64u;
+  }
+  const uint8_t* tail = p + 4 * blocks;
+  uint32_t k = 0;
+  switch (len & 3u) {
+    case 3: k ^= (uint32_t)tail[2] << 16; [[fallthrough]];
+    case 2: k ^= (uint32_t)tail[1] << 8; [[fallthrough]];
+    case 1: k ^= tail[0]; k *= c1; k = rotl(k, 15); k *= c2; h ^= k;
+  }
+  h ^= (uint32_t)len;
+  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+  return h;
+}
+
+std::string json_quote(const std::string& s) {
+  std::string o = "\"";
+  for (unsigned char c : s) {
+    switch (c) {
+      case '"': o += "\\\""; break;
+      case '\\': o += "\\\\"; break;
+      case '\b': o += "\\b"; break;
+      case '\f': o += "\\f"; break;
+      case '\n': o += "\\n"; break;
+      case '\r': o += "\\r"; break;
+      case '\t': o += "\\t"; break;
+      default:
+        if (c < 0x20u) { char b[8]; snprintf(b, sizeof(b), "\\u%04x", c); o += b; }
+        else o += (char)c;
+    }
+  }
+  return o + "\"";
+}
+
+namespace {
+void put_u32(std::vector<uint8_t>& b, uint32_t v) { for (int i = 0; i < 4; ++i) b.push_back((uint8_t)(v >> (8 * i))); }
+void put_f32(std::vector<uint8_t>& b, float v) { uint32_t u; memcpy(&u, &v, 4); put_u32(b, u); }
+void put_cstr(std::vector<uint8_t>& b, const std::string& s) { b.insert(b.end(), s.begin(), s.end()); b.push_back(0); }
+}  // namespace
+
+// OpenEXR 2.0, single part, scanline, ZIP: 16 lines per chunk; a chunk's lines hold every channel's samples, channel after channel in the
+// order of the (sorted) channel list; ZIP = bytes split into even / odd halves, a delta predictor (+128), zlib.  A chunk that zlib does not
+// shrink is stored as it is (readers take a chunk whose size equals the raw size as uncompressed).
+std::string write_exr(const char* path, uint32_t width, uint32_t height, uint32_t channel_count, const char* const* names,
+                      const float* const* planes, uint32_t attribute_count, const char* const* attr_names, const char* const* attr_values) {
+  if (!path || !*path) return "The file name is none!";
+  if (width == 0 || height == 0 || width > (1u << 20) || height > (1u << 20)) return "hala_write_exr: width and height must be in 1..2^20.";
+  if (channel_count == 0 || !names || !planes) return "hala_write_exr: at least one channel, with its name and pixels.";
+  if (attribute_count && (!attr_names || !attr_values)) return "hala_write_exr: an attribute table is null but its count is not 0.";
+  if ((uint64_t)16 * channel_count * width * 4 >= (1ull << 31)) return "hala_write_exr: a block of 16 lines must stay below 2^31 bytes (fewer channels or a narrower image).";
+  static const char* const kRequired[] = {"channels", "compression", "dataWindow", "displayWindow", "lineOrder", "pixelAspectRatio",
+                                          "screenWindowCenter", "screenWindowWidth"};
+  bool long_names = false;
+  std::vector<uint32_t> order(channel_count);
+  std::iota(order.begin(), order.end(), 0u);
+  for (uint32_t c = 0; c < channel_count; ++c) {
+    if (!names[c] || !*names[c] || !planes[c]) return "hala_write_exr: channel " + std::to_string(c) + " has no name or no pixels.";
+    const size_t n = strlen(names[c]);
+    if (n > 255) return "hala_write_exr: channel names are at most 255 bytes long.";
+    long_names = long_names || n > 31;
+  }
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return strcmp(names[a], names[b]) < 0; });
+  for (uint32_t c = 1; c < channel_count; ++c)
+    if (strcmp(names[order[c - 1]], names[order[c]]) == 0) return std::string("hala_write_exr: duplicate channel name \"") + names[order[c]] + "\".";
+  // header attributes, in ascending name order: the required ones and the caller's strings
+  std::vector<std::pair<std::string, std::pair<std::string, std::vector<uint8_t>>>> attrs;
+  std::vector<uint8_t> v;
+  for (uint32_t c : order) {
+    put_cstr(v, names[c]);
+    put_u32(v, 2u);                                    // FLOAT
+    v.push_back(0); v.push_back(0); v.push_back(0); v.push_back(0);  // pLinear, reserved
+    put_u32(v, 1u); put_u32(v, 1u);                    // x / y sampling
+  }
+  v.push_back(0);
+  attrs.push_back({"channels", {"chlist", v}});
+  attrs.push_back({"compression", {"compression", {3}}});  // ZIP_COMPRESSION
+  v.clear(); put_u32(v, 0u); put_u32(v, 0u); put_u32(v, width - 1); put_u32(v, height - 1);
+  attrs.push_back({"dataWindow", {"box2i", v}});
+  attrs.push_back({"displayWindow", {"box2i", v}});
+  attrs.push_back({"lineOrder", {"lineOrder", {0}}});  // INCREASING_Y
+  v.clear(); put_f32(v, 1.0f);
+  attrs.push_back({"pixelAspectRatio", {"float", v}});
+  attrs.push_back({"screenWindowWidth", {"float", v}});
+  v.clear(); put_f32(v, 0.0f); put_f32(v, 0.0f);
+  attrs.push_back({"screenWindowCenter", {"v2f", v}});
+  for (uint32_t a = 0; a < attribute_count; ++a) {
+    if (!attr_names[a] || !*attr_names[a] || !attr_values[a]) return "hala_write_exr: attribute " + std::to_string(a) + " has no name or no value.";
+    const std::string name = attr_names[a];
+    if (name.size() > 255) return "hala_write_exr: attribute names are at most 255 bytes long.";
+    for (const char* req : kRequired)
+      if (name == req) return "hala_write_exr: \"" + name + "\" is a required attribute the writer sets itself.";
+    const size_t n = strlen(attr_values[a]);
+    attrs.push_back({name, {"string", std::vector<uint8_t>(attr_values[a], attr_values[a] + n)}});
+    long_names = long_names || name.size() > 31;
+  }
+  std::sort(attrs.begin(), attrs.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+  for (size_t a = 1; a < attrs.size(); ++a)
+    if (attrs[a - 1].first == attrs[a].first) return "hala_write_exr: duplicate attribute \"" + attrs[a].first + "\".";
+  std::vector<uint8_t> file;
+  put_u32(file, 20000630u);
+  put_u32(file, 2u | (long_names ? 0x400u : 0u));  // version 2, single-part scanline (long names when some name exceeds 31 bytes)
+  for (const auto& a : attrs) {
+    put_cstr(file, a.first); put_cstr(file, a.second.first);
+    put_u32(file, (uint32_t)a.second.second.size());
+    file.insert(file.end(), a.second.second.begin(), a.second.second.end());
+  }
+  file.push_back(0);
+  const uint32_t chunks = (height + 15) / 16;
+  const size_t table = file.size();
+  file.resize(table + 8 * (size_t)chunks);
+  std::vector<uint8_t> raw, tmp, packed;
+  for (uint32_t k = 0; k < chunks; ++k) {
+    const uint32_t y0 = 16 * k, lines = std::min(16u, height - y0);
+    raw.resize((size_t)lines * channel_count * width * 4);
+    uint8_t* o = raw.data();
+    for (uint32_t l = 0; l < lines; ++l)
+      for (uint32_t c : order) { memcpy(o, planes[c] + (size_t)(y0 + l) * width, (size_t)width * 4); o += (size_t)width * 4; }  // little-endian host
+    const size_t n = raw.size(), half = (n + 1) / 2;
+    tmp.resize(n);
+    for (size_t i = 0; i < n; ++i) tmp[(i & 1) ? half + i / 2 : i / 2] = raw[i];
+    for (size_t i = n; i-- > 1;) tmp[i] = (uint8_t)(tmp[i] - tmp[i - 1] + 128);
+    uLongf out_len = compressBound((uLong)n);
+    packed.resize(out_len);
+    if (compress2(packed.data(), &out_len, tmp.data(), (uLong)n, Z_DEFAULT_COMPRESSION) != Z_OK) return "hala_write_exr: zlib failed.";
+    const bool keep_raw = out_len >= n;
+    const uint64_t at = file.size();
+    memcpy(&file[table + 8 * (size_t)k], &at, 8);
+    put_u32(file, y0);
+    put_u32(file, (uint32_t)(keep_raw ? n : out_len));
+    if (keep_raw) file.insert(file.end(), raw.begin(), raw.end());
+    else file.insert(file.end(), packed.begin(), packed.begin() + out_len);
+  }
+  FILE* f = fopen(path, "wb");
+  if (!f) return std::string("Failed to create the image file: \"") + path + "\"";
+  const size_t put = fwrite(file.data(), 1, file.size(), f);
+  if (fclose(f) != 0 || put != file.size()) return std::string("Failed to write the image file: \"") + path + "\"";
   return "";
 }
 

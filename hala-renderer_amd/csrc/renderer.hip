@@ -8,12 +8,14 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <string>
 #include <sys/stat.h>
 #include <vector>
 
 #include "adaptive.h"
+#include "cryptomatte.h"
 #include "denoise.h"
 #include "dyn_api.h"
 #include "hala_types.h"
@@ -211,6 +213,22 @@ struct hala_rt_renderer {
   DeviceArray<float4> group_img;
   DeviceArray<float4> relit[2];  // hala_rt_relight: linear, tonemapped (W x H)
   bool relit_valid = false;
+  // Cryptomatte (RENDER_SPEC §15; hala_rt_set_cryptomatte): layer mask 0 = off.  crypto_rec holds one 64-B record (4 quads) per pixel slot,
+  // view and enabled layer (cryptomatte.h: CryptoTables); the id tables are filled by the first update after commit, refit or the call.
+  // While on, the depth-0 shade writes the 16-B first-hit record of every path slot (ps_aov_ids) whether or not image 5 is on.
+  uint32_t crypto_mask = 0;
+  std::vector<std::string> crypto_material_names;  // the caller's names ("" = material<m>)
+  DeviceArray<uint4> crypto_rec;
+  std::vector<uint32_t> crypto_object, crypto_asset, crypto_material;  // ids per node / node / material, as uploaded
+  DeviceArray<uint32_t> d_crypto_object, d_crypto_asset, d_crypto_material;
+  bool crypto_tables = false;  // the tables belong to the committed scene
+  bool crypto_ready = false;   // an update has folded samples since the accumulation restarted
+  size_t crypto_quads() const { return 4 * (size_t)__builtin_popcount(crypto_mask) * view_count() * slot_count; }
+  bool wants_ids() const { return (aov_mask & 2u) || crypto_mask; }
+  CryptoTables crypto_view() const {
+    return CryptoTables{d_crypto_object.ptr, d_crypto_asset.ptr, d_crypto_material.ptr, (uint32_t)crypto_object.size(), (uint32_t)crypto_material.size(),
+                        crypto_mask, slot_count};
+  }
   DenoiseBuffers denoise;      // RENDER_SPEC 10: allocated by the first hala_rt_denoise
   bool denoised = false;       // denoise.out holds a result
   AdaptiveState adaptive;      // RENDER_SPEC 11: allocated by the first hala_rt_set_adaptive_sampling that enables it
@@ -316,7 +334,7 @@ struct hala_rt_renderer {
     return q;
   }
   PathState path_state() const {
-    return PathState{ps_lr.ptr, ps_le.ptr, ps_alb.ptr, ps_nrm.ptr, (aov_mask & 1u) ? ps_aov_pos.ptr : nullptr, (aov_mask & 2u) ? ps_aov_ids.ptr : nullptr,
+    return PathState{ps_lr.ptr, ps_le.ptr, ps_alb.ptr, ps_nrm.ptr, (aov_mask & 1u) ? ps_aov_pos.ptr : nullptr, wants_ids() ? ps_aov_ids.ptr : nullptr,
                      d_inst_node.ptr, d_light_node.ptr,
                      group_count ? ps_groups.ptr : nullptr, group_count ? d_light_group.ptr : nullptr, group_count ? d_material_group.ptr : nullptr,
                      group_count, group_count ? (uint32_t)((size_t)slot_count * batch_capacity) : 0u, env_group};
@@ -358,6 +376,7 @@ struct hala_rt_renderer {
     total_frames = 0;
     for (bool& v : full_valid) v = false;
     adaptive.restart(width * height);
+    crypto_ready = false;
   }
   // frames folded into the pixels that are still traced (every pixel with adaptive sampling off)
   uint32_t rendered_frames() const { return (uint32_t)std::min(total_frames, max_frames); }
@@ -476,15 +495,82 @@ int alloc_wavefront(hala_rt_renderer* r, uint32_t paths) {
   RT_HIP(r->ps_lr.resize(n)); RT_HIP(r->ps_le.resize(n)); RT_HIP(r->ps_alb.resize(n)); RT_HIP(r->ps_nrm.resize(n));
   RT_HIP(r->q_rays[0].resize(n)); RT_HIP(r->q_rays[1].resize(n)); RT_HIP(r->q_state[0].resize(n)); RT_HIP(r->q_state[1].resize(n));
   RT_HIP(r->q_hits.resize(n)); RT_HIP(r->q_perm.resize(n)); RT_HIP(r->q_shadow[0].resize(n)); RT_HIP(r->q_shadow[1].resize(n));
-  // first-hit AOVs (RENDER_SPEC §13): 16 B per path slot each, only while on
+  // first-hit AOVs (RENDER_SPEC §13): 16 B per path slot each, only while on (the ids also while Cryptomatte is on, §15)
   if (r->aov_mask & 1u) RT_HIP(r->ps_aov_pos.resize(n)); else r->ps_aov_pos.release();
-  if (r->aov_mask & 2u) RT_HIP(r->ps_aov_ids.resize(n)); else r->ps_aov_ids.release();
+  if (r->wants_ids()) RT_HIP(r->ps_aov_ids.resize(n)); else r->ps_aov_ids.release();
   // light groups (RENDER_SPEC §14): 12 B per path slot and group; light connections carry the group in the top bits of the slot word
   if (r->group_count) {
     if (n > kGroupSlotMask) RT_FAIL("Light groups need fewer than 2^29 path slots (pixels x samples x views).");
     RT_HIP(r->ps_groups.resize(n * r->group_count));
   } else r->ps_groups.release();
   r->batch_capacity = paths;
+  return HALA_OK;
+}
+
+// ---- Cryptomatte (RENDER_SPEC §15) on the host: names, id tables, records ---------------------------------------------------------
+std::string crypto_object_name(const HostScene& hs, uint32_t k) {
+  return hs.nodes[k].name.empty() ? "node" + std::to_string(k) : hs.nodes[k].name;
+}
+uint32_t crypto_root(const HostScene& hs, uint32_t k) {  // parents precede children (HostScene::assign), so this ends
+  while (hs.nodes[k].parent >= 0) k = (uint32_t)hs.nodes[k].parent;
+  return k;
+}
+std::string crypto_material_name(const hala_rt_renderer* r, uint32_t m) {
+  return m < r->crypto_material_names.size() && !r->crypto_material_names[m].empty() ? r->crypto_material_names[m] : "material" + std::to_string(m);
+}
+uint32_t crypto_name_id(const std::string& s) { return crypto_id(murmur3_32(s.data(), s.size(), 0u)); }
+// the unsharded slot of pixel (x, y) (RENDER_SPEC 9): where its record lives (cryptomatte.hip: crypto_slot)
+size_t crypto_host_slot(const hala_rt_renderer* r, uint32_t x, uint32_t y) {
+  if (kPixelBlock == 0u) return (size_t)y * r->width + x;
+  return ((size_t)(y / kPixelBlock) * r->blocks_x + x / kPixelBlock) * kPixelBlock * kPixelBlock + (y % kPixelBlock) * kPixelBlock + x % kPixelBlock;
+}
+// the first record of enabled layer `layer` and view `view`
+const uint4* crypto_records_of(const hala_rt_renderer* r, uint32_t view, uint32_t layer) {
+  const uint32_t slot = (uint32_t)__builtin_popcount(r->crypto_mask & ((1u << layer) - 1u));
+  return r->crypto_rec.ptr + 4 * (((size_t)slot * r->view_count() + view) * r->slot_count);
+}
+// every name the committed scene can produce in `layer`, with its id, in ascending byte order
+std::map<std::string, uint32_t> crypto_names(const hala_rt_renderer* r, uint32_t layer) {
+  const HostScene& hs = r->hs;
+  std::map<std::string, uint32_t> out;
+  if (layer == 1u) {
+    for (uint32_t m = 0; m < hs.gpu_materials.size(); ++m) { const std::string n = crypto_material_name(r, m); out[n] = crypto_name_id(n); }
+    return out;
+  }
+  std::vector<uint32_t> nodes(hs.instance_node);
+  nodes.insert(nodes.end(), hs.light_node.begin(), hs.light_node.end());
+  for (uint32_t k : nodes) {
+    const std::string n = crypto_object_name(hs, layer == 2u ? crypto_root(hs, k) : k);
+    out[n] = crypto_name_id(n);
+  }
+  return out;
+}
+// before an update's device work: the id tables of the committed scene (first update after commit, refit or hala_rt_set_cryptomatte) and
+// records sized for the current views (hala_rt_set_views may have changed them); nothing in flight may still read the old ones
+int crypto_prepare(hala_rt_renderer* r) {
+  if (!r->ps_aov_ids.ptr || r->ps_aov_ids.count < (size_t)r->slot_count * r->batch_capacity)
+    RT_FAIL("hala_rt_update: the first-hit records Cryptomatte folds are not allocated (call hala_rt_set_cryptomatte again).");
+  const size_t quads = r->crypto_quads();
+  if (r->crypto_tables && r->crypto_rec.count == quads) return HALA_OK;
+  if (r->join_tail() != HALA_OK) return HALA_ERR;
+  RT_HIP(hipStreamSynchronize(r->stream));
+  if (!r->crypto_tables) {
+    const HostScene& hs = r->hs;
+    const uint32_t nn = (uint32_t)hs.nodes.size(), nm = (uint32_t)hs.gpu_materials.size();
+    r->crypto_object.resize(nn); r->crypto_asset.resize(nn); r->crypto_material.resize(nm);
+    for (uint32_t k = 0; k < nn; ++k) r->crypto_object[k] = crypto_name_id(crypto_object_name(hs, k));
+    for (uint32_t k = 0; k < nn; ++k) r->crypto_asset[k] = r->crypto_object[crypto_root(hs, k)];
+    for (uint32_t m = 0; m < nm; ++m) r->crypto_material[m] = crypto_name_id(crypto_material_name(r, m));
+    RT_HIP(r->d_crypto_object.upload(r->crypto_object.data(), nn, r->stream));
+    RT_HIP(r->d_crypto_asset.upload(r->crypto_asset.data(), nn, r->stream));
+    RT_HIP(r->d_crypto_material.upload(r->crypto_material.data(), nm, r->stream));
+    r->crypto_tables = true;
+  }
+  if (r->crypto_rec.count != quads) {
+    RT_HIP(r->crypto_rec.resize(quads));
+    RT_HIP(hipMemsetAsync(r->crypto_rec.ptr, 0, r->crypto_rec.bytes(), r->stream));
+  }
+  RT_HIP(hipStreamSynchronize(r->stream));
   return HALA_OK;
 }
 
@@ -1112,6 +1198,7 @@ int hala_rt_commit(hala_rt_renderer* r) {
   if (r->hs.instances.empty()) RT_FAIL("The scene has no mesh primitive.");  // `primitives[0]` panics in the reference (gpu_uploader.rs:888)
   if (build_bvh(r) != HALA_OK) return HALA_ERR;
   r->committed = true;
+  r->crypto_tables = false;  // RENDER_SPEC §15: the next update hashes the committed scene's names
   r->reset_accumulation();
   return HALA_OK;
 }
@@ -1152,6 +1239,7 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
     RT_HIP(hipStreamSynchronize(r->stream));
     if (alloc_wavefront(r, samples * V) != HALA_OK) return HALA_ERR;
   }
+  if (r->crypto_mask && crypto_prepare(r) != HALA_OK) return HALA_ERR;  // RENDER_SPEC §15: id tables and records for this scene and views
   if (V > 1u) {  // the view table: tan_half / pixel_spread follow the cameras' yfov, which a new scene may change
     std::vector<ViewConst> table(V);
     for (uint32_t v = 0; v < V; ++v) table[v] = r->view_const(r->views[v], (float)r->height);
@@ -1261,6 +1349,10 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   }
   launch_resolve(fc, ps, r->img_local[0].ptr, r->img_local[1].ptr, r->img_local[2].ptr, r->img_local[3].ptr, r->has_image(4) ? r->img_local[4].ptr : nullptr,
                  r->has_image(5) ? reinterpret_cast<uint4*>(r->img_local[5].ptr) : nullptr, r->group_img.ptr, r->image_alloc(), ts);
+  if (r->crypto_mask) {  // RENDER_SPEC §15: fold the batch's first hits right behind the resolve, inside the same tail
+    launch_crypto_fold(fc, ps.aov_ids, r->crypto_view(), r->crypto_rec.ptr, ts);
+    r->crypto_ready = true;
+  }
   RT_HIP(hipMemcpyAsync(te.host_totals, &ctl->totals, sizeof(Totals), hipMemcpyDeviceToHost, ts));
   if (timed) RT_HIP(hipMemcpyAsync(te.host_sizes, &ctl->sizes, sizeof(QueueSizes), hipMemcpyDeviceToHost, ts));
   // frame_begin -> frame_end spans the whole update, its tail included
@@ -1470,12 +1562,13 @@ int hala_rt_set_aovs(hala_rt_renderer* r, uint32_t mask) {
     if (e == hipSuccess) e = hipMemsetAsync(r->img_local[k].ptr, 0, n * sizeof(float4), r->stream);
   }
   if (e == hipSuccess) { if (mask & 1u) e = r->ps_aov_pos.resize(paths); else r->ps_aov_pos.release(); }
-  if (e == hipSuccess) { if (mask & 2u) e = r->ps_aov_ids.resize(paths); else r->ps_aov_ids.release(); }
+  if (e == hipSuccess) { if (r->wants_ids()) e = r->ps_aov_ids.resize(paths); else r->ps_aov_ids.release(); }  // §15 keeps them
   if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
   if (e != hipSuccess) {  // out of memory: the AOVs are off, the other images are untouched
     r->aov_mask = 0;
     for (int k = 4; k < 6; ++k) r->img_local[k].release();
-    r->ps_aov_pos.release(); r->ps_aov_ids.release();
+    r->ps_aov_pos.release();
+    if (!r->crypto_mask) r->ps_aov_ids.release();
     RT_HIP(e);
   }
   r->reset_accumulation();
@@ -1580,6 +1673,147 @@ int hala_rt_get_relit_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_
   if (!r->relit_valid) RT_FAIL("Nothing relit: call hala_rt_relight while light groups are on first.");
   *d_ptr = r->relit[which].ptr;
   *bytes = r->relit[which].bytes();
+  return HALA_OK;
+}
+
+// ---- Cryptomatte (RENDER_SPEC 15) ------------------------------------------------------------------------------------------------
+static const char* const kCryptoLayerNames[kCryptoLayers] = {"CryptoObject", "CryptoMaterial", "CryptoAsset"};
+
+static std::string cryptomatte_check(const hala_cryptomatte_desc* d) {
+  if (d->layer_mask == 0u || d->layer_mask > 7u)
+    return "hala_rt_set_cryptomatte: layer_mask must be in 1..7 (bit 0 object, bit 1 material, bit 2 asset).";
+  if (d->material_name_count && !d->material_names) return "hala_rt_set_cryptomatte: the material name table is null but its count is not 0.";
+  if (d->reserved[0] || d->reserved[1]) return "hala_rt_set_cryptomatte: the reserved fields must be 0.";
+  return "";
+}
+int hala_rt_set_cryptomatte(hala_rt_renderer* r, const hala_cryptomatte_desc* d) {
+  if (d) {
+    const std::string bad = cryptomatte_check(d);  // first: the CPU tier pins it without a renderer
+    if (!bad.empty()) RT_FAIL(bad);
+  }
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (d && r->world > 1) RT_FAIL("hala_rt_set_cryptomatte: Cryptomatte is not available on a sharded renderer (world > 1).");
+  std::vector<std::string> names(d ? d->material_name_count : 0u);
+  for (size_t m = 0; m < names.size(); ++m) names[m] = d->material_names[m] ? d->material_names[m] : "";
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins an open tail
+  RT_HIP(hipStreamSynchronize(r->stream));
+  auto off = [r]() {
+    r->crypto_mask = 0; r->crypto_material_names.clear(); r->crypto_tables = false;
+    r->crypto_rec.release(); r->d_crypto_object.release(); r->d_crypto_asset.release(); r->d_crypto_material.release();
+    if (!(r->aov_mask & 2u)) r->ps_aov_ids.release();
+  };
+  off();
+  if (d) {
+    r->crypto_mask = d->layer_mask;
+    hipError_t e = r->ps_aov_ids.resize((size_t)r->slot_count * r->batch_capacity);
+    if (e == hipSuccess) e = r->crypto_rec.resize(r->crypto_quads());
+    if (e == hipSuccess) e = hipMemsetAsync(r->crypto_rec.ptr, 0, r->crypto_rec.bytes(), r->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    if (e != hipSuccess) { off(); RT_HIP(e); }  // out of memory: the feature is off, everything else untouched
+    r->crypto_material_names = std::move(names);
+  }
+  r->reset_accumulation();
+  return HALA_OK;
+}
+static int crypto_layer_check(hala_rt_renderer* r, uint32_t layer) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (!r->crypto_mask) RT_FAIL("Cryptomatte is off (hala_rt_set_cryptomatte).");
+  if (layer >= kCryptoLayers || !((r->crypto_mask >> layer) & 1u))
+    RT_FAIL("The Cryptomatte layer is off (hala_rt_set_cryptomatte enabled layer mask " + std::to_string(r->crypto_mask) + ").");
+  return HALA_OK;
+}
+static int crypto_read_check(hala_rt_renderer* r, uint32_t view, uint32_t layer) {
+  if (crypto_layer_check(r, layer) != HALA_OK) return HALA_ERR;
+  if (view >= r->view_count()) RT_FAIL("The view does not exist (hala_rt_set_views set " + std::to_string(r->view_count()) + ").");
+  if (!r->crypto_ready) RT_FAIL("No Cryptomatte samples since the accumulation restarted: update first.");
+  return HALA_OK;
+}
+int hala_rt_read_cryptomatte(hala_rt_renderer* r, uint32_t view, uint32_t layer, float* dst) {
+  if (crypto_read_check(r, view, layer) != HALA_OK) return HALA_ERR;
+  if (!dst) RT_FAIL("The output pointer is null!");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  const size_t px = (size_t)r->width * r->height;
+  DeviceArray<float4> out;
+  RT_HIP(out.resize(3 * px));
+  launch_crypto_rank(crypto_records_of(r, view, layer), r->width, r->height, r->blocks_x, out.ptr, r->stream);
+  RT_HIP(hipGetLastError());
+  RT_HIP(hipStreamSynchronize(r->stream));
+  RT_HIP(hipMemcpy(dst, out.ptr, out.bytes(), hipMemcpyDeviceToHost));
+  return HALA_OK;
+}
+int hala_rt_read_cryptomatte_records(hala_rt_renderer* r, uint32_t view, uint32_t layer, uint32_t* dst) {
+  if (crypto_read_check(r, view, layer) != HALA_OK) return HALA_ERR;
+  if (!dst) RT_FAIL("The output pointer is null!");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipStreamSynchronize(r->stream));
+  std::vector<uint4> rec((size_t)r->slot_count * 4);
+  RT_HIP(hipMemcpy(rec.data(), crypto_records_of(r, view, layer), rec.size() * sizeof(uint4), hipMemcpyDeviceToHost));
+  for (uint32_t y = 0; y < r->height; ++y)
+    for (uint32_t x = 0; x < r->width; ++x) memcpy(dst + 16 * ((size_t)y * r->width + x), &rec[4 * crypto_host_slot(r, x, y)], 64);
+  return HALA_OK;
+}
+static std::string crypto_manifest(const hala_rt_renderer* r, uint32_t layer) {
+  std::string j = "{";
+  for (const auto& kv : crypto_names(r, layer)) {
+    char hex[16];
+    snprintf(hex, sizeof(hex), "\"%08x\"", kv.second);
+    if (j.size() > 1) j += ",";
+    j += json_quote(kv.first) + ":" + hex;
+  }
+  return j + "}";
+}
+int hala_rt_get_cryptomatte_manifest(hala_rt_renderer* r, uint32_t layer, char* dst, size_t capacity, size_t* length) {
+  if (crypto_layer_check(r, layer) != HALA_OK) return HALA_ERR;
+  if (!length) RT_FAIL("The output pointer is null!");
+  const std::string j = crypto_manifest(r, layer);
+  *length = j.size();
+  if (dst) {
+    if (capacity < j.size() + 1) RT_FAIL("The destination buffer is too small (" + std::to_string(j.size() + 1) + " bytes needed).");
+    memcpy(dst, j.c_str(), j.size() + 1);
+  }
+  return HALA_OK;
+}
+int hala_rt_save_cryptomatte(hala_rt_renderer* r, uint32_t view, const char* path) {
+  RtRange range("halart::save_cryptomatte");
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (!r->crypto_mask) RT_FAIL("Cryptomatte is off (hala_rt_set_cryptomatte).");
+  if (crypto_read_check(r, view, (uint32_t)__builtin_ctz(r->crypto_mask)) != HALA_OK) return HALA_ERR;
+  if (!path || !*path) RT_FAIL("The file name is none!");
+  const size_t px = (size_t)r->width * r->height;
+  std::vector<float> accum(4 * px);
+  if (hala_rt_read_view_image(r, view, 0, accum.data()) != HALA_OK) return HALA_ERR;
+  std::vector<std::vector<float>> planes;
+  std::vector<std::string> names, attr_names, attr_values;
+  for (int c = 0; c < 4; ++c) {
+    names.push_back(std::string(1, "RGBA"[c]));
+    planes.emplace_back(px);
+    for (size_t i = 0; i < px; ++i) planes.back()[i] = accum[4 * i + c];
+  }
+  std::vector<float> ranked(12 * px);
+  for (uint32_t l = 0; l < kCryptoLayers; ++l) {
+    if (!((r->crypto_mask >> l) & 1u)) continue;
+    if (hala_rt_read_cryptomatte(r, view, l, ranked.data()) != HALA_OK) return HALA_ERR;
+    const std::string layer = kCryptoLayerNames[l];
+    for (int k = 0; k < 3; ++k)
+      for (int c = 0; c < 4; ++c) {
+        names.push_back(layer + "0" + std::to_string(k) + "." + "RGBA"[c]);
+        planes.emplace_back(px);
+        for (size_t i = 0; i < px; ++i) planes.back()[i] = ranked[4 * ((size_t)k * px + i) + c];
+      }
+    char key[16];
+    snprintf(key, sizeof(key), "%08x", murmur3_32(layer.data(), layer.size(), 0u));
+    const std::string base = "cryptomatte/" + std::string(key, 7) + "/";
+    attr_names.push_back(base + "name"); attr_values.push_back(layer);
+    attr_names.push_back(base + "hash"); attr_values.push_back("MurmurHash3_32");
+    attr_names.push_back(base + "conversion"); attr_values.push_back("uint32_to_float32");
+    attr_names.push_back(base + "manifest"); attr_values.push_back(crypto_manifest(r, l));
+  }
+  std::vector<const char*> np, an, av;
+  std::vector<const float*> pp;
+  for (size_t c = 0; c < names.size(); ++c) { np.push_back(names[c].c_str()); pp.push_back(planes[c].data()); }
+  for (size_t a = 0; a < attr_names.size(); ++a) { an.push_back(attr_names[a].c_str()); av.push_back(attr_values[a].c_str()); }
+  const std::string e = write_exr(path, r->width, r->height, (uint32_t)np.size(), np.data(), pp.data(), (uint32_t)an.size(), an.data(), av.data());
+  if (!e.empty()) RT_FAIL(e);
   return HALA_OK;
 }
 
@@ -1797,6 +2031,7 @@ int hala_rt_set_tile_shard(hala_rt_renderer* r, uint32_t rank, uint32_t world, u
   if (world > 1 && r->adaptive.enabled) RT_FAIL("Adaptive sampling is on: a sharded frame cannot use it (hala_rt_set_adaptive_sampling(r, NULL) first).");
   if (world > 1 && r->view_count() > 1u) RT_FAIL("The renderer has several views: a sharded frame renders one (hala_rt_set_views with one camera first).");
   if (world > 1 && r->group_count) RT_FAIL("Light groups are on: a sharded frame cannot use them (hala_rt_set_light_groups(r, NULL) first).");
+  if (world > 1 && r->crypto_mask) RT_FAIL("Cryptomatte is on: a sharded frame cannot use it (hala_rt_set_cryptomatte(r, NULL) first).");
   // a collective in flight belongs to the old shard: complete it (its receive buffer is laid out for the old world size)
   if (r->gather_pending && hala_rt_tile_allgather_finish(r) != HALA_OK) return HALA_ERR;
   // a communicator is bound to (rank, world): gather_recv is sized by it and the de-interleave indexes it by the shard's world
@@ -2164,6 +2399,7 @@ int hala_rt_refit(hala_rt_renderer* r) {
     if (configure_traversal(r) != HALA_OK) return HALA_ERR;
     r->vertices_dirty = false;
   }
+  r->crypto_tables = false;
   r->reset_accumulation();  // like the device-lost path: accumulation restarts (src/rt_renderer.rs:557)
   return HALA_OK;
 }
@@ -2189,6 +2425,19 @@ int hala_envmap_build_distribution(int device_ordinal, const float* rgba32f, uin
 
 void hala_tonemap_pixels(float* rgba32f, size_t pixel_count, int enable_tonemap, int enable_aces, int use_simple_aces) {
   if (rgba32f) tonemap_pixels(rgba32f, pixel_count, enable_tonemap, enable_aces, use_simple_aces);
+}
+int hala_cryptomatte_hash(const char* name, uint32_t* raw, uint32_t* id) {
+  if (!name) RT_FAIL("The name is null!");
+  const uint32_t h = murmur3_32(name, strlen(name), 0u);  // RENDER_SPEC 15: seed 0
+  if (raw) *raw = h;
+  if (id) *id = crypto_id(h);
+  return HALA_OK;
+}
+int hala_write_exr(const char* path, uint32_t width, uint32_t height, uint32_t channel_count, const char* const* channel_names,
+                   const float* const* planes, uint32_t attribute_count, const char* const* attr_names, const char* const* attr_values) {
+  const std::string e = write_exr(path, width, height, channel_count, channel_names, planes, attribute_count, attr_names, attr_values);
+  if (!e.empty()) RT_FAIL(e);
+  return HALA_OK;
 }
 int hala_write_pfm(const char* path, const float* rgba32f, uint32_t width, uint32_t height) {
   if (!path || !rgba32f) RT_FAIL("Invalid argument.");

@@ -277,6 +277,56 @@ class HalaRenderer:
         self._check(self._lib.hala_rt_get_relit_buffer(self._h, C.c_int(which), C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    # -- Cryptomatte (docs/RENDER_SPEC.md 15; include/halart.h "hala_rt_set_cryptomatte") ------------------------------------------------
+    CRYPTO_LAYERS = ("object", "material", "asset")
+
+    def _crypto_layer(self, layer):
+        return self.CRYPTO_LAYERS.index(layer) if isinstance(layer, str) else int(layer)
+
+    def set_cryptomatte(self, layers=("object", "material", "asset"), material_names=None):
+        """Cryptomatte ID mattes of the layers named ("object", "material", "asset"; None turns the feature off); material_names: a list
+        indexed by material (None or "" entries: material<m>).  Restarts the accumulation."""
+        if layers is None:
+            self._check(self._lib.hala_rt_set_cryptomatte(self._h, None))
+            return
+        mask = 0
+        for layer in layers:
+            mask |= 1 << self._crypto_layer(layer)
+        names = [None if n is None else str(n).encode("utf-8") for n in (material_names or [])]
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        d = A.CryptomatteDesc(layer_mask=mask, material_name_count=len(names), material_names=C.cast(arr, C.POINTER(C.c_char_p)))
+        self._check(self._lib.hala_rt_set_cryptomatte(self._h, C.byref(d)))
+
+    def read_cryptomatte(self, layer, view=0):
+        """-> (ids float32 [H, W, 6], coverage float32 [H, W, 6]) of ranks 0..5 (an id is the float whose bits are the uint32 id)"""
+        out = np.empty((3, self.height, self.width, 4), dtype=np.float32)
+        self._check(self._lib.hala_rt_read_cryptomatte(self._h, C.c_uint32(view), C.c_uint32(self._crypto_layer(layer)),
+                                                        out.ctypes.data_as(C.POINTER(C.c_float))))
+        ids = np.stack([out[r // 2][..., 2 * (r % 2)] for r in range(6)], axis=-1)
+        cov = np.stack([out[r // 2][..., 2 * (r % 2) + 1] for r in range(6)], axis=-1)
+        return ids, cov
+
+    def read_cryptomatte_records(self, layer, view=0) -> np.ndarray:
+        """[H, W, 16] uint32: n, other, (id, count) x 7 of every pixel"""
+        out = np.empty((self.height, self.width, 16), dtype=np.uint32)
+        self._check(self._lib.hala_rt_read_cryptomatte_records(self._h, C.c_uint32(view), C.c_uint32(self._crypto_layer(layer)),
+                                                                out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def cryptomatte_manifest(self, layer) -> dict:
+        """{name: 8 lowercase hex digits of the id} of every name the committed scene can produce in the layer"""
+        import json
+        n = C.c_size_t(0)
+        lay = C.c_uint32(self._crypto_layer(layer))
+        self._check(self._lib.hala_rt_get_cryptomatte_manifest(self._h, lay, None, C.c_size_t(0), C.byref(n)))
+        buf = C.create_string_buffer(n.value + 1)
+        self._check(self._lib.hala_rt_get_cryptomatte_manifest(self._h, lay, buf, C.c_size_t(n.value + 1), C.byref(n)))
+        return json.loads(buf.raw[:n.value].decode("utf-8"))
+
+    def save_cryptomatte(self, path, view=0):
+        """single-part scanline OpenEXR (ZIP): R, G, B, A = the view's accum and three sublayers per enabled layer, with the manifests"""
+        self._check(self._lib.hala_rt_save_cryptomatte(self._h, C.c_uint32(view), os.fsencode(path)))
+
     # -- denoising (docs/RENDER_SPEC.md 10; include/halart.h "hala_rt_denoise") -----------------------------------
     def denoise(self, iterations=None, sigma_color=None, sigma_albedo=None, normal_power=None, demodulate=True, timed=False):
         """filter accum / albedo / normal into the denoised image (stream-ordered; None: the library's default).  timed: wait and
@@ -532,6 +582,22 @@ def denoise_images(color, albedo, normal, device_ordinal=0, **params) -> np.ndar
     fp = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
     check(load_library().hala_denoise_images(device_ordinal, fp(c), fp(a), fp(n), w, h, C.byref(p), fp(out)))
     return out
+
+
+def cryptomatte_matte(ids, coverage, manifest, names) -> np.ndarray:
+    """[H, W] float32: what a compositor's keyer does with read_cryptomatte's (ids, coverage) — the coverage of the ranks whose id is one
+    of `names` (looked up in `manifest`), summed in rank order"""
+    missing = [n for n in names if n not in manifest]
+    if missing:
+        raise ValueError(f"cryptomatte_matte: no name {missing} in the manifest")
+    want = np.array([int(manifest[n], 16) for n in names], dtype=np.uint32)
+    bits = np.ascontiguousarray(ids, dtype=np.float32).view(np.uint32)
+    cov = np.asarray(coverage, dtype=np.float32)
+    sel = np.isin(bits, want) & (cov > 0)
+    acc = np.zeros(bits.shape[:-1], np.float32)
+    for r in range(bits.shape[-1]):
+        acc = (acc + np.where(sel[..., r], cov[..., r], np.float32(0.0))).astype(np.float32)
+    return acc
 
 
 def view_depth(position, camera):

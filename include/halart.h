@@ -404,7 +404,7 @@ int hala_rt_read_view_image(hala_rt_renderer* r, uint32_t view, int which, float
  * 16 B per path slot each, and restarts the accumulation.  read_image, read_view_image, tile_buffer, the scatter and exchange entry
  * points take `which` 4 / 5 and the all-gather masks bits 4 / 5 while that AOV is on, and refuse them while it is off.  Not built:
  * save_images does not write them (hala_write_pfm does), no depth image (view depth follows from position and the camera), no
- * per-sample (deep) ids, no motion vectors, no denoiser guided by position. */
+ * deep ids (coverage per id over every sample: hala_rt_set_cryptomatte), no motion vectors, no denoiser guided by position. */
 int hala_rt_set_aovs(hala_rt_renderer* r, uint32_t mask);
 
 /* Light groups (docs/RENDER_SPEC.md 14; no reference equivalent): the beauty image split by emitter, so that a converged frame can be
@@ -447,6 +447,46 @@ int hala_rt_relight(hala_rt_renderer* r, uint32_t view, const float* rgb_scales,
 int hala_rt_read_relit(hala_rt_renderer* r, int which, float* dst_rgba32f);
 /* zero-copy: device address and byte size of a relit image (valid until the next hala_rt_set_light_groups, or destroy) */
 int hala_rt_get_relit_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_t* bytes);
+
+/* Cryptomatte ID mattes (docs/RENDER_SPEC.md 15; no reference equivalent): per pixel, view and layer, a table of id -> coverage over every
+ * sample of the accumulation, in the Cryptomatte form (Psyop, 2015) that Nuke, Blender, Fusion and Houdini read.  Layers: bit 0 object
+ * (the name of the node a hit triangle's instance or a hit light came from; a null or empty name is node<k>), bit 1 material (material<m>,
+ * or the caller's name for m; a light has none), bit 2 asset (the object name of the node's root).  A name is hashed as its UTF-8 bytes
+ * with MurmurHash3_x86_32, seed 0; bit 23 of the hash is flipped when its exponent bits are 0 or 255, and the result is the stored id.
+ * Each sample's first hit (RENDER_SPEC 13; a miss has no id) is folded in frame order into one 64-B record per pixel, view and layer:
+ * [n, other, (id, count) x 7] as uint32, entries by count descending then id ascending, a sample whose id finds no room counts in other.
+ * Ranked output: ranks 0..5 as (id as float bits, count / n), sublayer k = ranks 2k and 2k + 1 as R, G, B, A.  Images 0-5, the
+ * statistics, the RNG and every existing refusal are the same with the feature on or off.  The records follow the views, adaptive sampling
+ * (converged blocks keep theirs), update_batch (k frames equal k updates) and the tail overlap; every restart of the accumulation empties
+ * them at the next frame 0.  NULL turns the feature off, the default.
+ * Refused, with the renderer left as it was and before any device work: layer_mask 0 or > 7, a null name table with a nonzero count,
+ * reserved words not 0 (these are checked before the handle is looked at), a sharded renderer (world > 1; hala_rt_set_tile_shard refuses
+ * the other order).  A successful call joins the tail of the last update, allocates (64 B per pixel, view and layer, and the 16-B
+ * first-hit record per path slot while image 5 is off) or frees the records and restarts the accumulation.  Cost: one HBM-bound fold
+ * launch per update in the tail, beside the resolve.  Not built: gathering the records across ranks, deep EXR, coverage
+ * through transparent surfaces, pixel filters other than the camera jitter's box, a preview channel, material names from glTF. */
+typedef struct hala_cryptomatte_desc {
+  uint32_t layer_mask;               /* bit 0 object, bit 1 material, bit 2 asset */
+  uint32_t material_name_count;      /* entries of material_names: material index -> UTF-8 name (NULL or "": material<m>) */
+  const char* const* material_names;
+  uint32_t reserved[2];              /* must be 0 */
+} hala_cryptomatte_desc;             /* 24 B */
+int hala_rt_set_cryptomatte(hala_rt_renderer* r, const hala_cryptomatte_desc* d);
+/* layer 0 object, 1 material, 2 asset of view `view`: the three ranked sublayers, image k (ranks 2k and 2k + 1 as R, G, B, A = id, coverage,
+ * id, coverage) at dst + k * W * H * 4, W*H*12 floats in all, row 0 = top; waits like hala_rt_read_image.  Refused while the layer is off,
+ * for a view that does not exist and before the first update after a restart of the accumulation. */
+int hala_rt_read_cryptomatte(hala_rt_renderer* r, uint32_t view, uint32_t layer, float* dst);
+/* the raw records of the same (W*H*16 uint32, row-major: n, other, id_0, count_0, ..., id_6, count_6), for tests and tools */
+int hala_rt_read_cryptomatte_records(hala_rt_renderer* r, uint32_t view, uint32_t layer, uint32_t* dst);
+/* the layer's manifest: the JSON object {"name":"xxxxxxxx",...} (8 lowercase hex digits of the id) of every name the committed scene can
+ * produce in it, in ascending byte order.  *length = its byte count without the terminating 0; dst NULL asks for the length only, else dst
+ * gets the text and a 0 (capacity >= length + 1, else refused).  Refused while the layer is off. */
+int hala_rt_get_cryptomatte_manifest(hala_rt_renderer* r, uint32_t layer, char* dst, size_t capacity, size_t* length);
+/* single-part scanline OpenEXR 2.0, ZIP (16 lines per block): R, G, B, A = the view's linear accum, and per enabled layer <Layer>00.R ...
+ * <Layer>02.A (CryptoObject, CryptoMaterial, CryptoAsset), all FLOAT, with the string attributes cryptomatte/<key>/name, /hash
+ * (MurmurHash3_32), /conversion (uint32_to_float32) and /manifest; key = the first 7 hex digits of the raw hash of the layer name.
+ * Refused like hala_rt_read_cryptomatte. */
+int hala_rt_save_cryptomatte(hala_rt_renderer* r, uint32_t view, const char* path);
 
 /* info()/statistics() (src/renderer.rs:212-218, :135-207) */
 typedef struct hala_rt_info {
@@ -755,6 +795,16 @@ int hala_load_float_image(const char* path, uint32_t* width, uint32_t* height, u
                           size_t capacity_floats);
 /* save_images' PFM writer (src/rt_renderer.rs:1318-1334). */
 int hala_write_pfm(const char* path, const float* rgba32f, uint32_t width, uint32_t height);
+/* Cryptomatte name hashing (docs/RENDER_SPEC.md 15), no GPU involved: raw = MurmurHash3_x86_32 of the bytes of `name`, seed 0; id = raw
+ * with bit 23 flipped when its exponent bits are 0 or 255 (either output may be NULL). */
+int hala_cryptomatte_hash(const char* name, uint32_t* raw, uint32_t* id);
+/* The OpenEXR writer of hala_rt_save_cryptomatte, no GPU involved: single-part scanline OpenEXR 2.0, ZIP compression (16 lines per block;
+ * a block that does not shrink is stored as it is), every channel FLOAT and written in ascending byte order of the names whatever the
+ * order given; planes[c] holds channel c's W*H floats, row 0 = top.  attr_names / attr_values: string attributes.  Refused: no channel, a
+ * null or empty name, duplicate names, a name longer than 255 bytes, a size of W or H outside 1..2^20, blocks of 2^31 bytes or more, an
+ * attribute named like one of the header attributes the writer sets itself. */
+int hala_write_exr(const char* path, uint32_t width, uint32_t height, uint32_t channel_count, const char* const* channel_names,
+                   const float* const* planes, uint32_t attribute_count, const char* const* attr_names, const char* const* attr_values);
 
 /* HalaRayTracingProgramDesc (src/raytracing_program.rs:25-55): parses the serde JSON field names and
  * defaults; returns the parsed counts (used by the host mirror of HalaRayTracingProgram::new). */

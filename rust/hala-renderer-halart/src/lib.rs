@@ -44,6 +44,10 @@ pub mod sys {
     pub group_count: u32, pub environment_group: u32, pub light_count: u32, pub material_count: u32,
     pub light_group: *const u32, pub material_group: *const u32,
   }
+  /// docs/RENDER_SPEC.md 15 (24 B): layer_mask bit 0 object, bit 1 material, bit 2 asset
+  #[repr(C)] pub struct hala_cryptomatte_desc {
+    pub layer_mask: u32, pub material_name_count: u32, pub material_names: *const *const c_char, pub reserved: [u32; 2],
+  }
   #[repr(C)] pub struct hala_image_desc { pub format: u32, pub width: u32, pub height: u32, pub data: *const c_void, pub num_of_bytes: usize }
   #[repr(C)] pub struct hala_index_pair { pub key: u32, pub value: u32 }
   #[repr(C)] pub struct hala_scene_desc {
@@ -132,6 +136,15 @@ pub mod sys {
     pub fn hala_rt_relight(r: *mut hala_rt_renderer, view: u32, rgb_scales: *const f32, group_count: u32) -> c_int;
     pub fn hala_rt_read_relit(r: *mut hala_rt_renderer, which: c_int, dst_rgba32f: *mut f32) -> c_int;
     pub fn hala_rt_get_relit_buffer(r: *mut hala_rt_renderer, which: c_int, d_ptr: *mut *mut c_void, bytes: *mut usize) -> c_int;
+    // Cryptomatte (docs/RENDER_SPEC.md 15): d = NULL turns it off; layer 0 object, 1 material, 2 asset
+    pub fn hala_rt_set_cryptomatte(r: *mut hala_rt_renderer, d: *const hala_cryptomatte_desc) -> c_int;
+    pub fn hala_rt_read_cryptomatte(r: *mut hala_rt_renderer, view: u32, layer: u32, dst: *mut f32) -> c_int;
+    pub fn hala_rt_read_cryptomatte_records(r: *mut hala_rt_renderer, view: u32, layer: u32, dst: *mut u32) -> c_int;
+    pub fn hala_rt_get_cryptomatte_manifest(r: *mut hala_rt_renderer, layer: u32, dst: *mut c_char, capacity: usize, length: *mut usize) -> c_int;
+    pub fn hala_rt_save_cryptomatte(r: *mut hala_rt_renderer, view: u32, path: *const c_char) -> c_int;
+    pub fn hala_cryptomatte_hash(name: *const c_char, raw: *mut u32, id: *mut u32) -> c_int;
+    pub fn hala_write_exr(path: *const c_char, width: u32, height: u32, channel_count: u32, channel_names: *const *const c_char,
+                          planes: *const *const f32, attribute_count: u32, attr_names: *const *const c_char, attr_values: *const *const c_char) -> c_int;
     // cpu::HalaScene::new inside the library (for hosts without the Rust `src/scene` module)
     pub fn hala_scene_load_gltf(path: *const c_char, out: *mut *mut hala_scene) -> c_int;
     pub fn hala_scene_get_desc(scene: *const hala_scene) -> *const hala_scene_desc;
