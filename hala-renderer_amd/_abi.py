@@ -202,6 +202,10 @@ class CryptomatteDesc(C.Structure):  # hala_cryptomatte_desc, 24 B (docs/RENDER_
                 ("reserved", C.c_uint32 * 2)]
 
 
+class TemporalParams(C.Structure):  # hala_temporal_params, 32 B (docs/RENDER_SPEC.md 16)
+    _fields_ = [("max_history", C.c_float), ("tol", C.c_float), ("min_weight", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
 # argtypes / restype of the denoise, adaptive sampling, view and AOV entry points (load_library installs them)
 PROTOTYPES = {
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
@@ -231,6 +235,13 @@ PROTOTYPES = {
     "hala_cryptomatte_hash": ([C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], C.c_int),
     "hala_write_exr": ([C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_float)), C.c_uint32,
                         C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)], C.c_int),
+    "hala_temporal_default_params": ([C.POINTER(TemporalParams)], None),
+    "hala_rt_set_temporal": ([C.c_void_p, C.POINTER(TemporalParams)], C.c_int),
+    "hala_rt_temporal_capture": ([C.c_void_p], C.c_int),
+    "hala_rt_temporal_resolve": ([C.c_void_p, C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_read_temporal": ([C.c_void_p, C.c_int, C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_get_temporal_buffer": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)], C.c_int),
+    "hala_rt_denoise_temporal": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
 }
 
 
@@ -271,4 +282,6 @@ EXPORTS = [
     "hala_rt_set_light_groups", "hala_rt_read_light_group", "hala_rt_relight", "hala_rt_read_relit", "hala_rt_get_relit_buffer",
     "hala_rt_set_cryptomatte", "hala_rt_read_cryptomatte", "hala_rt_read_cryptomatte_records", "hala_rt_get_cryptomatte_manifest",
     "hala_rt_save_cryptomatte", "hala_cryptomatte_hash", "hala_write_exr",
+    "hala_temporal_default_params", "hala_rt_set_temporal", "hala_rt_temporal_capture", "hala_rt_temporal_resolve", "hala_rt_read_temporal",
+    "hala_rt_get_temporal_buffer", "hala_rt_denoise_temporal",
 ]

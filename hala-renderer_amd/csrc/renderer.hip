@@ -23,6 +23,7 @@
 #include "host_scene.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "temporal.h"
 
 namespace rt { std::string decode_image_file_rgba8(const char* path, uint32_t* w, uint32_t* h, std::vector<uint8_t>* rgba); }  // gltf_loader.cpp
 
@@ -232,6 +233,7 @@ struct hala_rt_renderer {
   DenoiseBuffers denoise;      // RENDER_SPEC 10: allocated by the first hala_rt_denoise
   bool denoised = false;       // denoise.out holds a result
   AdaptiveState adaptive;      // RENDER_SPEC 11: allocated by the first hala_rt_set_adaptive_sampling that enables it
+  TemporalState temporal;      // RENDER_SPEC 16: allocated by hala_rt_set_temporal
   DeviceArray<P3> ps_lr, ps_le, ps_alb, ps_nrm;
   DeviceArray<hala_ray> q_rays[2];
   DeviceArray<float4> q_state[2];
@@ -1142,6 +1144,7 @@ int hala_rt_set_scene(hala_rt_renderer* r, const hala_scene_desc* scene) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   RT_HIP(hipStreamSynchronize(r->stream));
   r->has_scene = false; r->committed = false;  // "Release the old scene in the GPU." (src/rt_renderer.rs:1164)
+  r->temporal.drop_history();  // RENDER_SPEC §16: the history belongs to the old scene
   const std::string e = r->hs.assign(scene);
   if (!e.empty()) RT_FAIL(e);
   if (upload_packed(r) != HALA_OK) return HALA_ERR;
@@ -1199,6 +1202,7 @@ int hala_rt_commit(hala_rt_renderer* r) {
   if (build_bvh(r) != HALA_OK) return HALA_ERR;
   r->committed = true;
   r->crypto_tables = false;  // RENDER_SPEC §15: the next update hashes the committed scene's names
+  r->temporal.drop_history();  // RENDER_SPEC §16: instance and material indices mean something else now
   r->reset_accumulation();
   return HALA_OK;
 }
@@ -1442,6 +1446,7 @@ int hala_rt_set_views(hala_rt_renderer* r, const uint32_t* camera_indices, uint3
       RT_FAIL("hala_rt_set_views: camera index " + std::to_string(camera_indices[v]) + " is out of range (< " + std::to_string(HALA_MAX_CAMERA_COUNT) + ").");
   if (count > 1u && r->world > 1u) RT_FAIL("hala_rt_set_views: several views are not available on a sharded renderer (world > 1).");
   if (count > 1u && r->adaptive.enabled) RT_FAIL("hala_rt_set_views: several views are not available with adaptive sampling on.");
+  if (count > 1u && r->temporal.enabled) RT_FAIL("hala_rt_set_views: several views are not available with temporal reprojection on.");
   if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins an open tail
   RT_HIP(hipStreamSynchronize(r->stream));
   const size_t old_n = r->image_alloc();
@@ -1473,6 +1478,7 @@ int hala_rt_set_views(hala_rt_renderer* r, const uint32_t* camera_indices, uint3
     if (e != hipSuccess) { r->views = old_views; RT_HIP(e); }
   }
   r->relit_valid = false;
+  r->temporal.table_dirty = true;  // RENDER_SPEC §16: view 0 may render another camera
   r->reset_accumulation();
   return HALA_OK;
 }
@@ -1528,6 +1534,7 @@ int hala_rt_set_adaptive_sampling(hala_rt_renderer* r, const hala_adaptive_param
     if (kPixelBlock != 8u) RT_FAIL("Adaptive sampling needs the 8 x 8 pixel blocks of RENDER_SPEC 9 (this build has RT_PIXEL_BLOCK = " + std::to_string(kPixelBlock) + ").");
     if (r->world > 1) RT_FAIL("Adaptive sampling is not available on a sharded renderer (world > 1).");
     if (r->view_count() > 1u) RT_FAIL("Adaptive sampling is not available with several views (hala_rt_set_views with one camera first).");
+    if (r->temporal.enabled) RT_FAIL("Adaptive sampling is not available with temporal reprojection on (hala_rt_set_temporal(r, NULL) first).");
     if (!ad.enabled) {
       RT_HIP(hipStreamSynchronize(r->stream));
       const uint32_t blocks = r->blocks_x * ((r->height + kPixelBlock - 1) / kPixelBlock);
@@ -1553,6 +1560,7 @@ int hala_rt_set_aovs(hala_rt_renderer* r, uint32_t mask) {
   if (r->gather_stream) RT_HIP(hipStreamSynchronize(r->gather_stream));
   const uint32_t old = r->aov_mask;
   r->aov_mask = mask;
+  if ((mask & 3u) != 3u) r->temporal.drop_history();  // RENDER_SPEC §16: the history is validated against images 4 and 5
   hipError_t e = hipSuccess;
   const size_t n = r->image_alloc(), paths = (size_t)r->slot_count * r->batch_capacity;
   for (int k = 4; k < 6 && e == hipSuccess; ++k) {
@@ -1907,6 +1915,168 @@ int hala_rt_save_denoised(hala_rt_renderer* r, const char* path) {
   return HALA_OK;
 }
 
+// ---- temporal reprojection (RENDER_SPEC 16) ------------------------------------------------------------------------------------
+static int temporal_ready(hala_rt_renderer* r, const char* fn) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (!r->temporal.enabled) RT_FAIL(std::string(fn) + ": temporal reprojection is off (hala_rt_set_temporal).");
+  if ((r->aov_mask & 3u) != 3u) RT_FAIL(std::string(fn) + ": the position and ids AOVs must both be on (hala_rt_set_aovs(r, 3)).");
+  if (!r->committed) RT_FAIL(std::string(fn) + ": no scene is committed.");
+  if (r->views[0] >= r->hs.cameras.size()) RT_FAIL(std::string(fn) + ": view 0 renders a camera the committed scene lacks (hala_rt_set_views).");
+  return HALA_OK;
+}
+// The table of this resolve (temporal.h) and the launch, on the renderer's stream, which has joined the tail.  The table is rebuilt and
+// uploaded only while TemporalState::table_dirty (after a capture, a mark, a refit, ...), behind a wait for the resolves that still read the
+// old one; every other resolve is the launch alone.
+static int temporal_enqueue_resolve(hala_rt_renderer* r, hipEvent_t before = nullptr) {
+  TemporalState& t = r->temporal;
+  const HostScene& hs = r->hs;
+  const uint32_t cam = r->views[0];
+  const bool hist = t.has_history && t.world.size() == 16 * hs.instances.size() && t.inst_marked.size() == hs.instances.size() &&
+                    t.mat_marked.size() == hs.gpu_materials.size();
+  const uint32_t ni = hist ? (uint32_t)hs.instances.size() : 0u, nm = hist ? (uint32_t)hs.gpu_materials.size() : 0u;
+  if (t.table_dirty || !t.table.ptr) {
+    constexpr size_t kHeadWords = sizeof(TemporalHead) / 4, kInstWords = sizeof(TemporalInst) / 4;
+    std::vector<uint32_t> tab(kHeadWords + (size_t)ni * kInstWords + nm, 0u);
+    TemporalHead hd{};
+    hd.cur = temporal_camera(hs.cameras[cam], r->view_const(cam, (float)r->height).tan_half);
+    hd.prev = hist ? temporal_camera(t.cam, t.tan_half) : hd.cur;
+    hd.width = (float)r->width; hd.height = (float)r->height; hd.aspect = hd.width / hd.height;
+    hd.max_history = t.p.max_history; hd.tol = t.p.tol; hd.min_weight = t.p.min_weight;
+    hd.inst_count = ni; hd.mat_count = nm;
+    memcpy(tab.data(), &hd, sizeof(hd));
+    for (uint32_t i = 0; i < ni; ++i) {
+      TemporalInst ti{};
+      const bool ok = temporal_motion(&t.world[16 * (size_t)i], hs.instances[i].transform, ti.d);
+      ti.marked = (!ok || t.inst_marked[i]) ? 1u : 0u;
+      memcpy(tab.data() + kHeadWords + (size_t)i * kInstWords, &ti, sizeof(ti));
+    }
+    for (uint32_t m = 0; m < nm; ++m) tab[kHeadWords + (size_t)ni * kInstWords + m] = t.mat_marked[m] ? 1u : 0u;
+    RT_HIP(hipStreamSynchronize(r->stream));
+    RT_HIP(t.table.upload(tab.data(), tab.size(), r->stream));
+    RT_HIP(hipStreamSynchronize(r->stream));
+    t.table_dirty = false;
+  }
+  if (before) RT_HIP(hipEventRecord(before, r->stream));  // a timed resolve brackets the launch alone
+  launch_temporal_resolve(r->img_local[0].ptr, r->img_local[4].ptr, reinterpret_cast<const uint4*>(r->img_local[5].ptr), t.hc.ptr, t.hp.ptr,
+                          reinterpret_cast<const uint4*>(t.hi.ptr), t.table.ptr, r->width, r->height, r->rendered_frames(), hist, t.out[0].ptr,
+                          t.out[1].ptr, r->stream);
+  RT_HIP(hipGetLastError());
+  t.resolved = true;
+  return HALA_OK;
+}
+int hala_rt_set_temporal(hala_rt_renderer* r, const hala_temporal_params* p) {
+  if (p) {
+    const std::string bad = temporal_check_params(p);  // first: the CPU tier pins it without a renderer
+    if (!bad.empty()) RT_FAIL(bad);
+  }
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (p && r->world > 1) RT_FAIL("hala_rt_set_temporal: temporal reprojection is not available on a sharded renderer (world > 1).");
+  if (p && r->view_count() > 1u) RT_FAIL("hala_rt_set_temporal: temporal reprojection is not available with several views (hala_rt_set_views with one camera first).");
+  if (p && r->adaptive.enabled) RT_FAIL("hala_rt_set_temporal: temporal reprojection is not available with adaptive sampling on (hala_rt_set_adaptive_sampling(r, NULL) first).");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  TemporalState& t = r->temporal;
+  if (!p) {
+    if (t.enabled) { RT_HIP(hipStreamSynchronize(r->stream)); t.release(); }
+    return HALA_OK;
+  }
+  if (!t.enabled) {
+    const size_t n = (size_t)r->width * r->height;
+    hipError_t e = hipSuccess;
+    for (DeviceArray<float4>* a : {&t.hc, &t.hp, &t.hi, &t.out[0], &t.out[1]})
+      if (e == hipSuccess) e = a->resize(n);
+    if (e != hipSuccess) { t.release(); RT_HIP(e); }  // out of memory: the feature stays off
+    t.enabled = true;
+  }
+  t.p = *p;
+  t.table_dirty = true;
+  return HALA_OK;
+}
+int hala_rt_temporal_capture(hala_rt_renderer* r) {
+  RtRange range("halart::temporal_capture");
+  if (temporal_ready(r, "hala_rt_temporal_capture") != HALA_OK) return HALA_ERR;
+  if (r->rendered_frames() == 0) return HALA_OK;  // two edits with no frame between: the history stands
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (temporal_enqueue_resolve(r) != HALA_OK) return HALA_ERR;
+  TemporalState& t = r->temporal;
+  const size_t bytes = (size_t)r->width * r->height * sizeof(float4);
+  RT_HIP(hipMemcpyAsync(t.hc.ptr, t.out[0].ptr, bytes, hipMemcpyDeviceToDevice, r->stream));
+  RT_HIP(hipMemcpyAsync(t.hp.ptr, r->img_local[4].ptr, bytes, hipMemcpyDeviceToDevice, r->stream));
+  RT_HIP(hipMemcpyAsync(t.hi.ptr, r->img_local[5].ptr, bytes, hipMemcpyDeviceToDevice, r->stream));
+  const HostScene& hs = r->hs;
+  t.cam = hs.cameras[r->views[0]];
+  t.tan_half = r->view_const(r->views[0], (float)r->height).tan_half;
+  t.world.resize(16 * hs.instances.size());
+  for (size_t i = 0; i < hs.instances.size(); ++i) memcpy(&t.world[16 * i], hs.instances[i].transform, 64);
+  t.inst_marked.assign(hs.instances.size(), 0);
+  t.mat_marked.assign(hs.gpu_materials.size(), 0);
+  t.has_history = true;
+  t.table_dirty = true;
+  return HALA_OK;
+}
+int hala_rt_temporal_resolve(hala_rt_renderer* r, float* gpu_ms) {
+  RtRange range("halart::temporal_resolve");
+  if (temporal_ready(r, "hala_rt_temporal_resolve") != HALA_OK) return HALA_ERR;
+  if (r->rendered_frames() == 0) RT_FAIL("hala_rt_temporal_resolve: no sample has been folded since the accumulation restarted.");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!gpu_ms) return temporal_enqueue_resolve(r);
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  RT_HIP(hipEventCreate(&ev[0]));
+  if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipEventDestroy(ev[0]); RT_FAIL("hipEventCreate failed."); }
+  const int rc = temporal_enqueue_resolve(r, ev[0]);
+  hipError_t e = hipSuccess;
+  if (rc == HALA_OK) e = hipEventRecord(ev[1], r->stream);
+  if (rc == HALA_OK && e == hipSuccess) e = hipEventSynchronize(ev[1]);
+  if (rc == HALA_OK && e == hipSuccess) e = hipEventElapsedTime(gpu_ms, ev[0], ev[1]);
+  for (hipEvent_t x : ev) (void)hipEventDestroy(x);
+  if (rc != HALA_OK) return HALA_ERR;
+  if (e != hipSuccess) RT_FAIL(std::string("hala_rt_temporal_resolve: ") + hipGetErrorString(e));
+  return HALA_OK;
+}
+static int temporal_output_check(hala_rt_renderer* r, int which) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (which < 0 || which > 1) RT_FAIL("Invalid temporal image selector (0: temporal, 1: motion).");
+  if (!r->temporal.enabled) RT_FAIL("Temporal reprojection is off (hala_rt_set_temporal).");
+  if (!r->temporal.resolved) RT_FAIL("Nothing has been resolved yet (hala_rt_temporal_resolve).");
+  return HALA_OK;
+}
+int hala_rt_read_temporal(hala_rt_renderer* r, int which, float* dst) {
+  if (temporal_output_check(r, which) != HALA_OK) return HALA_ERR;
+  if (!dst) RT_FAIL("The output pointer is null!");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipStreamSynchronize(r->stream));
+  RT_HIP(hipMemcpy(dst, r->temporal.out[which].ptr, r->temporal.out[which].bytes(), hipMemcpyDeviceToHost));
+  return HALA_OK;
+}
+int hala_rt_get_temporal_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_t* bytes) {
+  if (temporal_output_check(r, which) != HALA_OK) return HALA_ERR;
+  if (!d_ptr || !bytes) RT_FAIL("Invalid argument.");
+  *d_ptr = r->temporal.out[which].ptr;
+  *bytes = r->temporal.out[which].bytes();
+  return HALA_OK;
+}
+int hala_rt_denoise_temporal(hala_rt_renderer* r, const hala_denoise_params* p, float* gpu_ms) {
+  RtRange range("halart::denoise_temporal");
+  const std::string bad = denoise_check_params(p);  // first, as in hala_rt_denoise
+  if (!bad.empty()) RT_FAIL(bad);
+  if (temporal_output_check(r, 0) != HALA_OK) return HALA_ERR;
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  RT_HIP(r->denoise.ensure(r->width, r->height));
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  if (gpu_ms) {
+    RT_HIP(hipEventCreate(&ev[0]));
+    if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipEventDestroy(ev[0]); RT_FAIL("hipEventCreate failed."); }
+  }
+  hipError_t e = gpu_ms ? hipEventRecord(ev[0], r->stream) : hipSuccess;
+  if (e == hipSuccess) e = denoise_enqueue(r->denoise, r->temporal.out[0].ptr, r->img_local[1].ptr, r->img_local[2].ptr, *p, r->stream);
+  if (e == hipSuccess && gpu_ms) e = hipEventRecord(ev[1], r->stream);
+  if (e == hipSuccess && gpu_ms) e = hipEventSynchronize(ev[1]);
+  if (e == hipSuccess && gpu_ms) e = hipEventElapsedTime(gpu_ms, ev[0], ev[1]);
+  for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+  if (e != hipSuccess) RT_FAIL(std::string("hala_rt_denoise_temporal: ") + hipGetErrorString(e));
+  r->denoised = true;
+  return HALA_OK;
+}
+
 int hala_rt_set_launch_timing_period(hala_rt_renderer* r, uint32_t period) {
   if (!r) RT_FAIL("The renderer handle is null!");
   r->launch_event_period = period;
@@ -2032,6 +2202,7 @@ int hala_rt_set_tile_shard(hala_rt_renderer* r, uint32_t rank, uint32_t world, u
   if (world > 1 && r->view_count() > 1u) RT_FAIL("The renderer has several views: a sharded frame renders one (hala_rt_set_views with one camera first).");
   if (world > 1 && r->group_count) RT_FAIL("Light groups are on: a sharded frame cannot use them (hala_rt_set_light_groups(r, NULL) first).");
   if (world > 1 && r->crypto_mask) RT_FAIL("Cryptomatte is on: a sharded frame cannot use it (hala_rt_set_cryptomatte(r, NULL) first).");
+  if (world > 1 && r->temporal.enabled) RT_FAIL("Temporal reprojection is on: a sharded frame cannot use it (hala_rt_set_temporal(r, NULL) first).");
   // a collective in flight belongs to the old shard: complete it (its receive buffer is laid out for the old world size)
   if (r->gather_pending && hala_rt_tile_allgather_finish(r) != HALA_OK) return HALA_ERR;
   // a communicator is bound to (rank, world): gather_recv is sized by it and the de-interleave indexes it by the shard's world
@@ -2041,6 +2212,7 @@ int hala_rt_set_tile_shard(hala_rt_renderer* r, uint32_t rank, uint32_t world, u
   RT_HIP(hipStreamSynchronize(r->stream));
   if (r->gather_stream) RT_HIP(hipStreamSynchronize(r->gather_stream));
   r->rank = rank; r->world = world; r->tile_size = tile_size;
+  r->temporal.drop_history();  // RENDER_SPEC §16
   compute_tiling(r);
   if (alloc_frame_buffers(r) != HALA_OK) return HALA_ERR;
   RT_HIP(hipStreamSynchronize(r->stream));
@@ -2337,6 +2509,9 @@ int hala_rt_update_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
   // the copy below reads the renderer's own host copy, which outlives it; earlier frames still read the arena: wait for them
   RT_HIP(hipStreamSynchronize(r->stream));
   r->vertices_dirty = true;
+  if (r->temporal.enabled)  // RENDER_SPEC §16: no motion is known under a deformation; every instance of the primitive starts without history
+    for (size_t i = 0; i < r->hs.instance_prim.size() && i < r->temporal.inst_marked.size(); ++i)
+      if (r->hs.instance_prim[i] == first + primitive_index) { r->temporal.inst_marked[i] = 1; r->temporal.table_dirty = true; }
   if (vertex_count) RT_HIP(hipMemcpyAsync(r->d_vertices.ptr + r->prim_vertex_offset[first + primitive_index], p.vertices.data(), (size_t)vertex_count * sizeof(hala_vertex), hipMemcpyHostToDevice, r->stream));
   return HALA_OK;
 }
@@ -2347,6 +2522,7 @@ int hala_rt_update_material(hala_rt_renderer* r, uint32_t material_index, const 
   if (material->type > 1u) RT_FAIL("Invalid material type.");  // cpu/material.rs:14
   if (r->hs.materials[material_index].opacity == 0.0f || material->opacity == 0.0f) r->materials_dirty_any = true;
   r->hs.materials[material_index] = *material;
+  if (r->temporal.enabled && material_index < r->temporal.mat_marked.size()) { r->temporal.mat_marked[material_index] = 1; r->temporal.table_dirty = true; }  // RENDER_SPEC §16
   return HALA_OK;
 }
 int hala_rt_refit(hala_rt_renderer* r) {
@@ -2400,6 +2576,7 @@ int hala_rt_refit(hala_rt_renderer* r) {
     r->vertices_dirty = false;
   }
   r->crypto_tables = false;
+  r->temporal.table_dirty = true;  // RENDER_SPEC §16: the instance transforms and the cameras were packed again
   r->reset_accumulation();  // like the device-lost path: accumulation restarts (src/rt_renderer.rs:557)
   return HALA_OK;
 }

@@ -1,0 +1,192 @@
+// temporal.hip — docs/RENDER_SPEC.md 16: temporal reprojection of the accumulated frame across scene edits.  One frame-space kernel
+// beside the integrator: k_temporal_resolve carries each pixel's mean first hit (image 4) back through the motion of its instance and the
+// captured camera, gathers the four bilinear taps of the history around that point, keeps the taps whose ids and position agree, and
+// blends them with the current accumulation by sample count.  Every operation is the one the spec writes, in its order
+// (-ffp-contract=off: an fma only where the spec says madd / dot), so that tests/temporal_ref.py reproduces both outputs bit for bit.
+//
+// Memory: per pixel three 16-B loads of the current frame, the 64-B motion record of its instance, three 16-B loads per tap and two 16-B
+// stores: 240 B requested and 32 B written when all four taps are in the frame.  Neighbouring pixels share their taps, so the unique traffic
+// is the six images read once (96 B per pixel) plus the two written; 16 x 16 workgroups keep the taps of a wave in a few lines.  The
+// cameras are wave-uniform and come in by scalar loads.  No LDS, no atomics (DESIGN.md "Temporal reprojection" has the measured time).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "rt_math.h"
+#include "temporal.h"
+
+namespace rt {
+
+namespace {
+
+constexpr uint32_t kTile = 16;  // 16 x 16 pixels per workgroup
+constexpr uint32_t kAbsentId = 0xFFFFFFFFu;
+
+struct Projected {
+  float u, v, z;  // continuous pixel coordinates (pixel centres are integers), view depth
+  bool ok;
+};
+
+// RENDER_SPEC 16 "Projection": the inverse of RENDER_SPEC 5 for an unjittered sample through the lens centre
+RT_DI Projected project(const TemporalCamera& cam, float width, float height, float aspect, f3 p) {
+  const f3 right = ld3(cam.right), up = ld3(cam.up), fwd = ld3(cam.forward);
+  const f3 v = p - ld3(cam.position);
+  const float ff = dot3(fwd, fwd);
+  const float vf = dot3(v, fwd);
+  const float a = dot3(v, right) / dot3(right, right);
+  const float b = dot3(v, up) / dot3(up, up);
+  Projected o;
+  o.z = vf * (1.0f / sqrtf(ff));
+  float ndc_x, ndc_y;
+  if (cam.type == 0u) {
+    const float c = vf / ff;
+    ndc_x = (a / c) / (aspect * cam.tan_half);
+    ndc_y = (b / c) / cam.tan_half;
+    o.ok = o.z > 0.0f;
+  } else {
+    ndc_x = a / cam.xmag;
+    ndc_y = b / cam.ymag;
+    o.ok = true;
+  }
+  o.u = ((ndc_x + 1.0f) * 0.5f) * width - 0.5f;
+  o.v = ((1.0f - ndc_y) * 0.5f) * height - 0.5f;
+  return o;
+}
+
+__global__ void __launch_bounds__(256) k_temporal_resolve(const float4* __restrict__ accum, const float4* __restrict__ pos, const uint4* __restrict__ ids,
+                                                          const float4* __restrict__ hc, const float4* __restrict__ hp, const uint4* __restrict__ hi,
+                                                          const uint32_t* __restrict__ table, uint32_t width, uint32_t height, float n,
+                                                          uint32_t has_history, float4* __restrict__ temporal, float4* __restrict__ motion) {
+  const uint32_t x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
+  if (x >= width || y >= height) return;
+  const uint32_t p = y * width + x;
+  const float4 c = accum[p];
+  float4 t_out = make_float4(c.x, c.y, c.z, n), m_out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const TemporalHead& hd = *reinterpret_cast<const TemporalHead*>(table);
+  const TemporalInst* insts = reinterpret_cast<const TemporalInst*>(table + sizeof(TemporalHead) / 4);
+  const uint32_t* mat_mark = table + sizeof(TemporalHead) / 4 + (size_t)hd.inst_count * (sizeof(TemporalInst) / 4);
+  const float4 pm = pos[p];
+  const uint4 id = ids[p];
+  bool history = has_history != 0u && id.y != kAbsentId && pm.w > 0.0f && id.y < hd.inst_count && id.z < hd.mat_count;
+  if (history) {
+    const float4* rec = reinterpret_cast<const float4*>(insts + id.y);
+    const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+    const uint32_t marked = __float_as_uint(rec[3].x) | mat_mark[id.z];
+    history = marked == 0u;
+    if (history) {
+      const f3 pw = f3{pm.x / pm.w, pm.y / pm.w, pm.z / pm.w};
+      const f3 pp = f3{__fmaf_rn(r0.z, pw.z, __fmaf_rn(r0.y, pw.y, __fmaf_rn(r0.x, pw.x, r0.w))),
+                       __fmaf_rn(r1.z, pw.z, __fmaf_rn(r1.y, pw.y, __fmaf_rn(r1.x, pw.x, r1.w))),
+                       __fmaf_rn(r2.z, pw.z, __fmaf_rn(r2.y, pw.y, __fmaf_rn(r2.x, pw.x, r2.w)))};
+      const Projected a = project(hd.prev, hd.width, hd.height, hd.aspect, pp);
+      const Projected b = project(hd.cur, hd.width, hd.height, hd.aspect, pw);
+      if (a.ok && b.ok) {
+        const float mx = a.u - b.u, my = a.v - b.v;
+        const float fx = (float)x + mx, fy = (float)y + my;
+        m_out = make_float4(mx, my, a.z, 1.0f);
+        if (fx > -1.0f && fx < hd.width && fy > -1.0f && fy < hd.height) {  // else all four taps are outside the frame (NaN fails)
+          const float x0f = floorf(fx), y0f = floorf(fy);
+          const float tx = fx - x0f, ty = fy - y0f;
+          const int x0 = (int)x0f, y0 = (int)y0f;
+          const float zt = hd.prev.type == 0u ? a.z : (2.0f * hd.prev.ymag) * sqrtf(dot3(ld3(hd.prev.up), ld3(hd.prev.up)));
+          const float lim = hd.tol * zt;
+          const float lim2 = lim * lim;
+          float sr = 0.0f, sg = 0.0f, sb = 0.0f, sh = 0.0f, sw = 0.0f;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
+            const float wx = (k & 1) ? tx : 1.0f - tx, wy = (k >> 1) ? ty : 1.0f - ty;
+            const float w = wx * wy;
+            if (qx < 0 || qx >= (int)width || qy < 0 || qy >= (int)height || !(w > 0.0f)) continue;
+            const uint32_t q = (uint32_t)qy * width + (uint32_t)qx;
+            const float4 qc = hc[q], qp = hp[q];
+            const uint4 qi = hi[q];
+            if (!(qc.w > 0.0f) || !(qp.w > 0.0f) || qi.y != id.y || qi.z != id.z) continue;
+            const float dx = qp.x / qp.w - pp.x, dy = qp.y / qp.w - pp.y, dz = qp.z / qp.w - pp.z;
+            const float d2 = (dx * dx + dy * dy) + dz * dz;
+            if (!(d2 <= lim2)) continue;
+            sr = sr + qc.x * w; sg = sg + qc.y * w; sb = sb + qc.z * w; sh = sh + qc.w * w;
+            sw = sw + w;
+          }
+          if (sw >= hd.min_weight) {  // min_weight > 0: at least one tap
+            const float hr = sr / sw, hg = sg / sw, hb = sb / sw, hl = sh / sw;
+            const float h = hl > hd.max_history ? hd.max_history : hl;
+            const float tw = h + n;
+            t_out = make_float4((hr * h + c.x * n) / tw, (hg * h + c.y * n) / tw, (hb * h + c.z * n) / tw, tw);
+          }
+        }
+      }
+    }
+  }
+  temporal[p] = t_out;
+  motion[p] = m_out;
+}
+
+}  // namespace
+
+std::string temporal_check_params(const hala_temporal_params* p) {
+  if (!p) return "The temporal parameters are null.";
+  if (!(p->max_history >= 1.0f && p->max_history <= 1048576.0f)) return "Invalid temporal max_history: expected a finite value in [1, 2^20].";  // NaN fails
+  if (!(p->tol >= 1e-6f && p->tol <= 1.0f)) return "Invalid temporal tol: expected a finite value in [1e-6, 1].";
+  if (!(p->min_weight > 0.0f && p->min_weight <= 1.0f)) return "Invalid temporal min_weight: expected a finite value in (0, 1].";
+  for (uint32_t v : p->reserved) if (v) return "The reserved words of the temporal parameters must be zero.";
+  return "";
+}
+
+bool temporal_motion(const float* w_prev, const float* w_cur, float d[12]) {
+  static const float kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  memcpy(d, kIdentity, sizeof(kIdentity));
+  if (memcmp(w_prev, w_cur, 64) == 0) return true;  // bit-equal transforms: exactly the identity
+  // a[r][c]: column-major 4 x 4, the affine part
+  const auto A = [w_cur](int r, int c) { return (double)w_cur[4 * c + r]; };
+  const auto P = [w_prev](int r, int c) { return (double)w_prev[4 * c + r]; };
+  double inv[3][3];
+  inv[0][0] = A(1, 1) * A(2, 2) - A(1, 2) * A(2, 1); inv[0][1] = A(0, 2) * A(2, 1) - A(0, 1) * A(2, 2); inv[0][2] = A(0, 1) * A(1, 2) - A(0, 2) * A(1, 1);
+  inv[1][0] = A(1, 2) * A(2, 0) - A(1, 0) * A(2, 2); inv[1][1] = A(0, 0) * A(2, 2) - A(0, 2) * A(2, 0); inv[1][2] = A(0, 2) * A(1, 0) - A(0, 0) * A(1, 2);
+  inv[2][0] = A(1, 0) * A(2, 1) - A(1, 1) * A(2, 0); inv[2][1] = A(0, 1) * A(2, 0) - A(0, 0) * A(2, 1); inv[2][2] = A(0, 0) * A(1, 1) - A(0, 1) * A(1, 0);
+  const double det = (A(0, 0) * inv[0][0] + A(0, 1) * inv[1][0]) + A(0, 2) * inv[2][0];
+  double scale = 1.0;
+  for (int c = 0; c < 3; ++c) scale = scale * std::sqrt((A(0, c) * A(0, c) + A(1, c) * A(1, c)) + A(2, c) * A(2, c));
+  if (!(std::fabs(det) > 1e-12 * scale)) return false;  // singular (NaN fails too)
+  for (auto& row : inv) for (double& v : row) v = v / det;
+  float out[12];
+  for (int r = 0; r < 3; ++r) {
+    double l[3];
+    for (int c = 0; c < 3; ++c) l[c] = (P(r, 0) * inv[0][c] + P(r, 1) * inv[1][c]) + P(r, 2) * inv[2][c];
+    const double t = P(r, 3) - ((l[0] * A(0, 3) + l[1] * A(1, 3)) + l[2] * A(2, 3));
+    out[4 * r + 0] = (float)l[0]; out[4 * r + 1] = (float)l[1]; out[4 * r + 2] = (float)l[2]; out[4 * r + 3] = (float)t;
+  }
+  for (float v : out) if (!std::isfinite(v)) return false;
+  memcpy(d, out, sizeof(out));
+  return true;
+}
+
+TemporalCamera temporal_camera(const hala_gpu_camera& c, float tan_half) {
+  TemporalCamera t{};
+  memcpy(t.position, c.position, 12); memcpy(t.right, c.right, 12); memcpy(t.up, c.up, 12); memcpy(t.forward, c.forward, 12);
+  t.tan_half = tan_half; t.xmag = c.focal_distance_or_xmag; t.ymag = c.aperture_or_ymag; t.type = c.type;
+  return t;
+}
+
+void launch_temporal_resolve(const float4* accum, const float4* pos, const uint4* ids, const float4* hc, const float4* hp, const uint4* hi,
+                             const uint32_t* table, uint32_t w, uint32_t h, uint32_t n, bool has_history, float4* temporal, float4* motion,
+                             hipStream_t s) {
+  const dim3 grid((w + kTile - 1) / kTile, (h + kTile - 1) / kTile), block(kTile, kTile);
+  hipLaunchKernelGGL(k_temporal_resolve, grid, block, 0, s, accum, pos, ids, hc, hp, hi, table, w, h, (float)n, has_history ? 1u : 0u, temporal, motion);
+}
+
+}  // namespace rt
+
+using namespace rt;
+
+static_assert(sizeof(hala_temporal_params) == 32, "hala_temporal_params is 32 B");
+
+void hala_temporal_default_params(hala_temporal_params* out) {
+  if (!out) return;
+  memset(out, 0, sizeof(*out));
+  out->max_history = 32.0f;  // DESIGN.md "Temporal reprojection" has the sweep behind the two
+  out->tol = 0.05f;
+  out->min_weight = 0.25f;
+}

@@ -352,6 +352,48 @@ class HalaRenderer:
         """<stem>_denoised.pfm, tonemapped on the host like save_images' <stem>_color.pfm"""
         self._check(self._lib.hala_rt_save_denoised(self._h, os.fsencode(path)))
 
+    # -- temporal reprojection (docs/RENDER_SPEC.md 16; include/halart.h "hala_rt_set_temporal") ---------------------------------------
+    def set_temporal(self, enable=True, max_history=None, tol=None, min_weight=None):
+        """carry the accumulated frame across scene edits (needs set_aovs(position=True, ids=True)); None: the library's default;
+        enable=False turns the feature off and frees its buffers.  Does not restart the accumulation."""
+        if not enable:
+            self._check(self._lib.hala_rt_set_temporal(self._h, None))
+            return
+        p = temporal_default_params(max_history=max_history, tol=tol, min_weight=min_weight)
+        self._check(self._lib.hala_rt_set_temporal(self._h, C.byref(p)))
+
+    def temporal_capture(self):
+        """keep the frame as it stands as the history; call it before update_node_transform / update_vertices / update_material"""
+        self._check(self._lib.hala_rt_temporal_capture(self._h))
+
+    def temporal_resolve(self, timed=False):
+        """blend the accumulation with the reprojected history (stream-ordered).  timed: wait and return the GPU milliseconds"""
+        ms = C.c_float(0.0)
+        self._check(self._lib.hala_rt_temporal_resolve(self._h, C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
+    def read_temporal(self, which=0) -> np.ndarray:
+        """[H, W, 4] float32 of the last resolve: 0 / "temporal" = (rgb, history length + samples), 1 / "motion" = (dx, dy, view depth, 1)"""
+        if isinstance(which, str):
+            which = ("temporal", "motion").index(which)
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self._lib.hala_rt_read_temporal(self._h, C.c_int(which), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def temporal_buffer(self, which=0):
+        """-> (device address, bytes) of the temporal (0) or motion (1) image (zero-copy, on the renderer's stream)"""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._lib.hala_rt_get_temporal_buffer(self._h, C.c_int(which), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def denoise_temporal(self, iterations=None, sigma_color=None, sigma_albedo=None, normal_power=None, demodulate=True, timed=False):
+        """denoise() with the temporal image of the last resolve as colour; the result is read with read_denoised()"""
+        p = denoise_default_params(iterations=iterations, sigma_color=sigma_color, sigma_albedo=sigma_albedo,
+                                   normal_power=normal_power, demodulate=demodulate)
+        ms = C.c_float(0.0)
+        self._check(self._lib.hala_rt_denoise_temporal(self._h, C.byref(p), C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
     # -- adaptive sampling (docs/RENDER_SPEC.md 11; include/halart.h "hala_rt_set_adaptive_sampling") -------------------------------
     def set_adaptive_sampling(self, threshold, min_samples=None, interval=None):
         """stop tracing the 8 x 8 pixel blocks whose error estimate fell below `threshold` (None: turn the feature off); None for
@@ -554,6 +596,17 @@ def adaptive_default_params(**overrides) -> A.AdaptiveParams:
     from . import load_library
     p = A.AdaptiveParams()
     load_library().hala_adaptive_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def temporal_default_params(**overrides) -> A.TemporalParams:
+    """hala_temporal_default_params with the fields given (not None) replaced"""
+    from . import load_library
+    p = A.TemporalParams()
+    load_library().hala_temporal_default_params(C.byref(p))
     for k, v in overrides.items():
         if v is not None:
             setattr(p, k, v)

@@ -779,6 +779,54 @@ int hala_rt_read_sample_counts(hala_rt_renderer* r, uint32_t* dst);
 int hala_rt_get_adaptive_status(hala_rt_renderer* r, hala_adaptive_status* out);
 
 /* ------------------------------------------------------------------------------------------------
+ * Temporal reprojection (docs/RENDER_SPEC.md 16; no reference equivalent): carries the accumulated frame across a scene edit.
+ * hala_rt_temporal_capture keeps the frame as the history before an edit; after hala_rt_refit and a few new samples,
+ * hala_rt_temporal_resolve reprojects the history through the captured camera and instance transforms, validates each tap against ids and
+ * position, and blends it with the new samples by sample count.  A frame-space pass beside the integrator: images 0-5, statistics and
+ * the existing refusals are the same with the feature on or off, and nothing is allocated for a renderer that never enables it.
+ *
+ *   hala_rt_set_aovs(r, 3); hala_rt_set_temporal(r, &params);
+ *   ... updates ...   hala_rt_temporal_capture(r);                       // before the edit
+ *   hala_rt_update_node_transform(...); hala_rt_refit(r);                 // the accumulation restarts
+ *   hala_rt_update_batch(r, 4); hala_rt_temporal_resolve(r, NULL);        // 4 new samples + the reprojected history
+ *   hala_rt_read_temporal(r, 0, dst);  or  hala_rt_denoise_temporal(r, &dp, NULL);
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hala_temporal_params {
+  float max_history;    /* the history length (in samples) a pixel may carry over, in [1, 2^20]: bounds the lag of indirect light */
+  float tol;            /* a tap is kept when its stored position lies within tol * (view depth) of the reprojected point, in [1e-6, 1] */
+  float min_weight;     /* the least bilinear weight the valid taps must add up to, in (0, 1] */
+  uint32_t reserved[5]; /* must be zero */
+} hala_temporal_params; /* 32 B */
+/* the defaults of RENDER_SPEC 16 (DESIGN.md "Temporal reprojection" records what stands behind them) */
+void hala_temporal_default_params(hala_temporal_params* out);
+/* RENDER_SPEC 16: p enables the feature with these parameters (a second call only replaces them and keeps the history); NULL turns it
+ * off and frees its buffers.  Does not restart the accumulation.  Refused, with the renderer left as it was: invalid parameters (checked
+ * before the handle is looked at), a sharded renderer (world > 1), several views, adaptive sampling on.  While the feature is on,
+ * hala_rt_set_views with several views, hala_rt_set_adaptive_sampling with parameters and hala_rt_set_tile_shard with world > 1 are
+ * refused in turn. */
+int hala_rt_set_temporal(hala_rt_renderer* r, const hala_temporal_params* p);
+/* RENDER_SPEC 16 "Capture": call it before editing the scene.  With samples folded since the last restart it resolves, then keeps the
+ * resolved image, images 4 and 5, view 0's packed camera and every instance's world transform as the history (device-to-device copies on
+ * the renderer's stream) and clears the edit marks; with none (two edits without a frame between) it succeeds and keeps the history it
+ * has.  Refused: the feature is off, AOV bits 0 and 1 are not both on. */
+int hala_rt_temporal_capture(hala_rt_renderer* r);
+/* RENDER_SPEC 16 "Resolve": view 0's accumulation blended with the reprojected history into the temporal image, and the motion image.
+ * Stream-ordered behind the updates enqueued so far; returns without waiting when gpu_ms is NULL, else times its launch with HIP events,
+ * waits and stores the milliseconds.  Without a history every pixel is the accumulation with its sample count.  Writes none of images
+ * 0-5.  Refused: the feature is off, AOV bits 0 and 1 are not both on, no sample folded since the accumulation restarted. */
+int hala_rt_temporal_resolve(hala_rt_renderer* r, float* gpu_ms);
+/* RENDER_SPEC 16 "Outputs": which = 0 the temporal image (rgb, history length + samples), 1 the motion image (dx, dy in pixels towards
+ * the history, view depth in the captured camera, 1; all 0 where nothing was reprojected); W*H*4 floats, row 0 = top.  Refused before
+ * the first resolve. */
+int hala_rt_read_temporal(hala_rt_renderer* r, int which, float* dst_rgba32f);
+/* RENDER_SPEC 16 "Outputs", zero-copy: the device address and byte size of the same images (valid until hala_rt_set_temporal(r, NULL)
+ * or destroy); reads of it belong on the renderer's stream */
+int hala_rt_get_temporal_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_t* bytes);
+/* RENDER_SPEC 16 "Denoising": the filter of hala_rt_denoise (RENDER_SPEC 10) with the temporal image of the last resolve as colour and the
+ * current albedo / normal as guides; the result goes to the denoised image (hala_rt_read_denoised).  Refused before the first resolve. */
+int hala_rt_denoise_temporal(hala_rt_renderer* r, const hala_denoise_params* p, float* gpu_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * Stand-alone pieces of the path (usable without a renderer)
  * ---------------------------------------------------------------------------------------------- */
 /* EnvMap::build_distribution_maps (src/envmap.rs:239-388) on the GPU. pixels: RGBA32F host, W*H*4. */
