@@ -162,7 +162,12 @@ class RtStatistics(C.Structure):
 
 class BuildOptions(C.Structure):  # hala_rt_build_options
     _fields_ = [("builder", C.c_uint32), ("ploc_tail", C.c_uint32), ("ploc_look_every", C.c_uint32),
-                ("collapse_look_every", C.c_uint32), ("instancing", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+                ("collapse_look_every", C.c_uint32), ("instancing", C.c_uint32), ("texture_bundles", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class TextureBundleInfo(C.Structure):  # hala_texture_bundle_info, 24 B
+    _fields_ = [("bundle_count", C.c_uint32), ("bundled_materials", C.c_uint32), ("unbundled_textured_materials", C.c_uint32),
+                ("reserved", C.c_uint32), ("bundle_bytes", C.c_uint64)]
 
 
 class BvhInfo(C.Structure):
@@ -235,6 +240,7 @@ PROTOTYPES = {
     "hala_cryptomatte_hash": ([C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], C.c_int),
     "hala_write_exr": ([C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_float)), C.c_uint32,
                         C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)], C.c_int),
+    "hala_rt_texture_bundle_info": ([C.c_void_p, C.POINTER(TextureBundleInfo)], C.c_int),
     "hala_temporal_default_params": ([C.POINTER(TemporalParams)], None),
     "hala_rt_set_temporal": ([C.c_void_p, C.POINTER(TemporalParams)], C.c_int),
     "hala_rt_temporal_capture": ([C.c_void_p], C.c_int),
@@ -284,4 +290,5 @@ EXPORTS = [
     "hala_rt_save_cryptomatte", "hala_cryptomatte_hash", "hala_write_exr",
     "hala_temporal_default_params", "hala_rt_set_temporal", "hala_rt_temporal_capture", "hala_rt_temporal_resolve", "hala_rt_read_temporal",
     "hala_rt_get_temporal_buffer", "hala_rt_denoise_temporal",
+    "hala_rt_texture_bundle_info",
 ]

@@ -130,6 +130,24 @@ __host__ __device__
 inline uint32_t tex_tiled_index(uint32_t x, uint32_t y, uint32_t w) { return (((y >> 2) * ((w + 3u) >> 2) + (x >> 2)) << 4) + ((y & 3u) << 2) + (x & 3u); }
 inline uint32_t tex_tiled_size(uint32_t w, uint32_t h) { return ((w + 3u) >> 2) * ((h + 3u) >> 2) * 16u; }
 static_assert(sizeof(TexDesc) == 80, "texture descriptor is 80 B");
+// Texel bundle (RENDER_SPEC 7.4: the storage form is not observable): the co-sized 8-bit maps of one material, interleaved.  A bundle
+// texel is 16 B — four RGBA8 words in the fixed lane order base colour, normal, metallic-roughness, emission (an absent lane is zero
+// and never decoded) — so the shade kernel fetches every map of the material with ONE dwordx4 load per texel position instead of one
+// dword load per map.  A 64-B line holds a 2x2 block of bundle texels; level l has the dimensions and the texel words of level l of
+// the source images (copied from the per-texture arena, which stays as it is); mip_offset[l] = first line of level l, in 64-B units.
+constexpr uint32_t kBundleLanes = 4;
+struct BundleDesc {
+  uint32_t width, height, mips;
+  uint32_t formats;               // byte k = kTexSrgb8 / kTexUnorm8 of lane k, 0 = lane absent
+  uint32_t mip_offset[kMaxMips];  // level l holds ceil(w/2) x ceil(h/2) lines
+};
+static_assert(sizeof(BundleDesc) == 80, "bundle descriptor is 80 B");
+// index of bundle texel (x, y), in 16-B units, inside a level of width w (x < w, y < h)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t bundle_texel_index(uint32_t x, uint32_t y, uint32_t w) { return (((y >> 1) * ((w + 1u) >> 1) + (x >> 1)) << 2) + ((y & 1u) << 1) + (x & 1u); }
+inline uint32_t bundle_level_lines(uint32_t w, uint32_t h) { return ((w + 1u) >> 1) * ((h + 1u) >> 1); }
 
 // What every kernel of one update() sees (the "descriptor sets" of src/rt_renderer.rs:141-209, :671-745 as
 // plain device pointers).
@@ -139,6 +157,11 @@ struct SceneView {
   const uint32_t* tex_arena8;  // 8-bit images (RGBA bytes, tiled 4x4)
   const float* tex_lut;        // 512 floats: the sRGB EOTF, then b / 255 (shading.h::tex8_fetch)
   uint32_t texture_count;
+  // texel bundles: material_bundle[m] = the bundle that holds all maps of material m, kAbsent = fetch each map from its own arena
+  // (nullptr: the scene has no bundle); read by the generic shade kernels only
+  const BundleDesc* bundles;
+  const uint4* bundle_arena;
+  const uint32_t* material_bundle;
   uint32_t shade_sort;  // 1: the scene's materials span several shading kinds — the bounce shade kernel regroups its paths by kind
   const BvhNode4* nodes;
   const Tri* tris;             // BVH order

@@ -54,6 +54,8 @@ void launch_mip_downsample(const float4* src, uint32_t sw, uint32_t sh, float4* 
 void launch_tile8(const uint32_t* src, uint32_t w, uint32_t h, uint32_t* dst, hipStream_t s);
 void launch_mip_downsample8(const uint32_t* src, uint32_t sw, uint32_t sh, uint32_t* dst, uint32_t dw, uint32_t dh, uint32_t format, const float* lut,
                             const float* thr, hipStream_t s);
+// texel bundles: one tiled 8-bit level -> lane `lane` of the bundle level of the same size (dst: its first 16-B texel)
+void launch_bundle_interleave(const uint32_t* src, uint32_t w, uint32_t h, uint4* dst, uint32_t lane, hipStream_t s);
 
 // bvh_build.hip — K1/K3/K4: flatten instances to world space, LBVH build, refit
 // How commit() builds the hierarchy (hala_rt_set_build_options; 0 = the default everywhere).  The driver fields only change HOW the

@@ -36,6 +36,12 @@ constexpr uint32_t kLeafMaxStaged = 4;  // ... unless the whole tree sits in LDS
 constexpr size_t kLdsStageBudget = 40 * 1024;  // a BVH up to this size is staged whole in LDS (next to the 24-KB stack)
 constexpr uint32_t kRefillThreshold = 24;      // idle lanes that trigger a refill of the wave (persistent_trace; profiles/r02_experiments.txt)
 constexpr int kStatRing = 16;
+// maps a material must reference to get a texel bundle.  Measured on configs[3] (profiles/texture_bundles.txt): the two-map DIFFUSE
+// materials (base colour + normal) gain from the 16-B bundle too, although half of every texel they load is idle
+#ifndef RT_BUNDLE_MIN_MAPS
+#define RT_BUNDLE_MIN_MAPS 2
+#endif
+constexpr uint32_t kBundleMinMaps = RT_BUNDLE_MIN_MAPS;
 constexpr uint32_t kMaxSampleBatch = 16;  // frames per wavefront pass in hala_rt_update_batch (~250 B of state per path)
 
 // ---- RENDER_SPEC §2.2 on the host (for tan(yfov/2); same polynomials as rt_math.h) ---------------------------
@@ -138,6 +144,17 @@ struct hala_rt_renderer {
   DeviceArray<float> d_srgb_lut, d_srgb_thr;
   DeviceArray<TexDesc> d_textures;
   std::vector<TexDesc> host_textures;
+  // texel bundles (hala_types.h: BundleDesc): the co-sized 8-bit maps of a material interleaved, built by commit beside the per-texture
+  // arenas; a refit follows material edits (update_texture_bundles)
+  struct BundleSource { uint32_t image[kBundleLanes], texture[kBundleLanes]; };  // per lane: the image (what bundles are shared by) and one texture that shows it, kAbsent = no map
+  uint32_t texture_bundles_mode = 0;  // hala_rt_build_options::texture_bundles: 0 automatic (on), 1 off
+  bool bundles_on = false;            // as the last commit decided (automatic mode gives up when the arena cannot be had)
+  std::vector<BundleSource> bundle_sources;
+  std::vector<BundleDesc> host_bundles;
+  DeviceArray<uint4> d_bundle_arena;
+  DeviceArray<BundleDesc> d_bundles;
+  DeviceArray<uint32_t> d_material_bundle;
+  uint32_t bundled_materials = 0, unbundled_textured_materials = 0;
 
   BvhBuffers bvh{};
   // two-level trees (RENDER_SPEC 4.5): scenes in which some primitive is referenced by several instances.  `bvh` then only carries the
@@ -321,7 +338,9 @@ struct hala_rt_renderer {
     sv.nodes = d_nodes.ptr; sv.tris = d_tris.ptr; sv.tris_any = any_invisible ? d_tris_any.ptr : d_tris.ptr; sv.tris_by_id = d_tris_by_id.ptr; sv.shade_tris = d_shade_tris.ptr;
     sv.inst_first_tri = d_inst_first_tri.ptr; sv.primitives = d_instances.ptr; sv.materials = d_materials.ptr; sv.material_kind = d_material_kind.ptr;
     sv.lights = d_lights.ptr; sv.cameras = d_cameras.ptr;
-    sv.textures = d_textures.ptr; sv.tex_arena = d_tex_arena.ptr; sv.tex_arena8 = d_tex_arena8.ptr; sv.tex_lut = d_srgb_lut.ptr; sv.texture_count = (uint32_t)host_textures.size(); sv.shade_sort = shade_sort ? 1u : 0u; sv.simple_materials = simple_materials ? 1u : 0u; sv.scatter_media = scatter_media ? 1u : 0u; sv.any_translucent = any_translucent ? 1u : 0u;
+    sv.textures = d_textures.ptr; sv.tex_arena = d_tex_arena.ptr; sv.tex_arena8 = d_tex_arena8.ptr; sv.tex_lut = d_srgb_lut.ptr; sv.texture_count = (uint32_t)host_textures.size();
+    if (!host_bundles.empty()) { sv.bundles = d_bundles.ptr; sv.bundle_arena = d_bundle_arena.ptr; sv.material_bundle = d_material_bundle.ptr; }
+    sv.shade_sort = shade_sort ? 1u : 0u; sv.simple_materials = simple_materials ? 1u : 0u; sv.scatter_media = scatter_media ? 1u : 0u; sv.any_translucent = any_translucent ? 1u : 0u;
     sv.env_pixels = reinterpret_cast<const float*>(d_env.ptr); sv.env_marginal = d_marginal.ptr; sv.env_conditional = d_conditional.ptr;
     sv.node_count = bvh.node_count; sv.tri_count = bvh.tri_count; sv.lds_nodes = lds_nodes; sv.lds_tris = lds_tris;
     sv.inst_refs = d_inst_refs.ptr; sv.inst_info = d_inst_info.ptr; sv.instance_count = (uint32_t)hs.instances.size(); sv.two_level = two_level ? 1u : 0u;
@@ -700,6 +719,94 @@ int upload_textures(hala_rt_renderer* r) {
   RT_HIP(hipStreamSynchronize(r->stream));  // (also: `staging` and the host images may go)
   RT_HIP(hipGetLastError());
   r->host_textures = tex;
+  return HALA_OK;
+}
+
+// Texel bundles: one per distinct tuple of images that a material's maps show, for the materials that reference at least two maps, all
+// 8-bit and of equal width and height; every other material keeps fetching from the per-texture arenas (kAbsent in the table).
+// fresh: a commit — everything is decided and built again.  Otherwise a refit: hala_rt_update_material may have changed map indices; the
+// table follows, and the arena is rebuilt when a tuple appears that has no bundle yet (bundles no longer referenced stay until then).
+// The levels are interleaved on the device from the levels upload_textures built: the texel words are the same by construction.
+int update_texture_bundles(hala_rt_renderer* r, bool fresh) {
+  const HostScene& hs = r->hs;
+  const uint32_t nt = (uint32_t)r->host_textures.size();
+  if (fresh) {
+    r->bundles_on = r->texture_bundles_mode == 0u;
+    r->bundle_sources.clear(); r->host_bundles.clear();
+  }
+  std::vector<hala_rt_renderer::BundleSource> sources = r->bundle_sources;
+  std::vector<uint32_t> table(hs.gpu_materials.size(), kAbsent);
+  uint32_t bundled = 0, textured = 0;
+  for (size_t m = 0; m < hs.gpu_materials.size(); ++m) {
+    const hala_gpu_material& gm = hs.gpu_materials[m];
+    const uint32_t idx[kBundleLanes] = {gm.base_color_map_index, gm.normal_map_index, gm.metallic_roughness_map_index, gm.emission_map_index};
+    hala_rt_renderer::BundleSource src;
+    uint32_t maps = 0, w = 0, h = 0;
+    bool same = true;
+    for (uint32_t k = 0; k < kBundleLanes; ++k) {
+      src.image[k] = src.texture[k] = kAbsent;
+      if (idx[k] >= nt) continue;
+      const TexDesc& td = r->host_textures[idx[k]];
+      if (maps == 0) { w = td.width; h = td.height; }
+      same = same && td.format != kTexFloat && td.width == w && td.height == h;
+      src.image[k] = hs.texture_image[idx[k]]; src.texture[k] = idx[k];
+      ++maps;
+    }
+    if (maps == 0) continue;
+    ++textured;
+    if (!r->bundles_on || maps < kBundleMinMaps || !same) continue;
+    size_t b = 0;
+    while (b < sources.size() && memcmp(sources[b].image, src.image, sizeof(src.image)) != 0) ++b;
+    if (b == sources.size()) sources.push_back(src);
+    table[m] = (uint32_t)b;
+    ++bundled;
+  }
+  if (sources.size() != r->host_bundles.size()) {  // new tuples: lay the arena out again and fill it
+    std::vector<BundleDesc> descs(sources.size());
+    size_t lines = 0;
+    for (size_t b = 0; b < sources.size(); ++b) {
+      BundleDesc& bd = descs[b];
+      memset(&bd, 0, sizeof(bd));
+      for (uint32_t k = 0; k < kBundleLanes; ++k) {
+        if (sources[b].texture[k] == kAbsent) continue;
+        const TexDesc& td = r->host_textures[sources[b].texture[k]];
+        bd.width = td.width; bd.height = td.height; bd.mips = td.mips;
+        bd.formats |= td.format << (8u * k);
+      }
+      for (uint32_t l = 0; l < bd.mips; ++l) {
+        if (lines > 0xffffffffull) break;
+        bd.mip_offset[l] = (uint32_t)lines;
+        lines += bundle_level_lines(std::max(1u, bd.width >> l), std::max(1u, bd.height >> l));
+      }
+    }
+    // automatic mode: an arena that cannot be addressed or cannot be had leaves every material on the per-texture path
+    bool ok = lines <= 0xffffffffull;
+    if (ok && r->d_bundle_arena.resize(lines * 4) != hipSuccess) { (void)hipGetLastError(); ok = false; }
+    if (!ok) {
+      r->bundles_on = false;
+      r->bundle_sources.clear(); r->host_bundles.clear();
+      r->d_bundle_arena.release();
+      std::fill(table.begin(), table.end(), kAbsent);
+      bundled = 0;
+    } else {
+      RT_HIP(hipMemsetAsync(r->d_bundle_arena.ptr, 0, lines * 64, r->stream));  // absent lanes, the padding texels of odd sizes
+      for (size_t b = 0; b < sources.size(); ++b)
+        for (uint32_t k = 0; k < kBundleLanes; ++k) {
+          if (sources[b].texture[k] == kAbsent) continue;
+          const TexDesc& td = r->host_textures[sources[b].texture[k]];
+          for (uint32_t l = 0; l < td.mips; ++l)
+            launch_bundle_interleave(r->d_tex_arena8.ptr + td.mip_offset[l], std::max(1u, td.width >> l), std::max(1u, td.height >> l),
+                                     r->d_bundle_arena.ptr + ((size_t)descs[b].mip_offset[l] << 2), k, r->stream);
+        }
+      RT_HIP(r->d_bundles.upload(descs.data(), descs.size(), r->stream));
+      r->bundle_sources = sources; r->host_bundles = descs;
+    }
+  }
+  if (r->host_bundles.empty()) r->d_bundle_arena.release();
+  RT_HIP(r->d_material_bundle.upload(table.data(), table.size(), r->stream));
+  RT_HIP(hipStreamSynchronize(r->stream));  // (`table` and `descs` may go)
+  RT_HIP(hipGetLastError());
+  r->bundled_materials = bundled; r->unbundled_textured_materials = textured - bundled;
   return HALA_OK;
 }
 
@@ -1199,6 +1306,8 @@ int hala_rt_commit(hala_rt_renderer* r) {
   if (!r->has_scene) RT_FAIL("The scene in GPU is none!");  // src/rt_renderer.rs:138
   if (r->hs.cameras.empty()) RT_FAIL("The scene has no camera.");
   if (r->hs.instances.empty()) RT_FAIL("The scene has no mesh primitive.");  // `primitives[0]` panics in the reference (gpu_uploader.rs:888)
+  RT_HIP(hipStreamSynchronize(r->stream));  // (a recommit: earlier frames may still read the bundles)
+  if (update_texture_bundles(r, true) != HALA_OK) return HALA_ERR;
   if (build_bvh(r) != HALA_OK) return HALA_ERR;
   r->committed = true;
   r->crypto_tables = false;  // RENDER_SPEC §15: the next update hashes the committed scene's names
@@ -1210,9 +1319,10 @@ int hala_rt_commit(hala_rt_renderer* r) {
 int hala_rt_set_build_options(hala_rt_renderer* r, const hala_rt_build_options* o) {
   if (!r) RT_FAIL("The renderer handle is null!");
   if (!o) RT_FAIL("The build options are null!");
-  if (o->builder > 3u || o->ploc_tail > 2u || o->instancing > 2u) RT_FAIL("Invalid build options.");
+  if (o->builder > 3u || o->ploc_tail > 2u || o->instancing > 2u || o->texture_bundles > 1u) RT_FAIL("Invalid build options.");
   for (uint32_t v : o->reserved) if (v != 0u) RT_FAIL("Invalid build options (reserved fields must be 0).");
   r->instancing_mode = o->instancing;
+  r->texture_bundles_mode = o->texture_bundles;
   r->bvh.opt.builder = o->builder; r->bvh.opt.ploc_tail = o->ploc_tail;
   r->bvh.opt.ploc_look_every = o->ploc_look_every; r->bvh.opt.collapse_look_every = o->collapse_look_every;
   return HALA_OK;
@@ -2152,6 +2262,17 @@ int hala_rt_get_texture_info(hala_rt_renderer* r, uint32_t texture, uint32_t* wi
   if (mips) *mips = td.mips;
   return HALA_OK;
 }
+int hala_rt_texture_bundle_info(hala_rt_renderer* r, hala_texture_bundle_info* info) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (!info) RT_FAIL("Invalid argument.");
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  info->bundle_count = (uint32_t)r->host_bundles.size();
+  info->bundled_materials = r->bundled_materials;
+  info->unbundled_textured_materials = r->unbundled_textured_materials;
+  info->reserved = 0;
+  info->bundle_bytes = r->host_bundles.empty() ? 0ull : (unsigned long long)r->d_bundle_arena.count * 16ull;
+  return HALA_OK;
+}
 int hala_rt_read_texture_level(hala_rt_renderer* r, uint32_t texture, uint32_t level, float* dst_rgba32f) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (!r->has_scene || texture >= r->host_textures.size() || !dst_rgba32f) RT_FAIL("The texture does not exist.");
@@ -2536,6 +2657,7 @@ int hala_rt_refit(hala_rt_renderer* r) {
   const std::string e = r->hs.pack();
   if (!e.empty()) RT_FAIL(e);
   if (upload_packed(r, false) != HALA_OK) return HALA_ERR;
+  if (update_texture_bundles(r, false) != HALA_OK) return HALA_ERR;  // a material edit may have changed which maps a material references
   r->bvh.primitives = r->d_instances.ptr; r->bvh.inst_first_tri = r->d_inst_first_tri.ptr;
   // only cameras / lights moved (the interactive case: a camera node): the geometry and its tree stand as they are
   const bool had_invisible = r->any_invisible;

@@ -495,10 +495,13 @@ RT_DI float log2_approx(float x) {
 // float*` (global) or `const RT_LDS float*`.
 constexpr uint32_t kTexLutEntries = 512;
 template <typename LUT>
-RT_DI float4 tex8_fetch(LUT lut, const uint32_t* base, uint32_t format, int x, int y, int w) {
-  const uint32_t t = base[tex_tiled_index((uint32_t)x, (uint32_t)y, (uint32_t)w)];
+RT_DI float4 tex8_texel(LUT lut, uint32_t t, uint32_t format) {
   const uint32_t o = format == kTexSrgb8 ? 0u : 256u;
   return make_float4(lut[o + (t & 0xffu)], lut[o + ((t >> 8) & 0xffu)], lut[o + ((t >> 16) & 0xffu)], lut[256u + (t >> 24)]);
+}
+template <typename LUT>
+RT_DI float4 tex8_fetch(LUT lut, const uint32_t* base, uint32_t format, int x, int y, int w) {
+  return tex8_texel(lut, base[tex_tiled_index((uint32_t)x, (uint32_t)y, (uint32_t)w)], format);
 }
 template <typename LUT>
 RT_DI float4 tex_bilinear(const SceneView& sv, LUT lut, const TexDesc& td, uint32_t level, float u, float v) {
@@ -547,6 +550,57 @@ RT_DI float4 tex_sample(const SceneView& sv, LUT lut, uint32_t tex, float u, flo
 RT_DI float tex_lod(const SceneView& sv, uint32_t tex, float lod_base) {
   const TexDesc& td = sv.textures[tex];
   return lod_base + 0.5f * log2_approx((float)td.width * (float)td.height);
+}
+// ---- texel bundles (hala_types.h: BundleDesc): all co-sized 8-bit maps of a material from one 16-B load per texel position ----------
+// The maps of a bundle share width, height and mip count, so tex_lod, the level, the fractions and the wrapped indices of tex_sample /
+// tex_bilinear are the same for each of them: computed once here, with the same expressions.  The texel words are copies of the
+// per-texture arena's, and bundle_bilinear / bundle_mix decode and filter them exactly like tex8_fetch / tex_bilinear / tex_sample.
+struct BundleTap { uint4 t00, t10, t01, t11; float fx, fy; };  // the 2x2 footprint of one level (all lanes) and its bilinear fractions
+RT_DI BundleTap bundle_fetch(const SceneView& sv, const BundleDesc& bd, uint32_t level, float u, float v) {
+  const int w = max((int)(bd.width >> level), 1), h = max((int)(bd.height >> level), 1);
+  const float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
+  const float x0 = floorf(x), y0 = floorf(y);
+  const int ix0 = wrapi((int)x0, w), iy0 = wrapi((int)y0, h);
+  const int ix1 = wrap_next(ix0, w), iy1 = wrap_next(iy0, h);
+  const uint4* base = sv.bundle_arena + ((size_t)bd.mip_offset[level] << 2);
+  BundleTap k;
+  k.t00 = base[bundle_texel_index((uint32_t)ix0, (uint32_t)iy0, (uint32_t)w)]; k.t10 = base[bundle_texel_index((uint32_t)ix1, (uint32_t)iy0, (uint32_t)w)];
+  k.t01 = base[bundle_texel_index((uint32_t)ix0, (uint32_t)iy1, (uint32_t)w)]; k.t11 = base[bundle_texel_index((uint32_t)ix1, (uint32_t)iy1, (uint32_t)w)];
+  k.fx = x - x0; k.fy = y - y0;
+  return k;
+}
+template <int LANE>
+RT_DI uint32_t bundle_word(const uint4& t) { return LANE == 0 ? t.x : (LANE == 1 ? t.y : (LANE == 2 ? t.z : t.w)); }
+template <int LANE, typename LUT>
+RT_DI float4 bundle_bilinear(LUT lut, const BundleTap& k, uint32_t format) {
+  const float4 c00 = tex8_texel(lut, bundle_word<LANE>(k.t00), format), c10 = tex8_texel(lut, bundle_word<LANE>(k.t10), format);
+  const float4 c01 = tex8_texel(lut, bundle_word<LANE>(k.t01), format), c11 = tex8_texel(lut, bundle_word<LANE>(k.t11), format);
+  const float fx = k.fx, fy = k.fy, gx = 1.0f - fx, gy = 1.0f - fy;
+  float4 r;
+  r.x = (c00.x * gx + c10.x * fx) * gy + (c01.x * gx + c11.x * fx) * fy;
+  r.y = (c00.y * gx + c10.y * fx) * gy + (c01.y * gx + c11.y * fx) * fy;
+  r.z = (c00.z * gx + c10.z * fx) * gy + (c01.z * gx + c11.z * fx) * fy;
+  r.w = (c00.w * gx + c10.w * fx) * gy + (c01.w * gx + c11.w * fx) * fy;
+  return r;
+}
+// where a trilinear sample of the bundle looks (tex_lod and the head of tex_sample): the level, whether level + 1 takes part, the fraction
+struct BundleLod { uint32_t level; bool two; float fl; };
+RT_DI BundleLod bundle_lod(const BundleDesc& bd, float lod_base) {
+  float lod = lod_base + 0.5f * log2_approx((float)bd.width * (float)bd.height);
+  const float top = (float)(bd.mips - 1u);
+  lod = lod < 0.0f ? 0.0f : (lod > top ? top : lod);
+  const float l0 = floorf(lod);
+  BundleLod bl;
+  bl.fl = lod - l0;
+  bl.level = (uint32_t)l0;
+  bl.two = bl.fl > 0.0f && bl.level + 1u < bd.mips;
+  return bl;
+}
+// the tail of tex_sample: a = level `level`, b = level + 1
+RT_DI float4 bundle_mix(float4 a, const float4 b, float fl) {
+  const float g = 1.0f - fl;
+  a.x = a.x * g + b.x * fl; a.y = a.y * g + b.y * fl; a.z = a.z * g + b.z * fl; a.w = a.w * g + b.w * fl;
+  return a;
 }
 
 // two-level trees (RENDER_SPEC 4.5): the instance a global triangle id belongs to (the last one whose first triangle is <= id; the
@@ -662,14 +716,14 @@ RT_DI Surface make_surface(const SceneView& sv, LUT lut, float pixel_spread, f3 
   sf.mat.base = ld3(m.base_color);
   sf.mat.emission = ld3(m.emission);
   sf.mat.ax = m.ax; sf.mat.ay = m.ay; sf.mat.type = SIMPLE ? 0u : m.type;
-  sf.mat.metallic = m.metallic; sf.mat.roughness = m.roughness; sf.mat.specular_tint = m.specular_tint;
-  sf.mat.sheen = m.sheen; sf.mat.sheen_tint = m.sheen_tint; sf.mat.clearcoat = m.clearcoat;
-  sf.mat.clearcoat_roughness = m.clearcoat_roughness; sf.mat.ior = m.ior;
-  sf.mat.trans = 0.0f; sf.mat.eta = m.ior; sf.mat.opacity = SIMPLE ? 1.0f : m.opacity;
+  sf.mat.metallic = m.metallic; sf.mat.roughness = m.roughness;
+  sf.mat.trans = 0.0f; sf.mat.opacity = SIMPLE ? 1.0f : m.opacity;
   // texture maps (set 2; u32::MAX = none, gltf_loader.rs:346-353)
   const uint32_t nt = sv.texture_count;
   const bool has_base = !SIMPLE && m.base_color_map_index < nt, has_nrm = !SIMPLE && m.normal_map_index < nt;
   const bool has_mr = !SIMPLE && m.metallic_roughness_map_index < nt, has_em = !SIMPLE && m.emission_map_index < nt;
+  // texel bundles: the table entry travels beside the material record (kAbsent: each map from its own arena)
+  const uint32_t bundle = !SIMPLE && sv.material_bundle ? sv.material_bundle[material] : kAbsent;
   if (has_base || has_nrm || has_mr || has_em) {
     // line 2: texture coordinates and tangents (in flight together with the texture descriptors)
     const float4 s4 = sp[4], s5 = sp[5], s6 = sp[6], s7 = sp[7];
@@ -686,17 +740,13 @@ RT_DI Surface make_surface(const SceneView& sv, LUT lut, float pixel_spread, f3 
     const float foot = t * pixel_spread / cosi;
     const float ratio = foot * foot * uv_area / world_area;
     const float lod_base = (ratio > 0.0f && ratio < 3.0e38f) ? 0.5f * log2_approx(ratio) : 0.0f;
-    if (has_base) {
-      const float4 s = tex_sample(sv, lut, m.base_color_map_index, tu, tv, tex_lod(sv, m.base_color_map_index, lod_base));
+    // what each map's sample does to the surface (the same arithmetic whichever way the texels were fetched)
+    const auto apply_base = [&](const float4 s) {
       sf.mat.base = sf.mat.base * mk3(s.x, s.y, s.z);
       sf.mat.opacity = sf.mat.opacity * s.w;
-    }
-    if (has_em) {
-      const float4 s = tex_sample(sv, lut, m.emission_map_index, tu, tv, tex_lod(sv, m.emission_map_index, lod_base));
-      sf.mat.emission = sf.mat.emission * mk3(s.x, s.y, s.z);
-    }
-    if (has_mr) {  // glTF: G = roughness, B = metallic
-      const float4 s = tex_sample(sv, lut, m.metallic_roughness_map_index, tu, tv, tex_lod(sv, m.metallic_roughness_map_index, lod_base));
+    };
+    const auto apply_emission = [&](const float4 s) { sf.mat.emission = sf.mat.emission * mk3(s.x, s.y, s.z); };
+    const auto apply_mr = [&](const float4 s) {  // glTF: G = roughness, B = metallic
       sf.mat.metallic = sf.mat.metallic * s.z;
       if (m.type == 1u) {  // re-derive the packed alphas exactly like src/scene/gpu/material.rs:61-69
         const float rl = sqrtf(m.roughness) * s.y;
@@ -706,11 +756,10 @@ RT_DI Surface make_surface(const SceneView& sv, LUT lut, float pixel_spread, f3 
         sf.mat.ax = maxf(0.001f, r2 / aspect);
         sf.mat.ay = maxf(0.001f, r2 * aspect);
       }
-    }
-    if (has_nrm) {
-      const float4 s = tex_sample(sv, lut, m.normal_map_index, tu, tv, tex_lod(sv, m.normal_map_index, lod_base));
-      // tangents: s5.z s5.w s6.x | s6.y s6.z s6.w | s7.x s7.y s7.z
-      const f3 tl = madd3(mk3(s7.x, s7.y, s7.z), v, madd3(mk3(s6.y, s6.z, s6.w), u, mk3(s5.z, s5.w, s6.x) * w0));
+    };
+    // the interpolated tangent; tangents: s5.z s5.w s6.x | s6.y s6.z s6.w | s7.x s7.y s7.z
+    const auto local_tangent = [&]() { return madd3(mk3(s7.x, s7.y, s7.z), v, madd3(mk3(s6.y, s6.z, s6.w), u, mk3(s5.z, s5.w, s6.x) * w0)); };
+    const auto apply_normal = [&](const float4 s, const f3 tl) {
       f3 tw = transform_vector(md.transform, tl);
       tw = tw - sf.ns * dot3(sf.ns, tw);  // Gram-Schmidt against the shading normal
       const float tl2 = dot3(tw, tw);
@@ -722,8 +771,46 @@ RT_DI Surface make_surface(const SceneView& sv, LUT lut, float pixel_spread, f3 
         const float nn2 = dot3(nn, nn);
         if (nn2 > 0.0f) sf.ns = nn * (1.0f / sqrtf(nn2));
       }
+    };
+    if (bundle != kAbsent) {
+      // every map of this material lives in one texel bundle: one 16-B load per texel position serves them all; a lane is
+      // decoded only for a map that exists.  One level at a time: the 2x2 footprints of both levels at once are 32 registers the kernel does not have
+      const BundleDesc& bd = sv.bundles[bundle];
+      const BundleLod bl = bundle_lod(bd, lod_base);
+      const uint32_t formats = bd.formats;
+      const f3 tl = local_tangent();  // (before the fetch: three registers across it instead of the nine of the vertex tangents)
+      const uint32_t f_base = formats & 0xffu, f_nrm = (formats >> 8) & 0xffu, f_mr = (formats >> 16) & 0xffu, f_em = formats >> 24;
+      float4 c_base = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c_nrm = c_base, c_mr = c_base, c_em = c_base;
+      {
+        const BundleTap k = bundle_fetch(sv, bd, bl.level, tu, tv);
+        if (has_base) c_base = bundle_bilinear<0>(lut, k, f_base);
+        if (has_nrm) c_nrm = bundle_bilinear<1>(lut, k, f_nrm);
+        if (has_mr) c_mr = bundle_bilinear<2>(lut, k, f_mr);
+        if (has_em) c_em = bundle_bilinear<3>(lut, k, f_em);
+      }
+      if (bl.two) {
+        const BundleTap k = bundle_fetch(sv, bd, bl.level + 1u, tu, tv);
+        if (has_base) c_base = bundle_mix(c_base, bundle_bilinear<0>(lut, k, f_base), bl.fl);
+        if (has_nrm) c_nrm = bundle_mix(c_nrm, bundle_bilinear<1>(lut, k, f_nrm), bl.fl);
+        if (has_mr) c_mr = bundle_mix(c_mr, bundle_bilinear<2>(lut, k, f_mr), bl.fl);
+        if (has_em) c_em = bundle_mix(c_em, bundle_bilinear<3>(lut, k, f_em), bl.fl);
+      }
+      if (has_base) apply_base(c_base);
+      if (has_em) apply_emission(c_em);
+      if (has_mr) apply_mr(c_mr);
+      if (has_nrm) apply_normal(c_nrm, tl);
+    } else {
+      if (has_base) apply_base(tex_sample(sv, lut, m.base_color_map_index, tu, tv, tex_lod(sv, m.base_color_map_index, lod_base)));
+      if (has_em) apply_emission(tex_sample(sv, lut, m.emission_map_index, tu, tv, tex_lod(sv, m.emission_map_index, lod_base)));
+      if (has_mr) apply_mr(tex_sample(sv, lut, m.metallic_roughness_map_index, tu, tv, tex_lod(sv, m.metallic_roughness_map_index, lod_base)));
+      if (has_nrm) apply_normal(tex_sample(sv, lut, m.normal_map_index, tu, tv, tex_lod(sv, m.normal_map_index, lod_base)), local_tangent());
     }
   }
+  // the parameters no map touches are read behind the texture fetches: they are not needed before the BSDF, and the fetches want the registers
+  sf.mat.specular_tint = m.specular_tint;
+  sf.mat.sheen = m.sheen; sf.mat.sheen_tint = m.sheen_tint; sf.mat.clearcoat = m.clearcoat;
+  sf.mat.clearcoat_roughness = m.clearcoat_roughness; sf.mat.ior = m.ior;
+  sf.mat.eta = m.ior;
   if (!SIMPLE && m.type == 1u) sf.mat.trans = m.specular_transmission * (1.0f - sf.mat.metallic);  // after the metallic map
   if (dot3(sf.ns, sf.ng) < 0.0f) sf.ng = -sf.ng;
   sf.absorb = splat3(1.0f); sf.glow = splat3(0.0f);

@@ -71,6 +71,17 @@ __global__ void __launch_bounds__(256) k_mip_downsample8(const uint32_t* __restr
   for (int k = 0; k < 3; ++k) out |= (format == kTexSrgb8 ? tex8_encode_srgb(r4[k], thr) : tex8_encode_unorm(r4[k])) << (8 * k);
   dst[tex_tiled_index(x, y, dw)] = out;
 }
+// texel bundles (hala_types.h: BundleDesc): lane `lane` of every bundle texel of one level = the texel word of the tiled source level,
+// copied as it is — the bundled fetch decodes exactly the words the per-texture fetch would
+__global__ void __launch_bounds__(256) k_bundle_interleave(const uint32_t* __restrict__ src, uint32_t w, uint32_t h, uint32_t* __restrict__ dst, uint32_t lane) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= w * h) return;
+  const uint32_t y = i / w, x = i - y * w;
+  dst[(size_t)bundle_texel_index(x, y, w) * kBundleLanes + lane] = src[tex_tiled_index(x, y, w)];
+}
+void launch_bundle_interleave(const uint32_t* src, uint32_t w, uint32_t h, uint4* dst, uint32_t lane, hipStream_t s) {
+  hipLaunchKernelGGL(k_bundle_interleave, dim3((w * h + 255u) / 256u), dim3(256), 0, s, src, w, h, reinterpret_cast<uint32_t*>(dst), lane);
+}
 void launch_tile8(const uint32_t* src, uint32_t w, uint32_t h, uint32_t* dst, hipStream_t s) {
   hipLaunchKernelGGL(k_tile8, dim3((w * h + 255u) / 256u), dim3(256), 0, s, src, w, h, dst);
 }

@@ -120,13 +120,15 @@ class HalaRenderer:
 
     BUILDERS = {None: 0, "auto": 0, "sah": 1, "ploc": 2, "lbvh": 3}
 
-    def set_build_options(self, builder=None, ploc_tail=0, ploc_look_every=0, collapse_look_every=0, instancing=None):
+    def set_build_options(self, builder=None, ploc_tail=0, ploc_look_every=0, collapse_look_every=0, instancing=None, texture_bundles=None):
         """how the next commit() builds the acceleration structure (hala_rt_set_build_options): builder = None | "sah" | "ploc" | "lbvh";
         instancing = True: two-level tree (RENDER_SPEC 4.5: primitives referenced by several instances are stored once), False: every
         instance flattened to world space (one tree), None: automatic (flattened up to 2^26 triangles); the other fields only change how the
-        host drives the build rounds (same tree)"""
+        host drives the build rounds (same tree); texture_bundles = None / True: the co-sized 8-bit maps of a material are also stored
+        interleaved and fetched together (same images, faster shading), False: off"""
         o = A.BuildOptions(builder=self.BUILDERS[builder], ploc_tail=ploc_tail, ploc_look_every=ploc_look_every, collapse_look_every=collapse_look_every,
-                           instancing=0 if instancing is None else (2 if instancing else 1))
+                           instancing=0 if instancing is None else (2 if instancing else 1),
+                           texture_bundles=0 if texture_bundles is None or texture_bundles else 1)
         self._check(self._lib.hala_rt_set_build_options(self._h, C.byref(o)))
 
     def update(self, delta_time=0.0, width=None, height=None, ui_fn=None):
@@ -451,6 +453,13 @@ class HalaRenderer:
         w, h, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
         self._check(self._lib.hala_rt_get_texture_info(self._h, C.c_uint32(texture), C.byref(w), C.byref(h), C.byref(m)))
         return w.value, h.value, m.value
+
+    def texture_bundle_info(self):
+        """texel bundles of the committed scene (hala_rt_texture_bundle_info): bundle_count, bundled_materials,
+        unbundled_textured_materials, bundle_bytes"""
+        i = A.TextureBundleInfo()
+        self._check(self._lib.hala_rt_texture_bundle_info(self._h, C.byref(i)))
+        return i
 
     def read_texture_level(self, texture, level):
         w, h, _ = self.texture_info(texture)

@@ -346,7 +346,13 @@ typedef struct hala_rt_build_options {
                                  *  0: automatic — 1 unless the flattened scene holds more than 2^26 triangles (about 15 GB of tree), then 2.
                                  * The two forms intersect instanced geometry in different spaces: images agree to rounding, not bit for bit;
                                  * hala_bvh_info::instance_ref_count tells which one a commit chose. */
-  uint32_t reserved[3];         /* must be 0 */
+  uint32_t texture_bundles;     /* texel bundles: the co-sized 8-bit maps of a material (at least two of base colour, normal, metallic-
+                                 * roughness, emission; equal width and height) are also stored interleaved, 16 B per texel position, and
+                                 * the shade kernels fetch all of them with one load per texel.  Not observable in any image (RENDER_SPEC
+                                 * 7.4); costs 16 B per texel of every bundled tuple beside the textures themselves.
+                                 *  0: automatic — on, unless the bundle memory cannot be had (then silently off);  1: off.
+                                 * hala_rt_texture_bundle_info tells what a commit built. */
+  uint32_t reserved[2];         /* must be 0 */
 } hala_rt_build_options;
 int hala_rt_set_build_options(hala_rt_renderer* r, const hala_rt_build_options* options);
 
@@ -576,6 +582,17 @@ int hala_rt_get_env_distribution(hala_rt_renderer* r, float* total_sum, float* m
  * triples. */
 int hala_rt_get_texture_info(hala_rt_renderer* r, uint32_t texture, uint32_t* width, uint32_t* height, uint32_t* mips);
 int hala_rt_read_texture_level(hala_rt_renderer* r, uint32_t texture, uint32_t level, float* dst_rgba32f);
+/* Texel bundles of the committed scene (hala_rt_build_options::texture_bundles), as the last commit or refit left them: materials whose
+ * maps are fetched from a bundle, materials with at least one map that are not (one map only, maps of different sizes, a float image,
+ * bundles off), and the bytes of the bundle arena.  Fails before the first commit. */
+typedef struct hala_texture_bundle_info {
+  uint32_t bundle_count;
+  uint32_t bundled_materials;
+  uint32_t unbundled_textured_materials;
+  uint32_t reserved;
+  unsigned long long bundle_bytes;
+} hala_texture_bundle_info;
+int hala_rt_texture_bundle_info(hala_rt_renderer* r, hala_texture_bundle_info* info);
 int hala_rt_sample_texture_host(hala_rt_renderer* r, uint32_t texture, const float* uv_lod, uint32_t count, float* dst_rgba32f);
 
 /* Multi-GPU pixel-tile sharding (no reference equivalent; BASELINE.json north_star).  The frame is cut

@@ -66,7 +66,7 @@ pub mod sys {
 
   /// hala_rt_build_options (include/halart.h): every field 0 = the default
   #[repr(C)] #[derive(Default, Clone, Copy)]
-  pub struct hala_rt_build_options { pub builder: u32, pub ploc_tail: u32, pub ploc_look_every: u32, pub collapse_look_every: u32, pub instancing: u32, pub reserved: [u32; 3] }
+  pub struct hala_rt_build_options { pub builder: u32, pub ploc_tail: u32, pub ploc_look_every: u32, pub collapse_look_every: u32, pub instancing: u32, pub texture_bundles: u32, pub reserved: [u32; 2] }
   #[repr(C)] pub struct hala_scene { _private: [u8; 0] }
   #[repr(C)] pub struct hala_rtprog { _private: [u8; 0] }
   extern "C" {
