@@ -14,7 +14,7 @@ namespace rt {
 
 namespace {
 
-constexpr uint32_t kBlock = 8;              // RENDER_SPEC 11: the 8 x 8 blocks of §9 (renderer.hip refuses other RT_PIXEL_BLOCK builds)
+constexpr uint32_t kBlock = 8;              // RENDER_SPEC 11: the 8 x 8 blocks of §9 (rt_outputs.hip refuses other RT_PIXEL_BLOCK builds)
 constexpr uint32_t kCheckThreads = 256;     // four blocks per workgroup, one per wave
 constexpr uint32_t kCompactThreads = 1024;  // one workgroup scans every block: 130 K blocks at 3840 x 2160 are 128 passes
 

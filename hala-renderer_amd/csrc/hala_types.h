@@ -275,7 +275,7 @@ struct WorkCounters {
   uint32_t c[kWorkShards * kWorkStride];
   unsigned long long dry[kWorkStride / 2];  // dry[0]: bit s set once shard s has handed out all of its batches (own 128-B line)
 };
-// The two parts of the control block the host reads back after an update, each in one copy (renderer.hip: TraceEvents)
+// The two parts of the control block the host reads back after an update, each in one copy (renderer_state.h: TraceEvents)
 struct QueueSizes {
   uint32_t n_active[kMaxDepth + 1];  // ray-queue size entering bounce d
   uint32_t n_shadow[2][kMaxDepth];   // connections produced by bounce d: [0] light, [1] environment

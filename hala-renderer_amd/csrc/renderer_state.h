@@ -1,0 +1,486 @@
+// renderer_state.h — the renderer object behind the C ABI (struct hala_rt_renderer), shared by the host units that implement it:
+// renderer.hip (life cycle, scene, update), rt_scene.hip (uploads, trees, edits), rt_outputs.hip (views, AOVs, adaptive sampling, light
+// groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
+// Each feature keeps its state in one struct that knows how to turn itself off.  Nothing outside csrc/ includes this header.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <string>
+#include <sys/stat.h>
+#include <vector>
+
+#include "adaptive.h"
+#include "cryptomatte.h"
+#include "denoise.h"
+#include "dyn_api.h"
+#include "hala_types.h"
+#include "host_image.h"
+#include "host_scene.h"
+#include "host_util.h"
+#include "kernels.h"
+#include "temporal.h"
+
+namespace rt { std::string decode_image_file_rgba8(const char* path, uint32_t* w, uint32_t* h, std::vector<uint8_t>* rgba); }  // gltf_loader.cpp
+
+#pragma GCC visibility push(hidden)  // internal to libhalart.so: nothing below joins the exported symbols
+
+namespace rt {
+
+constexpr uint32_t kLeafMax = 4;  // triangles per leaf, large scenes: the wave tests a leaf's triangles side by side (traverse.h), so fewer, fuller leaves win (profiles/r02_experiments.txt; 2 while each lane tested its own leaves)
+constexpr uint32_t kLeafMaxStaged = 4;  // ... unless the whole tree sits in LDS: leaves of two packed pairs, fewer node steps (+2 % on Cornell)
+constexpr size_t kLdsStageBudget = 40 * 1024;  // a BVH up to this size is staged whole in LDS (next to the 24-KB stack)
+constexpr uint32_t kRefillThreshold = 24;      // idle lanes that trigger a refill of the wave (persistent_trace; profiles/r02_experiments.txt)
+constexpr int kStatRing = 16;
+// maps a material must reference to get a texel bundle.  Measured on configs[3] (profiles/texture_bundles.txt): the two-map DIFFUSE
+// materials (base colour + normal) gain from the 16-B bundle too, although half of every texel they load is idle
+#ifndef RT_BUNDLE_MIN_MAPS
+#define RT_BUNDLE_MIN_MAPS 2
+#endif
+constexpr uint32_t kBundleMinMaps = RT_BUNDLE_MIN_MAPS;
+constexpr uint32_t kMaxSampleBatch = 16;  // frames per wavefront pass in hala_rt_update_batch (~250 B of state per path)
+
+// ---- RENDER_SPEC §2.2 on the host (for tan(yfov/2); same polynomials as rt_math.h) ---------------------------
+inline float h_sin_poly(float a) {
+  float a2 = a * a;
+  float p = -2.50521083854417187751e-8f;
+  p = std::fmaf(p, a2, 2.75573192239858906526e-6f);
+  p = std::fmaf(p, a2, -1.98412698412698412698e-4f);
+  p = std::fmaf(p, a2, 8.33333333333333333333e-3f);
+  p = std::fmaf(p, a2, -1.66666666666666666667e-1f);
+  p = std::fmaf(p, a2, 1.0f);
+  return a * p;
+}
+inline float h_cos_poly(float a) {
+  float a2 = a * a;
+  float p = 2.08767569878680989792e-9f;
+  p = std::fmaf(p, a2, -2.75573192239858906526e-7f);
+  p = std::fmaf(p, a2, 2.48015873015873015873e-5f);
+  p = std::fmaf(p, a2, -1.38888888888888888889e-3f);
+  p = std::fmaf(p, a2, 4.16666666666666666667e-2f);
+  p = std::fmaf(p, a2, -0.5f);
+  p = std::fmaf(p, a2, 1.0f);
+  return p;
+}
+inline void h_sincos_rad(float a, float* s, float* c) {
+  float t = a * 0.15915494309189533577f;
+  t = t - std::floor(t);
+  if (t >= 1.0f) t = 0.0f;
+  float x = t * 4.0f;
+  int q = (int)x;
+  float f = x - (float)q;
+  float ang = f * 1.57079632679489661923f;
+  float sa = h_sin_poly(ang), ca = h_cos_poly(ang);
+  switch (q & 3) {
+    case 0: *s = sa; *c = ca; break;
+    case 1: *s = ca; *c = -sa; break;
+    case 2: *s = -sa; *c = -ca; break;
+    default: *s = -ca; *c = sa; break;
+  }
+}
+
+struct TraceEvents {
+  std::vector<hipEvent_t> ev;  // pairs
+  size_t used = 0;
+  hipEvent_t frame_begin = nullptr, frame_end = nullptr;
+  bool pending = false, counted = false;
+  uint32_t samples = 1;  // frames rendered by this wavefront pass
+  uint32_t primary_pixels = 0;  // pixels that traced a camera ray per frame (all real ones; the active blocks' under adaptive sampling)
+  uint32_t shadow_launches = 0;  // k_trace_shadow launches inside the timed brackets of this pass (0, 1 or 2 per depth)
+  // timed passes: bit d of fused_mask = the third bracket of depth d holds a fused launch (k_trace_shadow_then_batch); bit d of
+  // traced_mask = the closest-hit pass of depth d ran inside depth d - 1's fused launch (its own bracket is empty)
+  unsigned long long fused_mask = 0, traced_mask = 0;
+  QueueSizes* host_sizes = nullptr;  // pinned copy of Control::sizes as the pass left it (timed passes only)
+  Totals* host_totals = nullptr;     // pinned copy of Control::totals
+};
+
+// ---- one struct per feature -------------------------------------------------------------------------------------------------------
+
+// texel bundles (hala_types.h: BundleDesc): the co-sized 8-bit maps of a material interleaved, built by commit beside the per-texture
+// arenas; a refit follows material edits (update_texture_bundles)
+struct BundleState {
+  struct Source { uint32_t image[kBundleLanes], texture[kBundleLanes]; };  // per lane: the image (what bundles are shared by) and one texture that shows it, kAbsent = no map
+  uint32_t mode = 0;  // hala_rt_build_options::texture_bundles: 0 automatic (on), 1 off
+  bool on = false;    // as the last commit decided (automatic mode gives up when the arena cannot be had)
+  std::vector<Source> sources;
+  std::vector<BundleDesc> host;
+  DeviceArray<uint4> d_arena;
+  DeviceArray<BundleDesc> d_descs;
+  DeviceArray<uint32_t> d_material;
+  uint32_t bundled_materials = 0, unbundled_textured_materials = 0;
+  void off() { on = false; sources.clear(); host.clear(); d_arena.release(); }  // every material on the per-texture path
+};
+
+// light groups (RENDER_SPEC §14; hala_rt_set_light_groups): count 0 = off.  The tables as set (they may cover more lights /
+// materials than the committed scene has); img holds group g of every view at g * image_alloc(), laid out like accum
+struct LightGroupState {
+  uint32_t count = 0, env_group = 0;
+  std::vector<uint32_t> light_group, material_group;
+  DeviceArray<uint32_t> d_light_group, d_material_group;
+  DeviceArray<P3> ps;    // count x path slots (slot_count x batch_capacity), group-major
+  DeviceArray<float4> img;
+  DeviceArray<float4> relit[2];  // hala_rt_relight: linear, tonemapped (W x H)
+  bool relit_valid = false;
+  void off() {
+    count = 0; env_group = 0;
+    light_group.clear(); material_group.clear();
+    d_light_group.release(); d_material_group.release(); ps.release(); img.release();
+    relit[0].release(); relit[1].release(); relit_valid = false;
+  }
+};
+
+// Cryptomatte (RENDER_SPEC §15; hala_rt_set_cryptomatte): layer mask 0 = off.  rec holds one 64-B record (4 quads) per pixel slot,
+// view and enabled layer (cryptomatte.h: CryptoTables); the id tables are filled by the first update after commit, refit or the call.
+// While on, the depth-0 shade writes the 16-B first-hit record of every path slot (ps_aov_ids) whether or not image 5 is on.
+struct CryptoState {
+  uint32_t mask = 0;
+  std::vector<std::string> material_names;  // the caller's names ("" = material<m>)
+  DeviceArray<uint4> rec;
+  std::vector<uint32_t> object, asset, material;  // ids per node / node / material, as uploaded
+  DeviceArray<uint32_t> d_object, d_asset, d_material;
+  bool tables = false;  // the tables belong to the committed scene
+  bool ready = false;   // an update has folded samples since the accumulation restarted
+  size_t quads(uint32_t views, uint32_t slot_count) const { return 4 * (size_t)__builtin_popcount(mask) * views * slot_count; }
+  CryptoTables view(uint32_t slot_count) const {
+    return CryptoTables{d_object.ptr, d_asset.ptr, d_material.ptr, (uint32_t)object.size(), (uint32_t)material.size(), mask, slot_count};
+  }
+  void off() {  // (the first-hit records belong to the renderer: hala_rt_renderer::crypto_off)
+    mask = 0; material_names.clear(); tables = false;
+    rec.release(); d_object.release(); d_asset.release(); d_material.release();
+  }
+};
+
+// update() and trace_rays() share per-renderer scratch (work counters, step counters, the stack spill area): launches that use it
+// are ordered across streams by an event — the last user records one, a user on another stream waits for it first
+struct ScratchOrder {
+  hipEvent_t event = nullptr;       // not owned: a ring slot's frame_end or batch_done
+  hipStream_t stream = nullptr;
+  hipEvent_t batch_done = nullptr;
+  int acquire(hipStream_t s) {
+    if (event && stream != s) RT_HIP(hipStreamWaitEvent(s, event, 0));
+    return HALA_OK;
+  }
+  void release() { if (batch_done) (void)hipEventDestroy(batch_done); }
+};
+
+// multi-GPU exchange (C1 of SURVEY 2.1): one RCCL all-gather of the rank's tile buffer per AOV and frame, inside the library
+struct ExchangeState {
+  ncclComm_t comm = nullptr;
+  bool comm_owned = false;
+  int comm_rank = 0, comm_world = 1;
+  hipStream_t stream = nullptr;
+  DeviceArray<float4> stage[6], recv[6];
+  hipEvent_t ev_rendered = nullptr, ev_staged = nullptr, ev_gathered = nullptr;
+  uint32_t pending = 0;  // AOV mask of the collective in flight (hala_rt_tile_allgather_begin)
+  void release() {
+    if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+    for (hipEvent_t e : {ev_rendered, ev_staged, ev_gathered}) if (e) (void)hipEventDestroy(e);
+    if (comm && comm_owned) { if (const RcclApi* api = rccl_api(nullptr)) (void)api->CommDestroy(comm); }
+  }
+};
+
+// The tail of an untimed update — the last bounce's shadow launch(es), k_resolve and the read-back of the totals — runs on its own stream,
+// beside the next update's k_trace_primary, which needs none of it.  The tail uses the update's own control block
+// (d_ctl holds two, updates alternate) and its own stack spill area.  While open the renderer's stream has not waited for it:
+// every entry point joins it first (ensure_device), except update — after its camera-ray launch — and render.
+struct TailState {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_shaded = nullptr;  // the last k_shade of an untimed update: where its tail starts
+  hipEvent_t done = nullptr;       // not owned: the frame_end of that update, recorded on the tail's stream
+  bool open = false;
+  uint32_t ctl_pos = 0;            // control block of the next update
+  DeviceArray<uint2> d_spill;
+  int join(hipStream_t renderer_stream) {
+    if (open) RT_HIP(hipStreamWaitEvent(renderer_stream, done, 0));
+    open = false;
+    return HALA_OK;
+  }
+  void release() {
+    if (ev_shaded) (void)hipEventDestroy(ev_shaded);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+enum class Changed { Commit, Refit, Views, Aovs };  // hala_rt_renderer::invalidate
+
+}  // namespace rt
+
+#pragma GCC visibility pop
+
+using namespace rt;  // (every unit that includes this header is written inside the library's namespace)
+
+struct hala_rt_renderer {
+  std::string name;
+  uint32_t width = 0, height = 0;
+  int device = 0;
+  uint32_t max_depth = 0, rr_depth = 0;
+  bool enable_tonemap = false, enable_aces = false, use_simple_aces = false;
+  uint64_t max_frames = 0;
+  hipStream_t stream = nullptr;
+  uint32_t cu_count = 256;
+
+  float ground[4] = {1.0f, 1.0f, 1.0f, 1.0f};  // src/rt_renderer.rs:799
+  float sky[4] = {0.5f, 0.7f, 1.0f, 1.0f};     // :800
+  float env_intensity = 1.0f, exposure = 1.0f, env_rotation = 0.0f;  // :798-803
+
+  uint32_t n_raygen = 0, n_miss = 0, n_callable = 0, n_hit = 0;
+  DeviceArray<uint8_t> blue_noise;
+  uint32_t blue_w = 0, blue_h = 0;
+
+  bool has_scene = false, committed = false;
+  HostScene hs;
+  DeviceArray<hala_vertex> d_vertices;
+  DeviceArray<uint32_t> d_indices;
+  std::vector<size_t> prim_vertex_offset, prim_index_offset;
+  DeviceArray<hala_gpu_camera> d_cameras;
+  DeviceArray<hala_gpu_light> d_lights;
+  DeviceArray<hala_gpu_material> d_materials;
+  DeviceArray<uint8_t> d_material_kind;
+  std::vector<uint8_t> material_kind;  // host copy: a refit restamps the triangles when an edit changed a material's shading kind
+  bool shade_sort = false, simple_materials = false, scatter_media = false;
+  DeviceArray<hala_gpu_mesh_data> d_instances;
+  DeviceArray<uint32_t> d_inst_first_tri;
+  DeviceArray<float4> d_tex_arena;
+  DeviceArray<uint32_t> d_tex_arena8;  // 8-bit images: RGBA bytes, tiled 4x4 (RENDER_SPEC 7.4)
+  DeviceArray<float> d_srgb_lut, d_srgb_thr;
+  DeviceArray<TexDesc> d_textures;
+  std::vector<TexDesc> host_textures;
+  BundleState bundles;
+
+  BvhBuffers bvh{};
+  // two-level trees (RENDER_SPEC 4.5): scenes in which some primitive is referenced by several instances.  `bvh` then only carries the
+  // totals; the trees live in `blas` — [0] the world-space tree over the triangles of all instances that are NOT instanced (if any), then
+  // one object-space tree per instanced primitive — as sub-ranges of the node / triangle / shading-record arrays, behind the instance
+  // levels (the first tlas_capacity nodes), which are rebuilt on the host whenever a node moves.
+  struct Blas {
+    BvhBuffers b{};
+    uint32_t node_off = 0, tri_off = 0, node_cap = 0;
+    bool object_space = false;
+    uint32_t prim = 0;                      // object_space: the primitive (index into hs.prims)
+    std::vector<uint32_t> insts;            // world tree: the instances it holds, in instance order
+    DeviceArray<hala_gpu_mesh_data> d_md;
+    DeviceArray<uint32_t> d_first, d_gid, d_inst;
+    ~Blas() { if (b.topology) bvh_free_topology(b.topology); }
+  };
+  std::vector<std::unique_ptr<Blas>> blas;
+  bool two_level = false;
+  uint32_t instancing_mode = 0;            // hala_rt_build_options::instancing: 0 automatic (by size), 1 never (everything flattened), 2 by the rule of RENDER_SPEC 4.5
+  std::vector<uint8_t> inst_instanced;     // per instance: intersected in object space
+  std::vector<int32_t> prim_blas;          // per primitive: index into blas, -1
+  uint32_t tlas_capacity = 0, tlas_nodes = 0, stored_tris = 0;
+  std::vector<InstRef> inst_refs;
+  DeviceArray<InstRef> d_inst_refs;
+  DeviceArray<InstInfo> d_inst_info;
+  DeviceArray<Tri> d_tris_by_id, d_tris;
+  DeviceArray<Tri> d_tris_any;
+  DeviceArray<ShadeTri> d_shade_tris;
+  DeviceArray<BvhNode4> d_nodes;
+  uint32_t lds_nodes = 0, lds_tris = 0;
+  bool staged = false;  // whole BVH staged in LDS by the traversal kernels
+  uint32_t leaf_max_built = 0;
+  float ray_eps = 0.0f;
+  DeviceArray<uint2> d_spill;
+  LaunchCfg lcfg{};
+  uint32_t fuse_mode = 1;  // hala_rt_set_pass_fusion: 0 never, 1 untimed updates, 2 always (shadow passes of bounce d + closest-hit pass of bounce d + 1 in one launch)
+
+  bool has_env = false;
+  uint32_t env_w = 0, env_h = 0;
+  DeviceArray<float4> d_env;
+  DeviceArray<float> d_env_total, d_marginal, d_conditional;
+  float env_total_sum = 0.0f;
+
+  // tile shard (RENDER_SPEC §9)
+  uint32_t real_pixels = 0;  // pixels among the rank's slot_count slots that exist in the frame
+  uint32_t rank = 0, world = 1, tile_size = 32, tiles_x = 0, tiles_y = 0, tiles_per_rank = 0, perm_a_inv = 0, perm_b = 7;
+  uint32_t slot_count = 0;      // pixel slots of this rank
+  uint32_t blocks_x = 0;        // world == 1: 8 x 8 pixel blocks per row of blocks (hala_types.h: kPixelBlock)
+  // pixels of this rank's image buffers: its tile slots when sharded, the row-major frame otherwise (whose path slots may hold padding)
+  size_t image_pixels() const { return world <= 1 ? (size_t)width * height : (size_t)slot_count; }
+  uint32_t batch_capacity = 1;  // paths per pixel slot the wavefront buffers can hold in flight: samples x views (hala_rt_update_batch)
+  // views (RENDER_SPEC §12): the packed camera of each; view v's images follow view 0's in img_local, image_pixels() apart
+  std::vector<uint32_t> views{0u};
+  DeviceArray<ViewConst> d_views;  // what the kernels read when views.size() > 1 (rebuilt when a camera's yfov changes)
+  std::vector<ViewConst> views_uploaded;
+  uint32_t view_count() const { return (uint32_t)views.size(); }
+  size_t image_alloc() const { return (size_t)slot_count + (size_t)(view_count() - 1) * image_pixels(); }  // view 0 keeps its slot_count
+
+  DeviceArray<float4> img_local[6];  // accum, albedo, normal, final, position, ids (slot order); 4 and 5 only while that AOV is on
+  DeviceArray<float4> img_full[6];   // row-major, only after scatter_gathered_tiles (world > 1)
+  bool full_valid[6] = {false, false, false, false, false, false};
+  // first-hit AOVs (RENDER_SPEC §13): bit 0 position (image 4), bit 1 ids (image 5); hala_rt_set_aovs
+  uint32_t aov_mask = 0;
+  bool has_image(int which) const { return which >= 0 && (which < 4 || (which < 6 && ((aov_mask >> (which - 4)) & 1u))); }
+  DeviceArray<float4> ps_aov_pos;
+  DeviceArray<uint4> ps_aov_ids;
+  DeviceArray<uint32_t> d_inst_node, d_light_node;  // per instance / per light: the scene node it came from
+  LightGroupState groups;
+  CryptoState crypto;
+  bool wants_ids() const { return (aov_mask & 2u) || crypto.mask; }
+  void crypto_off() {
+    crypto.off();
+    if (!(aov_mask & 2u)) ps_aov_ids.release();
+  }
+  DenoiseBuffers denoise;      // RENDER_SPEC 10: allocated by the first hala_rt_denoise
+  bool denoised = false;       // denoise.out holds a result
+  AdaptiveState adaptive;      // RENDER_SPEC 11: allocated by the first hala_rt_set_adaptive_sampling that enables it
+  TemporalState temporal;      // RENDER_SPEC 16: allocated by hala_rt_set_temporal
+  DeviceArray<P3> ps_lr, ps_le, ps_alb, ps_nrm;
+  DeviceArray<hala_ray> q_rays[2];
+  DeviceArray<float4> q_state[2];
+  DeviceArray<hala_hit> q_hits;
+  DeviceArray<uint32_t> q_perm;
+  DeviceArray<ShadowEntry> q_shadow[2];
+  DeviceArray<Control> d_ctl;
+  DeviceArray<WorkCounters> d_batch_work;
+
+  uint64_t total_frames = 0;
+  bool counting = false;
+  hala_global_uniform last_uniform{};
+  TraceEvents ring[kStatRing];
+  int ring_pos = 0;
+  bool vertices_dirty = false;  // hala_rt_update_vertices since the last refit
+  bool materials_dirty_any = false;  // a material edit touched an opacity-0 material (old or new)
+  bool materials_dirty_any_refit = false;  // ... as hala_rt_refit found it
+  bool any_invisible = false;   // the scene has invisible or translucent materials: the any-hit launches traverse d_tris_any (RENDER_SPEC 7.1d)
+  bool any_translucent = false; // ... translucent ones: the ALPHA variants of the any-hit kernels
+  DeviceArray<uint8_t> d_material_any_class;
+  std::vector<uint8_t> material_any_class;
+  uint32_t launch_event_period = 0;  // per-launch timing events on every n-th update (hala_rt_set_launch_timing_period; 0: none)
+  unsigned long long update_counter = 0;
+  hala_rt_statistics stats{};
+  ScratchOrder scratch;
+  ExchangeState exchange;
+  TailState tail;
+
+  ~hala_rt_renderer() {
+    if (device >= 0) (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (tail.stream) (void)hipStreamSynchronize(tail.stream);
+    for (auto& t : ring) {
+      for (auto e : t.ev) (void)hipEventDestroy(e);
+      if (t.frame_begin) (void)hipEventDestroy(t.frame_begin);
+      if (t.frame_end) (void)hipEventDestroy(t.frame_end);
+      if (t.host_totals) (void)hipHostFree(t.host_totals);
+      if (t.host_sizes) (void)hipHostFree(t.host_sizes);
+    }
+    scratch.release();
+    exchange.release();
+    // images first, then everything else (src/rt_renderer.rs:620-633)
+    for (auto& i : img_local) i.release();
+    for (auto& i : img_full) i.release();
+    if (bvh.topology) bvh_free_topology(bvh.topology);
+    blas.clear();
+    tail.release();
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+
+  SceneView view() const {
+    SceneView sv{};
+    sv.nodes = d_nodes.ptr; sv.tris = d_tris.ptr; sv.tris_any = any_invisible ? d_tris_any.ptr : d_tris.ptr; sv.tris_by_id = d_tris_by_id.ptr; sv.shade_tris = d_shade_tris.ptr;
+    sv.inst_first_tri = d_inst_first_tri.ptr; sv.primitives = d_instances.ptr; sv.materials = d_materials.ptr; sv.material_kind = d_material_kind.ptr;
+    sv.lights = d_lights.ptr; sv.cameras = d_cameras.ptr;
+    sv.textures = d_textures.ptr; sv.tex_arena = d_tex_arena.ptr; sv.tex_arena8 = d_tex_arena8.ptr; sv.tex_lut = d_srgb_lut.ptr; sv.texture_count = (uint32_t)host_textures.size();
+    if (!bundles.host.empty()) { sv.bundles = bundles.d_descs.ptr; sv.bundle_arena = bundles.d_arena.ptr; sv.material_bundle = bundles.d_material.ptr; }
+    sv.shade_sort = shade_sort ? 1u : 0u; sv.simple_materials = simple_materials ? 1u : 0u; sv.scatter_media = scatter_media ? 1u : 0u; sv.any_translucent = any_translucent ? 1u : 0u;
+    sv.env_pixels = reinterpret_cast<const float*>(d_env.ptr); sv.env_marginal = d_marginal.ptr; sv.env_conditional = d_conditional.ptr;
+    sv.node_count = bvh.node_count; sv.tri_count = bvh.tri_count; sv.lds_nodes = lds_nodes; sv.lds_tris = lds_tris;
+    sv.inst_refs = d_inst_refs.ptr; sv.inst_info = d_inst_info.ptr; sv.instance_count = (uint32_t)hs.instances.size(); sv.two_level = two_level ? 1u : 0u;
+    sv.ray_eps = ray_eps;
+    sv.staged = staged ? 1u : 0u;
+    return sv;
+  }
+  Queues queues() const {
+    Queues q{};
+    q.rays[0] = q_rays[0].ptr; q.rays[1] = q_rays[1].ptr; q.state[0] = q_state[0].ptr; q.state[1] = q_state[1].ptr;
+    q.hits = q_hits.ptr; q.perm = q_perm.ptr; q.shadow[0] = q_shadow[0].ptr; q.shadow[1] = q_shadow[1].ptr;
+    return q;
+  }
+  PathState path_state() const {
+    return PathState{ps_lr.ptr, ps_le.ptr, ps_alb.ptr, ps_nrm.ptr, (aov_mask & 1u) ? ps_aov_pos.ptr : nullptr, wants_ids() ? ps_aov_ids.ptr : nullptr,
+                     d_inst_node.ptr, d_light_node.ptr,
+                     groups.count ? groups.ps.ptr : nullptr, groups.count ? groups.d_light_group.ptr : nullptr, groups.count ? groups.d_material_group.ptr : nullptr,
+                     groups.count, groups.count ? (uint32_t)((size_t)slot_count * batch_capacity) : 0u, groups.env_group};
+  }
+
+  // RENDER_SPEC §5 / §7.4 for packed camera `cam`: tan(yfov / 2) and the angular size of one pixel
+  ViewConst view_const(uint32_t cam, float height) const {
+    ViewConst v{};
+    float sn = 0.0f, cs = 1.0f;
+    if (cam < hs.cameras.size()) h_sincos_rad(0.5f * hs.cameras[cam].yfov, &sn, &cs);
+    v.camera = cam;
+    v.tan_half = sn / cs;
+    v.pixel_spread = 2.0f * v.tan_half / height;
+    return v;
+  }
+  FrameConst frame_const(const hala_global_uniform& u, uint32_t samples = 1) const {
+    FrameConst fc{};
+    fc.u = u;
+    fc.aspect = u.resolution[0] / u.resolution[1];
+    const ViewConst v0 = view_const(views[0], u.resolution[1]);
+    fc.tan_half = v0.tan_half;
+    fc.pixel_spread = v0.pixel_spread;
+    fc.views = view_count();
+    fc.view_pixels = (uint32_t)image_pixels();
+    fc.view_table = fc.views > 1u ? d_views.ptr : nullptr;
+    fc.width = width; fc.height = height;
+    fc.tile_size = tile_size; fc.tiles_x = tiles_x; fc.tiles_y = tiles_y; fc.world = world; fc.rank = rank; fc.blocks_x = blocks_x;
+    fc.tiles_per_rank = tiles_per_rank; fc.perm_a = perm_a_inv; fc.perm_b = perm_b;
+    fc.pixel_slots = slot_count; fc.samples = samples; fc.slot_count = slot_count * samples * fc.views;
+    if (adaptive.enabled) {  // RENDER_SPEC 11: slots for the active blocks only (one view)
+      fc.block_list = adaptive.lists[adaptive.cur].ptr;
+      fc.pixel_slots = adaptive.active_blocks * kPixelBlock * kPixelBlock;
+      fc.slot_count = fc.pixel_slots * samples;
+    }
+    return fc;
+  }
+
+  void reset_accumulation() {  // statistics.reset() of the device-lost path (src/rt_renderer.rs:557)
+    total_frames = 0;
+    for (bool& v : full_valid) v = false;
+    adaptive.restart(width * height);
+    crypto.ready = false;
+  }
+  // frames folded into the pixels that are still traced (every pixel with adaptive sampling off)
+  uint32_t rendered_frames() const { return (uint32_t)std::min(total_frames, max_frames); }
+
+  // What a change makes stale, feature by feature; the caller restarts the accumulation.  A new feature hooks in here.
+  void invalidate(Changed c) {
+    // RENDER_SPEC §15: the next update hashes the committed scene's names
+    if (c == Changed::Commit || c == Changed::Refit) crypto.tables = false;
+    // RENDER_SPEC §16: after a commit instance and material indices mean something else, and the history is validated against images 4 and
+    // 5; a refit packed the instance transforms and the cameras again, and view 0 may render another camera: only the table follows
+    if (c == Changed::Commit || (c == Changed::Aovs && (aov_mask & 3u) != 3u)) temporal.drop_history();
+    else if (c == Changed::Refit || c == Changed::Views) temporal.table_dirty = true;
+    if (c == Changed::Views) groups.relit_valid = false;
+  }
+  // the renderer's output settings, as an update uploads them
+  void output_settings(hala_global_uniform* u) const {
+    u->exposure_value = exposure; u->enable_tonemap = enable_tonemap; u->enable_aces = enable_aces; u->use_simple_aces = use_simple_aces;
+  }
+};
+
+#pragma GCC visibility push(hidden)
+namespace rt {
+
+// ---- what several units need of each other ----------------------------------------------------------------------------------------
+// renderer.hip.  join = false: update and render only, which leave the tail of the last update running (TailState)
+int ensure_device(hala_rt_renderer* r, bool join = true);
+int alloc_frame_buffers(hala_rt_renderer* r);
+std::string file_stem(const char* path);
+// rt_scene.hip
+int upload_packed(hala_rt_renderer* r, bool geometry = true);
+int upload_textures(hala_rt_renderer* r);
+int update_texture_bundles(hala_rt_renderer* r, bool fresh);
+int build_bvh(hala_rt_renderer* r);
+// rt_cryptomatte.hip
+int crypto_prepare(hala_rt_renderer* r);
+// rt_tiles.hip
+void compute_tiling(hala_rt_renderer* r);
+
+}  // namespace rt
+#pragma GCC visibility pop
