@@ -8,6 +8,8 @@ import ctypes as C
 INVALID_INDEX = 0xFFFFFFFF  # u32::MAX, reference: src/scene/cpu/node.rs:23-25
 MAX_CAMERA_COUNT = 8        # reference: src/scene/loader/gpu_uploader.rs:39
 MAX_LIGHT_COUNT = 32        # reference: src/scene/loader/gpu_uploader.rs:40
+MAX_MORPH_TARGETS = 64      # HALA_MAX_MORPH_TARGETS (docs/RENDER_SPEC.md 17)
+MAX_JOINTS = 256            # HALA_MAX_JOINTS
 
 
 class Vertex(C.Structure):  # src/scene/vertex.rs:2-9, 44 B
@@ -211,6 +213,13 @@ class TemporalParams(C.Structure):  # hala_temporal_params, 32 B (docs/RENDER_SP
     _fields_ = [("max_history", C.c_float), ("tol", C.c_float), ("min_weight", C.c_float), ("reserved", C.c_uint32 * 5)]
 
 
+class DeformerDesc(C.Structure):  # hala_deformer_desc, 64 B (docs/RENDER_SPEC.md 17)
+    _fields_ = [("mesh_index", C.c_uint32), ("primitive_index", C.c_uint32), ("target_count", C.c_uint32),
+                ("target_position_deltas", C.POINTER(C.c_float)), ("target_normal_deltas", C.POINTER(C.c_float)),
+                ("target_tangent_deltas", C.POINTER(C.c_float)), ("joint_count", C.c_uint32),
+                ("joints", C.POINTER(C.c_uint16)), ("weights", C.POINTER(C.c_float))]
+
+
 # argtypes / restype of the denoise, adaptive sampling, view and AOV entry points (load_library installs them)
 PROTOTYPES = {
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
@@ -248,6 +257,10 @@ PROTOTYPES = {
     "hala_rt_read_temporal": ([C.c_void_p, C.c_int, C.POINTER(C.c_float)], C.c_int),
     "hala_rt_get_temporal_buffer": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)], C.c_int),
     "hala_rt_denoise_temporal": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_set_deformer": ([C.c_void_p, C.POINTER(DeformerDesc)], C.c_int),
+    "hala_rt_update_deformer": ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float), C.c_uint32], C.c_int),
+    "hala_rt_clear_deformer": ([C.c_void_p, C.c_uint32, C.c_uint32], C.c_int),
+    "hala_rt_read_vertices": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)], C.c_int),
 }
 
 
@@ -291,4 +304,5 @@ EXPORTS = [
     "hala_temporal_default_params", "hala_rt_set_temporal", "hala_rt_temporal_capture", "hala_rt_temporal_resolve", "hala_rt_read_temporal",
     "hala_rt_get_temporal_buffer", "hala_rt_denoise_temporal",
     "hala_rt_texture_bundle_info",
+    "hala_rt_set_deformer", "hala_rt_update_deformer", "hala_rt_clear_deformer", "hala_rt_read_vertices",
 ]

@@ -1,0 +1,65 @@
+// deform.h — GPU-resident deformers of docs/RENDER_SPEC.md 17: morph targets and a four-influence skin per primitive, their tables on
+// the device, the parameters the host records per frame, and the host side of the kernel of deform.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <map>
+#include <memory>
+#include <vector>
+
+#include "hala_types.h"
+#include "host_util.h"
+
+namespace rt {
+
+constexpr uint32_t kMaxMorphTargets = HALA_MAX_MORPH_TARGETS;
+constexpr uint32_t kMaxJoints = HALA_MAX_JOINTS;
+constexpr uint32_t kDeformThreads = 256;  // one lane per vertex
+
+// what k_deform reads and writes of one primitive
+struct DeformTables {
+  const hala_vertex* rest;  // the rest pose, vertex_count records
+  hala_vertex* out;         // the primitive's range of the vertex arena
+  const float* dp;          // position deltas [target][vertex][3]; null: no targets
+  const float* dn;          // normal deltas, same shape, or null
+  const float* dt;          // tangent deltas, same shape, or null
+  const uint2* joints;      // four uint16 per vertex; null: no skin
+  const float4* weights;    // four floats per vertex
+  const float* palette;     // joint_count row-major 3 x 4 matrices
+  uint32_t vertex_count, joint_count;
+  uint32_t* flag;           // set to 1 when a posed position is not finite
+};
+// the targets whose weight is not 0, in ascending order (RENDER_SPEC 17): passed by value, read with scalar loads
+struct DeformActive {
+  uint32_t count;
+  uint32_t index[kMaxMorphTargets];
+  float weight[kMaxMorphTargets];
+};
+
+// The registered deformer of one primitive.  `applied` is what the arena holds, `pending` what the next refit applies.
+struct Deformer {
+  uint32_t prim = 0, vertex_count = 0, target_count = 0, joint_count = 0;
+  DeviceArray<hala_vertex> d_rest;
+  DeviceArray<float> d_dp, d_dn, d_dt, d_palette;
+  DeviceArray<uint2> d_joints;
+  DeviceArray<float4> d_weights;
+  bool has_dn = false, has_dt = false;
+  struct Params { std::vector<float> weights, palette; };
+  Params applied, pending;
+  bool dirty = false;  // hala_rt_update_deformer since the last refit
+  bool posed = false;  // the arena holds k_deform(applied) and not the rest pose as uploaded
+};
+
+struct DeformState {
+  std::map<uint32_t, std::unique_ptr<Deformer>> by_prim;  // key: index into HostScene::prims
+  DeviceArray<uint32_t> d_flags;                           // one overflow word per launch of a refit
+  bool restored = false;                                   // (deform_apply_pending: the failing refit put the arena back)
+  bool lost = false;                                       // a device error interrupted a refit's launches: the arena is undefined
+  void off() { by_prim.clear(); d_flags.release(); lost = false; }
+};
+
+// one lane per vertex, one launch on `s`
+void launch_deform(const DeformTables& t, const DeformActive& a, hipStream_t s);
+
+}  // namespace rt

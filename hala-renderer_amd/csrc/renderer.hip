@@ -248,6 +248,7 @@ int hala_rt_set_scene(hala_rt_renderer* r, const hala_scene_desc* scene) {
   RT_HIP(hipStreamSynchronize(r->stream));
   r->has_scene = false; r->committed = false;  // "Release the old scene in the GPU." (src/rt_renderer.rs:1164)
   r->temporal.drop_history();  // RENDER_SPEC §16: the history belongs to the old scene
+  r->deform.off();             // RENDER_SPEC §17: so do the deformers
   const std::string e = r->hs.assign(scene);
   if (!e.empty()) RT_FAIL(e);
   if (upload_packed(r) != HALA_OK) return HALA_ERR;

@@ -1,6 +1,6 @@
 // renderer_state.h — the renderer object behind the C ABI (struct hala_rt_renderer), shared by the host units that implement it:
 // renderer.hip (life cycle, scene, update), rt_scene.hip (uploads, trees, edits), rt_outputs.hip (views, AOVs, adaptive sampling, light
-// groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
+// groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_deform.hip (deformers), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
 // Each feature keeps its state in one struct that knows how to turn itself off.  Nothing outside csrc/ includes this header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 
 #include "adaptive.h"
 #include "cryptomatte.h"
+#include "deform.h"
 #include "denoise.h"
 #include "dyn_api.h"
 #include "hala_types.h"
@@ -329,6 +330,7 @@ struct hala_rt_renderer {
   bool denoised = false;       // denoise.out holds a result
   AdaptiveState adaptive;      // RENDER_SPEC 11: allocated by the first hala_rt_set_adaptive_sampling that enables it
   TemporalState temporal;      // RENDER_SPEC 16: allocated by hala_rt_set_temporal
+  DeformState deform;          // RENDER_SPEC 17: one deformer per primitive (hala_rt_set_deformer)
   DeviceArray<P3> ps_lr, ps_le, ps_alb, ps_nrm;
   DeviceArray<hala_ray> q_rays[2];
   DeviceArray<float4> q_state[2];
@@ -477,6 +479,9 @@ int upload_packed(hala_rt_renderer* r, bool geometry = true);
 int upload_textures(hala_rt_renderer* r);
 int update_texture_bundles(hala_rt_renderer* r, bool fresh);
 int build_bvh(hala_rt_renderer* r);
+// rt_deform.hip: poses the deformers whose parameters changed (hala_rt_refit, on an idle stream); is a deformer registered on the primitive
+int deform_apply_pending(hala_rt_renderer* r);
+bool deform_registered(const hala_rt_renderer* r, uint32_t prim);
 // rt_cryptomatte.hip
 int crypto_prepare(hala_rt_renderer* r);
 // rt_tiles.hip

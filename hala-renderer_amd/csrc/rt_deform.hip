@@ -1,0 +1,219 @@
+// rt_deform.hip — deformers (docs/RENDER_SPEC.md 17; include/halart.h "Deformers"): the registry of one deformer per primitive, the
+// host-side checks of tables and parameters, the launches of k_deform (deform.hip) that hala_rt_refit makes ahead of refitting the
+// tree, and the read-back of a primitive's vertices.  Invariant: the primitive's range of the vertex arena holds the rest pose while
+// Deformer::posed is false, and k_deform(rest, tables, Deformer::applied) otherwise; HostPrimitive::vertices stays the rest pose.
+#include "renderer_state.h"
+
+namespace rt {
+
+static int find_primitive(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, uint32_t* prim) {
+  if (mesh_index + 1u >= r->hs.mesh_first_prim.size() || mesh_index == 0xffffffffu) RT_FAIL("The mesh does not exist.");
+  const uint32_t first = r->hs.mesh_first_prim[mesh_index], end = r->hs.mesh_first_prim[mesh_index + 1u];
+  if (primitive_index >= end - first) RT_FAIL("The primitive does not exist.");
+  *prim = first + primitive_index;
+  return HALA_OK;
+}
+
+static bool all_finite(const float* v, size_t n) {
+  for (size_t k = 0; k < n; ++k)
+    if (!std::isfinite(v[k])) return false;
+  return true;
+}
+
+// RENDER_SPEC §16: no motion is known under a deformation; every instance of the primitive starts without history
+static void mark_no_history(hala_rt_renderer* r, uint32_t prim) {
+  if (!r->temporal.enabled) return;
+  for (size_t i = 0; i < r->hs.instance_prim.size() && i < r->temporal.inst_marked.size(); ++i)
+    if (r->hs.instance_prim[i] == prim) { r->temporal.inst_marked[i] = 1; r->temporal.table_dirty = true; }
+}
+
+static hala_vertex* arena_of(hala_rt_renderer* r, uint32_t prim) { return r->d_vertices.ptr + r->prim_vertex_offset[prim]; }
+
+// the arena's range of the primitive <- the rest pose (stream-ordered); the tree follows at the next refit
+static int restore_rest(hala_rt_renderer* r, Deformer& d) {
+  if (d.vertex_count)
+    RT_HIP(hipMemcpyAsync(arena_of(r, d.prim), d.d_rest.ptr, (size_t)d.vertex_count * sizeof(hala_vertex), hipMemcpyDeviceToDevice, r->stream));
+  d.posed = false;
+  return HALA_OK;
+}
+
+static int launch(hala_rt_renderer* r, Deformer& d, const Deformer::Params& p, uint32_t* flag) {
+  DeformTables t{};
+  t.rest = d.d_rest.ptr; t.out = arena_of(r, d.prim);
+  t.dp = d.target_count ? d.d_dp.ptr : nullptr;
+  t.dn = d.has_dn ? d.d_dn.ptr : nullptr;
+  t.dt = d.has_dt ? d.d_dt.ptr : nullptr;
+  t.joints = d.joint_count ? d.d_joints.ptr : nullptr;
+  t.weights = d.d_weights.ptr; t.palette = d.d_palette.ptr;
+  t.vertex_count = d.vertex_count; t.joint_count = d.joint_count;
+  t.flag = flag;
+  DeformActive a{};
+  for (uint32_t k = 0; k < d.target_count; ++k)
+    if (p.weights[k] != 0.0f) { a.index[a.count] = k; a.weight[a.count] = p.weights[k]; ++a.count; }
+  // (the palette lives in the Deformer, which outlives the copy: every caller synchronises before it changes the parameters)
+  if (d.joint_count) RT_HIP(hipMemcpyAsync(d.d_palette.ptr, p.palette.data(), p.palette.size() * 4, hipMemcpyHostToDevice, r->stream));
+  launch_deform(t, a, r->stream);
+  RT_HIP(hipGetLastError());
+  return HALA_OK;
+}
+
+// hala_rt_refit, on an idle stream: poses every deformer whose parameters changed.  Overflow to a non-finite position: the arena is put
+// back by running the kernel again with the last applied parameters — it is deterministic, and the common case pays for no spare
+// buffer and no copy —, the offending parameters are dropped, and the refit fails.
+static int apply_pending(hala_rt_renderer* r);
+// A HIP error between the first launch and the bookkeeping leaves some deformers posed on the device and none recorded as such (such
+// errors are sticky: the device is gone).  The invariant above no longer holds, so every later refit is refused until hala_rt_set_scene
+// uploads the arena again.
+int deform_apply_pending(hala_rt_renderer* r) {
+  if (r->deform.lost) RT_FAIL("A device error interrupted an earlier deformation and the vertices on the device are undefined: set the scene again.");
+  r->deform.lost = true;
+  const int e = apply_pending(r);
+  // (the overflow refusal comes back with the arena restored and synchronised: that one is not a loss)
+  if (e == HALA_OK || r->deform.restored) r->deform.lost = false;
+  r->deform.restored = false;
+  return e;
+}
+static int apply_pending(hala_rt_renderer* r) {
+  std::vector<Deformer*> dirty;
+  for (auto& kv : r->deform.by_prim)
+    if (kv.second->dirty) dirty.push_back(kv.second.get());
+  if (dirty.empty()) return HALA_OK;
+  RT_HIP(r->deform.d_flags.resize(dirty.size()));
+  RT_HIP(hipMemsetAsync(r->deform.d_flags.ptr, 0, dirty.size() * 4, r->stream));
+  for (size_t k = 0; k < dirty.size(); ++k)
+    if (launch(r, *dirty[k], dirty[k]->pending, r->deform.d_flags.ptr + k) != HALA_OK) return HALA_ERR;
+  std::vector<uint32_t> flags(dirty.size());
+  RT_HIP(hipMemcpyAsync(flags.data(), r->deform.d_flags.ptr, flags.size() * 4, hipMemcpyDeviceToHost, r->stream));
+  RT_HIP(hipStreamSynchronize(r->stream));
+  bool overflow = false;
+  for (uint32_t f : flags) overflow = overflow || f != 0u;
+  if (overflow) {
+    for (size_t k = 0; k < dirty.size(); ++k) {
+      Deformer& d = *dirty[k];
+      if (!d.posed) { if (restore_rest(r, d) != HALA_OK) return HALA_ERR; }
+      else if (launch(r, d, d.applied, r->deform.d_flags.ptr + k) != HALA_OK) return HALA_ERR;
+    }
+    RT_HIP(hipStreamSynchronize(r->stream));
+    for (size_t k = 0; k < dirty.size(); ++k)
+      if (flags[k]) { dirty[k]->pending = dirty[k]->applied; dirty[k]->dirty = false; }
+    r->deform.restored = true;
+    RT_FAIL("Vertex position is not finite.");
+  }
+  for (Deformer* d : dirty) {
+    d->applied = d->pending; d->dirty = false; d->posed = true;
+    mark_no_history(r, d->prim);
+  }
+  r->vertices_dirty = true;
+  return HALA_OK;
+}
+
+bool deform_registered(const hala_rt_renderer* r, uint32_t prim) { return r->deform.by_prim.count(prim) != 0; }
+
+}  // namespace rt
+
+extern "C" {
+
+int hala_rt_set_deformer(hala_rt_renderer* r, const hala_deformer_desc* desc) {
+  if (!r || !desc) RT_FAIL("Invalid argument.");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  uint32_t prim = 0;
+  if (find_primitive(r, desc->mesh_index, desc->primitive_index, &prim) != HALA_OK) return HALA_ERR;
+  if (desc->target_count > kMaxMorphTargets) RT_FAIL("The deformer has more than " + std::to_string(kMaxMorphTargets) + " morph targets.");
+  if (desc->joint_count > kMaxJoints) RT_FAIL("The deformer has more than " + std::to_string(kMaxJoints) + " joints.");
+  if (desc->target_count == 0u && desc->joint_count == 0u) RT_FAIL("The deformer has neither morph targets nor a skin.");
+  if (desc->target_count && !desc->target_position_deltas) RT_FAIL("The deformer's morph targets have no position deltas.");
+  if (desc->joint_count && (!desc->joints || !desc->weights)) RT_FAIL("The deformer's skin has no joints or no weights.");
+  const HostPrimitive& p = r->hs.prims[prim];
+  const size_t nv = p.vertices.size(), nd = (size_t)desc->target_count * nv * 3u;
+  const bool has_dn = desc->target_count && desc->target_normal_deltas, has_dt = desc->target_count && desc->target_tangent_deltas;
+  if (!all_finite(desc->target_position_deltas, nd) || (has_dn && !all_finite(desc->target_normal_deltas, nd)) ||
+      (has_dt && !all_finite(desc->target_tangent_deltas, nd)))
+    RT_FAIL("A morph target delta is not finite.");
+  if (desc->joint_count) {
+    for (size_t k = 0; k < nv * 4u; ++k)
+      if (desc->joints[k] >= desc->joint_count) RT_FAIL("A joint index is not below the joint count (" + std::to_string(desc->joint_count) + ").");
+    if (!all_finite(desc->weights, nv * 4u)) RT_FAIL("A skin weight is not finite.");
+  }
+  std::unique_ptr<Deformer> d(new Deformer());
+  d->prim = prim; d->vertex_count = (uint32_t)nv; d->target_count = desc->target_count; d->joint_count = desc->joint_count;
+  d->has_dn = has_dn; d->has_dt = has_dt;
+  RT_HIP(d->d_rest.upload(p.vertices.data(), nv, r->stream));  // (the host copy is the rest pose: nothing but the upload reads it after commit)
+  if (desc->target_count) RT_HIP(d->d_dp.upload(desc->target_position_deltas, nd, r->stream));
+  if (has_dn) RT_HIP(d->d_dn.upload(desc->target_normal_deltas, nd, r->stream));
+  if (has_dt) RT_HIP(d->d_dt.upload(desc->target_tangent_deltas, nd, r->stream));
+  if (desc->joint_count) {
+    RT_HIP(d->d_joints.upload(reinterpret_cast<const uint2*>(desc->joints), nv, r->stream));
+    RT_HIP(d->d_weights.upload(reinterpret_cast<const float4*>(desc->weights), nv, r->stream));
+    RT_HIP(d->d_palette.resize((size_t)desc->joint_count * 12u));
+  }
+  d->applied.weights.assign(desc->target_count, 0.0f);
+  d->applied.palette.assign((size_t)desc->joint_count * 12u, 0.0f);
+  for (uint32_t j = 0; j < desc->joint_count; ++j) d->applied.palette[j * 12u] = d->applied.palette[j * 12u + 5u] = d->applied.palette[j * 12u + 10u] = 1.0f;
+  d->pending = d->applied;
+  auto old = r->deform.by_prim.find(prim);
+  if (old != r->deform.by_prim.end() && old->second->posed) {  // the arena holds the old deformer's pose: back to the rest pose
+    if (restore_rest(r, *d) != HALA_OK) return HALA_ERR;
+    r->vertices_dirty = true;
+    mark_no_history(r, prim);
+  }
+  RT_HIP(hipStreamSynchronize(r->stream));  // the caller's tables may go
+  r->deform.by_prim[prim] = std::move(d);
+  return HALA_OK;
+}
+
+int hala_rt_update_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, const float* morph_weights, uint32_t weight_count,
+                            const float* joint_matrices_3x4, uint32_t joint_count) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  uint32_t prim = 0;
+  if (find_primitive(r, mesh_index, primitive_index, &prim) != HALA_OK) return HALA_ERR;
+  auto it = r->deform.by_prim.find(prim);
+  if (it == r->deform.by_prim.end()) RT_FAIL("The primitive has no deformer.");
+  Deformer& d = *it->second;
+  if (morph_weights && weight_count != d.target_count)
+    RT_FAIL("The weight count differs from the deformer's target count (" + std::to_string(d.target_count) + ").");
+  if (joint_matrices_3x4 && joint_count != d.joint_count)
+    RT_FAIL("The joint count differs from the deformer's joint count (" + std::to_string(d.joint_count) + ").");
+  if (morph_weights && !all_finite(morph_weights, weight_count)) RT_FAIL("A morph weight is not finite.");
+  if (joint_matrices_3x4 && !all_finite(joint_matrices_3x4, (size_t)joint_count * 12u)) RT_FAIL("A joint matrix is not finite.");
+  if (morph_weights) d.pending.weights.assign(morph_weights, morph_weights + weight_count);
+  if (joint_matrices_3x4) d.pending.palette.assign(joint_matrices_3x4, joint_matrices_3x4 + (size_t)joint_count * 12u);
+  d.dirty = d.dirty || morph_weights || joint_matrices_3x4;
+  return HALA_OK;
+}
+
+int hala_rt_clear_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  uint32_t prim = 0;
+  if (find_primitive(r, mesh_index, primitive_index, &prim) != HALA_OK) return HALA_ERR;
+  auto it = r->deform.by_prim.find(prim);
+  if (it == r->deform.by_prim.end()) RT_FAIL("The primitive has no deformer.");
+  if (it->second->posed) {
+    if (restore_rest(r, *it->second) != HALA_OK) return HALA_ERR;
+    RT_HIP(hipStreamSynchronize(r->stream));  // the copy reads the tables freed below
+    r->vertices_dirty = true;
+    mark_no_history(r, prim);
+  }
+  r->deform.by_prim.erase(it);
+  return HALA_OK;
+}
+
+int hala_rt_read_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, hala_vertex* dst, uint32_t capacity, uint32_t* count) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!count) RT_FAIL("Invalid argument.");
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  uint32_t prim = 0;
+  if (find_primitive(r, mesh_index, primitive_index, &prim) != HALA_OK) return HALA_ERR;
+  const size_t nv = r->hs.prims[prim].vertices.size();
+  *count = (uint32_t)nv;
+  const size_t n = std::min<size_t>(capacity, nv);
+  if (dst && n) {
+    RT_HIP(hipMemcpyAsync(dst, arena_of(r, prim), n * sizeof(hala_vertex), hipMemcpyDeviceToHost, r->stream));
+    RT_HIP(hipStreamSynchronize(r->stream));
+  }
+  return HALA_OK;
+}
+
+}  // extern "C"

@@ -630,6 +630,7 @@ int hala_rt_update_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
   const uint32_t first = r->hs.mesh_first_prim[mesh_index], end = r->hs.mesh_first_prim[mesh_index + 1u];
   if (primitive_index >= end - first) RT_FAIL("The primitive does not exist.");
   HostPrimitive& p = r->hs.prims[first + primitive_index];
+  if (deform_registered(r, first + primitive_index)) RT_FAIL("The primitive has a deformer: clear it first (hala_rt_clear_deformer).");
   if (vertex_count != p.vertices.size()) RT_FAIL("The vertex count differs from the primitive's (" + std::to_string(p.vertices.size()) + "): refit keeps the topology, use set_scene + commit.");
   for (uint32_t k = 0; k < vertex_count; ++k)
     if (!std::isfinite(vertices[k].position[0]) || !std::isfinite(vertices[k].position[1]) || !std::isfinite(vertices[k].position[2])) RT_FAIL("Vertex position is not finite.");
@@ -658,6 +659,7 @@ int hala_rt_refit(hala_rt_renderer* r) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
   RT_HIP(hipStreamSynchronize(r->stream));
+  if (deform_apply_pending(r) != HALA_OK) return HALA_ERR;  // RENDER_SPEC §17: the posed vertices, just ahead of the refit that reads them
   const std::vector<hala_gpu_mesh_data> before = r->hs.instances;  // object -> world of every instance as the tree was fitted to it
   const std::vector<uint8_t> kinds_before = r->material_kind;
   r->hs.update_node_hierarchies();

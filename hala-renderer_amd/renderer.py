@@ -527,6 +527,69 @@ class HalaRenderer:
     def refit(self):
         self._check(self._lib.hala_rt_refit(self._h))
 
+    # -- deformers (docs/RENDER_SPEC.md 17; include/halart.h "Deformers") ---------------------------------------------------------------
+    def set_deformer(self, mesh, prim, targets=None, normal_targets=None, tangent_targets=None, joints=None, weights=None, joint_count=0):
+        """register morph targets ([T, V, 3] position deltas, optionally normal / tangent deltas of the same shape) and / or a skin
+        (joints [V, 4] uint16 below joint_count, weights [V, 4]) on one primitive of the committed scene; its current vertices become
+        the rest pose.  Uploaded once; update_deformer() then poses it"""
+        fp = C.POINTER(C.c_float)
+
+        def deltas(a):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            return a, a.ctypes.data_as(fp)
+
+        d = A.DeformerDesc()
+        d.mesh_index, d.primitive_index = mesh, prim
+        t, d.target_position_deltas = deltas(targets)
+        nt, d.target_normal_deltas = deltas(normal_targets)
+        tt, d.target_tangent_deltas = deltas(tangent_targets)
+        d.target_count = 0 if t is None else t.shape[0]
+        for other in (nt, tt):
+            if other is not None and (t is None or other.shape != t.shape):
+                raise ValueError("normal and tangent deltas have the shape of the position deltas")
+        d.joint_count = joint_count
+        j = w = None
+        if joint_count:
+            if joints is None or weights is None:
+                raise ValueError("a skin (joint_count > 0) needs joints and weights, both [V, 4]")
+            j = np.ascontiguousarray(joints, dtype=np.uint16)
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if j.ndim != 2 or j.shape[1] != 4 or w.shape != j.shape:
+                raise ValueError("joints and weights are [V, 4]")
+            d.joints, d.weights = j.ctypes.data_as(C.POINTER(C.c_uint16)), w.ctypes.data_as(fp)
+        n = C.c_uint32(0)
+        self._check(self._lib.hala_rt_read_vertices(self._h, C.c_uint32(mesh), C.c_uint32(prim), None, C.c_uint32(0), C.byref(n)))
+        for a in (t, nt, tt):
+            if a is not None and (a.ndim != 3 or a.shape[1:] != (n.value, 3)):
+                raise ValueError(f"morph target deltas are [T, {n.value}, 3]")
+        if j is not None and j.shape[0] != n.value:
+            raise ValueError(f"joints and weights are [{n.value}, 4]")
+        self._check(self._lib.hala_rt_set_deformer(self._h, C.byref(d)))
+
+    def update_deformer(self, mesh, prim, morph_weights=None, joint_matrices=None):
+        """this frame's pose: morph weights [T] and / or joint matrices [J, 3, 4] (row-major, in the primitive's object space); None
+        keeps that part.  Recorded on the host only; applied by the next refit()"""
+        fp = C.POINTER(C.c_float)
+        w = None if morph_weights is None else np.ascontiguousarray(morph_weights, dtype=np.float32).reshape(-1)
+        m = None if joint_matrices is None else np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 12)
+        self._check(self._lib.hala_rt_update_deformer(self._h, C.c_uint32(mesh), C.c_uint32(prim),
+                                                      None if w is None else w.ctypes.data_as(fp), C.c_uint32(0 if w is None else w.shape[0]),
+                                                      None if m is None else m.ctypes.data_as(fp), C.c_uint32(0 if m is None else m.shape[0])))
+
+    def clear_deformer(self, mesh, prim):
+        """remove the primitive's deformer: the rest pose is back at the next refit()"""
+        self._check(self._lib.hala_rt_clear_deformer(self._h, C.c_uint32(mesh), C.c_uint32(prim)))
+
+    def read_vertices(self, mesh, prim) -> np.ndarray:
+        """a primitive's vertices as the device holds them (VERTEX_DTYPE records): the posed mesh of a deformed primitive"""
+        n = C.c_uint32(0)
+        self._check(self._lib.hala_rt_read_vertices(self._h, C.c_uint32(mesh), C.c_uint32(prim), None, C.c_uint32(0), C.byref(n)))
+        out = np.empty(n.value, dtype=A.VERTEX_DTYPE)
+        self._check(self._lib.hala_rt_read_vertices(self._h, C.c_uint32(mesh), C.c_uint32(prim), C.c_void_p(out.ctypes.data), C.c_uint32(n.value), C.byref(n)))
+        return out
+
     # -- multi-GPU tile sharding ---------------------------------------------------------------------------------------
     def set_tile_shard(self, rank, world, tile_size=32):
         self._check(self._lib.hala_rt_set_tile_shard(self._h, C.c_uint32(rank), C.c_uint32(world), C.c_uint32(tile_size)))

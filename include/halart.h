@@ -32,6 +32,8 @@ extern "C" {
 #define HALA_INVALID_INDEX 0xffffffffu /* u32::MAX "none" marker (src/scene/cpu/node.rs:23-25) */
 #define HALA_MAX_CAMERA_COUNT 8        /* src/scene/loader/gpu_uploader.rs:39 */
 #define HALA_MAX_LIGHT_COUNT 32        /* src/scene/loader/gpu_uploader.rs:40 */
+#define HALA_MAX_MORPH_TARGETS 64      /* morph targets of one deformer (docs/RENDER_SPEC.md 17) */
+#define HALA_MAX_JOINTS 256            /* joint matrices of one deformer's palette */
 
 /* ------------------------------------------------------------------------------------------------
  * Byte-exact device records (what the reference's shaders read).  Sizes/offsets are static_asserted
@@ -734,6 +736,50 @@ int hala_rt_update_material(hala_rt_renderer* r, uint32_t material_index, const 
  * tables and the adaptive-sampling parameters are kept.  hala_rt_denoise is refused until new samples (and, sharded, a new gather)
  * arrive; hala_rt_read_denoised keeps returning the last denoised frame. */
 int hala_rt_refit(hala_rt_renderer* r);
+
+/* ------------------------------------------------------------------------------------------------
+ * Deformers (docs/RENDER_SPEC.md 17; no reference equivalent): morph targets and a four-influence skin of one primitive, resident on
+ * the GPU.  The rest pose, the deltas and the skin bindings are uploaded once; per frame the host hands over morph weights and joint
+ * matrices (a few hundred bytes), and the next hala_rt_refit poses the vertices on the device just ahead of refitting the tree.
+ * A renderer that never registers a deformer behaves exactly as before.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hala_deformer_desc {
+  uint32_t mesh_index, primitive_index;
+  uint32_t target_count;               /* 0 .. HALA_MAX_MORPH_TARGETS */
+  const float* target_position_deltas; /* [target][vertex][3] */
+  const float* target_normal_deltas;   /* same shape, or NULL */
+  const float* target_tangent_deltas;  /* same shape, or NULL */
+  uint32_t joint_count;                /* 0: no skin; <= HALA_MAX_JOINTS */
+  const uint16_t* joints;              /* [vertex][4], each < joint_count */
+  const float* weights;                /* [vertex][4], used as given (not renormalised) */
+} hala_deformer_desc; /* 64 B */
+/* Registers a deformer on one primitive of the committed scene (before hala_rt_commit the call is refused like the other edits).  The
+ * primitive's current vertices become the rest pose; host pointers, copied to the device before the call returns.  The weights start
+ * at 0 and the palette at the identity: a refit right after the call changes nothing.  One deformer per primitive: a second call
+ * replaces the first (the rest pose stays the one the first call took).  Refused, changing nothing: the mesh or primitive does not
+ * exist; target_count above HALA_MAX_MORPH_TARGETS or joint_count above HALA_MAX_JOINTS; neither targets nor a skin; a joint index
+ * >= joint_count; a delta or weight that is not finite (checked here, on the host).  hala_rt_set_scene drops every deformer. */
+int hala_rt_set_deformer(hala_rt_renderer* r, const hala_deformer_desc* desc);
+/* Records the pose of a deformer on the host: no device work, no synchronisation.  morph_weights (weight_count of them) and
+ * joint_matrices_3x4 (joint_count row-major 3 x 4 matrices acting in the primitive's object space, after the morph) may each be NULL:
+ * that part of the pose is kept.  Takes effect at the next hala_rt_refit: until then updates render the scene as it was and keep
+ * accumulating.  Refused, changing nothing: the primitive has no deformer; weight_count differs from the registered target_count or
+ * joint_count from the registered joint_count; a weight or matrix entry that is not finite. */
+int hala_rt_update_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, const float* morph_weights,
+                            uint32_t weight_count, const float* joint_matrices_3x4, uint32_t joint_count);
+/* Removes the deformer of a primitive: the next hala_rt_refit restores the rest pose and frees the tables.  Refused when the primitive
+ * has none.  While a primitive has a deformer, hala_rt_update_vertices on it is refused ("clear it first").
+ * The refit contract: hala_rt_refit poses every deformer whose parameters changed (one kernel launch each on the renderer's stream)
+ * and then refits as it does after hala_rt_update_vertices; every instance of a posed primitive starts without temporal history
+ * (hala_rt_set_temporal).  Finite parameters can still overflow: when a posed position is not finite, hala_rt_refit fails with
+ * "Vertex position is not finite.", the vertices and the tree stay exactly as they were, the offending parameters fall back to the last
+ * applied ones, and every other pending edit stays pending for the next refit. */
+int hala_rt_clear_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index);
+/* Reads a primitive's vertices back from the device, behind everything enqueued on the renderer's stream: the posed mesh of a deformed
+ * primitive (as the last refit left it), the uploaded vertices of any other.  Copies min(capacity, count) records; *count receives
+ * the primitive's vertex count.  Needs a committed scene. */
+int hala_rt_read_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, hala_vertex* dst, uint32_t capacity,
+                          uint32_t* count);
 
 /* ------------------------------------------------------------------------------------------------
  * Denoising (docs/RENDER_SPEC.md 10; no reference equivalent): an edge-avoiding a-trous wavelet filter over the running
