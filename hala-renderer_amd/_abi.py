@@ -252,6 +252,7 @@ PROTOTYPES = {
     "hala_rt_texture_bundle_info": ([C.c_void_p, C.POINTER(TextureBundleInfo)], C.c_int),
     "hala_temporal_default_params": ([C.POINTER(TemporalParams)], None),
     "hala_rt_set_temporal": ([C.c_void_p, C.POINTER(TemporalParams)], C.c_int),
+    "hala_rt_set_temporal_vertex_motion": ([C.c_void_p, C.c_int], C.c_int),
     "hala_rt_temporal_capture": ([C.c_void_p], C.c_int),
     "hala_rt_temporal_resolve": ([C.c_void_p, C.POINTER(C.c_float)], C.c_int),
     "hala_rt_read_temporal": ([C.c_void_p, C.c_int, C.POINTER(C.c_float)], C.c_int),
@@ -302,7 +303,7 @@ EXPORTS = [
     "hala_rt_set_cryptomatte", "hala_rt_read_cryptomatte", "hala_rt_read_cryptomatte_records", "hala_rt_get_cryptomatte_manifest",
     "hala_rt_save_cryptomatte", "hala_cryptomatte_hash", "hala_write_exr",
     "hala_temporal_default_params", "hala_rt_set_temporal", "hala_rt_temporal_capture", "hala_rt_temporal_resolve", "hala_rt_read_temporal",
-    "hala_rt_get_temporal_buffer", "hala_rt_denoise_temporal",
+    "hala_rt_get_temporal_buffer", "hala_rt_denoise_temporal", "hala_rt_set_temporal_vertex_motion",
     "hala_rt_texture_bundle_info",
     "hala_rt_set_deformer", "hala_rt_update_deformer", "hala_rt_clear_deformer", "hala_rt_read_vertices",
 ]

@@ -102,6 +102,8 @@ static int temporal_enqueue_resolve(hala_rt_renderer* r, hipEvent_t before = nul
   const bool hist = t.has_history && t.world.size() == 16 * hs.instances.size() && t.inst_marked.size() == hs.instances.size() &&
                     t.mat_marked.size() == hs.gpu_materials.size();
   const uint32_t ni = hist ? (uint32_t)hs.instances.size() : 0u, nm = hist ? (uint32_t)hs.gpu_materials.size() : 0u;
+  // RENDER_SPEC 16 "Vertex motion": the snapshot can follow a vertex edit only on the one-level tree it was taken from
+  const bool follow = hist && t.vertex_motion && t.has_snapshot && !r->two_level && t.snapshot.count == r->bvh.tri_count && r->bvh.tri_count != 0u;
   if (t.table_dirty || !t.table.ptr) {
     constexpr size_t kHeadWords = sizeof(TemporalHead) / 4, kInstWords = sizeof(TemporalInst) / 4;
     std::vector<uint32_t> tab(kHeadWords + (size_t)ni * kInstWords + nm, 0u);
@@ -112,10 +114,12 @@ static int temporal_enqueue_resolve(hala_rt_renderer* r, hipEvent_t before = nul
     hd.max_history = t.p.max_history; hd.tol = t.p.tol; hd.min_weight = t.p.min_weight;
     hd.inst_count = ni; hd.mat_count = nm;
     memcpy(tab.data(), &hd, sizeof(hd));
+    t.table_vertex = false;
     for (uint32_t i = 0; i < ni; ++i) {
       TemporalInst ti{};
       const bool ok = temporal_motion(&t.world[16 * (size_t)i], hs.instances[i].transform, ti.d);
-      ti.marked = (!ok || t.inst_marked[i]) ? 1u : 0u;
+      ti.marked = !ok ? 1u : (t.inst_marked[i] ? (follow ? 2u : 1u) : 0u);
+      t.table_vertex = t.table_vertex || ti.marked == 2u;
       memcpy(tab.data() + kHeadWords + (size_t)i * kInstWords, &ti, sizeof(ti));
     }
     for (uint32_t m = 0; m < nm; ++m) tab[kHeadWords + (size_t)ni * kInstWords + m] = t.mat_marked[m] ? 1u : 0u;
@@ -127,7 +131,8 @@ static int temporal_enqueue_resolve(hala_rt_renderer* r, hipEvent_t before = nul
   if (before) RT_HIP(hipEventRecord(before, r->stream));  // a timed resolve brackets the launch alone
   launch_temporal_resolve(r->img_local[0].ptr, r->img_local[4].ptr, reinterpret_cast<const uint4*>(r->img_local[5].ptr), t.hc.ptr, t.hp.ptr,
                           reinterpret_cast<const uint4*>(t.hi.ptr), t.table.ptr, r->width, r->height, r->rendered_frames(), hist, t.out[0].ptr,
-                          t.out[1].ptr, r->stream);
+                          t.out[1].ptr, t.table_vertex ? r->d_tris_by_id.ptr : nullptr, t.table_vertex ? t.snapshot.ptr : nullptr,
+                          t.table_vertex ? r->bvh.tri_count : 0u, r->stream);
   RT_HIP(hipGetLastError());
   t.resolved = true;
   return HALA_OK;
@@ -159,13 +164,33 @@ int hala_rt_set_temporal(hala_rt_renderer* r, const hala_temporal_params* p) {
   t.table_dirty = true;
   return HALA_OK;
 }
+int hala_rt_set_temporal_vertex_motion(hala_rt_renderer* r, int enable) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (!r->temporal.enabled) RT_FAIL("hala_rt_set_temporal_vertex_motion: temporal reprojection is off (hala_rt_set_temporal).");
+  TemporalState& t = r->temporal;
+  if (!enable && t.has_snapshot) {
+    if (ensure_device(r) != HALA_OK) return HALA_ERR;
+    RT_HIP(hipStreamSynchronize(r->stream));  // a resolve may still read the snapshot
+    t.drop_snapshot();
+  }
+  t.vertex_motion = enable != 0;
+  t.table_dirty = true;
+  return HALA_OK;
+}
 int hala_rt_temporal_capture(hala_rt_renderer* r) {
   RtRange range("halart::temporal_capture");
   if (temporal_ready(r, "hala_rt_temporal_capture") != HALA_OK) return HALA_ERR;
   if (r->rendered_frames() == 0) return HALA_OK;  // two edits with no frame between: the history stands
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
-  if (temporal_enqueue_resolve(r) != HALA_OK) return HALA_ERR;
   TemporalState& t = r->temporal;
+  // RENDER_SPEC 16 "Vertex motion": the snapshot of the new history.  A snapshot of another size follows nothing, so it goes before the
+  // resolve; one of this size is what the resolve reads, and the copy below overwrites it behind the resolve on the same stream.
+  const uint32_t snap_count = t.vertex_motion && !r->two_level ? r->bvh.tri_count : 0u;
+  if (t.has_snapshot && t.snapshot.count != snap_count) { RT_HIP(hipStreamSynchronize(r->stream)); t.drop_snapshot(); }
+  if (snap_count) RT_HIP(t.snapshot.resize(snap_count));
+  if (temporal_enqueue_resolve(r) != HALA_OK) return HALA_ERR;
+  if (snap_count) RT_HIP(hipMemcpyAsync(t.snapshot.ptr, r->d_tris_by_id.ptr, (size_t)snap_count * sizeof(Tri), hipMemcpyDeviceToDevice, r->stream));
+  t.has_snapshot = snap_count != 0u;
   const size_t bytes = (size_t)r->width * r->height * sizeof(float4);
   RT_HIP(hipMemcpyAsync(t.hc.ptr, t.out[0].ptr, bytes, hipMemcpyDeviceToDevice, r->stream));
   RT_HIP(hipMemcpyAsync(t.hp.ptr, r->img_local[4].ptr, bytes, hipMemcpyDeviceToDevice, r->stream));

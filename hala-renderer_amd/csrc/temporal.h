@@ -29,7 +29,7 @@ struct TemporalHead {
 };
 struct TemporalInst {
   float d[12];      // D = W_prev . W_cur^-1, rows of a 3 x 4 matrix
-  uint32_t marked;  // vertices edited since the capture, or W_cur singular
+  uint32_t marked;  // 0 rigid motion by d; 1 no history (W_cur singular, or vertices edited and not followed); 2 vertex motion
   uint32_t pad[3];
 };
 static_assert(sizeof(TemporalCamera) == 64 && sizeof(TemporalHead) == 160 && sizeof(TemporalInst) == 64, "the table is read as 16-B quads");
@@ -45,6 +45,10 @@ struct TemporalState {
   std::vector<float> world;  // 16 floats per instance, column-major object -> world, as captured
   // edited since the capture (hala_rt_update_vertices / hala_rt_update_material)
   std::vector<uint8_t> inst_marked, mat_marked;
+  // RENDER_SPEC 16 "Vertex motion" (hala_rt_set_temporal_vertex_motion): tris_by_id of a one-level tree as the last capture found it.
+  // Allocated by the first capture with the feature on; a history captured with it off has none.
+  bool vertex_motion = false, has_snapshot = false;
+  DeviceArray<Tri> snapshot;
   // the outputs of the last resolve: temporal, motion
   DeviceArray<float4> out[2];
   bool resolved = false;
@@ -53,13 +57,15 @@ struct TemporalState {
   // view list, a dropped history.  Every other resolve launches straight away.
   DeviceArray<uint32_t> table;
   bool table_dirty = true;
+  bool table_vertex = false;  // some instance of the table carries mark 2: the resolve launches the vertex-motion instantiation
 
+  void drop_snapshot() { has_snapshot = false; table_dirty = true; snapshot.release(); }
   void drop_history() {
-    has_history = false; table_dirty = true;
+    has_history = false; drop_snapshot();
     std::fill(inst_marked.begin(), inst_marked.end(), 0); std::fill(mat_marked.begin(), mat_marked.end(), 0);
   }
   void release() {
-    enabled = false; has_history = false; resolved = false; table_dirty = true;
+    enabled = false; has_history = false; resolved = false; vertex_motion = false; drop_snapshot();
     for (DeviceArray<float4>* a : {&hc, &hp, &hi, &out[0], &out[1]}) a->release();
     table.release(); world.clear(); inst_marked.clear(); mat_marked.clear();
   }
@@ -74,9 +80,10 @@ bool temporal_motion(const float* w_prev, const float* w_cur, float d[12]);
 
 TemporalCamera temporal_camera(const hala_gpu_camera& c, float tan_half);
 
-// one thread per pixel of the row-major w x h frame; table: TemporalHead, TemporalInst x inst_count, mark words x mat_count
+// one thread per pixel of the row-major w x h frame; table: TemporalHead, TemporalInst x inst_count, mark words x mat_count.
+// tris / snap: tri_count triangles in id order, now and as captured, when an instance of the table carries mark 2; else null
 void launch_temporal_resolve(const float4* accum, const float4* pos, const uint4* ids, const float4* hc, const float4* hp, const uint4* hi,
                              const uint32_t* table, uint32_t w, uint32_t h, uint32_t n, bool has_history, float4* temporal, float4* motion,
-                             hipStream_t s);
+                             const Tri* tris, const Tri* snap, uint32_t tri_count, hipStream_t s);
 
 }  // namespace rt

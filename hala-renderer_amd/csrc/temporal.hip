@@ -8,6 +8,9 @@
 // stores: 240 B requested and 32 B written when all four taps are in the frame.  Neighbouring pixels share their taps, so the unique traffic
 // is the six images read once (96 B per pixel) plus the two written; 16 x 16 workgroups keep the taps of a wave in a few lines.  The
 // cameras are wave-uniform and come in by scalar loads.  No LDS, no atomics (DESIGN.md "Temporal reprojection" has the measured time).
+//
+// "Vertex motion" of the same section is the kernel's second instantiation: a pixel of a deformed primitive is carried by its triangle's
+// two records, now and as captured, instead of its instance's motion (tests/temporal_vertex_ref.py is its twin).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -55,10 +58,36 @@ RT_DI Projected project(const TemporalCamera& cam, float width, float height, fl
   return o;
 }
 
+// RENDER_SPEC 16 "Vertex motion" steps 1-4: the barycentrics of the foot of pw on triangle g as it is now, placed on that triangle now
+// (pc, the point cam_cur projects) and as captured (pp).  false: no history.
+RT_DI bool vertex_points(const float4* __restrict__ tris, const float4* __restrict__ snap, uint32_t tri_count, uint32_t g, f3 pw, f3* pp, f3* pc) {
+  if (g >= tri_count) return false;
+  const float4 t0 = tris[3u * (size_t)g], t1 = tris[3u * (size_t)g + 1u], t2 = tris[3u * (size_t)g + 2u];
+  const f3 v0 = f3{t0.x, t0.y, t0.z}, e1 = f3{t1.x, t1.y, t1.z}, e2 = f3{t2.x, t2.y, t2.z};
+  const f3 q = pw - v0;
+  const float d11 = dot3(e1, e1), d12 = dot3(e1, e2), d22 = dot3(e2, e2);
+  const float q1 = dot3(q, e1), q2 = dot3(q, e2);
+  const float det = d11 * d22 - d12 * d12;
+  if (!(det > 0.0f)) return false;  // a degenerate triangle (NaN fails)
+  const float u = (d22 * q1 - d12 * q2) / det, v = (d11 * q2 - d12 * q1) / det;
+  const float w0 = (1.0f - u) - v;
+  if (!(u >= -1.0f && v >= -1.0f && w0 >= -1.0f)) return false;  // beyond the triangle and its mirror images across its edges (NaN fails)
+  const float4 s0 = snap[3u * (size_t)g], s1 = snap[3u * (size_t)g + 1u], s2 = snap[3u * (size_t)g + 2u];
+  *pc = f3{__fmaf_rn(v, e2.x, __fmaf_rn(u, e1.x, v0.x)), __fmaf_rn(v, e2.y, __fmaf_rn(u, e1.y, v0.y)), __fmaf_rn(v, e2.z, __fmaf_rn(u, e1.z, v0.z))};
+  *pp = f3{__fmaf_rn(v, s2.x, __fmaf_rn(u, s1.x, s0.x)), __fmaf_rn(v, s2.y, __fmaf_rn(u, s1.y, s0.y)), __fmaf_rn(v, s2.z, __fmaf_rn(u, s1.z, s0.z))};
+  return isfinite(pp->x) && isfinite(pp->y) && isfinite(pp->z);
+}
+
+// VERTEX: some instance of the table carries mark 2 (RENDER_SPEC 16 "Vertex motion").  A pixel of such an instance takes the barycentrics
+// of its mean hit point on triangle I.w as it is now (tris) and places them on the same triangle of the capture (snap): six more 16-B
+// loads, two 48-B records that neighbouring pixels share or find next to theirs.  The false instantiation is the kernel as it was before
+// vertex motion existed and is the one launched whenever no instance carries mark 2; it never reads tris, snap or tri_count.
+template <bool VERTEX>
 __global__ void __launch_bounds__(256) k_temporal_resolve(const float4* __restrict__ accum, const float4* __restrict__ pos, const uint4* __restrict__ ids,
                                                           const float4* __restrict__ hc, const float4* __restrict__ hp, const uint4* __restrict__ hi,
                                                           const uint32_t* __restrict__ table, uint32_t width, uint32_t height, float n,
-                                                          uint32_t has_history, float4* __restrict__ temporal, float4* __restrict__ motion) {
+                                                          uint32_t has_history, float4* __restrict__ temporal, float4* __restrict__ motion,
+                                                          const float4* __restrict__ tris, const float4* __restrict__ snap, uint32_t tri_count) {
   const uint32_t x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
   if (x >= width || y >= height) return;
   const uint32_t p = y * width + x;
@@ -73,16 +102,30 @@ __global__ void __launch_bounds__(256) k_temporal_resolve(const float4* __restri
   if (history) {
     const float4* rec = reinterpret_cast<const float4*>(insts + id.y);
     const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
-    const uint32_t marked = __float_as_uint(rec[3].x) | mat_mark[id.z];
+    const uint32_t inst_mark = __float_as_uint(rec[3].x);
+    const bool by_vertex = VERTEX && inst_mark == 2u;
+    const uint32_t marked = (by_vertex ? 0u : inst_mark) | mat_mark[id.z];  // a material mark wins over vertex motion
     history = marked == 0u;
     if (history) {
       const f3 pw = f3{pm.x / pm.w, pm.y / pm.w, pm.z / pm.w};
-      const f3 pp = f3{__fmaf_rn(r0.z, pw.z, __fmaf_rn(r0.y, pw.y, __fmaf_rn(r0.x, pw.x, r0.w))),
-                       __fmaf_rn(r1.z, pw.z, __fmaf_rn(r1.y, pw.y, __fmaf_rn(r1.x, pw.x, r1.w))),
-                       __fmaf_rn(r2.z, pw.z, __fmaf_rn(r2.y, pw.y, __fmaf_rn(r2.x, pw.x, r2.w)))};
+      f3 pp = pw, pc = pw;  // the point under the capture, and the point cam_cur projects
+      if (by_vertex) {
+        history = vertex_points(tris, snap, tri_count, id.w, pw, &pp, &pc);
+      } else {
+        pp = f3{__fmaf_rn(r0.z, pw.z, __fmaf_rn(r0.y, pw.y, __fmaf_rn(r0.x, pw.x, r0.w))),
+                __fmaf_rn(r1.z, pw.z, __fmaf_rn(r1.y, pw.y, __fmaf_rn(r1.x, pw.x, r1.w))),
+                __fmaf_rn(r2.z, pw.z, __fmaf_rn(r2.y, pw.y, __fmaf_rn(r2.x, pw.x, r2.w)))};
+      }
       const Projected a = project(hd.prev, hd.width, hd.height, hd.aspect, pp);
-      const Projected b = project(hd.cur, hd.width, hd.height, hd.aspect, pw);
-      if (a.ok && b.ok) {
+      const Projected b = project(hd.cur, hd.width, hd.height, hd.aspect, pc);
+      bool carry = history && a.ok && b.ok;
+      if (by_vertex && carry) {  // step 6: a mean hit point off the plane of its triangle averages several surfaces
+        const f3 r = pw - pc;
+        const float zc = hd.cur.type == 0u ? b.z : (2.0f * hd.cur.ymag) * sqrtf(dot3(ld3(hd.cur.up), ld3(hd.cur.up)));
+        const float rl = hd.tol * zc;
+        carry = (r.x * r.x + r.y * r.y) + r.z * r.z <= rl * rl;
+      }
+      if (carry) {
         const float mx = a.u - b.u, my = a.v - b.v;
         const float fx = (float)x + mx, fy = (float)y + my;
         m_out = make_float4(mx, my, a.z, 1.0f);
@@ -172,9 +215,12 @@ TemporalCamera temporal_camera(const hala_gpu_camera& c, float tan_half) {
 
 void launch_temporal_resolve(const float4* accum, const float4* pos, const uint4* ids, const float4* hc, const float4* hp, const uint4* hi,
                              const uint32_t* table, uint32_t w, uint32_t h, uint32_t n, bool has_history, float4* temporal, float4* motion,
-                             hipStream_t s) {
+                             const Tri* tris, const Tri* snap, uint32_t tri_count, hipStream_t s) {
   const dim3 grid((w + kTile - 1) / kTile, (h + kTile - 1) / kTile), block(kTile, kTile);
-  hipLaunchKernelGGL(k_temporal_resolve, grid, block, 0, s, accum, pos, ids, hc, hp, hi, table, w, h, (float)n, has_history ? 1u : 0u, temporal, motion);
+  const bool vertex = has_history && tris && snap && tri_count;
+  hipLaunchKernelGGL(vertex ? k_temporal_resolve<true> : k_temporal_resolve<false>, grid, block, 0, s, accum, pos, ids, hc, hp, hi, table, w, h,
+                     (float)n, has_history ? 1u : 0u, temporal, motion, reinterpret_cast<const float4*>(tris), reinterpret_cast<const float4*>(snap),
+                     vertex ? tri_count : 0u);
 }
 
 }  // namespace rt

@@ -364,6 +364,11 @@ class HalaRenderer:
         p = temporal_default_params(max_history=max_history, tol=tol, min_weight=min_weight)
         self._check(self._lib.hala_rt_set_temporal(self._h, C.byref(p)))
 
+    def set_temporal_vertex_motion(self, enable=True):
+        """let the history follow vertex edits (update_vertices, posed deformers) on a one-level tree: every capture from now on also
+        keeps the triangles as they stand (RENDER_SPEC 16 "Vertex motion").  Refused while set_temporal() is off"""
+        self._check(self._lib.hala_rt_set_temporal_vertex_motion(self._h, C.c_int(1 if enable else 0)))
+
     def temporal_capture(self):
         """keep the frame as it stands as the history; call it before update_node_transform / update_vertices / update_material"""
         self._check(self._lib.hala_rt_temporal_capture(self._h))

@@ -771,7 +771,7 @@ int hala_rt_update_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
  * has none.  While a primitive has a deformer, hala_rt_update_vertices on it is refused ("clear it first").
  * The refit contract: hala_rt_refit poses every deformer whose parameters changed (one kernel launch each on the renderer's stream)
  * and then refits as it does after hala_rt_update_vertices; every instance of a posed primitive starts without temporal history
- * (hala_rt_set_temporal).  Finite parameters can still overflow: when a posed position is not finite, hala_rt_refit fails with
+ * (hala_rt_set_temporal) unless hala_rt_set_temporal_vertex_motion lets the history follow its triangles.  Finite parameters can still overflow: when a posed position is not finite, hala_rt_refit fails with
  * "Vertex position is not finite.", the vertices and the tree stay exactly as they were, the offending parameters fall back to the last
  * applied ones, and every other pending edit stays pending for the next refit. */
 int hala_rt_clear_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index);
@@ -868,6 +868,14 @@ void hala_temporal_default_params(hala_temporal_params* out);
  * hala_rt_set_views with several views, hala_rt_set_adaptive_sampling with parameters and hala_rt_set_tile_shard with world > 1 are
  * refused in turn. */
 int hala_rt_set_temporal(hala_rt_renderer* r, const hala_temporal_params* p);
+/* RENDER_SPEC 16 "Vertex motion": enable != 0 lets the history follow vertex edits (hala_rt_update_vertices, posed deformers) on a
+ * one-level tree.  From then on every capture also keeps the triangles in id order as they stand (one device-to-device copy of 48 B per
+ * triangle on the renderer's stream, allocated by the first such capture), and a resolve carries a pixel of an edited primitive by the
+ * barycentrics of its mean hit point on its triangle, placed on the same triangle of the capture.  On a two-level tree, with a history
+ * captured before the call, or with enable = 0 (which frees the kept triangles) such a primitive starts without history as it always
+ * did.  Off by default and turned off by hala_rt_set_temporal(r, NULL).  Does not restart the accumulation.  Refused, with the renderer
+ * left as it was, while temporal reprojection is off. */
+int hala_rt_set_temporal_vertex_motion(hala_rt_renderer* r, int enable);
 /* RENDER_SPEC 16 "Capture": call it before editing the scene.  With samples folded since the last restart it resolves, then keeps the
  * resolved image, images 4 and 5, view 0's packed camera and every instance's world transform as the history (device-to-device copies on
  * the renderer's stream) and clears the edit marks; with none (two edits without a frame between) it succeeds and keeps the history it

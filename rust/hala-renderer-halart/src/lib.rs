@@ -67,6 +67,9 @@ pub mod sys {
   /// hala_rt_build_options (include/halart.h): every field 0 = the default
   #[repr(C)] #[derive(Default, Clone, Copy)]
   pub struct hala_rt_build_options { pub builder: u32, pub ploc_tail: u32, pub ploc_look_every: u32, pub collapse_look_every: u32, pub instancing: u32, pub texture_bundles: u32, pub reserved: [u32; 2] }
+  /// hala_temporal_params (include/halart.h, docs/RENDER_SPEC.md 16; 32 B): fill it with hala_temporal_default_params
+  #[repr(C)] #[derive(Default, Clone, Copy)]
+  pub struct hala_temporal_params { pub max_history: f32, pub tol: f32, pub min_weight: f32, pub reserved: [u32; 5] }
   #[repr(C)] pub struct hala_scene { _private: [u8; 0] }
   #[repr(C)] pub struct hala_rtprog { _private: [u8; 0] }
   extern "C" {
@@ -130,6 +133,12 @@ pub mod sys {
                                         d_receive: *mut *mut c_void, receive_bytes: *mut usize, hip_stream: *mut *mut c_void) -> c_int;
     // first-hit AOVs (docs/RENDER_SPEC.md 13): mask bit 0 = image 4 position, bit 1 = image 5 ids
     pub fn hala_rt_set_aovs(r: *mut hala_rt_renderer, mask: u32) -> c_int;
+    pub fn hala_temporal_default_params(out: *mut hala_temporal_params);
+    pub fn hala_rt_set_temporal(r: *mut hala_rt_renderer, p: *const hala_temporal_params) -> c_int;
+    pub fn hala_rt_set_temporal_vertex_motion(r: *mut hala_rt_renderer, enable: c_int) -> c_int;
+    pub fn hala_rt_temporal_capture(r: *mut hala_rt_renderer) -> c_int;
+    pub fn hala_rt_temporal_resolve(r: *mut hala_rt_renderer, gpu_ms: *mut f32) -> c_int;
+    pub fn hala_rt_read_temporal(r: *mut hala_rt_renderer, which: c_int, dst_rgba32f: *mut f32) -> c_int;
     // light groups (docs/RENDER_SPEC.md 14): g = NULL turns them off; relight which 0 = linear, 1 = tonemapped
     pub fn hala_rt_set_light_groups(r: *mut hala_rt_renderer, g: *const hala_light_groups) -> c_int;
     pub fn hala_rt_read_light_group(r: *mut hala_rt_renderer, view: u32, group: u32, dst_rgba32f: *mut f32) -> c_int;
@@ -274,6 +283,23 @@ impl HalaRenderer {
     check(unsafe { sys::hala_rt_set_build_options(self.h, &o) })
   }
   pub fn set_tile_shard(&mut self, rank: u32, world: u32, tile_size: u32) -> Result<(), HalaRendererError> { check(unsafe { sys::hala_rt_set_tile_shard(self.h, rank, world, tile_size) }) }
+
+  // temporal reprojection across scene edits (docs/RENDER_SPEC.md 16); needs AOV bits 0 and 1 (sys::hala_rt_set_aovs(h, 3))
+  /// the library's default parameters when `enable`, else the feature off and its buffers freed
+  pub fn set_temporal(&mut self, enable: bool) -> Result<(), HalaRendererError> {
+    if !enable { return check(unsafe { sys::hala_rt_set_temporal(self.h, std::ptr::null()) }); }
+    let mut p = sys::hala_temporal_params::default();
+    unsafe { sys::hala_temporal_default_params(&mut p) };
+    check(unsafe { sys::hala_rt_set_temporal(self.h, &p) })
+  }
+  /// RENDER_SPEC 16 "Vertex motion": the history follows vertex edits and posed deformers on a one-level tree
+  pub fn set_temporal_vertex_motion(&mut self, enable: bool) -> Result<(), HalaRendererError> {
+    check(unsafe { sys::hala_rt_set_temporal_vertex_motion(self.h, enable as c_int) })
+  }
+  /// before an edit: keep the frame as the history
+  pub fn temporal_capture(&mut self) -> Result<(), HalaRendererError> { check(unsafe { sys::hala_rt_temporal_capture(self.h) }) }
+  /// after the edit, refit and a few updates: blend the reprojected history with the new samples (read with sys::hala_rt_read_temporal)
+  pub fn temporal_resolve(&mut self) -> Result<(), HalaRendererError> { check(unsafe { sys::hala_rt_temporal_resolve(self.h, std::ptr::null_mut()) }) }
 }
 impl Drop for HalaRenderer { fn drop(&mut self) { unsafe { sys::hala_rt_destroy(self.h) } } }
 
