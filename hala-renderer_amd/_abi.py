@@ -213,6 +213,10 @@ class TemporalParams(C.Structure):  # hala_temporal_params, 32 B (docs/RENDER_SP
     _fields_ = [("max_history", C.c_float), ("tol", C.c_float), ("min_weight", C.c_float), ("reserved", C.c_uint32 * 5)]
 
 
+class TemporalClampParams(C.Structure):  # hala_temporal_clamp_params, 16 B (docs/RENDER_SPEC.md 16 "History clamp")
+    _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 class DeformerDesc(C.Structure):  # hala_deformer_desc, 64 B (docs/RENDER_SPEC.md 17)
     _fields_ = [("mesh_index", C.c_uint32), ("primitive_index", C.c_uint32), ("target_count", C.c_uint32),
                 ("target_position_deltas", C.POINTER(C.c_float)), ("target_normal_deltas", C.POINTER(C.c_float)),
@@ -253,6 +257,8 @@ PROTOTYPES = {
     "hala_temporal_default_params": ([C.POINTER(TemporalParams)], None),
     "hala_rt_set_temporal": ([C.c_void_p, C.POINTER(TemporalParams)], C.c_int),
     "hala_rt_set_temporal_vertex_motion": ([C.c_void_p, C.c_int], C.c_int),
+    "hala_temporal_clamp_default_params": ([C.POINTER(TemporalClampParams)], None),
+    "hala_rt_set_temporal_clamp": ([C.c_void_p, C.POINTER(TemporalClampParams)], C.c_int),
     "hala_rt_temporal_capture": ([C.c_void_p], C.c_int),
     "hala_rt_temporal_resolve": ([C.c_void_p, C.POINTER(C.c_float)], C.c_int),
     "hala_rt_read_temporal": ([C.c_void_p, C.c_int, C.POINTER(C.c_float)], C.c_int),
@@ -304,6 +310,7 @@ EXPORTS = [
     "hala_rt_save_cryptomatte", "hala_cryptomatte_hash", "hala_write_exr",
     "hala_temporal_default_params", "hala_rt_set_temporal", "hala_rt_temporal_capture", "hala_rt_temporal_resolve", "hala_rt_read_temporal",
     "hala_rt_get_temporal_buffer", "hala_rt_denoise_temporal", "hala_rt_set_temporal_vertex_motion",
+    "hala_temporal_clamp_default_params", "hala_rt_set_temporal_clamp",
     "hala_rt_texture_bundle_info",
     "hala_rt_set_deformer", "hala_rt_update_deformer", "hala_rt_clear_deformer", "hala_rt_read_vertices",
 ]

@@ -132,7 +132,7 @@ static int temporal_enqueue_resolve(hala_rt_renderer* r, hipEvent_t before = nul
   launch_temporal_resolve(r->img_local[0].ptr, r->img_local[4].ptr, reinterpret_cast<const uint4*>(r->img_local[5].ptr), t.hc.ptr, t.hp.ptr,
                           reinterpret_cast<const uint4*>(t.hi.ptr), t.table.ptr, r->width, r->height, r->rendered_frames(), hist, t.out[0].ptr,
                           t.out[1].ptr, t.table_vertex ? r->d_tris_by_id.ptr : nullptr, t.table_vertex ? t.snapshot.ptr : nullptr,
-                          t.table_vertex ? r->bvh.tri_count : 0u, r->stream);
+                          t.table_vertex ? r->bvh.tri_count : 0u, t.clamp ? &t.cp : nullptr, r->stream);
   RT_HIP(hipGetLastError());
   t.resolved = true;
   return HALA_OK;
@@ -175,6 +175,18 @@ int hala_rt_set_temporal_vertex_motion(hala_rt_renderer* r, int enable) {
   }
   t.vertex_motion = enable != 0;
   t.table_dirty = true;
+  return HALA_OK;
+}
+int hala_rt_set_temporal_clamp(hala_rt_renderer* r, const hala_temporal_clamp_params* p) {
+  if (p) {
+    const std::string bad = temporal_check_clamp_params(p);  // first: the CPU tier pins it without a renderer
+    if (!bad.empty()) RT_FAIL(bad);
+  }
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (!r->temporal.enabled) RT_FAIL("hala_rt_set_temporal_clamp: temporal reprojection is off (hala_rt_set_temporal).");
+  // two launch arguments of the next resolve: nothing on the device changes, and the resolves enqueued so far keep theirs
+  r->temporal.clamp = p != nullptr;
+  if (p) r->temporal.cp = *p;
   return HALA_OK;
 }
 int hala_rt_temporal_capture(hala_rt_renderer* r) {

@@ -49,6 +49,9 @@ struct TemporalState {
   // Allocated by the first capture with the feature on; a history captured with it off has none.
   bool vertex_motion = false, has_snapshot = false;
   DeviceArray<Tri> snapshot;
+  // RENDER_SPEC 16 "History clamp" (hala_rt_set_temporal_clamp): two launch arguments of the resolve, no state on the device
+  bool clamp = false;
+  hala_temporal_clamp_params cp{};
   // the outputs of the last resolve: temporal, motion
   DeviceArray<float4> out[2];
   bool resolved = false;
@@ -65,7 +68,7 @@ struct TemporalState {
     std::fill(inst_marked.begin(), inst_marked.end(), 0); std::fill(mat_marked.begin(), mat_marked.end(), 0);
   }
   void release() {
-    enabled = false; has_history = false; resolved = false; vertex_motion = false; drop_snapshot();
+    enabled = false; has_history = false; resolved = false; vertex_motion = false; clamp = false; drop_snapshot();
     for (DeviceArray<float4>* a : {&hc, &hp, &hi, &out[0], &out[1]}) a->release();
     table.release(); world.clear(); inst_marked.clear(); mat_marked.clear();
   }
@@ -73,6 +76,7 @@ struct TemporalState {
 
 // "" or the reason the parameters are refused (no device call)
 std::string temporal_check_params(const hala_temporal_params* p);
+std::string temporal_check_clamp_params(const hala_temporal_clamp_params* p);
 
 // D = W_prev . W_cur^-1 in double, rounded once (RENDER_SPEC 16 "Motion of an instance"); w_prev / w_cur: 16 floats, column-major.
 // Returns false when W_cur is singular (d is then the identity).
@@ -81,9 +85,10 @@ bool temporal_motion(const float* w_prev, const float* w_cur, float d[12]);
 TemporalCamera temporal_camera(const hala_gpu_camera& c, float tan_half);
 
 // one thread per pixel of the row-major w x h frame; table: TemporalHead, TemporalInst x inst_count, mark words x mat_count.
-// tris / snap: tri_count triangles in id order, now and as captured, when an instance of the table carries mark 2; else null
+// tris / snap: tri_count triangles in id order, now and as captured, when an instance of the table carries mark 2; else null.
+// clamp: the checked parameters of RENDER_SPEC 16 "History clamp", or null (off)
 void launch_temporal_resolve(const float4* accum, const float4* pos, const uint4* ids, const float4* hc, const float4* hp, const uint4* hi,
                              const uint32_t* table, uint32_t w, uint32_t h, uint32_t n, bool has_history, float4* temporal, float4* motion,
-                             const Tri* tris, const Tri* snap, uint32_t tri_count, hipStream_t s);
+                             const Tri* tris, const Tri* snap, uint32_t tri_count, const hala_temporal_clamp_params* clamp, hipStream_t s);
 
 }  // namespace rt

@@ -11,6 +11,11 @@
 //
 // "Vertex motion" of the same section is the kernel's second instantiation: a pixel of a deformed primitive is carried by its triangle's
 // two records, now and as captured, instead of its instance's motion (tests/temporal_vertex_ref.py is its twin).
+//
+// "History clamp" of the same section is two more instantiations: the workgroup stages the rgb of its 16 x 16 pixels of the current
+// accumulation and a halo of `radius` pixels in LDS (three planes, no new unique traffic: the kernel reads that image anyway), and a pixel
+// that found its history clamps it to mean +- gamma standard errors of its (2 radius + 1)^2 neighbourhood before the blend
+// (tests/temporal_clamp_ref.py is the twin of all four instantiations).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -26,6 +31,13 @@ namespace {
 
 constexpr uint32_t kTile = 16;  // 16 x 16 pixels per workgroup
 constexpr uint32_t kAbsentId = 0xFFFFFFFFu;
+
+// RENDER_SPEC 16 "History clamp": the staged tile is (16 + 2 radius)^2 <= 22 x 22 floats per plane.  Rows are kClampPitch = 48 floats apart:
+// a ds_read_b32 is served in two halves of 32 lanes, a half is two tile rows of 16 pixels, and the banks are (address / 4) mod 32, so the
+// two rows of a half must lie 16 mod 32 banks apart (22 <= pitch: 48) to cover the 32 banks once for whatever tap offset (DESIGN.md 15
+// "History clamp").  3 planes x 22 rows x 48 floats = 12672 B per workgroup, which is above no occupancy limit of the kernel.
+constexpr uint32_t kClampMaxRadius = 3, kClampSide = kTile + 2 * kClampMaxRadius, kClampPitch = 48, kClampPlane = kClampSide * kClampPitch;
+typedef __attribute__((address_space(3))) float lds_float;  // (generic pointers to LDS compile to flat loads)
 
 struct Projected {
   float u, v, z;  // continuous pixel coordinates (pixel centres are integers), view depth
@@ -82,13 +94,35 @@ RT_DI bool vertex_points(const float4* __restrict__ tris, const float4* __restri
 // of its mean hit point on triangle I.w as it is now (tris) and places them on the same triangle of the capture (snap): six more 16-B
 // loads, two 48-B records that neighbouring pixels share or find next to theirs.  The false instantiation is the kernel as it was before
 // vertex motion existed and is the one launched whenever no instance carries mark 2; it never reads tris, snap or tri_count.
-template <bool VERTEX>
+//
+// CLAMP: RENDER_SPEC 16 "History clamp" is on and a history exists.  All 256 threads of the workgroup, those outside the frame included,
+// stage the tile and meet at one barrier before any of them returns; a tap is valid by its coordinates, so the entries of the tile that
+// lie outside the frame are neither written nor read.  The statistics are computed by the lanes that reach the blend, from LDS, two passes
+// over the taps in the order the spec writes.  The two CLAMP = false instantiations are the kernels as they were before the clamp existed.
+template <bool VERTEX, bool CLAMP>
 __global__ void __launch_bounds__(256) k_temporal_resolve(const float4* __restrict__ accum, const float4* __restrict__ pos, const uint4* __restrict__ ids,
                                                           const float4* __restrict__ hc, const float4* __restrict__ hp, const uint4* __restrict__ hi,
                                                           const uint32_t* __restrict__ table, uint32_t width, uint32_t height, float n,
                                                           uint32_t has_history, float4* __restrict__ temporal, float4* __restrict__ motion,
-                                                          const float4* __restrict__ tris, const float4* __restrict__ snap, uint32_t tri_count) {
+                                                          const float4* __restrict__ tris, const float4* __restrict__ snap, uint32_t tri_count,
+                                                          uint32_t radius, float gamma) {
   const uint32_t x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
+  [[maybe_unused]] lds_float* tile = nullptr;
+  if constexpr (CLAMP) {
+    __shared__ float staged[3 * kClampPlane];
+    tile = (lds_float*)staged;
+    const uint32_t side = kTile + 2u * radius;  // radius <= kClampMaxRadius (the launcher)
+    const int bx = (int)(blockIdx.x * kTile) - (int)radius, by = (int)(blockIdx.y * kTile) - (int)radius;
+    for (uint32_t e = threadIdx.y * kTile + threadIdx.x; e < side * side; e += kTile * kTile) {
+      const uint32_t ey = e / side, ex = e - ey * side;
+      const int qx = bx + (int)ex, qy = by + (int)ey;
+      if (qx < 0 || qx >= (int)width || qy < 0 || qy >= (int)height) continue;
+      const float4 v = accum[(uint32_t)qy * width + (uint32_t)qx];
+      lds_float* at = tile + ey * kClampPitch + ex;
+      at[0] = v.x; at[kClampPlane] = v.y; at[2u * kClampPlane] = v.z;
+    }
+    __syncthreads();
+  }
   if (x >= width || y >= height) return;
   const uint32_t p = y * width + x;
   const float4 c = accum[p];
@@ -154,7 +188,38 @@ __global__ void __launch_bounds__(256) k_temporal_resolve(const float4* __restri
             sw = sw + w;
           }
           if (sw >= hd.min_weight) {  // min_weight > 0: at least one tap
-            const float hr = sr / sw, hg = sg / sw, hb = sb / sw, hl = sh / sw;
+            float hr = sr / sw, hg = sg / sw, hb = sb / sw;
+            const float hl = sh / sw;
+            if constexpr (CLAMP) {
+              const int rad = (int)radius;
+              const lds_float* centre = tile + (threadIdx.y + radius) * kClampPitch + (threadIdx.x + radius);
+              float cnt = 0.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f;
+              for (int dy = -rad; dy <= rad; ++dy) {
+                if ((int)y + dy < 0 || (int)y + dy >= (int)height) continue;
+                for (int dx = -rad; dx <= rad; ++dx) {
+                  if ((int)x + dx < 0 || (int)x + dx >= (int)width) continue;
+                  const lds_float* q = centre + dy * (int)kClampPitch + dx;
+                  cnt = cnt + 1.0f;
+                  ar = ar + q[0]; ag = ag + q[kClampPlane]; ab = ab + q[2u * kClampPlane];
+                }
+              }
+              const float mr = ar / cnt, mg = ag / cnt, mb = ab / cnt;
+              float vr = 0.0f, vg = 0.0f, vb = 0.0f;
+              for (int dy = -rad; dy <= rad; ++dy) {
+                if ((int)y + dy < 0 || (int)y + dy >= (int)height) continue;
+                for (int dx = -rad; dx <= rad; ++dx) {
+                  if ((int)x + dx < 0 || (int)x + dx >= (int)width) continue;
+                  const lds_float* q = centre + dy * (int)kClampPitch + dx;
+                  const float er = q[0] - mr, eg = q[kClampPlane] - mg, eb = q[2u * kClampPlane] - mb;
+                  vr = vr + er * er; vg = vg + eg * eg; vb = vb + eb * eb;
+                }
+              }
+              const float wr = gamma * sqrtf((vr / cnt) / cnt), wg = gamma * sqrtf((vg / cnt) / cnt), wb = gamma * sqrtf((vb / cnt) / cnt);
+              const float lr = mr - wr, ur = mr + wr, lg = mg - wg, ug = mg + wg, lb = mb - wb, ub = mb + wb;
+              hr = hr < lr ? lr : (hr > ur ? ur : hr);  // a NaN history stays NaN; NaN bounds leave it as it is
+              hg = hg < lg ? lg : (hg > ug ? ug : hg);
+              hb = hb < lb ? lb : (hb > ub ? ub : hb);
+            }
             const float h = hl > hd.max_history ? hd.max_history : hl;
             const float tw = h + n;
             t_out = make_float4((hr * h + c.x * n) / tw, (hg * h + c.y * n) / tw, (hb * h + c.z * n) / tw, tw);
@@ -175,6 +240,14 @@ std::string temporal_check_params(const hala_temporal_params* p) {
   if (!(p->tol >= 1e-6f && p->tol <= 1.0f)) return "Invalid temporal tol: expected a finite value in [1e-6, 1].";
   if (!(p->min_weight > 0.0f && p->min_weight <= 1.0f)) return "Invalid temporal min_weight: expected a finite value in (0, 1].";
   for (uint32_t v : p->reserved) if (v) return "The reserved words of the temporal parameters must be zero.";
+  return "";
+}
+
+std::string temporal_check_clamp_params(const hala_temporal_clamp_params* p) {
+  if (!p) return "The temporal clamp parameters are null.";
+  if (!(p->radius >= 1u && p->radius <= kClampMaxRadius)) return "Invalid temporal clamp radius: expected 1, 2 or 3.";
+  if (!(p->gamma > 0.0f && p->gamma <= 1000.0f)) return "Invalid temporal clamp gamma: expected a finite value in (0, 1000].";  // NaN fails
+  for (uint32_t v : p->reserved) if (v) return "The reserved words of the temporal clamp parameters must be zero.";
   return "";
 }
 
@@ -215,12 +288,16 @@ TemporalCamera temporal_camera(const hala_gpu_camera& c, float tan_half) {
 
 void launch_temporal_resolve(const float4* accum, const float4* pos, const uint4* ids, const float4* hc, const float4* hp, const uint4* hi,
                              const uint32_t* table, uint32_t w, uint32_t h, uint32_t n, bool has_history, float4* temporal, float4* motion,
-                             const Tri* tris, const Tri* snap, uint32_t tri_count, hipStream_t s) {
+                             const Tri* tris, const Tri* snap, uint32_t tri_count, const hala_temporal_clamp_params* clamp, hipStream_t s) {
   const dim3 grid((w + kTile - 1) / kTile, (h + kTile - 1) / kTile), block(kTile, kTile);
   const bool vertex = has_history && tris && snap && tri_count;
-  hipLaunchKernelGGL(vertex ? k_temporal_resolve<true> : k_temporal_resolve<false>, grid, block, 0, s, accum, pos, ids, hc, hp, hi, table, w, h,
-                     (float)n, has_history ? 1u : 0u, temporal, motion, reinterpret_cast<const float4*>(tris), reinterpret_cast<const float4*>(snap),
-                     vertex ? tri_count : 0u);
+  // without a history no pixel reaches the blend: the plain kernels, which stage nothing
+  const bool clamped = has_history && clamp && clamp->radius >= 1u && clamp->radius <= kClampMaxRadius;
+  const auto kernel = clamped ? (vertex ? k_temporal_resolve<true, true> : k_temporal_resolve<false, true>)
+                              : (vertex ? k_temporal_resolve<true, false> : k_temporal_resolve<false, false>);
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, accum, pos, ids, hc, hp, hi, table, w, h, (float)n, has_history ? 1u : 0u, temporal, motion,
+                     reinterpret_cast<const float4*>(tris), reinterpret_cast<const float4*>(snap), vertex ? tri_count : 0u,
+                     clamped ? clamp->radius : 0u, clamped ? clamp->gamma : 0.0f);
 }
 
 }  // namespace rt
@@ -228,6 +305,7 @@ void launch_temporal_resolve(const float4* accum, const float4* pos, const uint4
 using namespace rt;
 
 static_assert(sizeof(hala_temporal_params) == 32, "hala_temporal_params is 32 B");
+static_assert(sizeof(hala_temporal_clamp_params) == 16, "hala_temporal_clamp_params is 16 B");
 
 void hala_temporal_default_params(hala_temporal_params* out) {
   if (!out) return;
@@ -235,4 +313,11 @@ void hala_temporal_default_params(hala_temporal_params* out) {
   out->max_history = 32.0f;  // DESIGN.md "Temporal reprojection" has the sweep behind the two
   out->tol = 0.05f;
   out->min_weight = 0.25f;
+}
+
+void hala_temporal_clamp_default_params(hala_temporal_clamp_params* out) {
+  if (!out) return;
+  memset(out, 0, sizeof(*out));
+  out->radius = 1u;  // DESIGN.md "History clamp" has the sweep behind the two
+  out->gamma = 2.0f;
 }

@@ -369,6 +369,16 @@ class HalaRenderer:
         keeps the triangles as they stand (RENDER_SPEC 16 "Vertex motion").  Refused while set_temporal() is off"""
         self._check(self._lib.hala_rt_set_temporal_vertex_motion(self._h, C.c_int(1 if enable else 0)))
 
+    def set_temporal_clamp(self, radius=None, gamma=None, enable=True):
+        """clamp the reprojected history of every resolve and capture to gamma standard errors around the mean of the current
+        accumulation over the (2 radius + 1)^2 neighbourhood (RENDER_SPEC 16 "History clamp"), so that light an edit changed does not
+        lag; None: the library's default; enable=False turns it off.  Refused while set_temporal() is off"""
+        if not enable:
+            self._check(self._lib.hala_rt_set_temporal_clamp(self._h, None))
+            return
+        p = temporal_clamp_default_params(radius=radius, gamma=gamma)
+        self._check(self._lib.hala_rt_set_temporal_clamp(self._h, C.byref(p)))
+
     def temporal_capture(self):
         """keep the frame as it stands as the history; call it before update_node_transform / update_vertices / update_material"""
         self._check(self._lib.hala_rt_temporal_capture(self._h))
@@ -684,6 +694,17 @@ def temporal_default_params(**overrides) -> A.TemporalParams:
     from . import load_library
     p = A.TemporalParams()
     load_library().hala_temporal_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def temporal_clamp_default_params(**overrides) -> A.TemporalClampParams:
+    """hala_temporal_clamp_default_params with the fields given (not None) replaced"""
+    from . import load_library
+    p = A.TemporalClampParams()
+    load_library().hala_temporal_clamp_default_params(C.byref(p))
     for k, v in overrides.items():
         if v is not None:
             setattr(p, k, v)

@@ -876,6 +876,21 @@ int hala_rt_set_temporal(hala_rt_renderer* r, const hala_temporal_params* p);
  * did.  Off by default and turned off by hala_rt_set_temporal(r, NULL).  Does not restart the accumulation.  Refused, with the renderer
  * left as it was, while temporal reprojection is off. */
 int hala_rt_set_temporal_vertex_motion(hala_rt_renderer* r, int enable);
+typedef struct hala_temporal_clamp_params {
+  uint32_t radius;      /* the neighbourhood is (2 radius + 1)^2 pixels of the current accumulation, radius in {1, 2, 3} */
+  float gamma;          /* the history may lie within gamma standard errors of the neighbourhood mean, finite, in (0, 1000] */
+  uint32_t reserved[2]; /* must be zero */
+} hala_temporal_clamp_params; /* 16 B */
+/* the defaults of RENDER_SPEC 16 "History clamp" (DESIGN.md "History clamp" has the sweep behind them) */
+void hala_temporal_clamp_default_params(hala_temporal_clamp_params* out);
+/* RENDER_SPEC 16 "History clamp": p makes every resolve (and so every capture) clamp the reprojected history colour of a pixel, per
+ * channel, to mean +- gamma standard errors of the current accumulation over the pixel's (2 radius + 1)^2 neighbourhood before it is
+ * blended, so that light the edit changed does not lag by max_history samples; NULL turns the clamp off, and every output is then bit
+ * for bit what it is without this call.  History length, sample counts, the motion image and pixels without history are the same
+ * either way.  Off by default and turned off by hala_rt_set_temporal(r, NULL).  Does not restart the accumulation, does not drop the
+ * history and allocates nothing.  Refused, with the renderer left as it was: invalid parameters (checked before the handle is looked
+ * at), temporal reprojection off. */
+int hala_rt_set_temporal_clamp(hala_rt_renderer* r, const hala_temporal_clamp_params* p);
 /* RENDER_SPEC 16 "Capture": call it before editing the scene.  With samples folded since the last restart it resolves, then keeps the
  * resolved image, images 4 and 5, view 0's packed camera and every instance's world transform as the history (device-to-device copies on
  * the renderer's stream) and clears the edit marks; with none (two edits without a frame between) it succeeds and keeps the history it

@@ -70,6 +70,9 @@ pub mod sys {
   /// hala_temporal_params (include/halart.h, docs/RENDER_SPEC.md 16; 32 B): fill it with hala_temporal_default_params
   #[repr(C)] #[derive(Default, Clone, Copy)]
   pub struct hala_temporal_params { pub max_history: f32, pub tol: f32, pub min_weight: f32, pub reserved: [u32; 5] }
+  /// hala_temporal_clamp_params (include/halart.h, docs/RENDER_SPEC.md 16 "History clamp"; 16 B): fill it with hala_temporal_clamp_default_params
+  #[repr(C)] #[derive(Default, Clone, Copy)]
+  pub struct hala_temporal_clamp_params { pub radius: u32, pub gamma: f32, pub reserved: [u32; 2] }
   #[repr(C)] pub struct hala_scene { _private: [u8; 0] }
   #[repr(C)] pub struct hala_rtprog { _private: [u8; 0] }
   extern "C" {
@@ -136,6 +139,8 @@ pub mod sys {
     pub fn hala_temporal_default_params(out: *mut hala_temporal_params);
     pub fn hala_rt_set_temporal(r: *mut hala_rt_renderer, p: *const hala_temporal_params) -> c_int;
     pub fn hala_rt_set_temporal_vertex_motion(r: *mut hala_rt_renderer, enable: c_int) -> c_int;
+    pub fn hala_temporal_clamp_default_params(out: *mut hala_temporal_clamp_params);
+    pub fn hala_rt_set_temporal_clamp(r: *mut hala_rt_renderer, p: *const hala_temporal_clamp_params) -> c_int;
     pub fn hala_rt_temporal_capture(r: *mut hala_rt_renderer) -> c_int;
     pub fn hala_rt_temporal_resolve(r: *mut hala_rt_renderer, gpu_ms: *mut f32) -> c_int;
     pub fn hala_rt_read_temporal(r: *mut hala_rt_renderer, which: c_int, dst_rgba32f: *mut f32) -> c_int;
@@ -295,6 +300,13 @@ impl HalaRenderer {
   /// RENDER_SPEC 16 "Vertex motion": the history follows vertex edits and posed deformers on a one-level tree
   pub fn set_temporal_vertex_motion(&mut self, enable: bool) -> Result<(), HalaRendererError> {
     check(unsafe { sys::hala_rt_set_temporal_vertex_motion(self.h, enable as c_int) })
+  }
+  /// RENDER_SPEC 16 "History clamp": the library's default radius and gamma when `enable`, else the clamp off
+  pub fn set_temporal_clamp(&mut self, enable: bool) -> Result<(), HalaRendererError> {
+    if !enable { return check(unsafe { sys::hala_rt_set_temporal_clamp(self.h, std::ptr::null()) }); }
+    let mut p = sys::hala_temporal_clamp_params::default();
+    unsafe { sys::hala_temporal_clamp_default_params(&mut p) };
+    check(unsafe { sys::hala_rt_set_temporal_clamp(self.h, &p) })
   }
   /// before an edit: keep the frame as the history
   pub fn temporal_capture(&mut self) -> Result<(), HalaRendererError> { check(unsafe { sys::hala_rt_temporal_capture(self.h) }) }
