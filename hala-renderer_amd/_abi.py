@@ -287,7 +287,7 @@ EXPORTS = [
     "hala_rt_set_envmap_file", "hala_rt_set_ground_color", "hala_rt_set_sky_color",
     "hala_rt_set_env_intensity", "hala_rt_set_exposure_value", "hala_rt_commit", "hala_rt_set_build_options", "hala_rt_update", "hala_rt_update_batch",
     "hala_rt_render", "hala_rt_wait_idle", "hala_rt_save_images", "hala_rt_read_image",
-    "hala_rt_get_info", "hala_rt_get_statistics", "hala_rt_set_counting", "hala_rt_set_launch_timing_period", "hala_rt_set_pass_fusion", "hala_rt_reset_accumulation", "hala_rt_get_global_uniform",
+    "hala_rt_get_info", "hala_rt_get_statistics", "hala_rt_set_counting", "hala_rt_set_launch_timing_period", "hala_rt_set_pass_fusion", "hala_rt_set_frames_in_flight", "hala_rt_frames_in_flight_info", "hala_rt_reset_accumulation", "hala_rt_get_global_uniform",
     "hala_rt_get_packed_cameras", "hala_rt_get_packed_lights", "hala_rt_get_packed_materials",
     "hala_rt_get_packed_primitives", "hala_rt_get_env_distribution", "hala_rt_get_texture_info",
     "hala_rt_read_texture_level", "hala_rt_sample_texture_host", "hala_rt_set_tile_shard",

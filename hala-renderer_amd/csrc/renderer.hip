@@ -11,7 +11,7 @@ namespace rt {
 int ensure_device(hala_rt_renderer* r, bool join) {
   if (!r) RT_FAIL("The renderer handle is null!");
   RT_HIP(hipSetDevice(r->device));
-  if (join && r->tail.join(r->stream) != HALA_OK) return HALA_ERR;
+  if (join && r->slots.join(r->stream) != HALA_OK) return HALA_ERR;
   return HALA_OK;
 }
 
@@ -31,7 +31,39 @@ static int alloc_wavefront(hala_rt_renderer* r, uint32_t paths) {
     RT_HIP(r->groups.ps.resize(n * r->groups.count));
   } else r->groups.ps.release();
   r->batch_capacity = paths;
+  // the second frame slot follows (callers have joined it and waited); if it cannot, the renderer works with one slot
+  r->slots.second_failed = false;
+  if (r->slots.second.paths && r->slots.second.alloc(n, (r->aov_mask & 1u) != 0u, r->wants_ids(), r->groups.count) != hipSuccess) {
+    (void)hipGetLastError();
+    r->slots.second_failed = true;
+  }
   return HALA_OK;
+}
+
+// The slot of an overlapped update: the other one than the latest update's — slot 1 only once its buffers exist, which are allocated the
+// first time slot 0 is found busy (and again after a feature changed what a path slot holds).  Never fails: without them slot 0, serial.
+static int pick_slot(hala_rt_renderer* r) {
+  FrameSlots& fs = r->slots;
+  if (fs.last == 1) return 0;
+  if (r->staged) return 1;  // slot 1's stream and control block, slot 0's buffers (update_impl)
+  WavefrontSet& w = fs.second;
+  const size_t n = (size_t)r->slot_count * r->batch_capacity;
+  const bool pos = (r->aov_mask & 1u) != 0u, ids = r->wants_ids();
+  if (w.paths == n && w.aov_pos == pos && w.aov_ids == ids && w.groups == r->groups.count) return 1;
+  if (fs.second_failed) return 0;
+  if (w.paths == 0) {  // not yet: only when it would help
+    const bool busy = fs.busy && hipEventQuery(fs.busy) == hipErrorNotReady;
+    (void)hipGetLastError();
+    if (!busy) return 0;
+  } else {  // sized for other features (their setters joined and waited)
+    if (fs.join(r->stream) != HALA_OK || hipStreamSynchronize(r->stream) != hipSuccess) return 0;
+  }
+  if (w.alloc(n, pos, ids, r->groups.count) != hipSuccess) {
+    (void)hipGetLastError();
+    fs.second_failed = true;
+    return 0;
+  }
+  return 1;
 }
 
 int alloc_frame_buffers(hala_rt_renderer* r) {
@@ -44,7 +76,7 @@ int alloc_frame_buffers(hala_rt_renderer* r) {
   if (r->groups.count) { RT_HIP(r->groups.img.resize(n * r->groups.count)); RT_HIP(hipMemsetAsync(r->groups.img.ptr, 0, r->groups.img.bytes(), r->stream)); }
   r->groups.relit_valid = false;
   if (alloc_wavefront(r, 1) != HALA_OK) return HALA_ERR;
-  RT_HIP(r->d_ctl.resize(2));  // updates alternate between the two: a tail still running accounts into its own
+  RT_HIP(r->d_ctl.resize(2));  // one per frame slot
   RT_HIP(hipMemsetAsync(r->d_ctl.ptr, 0, 2 * sizeof(Control), r->stream));
   RT_HIP(r->d_batch_work.resize(1));
   return HALA_OK;
@@ -181,8 +213,8 @@ int hala_rt_create(const char* name, uint32_t width, uint32_t height, int device
   RT_HIP(hipGetDeviceProperties(&prop, device_ordinal));
   r->cu_count = (uint32_t)prop.multiProcessorCount;
   RT_HIP(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-  RT_HIP(hipStreamCreateWithFlags(&r->tail.stream, hipStreamNonBlocking));
-  RT_HIP(hipEventCreateWithFlags(&r->tail.ev_shaded, hipEventDisableTiming));
+  RT_HIP(hipStreamCreateWithFlags(&r->slots.stream, hipStreamNonBlocking));
+  for (hipEvent_t* e : {&r->slots.folded[0], &r->slots.folded[1], &r->slots.lead[0], &r->slots.lead[1], &r->slots.forked}) RT_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
   compute_tiling(r.get());
   // create_storage_images (src/rt_renderer.rs:818-917): final, accum, albedo, normal
   if (alloc_frame_buffers(r.get()) != HALA_OK) return HALA_ERR;
@@ -333,7 +365,7 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   if (first >= r->max_frames) return HALA_OK;
   const uint32_t samples = (uint32_t)std::min<uint64_t>(frames, r->max_frames - first);
   if (samples * V > r->batch_capacity) {
-    if (r->tail.join(r->stream) != HALA_OK) return HALA_ERR;
+    if (r->slots.join(r->stream) != HALA_OK) return HALA_ERR;
     RT_HIP(hipStreamSynchronize(r->stream));
     if (alloc_wavefront(r, samples * V) != HALA_OK) return HALA_ERR;
   }
@@ -342,7 +374,7 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
     std::vector<ViewConst> table(V);
     for (uint32_t v = 0; v < V; ++v) table[v] = r->view_const(r->views[v], (float)r->height);
     if (table.size() != r->views_uploaded.size() || memcmp(table.data(), r->views_uploaded.data(), V * sizeof(ViewConst)) != 0) {
-      if (r->tail.join(r->stream) != HALA_OK) return HALA_ERR;
+      if (r->slots.join(r->stream) != HALA_OK) return HALA_ERR;
       RT_HIP(hipStreamSynchronize(r->stream));  // no update in flight reads the old table
       RT_HIP(r->d_views.upload(table.data(), V, r->stream));
       RT_HIP(hipStreamSynchronize(r->stream));
@@ -365,7 +397,7 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   r->last_uniform = u;
   r->last_uniform.frame_index = (uint32_t)(first + samples - 1);  // what the last frame of the batch would have uploaded
   AdaptiveState& ad = r->adaptive;
-  if (ad.enabled && first == 0 && (r->tail.join(r->stream) != HALA_OK || adaptive_begin(ad, r->stream) != hipSuccess)) RT_FAIL("hala_rt_update: the adaptive sampling state could not be reset.");
+  if (ad.enabled && first == 0 && (r->slots.join(r->stream) != HALA_OK || adaptive_begin(ad, r->stream) != hipSuccess)) RT_FAIL("hala_rt_update: the adaptive sampling state could not be reset.");
   if (ad.enabled && ad.active_blocks == 0) {  // RENDER_SPEC 11: every block has converged; the frames count, nothing is launched
     for (int k = 0; k < kStatRing; ++k) resolve_slot(r, r->ring[(r->ring_pos + k) % kStatRing]);  // done: the last check waited for them
     r->stats.rays_last_update = 0;
@@ -383,22 +415,35 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   te.primary_pixels = primary_pixels;
   const FrameConst fc = r->frame_const(u, samples);
   const SceneView sv = r->view();
-  const Queues q = r->queues();
-  const PathState ps = r->path_state();
-  Control* ctl = r->d_ctl.ptr + r->tail.ctl_pos;
-  r->tail.ctl_pos ^= 1u;
-  const hipStream_t s = r->stream;
   // per-launch HIP events (statistics: traverse_*_ms_total) on every launch_event_period-th update; each record is a barrier
   // packet on the stream, i.e. a few microseconds between two launches
   const bool timed = r->launch_event_period == 1u || (r->launch_event_period > 1u && (r->update_counter % r->launch_event_period) == 0u);
   r->update_counter++;
-  // Untimed updates put their tail on the tail's stream (TailState).  Updates that carry per-launch timing events or
-  // counting kernels keep the serial order on one stream, so that every measured launch has the chip to itself.
-  const bool split_tail = !timed && !r->counting;
-  if (!split_tail && r->tail.join(r->stream) != HALA_OK) return HALA_ERR;
-  // an open tail is the last user of the scratch (external trace_rays calls join it), and it uses none of what this update's
-  // camera-ray launch uses: that launch starts beside it, the depth-0 shade waits for it
-  if (!r->tail.open && r->scratch.acquire(s) != HALA_OK) return HALA_ERR;
+  // Untimed updates alternate between the two frame slots (FrameSlots), each wholly on its slot's stream.  Updates that carry per-launch
+  // timing events or counting kernels join both slots and run alone, so that every measured launch has the chip to itself.
+  FrameSlots& fs = r->slots;
+  const bool overlapped = fs.in_flight == 2u && !timed && !r->counting;
+  if (!overlapped && fs.join(r->stream) != HALA_OK) return HALA_ERR;
+  const int slot = overlapped ? pick_slot(r) : 0;
+  // LDS-staged trees (small scenes): two workgroups of their traversal kernels fill a CU's LDS, so the traversal launches of two updates
+  // cannot share the chip, and a second set of buffers only halves what the caches keep from frame to frame (profiles/frames_in_flight.txt).
+  // Their updates alternate between the streams and control blocks but share slot 0's buffers: the camera-ray launch, which touches
+  // none of what the end of the update before it reads or writes, starts behind that update's last shade, the depth-0 shade behind its end
+  const bool shared = overlapped && r->staged;
+  const Queues q = r->queues(shared ? 0 : slot);
+  const PathState ps = r->path_state(shared ? 0 : slot);
+  hipEvent_t const before_end = fs.last == 0 ? fs.busy : fs.done;  // frame_end of the update before this one
+  Control* ctl = r->d_ctl.ptr + slot;
+  const hipStream_t s = slot == 1 ? fs.stream : r->stream;
+  if (slot == 1 && fs.fork) {  // whatever the renderer's stream did since the last join (edits, restarts, serial updates) comes first
+    RT_HIP(hipEventRecord(fs.forked, r->stream));
+    RT_HIP(hipStreamWaitEvent(s, fs.forked, 0));
+    fs.fork = false;
+  }
+  // the camera-ray launch starts beside the last bounces of the update before it (kLeadBounces), which runs on the other slot
+  if (overlapped && fs.last != slot) RT_HIP(hipStreamWaitEvent(s, fs.lead[fs.last], 0));
+  // slot 0 shares its control block and spill area with external trace_rays calls (which join both slots)
+  if (slot == 0 && r->scratch.acquire(s) != HALA_OK) return HALA_ERR;
   RT_HIP(hipEventRecord(te.frame_begin, s));
   RT_HIP(hipMemsetAsync(ctl, 0, sizeof(Control), s));
   // The shadow passes of bounce d and the closest-hit traversal of bounce d + 1 are independent: untimed updates issue them as ONE
@@ -407,69 +452,68 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
   const bool fuse = (r->fuse_mode == 2u || (r->fuse_mode == 1u && !timed)) && !r->counting && (u.num_of_lights > 0 || u.env_type == 1u);
   if (timed && !te.host_sizes) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&te.host_sizes), sizeof(QueueSizes), hipHostMallocDefault));
   bool traced = false;  // the closest-hit pass of this depth already ran inside the previous depth's fused launch
-  hipStream_t ts = s;  // the stream of the shadow launches, then of the tail
-  LaunchCfg lc = r->lcfg;
+  const LaunchCfg lc = r->launch_cfg(slot);
+  // LDS-staged trees: the next update starts behind the last shade (beside the last shadow launches and the resolve only)
+  const uint32_t lead_bounces = r->staged ? 0u : std::min(kLeadBounces, r->max_depth - 1u);
   for (uint32_t depth = 0; depth < r->max_depth; ++depth) {
     if (timed) { hipEvent_t a = next_event(te); RT_HIP(hipEventRecord(a, s)); }
     // depth 0: the camera rays are generated inside the traversal kernel, there is no ray-generation pass
     if (depth == 0) {
-      launch_trace_primary(r->lcfg, sv, fc, q.hits, &ctl->work_closest, ctl, primary_pixels * samples, r->counting, s);
+      launch_trace_primary(lc, sv, fc, q.hits, &ctl->work_closest, ctl, primary_pixels * samples, r->counting, s);
       if (r->counting) RT_HIP(hipMemcpyAsync(ctl->totals.primary_steps, ctl->totals.steps[0], 16, hipMemcpyDeviceToDevice, s));
-      // the depth-0 shade resets the paths' radiance the previous tail still adds to, and rewrites the connection queues it reads
-      if (r->tail.join(r->stream) != HALA_OK) return HALA_ERR;
+      if (shared && fs.last != slot && before_end) RT_HIP(hipStreamWaitEvent(s, before_end, 0));
     }
-    else if (!traced) launch_trace_batch(r->lcfg, sv, q.rays[depth & 1u], q.hits, &ctl->sizes.n_active[depth], 0, &ctl->work_closest, ctl, false, r->counting, true, s);
+    else if (!traced) launch_trace_batch(lc, sv, q.rays[depth & 1u], q.hits, &ctl->sizes.n_active[depth], 0, &ctl->work_closest, ctl, false, r->counting, true, s);
     traced = false;
     if (timed) { hipEvent_t b = next_event(te); RT_HIP(hipEventRecord(b, s)); }
     launch_shade(fc, sv, q, ps, ctl, depth, s);
+    if (depth + 1u + lead_bounces == r->max_depth) RT_HIP(hipEventRecord(fs.lead[slot], s));
     if (timed) { hipEvent_t c = next_event(te); RT_HIP(hipEventRecord(c, s)); }
     // light connections add to the path's L, environment connections to its Le (RENDER_SPEC §6): the two passes are independent of each
     // other and of the next bounce's closest-hit pass
     const uint32_t kinds = (u.num_of_lights > 0 ? 1u : 0u) | (u.env_type == 1u ? 2u : 0u);
     const bool last = depth + 1u >= r->max_depth;  // no closest-hit pass follows: only worth one launch when there are two shadow passes
-    if (last && split_tail) {  // the tail: from here on everything goes to the tail's stream, its traversal to the tail's spill area
-      RT_HIP(hipEventRecord(r->tail.ev_shaded, s));
-      RT_HIP(hipStreamWaitEvent(r->tail.stream, r->tail.ev_shaded, 0));
-      ts = r->tail.stream;
-      lc.spill = r->lcfg.spill ? r->tail.d_spill.ptr : nullptr;
-    }
-    if (fuse && kinds && (!last || kinds == 3u) && launch_trace_shadow_then_batch(lc, sv, q, ps, ctl, depth, kinds, !last, ts)) {
+    if (fuse && kinds && (!last || kinds == 3u) && launch_trace_shadow_then_batch(lc, sv, q, ps, ctl, depth, kinds, !last, s)) {
       traced = !last;
       if (timed) { te.fused_mask |= 1ull << depth; if (traced) te.traced_mask |= 1ull << (depth + 1u); }
     }
     else
       for (uint32_t kind = 0; kind < 2u; ++kind) {
         if (!((kinds >> kind) & 1u)) continue;
-        launch_trace_shadow(lc, sv, q, ps, ctl, depth, kind, r->counting, ts);
+        launch_trace_shadow(lc, sv, q, ps, ctl, depth, kind, r->counting, s);
         te.shadow_launches += timed ? 1u : 0u;
       }
     if (timed) { hipEvent_t d = next_event(te); RT_HIP(hipEventRecord(d, s)); }
   }
+  // everything that folds into the accumulated images stays in frame order: behind the fold of the update before this one
+  if (fs.last_folded >= 0 && fs.last_folded != slot) RT_HIP(hipStreamWaitEvent(s, fs.folded[fs.last_folded], 0));
   launch_resolve(fc, ps, r->img_local[0].ptr, r->img_local[1].ptr, r->img_local[2].ptr, r->img_local[3].ptr, r->has_image(4) ? r->img_local[4].ptr : nullptr,
-                 r->has_image(5) ? reinterpret_cast<uint4*>(r->img_local[5].ptr) : nullptr, r->groups.img.ptr, r->image_alloc(), ts);
-  if (r->crypto.mask) {  // RENDER_SPEC §15: fold the batch's first hits right behind the resolve, inside the same tail
-    launch_crypto_fold(fc, ps.aov_ids, r->crypto.view(r->slot_count), r->crypto.rec.ptr, ts);
+                 r->has_image(5) ? reinterpret_cast<uint4*>(r->img_local[5].ptr) : nullptr, r->groups.img.ptr, r->image_alloc(), s);
+  if (r->crypto.mask) {  // RENDER_SPEC §15: fold the batch's first hits right behind the resolve
+    launch_crypto_fold(fc, ps.aov_ids, r->crypto.view(r->slot_count), r->crypto.rec.ptr, s);
     r->crypto.ready = true;
   }
-  RT_HIP(hipMemcpyAsync(te.host_totals, &ctl->totals, sizeof(Totals), hipMemcpyDeviceToHost, ts));
-  if (timed) RT_HIP(hipMemcpyAsync(te.host_sizes, &ctl->sizes, sizeof(QueueSizes), hipMemcpyDeviceToHost, ts));
-  // frame_begin -> frame_end spans the whole update, its tail included
-  RT_HIP(hipEventRecord(te.frame_end, ts));
-  r->scratch.event = te.frame_end; r->scratch.stream = ts;
-  r->tail.done = te.frame_end; r->tail.open = ts != s;
+  RT_HIP(hipEventRecord(fs.folded[slot], s));
+  fs.last_folded = slot; fs.last = slot;
+  RT_HIP(hipMemcpyAsync(te.host_totals, &ctl->totals, sizeof(Totals), hipMemcpyDeviceToHost, s));
+  if (timed) RT_HIP(hipMemcpyAsync(te.host_sizes, &ctl->sizes, sizeof(QueueSizes), hipMemcpyDeviceToHost, s));
+  // frame_begin -> frame_end spans the whole update
+  RT_HIP(hipEventRecord(te.frame_end, s));
+  if (slot == 0) { r->scratch.event = te.frame_end; r->scratch.stream = s; fs.busy = te.frame_end; }
+  else { fs.done = te.frame_end; fs.open = true; fs.second_updates++; }
   RT_HIP(hipGetLastError());
   te.pending = true;
   for (bool& v : r->full_valid) v = false;
   // RENDER_SPEC 11: hala_rt_update_batch ends its chunks on these frames, so n is the snapshot or check frame itself
   const uint32_t n = (uint32_t)(first + samples);
-  if (ad.enabled && (n == ad.p.min_samples / 2u || adaptive_is_check(ad.p, n)) && r->tail.join(r->stream) != HALA_OK) return HALA_ERR;  // they read the accumulation
+  if (ad.enabled && (n == ad.p.min_samples / 2u || adaptive_is_check(ad.p, n)) && fs.join(r->stream) != HALA_OK) return HALA_ERR;  // they read the accumulation
   if (ad.enabled && n == ad.p.min_samples / 2u) {
-    RT_HIP(hipMemcpyAsync(ad.snapshot.ptr, r->img_local[0].ptr, ad.snapshot.bytes(), hipMemcpyDeviceToDevice, s));
+    RT_HIP(hipMemcpyAsync(ad.snapshot.ptr, r->img_local[0].ptr, ad.snapshot.bytes(), hipMemcpyDeviceToDevice, r->stream));
     ad.last_snapshot = n;
   }
   if (ad.enabled && adaptive_is_check(ad.p, n)) {  // the one synchronising update: the next ones are sized by the two counts
-    RT_HIP(adaptive_enqueue_check(ad, r->img_local[0].ptr, r->width, r->height, r->blocks_x, r->exposure, n, s));
-    RT_HIP(hipStreamSynchronize(s));
+    RT_HIP(adaptive_enqueue_check(ad, r->img_local[0].ptr, r->width, r->height, r->blocks_x, r->exposure, n, r->stream));
+    RT_HIP(hipStreamSynchronize(r->stream));
     adaptive_finish_check(ad, n);
   }
   return HALA_OK;
@@ -562,6 +606,23 @@ int hala_rt_set_launch_timing_period(hala_rt_renderer* r, uint32_t period) {
   if (!r) RT_FAIL("The renderer handle is null!");
   r->launch_event_period = period;
   r->update_counter = 0;
+  return HALA_OK;
+}
+int hala_rt_set_frames_in_flight(hala_rt_renderer* r, uint32_t n) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins both slots
+  if (n != 1u && n != 2u) RT_FAIL("hala_rt_set_frames_in_flight: n must be 1 or 2.");
+  r->slots.in_flight = n;
+  r->slots.second_failed = false;
+  if (n == 1u) {  // strictly serial: one slot, one stream, one set of buffers
+    RT_HIP(hipStreamSynchronize(r->stream));
+    r->slots.second.release();
+  }
+  return HALA_OK;
+}
+int hala_rt_frames_in_flight_info(hala_rt_renderer* r, unsigned long long* second_slot_updates, uint32_t* second_buffers) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (second_slot_updates) *second_slot_updates = r->slots.second_updates;
+  if (second_buffers) *second_buffers = r->slots.second.paths ? 1u : 0u;
   return HALA_OK;
 }
 int hala_rt_set_pass_fusion(hala_rt_renderer* r, uint32_t mode) {

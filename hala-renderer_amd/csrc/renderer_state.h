@@ -44,6 +44,11 @@ constexpr int kStatRing = 16;
 #define RT_BUNDLE_MIN_MAPS 2
 #endif
 constexpr uint32_t kBundleMinMaps = RT_BUNDLE_MIN_MAPS;
+// Two updates in flight (FrameSlots): the next update starts behind the shade of the bounce this many before the last one of the update
+// before it, so that its camera-ray launch and depth-0 shade (dense work) run beside that update's last launches (short queues: mostly
+// the tails of a few long rays), not beside its dense early bounces.  Measured on configs[3] (profiles/frames_in_flight.txt): 1 is
+// best; 0 (behind the last shade) equals the former tail stream; starting earlier, or with no start dependency at all, is slower.
+constexpr uint32_t kLeadBounces = 1;
 constexpr uint32_t kMaxSampleBatch = 16;  // frames per wavefront pass in hala_rt_update_batch (~250 B of state per path)
 
 // ---- RENDER_SPEC §2.2 on the host (for tan(yfov/2); same polynomials as rt_math.h) ---------------------------
@@ -185,24 +190,72 @@ struct ExchangeState {
   }
 };
 
-// The tail of an untimed update — the last bounce's shadow launch(es), k_resolve and the read-back of the totals — runs on its own stream,
-// beside the next update's k_trace_primary, which needs none of it.  The tail uses the update's own control block
-// (d_ctl holds two, updates alternate) and its own stack spill area.  While open the renderer's stream has not waited for it:
-// every entry point joins it first (ensure_device), except update — after its camera-ray launch — and render.
-struct TailState {
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_shaded = nullptr;  // the last k_shade of an untimed update: where its tail starts
-  hipEvent_t done = nullptr;       // not owned: the frame_end of that update, recorded on the tail's stream
-  bool open = false;
-  uint32_t ctl_pos = 0;            // control block of the next update
-  DeviceArray<uint2> d_spill;
+// Two frame slots: consecutive updates are independent except for the order in which their samples are folded into the
+// accumulated images, so untimed updates alternate between two slots and the start of one runs beside the end of the other (`lead`).  A
+// slot owns what one update in flight needs: a stream (slot 0 the
+// renderer's, slot 1 `stream`), a control block (d_ctl[slot]), a stack spill area, the per-path state and the queues (slot 0 the renderer's
+// members, slot 1 `second`).  An update waits for the previous use of its slot by stream order; between the slots there is one dependency:
+// the resolve (and the Cryptomatte fold) of an update waits for `folded` of the update before it.  While slot 1 is open the renderer's
+// stream has not waited for it: every entry point joins it first (ensure_device), except update and render.
+struct WavefrontSet {  // slot 1's copy of what alloc_wavefront gives slot 0; allocated when an update first finds slot 0 busy
+  DeviceArray<P3> ps_lr, ps_le, ps_alb, ps_nrm, groups_ps;
+  DeviceArray<float4> ps_aov_pos;
+  DeviceArray<uint4> ps_aov_ids;
+  DeviceArray<hala_ray> q_rays[2];
+  DeviceArray<float4> q_state[2];
+  DeviceArray<hala_hit> q_hits;
+  DeviceArray<uint32_t> q_perm;
+  DeviceArray<ShadowEntry> q_shadow[2];
+  size_t paths = 0;  // path slots it holds; 0: not allocated
+  bool aov_pos = false, aov_ids = false;
+  uint32_t groups = 0;
+  void release() {
+    ps_lr.release(); ps_le.release(); ps_alb.release(); ps_nrm.release(); groups_ps.release(); ps_aov_pos.release(); ps_aov_ids.release();
+    for (int k = 0; k < 2; ++k) { q_rays[k].release(); q_state[k].release(); q_shadow[k].release(); }
+    q_hits.release(); q_perm.release();
+    paths = 0;
+  }
+  hipError_t alloc(size_t n, bool pos, bool ids, uint32_t group_count) {
+    hipError_t e = hipSuccess;
+    auto get = [&](auto& a, size_t count) { if (e == hipSuccess) e = a.resize(count); };
+    get(ps_lr, n); get(ps_le, n); get(ps_alb, n); get(ps_nrm, n);
+    for (int k = 0; k < 2; ++k) { get(q_rays[k], n); get(q_state[k], n); get(q_shadow[k], n); }
+    get(q_hits, n); get(q_perm, n);
+    if (pos) get(ps_aov_pos, n); else ps_aov_pos.release();
+    if (ids) get(ps_aov_ids, n); else ps_aov_ids.release();
+    if (group_count) get(groups_ps, n * group_count); else groups_ps.release();
+    if (e != hipSuccess) { release(); return e; }
+    paths = n; aov_pos = pos; aov_ids = ids; groups = group_count;
+    return hipSuccess;
+  }
+};
+struct FrameSlots {
+  uint32_t in_flight = 2;          // hala_rt_set_frames_in_flight: 1 = one slot, one stream
+  hipStream_t stream = nullptr;    // slot 1's
+  hipEvent_t folded[2] = {nullptr, nullptr};  // behind the resolve and the Cryptomatte fold of the slot's latest update
+  hipEvent_t lead[2] = {nullptr, nullptr};    // behind the shade kLeadBounces before the last of the slot's latest update: where the next update starts
+  hipEvent_t forked = nullptr;     // the renderer's stream as the last join left it: where slot 1 starts again
+  // not owned: the frame_end events of the two slots' latest updates, which live in the statistics ring.  A ring entry is recorded
+  // again 16 updates later; by then its slot has run a newer update (updates alternate, and every serial one runs on slot 0, so no
+  // slot sits out 16 updates while the other runs) and the pointer has moved on — except `done` while slot 1 is unused, which is only
+  // waited for while `open`, i.e. before the first join after slot 1's latest update
+  hipEvent_t done = nullptr;       // slot 1's
+  hipEvent_t busy = nullptr;       // slot 0's
+  bool open = false;               // slot 1 holds work the renderer's stream has not waited for
+  bool fork = true;                // the renderer's stream holds work slot 1 has not waited for
+  bool second_failed = false;      // slot 1's buffers could not be had: one slot until the buffers are sized again
+  int last = 1;                    // slot of the latest update (the next overlapped one takes the other)
+  unsigned long long second_updates = 0;  // updates that ran on slot 1 (hala_rt_frames_in_flight_info)
+  int last_folded = -1;            // slot whose `folded` is the latest
+  WavefrontSet second;
+  DeviceArray<uint2> d_spill;      // slot 1's stack spill area
   int join(hipStream_t renderer_stream) {
     if (open) RT_HIP(hipStreamWaitEvent(renderer_stream, done, 0));
-    open = false;
+    open = false; fork = true;
     return HALA_OK;
   }
   void release() {
-    if (ev_shaded) (void)hipEventDestroy(ev_shaded);
+    for (hipEvent_t e : {folded[0], folded[1], lead[0], lead[1], forked}) if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -357,12 +410,12 @@ struct hala_rt_renderer {
   hala_rt_statistics stats{};
   ScratchOrder scratch;
   ExchangeState exchange;
-  TailState tail;
+  FrameSlots slots;
 
   ~hala_rt_renderer() {
     if (device >= 0) (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
-    if (tail.stream) (void)hipStreamSynchronize(tail.stream);
+    if (slots.stream) (void)hipStreamSynchronize(slots.stream);
     for (auto& t : ring) {
       for (auto e : t.ev) (void)hipEventDestroy(e);
       if (t.frame_begin) (void)hipEventDestroy(t.frame_begin);
@@ -377,7 +430,7 @@ struct hala_rt_renderer {
     for (auto& i : img_full) i.release();
     if (bvh.topology) bvh_free_topology(bvh.topology);
     blas.clear();
-    tail.release();
+    slots.release();
     if (stream) (void)hipStreamDestroy(stream);
   }
 
@@ -396,13 +449,36 @@ struct hala_rt_renderer {
     sv.staged = staged ? 1u : 0u;
     return sv;
   }
-  Queues queues() const {
+  // the traversal launches of an update on frame slot `slot`: with the slot's spill area
+  LaunchCfg launch_cfg(int slot) const {
+    LaunchCfg lc = lcfg;
+    if (slot == 1 && lcfg.spill) lc.spill = slots.d_spill.ptr;
+    return lc;
+  }
+  Queues queues(int slot = 0) const {
     Queues q{};
+    if (slot == 1) {
+      const WavefrontSet& w = slots.second;
+      q.rays[0] = w.q_rays[0].ptr; q.rays[1] = w.q_rays[1].ptr; q.state[0] = w.q_state[0].ptr; q.state[1] = w.q_state[1].ptr;
+      q.hits = w.q_hits.ptr; q.perm = w.q_perm.ptr; q.shadow[0] = w.q_shadow[0].ptr; q.shadow[1] = w.q_shadow[1].ptr;
+      return q;
+    }
     q.rays[0] = q_rays[0].ptr; q.rays[1] = q_rays[1].ptr; q.state[0] = q_state[0].ptr; q.state[1] = q_state[1].ptr;
     q.hits = q_hits.ptr; q.perm = q_perm.ptr; q.shadow[0] = q_shadow[0].ptr; q.shadow[1] = q_shadow[1].ptr;
     return q;
   }
-  PathState path_state() const {
+  PathState path_state(int slot = 0) const {
+    PathState ps = path_state0();
+    if (slot == 1) {
+      const WavefrontSet& w = slots.second;
+      ps.radiance = w.ps_lr.ptr; ps.radiance_env = w.ps_le.ptr; ps.albedo = w.ps_alb.ptr; ps.normal = w.ps_nrm.ptr;
+      if (ps.aov_pos) ps.aov_pos = w.ps_aov_pos.ptr;
+      if (ps.aov_ids) ps.aov_ids = w.ps_aov_ids.ptr;
+      if (ps.groups) ps.groups = w.groups_ps.ptr;
+    }
+    return ps;
+  }
+  PathState path_state0() const {
     return PathState{ps_lr.ptr, ps_le.ptr, ps_alb.ptr, ps_nrm.ptr, (aov_mask & 1u) ? ps_aov_pos.ptr : nullptr, wants_ids() ? ps_aov_ids.ptr : nullptr,
                      d_inst_node.ptr, d_light_node.ptr,
                      groups.count ? groups.ps.ptr : nullptr, groups.count ? groups.d_light_group.ptr : nullptr, groups.count ? groups.d_material_group.ptr : nullptr,
@@ -470,7 +546,7 @@ struct hala_rt_renderer {
 namespace rt {
 
 // ---- what several units need of each other ----------------------------------------------------------------------------------------
-// renderer.hip.  join = false: update and render only, which leave the tail of the last update running (TailState)
+// renderer.hip.  join = false: update and render only, which leave slot 1 running (FrameSlots)
 int ensure_device(hala_rt_renderer* r, bool join = true);
 int alloc_frame_buffers(hala_rt_renderer* r);
 std::string file_stem(const char* path);

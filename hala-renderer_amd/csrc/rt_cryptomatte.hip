@@ -48,7 +48,7 @@ int crypto_prepare(hala_rt_renderer* r) {
     RT_FAIL("hala_rt_update: the first-hit records Cryptomatte folds are not allocated (call hala_rt_set_cryptomatte again).");
   const size_t quads = r->crypto.quads(r->view_count(), r->slot_count);
   if (r->crypto.tables && r->crypto.rec.count == quads) return HALA_OK;
-  if (r->tail.join(r->stream) != HALA_OK) return HALA_ERR;
+  if (r->slots.join(r->stream) != HALA_OK) return HALA_ERR;
   RT_HIP(hipStreamSynchronize(r->stream));
   if (!r->crypto.tables) {
     const HostScene& hs = r->hs;
@@ -92,7 +92,7 @@ int hala_rt_set_cryptomatte(hala_rt_renderer* r, const hala_cryptomatte_desc* d)
   if (d && r->world > 1) RT_FAIL("hala_rt_set_cryptomatte: Cryptomatte is not available on a sharded renderer (world > 1).");
   std::vector<std::string> names(d ? d->material_name_count : 0u);
   for (size_t m = 0; m < names.size(); ++m) names[m] = d->material_names[m] ? d->material_names[m] : "";
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins an open tail
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins the second frame slot
   RT_HIP(hipStreamSynchronize(r->stream));
   r->crypto_off();
   if (d) {

@@ -26,7 +26,7 @@ int hala_rt_set_views(hala_rt_renderer* r, const uint32_t* camera_indices, uint3
   if (count > 1u && r->world > 1u) RT_FAIL("hala_rt_set_views: several views are not available on a sharded renderer (world > 1).");
   if (count > 1u && r->adaptive.enabled) RT_FAIL("hala_rt_set_views: several views are not available with adaptive sampling on.");
   if (count > 1u && r->temporal.enabled) RT_FAIL("hala_rt_set_views: several views are not available with temporal reprojection on.");
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins an open tail
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins the second frame slot
   RT_HIP(hipStreamSynchronize(r->stream));
   const size_t old_n = r->image_alloc();
   std::vector<uint32_t> old_views = r->views;
@@ -65,7 +65,7 @@ int hala_rt_set_views(hala_rt_renderer* r, const uint32_t* camera_indices, uint3
 int hala_rt_set_aovs(hala_rt_renderer* r, uint32_t mask) {
   if (!r) RT_FAIL("The renderer handle is null!");
   if (mask > 3u) RT_FAIL("hala_rt_set_aovs: unknown AOV bits (bit 0: position, bit 1: ids).");
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins an open tail
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins the second frame slot
   if (r->exchange.pending && hala_rt_tile_allgather_finish(r) != HALA_OK) return HALA_ERR;  // an exchange in flight may stage images 4 and 5
   RT_HIP(hipStreamSynchronize(r->stream));
   if (r->exchange.stream) RT_HIP(hipStreamSynchronize(r->exchange.stream));
@@ -177,7 +177,7 @@ int hala_rt_set_light_groups(hala_rt_renderer* r, const hala_light_groups* g) {
   if (g && r->world > 1) RT_FAIL("hala_rt_set_light_groups: light groups are not available on a sharded renderer (world > 1).");
   if (g && (size_t)r->slot_count * r->batch_capacity > kGroupSlotMask)
     RT_FAIL("hala_rt_set_light_groups: light groups need fewer than 2^29 path slots (pixels x samples x views).");
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins an open tail
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins the second frame slot
   RT_HIP(hipStreamSynchronize(r->stream));
   r->groups.off();
   if (g) {

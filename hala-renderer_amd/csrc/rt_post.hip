@@ -92,7 +92,7 @@ static int temporal_ready(hala_rt_renderer* r, const char* fn) {
   if (r->views[0] >= r->hs.cameras.size()) RT_FAIL(std::string(fn) + ": view 0 renders a camera the committed scene lacks (hala_rt_set_views).");
   return HALA_OK;
 }
-// The table of this resolve (temporal.h) and the launch, on the renderer's stream, which has joined the tail.  The table is rebuilt and
+// The table of this resolve (temporal.h) and the launch, on the renderer's stream, which has joined the second frame slot.  The table is rebuilt and
 // uploaded only while TemporalState::table_dirty (after a capture, a mark, a refit, ...), behind a wait for the resolves that still read the
 // old one; every other resolve is the launch alone.
 static int temporal_enqueue_resolve(hala_rt_renderer* r, hipEvent_t before = nullptr) {

@@ -248,7 +248,7 @@ static int configure_traversal(hala_rt_renderer* r) {
     if (r->bvh.stack_need > traverse_stack_lds_levels(tree) + traverse_stack_spill_levels())
       RT_FAIL("The BVH is deeper than the traversal stack supports (" + std::to_string(r->bvh.max_depth) + " levels, " + std::to_string(r->bvh.stack_need) + " stack entries).");
     RT_HIP(r->d_spill.resize((size_t)r->lcfg.persistent_blocks * 256 * traverse_stack_spill_levels()));
-    RT_HIP(r->tail.d_spill.resize(r->d_spill.count));  // the launches of an update's tail, which run beside the next camera-ray launch
+    RT_HIP(r->slots.d_spill.resize(r->d_spill.count));  // the second frame slot's launches, which run beside the first's
     r->lcfg.spill = r->d_spill.ptr;
   }
   const float ex = r->bvh.scene_max[0] - r->bvh.scene_min[0], ey = r->bvh.scene_max[1] - r->bvh.scene_min[1], ez = r->bvh.scene_max[2] - r->bvh.scene_min[2];

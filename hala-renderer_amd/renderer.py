@@ -176,6 +176,16 @@ class HalaRenderer:
         """0: one launch per pass; 1 (default): fused launches except in timed updates; 2: always (timed updates fill traverse_fused_*)"""
         self._check(self._lib.hala_rt_set_pass_fusion(self._h, C.c_uint32(mode)))
 
+    def set_frames_in_flight(self, n):
+        """2 (default): untimed updates alternate between two frame slots and overlap; 1: strictly serial — see include/halart.h"""
+        self._check(self._lib.hala_rt_set_frames_in_flight(self._h, C.c_uint32(n)))
+
+    def frames_in_flight_info(self):
+        """-> (updates that ran on the second frame slot, the second set of wavefront buffers is allocated)"""
+        n, b = C.c_ulonglong(0), C.c_uint32(0)
+        self._check(self._lib.hala_rt_frames_in_flight_info(self._h, C.byref(n), C.byref(b)))
+        return n.value, bool(b.value)
+
     def set_launch_timing_period(self, period):
         """per-launch HIP events on every `period`-th update (1: all, the default; 0: none) — see include/halart.h"""
         self._check(self._lib.hala_rt_set_launch_timing_period(self._h, C.c_uint32(period)))

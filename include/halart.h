@@ -408,7 +408,7 @@ int hala_rt_read_view_image(hala_rt_renderer* r, uint32_t view, int which, float
  *     hala_rt_get_packed_primitives and the node it came from.  Light: (node of the light, 0xFFFFFFFF, 0xFFFFFFFF, 0x80000000 | light
  *     index).  Miss: all 0xFFFFFFFF.
  * They follow the tile layout, the views, adaptive sampling and update_batch like images 0-3.  Bits above 1 are refused with the
- * renderer left as it was.  A successful call joins the tail of the last update, allocates or frees images 4 / 5 of every view and
+ * renderer left as it was.  A successful call joins the second frame slot, allocates or frees images 4 / 5 of every view and
  * 16 B per path slot each, and restarts the accumulation.  read_image, read_view_image, tile_buffer, the scatter and exchange entry
  * points take `which` 4 / 5 and the all-gather masks bits 4 / 5 while that AOV is on, and refuse them while it is off.  Not built:
  * save_images does not write them (hala_write_pfm does), no depth image (view depth follows from position and the camera), no
@@ -426,12 +426,12 @@ int hala_rt_set_aovs(hala_rt_renderer* r, uint32_t mask);
  * on the isolated scene of g (every light outside g at intensity 0, env_intensity 0 unless the environment is in g, every material
  * outside g with emission 0 and, if its medium is EMISSIVE, medium colour 0) bit for bit, except in samples where a zeroed term is
  * non-finite (0 * inf).  The images follow the views, adaptive sampling (converged blocks keep theirs), update_batch (k frames equal k
- * updates) and the tail overlap like accum.
+ * updates) and two updates in flight like accum.
  * Refused, with the renderer left as it was and before any device work: group_count 0 or > 8, a group index >= group_count, a null
  * table with a nonzero count (these are checked before the handle is looked at), a sharded renderer (world > 1; hala_rt_set_tile_shard
  * refuses the other order), and more than 2^29 - 1 path slots (pixels x samples x views: light connections carry the group in the top
  * bits of their slot word).  An update whose committed scene has more lights or materials than the tables cover fails before any
- * device work.  A successful call joins the tail of the last update, allocates (12 B per path slot and group, 16 B per pixel, view
+ * device work.  A successful call joins the second frame slot, allocates (12 B per path slot and group, 16 B per pixel, view
  * and group) or frees the buffers and restarts the accumulation.  Not built: gathering the images across ranks, groups in save_images,
  * light path expressions beyond the emitter. */
 typedef struct hala_light_groups {
@@ -465,13 +465,13 @@ int hala_rt_get_relit_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_
  * [n, other, (id, count) x 7] as uint32, entries by count descending then id ascending, a sample whose id finds no room counts in other.
  * Ranked output: ranks 0..5 as (id as float bits, count / n), sublayer k = ranks 2k and 2k + 1 as R, G, B, A.  Images 0-5, the
  * statistics, the RNG and every existing refusal are the same with the feature on or off.  The records follow the views, adaptive sampling
- * (converged blocks keep theirs), update_batch (k frames equal k updates) and the tail overlap; every restart of the accumulation empties
+ * (converged blocks keep theirs), update_batch (k frames equal k updates) and two updates in flight; every restart of the accumulation empties
  * them at the next frame 0.  NULL turns the feature off, the default.
  * Refused, with the renderer left as it was and before any device work: layer_mask 0 or > 7, a null name table with a nonzero count,
  * reserved words not 0 (these are checked before the handle is looked at), a sharded renderer (world > 1; hala_rt_set_tile_shard refuses
- * the other order).  A successful call joins the tail of the last update, allocates (64 B per pixel, view and layer, and the 16-B
+ * the other order).  A successful call joins the second frame slot, allocates (64 B per pixel, view and layer, and the 16-B
  * first-hit record per path slot while image 5 is off) or frees the records and restarts the accumulation.  Cost: one HBM-bound fold
- * launch per update in the tail, beside the resolve.  Not built: gathering the records across ranks, deep EXR, coverage
+ * launch per update right behind the resolve.  Not built: gathering the records across ranks, deep EXR, coverage
  * through transparent surfaces, pixel filters other than the camera jitter's box, a preview channel, material names from glTF. */
 typedef struct hala_cryptomatte_desc {
   uint32_t layer_mask;               /* bit 0 object, bit 1 material, bit 2 asset */
@@ -564,6 +564,19 @@ int hala_rt_set_launch_timing_period(hala_rt_renderer* r, uint32_t period);
  * keep one launch per pass so that every measured launch is one kernel symbol with the chip to itself; 2: always — timed updates then
  * fill the traverse_fused_* statistics.  Counting updates (hala_rt_set_counting) never fuse.  Images do not depend on the mode. */
 int hala_rt_set_pass_fusion(hala_rt_renderer* r, uint32_t mode);
+/* Frames in flight.  Consecutive updates are independent except for the order in which their samples are folded into the accumulated
+ * images, so updates without per-launch timing or counting alternate between two frame slots, each with its own stream, control block,
+ * stack spill area, per-path state and queues: update k + 1 starts beside the last bounces of update k (its dense camera-ray launch and
+ * depth-0 shade fill the chip the short last queues leave idle); its resolve and Cryptomatte fold wait for those of update k.  n = 2
+ * (default): as described; hala_rt_render keeps bounding the updates in flight to two.  n = 1: strictly serial, one slot on the
+ * renderer's stream.  Images, AOVs and ray counts do not depend on n, bit for bit.  Memory: the second slot doubles the wavefront
+ * buffers (about 250 B per path: 2.1 -> 4.2 GB for a 1080p batch of four samples); it is allocated the first time an update finds the
+ * other slot busy, and if that allocation fails the renderer keeps working with one slot.  gpu_ms_total sums the spans of the updates,
+ * which overlap: it can exceed wall time.  The call joins both slots, then applies; n = 1 frees the second slot's buffers. */
+int hala_rt_set_frames_in_flight(hala_rt_renderer* r, uint32_t n);
+/* How many updates ran on the second frame slot since the renderer was created, and whether the second set of wavefront buffers is
+ * allocated (LDS-staged scenes never allocate it: their updates share one set).  Either pointer may be null. */
+int hala_rt_frames_in_flight_info(hala_rt_renderer* r, unsigned long long* second_slot_updates, uint32_t* second_buffers);
 /* the 112-B record the last update uploaded (src/rt_renderer.rs:408-427) */
 int hala_rt_get_global_uniform(hala_rt_renderer* r, hala_global_uniform* out);
 
@@ -608,10 +621,10 @@ int hala_rt_sample_texture_host(hala_rt_renderer* r, uint32_t texture, const flo
  * (hala_rt_set_views). */
 int hala_rt_set_tile_shard(hala_rt_renderer* r, uint32_t rank, uint32_t world, uint32_t tile_size);
 int hala_rt_tile_buffer(hala_rt_renderer* r, int which, void** d_ptr, size_t* bytes);
-/* the hipStream_t every launch of this renderer goes to (for stream-ordered hand-overs: hipStreamWaitEvent both ways).  Exception: the
- * tail of an update without per-launch timing (its last shadow launches and the resolve) runs on a second stream beside the next update's
- * camera-ray launch; every call into the library other than update and render first puts the renderer's stream behind it, this one
- * included — fetch the stream after the updates a hand-over is to cover. */
+/* the hipStream_t every launch of this renderer goes to (for stream-ordered hand-overs: hipStreamWaitEvent both ways).  Exception: every
+ * other update without per-launch timing runs, from its camera-ray launch to the tail of its resolve, on a second stream beside the update
+ * before it (hala_rt_set_frames_in_flight); every call into the library other than update and render first puts the renderer's stream
+ * behind it, this one included — fetch the stream after the updates a hand-over is to cover. */
 int hala_rt_get_stream(hala_rt_renderer* r, void** hip_stream);
 int hala_rt_scatter_gathered_tiles(hala_rt_renderer* r, int which, const void* d_gathered, size_t bytes);
 

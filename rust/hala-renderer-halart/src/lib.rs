@@ -130,6 +130,8 @@ pub mod sys {
     pub fn hala_rt_get_stream(r: *mut hala_rt_renderer, hip_stream: *mut *mut c_void) -> c_int;
     pub fn hala_rt_set_launch_timing_period(r: *mut hala_rt_renderer, period: u32) -> c_int;
     pub fn hala_rt_set_pass_fusion(r: *mut hala_rt_renderer, mode: u32) -> c_int;
+    pub fn hala_rt_set_frames_in_flight(r: *mut hala_rt_renderer, n: u32) -> c_int;
+    pub fn hala_rt_frames_in_flight_info(r: *mut hala_rt_renderer, second_slot_updates: *mut u64, second_buffers: *mut u32) -> c_int;
     pub fn hala_rt_set_build_options(r: *mut hala_rt_renderer, options: *const hala_rt_build_options) -> c_int;
     pub fn hala_rt_tile_allgather_begin_external(r: *mut hala_rt_renderer, aov_mask: u32) -> c_int;
     pub fn hala_rt_get_exchange_buffers(r: *mut hala_rt_renderer, which: c_int, d_staged: *mut *mut c_void, staged_bytes: *mut usize,
@@ -279,6 +281,8 @@ impl HalaRenderer {
   }
   /// per-launch timing events on every `period`-th update (1: all, 0: none)
   pub fn set_launch_timing_period(&mut self, period: u32) -> Result<(), HalaRendererError> { check(unsafe { sys::hala_rt_set_launch_timing_period(self.h, period) }) }
+  /// 2 (default): updates without per-launch timing alternate between two frame slots and overlap; 1: strictly serial
+  pub fn set_frames_in_flight(&mut self, n: u32) -> Result<(), HalaRendererError> { check(unsafe { sys::hala_rt_set_frames_in_flight(self.h, n) }) }
   /// 0: one launch per pass, 1 (default): fused launches except in timed updates, 2: always
   pub fn set_pass_fusion(&mut self, mode: u32) -> Result<(), HalaRendererError> { check(unsafe { sys::hala_rt_set_pass_fusion(self.h, mode) }) }
   /// How the next commit() builds the acceleration structure: builder 0 auto | 1 SAH | 2 PLOC | 3 LBVH; instancing 0 auto | 1 flattened |

@@ -61,7 +61,7 @@ def time_relight(r, calls):
 def run(r, steps):
     """(host ms per step, GPU ms per step).  The GPU figure is a pair of HIP events on the renderer's stream around all the steps: the
     end event follows the last update's tail, which stream_handle() joins into that stream.  (The updates' own frame_begin -> frame_end
-    spans overlap under the tail overlap and do not add up to the frame time.)"""
+    spans overlap with two updates in flight and do not add up to the frame time.)"""
     import torch
     r.wait_idle()
     stream = torch.cuda.ExternalStream(r.stream_handle())
@@ -71,7 +71,7 @@ def run(r, steps):
     for _ in range(steps):
         r.update_batch(SPP)
         r.render()
-    stream = torch.cuda.ExternalStream(r.stream_handle())  # joins the open tail
+    stream = torch.cuda.ExternalStream(r.stream_handle())  # joins the second frame slot
     e1.record(stream)
     e1.synchronize()
     host = 1e3 * (time.perf_counter() - t0) / steps

@@ -41,7 +41,7 @@ def summary(xs):
 
 
 def events(r, fn, calls):
-    """GPU ms of each of `calls` calls of fn(), between two HIP events on the renderer's stream (stream_handle() joins an open tail)"""
+    """GPU ms of each of `calls` calls of fn(), between two HIP events on the renderer's stream (stream_handle() joins the second frame slot)"""
     import torch
     out = []
     for _ in range(calls):
