@@ -224,6 +224,15 @@ class DeformerDesc(C.Structure):  # hala_deformer_desc, 64 B (docs/RENDER_SPEC.m
                 ("joints", C.POINTER(C.c_uint16)), ("weights", C.POINTER(C.c_float))]
 
 
+class ShutterParams(C.Structure):  # hala_shutter_params, 32 B (docs/RENDER_SPEC.md 18)
+    _fields_ = [("shutter_open", C.c_float), ("shutter_close", C.c_float), ("time_stride", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class ShutterStatus(C.Structure):  # hala_shutter_status, 32 B
+    _fields_ = [("enabled", C.c_uint32), ("time_stride", C.c_uint32), ("step", C.c_uint32), ("time", C.c_float), ("steps", C.c_uint64),
+                ("reserved", C.c_uint32 * 2)]
+
+
 # argtypes / restype of the denoise, adaptive sampling, view and AOV entry points (load_library installs them)
 PROTOTYPES = {
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
@@ -268,6 +277,13 @@ PROTOTYPES = {
     "hala_rt_update_deformer": ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float), C.c_uint32], C.c_int),
     "hala_rt_clear_deformer": ([C.c_void_p, C.c_uint32, C.c_uint32], C.c_int),
     "hala_rt_read_vertices": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)], C.c_int),
+    "hala_shutter_default_params": ([C.POINTER(ShutterParams)], None),
+    "hala_rt_set_shutter": ([C.c_void_p, C.POINTER(ShutterParams)], C.c_int),
+    "hala_rt_get_shutter_status": ([C.c_void_p, C.POINTER(ShutterStatus)], C.c_int),
+    "hala_rt_set_node_keys": ([C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_set_deformer_keys": ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32,
+                                   C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32], C.c_int),
+    "hala_rt_set_vertex_keys": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32], C.c_int),
 }
 
 
@@ -313,4 +329,6 @@ EXPORTS = [
     "hala_temporal_clamp_default_params", "hala_rt_set_temporal_clamp",
     "hala_rt_texture_bundle_info",
     "hala_rt_set_deformer", "hala_rt_update_deformer", "hala_rt_clear_deformer", "hala_rt_read_vertices",
+    "hala_shutter_default_params", "hala_rt_set_shutter", "hala_rt_get_shutter_status", "hala_rt_set_node_keys", "hala_rt_set_deformer_keys",
+    "hala_rt_set_vertex_keys",
 ]

@@ -281,6 +281,7 @@ int hala_rt_set_scene(hala_rt_renderer* r, const hala_scene_desc* scene) {
   r->has_scene = false; r->committed = false;  // "Release the old scene in the GPU." (src/rt_renderer.rs:1164)
   r->temporal.drop_history();  // RENDER_SPEC §16: the history belongs to the old scene
   r->deform.off();             // RENDER_SPEC §17: so do the deformers
+  r->shutter.off();            // RENDER_SPEC §18: and every key, and the shutter
   const std::string e = r->hs.assign(scene);
   if (!e.empty()) RT_FAIL(e);
   if (upload_packed(r) != HALA_OK) return HALA_ERR;
@@ -361,6 +362,12 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
             " material(s), but the committed scene has " + std::to_string(r->hs.lights.size()) + " and " + std::to_string(r->hs.gpu_materials.size()) +
             " (hala_rt_set_light_groups).");
   const uint64_t first = r->total_frames;  // frame_index of the first frame of this batch = total_frames - 1 after its increment
+  // RENDER_SPEC §18: a frame of another step than the one the scene stands at moves the scene first (hala_rt_update_batch ends its chunks
+  // on stride boundaries: every frame of this batch belongs to one step).  The frame counter advances only behind a successful step.
+  if (r->shutter.act.active() && first < r->max_frames) {
+    const uint32_t step = (uint32_t)first / r->shutter.act.stride;
+    if (step != r->shutter.step && shutter_step(r, step) != HALA_OK) return HALA_ERR;
+  }
   r->total_frames += frames;
   if (first >= r->max_frames) return HALA_OK;
   const uint32_t samples = (uint32_t)std::min<uint64_t>(frames, r->max_frames - first);
@@ -529,6 +536,8 @@ int hala_rt_update_batch(hala_rt_renderer* r, uint32_t frames) {
     uint32_t chunk = std::min(frames, max_chunk);
     if (r->adaptive.enabled && r->total_frames < r->max_frames)  // a chunk ends on the next snapshot or check frame (RENDER_SPEC 11)
       chunk = (uint32_t)std::min<uint64_t>(chunk, adaptive_frames_to_event(r->adaptive.p, r->total_frames));
+    if (r->shutter.act.active() && r->total_frames < r->max_frames)  // ... and on the last frame of the shutter's step (RENDER_SPEC §18)
+      chunk = std::min(chunk, r->shutter.act.stride - (uint32_t)r->total_frames % r->shutter.act.stride);
     if (update_impl(r, chunk) != HALA_OK) return HALA_ERR;
     frames -= chunk;
   }

@@ -1,6 +1,6 @@
 // renderer_state.h — the renderer object behind the C ABI (struct hala_rt_renderer), shared by the host units that implement it:
 // renderer.hip (life cycle, scene, update), rt_scene.hip (uploads, trees, edits), rt_outputs.hip (views, AOVs, adaptive sampling, light
-// groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_deform.hip (deformers), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
+// groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_deform.hip (deformers), rt_shutter.hip (shutter motion blur), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
 // Each feature keeps its state in one struct that knows how to turn itself off.  Nothing outside csrc/ includes this header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@
 #include "host_scene.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "shutter.h"
 #include "temporal.h"
 
 namespace rt { std::string decode_image_file_rgba8(const char* path, uint32_t* w, uint32_t* h, std::vector<uint8_t>* rgba); }  // gltf_loader.cpp
@@ -260,6 +261,20 @@ struct FrameSlots {
   }
 };
 
+// shutter motion blur (RENDER_SPEC §18; hala_rt_set_shutter, hala_rt_set_*_keys).  `rec` is what the setters recorded (edits), `act` what the last hala_rt_refit applied: the update path only reads `act`.
+struct ShutterState {
+  ShutterKeys rec, act;
+  uint32_t step = kShutterNoStep;  // the step the scene stands at
+  float time = 0.0f;
+  unsigned long long steps = 0;    // steps performed since create
+  // the edits as the last refit found them: a step refits from these, so that edits recorded since do not ride along with it
+  std::vector<Mat4> locals;
+  std::vector<hala_material_desc> materials;
+  std::vector<uint32_t> stale;     // primitives whose arena range the next refit uploads again from the host copy
+  DeviceArray<uint32_t> d_flags;   // one overflow word per launch of k_shutter_lerp
+  void off() { rec = ShutterKeys(); act = ShutterKeys(); step = kShutterNoStep; time = 0.0f; locals.clear(); materials.clear(); stale.clear(); }
+};
+
 enum class Changed { Commit, Refit, Views, Aovs };  // hala_rt_renderer::invalidate
 
 }  // namespace rt
@@ -384,6 +399,7 @@ struct hala_rt_renderer {
   AdaptiveState adaptive;      // RENDER_SPEC 11: allocated by the first hala_rt_set_adaptive_sampling that enables it
   TemporalState temporal;      // RENDER_SPEC 16: allocated by hala_rt_set_temporal
   DeformState deform;          // RENDER_SPEC 17: one deformer per primitive (hala_rt_set_deformer)
+  ShutterState shutter;        // RENDER_SPEC 18: keys and shutter (hala_rt_set_shutter)
   DeviceArray<P3> ps_lr, ps_le, ps_alb, ps_nrm;
   DeviceArray<hala_ray> q_rays[2];
   DeviceArray<float4> q_state[2];
@@ -558,6 +574,13 @@ int build_bvh(hala_rt_renderer* r);
 // rt_deform.hip: poses the deformers whose parameters changed (hala_rt_refit, on an idle stream); is a deformer registered on the primitive
 int deform_apply_pending(hala_rt_renderer* r);
 bool deform_registered(const hala_rt_renderer* r, uint32_t prim);
+int find_primitive(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, uint32_t* prim);
+// rt_scene.hip: hala_rt_refit without the restart — hierarchies, packed records, the tree (rebuilt when the instancing flags change)
+int refit_geometry(hala_rt_renderer* r);
+// rt_shutter.hip (RENDER_SPEC §18).  shutter_refit: hala_rt_refit's geometry part with the recorded keys applied, the scene left at step
+// 0; shutter_step: moves the scene to step `j` between two frames of one accumulation (update_impl, while the shutter is active)
+int shutter_refit(hala_rt_renderer* r);
+int shutter_step(hala_rt_renderer* r, uint32_t j);
 // rt_cryptomatte.hip
 int crypto_prepare(hala_rt_renderer* r);
 // rt_tiles.hip

@@ -6,7 +6,7 @@
 
 namespace rt {
 
-static int find_primitive(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, uint32_t* prim) {
+int find_primitive(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, uint32_t* prim) {
   if (mesh_index + 1u >= r->hs.mesh_first_prim.size() || mesh_index == 0xffffffffu) RT_FAIL("The mesh does not exist.");
   const uint32_t first = r->hs.mesh_first_prim[mesh_index], end = r->hs.mesh_first_prim[mesh_index + 1u];
   if (primitive_index >= end - first) RT_FAIL("The primitive does not exist.");
@@ -119,6 +119,8 @@ int hala_rt_set_deformer(hala_rt_renderer* r, const hala_deformer_desc* desc) {
   if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
   uint32_t prim = 0;
   if (find_primitive(r, desc->mesh_index, desc->primitive_index, &prim) != HALA_OK) return HALA_ERR;
+  if (r->shutter.rec.vertices.count(prim) || r->shutter.act.vertices.count(prim)) RT_FAIL("The primitive has shutter vertex keys: clear them and refit first (hala_rt_set_vertex_keys).");
+  if (r->shutter.rec.deformers.count(prim) || r->shutter.act.deformers.count(prim)) RT_FAIL("The primitive's deformer has shutter keys: clear them and refit first (hala_rt_set_deformer_keys).");
   if (desc->target_count > kMaxMorphTargets) RT_FAIL("The deformer has more than " + std::to_string(kMaxMorphTargets) + " morph targets.");
   if (desc->joint_count > kMaxJoints) RT_FAIL("The deformer has more than " + std::to_string(kMaxJoints) + " joints.");
   if (desc->target_count == 0u && desc->joint_count == 0u) RT_FAIL("The deformer has neither morph targets nor a skin.");
@@ -171,6 +173,7 @@ int hala_rt_update_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
   auto it = r->deform.by_prim.find(prim);
   if (it == r->deform.by_prim.end()) RT_FAIL("The primitive has no deformer.");
   Deformer& d = *it->second;
+  if (r->shutter.rec.deformers.count(prim)) RT_FAIL("The deformer has shutter keys: clear them first (hala_rt_set_deformer_keys with all keys NULL).");
   if (morph_weights && weight_count != d.target_count)
     RT_FAIL("The weight count differs from the deformer's target count (" + std::to_string(d.target_count) + ").");
   if (joint_matrices_3x4 && joint_count != d.joint_count)
@@ -190,6 +193,7 @@ int hala_rt_clear_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t pr
   if (find_primitive(r, mesh_index, primitive_index, &prim) != HALA_OK) return HALA_ERR;
   auto it = r->deform.by_prim.find(prim);
   if (it == r->deform.by_prim.end()) RT_FAIL("The primitive has no deformer.");
+  if (r->shutter.rec.deformers.count(prim) || r->shutter.act.deformers.count(prim)) RT_FAIL("The deformer has shutter keys: clear them and refit first (hala_rt_set_deformer_keys).");
   if (it->second->posed) {
     if (restore_rest(r, *it->second) != HALA_OK) return HALA_ERR;
     RT_HIP(hipStreamSynchronize(r->stream));  // the copy reads the tables freed below

@@ -107,6 +107,7 @@ int hala_rt_set_adaptive_sampling(hala_rt_renderer* r, const hala_adaptive_param
     if (r->world > 1) RT_FAIL("Adaptive sampling is not available on a sharded renderer (world > 1).");
     if (r->view_count() > 1u) RT_FAIL("Adaptive sampling is not available with several views (hala_rt_set_views with one camera first).");
     if (r->temporal.enabled) RT_FAIL("Adaptive sampling is not available with temporal reprojection on (hala_rt_set_temporal(r, NULL) first).");
+    if (r->shutter.rec.on || r->shutter.act.on) RT_FAIL("Adaptive sampling is not available with the shutter on (hala_rt_set_shutter(r, NULL) first).");
     if (!ad.enabled) {
       RT_HIP(hipStreamSynchronize(r->stream));
       const uint32_t blocks = r->blocks_x * ((r->height + kPixelBlock - 1) / kPixelBlock);

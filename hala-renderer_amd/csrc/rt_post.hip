@@ -146,6 +146,7 @@ int hala_rt_set_temporal(hala_rt_renderer* r, const hala_temporal_params* p) {
   if (p && r->world > 1) RT_FAIL("hala_rt_set_temporal: temporal reprojection is not available on a sharded renderer (world > 1).");
   if (p && r->view_count() > 1u) RT_FAIL("hala_rt_set_temporal: temporal reprojection is not available with several views (hala_rt_set_views with one camera first).");
   if (p && r->adaptive.enabled) RT_FAIL("hala_rt_set_temporal: temporal reprojection is not available with adaptive sampling on (hala_rt_set_adaptive_sampling(r, NULL) first).");
+  if (p && (r->shutter.rec.on || r->shutter.act.on)) RT_FAIL("hala_rt_set_temporal: temporal reprojection is not available with the shutter on (hala_rt_set_shutter(r, NULL) first).");
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   TemporalState& t = r->temporal;
   if (!p) {

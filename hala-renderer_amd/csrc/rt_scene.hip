@@ -619,6 +619,7 @@ int hala_rt_update_node_transform(hala_rt_renderer* r, uint32_t node_index, cons
   if (!r || !local_transform) RT_FAIL("Invalid argument.");
   if (!r->committed) RT_FAIL("The top level acceleration structure is none!");  // commit builds from what set_scene packed: an edit before it would not reach it
   if (node_index >= r->hs.nodes.size()) RT_FAIL("The node does not exist.");
+  if (r->shutter.rec.nodes.count(node_index)) RT_FAIL("The node has shutter keys: clear them first (hala_rt_set_node_keys with both keys NULL).");
   memcpy(r->hs.nodes[node_index].local.m, local_transform, 64);
   return HALA_OK;
 }
@@ -631,10 +632,16 @@ int hala_rt_update_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
   if (primitive_index >= end - first) RT_FAIL("The primitive does not exist.");
   HostPrimitive& p = r->hs.prims[first + primitive_index];
   if (deform_registered(r, first + primitive_index)) RT_FAIL("The primitive has a deformer: clear it first (hala_rt_clear_deformer).");
+  if (r->shutter.rec.vertices.count(first + primitive_index)) RT_FAIL("The primitive has shutter keys: clear them first (hala_rt_set_vertex_keys with both keys NULL).");
   if (vertex_count != p.vertices.size()) RT_FAIL("The vertex count differs from the primitive's (" + std::to_string(p.vertices.size()) + "): refit keeps the topology, use set_scene + commit.");
   for (uint32_t k = 0; k < vertex_count; ++k)
     if (!std::isfinite(vertices[k].position[0]) || !std::isfinite(vertices[k].position[1]) || !std::isfinite(vertices[k].position[2])) RT_FAIL("Vertex position is not finite.");
   memcpy(p.vertices.data(), vertices, (size_t)vertex_count * sizeof(hala_vertex));
+  if (r->shutter.act.active()) {  // RENDER_SPEC §18: the steps until the refit read the arena; the refit uploads the host copy
+    r->shutter.stale.push_back(first + primitive_index);
+    r->vertices_dirty = true;
+    return HALA_OK;
+  }
   // the copy below reads the renderer's own host copy, which outlives it; earlier frames still read the arena: wait for them
   RT_HIP(hipStreamSynchronize(r->stream));
   r->vertices_dirty = true;
@@ -654,12 +661,13 @@ int hala_rt_update_material(hala_rt_renderer* r, uint32_t material_index, const 
   if (r->temporal.enabled && material_index < r->temporal.mat_marked.size()) { r->temporal.mat_marked[material_index] = 1; r->temporal.table_dirty = true; }  // RENDER_SPEC §16
   return HALA_OK;
 }
-int hala_rt_refit(hala_rt_renderer* r) {
-  RtRange range("halart::refit");
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;
-  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
-  RT_HIP(hipStreamSynchronize(r->stream));
-  if (deform_apply_pending(r) != HALA_OK) return HALA_ERR;  // RENDER_SPEC §17: the posed vertices, just ahead of the refit that reads them
+}  // extern "C"
+
+namespace rt {
+
+// The geometry part of hala_rt_refit: everything but the restart of the accumulation.  The caller has joined both frame slots, waited,
+// and posed what is posed on the device (deform_apply_pending, k_shutter_lerp).  A step of the shutter (RENDER_SPEC §18) is this alone.
+int refit_geometry(hala_rt_renderer* r) {
   const std::vector<hala_gpu_mesh_data> before = r->hs.instances;  // object -> world of every instance as the tree was fitted to it
   const std::vector<uint8_t> kinds_before = r->material_kind;
   r->hs.update_node_hierarchies();
@@ -706,6 +714,20 @@ int hala_rt_refit(hala_rt_renderer* r) {
     if (configure_traversal(r) != HALA_OK) return HALA_ERR;
     r->vertices_dirty = false;
   }
+  return HALA_OK;
+}
+
+}  // namespace rt
+
+extern "C" {
+
+int hala_rt_refit(hala_rt_renderer* r) {
+  RtRange range("halart::refit");
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  RT_HIP(hipStreamSynchronize(r->stream));
+  // RENDER_SPEC §17 and §18: the posed vertices (and the keyed state at step 0), just ahead of the refit that reads them; then the geometry part
+  if (shutter_refit(r) != HALA_OK) return HALA_ERR;
   r->invalidate(Changed::Refit);
   r->reset_accumulation();  // like the device-lost path: accumulation restarts (src/rt_renderer.rs:557)
   return HALA_OK;

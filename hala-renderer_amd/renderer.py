@@ -615,6 +615,60 @@ class HalaRenderer:
         self._check(self._lib.hala_rt_read_vertices(self._h, C.c_uint32(mesh), C.c_uint32(prim), C.c_void_p(out.ctypes.data), C.c_uint32(n.value), C.byref(n)))
         return out
 
+    # -- shutter motion blur (docs/RENDER_SPEC.md 18; include/halart.h "Shutter") -------------------------------------------------------
+    def set_shutter(self, open=0.0, close=1.0, time_stride=1):
+        """frame k of an accumulation renders the keyed holders at the time of step k // time_stride, a stratified sequence over
+        [open, close); set_shutter(None) turns the shutter off.  Applied by the next refit()"""
+        if open is None:
+            self._check(self._lib.hala_rt_set_shutter(self._h, None))
+            return
+        p = A.ShutterParams()
+        self._lib.hala_shutter_default_params(C.byref(p))
+        p.shutter_open, p.shutter_close, p.time_stride = open, close, time_stride
+        self._check(self._lib.hala_rt_set_shutter(self._h, C.byref(p)))
+
+    def shutter_status(self) -> A.ShutterStatus:
+        """enabled, time_stride, step (0xFFFFFFFF: none), time, steps: as the last refit() and the updates since left them"""
+        s = A.ShutterStatus()
+        self._check(self._lib.hala_rt_get_shutter_status(self._h, C.byref(s)))
+        return s
+
+    def set_node_keys(self, node_index, open=None, close=None):
+        """the node's local transform ([4, 4], as update_node_transform takes it) at time 0 and at time 1; both None clears the keys.
+        Applied by the next refit()"""
+        def arg(m):
+            return None if m is None else (C.c_float * 16)(*np.asarray(m, dtype=np.float32).T.reshape(-1).tolist())
+        self._check(self._lib.hala_rt_set_node_keys(self._h, C.c_uint32(node_index), arg(open), arg(close)))
+
+    def set_deformer_keys(self, mesh, prim, open=None, close=None):
+        """the deformer's pose at time 0 and at time 1, each a dict(morph_weights=..., joint_matrices=...) as update_deformer takes
+        them (a part that is None in one pose must be None in the other); both None clears the keys.  Applied by the next refit()"""
+        fp = C.POINTER(C.c_float)
+
+        def part(pose, key, cols):
+            a = None if pose is None else pose.get(key)
+            return None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1, cols)
+
+        wo, wc = part(open, "morph_weights", 1), part(close, "morph_weights", 1)
+        mo, mc = part(open, "joint_matrices", 12), part(close, "joint_matrices", 12)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(fp)  # noqa: E731
+        count = lambda a, b: next((x.shape[0] for x in (a, b) if x is not None), 0)  # noqa: E731
+        if (wo is not None and wc is not None and wo.shape != wc.shape) or (mo is not None and mc is not None and mo.shape != mc.shape):
+            raise ValueError("the two poses have the same number of weights and of joint matrices")
+        self._check(self._lib.hala_rt_set_deformer_keys(self._h, C.c_uint32(mesh), C.c_uint32(prim), ptr(wo), ptr(wc), C.c_uint32(count(wo, wc)),
+                                                        ptr(mo), ptr(mc), C.c_uint32(count(mo, mc))))
+
+    def set_vertex_keys(self, mesh, prim, open=None, close=None):
+        """the primitive's vertices (VERTEX_DTYPE records, the primitive's count) at time 0 and at time 1; both None clears the keys.
+        Both stay on the device.  Applied by the next refit()"""
+        o = None if open is None else np.ascontiguousarray(open, dtype=A.VERTEX_DTYPE)
+        c = None if close is None else np.ascontiguousarray(close, dtype=A.VERTEX_DTYPE)
+        if o is not None and c is not None and o.shape != c.shape:
+            raise ValueError("the two keys have the same number of vertices")
+        n = next((x.shape[0] for x in (o, c) if x is not None), 0)
+        self._check(self._lib.hala_rt_set_vertex_keys(self._h, C.c_uint32(mesh), C.c_uint32(prim), None if o is None else C.c_void_p(o.ctypes.data),
+                                                      None if c is None else C.c_void_p(c.ctypes.data), C.c_uint32(n)))
+
     # -- multi-GPU tile sharding ---------------------------------------------------------------------------------------
     def set_tile_shard(self, rank, world, tile_size=32):
         self._check(self._lib.hala_rt_set_tile_shard(self._h, C.c_uint32(rank), C.c_uint32(world), C.c_uint32(tile_size)))

@@ -795,6 +795,71 @@ int hala_rt_read_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t pri
                           uint32_t* count);
 
 /* ------------------------------------------------------------------------------------------------
+ * Shutter (docs/RENDER_SPEC.md 18; no reference equivalent): motion blur by accumulation.  Holders — a node's local transform, a
+ * deformer's parameters, a primitive's vertices — carry two keys, the state at time 0 and at time 1.  While the shutter is on, frame k
+ * of an accumulation renders the scene at the time of step k / time_stride, a stratified sequence over [shutter_open, shutter_close):
+ * between two frames of different steps the library interpolates every keyed holder and refits the tree, without restarting the
+ * accumulation.  All four setters are edits: they record on the host and take effect at the next hala_rt_refit, which leaves the
+ * scene at step 0; until then updates render what they rendered and keep accumulating.  hala_rt_set_scene drops every key and the
+ * shutter; hala_rt_commit keeps them.  A renderer that never sets a key or a shutter behaves exactly as before.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hala_shutter_params {
+  float shutter_open;   /* 0 <= shutter_open <= shutter_close <= 1 */
+  float shutter_close;
+  uint32_t time_stride; /* 1 ... 65536: consecutive frames that share one time */
+  uint32_t reserved[5]; /* 0 */
+} hala_shutter_params;  /* 32 B */
+typedef struct hala_shutter_status {
+  uint32_t enabled;     /* the shutter as the last hala_rt_refit applied it: 1 on, 0 off */
+  uint32_t time_stride;
+  uint32_t step;        /* the step the scene stands at; 0xFFFFFFFF: none (no key applied) */
+  float time;           /* its time */
+  uint64_t steps;       /* steps performed since hala_rt_create */
+  uint32_t reserved[2];
+} hala_shutter_status;  /* 32 B */
+/* (0, 1, 1): the whole interval, a new time for every frame */
+void hala_shutter_default_params(hala_shutter_params* out);
+/* Records the shutter; NULL turns it off.  Takes effect at the next hala_rt_refit.  The time of step j is shutter_open + u_j *
+ * (shutter_close - shutter_open) with u_j the base-2 radical inverse of j (24 bits).  The shutter is inactive — no step, no other
+ * work on the update path — while it is off, while shutter_close == shutter_open, or while no holder has two keys that differ; a refit
+ * then leaves the scene at time shutter_open (on) or 0 (off) for good.  While it is active, hala_rt_update_batch ends its chunks on
+ * stride boundaries (the images equal those of single updates bit for bit), frames of one step overlap on the two frame slots as
+ * always and frames of different steps do not, and an update whose step interpolates a position that is not finite fails with
+ * "Vertex position is not finite.": nothing is rendered, the vertices and the tree are back at the previous step, the frame counter
+ * stands.  Frames past max_frames take no step.  Ray batches, hala_rt_download_bvh, hala_rt_read_vertices and hala_rt_get_packed_*
+ * see the scene at the step it stands at.  Refused, changing nothing: a NaN, shutter_open < 0, shutter_close > 1 or shutter_open >
+ * shutter_close; time_stride outside 1 ... 65536; a reserved word that is not 0; temporal reprojection or adaptive sampling on (and
+ * hala_rt_set_temporal / hala_rt_set_adaptive_sampling are refused while the shutter is on). */
+int hala_rt_set_shutter(hala_rt_renderer* r, const hala_shutter_params* p);
+/* the shutter and the step as the last hala_rt_refit and the updates since left them */
+int hala_rt_get_shutter_status(hala_rt_renderer* r, hala_shutter_status* out);
+/* Keys of a node's local transform (column-major 4 x 4, as hala_rt_update_node_transform takes it): any node of the committed scene,
+ * so cameras and lights move too.  Both NULL clears the keys.  Takes effect at the next hala_rt_refit.  Setting keys makes the node's
+ * local transform the open key; clearing leaves it there.  While a node has keys, hala_rt_update_node_transform on it is refused.
+ * Refused, changing nothing: the node does not exist; one key NULL and one not; an entry that is not finite. */
+int hala_rt_set_node_keys(hala_rt_renderer* r, uint32_t node_index, const float open[16], const float close[16]);
+/* Keys of a deformer's pose: morph weights and / or joint matrices as hala_rt_update_deformer takes them, each part given for both
+ * keys or for neither (that part then keeps the recorded pose at both ends); everything NULL clears the keys.  Takes effect at the
+ * next hala_rt_refit.  Setting keys makes the open pose pending; clearing leaves it there.  Every weight and palette entry is
+ * interpolated on the host, then k_deform poses the primitive from the rest pose as always.  While the keys are set,
+ * hala_rt_update_deformer on the primitive is refused (and hala_rt_set_deformer / hala_rt_clear_deformer until a refit applied the
+ * clearing).  Refused, changing nothing: the primitive has no deformer; one key of a part NULL and one not; weight_count differs
+ * from the registered target_count or joint_count from the registered joint_count; a weight or matrix entry that is not finite. */
+int hala_rt_set_deformer_keys(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, const float* weights_open,
+                              const float* weights_close, uint32_t weight_count, const float* palette_open, const float* palette_close,
+                              uint32_t joint_count);
+/* Keys of a primitive's vertices, for a primitive without a deformer: position, normal and tangent are interpolated on the device
+ * (k_shutter_lerp), tex_coord is the open key's.  Both keys are copied to the device before the call returns and stay there, 88 B
+ * per vertex.  Both NULL clears the keys.  Takes effect at the next hala_rt_refit.  Setting keys acts as
+ * hala_rt_update_vertices(open); clearing leaves the vertices there.  While the keys are set, hala_rt_update_vertices and
+ * hala_rt_set_deformer on the primitive are refused.  Refused, changing nothing: the mesh or primitive does not exist; the primitive
+ * has a deformer; one key NULL and one not; vertex_count differs from the primitive's; a position that is not finite.  Finite keys
+ * can still overflow in between: hala_rt_refit (at step 0) or the update that takes the step then fails with "Vertex position is not
+ * finite." and the vertices stay exactly as they were. */
+int hala_rt_set_vertex_keys(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, const hala_vertex* open,
+                            const hala_vertex* close, uint32_t vertex_count);
+
+/* ------------------------------------------------------------------------------------------------
  * Denoising (docs/RENDER_SPEC.md 10; no reference equivalent): an edge-avoiding a-trous wavelet filter over the running
  * means, guided by the first-hit albedo and normal AOVs.  Opt-in: nothing is allocated for a renderer that never denoises.
  * ---------------------------------------------------------------------------------------------- */

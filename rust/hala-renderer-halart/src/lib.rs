@@ -73,6 +73,11 @@ pub mod sys {
   /// hala_temporal_clamp_params (include/halart.h, docs/RENDER_SPEC.md 16 "History clamp"; 16 B): fill it with hala_temporal_clamp_default_params
   #[repr(C)] #[derive(Default, Clone, Copy)]
   pub struct hala_temporal_clamp_params { pub radius: u32, pub gamma: f32, pub reserved: [u32; 2] }
+  /// hala_shutter_params / hala_shutter_status (include/halart.h "Shutter", docs/RENDER_SPEC.md 18; 32 B each)
+  #[repr(C)] #[derive(Default, Clone, Copy)]
+  pub struct hala_shutter_params { pub shutter_open: f32, pub shutter_close: f32, pub time_stride: u32, pub reserved: [u32; 5] }
+  #[repr(C)] #[derive(Default, Clone, Copy)]
+  pub struct hala_shutter_status { pub enabled: u32, pub time_stride: u32, pub step: u32, pub time: f32, pub steps: u64, pub reserved: [u32; 2] }
   #[repr(C)] pub struct hala_scene { _private: [u8; 0] }
   #[repr(C)] pub struct hala_rtprog { _private: [u8; 0] }
   extern "C" {
@@ -143,6 +148,15 @@ pub mod sys {
     pub fn hala_rt_set_temporal_vertex_motion(r: *mut hala_rt_renderer, enable: c_int) -> c_int;
     pub fn hala_temporal_clamp_default_params(out: *mut hala_temporal_clamp_params);
     pub fn hala_rt_set_temporal_clamp(r: *mut hala_rt_renderer, p: *const hala_temporal_clamp_params) -> c_int;
+    // shutter motion blur (RENDER_SPEC 18): every setter is an edit, applied by hala_rt_refit; a NULL pair of keys clears them
+    pub fn hala_shutter_default_params(out: *mut hala_shutter_params);
+    pub fn hala_rt_set_shutter(r: *mut hala_rt_renderer, p: *const hala_shutter_params) -> c_int;
+    pub fn hala_rt_get_shutter_status(r: *mut hala_rt_renderer, out: *mut hala_shutter_status) -> c_int;
+    pub fn hala_rt_set_node_keys(r: *mut hala_rt_renderer, node_index: u32, open: *const f32, close: *const f32) -> c_int;
+    pub fn hala_rt_set_deformer_keys(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, weights_open: *const f32, weights_close: *const f32,
+                                     weight_count: u32, palette_open: *const f32, palette_close: *const f32, joint_count: u32) -> c_int;
+    pub fn hala_rt_set_vertex_keys(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, open: *const c_void, close: *const c_void,
+                                   vertex_count: u32) -> c_int;
     pub fn hala_rt_temporal_capture(r: *mut hala_rt_renderer) -> c_int;
     pub fn hala_rt_temporal_resolve(r: *mut hala_rt_renderer, gpu_ms: *mut f32) -> c_int;
     pub fn hala_rt_read_temporal(r: *mut hala_rt_renderer, which: c_int, dst_rgba32f: *mut f32) -> c_int;

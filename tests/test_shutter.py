@@ -1,0 +1,700 @@
+"""Shutter motion blur (docs/RENDER_SPEC.md 18; include/halart.h "Shutter"): keyed nodes, deformers and vertices, one time per frame of
+an accumulation, a step (the geometry part of the refit) between frames of different times.
+
+CPU tier: the time sequence, the interpolation rule, the oracle chains of tests/shutter_ref.py (a chain over static keys equals one
+render by bytes, chains over moving keys differ from it), the struct sizes and the header's contract.  GPU tier, every comparison by
+bytes: the accumulation equals the chain of one-frame oracle renders of the scene at each frame's time, on both tree forms, with one
+and two frames in flight, for node, light, camera, deformer and vertex keys; k_shutter_lerp equals the twin across wave, workgroup
+and arena edges; strides, sub-intervals, inactive shutters, the refit contract, restarts, views, tile shards, refusals, overflow and
+lifetime."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import deform_ref as D
+import scene_edits as E
+import shutter_ref as S
+import test_deformers as TD
+import test_scene_edits as SE
+from conftest import ROOT
+from hala_renderer_amd import _abi as A
+from hala_renderer_amd import scenes
+
+gpu = pytest.mark.gpu
+f32 = np.float32
+FRAMES = 4
+
+
+def cornell():
+    return SE.base_of("cornell")
+
+
+# ---- the keys of the issue, on the Cornell base ---------------------------------------------------------------------------------------------
+def node_keys(edit):
+    """every node operation of a scene edit as keys: the node's own matrix open, the edit's matrix close"""
+    s = cornell().scene
+    fwd, _ = E.edit_ops(edit, s)
+    return S.Keys(nodes={op[1]: (np.asarray(s.nodes[op[1]].local_transform, dtype=f32).copy(), op[2]) for op in fwd})
+
+
+def deformer_keys():
+    """poses 1 -> 2 of tests/test_deformers.py on both blocks"""
+    p1, p2 = TD.cornell_pose(1), TD.cornell_pose(2)
+    return S.Keys(deformers={mesh: (rig, p1[mesh], p2[mesh]) for mesh, rig in TD.cornell_rigs().items()})
+
+
+def vertex_keys():
+    """E4: the shared mesh's vertices open, the deformed ones close"""
+    fwd, inv = E.edit_ops("E4-deform-shared", cornell().scene)
+    return S.Keys(vertices={(fwd[0][1], fwd[0][2]): (inv[0][3], fwd[0][3])})
+
+
+KEYS = {"E1": lambda: node_keys("E1-move-mesh-node"), "E2": lambda: node_keys("E2-move-lights"), "E3": lambda: node_keys("E3-move-camera-1"),
+        "deformers": deformer_keys, "E4": vertex_keys, "none": S.Keys}
+_CHAINS = {}
+
+
+def render_one(oracle):
+    return lambda scene, k, images: SE.oracle_images(oracle, cornell(), scene, 1, first_frame=k, images=images)
+
+
+def chain_of(oracle, name, frames=FRAMES, two_level=False, camera=0, **shutter):
+    """the chain's images, rendered once per case and shared (inside SE.tree_form when two_level); a copy, so that no test changes it"""
+    key = (name, frames, two_level, camera, tuple(sorted(shutter.items())))
+    if key not in _CHAINS:
+        _CHAINS[key] = S.chain(render_one(oracle), cornell().scene, KEYS[name](), frames, camera=camera, **shutter)
+    return [i.copy() for i in _CHAINS[key]]
+
+
+def static_of(oracle, frames=FRAMES, two_level=False):
+    key = ("static", frames, two_level)
+    if key not in _CHAINS:
+        _CHAINS[key] = SE.oracle_images(oracle, cornell(), cornell().scene, frames)
+    return [i.copy() for i in _CHAINS[key]]
+
+
+def changed_pixels(a, b):
+    return int(np.any(a[0] != b[0], axis=-1).sum())
+
+
+# ---- CPU tier -----------------------------------------------------------------------------------------------------------------------------
+def test_time_sequence():
+    assert [float(S.step_time(j)) for j in range(8)] == [0.0, 0.5, 0.25, 0.75, 0.125, 0.625, 0.375, 0.875]
+    assert all(S.step_time(j).dtype == f32 for j in range(8))
+    t = np.array([S.step_time(j, 0.25, 0.75) for j in range(4096)])
+    assert t.dtype == f32 and (t >= f32(0.25)).all() and (t < f32(0.75)).all()
+    assert len(set(t.tolist())) == 4096  # every prefix of 2^m steps is stratified: here all distinct
+    assert [float(S.frame_time(k, stride=3)) for k in range(9)] == [0.0] * 3 + [0.5] * 3 + [0.25] * 3
+    assert S.step_time(2 ** 24 + 1) == S.step_time(1) == f32(0.5)  # 24 bits of the radical inverse
+    assert S.frame_step(7, 2) == 3
+
+
+def test_interpolation_rule():
+    a = np.array([-0.0, 0.0, 1.5, -3.25e-40, np.float32(3e38), 7.0], dtype=f32)
+    for tau in (0.0, 0.375, 0.999):
+        assert S.mix(a, a.copy(), tau).tobytes() == a.tobytes(), tau  # equal keys come back by bytes, -0.0 and denormals included
+    b = np.array([1.0, -2.0, 1.5, 4.0, 1e38, -7.0], dtype=f32)
+    m0 = S.mix(a, b, 0.0)
+    assert np.array_equal(m0, a)  # unequal keys at tau = 0 give the open key (by value: -0.0 + 0.0 is +0.0)
+    assert m0[2:3].tobytes() == a[2:3].tobytes()
+    m = S.mix(a, b, 0.5)
+    assert m.dtype == f32 and float(m[1]) == -1.0 and float(m[5]) == 0.0 and float(m[2]) == 1.5
+    v0 = D.strip(9, seed=1)[1]
+    v1 = v0.copy(); v1["position"] += f32(1.0); v1["tex_coord"] += f32(0.5)
+    vt = S.vertices_at(v0, v1, 0.25)
+    assert vt["tex_coord"].tobytes() == v0["tex_coord"].tobytes() and np.array_equal(vt["position"], v0["position"] + f32(0.25) * (v1["position"] - v0["position"]))
+    assert vt["normal"].tobytes() == v0["normal"].tobytes()
+
+
+def test_chain_over_static_keys_equals_one_render(oracle):
+    s = cornell().scene
+    k = E.shared_node(s)
+    m = np.asarray(s.nodes[k].local_transform, dtype=f32)
+    v = s.meshes[1].primitives[0].vertices
+    keys = S.Keys(nodes={k: (m, m.copy())}, vertices={(1, 0): (v, v.copy())})
+    got = S.chain(render_one(oracle), s, keys, FRAMES)
+    want = static_of(oracle)
+    for i in range(4):
+        assert got[i].tobytes() == want[i].tobytes(), i
+    off = S.chain(render_one(oracle), s, KEYS["E1"](), FRAMES, on=False)
+    for i in range(4):
+        assert off[i].tobytes() == want[i].tobytes(), i
+
+
+@pytest.mark.parametrize("name", ["E1", "deformers", "E4"])
+def test_chain_over_moving_keys_differs_from_the_static_frame(oracle, name):
+    """more than 100 pixels: a condition, not a measurement (518 / 1070 / 732 are seen here)"""
+    n = changed_pixels(chain_of(oracle, name), static_of(oracle))
+    print(f"{name}: {n} of {E.W * E.H_} pixels differ from the static frame")
+    assert n > 100, (name, n)
+
+
+def test_chain_of_the_deformer_keys_differs_on_the_two_level_tree_too(oracle):
+    with SE.tree_form(oracle, True):
+        n = changed_pixels(chain_of(oracle, "deformers", two_level=True), static_of(oracle, two_level=True))
+    assert n > 100, n
+
+
+def test_struct_sizes_and_exports():
+    assert C.sizeof(A.ShutterParams) == 32 and C.sizeof(A.ShutterStatus) == 32
+    for fn in ("hala_shutter_default_params", "hala_rt_set_shutter", "hala_rt_get_shutter_status", "hala_rt_set_node_keys",
+               "hala_rt_set_deformer_keys", "hala_rt_set_vertex_keys"):
+        assert fn in A.EXPORTS and fn in A.PROTOTYPES, fn
+    text = open(os.path.join(ROOT, "include", "halart.h")).read()
+    for name in ("hala_shutter_params", "hala_shutter_status"):
+        assert re.search(r"\} " + name + r";\s*/\* 32 B \*/", text), name
+
+
+def test_header_states_the_contract():
+    text = open(os.path.join(ROOT, "include", "halart.h")).read()
+
+    def comment_of(fn):
+        m = re.search(r"/\*((?:(?!\*/).)*)\*/\s*int " + fn + r"\(", text, flags=re.S)
+        assert m, fn
+        return re.sub(r"\s*\n \*\s*", " ", m.group(1))
+
+    for fn, words in (
+            ("hala_rt_set_shutter", ("Takes effect at the next hala_rt_refit", "NULL turns it off", "inactive", "stride boundaries", "Vertex position is not finite.",
+                                     "frame counter stands", "Frames past max_frames take no step", "see the scene at the step it stands at", "a NaN",
+                                     "time_stride outside", "reserved word", "temporal reprojection or adaptive sampling on")),
+            ("hala_rt_set_node_keys", ("Takes effect at the next hala_rt_refit", "Both NULL clears the keys", "the open key", "hala_rt_update_node_transform on it is refused",
+                                       "one key NULL and one not", "not finite")),
+            ("hala_rt_set_deformer_keys", ("Takes effect at the next hala_rt_refit", "makes the open pose pending", "hala_rt_update_deformer on the primitive is refused",
+                                           "has no deformer", "differs from the registered target_count", "not finite")),
+            ("hala_rt_set_vertex_keys", ("Takes effect at the next hala_rt_refit", "88 B per vertex", "acts as hala_rt_update_vertices(open)",
+                                         "hala_rt_update_vertices and hala_rt_set_deformer on the primitive are refused", "has a deformer", "vertex_count differs",
+                                         "not finite"))):
+        c = comment_of(fn)
+        for w in words:
+            assert w in c, (fn, w)
+    assert "hala_rt_set_scene drops every key and the shutter; hala_rt_commit keeps them" in re.sub(r"\s*\n \*\s*", " ", text)
+
+
+# ---- GPU tier -----------------------------------------------------------------------------------------------------------------------------
+def keyed(halart, name, build=None, shutter=None, shard=None, refit=True):
+    """a Cornell renderer with the keys of `name` recorded (deformers registered first) and the shutter set"""
+    r = SE.make(halart, cornell(), build=build, shard=shard)
+    keys = KEYS[name]()
+    if keys.deformers:
+        TD.register(r)
+    S.apply_keys(r, keys)
+    if shutter is not None:
+        r.set_shutter(**shutter)
+    if refit:
+        r.refit()
+    return r
+
+
+def status(r):
+    st = r.shutter_status()
+    return (st.enabled, st.time_stride, st.step, st.time, st.steps)
+
+
+def check_scene(oracle, r, scene, what):
+    """tree and ray batches against the oracle's scene"""
+    base = cornell()
+    osc = oracle.OracleScene(scene, envmap=base.env)
+    try:
+        assert SE.validate_tree(oracle, osc, r) == 0, what
+        rays = SE.rays_of(osc, base)
+        for mode in (0, 1):
+            assert r.trace_rays_host(rays, mode).tobytes() == osc.trace(rays, mode).tobytes(), (what, mode)
+    finally:
+        osc.close()
+
+
+TREE = pytest.mark.parametrize("two_level", [False, True], ids=["one_level", "two_level"])
+
+
+@gpu
+@TREE
+@pytest.mark.parametrize("in_flight", [1, 2])
+def test_node_keys(halart, oracle, two_level, in_flight):
+    """1: E1's matrix as the close key of the shared node (instanced on the two-level tree)"""
+    with SE.tree_form(oracle, two_level) as build:
+        r = keyed(halart, "E1", build=build, shutter={}, refit=False)
+        try:
+            r.set_frames_in_flight(in_flight)
+            r.refit()
+            assert status(r) == (1, 1, 0, 0.0, 0)
+            r.update_batch(3); r.update(); r.render()
+            SE.assert_images(r, chain_of(oracle, "E1", two_level=two_level), f"node keys, two_level={two_level}, in flight {in_flight}")
+            assert r.statistics().total_frames == 4
+            assert status(r) == (1, 1, 3, 0.75, 3)
+            check_scene(oracle, r, S.scene_at(cornell().scene, KEYS["E1"](), 0.75), "the scene at step 3")
+        finally:
+            r.close()
+
+
+@gpu
+def test_light_keys(halart, oracle):
+    """2: the light nodes carry E2"""
+    r = keyed(halart, "E2", shutter={})
+    try:
+        r.update_batch(FRAMES)
+        SE.assert_images(r, chain_of(oracle, "E2"), "light keys")
+        assert changed_pixels(chain_of(oracle, "E2"), static_of(oracle)) > 100
+    finally:
+        r.close()
+
+
+@gpu
+def test_camera_keys(halart, oracle):
+    """2: camera 1's node carries E3, rendered through set_views([1]); the reference swaps the cameras as tests/test_views.py does"""
+    r = keyed(halart, "E3", shutter={}, refit=False)
+    try:
+        r.set_views([1])
+        r.refit()
+        r.update_batch(2); r.update(); r.update()
+        want = chain_of(oracle, "E3", camera=1)
+        SE.assert_images(r, want, "camera keys")
+        still = SE.oracle_images(oracle, cornell(), scenes.swap_cameras(cornell().scene, 1), FRAMES)
+        assert changed_pixels(want, still) > 100
+    finally:
+        r.close()
+
+
+@gpu
+@TREE
+def test_deformer_keys(halart, oracle, two_level):
+    """3: poses 1 -> 2 on both blocks; the parameters are interpolated, then k_deform poses from the rest pose"""
+    with SE.tree_form(oracle, two_level) as build:
+        r = keyed(halart, "deformers", build=build, shutter={})
+        try:
+            r.update_batch(3); r.update()
+            SE.assert_images(r, chain_of(oracle, "deformers", two_level=two_level), f"deformer keys, two_level={two_level}")
+            assert status(r)[2:] == (3, 0.75, 3)
+            at = S.scene_at(cornell().scene, KEYS["deformers"](), 0.75)
+            for mesh in (TD.TALL, TD.SHORT):
+                assert r.read_vertices(mesh, 0).tobytes() == at.meshes[mesh].primitives[0].vertices.tobytes(), mesh
+            check_scene(oracle, r, at, "the scene at step 3")
+        finally:
+            r.close()
+
+
+@gpu
+@TREE
+def test_vertex_keys(halart, oracle, two_level):
+    """4: E4 on the shared mesh (one object-space tree on the two-level form)"""
+    with SE.tree_form(oracle, two_level) as build:
+        r = keyed(halart, "E4", build=build, shutter={})
+        try:
+            r.update_batch(3); r.update()
+            SE.assert_images(r, chain_of(oracle, "E4", two_level=two_level), f"vertex keys, two_level={two_level}")
+            assert status(r)[2:] == (3, 0.75, 3)
+            check_scene(oracle, r, S.scene_at(cornell().scene, KEYS["E4"](), 0.75), "the scene at step 3")
+        finally:
+            r.close()
+
+
+def strip_keys(nv):
+    """the strip as the open key; a close key that moves most floats, keeps some equal (one of them -0.0) and has other tex_coords"""
+    _, v0 = D.strip(nv, seed=nv)
+    rs = np.random.RandomState(nv)
+    v0 = v0.copy()
+    v0["normal"][0, 0] = f32(-0.0)
+    v1 = v0.copy()
+    for name, amp in (("position", 0.7), ("normal", 0.3), ("tangent", 0.3)):
+        d = (rs.normal(size=(nv, 3)) * amp).astype(f32)
+        d[rs.uniform(size=d.shape) < 0.25] = 0.0
+        v1[name] = v0[name] + d
+    v1["normal"][0, 0] = f32(-0.0)
+    v1["tex_coord"] = rs.uniform(0.0, 1.0, (nv, 2)).astype(f32)
+    return v0, v1
+
+
+@gpu
+@pytest.mark.parametrize("nv", [1, 63, 64, 65, 255, 256, 257, 1000])
+def test_kernel_equals_the_twin(halart, nv):
+    """4b: k_shutter_lerp alone, on strip primitives between two neighbours in the arena: read_vertices equals the twin at 0.375 after
+    the refit and at tau_1 after update_batch(2); tex_coord is the open key's; the neighbours come back untouched"""
+    scene = TD.strip_scene(nv, neighbours=True, seed=nv)
+    v0, v1 = strip_keys(nv)
+    scene.meshes[3].primitives[1].vertices = v0.copy()
+    r = SE.make(halart, cornell(), scene=scene)
+    try:
+        r.set_vertex_keys(3, 1, v0, v1)
+        r.set_shutter(0.375, 1.0)
+        r.refit()
+        want = S.vertices_at(v0, v1, 0.375)
+        got = r.read_vertices(3, 1)
+        assert got.tobytes() == want.tobytes(), f"V={nv} at step 0: {int((got.view(np.uint32) != want.view(np.uint32)).sum())} words differ"
+        r.update_batch(2)
+        tau = S.step_time(1, 0.375, 1.0)
+        assert float(tau) == 0.6875
+        want = S.vertices_at(v0, v1, tau)
+        got = r.read_vertices(3, 1)
+        assert got.tobytes() == want.tobytes(), f"V={nv} at step 1: {int((got.view(np.uint32) != want.view(np.uint32)).sum())} words differ"
+        assert got["tex_coord"].tobytes() == v0["tex_coord"].tobytes() != v1["tex_coord"].tobytes()
+        assert want["position"].tobytes() != v0["position"].tobytes()
+        assert status(r) == (1, 1, 1, 0.6875, 1)
+        for p in (0, 2):
+            assert r.read_vertices(3, p).tobytes() == scene.meshes[3].primitives[p].vertices.tobytes(), ("neighbour", p)
+    finally:
+        r.close()
+
+
+@gpu
+def test_stride_two_five_frames(halart, oracle):
+    """5: update_batch(5) equals five update() calls by bytes and equals the chain.  Frames 0-4 use three steps (0, 0, 1, 1, 2): the
+    refit leaves the scene at step 0, so the status counts two steps performed and stands at step 2"""
+    want = chain_of(oracle, "E1", frames=5, stride=2)
+    a = keyed(halart, "E1", shutter=dict(time_stride=2))
+    b = keyed(halart, "E1", shutter=dict(time_stride=2))
+    try:
+        a.update_batch(5)
+        for _ in range(5):
+            b.update()
+        for k in range(4):
+            SE.assert_same(a.read_image(k), b.read_image(k), f"batch against single updates, image {k}")
+        SE.assert_images(a, want, "stride 2")
+        for r in (a, b):
+            assert status(r) == (1, 2, 2, 0.25, 2)
+            assert r.statistics().total_frames == 5
+    finally:
+        a.close(); b.close()
+
+
+@gpu
+def test_sub_interval(halart, oracle):
+    """6: shutter (0.25, 0.75)"""
+    r = keyed(halart, "E1", shutter=dict(open=0.25, close=0.75))
+    try:
+        assert status(r) == (1, 1, 0, 0.25, 0)
+        r.update(); r.update_batch(3)
+        SE.assert_images(r, chain_of(oracle, "E1", open=0.25, close=0.75), "shutter (0.25, 0.75)")
+        assert status(r) == (1, 1, 3, 0.625, 3)
+    finally:
+        r.close()
+
+
+@gpu
+@pytest.mark.parametrize("case", ["static-keys", "no-keys", "closed-interval"])
+def test_inactive_shutter_is_the_renderer_without_the_feature(halart, oracle, case):
+    """7: static keys (open == close) under shutter (0, 1), a shutter on with no key at all, and static keys under a shutter whose
+    interval is empty: the bytes of the renderer without the feature, and zero steps"""
+    s = cornell().scene
+    r = SE.make(halart, cornell())
+    try:
+        if case != "no-keys":
+            k = E.shared_node(s)
+            m = np.asarray(s.nodes[k].local_transform, dtype=f32)
+            v = s.meshes[1].primitives[0].vertices
+            r.set_node_keys(k, m, m.copy())
+            r.set_vertex_keys(1, 0, v, v.copy())
+        r.set_shutter(0.5, 0.5) if case == "closed-interval" else r.set_shutter()
+        r.refit()
+        r.update_batch(3); r.update()
+        SE.assert_images(r, static_of(oracle), case)
+        assert r.shutter_status().steps == 0 and r.shutter_status().enabled == 1
+    finally:
+        r.close()
+
+
+@gpu
+def test_keys_take_effect_at_the_refit(halart, oracle):
+    """8: keys and shutter set but no refit: two more updates continue the old accumulation and equal the oracle's static frames;
+    then the refit applies the keys"""
+    r = SE.make(halart, cornell())
+    try:
+        r.update_batch(2)
+        S.apply_keys(r, KEYS["E1"]()); S.apply_keys(r, KEYS["E4"]())
+        r.set_shutter()
+        r.update(); r.update()
+        SE.assert_images(r, static_of(oracle), "before the refit")
+        assert r.statistics().total_frames == 4 and status(r) == (0, 1, S.NO_STEP, 0.0, 0)
+        r.refit()
+        r.update_batch(FRAMES)
+        both = S.Keys(nodes=KEYS["E1"]().nodes, vertices=KEYS["E4"]().vertices)
+        SE.assert_images(r, S.chain(render_one(oracle), cornell().scene, both, FRAMES), "after the refit")
+        assert status(r) == (1, 1, 3, 0.75, 3)
+    finally:
+        r.close()
+
+
+@gpu
+def test_restart_steps_back_to_step_0(halart, oracle):
+    """9: reset_accumulation after three frames, then four frames: the chain from frame 0"""
+    r = keyed(halart, "E1", shutter={})
+    try:
+        r.update_batch(3)
+        assert status(r)[2:] == (2, 0.25, 2)
+        r.reset_accumulation()
+        r.update(); r.update_batch(3)
+        SE.assert_images(r, chain_of(oracle, "E1"), "after the restart")
+        assert status(r)[2:] == (3, 0.75, 6) and r.statistics().total_frames == 4
+    finally:
+        r.close()
+
+
+@gpu
+def test_views(halart, oracle):
+    """10: views [2, 0, 1] with node keys on a mesh: each view equals its own chain"""
+    r = keyed(halart, "E1", shutter={}, refit=False)
+    try:
+        r.set_views(SE.VIEWS)
+        r.refit()
+        r.update_batch(FRAMES)
+        for v, c in enumerate(SE.VIEWS):
+            SE.assert_images(r, chain_of(oracle, "E1", camera=c), f"view {v}", view=v)
+    finally:
+        r.close()
+
+
+@gpu
+def test_two_tile_shards(halart, oracle):
+    """11: two emulated ranks of tile size 16 take the same steps; the gathered frame equals the chain"""
+    import torch
+
+    import hala_renderer_amd.dist  # noqa: F401  (halart.dist._DeviceView)
+    world, ts = 2, 16
+    parts = {k: [] for k in range(3)}
+    last = None
+    try:
+        for rank in range(world):
+            r = keyed(halart, "E1", shutter={}, shard=(rank, world, ts))
+            if last is not None:
+                last.close()
+            last = r
+            r.update_batch(FRAMES); r.render(); r.wait_idle()
+            assert status(r) == (1, 1, 3, 0.75, 3)
+            for k in range(3):
+                ptr, nbytes = r.tile_buffer(k)
+                t = torch.as_tensor(halart.dist._DeviceView(ptr, nbytes // 4), device="cuda:0").clone()
+                torch.cuda.synchronize()
+                parts[k].append(t)
+        want = chain_of(oracle, "E1")
+        for k in range(3):
+            g = torch.cat(parts[k]).contiguous()
+            torch.cuda.synchronize()
+            last.scatter_gathered_tiles(k, g.data_ptr(), g.numel() * 4)
+            SE.assert_same(last.read_image(k), want[k], f"gathered image {k}")
+    finally:
+        if last is not None:
+            last.close()
+
+
+@gpu
+def test_refusals_change_nothing(halart, oracle):
+    """12: every refused call leaves images, tree bytes and status as they were"""
+    s = cornell().scene
+    keys = KEYS["E1"]()
+    node, (m0, m1) = next(iter(keys.nodes.items()))
+    (vm, vp), (v0, v1) = next(iter(KEYS["E4"]().vertices.items()))
+    p1, p2 = TD.cornell_pose(1), TD.cornell_pose(2)
+    r = SE.make(halart, cornell())
+    try:
+        TD.register(r, meshes=(TD.TALL,))
+        r.set_node_keys(node, m0, m1)
+        r.set_vertex_keys(vm, vp, v0, v1)
+        r.set_deformer_keys(TD.TALL, 0, open=p1[TD.TALL], close=p2[TD.TALL])
+        r.set_shutter()
+        r.refit()
+        r.update_batch(3)
+        before = ([r.read_image(k).tobytes() for k in range(4)], [x.tobytes() for x in r.download_bvh()], status(r))
+        P = A.ShutterParams
+
+        def raw_shutter(o, c, stride, reserved=0):
+            p = P(); p.shutter_open, p.shutter_close, p.time_stride = o, c, stride
+            p.reserved[2] = reserved
+            r._check(r._lib.hala_rt_set_shutter(r._h, C.byref(p)))
+
+        def bad(a, where, value):
+            b = np.array(a, copy=True)
+            b[where] = value
+            return b
+
+        vnan = v1.copy(); vnan["position"][2, 1] = np.nan
+        wbad = dict(p2[TD.TALL]); wbad["morph_weights"] = bad(p2[TD.TALL]["morph_weights"], 0, np.inf)
+        short = dict(p2[TD.TALL]); short["morph_weights"] = p2[TD.TALL]["morph_weights"][:-1]
+        short1 = dict(p1[TD.TALL]); short1["morph_weights"] = p1[TD.TALL]["morph_weights"][:-1]
+        fp = C.POINTER(C.c_float)
+        mat = (C.c_float * 16)(*np.eye(4, dtype=f32).reshape(-1).tolist())
+        refusals = [
+            (lambda: raw_shutter(float("nan"), 1.0, 1), "shutter interval"), (lambda: raw_shutter(0.0, float("nan"), 1), "shutter interval"),
+            (lambda: raw_shutter(0.75, 0.25, 1), "shutter interval"), (lambda: raw_shutter(-0.125, 1.0, 1), "shutter interval"),
+            (lambda: raw_shutter(0.0, 1.5, 1), "shutter interval"), (lambda: raw_shutter(0.0, 1.0, 0), "time_stride"),
+            (lambda: raw_shutter(0.0, 1.0, 65537), "time_stride"), (lambda: raw_shutter(0.0, 1.0, 1, reserved=1), "reserved"),
+            (lambda: r.set_node_keys(len(s.nodes), m0, m1), "node does not exist"),
+            (lambda: r.set_node_keys(node, m0, None), "both"), (lambda: r.set_node_keys(node, None, m1), "both"),
+            (lambda: r._check(r._lib.hala_rt_set_node_keys(r._h, 0, C.cast(mat, fp), None)), "both"),
+            (lambda: r.set_node_keys(node, m0, bad(m1, (1, 2), np.nan)), "finite"), (lambda: r.set_node_keys(0, bad(m0, (0, 3), np.inf), m1), "finite"),
+            (lambda: r.set_deformer_keys(TD.TALL, 0, open=p1[TD.TALL], close=wbad), "finite"),
+            (lambda: r.set_deformer_keys(TD.TALL, 0, open=short1, close=short), "weight count"),
+            (lambda: r.set_deformer_keys(TD.SHORT, 0, open=p1[TD.SHORT], close=p2[TD.SHORT]), "no deformer"),
+            (lambda: r.set_vertex_keys(vm, vp, v0, vnan), "finite"), (lambda: r.set_vertex_keys(vm, vp, v0[:-1], v1[:-1]), "count"),
+            (lambda: r.set_vertex_keys(vm, vp, v0, None), "both"), (lambda: r.set_vertex_keys(len(s.meshes), 0, v0, v1), "mesh"),
+            (lambda: r.set_vertex_keys(TD.TALL, 0, s.meshes[TD.TALL].primitives[0].vertices, s.meshes[TD.TALL].primitives[0].vertices), "has a deformer"),
+            (lambda: r.set_deformer(vm, vp, **TD.cornell_rigs()[TD.SHORT]), "vertex keys"),
+            (lambda: r.update_node_transform(node, m1), "shutter keys"), (lambda: r.update_deformer(TD.TALL, 0, **p1[TD.TALL]), "shutter keys"),
+            (lambda: r.update_vertices(vm, vp, v1), "shutter keys"),
+            (lambda: r.set_temporal(), "shutter"), (lambda: r.set_adaptive_sampling(0.01), "shutter"),
+        ]
+        for call, word in refusals:
+            with pytest.raises(halart.HalaRendererError, match=word):
+                call()
+            assert status(r) == before[2], word
+        assert [r.read_image(k).tobytes() for k in range(4)] == before[0]
+        assert [x.tobytes() for x in r.download_bvh()] == before[1]
+        # nothing was recorded either: a refit gives the same accumulation again
+        r.refit()
+        r.update_batch(3)
+        assert ([r.read_image(k).tobytes() for k in range(4)], [x.tobytes() for x in r.download_bvh()]) == before[:2]
+        assert status(r) == before[2][:4] + (4,)
+    finally:
+        r.close()
+    # the other order: temporal reprojection or adaptive sampling first, then the shutter
+    for first in ("temporal", "adaptive"):
+        r = SE.make(halart, cornell())
+        try:
+            if first == "temporal":
+                r.set_aovs(True, True)
+                r.set_temporal()
+            else:
+                r.set_adaptive_sampling(0.01)
+            r.update_batch(2)
+            img = r.read_image(0).tobytes()
+            with pytest.raises(halart.HalaRendererError, match=first):
+                r.set_shutter()
+            assert status(r) == (0, 1, S.NO_STEP, 0.0, 0) and r.read_image(0).tobytes() == img
+        finally:
+            r.close()
+
+
+@gpu
+def test_overflow(halart, oracle):
+    """13: finite keys whose interpolation is not finite.  Vertex keys of +-3e38 on one vertex: b - a is infinite, so every time gives a
+    position that is not finite, step 0 included (0 * inf is NaN): no update can be the first to meet it, and the refit that would apply
+    the keys fails with the stated message and changes nothing; clearing the keys, then refit, then update, succeeds.  Deformer keys whose close weight is 3e38 are finite at time 0 and
+    overflow at time 0.5: the UPDATE fails, total_frames stands, read_vertices returns the previous step's bytes.  Host-checked failure
+    paths: nothing on the device faults"""
+    s = cornell().scene
+    (vm, vp), (v0, v1) = next(iter(KEYS["E4"]().vertices.items()))
+    r = keyed(halart, "E4", shutter={})
+    try:
+        r.update_batch(2)
+        held = r.read_vertices(vm, vp).tobytes()
+        tree = [x.tobytes() for x in r.download_bvh()]
+        assert held == S.vertices_at(v0, v1, 0.5).tobytes()
+        lo, hi = v0.copy(), v1.copy()
+        lo["position"][5, 0], hi["position"][5, 0] = f32(3e38), f32(-3e38)
+        r.set_vertex_keys(vm, vp, None, None)
+        r.set_vertex_keys(vm, vp, lo, hi)
+        with pytest.raises(halart.HalaRendererError, match="Vertex position is not finite."):
+            r.refit()
+        assert r.statistics().total_frames == 2 and status(r)[2:] == (1, 0.5, 1)
+        assert r.read_vertices(vm, vp).tobytes() == held and [x.tobytes() for x in r.download_bvh()] == tree
+        r.update()  # the old keys still move the scene: step 1 -> frame 2's step
+        assert r.statistics().total_frames == 3 and r.read_vertices(vm, vp).tobytes() == S.vertices_at(v0, v1, 0.25).tobytes()
+        r.set_vertex_keys(vm, vp, None, None)  # clearing leaves the vertices at the open key (3e38): put the mesh back as well
+        r.update_vertices(vm, vp, v0)
+        r.refit()
+        r.update_batch(2)
+        assert r.read_vertices(vm, vp).tobytes() == v0.tobytes()
+        assert r.statistics().total_frames == 2 and r.shutter_status().step == S.NO_STEP
+        SE.assert_images(r, static_of(oracle, 2), "after the keys were cleared")
+        # a step that overflows: the tall block's first morph weight runs from 0 to 3e38
+        TD.register(r, meshes=(TD.TALL,))
+        p0 = dict(morph_weights=np.zeros(2, f32), joint_matrices=D.identity_palette(3))
+        p1 = dict(morph_weights=np.array([3e38, 0.0], f32), joint_matrices=D.identity_palette(3))
+        r.set_deformer_keys(TD.TALL, 0, open=p0, close=p1)
+        r.refit()
+        rest = s.meshes[TD.TALL].primitives[0].vertices
+        assert r.read_vertices(TD.TALL, 0).tobytes() == D.pose_vertices(rest, TD.cornell_rigs()[TD.TALL], p0).tobytes()
+        r.update()
+        held = r.read_vertices(TD.TALL, 0).tobytes()
+        tree = [x.tobytes() for x in r.download_bvh()]
+        img = [r.read_image(k).tobytes() for k in range(4)]
+        steps = r.shutter_status().steps
+        for _ in range(2):
+            with pytest.raises(halart.HalaRendererError, match="Vertex position is not finite."):
+                r.update()
+            assert r.statistics().total_frames == 1 and status(r)[2:] == (0, 0.0, steps)
+            assert r.read_vertices(TD.TALL, 0).tobytes() == held and [x.tobytes() for x in r.download_bvh()] == tree
+            assert [r.read_image(k).tobytes() for k in range(4)] == img
+        r.set_deformer_keys(TD.TALL, 0, None, None)
+        r.refit()
+        r.update_batch(2)
+        assert r.statistics().total_frames == 2
+    finally:
+        r.close()
+
+
+@gpu
+def test_cleared_deformer_keys_leave_the_open_pose(halart, oracle):
+    """the keys of both deformers cleared while the shutter is stepping, one more update (a step, still with the applied keys), then
+    the refit: the vertices are the open pose and the frames the oracle's render of the scene posed so, not the last step's pose"""
+    s = cornell().scene
+    r = keyed(halart, "deformers", shutter={})
+    try:
+        r.update_batch(2)
+        for mesh in (TD.TALL, TD.SHORT):
+            r.set_deformer_keys(mesh, 0, None, None)
+        r.update()
+        assert r.statistics().total_frames == 3 and status(r)[2:] == (2, 0.25, 2)  # until the refit the applied keys move the scene
+        at = S.scene_at(s, KEYS["deformers"](), 0.25)
+        for mesh in (TD.TALL, TD.SHORT):
+            assert r.read_vertices(mesh, 0).tobytes() == at.meshes[mesh].primitives[0].vertices.tobytes(), mesh
+        r.refit()
+        assert r.shutter_status().step == S.NO_STEP
+        for op in TD.posed_ops(TD.cornell_pose(1)):
+            assert r.read_vertices(op[1], op[2]).tobytes() == op[3].tobytes(), op[1]
+        r.update_batch(3)
+        SE.assert_images(r, TD.posed_images(oracle, 1, 3), "the open pose after the keys were cleared")
+        assert r.shutter_status().steps == 2
+    finally:
+        r.close()
+
+
+@gpu
+def test_vertices_edited_under_an_active_shutter_then_deformed(halart):
+    """update_vertices while steps read the arena is uploaded by the refit; a deformer registered on the primitive in between is posed
+    over the new vertices, not overwritten by them"""
+    s = cornell().scene
+    rig = TD.cornell_rigs()[TD.TALL]
+    pose = TD.cornell_pose(3)[TD.TALL]
+    edited = s.meshes[TD.TALL].primitives[0].vertices.copy()
+    edited["position"][:, 1] *= f32(0.75)
+    r = keyed(halart, "E1", shutter={})
+    try:
+        r.update_batch(2)
+        before = r.read_vertices(TD.TALL, 0).tobytes()
+        r.update_vertices(TD.TALL, 0, edited)
+        r.update()
+        assert r.read_vertices(TD.TALL, 0).tobytes() == before  # waits for the refit
+        r.set_deformer(TD.TALL, 0, **rig)
+        r.update_deformer(TD.TALL, 0, **pose)
+        r.refit()
+        want = D.pose_vertices(edited, rig, pose)
+        assert want.tobytes() != edited.tobytes()
+        assert r.read_vertices(TD.TALL, 0).tobytes() == want.tobytes()
+    finally:
+        r.close()
+
+
+@gpu
+def test_lifetime(halart, oracle):
+    """14: a second commit keeps the keys and the shutter; set_scene drops them"""
+    r = keyed(halart, "E1", shutter={})
+    try:
+        r.update_batch(2)
+        r.commit()
+        assert r.shutter_status().enabled == 1
+        r.update_batch(FRAMES)
+        SE.assert_images(r, chain_of(oracle, "E1"), "after the second commit")
+        node = next(iter(KEYS["E1"]().nodes))
+        with pytest.raises(halart.HalaRendererError, match="shutter keys"):
+            r.update_node_transform(node, np.eye(4, dtype=f32))
+        r.set_scene(cornell().scene)
+        r.commit()
+        assert status(r)[:4] == (0, 1, S.NO_STEP, 0.0)
+        r.update_node_transform(node, cornell().scene.nodes[node].local_transform)  # no keys: accepted
+        r.refit()
+        r.update_batch(FRAMES)
+        SE.assert_images(r, static_of(oracle), "after set_scene")
+        assert r.shutter_status().enabled == 0
+    finally:
+        r.close()
