@@ -61,5 +61,7 @@ from .renderer import (HalaRenderer, adaptive_default_params, cryptomatte_matte,
 from .raytracing_program import (HalaRayTracingProgram, HalaRayTracingProgramDesc,  # noqa: E402,F401
                                  HalaRayTracingHitShaderDesc)
 
+from .rig import Rig, sample_clip  # noqa: E402,F401
+
 # reference: src/prelude.rs:17-18
 HalaRayTracingRenderer = HalaRenderer

@@ -233,6 +233,54 @@ class ShutterStatus(C.Structure):  # hala_shutter_status, 32 B
                 ("reserved", C.c_uint32 * 2)]
 
 
+# the rig of a glTF file (docs/RENDER_SPEC.md 19; include/halart.h "The rig of a glTF file")
+RIG_STEP, RIG_LINEAR, RIG_CUBICSPLINE = 0, 1, 2
+RIG_TRANSLATION, RIG_ROTATION, RIG_SCALE, RIG_WEIGHTS = 0, 1, 2, 3
+
+
+class RigNode(C.Structure):  # hala_rig_node, 112 B
+    _fields_ = [("parent", C.c_int32), ("is_matrix", C.c_uint32), ("local_transform", C.c_float * 16), ("translation", C.c_float * 3),
+                ("rotation", C.c_float * 4), ("scale", C.c_float * 3)]
+
+
+class RigSkin(C.Structure):  # hala_rig_skin, 24 B
+    _fields_ = [("joint_count", C.c_uint32), ("reserved", C.c_uint32), ("joints", C.POINTER(C.c_uint32)), ("inverse_bind_matrices", C.POINTER(C.c_float))]
+
+
+class RigBinding(C.Structure):  # hala_rig_binding, 88 B
+    _fields_ = [("mesh_index", C.c_uint32), ("primitive_index", C.c_uint32), ("node", C.c_uint32), ("node_count", C.c_uint32), ("skin", C.c_uint32),
+                ("vertex_count", C.c_uint32), ("influence_sets", C.c_uint32), ("target_count", C.c_uint32), ("joints", C.POINTER(C.c_uint16)),
+                ("weights", C.POINTER(C.c_float)), ("target_position_deltas", C.POINTER(C.c_float)), ("target_normal_deltas", C.POINTER(C.c_float)),
+                ("target_tangent_deltas", C.POINTER(C.c_float)), ("default_weights", C.POINTER(C.c_float)), ("weight_first", C.c_uint32),
+                ("palette_first", C.c_uint32)]
+
+
+class RigSampler(C.Structure):  # hala_rig_sampler, 32 B
+    _fields_ = [("times", C.POINTER(C.c_float)), ("values", C.POINTER(C.c_float)), ("key_count", C.c_uint32), ("interpolation", C.c_uint32),
+                ("width", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RigChannel(C.Structure):  # hala_rig_channel, 16 B
+    _fields_ = [("sampler", C.c_uint32), ("node", C.c_uint32), ("path", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RigClip(C.Structure):  # hala_rig_clip, 40 B
+    _fields_ = [("name", C.c_char_p), ("samplers", C.POINTER(RigSampler)), ("channels", C.POINTER(RigChannel)), ("sampler_count", C.c_uint32),
+                ("channel_count", C.c_uint32), ("time_first", C.c_float), ("time_last", C.c_float)]
+
+
+class RigDesc(C.Structure):  # hala_rig_desc, 72 B
+    _fields_ = [("node_count", C.c_uint32), ("gltf_node_count", C.c_uint32), ("nodes", C.POINTER(RigNode)), ("node_of_gltf", C.POINTER(C.c_uint32)),
+                ("skins", C.POINTER(RigSkin)), ("bindings", C.POINTER(RigBinding)), ("clips", C.POINTER(RigClip)), ("skin_count", C.c_uint32),
+                ("binding_count", C.c_uint32), ("clip_count", C.c_uint32), ("weight_floats", C.c_uint32), ("palette_floats", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class RigStatus(C.Structure):  # hala_rig_status, 32 B
+    _fields_ = [("bindings", C.c_uint32), ("deformers", C.c_uint32), ("pose_launches", C.c_uint64), ("segments_posed", C.c_uint64),
+                ("batch_launches", C.c_uint64)]
+
+
 # argtypes / restype of the denoise, adaptive sampling, view and AOV entry points (load_library installs them)
 PROTOTYPES = {
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
@@ -284,6 +332,14 @@ PROTOTYPES = {
     "hala_rt_set_deformer_keys": ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32,
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32], C.c_int),
     "hala_rt_set_vertex_keys": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32], C.c_int),
+    "hala_scene_get_rig": ([C.c_void_p], C.POINTER(RigDesc)),
+    "hala_rig_sample_clip": ([C.POINTER(RigDesc), C.c_uint32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_set_rig": ([C.c_void_p, C.POINTER(RigDesc)], C.c_int),
+    "hala_rt_pose_rig": ([C.c_void_p, C.c_uint32, C.c_float], C.c_int),
+    "hala_rt_key_rig": ([C.c_void_p, C.c_uint32, C.c_float, C.c_float], C.c_int),
+    "hala_rt_get_rig_pose": ([C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                              C.POINTER(C.c_float)], C.c_int),
+    "hala_rt_get_rig_status": ([C.c_void_p, C.POINTER(RigStatus)], C.c_int),
 }
 
 
@@ -331,4 +387,6 @@ EXPORTS = [
     "hala_rt_set_deformer", "hala_rt_update_deformer", "hala_rt_clear_deformer", "hala_rt_read_vertices",
     "hala_shutter_default_params", "hala_rt_set_shutter", "hala_rt_get_shutter_status", "hala_rt_set_node_keys", "hala_rt_set_deformer_keys",
     "hala_rt_set_vertex_keys",
+    "hala_scene_get_rig", "hala_rig_sample_clip", "hala_rt_set_rig", "hala_rt_pose_rig", "hala_rt_key_rig", "hala_rt_get_rig_pose",
+    "hala_rt_get_rig_status",
 ]

@@ -16,6 +16,7 @@ namespace rt {
 constexpr uint32_t kMaxMorphTargets = HALA_MAX_MORPH_TARGETS;
 constexpr uint32_t kMaxJoints = HALA_MAX_JOINTS;
 constexpr uint32_t kDeformThreads = 256;  // one lane per vertex
+constexpr size_t kDeformBatchMin = 2;     // dirty deformers from which a refit poses them all with one launch
 
 // what k_deform reads and writes of one primitive
 struct DeformTables {
@@ -37,9 +38,20 @@ struct DeformActive {
   float weight[kMaxMorphTargets];
 };
 
+// The batch form (k_deform_batch: two or more dirty deformers, one launch).  One segment per deformer, a map from workgroups to
+// segments, and the active targets of all segments packed; with the palettes they make one staged buffer, copied once.
+struct DeformActiveEntry { uint32_t index; float weight; };
+struct DeformSegment {
+  DeformTables t;                       // palette: into the staged buffer; flag: the segment's own overflow word
+  uint32_t active_first, active_count;  // into the packed active-target list
+};
+struct DeformBlock { uint32_t segment, first_vertex; };  // 8 B per workgroup
+static_assert(sizeof(DeformSegment) % 8 == 0 && sizeof(DeformBlock) == 8 && sizeof(DeformActiveEntry) == 8, "the staged sections are 8-byte records");
+
 // The registered deformer of one primitive.  `applied` is what the arena holds, `pending` what the next refit applies.
 struct Deformer {
   uint32_t prim = 0, vertex_count = 0, target_count = 0, joint_count = 0;
+  uint64_t id = 0;  // unique among the deformers of one renderer (DeformState::next_id): tells a replacement on the same primitive apart
   DeviceArray<hala_vertex> d_rest;
   DeviceArray<float> d_dp, d_dn, d_dt, d_palette;
   DeviceArray<uint2> d_joints;
@@ -53,13 +65,21 @@ struct Deformer {
 
 struct DeformState {
   std::map<uint32_t, std::unique_ptr<Deformer>> by_prim;  // key: index into HostScene::prims
-  DeviceArray<uint32_t> d_flags;                           // one overflow word per launch of a refit
+  DeviceArray<uint32_t> d_flags;                           // one overflow word per dirty deformer of a refit
+  std::vector<unsigned char> h_stage;                      // the batch launch's tables as laid out on the host, and their device copy
+  DeviceArray<unsigned char> d_stage;
+  uint64_t launches = 0, segments = 0;                     // pose launches (either kernel) and deformers they posed, since hala_rt_create
+  uint64_t batch_launches = 0;                             // those of k_deform_batch among them
+  uint64_t next_id = 0;
   bool restored = false;                                   // (deform_apply_pending: the failing refit put the arena back)
   bool lost = false;                                       // a device error interrupted a refit's launches: the arena is undefined
-  void off() { by_prim.clear(); d_flags.release(); lost = false; }
+  void off() { by_prim.clear(); d_flags.release(); d_stage.release(); lost = false; }
 };
 
 // one lane per vertex, one launch on `s`
 void launch_deform(const DeformTables& t, const DeformActive& a, hipStream_t s);
+// the same for every segment at once: device pointers, block_count workgroups, LDS for the largest palette of the launch
+void launch_deform_batch(const DeformSegment* segments, const DeformBlock* blocks, const DeformActiveEntry* active, uint32_t block_count,
+                         uint32_t max_joint_count, hipStream_t s);
 
 }  // namespace rt

@@ -1,5 +1,7 @@
 // deform.hip — docs/RENDER_SPEC.md 17: morph targets and skinning on the GPU.  k_deform poses the vertices of one primitive from its
-// rest pose into the vertex arena, just ahead of the refit that reads them: one lane per vertex, 256-thread workgroups, wave64.  Every
+// rest pose into the vertex arena, just ahead of the refit that reads them: one lane per vertex, 256-thread workgroups, wave64.
+// k_deform_batch does the same for every dirty deformer of a refit in one launch (a segment per deformer, a workgroup inside one
+// segment); both call pose_vertex, so the arithmetic is one piece of code.  Every
 // `*` and `+` is the one the spec writes, each rounded (-ffp-contract=off: no fma), so that tests/deform_ref.py reproduces the
 // vertices bit for bit.
 //
@@ -23,14 +25,18 @@ namespace rt {
 namespace {
 
 #define DF_LDS __attribute__((address_space(3)))
+// Device memory, said so: a pointer that k_deform_batch reads from its segment table is generic to the compiler, which would address it
+// with flat instructions; a kernel argument's is global already and the cast changes nothing.
+#define DF_GLOBAL __attribute__((address_space(1)))
 typedef float df_f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t df_u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr uint32_t kRecordWords = sizeof(hala_vertex) / 4;  // 11
 static_assert(sizeof(hala_vertex) == 44, "k_deform moves 11 dwords per vertex");
 
 struct Row { float x, y, z, w; };
 
-__device__ __forceinline__ void morph(float* a, const float* deltas, size_t at, float w) {
+__device__ __forceinline__ void morph(float* a, const DF_GLOBAL float* deltas, size_t at, float w) {
   // p = p + (w_t * delta) per component
   const float dx = deltas[at], dy = deltas[at + 1], dz = deltas[at + 2];
   a[0] = a[0] + (w * dx); a[1] = a[1] + (w * dy); a[2] = a[2] + (w * dz);
@@ -39,56 +45,95 @@ __device__ __forceinline__ void morph(float* a, const float* deltas, size_t at, 
 __device__ __forceinline__ float affine(const Row& m, const float* p) { return ((m.x * p[0] + m.y * p[1]) + m.z * p[2]) + m.w; }
 __device__ __forceinline__ float linear(const Row& m, const float* p) { return (m.x * p[0] + m.y * p[1]) + m.z * p[2]; }
 
+// RENDER_SPEC 17 for vertex `v` of the primitive `t` describes: the arithmetic both kernels share.  `active(i, &index, &weight)` names the
+// i-th active target (wave-uniform); `palette` is the primitive's palette in LDS.  -> whether the posed position is not finite
+template <class Active>
+__device__ __forceinline__ bool pose_vertex(const DeformTables& t, uint32_t active_count, const Active& active, DF_LDS df_f32x4* palette, uint32_t v) {
+  const uint32_t n = t.vertex_count;
+  float r[kRecordWords];  // position, normal, tangent, tex_coord
+  const DF_GLOBAL float* src = (const DF_GLOBAL float*)(t.rest + v);
+  const DF_GLOBAL float* dp = (const DF_GLOBAL float*)t.dp;
+  const DF_GLOBAL float* dn = (const DF_GLOBAL float*)t.dn;
+  const DF_GLOBAL float* dt = (const DF_GLOBAL float*)t.dt;
+  for (uint32_t k = 0; k < kRecordWords; ++k) r[k] = src[k];
+  for (uint32_t i = 0; i < active_count; ++i) {
+    uint32_t index; float w;
+    active(i, &index, &w);
+    const size_t at = ((size_t)index * n + v) * 3u;
+    morph(r, dp, at, w);
+    if (dn) morph(r + 3, dn, at, w);
+    if (dt) morph(r + 6, dt, at, w);
+  }
+  if (t.joint_count) {
+    const df_u32x2 jw = ((const DF_GLOBAL df_u32x2*)t.joints)[v];
+    const df_f32x4 w4 = ((const DF_GLOBAL df_f32x4*)t.weights)[v];
+    const uint32_t j[4] = {jw.x & 0xffffu, jw.x >> 16, jw.y & 0xffffu, jw.y >> 16};
+    const float w[4] = {w4.x, w4.y, w4.z, w4.w};
+    Row m[3] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+    for (uint32_t k = 0; k < 4; ++k)
+      for (uint32_t row = 0; row < 3; ++row) {
+        const df_f32x4 q = palette[j[k] * 3u + row];
+        m[row].x = m[row].x + (w[k] * q.x); m[row].y = m[row].y + (w[k] * q.y);
+        m[row].z = m[row].z + (w[k] * q.z); m[row].w = m[row].w + (w[k] * q.w);
+      }
+    const float p[3] = {r[0], r[1], r[2]}, nr[3] = {r[3], r[4], r[5]}, tg[3] = {r[6], r[7], r[8]};
+    for (uint32_t row = 0; row < 3; ++row) {
+      r[row] = affine(m[row], p);
+      r[3 + row] = linear(m[row], nr);
+      r[6 + row] = linear(m[row], tg);
+    }
+  }
+  DF_GLOBAL float* dst = (DF_GLOBAL float*)(t.out + v);
+  for (uint32_t k = 0; k < kRecordWords; ++k) dst[k] = r[k];
+  return !(isfinite(r[0]) && isfinite(r[1]) && isfinite(r[2]));
+}
+
+// the palette of one primitive -> LDS, once per workgroup (uniform branch: every thread of the workgroup passes the barrier or none)
+__device__ __forceinline__ void stage_palette(DF_LDS df_f32x4* palette, const float* src, uint32_t joint_count, uint32_t tid) {
+  if (!joint_count) return;
+  DF_LDS float* pal = (DF_LDS float*)palette;
+  const DF_GLOBAL float* from = (const DF_GLOBAL float*)src;
+  for (uint32_t k = tid; k < joint_count * 12u; k += kDeformThreads) pal[k] = from[k];
+  __syncthreads();
+}
+
+// one ballot per wave, one atomic only when a lane offends
+__device__ __forceinline__ void raise_flag(bool bad, uint32_t tid, uint32_t* flag) {
+  const unsigned long long offenders = __ballot(bad);
+  if (offenders && (tid & 63u) == (uint32_t)__ffsll((long long)offenders) - 1u)
+    __hip_atomic_fetch_or((DF_GLOBAL uint32_t*)flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (atomicOr, on global memory)
+}
+
 __global__ __launch_bounds__(kDeformThreads) void k_deform(const DeformTables t, const DeformActive a) {
   extern __shared__ df_f32x4 smem[];  // the palette: 48 B per joint
   DF_LDS df_f32x4* palette = (DF_LDS df_f32x4*)smem;
   const uint32_t tid = threadIdx.x;
   const uint32_t v = blockIdx.x * kDeformThreads + tid;
-  const uint32_t n = t.vertex_count;
-
-  if (t.joint_count) {  // (uniform)
-    DF_LDS float* pal = (DF_LDS float*)palette;
-    for (uint32_t k = tid; k < t.joint_count * 12u; k += kDeformThreads) pal[k] = t.palette[k];
-    __syncthreads();
-  }
-
+  stage_palette(palette, t.palette, t.joint_count, tid);
   bool bad = false;
-  if (v < n) {
-    float r[kRecordWords];  // position, normal, tangent, tex_coord
-    const float* src = reinterpret_cast<const float*>(t.rest + v);
-    for (uint32_t k = 0; k < kRecordWords; ++k) r[k] = src[k];
-    for (uint32_t i = 0; i < a.count; ++i) {
-      const size_t at = ((size_t)a.index[i] * n + v) * 3u;
-      const float w = a.weight[i];
-      morph(r, t.dp, at, w);
-      if (t.dn) morph(r + 3, t.dn, at, w);
-      if (t.dt) morph(r + 6, t.dt, at, w);
-    }
-    if (t.joint_count) {
-      const uint2 jw = t.joints[v];
-      const float4 w4 = t.weights[v];
-      const uint32_t j[4] = {jw.x & 0xffffu, jw.x >> 16, jw.y & 0xffffu, jw.y >> 16};
-      const float w[4] = {w4.x, w4.y, w4.z, w4.w};
-      Row m[3] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
-      for (uint32_t k = 0; k < 4; ++k)
-        for (uint32_t row = 0; row < 3; ++row) {
-          const df_f32x4 q = palette[j[k] * 3u + row];
-          m[row].x = m[row].x + (w[k] * q.x); m[row].y = m[row].y + (w[k] * q.y);
-          m[row].z = m[row].z + (w[k] * q.z); m[row].w = m[row].w + (w[k] * q.w);
-        }
-      const float p[3] = {r[0], r[1], r[2]}, nr[3] = {r[3], r[4], r[5]}, tg[3] = {r[6], r[7], r[8]};
-      for (uint32_t row = 0; row < 3; ++row) {
-        r[row] = affine(m[row], p);
-        r[3 + row] = linear(m[row], nr);
-        r[6 + row] = linear(m[row], tg);
-      }
-    }
-    bad = !(isfinite(r[0]) && isfinite(r[1]) && isfinite(r[2]));
-    float* dst = reinterpret_cast<float*>(t.out + v);
-    for (uint32_t k = 0; k < kRecordWords; ++k) dst[k] = r[k];
-  }
-  const unsigned long long offenders = __ballot(bad);
-  if (offenders && (tid & 63u) == (uint32_t)__ffsll((long long)offenders) - 1u) atomicOr(t.flag, 1u);
+  if (v < t.vertex_count)
+    bad = pose_vertex(t, a.count, [&a](uint32_t i, uint32_t* index, float* w) { *index = a.index[i]; *w = a.weight[i]; }, palette, v);
+  raise_flag(bad, tid, t.flag);
+}
+
+// The batch form: every dirty deformer of a refit in one launch.  Workgroup b poses the 256 vertices from DeformBlock::first_vertex on of
+// segment DeformBlock::segment; no workgroup spans two segments, so the segment, its tables and its active targets are uniform over
+// the workgroup: their addresses derive from blockIdx.x alone and nothing the launch writes aliases them, so the loads are scalar.
+__global__ __launch_bounds__(kDeformThreads) void k_deform_batch(const DeformSegment* __restrict__ segments, const DeformBlock* __restrict__ blocks,
+                                                                  const DeformActiveEntry* __restrict__ active) {
+  extern __shared__ df_f32x4 smem[];  // the palette of this workgroup's segment
+  DF_LDS df_f32x4* palette = (DF_LDS df_f32x4*)smem;
+  const uint32_t tid = threadIdx.x;
+  const DeformBlock b = blocks[blockIdx.x];
+  const DeformTables t = segments[b.segment].t;
+  const uint32_t active_count = segments[b.segment].active_count;
+  const DeformActiveEntry* __restrict__ act = active + segments[b.segment].active_first;
+  const uint32_t v = b.first_vertex + tid;
+  stage_palette(palette, t.palette, t.joint_count, tid);
+  bool bad = false;
+  if (v < t.vertex_count)
+    bad = pose_vertex(t, active_count, [act](uint32_t i, uint32_t* index, float* w) { *index = act[i].index; *w = act[i].weight; }, palette, v);
+  raise_flag(bad, tid, t.flag);
 }
 
 }  // namespace
@@ -97,6 +142,12 @@ void launch_deform(const DeformTables& t, const DeformActive& a, hipStream_t s) 
   if (!t.vertex_count) return;
   const uint32_t blocks = (t.vertex_count + kDeformThreads - 1) / kDeformThreads;
   hipLaunchKernelGGL(k_deform, dim3(blocks), dim3(kDeformThreads), (size_t)t.joint_count * 48, s, t, a);
+}
+
+void launch_deform_batch(const DeformSegment* segments, const DeformBlock* blocks, const DeformActiveEntry* active, uint32_t block_count,
+                         uint32_t max_joint_count, hipStream_t s) {
+  if (!block_count) return;
+  hipLaunchKernelGGL(k_deform_batch, dim3(block_count), dim3(kDeformThreads), (size_t)max_joint_count * 48, s, segments, blocks, active);
 }
 
 }  // namespace rt

@@ -37,6 +37,21 @@ struct hala_scene {
   std::deque<std::vector<uint8_t>> pixels;
   std::vector<hala_image_desc> images;
   hala_scene_desc desc{};
+  // the rig (RENDER_SPEC 19): hala_rig_desc and the arrays it borrows
+  struct Rig {
+    std::vector<hala_rig_node> nodes;
+    std::vector<uint32_t> node_of_gltf, gltf_of_node;
+    std::deque<std::vector<uint32_t>> u32s;
+    std::deque<std::vector<uint16_t>> u16s;
+    std::deque<std::vector<float>> f32s;
+    std::deque<std::vector<hala_rig_sampler>> samplers;
+    std::deque<std::vector<hala_rig_channel>> channels;
+    std::deque<std::string> names;
+    std::vector<hala_rig_skin> skins;
+    std::vector<hala_rig_binding> bindings;
+    std::vector<hala_rig_clip> clips;
+    hala_rig_desc desc{};
+  } rig;
 };
 
 namespace {
@@ -590,6 +605,223 @@ hala_camera_desc load_camera(const JsonValue& c) {  // :492-538
   return o;  // xmag / ymag stay 0: orthographic only
 }
 
+// ---- the rig (docs/RENDER_SPEC.md 19): skins, morph targets and animations, every index a scene index -----------------------------------
+[[noreturn]] void rig_fail(const std::string& m) { fail("glTF rig: " + m); }
+
+// the TRS of a node as the file gives it (binary32), or the flag that it came as a matrix
+hala_rig_node rig_node_of(const JsonValue& n, const hala_node_desc& nd) {
+  hala_rig_node o{};
+  o.parent = nd.parent;
+  o.is_matrix = has(n, "matrix") ? 1u : 0u;
+  memcpy(o.local_transform, nd.local_transform, 64);
+  const float zero3[3] = {0, 0, 0}, one3[3] = {1, 1, 1}, unit[4] = {0, 0, 0, 1};
+  floats(n, "translation", o.translation, 3, zero3);
+  floats(n, "rotation", o.rotation, 4, unit);
+  floats(n, "scale", o.scale, 3, one3);
+  return o;
+}
+
+const float* rig_floats(hala_scene* s, const std::vector<double>& v) {
+  s->rig.f32s.emplace_back(v.size());
+  for (size_t i = 0; i < v.size(); ++i) s->rig.f32s.back()[i] = (float)v[i];
+  return s->rig.f32s.back().data();
+}
+
+uint32_t rig_scene_node(const hala_scene* s, const JsonValue& v, const std::string& what) {
+  if (v.kind != JsonValue::Number || !(v.num >= 0.0) || v.num != std::floor(v.num) || v.num >= (double)s->rig.node_of_gltf.size() ||
+      s->rig.node_of_gltf[(size_t)v.num] == HALA_INVALID_INDEX)
+    rig_fail(what + " is out of range.");
+  return s->rig.node_of_gltf[(size_t)v.num];
+}
+
+// target deltas of one attribute as [target][vertex][3]; a target without the attribute contributes zeros; none has it: no array
+const float* rig_target_deltas(const Doc& d, hala_scene* s, const std::vector<JsonValue>& targets, const char* attribute, size_t vertex_count, bool required,
+                               const std::string& where) {
+  bool any = false;
+  for (const JsonValue& t : targets) any = any || has(t, attribute);
+  if (!any && !required) return nullptr;
+  std::vector<double> all(targets.size() * vertex_count * 3u, 0.0);
+  for (size_t k = 0; k < targets.size(); ++k) {
+    if (!has(targets[k], attribute)) continue;
+    const Accessor a = read_accessor(d, index_or_invalid(targets[k], attribute));
+    if (a.ncomp != 3 || a.count != vertex_count) rig_fail("a " + std::string(attribute) + " target of " + where + " does not have one VEC3 per vertex.");
+    std::copy(a.v.begin(), a.v.end(), all.begin() + k * vertex_count * 3u);
+  }
+  return rig_floats(s, all);
+}
+
+void load_rig(const Doc& d, hala_scene* s) {
+  hala_scene::Rig& rg = s->rig;
+  const auto& jnodes = arr(d.j, "nodes");
+  const auto& jmeshes = arr(d.j, "meshes");
+  const auto& jskins = arr(d.j, "skins");
+  const auto& janims = arr(d.j, "animations");
+  bool any_targets = false;
+  for (const JsonValue& m : jmeshes)
+    for (const JsonValue& p : arr(m, "primitives")) any_targets = any_targets || !arr(p, "targets").empty();
+  if (jskins.empty() && janims.empty() && !any_targets) { rg = hala_scene::Rig(); return; }  // nothing to pose: every count is 0
+
+  for (const JsonValue& sk : jskins) {
+    const auto& joints = arr(sk, "joints");
+    rg.u32s.emplace_back();
+    for (const JsonValue& j : joints) rg.u32s.back().push_back(rig_scene_node(s, j, "a joint of skin " + std::to_string(rg.skins.size())));
+    std::vector<double> ibm;
+    if (has(sk, "inverseBindMatrices")) {
+      const Accessor a = read_accessor(d, index_or_invalid(sk, "inverseBindMatrices"));
+      if (a.ncomp != 16 || a.count != joints.size())
+        rig_fail("skin " + std::to_string(rg.skins.size()) + " has " + std::to_string(a.count) + " inverse bind matrices for " + std::to_string(joints.size()) + " joints.");
+      ibm = a.v;
+    } else {
+      ibm.assign(joints.size() * 16u, 0.0);
+      for (size_t j = 0; j < joints.size(); ++j) ibm[16 * j] = ibm[16 * j + 5] = ibm[16 * j + 10] = ibm[16 * j + 15] = 1.0;
+    }
+    hala_rig_skin o{};
+    o.joint_count = (uint32_t)joints.size();
+    o.joints = rg.u32s.back().data();
+    o.inverse_bind_matrices = rig_floats(s, ibm);
+    rg.skins.push_back(o);
+  }
+
+  // target count of each mesh (its primitives must agree), and the bindings
+  std::vector<uint32_t> mesh_targets(jmeshes.size(), 0);
+  uint32_t weight_first = 0, palette_first = 0;
+  for (uint32_t m = 0; m < jmeshes.size(); ++m) {
+    const auto& jprims = arr(jmeshes[m], "primitives");
+    for (size_t p = 0; p < jprims.size(); ++p) {
+      const uint32_t n = (uint32_t)arr(jprims[p], "targets").size();
+      if (p && n != mesh_targets[m]) rig_fail("the primitives of mesh " + std::to_string(m) + " have different target counts.");
+      mesh_targets[m] = n;
+    }
+    uint32_t node = HALA_INVALID_INDEX, node_count = 0;
+    for (uint32_t k = 0; k < s->nodes.size(); ++k)
+      if (s->nodes[k].mesh_index == m) { if (!node_count) node = k; ++node_count; }
+    if (!node_count) continue;  // never drawn
+    const uint32_t skin = index_or_invalid(jnodes[rg.gltf_of_node[node]], "skin");
+    if (skin != HALA_INVALID_INDEX && skin >= rg.skins.size()) rig_fail("the skin of the node of mesh " + std::to_string(m) + " is out of range.");
+    std::vector<double> dflt(mesh_targets[m], 0.0);
+    if (has(jmeshes[m], "weights")) {
+      const auto& w = arr(jmeshes[m], "weights");
+      if (w.size() != mesh_targets[m]) rig_fail("mesh " + std::to_string(m) + " has " + std::to_string(w.size()) + " weights for " + std::to_string(mesh_targets[m]) + " targets.");
+      for (size_t k = 0; k < w.size(); ++k) dflt[k] = w[k].num;
+    }
+    for (uint32_t p = 0; p < jprims.size(); ++p) {
+      const std::string where = "mesh " + std::to_string(m) + " primitive " + std::to_string(p);
+      const JsonValue* attr = get(jprims[p], "attributes");
+      const bool skinned = skin != HALA_INVALID_INDEX && attr && has(*attr, "JOINTS_0") && has(*attr, "WEIGHTS_0");
+      if (!skinned && !mesh_targets[m]) continue;
+      hala_rig_binding b{};
+      b.mesh_index = m; b.primitive_index = p; b.node = node; b.node_count = node_count;
+      b.skin = skinned ? skin : HALA_INVALID_INDEX;
+      b.vertex_count = s->prims[m][p].vertex_count;
+      for (uint32_t k = 0; attr && has(*attr, ("JOINTS_" + std::to_string(k)).c_str()); ++k) b.influence_sets = k + 1u;
+      if (skinned) {
+        const Accessor ja = read_accessor(d, index_or_invalid(*attr, "JOINTS_0")), wa = read_accessor(d, index_or_invalid(*attr, "WEIGHTS_0"));
+        if (ja.ncomp != 4 || ja.count != b.vertex_count) rig_fail("JOINTS_0 of " + where + " does not have one VEC4 per vertex.");
+        if (wa.ncomp != 4 || wa.count != b.vertex_count) rig_fail("WEIGHTS_0 of " + where + " does not have one VEC4 per vertex.");
+        rg.u16s.emplace_back(ja.v.size());
+        for (size_t k = 0; k < ja.v.size(); ++k) {
+          if (!(ja.v[k] >= 0.0) || ja.v[k] >= (double)rg.skins[skin].joint_count) rig_fail("a joint index of " + where + " is not below the skin's joint count.");
+          rg.u16s.back()[k] = (uint16_t)ja.v[k];
+        }
+        b.joints = rg.u16s.back().data();
+        b.weights = rig_floats(s, wa.v);
+        b.palette_first = palette_first;
+        palette_first += rg.skins[skin].joint_count * 12u;
+      }
+      b.target_count = mesh_targets[m];
+      if (b.target_count) {
+        const auto& targets = arr(jprims[p], "targets");
+        b.target_position_deltas = rig_target_deltas(d, s, targets, "POSITION", b.vertex_count, true, where);
+        b.target_normal_deltas = rig_target_deltas(d, s, targets, "NORMAL", b.vertex_count, false, where);
+        b.target_tangent_deltas = rig_target_deltas(d, s, targets, "TANGENT", b.vertex_count, false, where);
+        b.default_weights = rig_floats(s, dflt);
+        b.weight_first = weight_first;
+        weight_first += b.target_count;
+      }
+      rg.bindings.push_back(b);
+    }
+  }
+
+  for (const JsonValue& an : janims) {
+    const std::string which = "animation " + std::to_string(rg.clips.size());
+    const auto& jsamplers = arr(an, "samplers");
+    const auto& jchannels = arr(an, "channels");
+    // channels first: a sampler's width is that of the path that reads it
+    std::vector<hala_rig_channel> channels;
+    std::vector<uint32_t> width(jsamplers.size(), 0);
+    for (const JsonValue& ch : jchannels) {
+      const JsonValue* target = get(ch, "target");
+      if (!target || !has(*target, "node")) continue;  // glTF 2.0 3.11: a channel without a node is ignored
+      const JsonValue* path = get(*target, "path");
+      static const std::map<std::string, uint32_t> paths = {{"translation", HALA_RIG_TRANSLATION}, {"rotation", HALA_RIG_ROTATION}, {"scale", HALA_RIG_SCALE}, {"weights", HALA_RIG_WEIGHTS}};
+      if (!path || !paths.count(path->str)) continue;  // (KHR_animation_pointer and the like: not posed)
+      hala_rig_channel o{};
+      o.node = rig_scene_node(s, *get(*target, "node"), "the node of a channel of " + which);
+      o.path = paths.at(path->str);
+      o.sampler = index_or_invalid(ch, "sampler");
+      if (o.sampler >= jsamplers.size()) rig_fail("the sampler of a channel of " + which + " is out of range.");
+      if (rg.nodes[o.node].is_matrix) rig_fail("a channel of " + which + " targets node " + std::to_string(rg.gltf_of_node[o.node]) + ", which is given as a matrix.");
+      uint32_t w = o.path == HALA_RIG_ROTATION ? 4u : 3u;
+      if (o.path == HALA_RIG_WEIGHTS) {
+        const uint32_t mesh = s->nodes[o.node].mesh_index;
+        if (mesh >= mesh_targets.size() || !mesh_targets[mesh]) rig_fail("a weights channel of " + which + " targets a node without a morphed mesh.");
+        w = mesh_targets[mesh];
+      }
+      if (width[o.sampler] && width[o.sampler] != w) rig_fail("a sampler of " + which + " is read by channels of different widths.");
+      width[o.sampler] = w;
+      channels.push_back(o);
+    }
+    std::vector<hala_rig_sampler> samplers;
+    for (size_t k = 0; k < jsamplers.size(); ++k) {
+      const JsonValue& js = jsamplers[k];
+      hala_rig_sampler o{};
+      const JsonValue* ip = get(js, "interpolation");
+      const std::string mode = ip ? ip->str : "LINEAR";
+      if (mode == "STEP") o.interpolation = HALA_RIG_STEP;
+      else if (mode == "LINEAR") o.interpolation = HALA_RIG_LINEAR;
+      else if (mode == "CUBICSPLINE") o.interpolation = HALA_RIG_CUBICSPLINE;
+      else rig_fail("a sampler of " + which + " has an unknown interpolation.");
+      const Accessor in = read_accessor(d, index_or_invalid(js, "input")), out = read_accessor(d, index_or_invalid(js, "output"));
+      if (in.ncomp != 1 || in.count == 0) rig_fail("a sampler of " + which + " has no key times.");
+      for (size_t i = 0; i < in.count; ++i)
+        if (!std::isfinite(in.v[i]) || (i && !(in.v[i] > in.v[i - 1]))) rig_fail("the key times of a sampler of " + which + " are not finite and strictly increasing.");
+      o.key_count = (uint32_t)in.count;
+      o.width = width[k] ? width[k] : (uint32_t)out.ncomp;
+      const size_t want = in.count * o.width * (o.interpolation == HALA_RIG_CUBICSPLINE ? 3u : 1u);
+      if (out.v.size() != want)
+        rig_fail("the output of a sampler of " + which + " has " + std::to_string(out.v.size()) + " values for " + std::to_string(in.count) + " keys (" + std::to_string(want) + " expected).");
+      for (double v : out.v) if (!std::isfinite(v)) rig_fail("an output of a sampler of " + which + " is not finite.");
+      o.times = rig_floats(s, in.v);
+      o.values = rig_floats(s, out.v);
+      samplers.push_back(o);
+    }
+    hala_rig_clip c{};
+    const JsonValue* nm = get(an, "name");
+    rg.names.push_back(nm ? nm->str : "");
+    c.name = rg.names.back().c_str();
+    bool first = true;
+    for (const hala_rig_channel& ch : channels) {
+      const hala_rig_sampler& sm = samplers[ch.sampler];
+      c.time_first = first ? sm.times[0] : std::min(c.time_first, sm.times[0]);
+      c.time_last = first ? sm.times[sm.key_count - 1] : std::max(c.time_last, sm.times[sm.key_count - 1]);
+      first = false;
+    }
+    rg.samplers.push_back(std::move(samplers));
+    rg.channels.push_back(std::move(channels));
+    c.samplers = rg.samplers.back().data(); c.sampler_count = (uint32_t)rg.samplers.back().size();
+    c.channels = rg.channels.back().data(); c.channel_count = (uint32_t)rg.channels.back().size();
+    rg.clips.push_back(c);
+  }
+
+  hala_rig_desc& o = rg.desc;
+  o.node_count = (uint32_t)rg.nodes.size(); o.nodes = rg.nodes.data();
+  o.gltf_node_count = (uint32_t)rg.node_of_gltf.size(); o.node_of_gltf = rg.node_of_gltf.data();
+  o.skins = rg.skins.data(); o.skin_count = (uint32_t)rg.skins.size();
+  o.bindings = rg.bindings.data(); o.binding_count = (uint32_t)rg.bindings.size();
+  o.clips = rg.clips.data(); o.clip_count = (uint32_t)rg.clips.size();
+  o.weight_floats = weight_first; o.palette_floats = palette_first;
+}
+
 void load(const std::string& path, hala_scene* s) {
   Doc d;
   const size_t slash = path.find_last_of("/\\");
@@ -611,6 +843,7 @@ void load(const std::string& path, hala_scene* s) {
   if (scenes.empty()) fail("No scene in glTF file \"" + path + "\".");  // :130
   const auto& jnodes = arr(d.j, "nodes");
   // BFS from the scene roots, parents before children (:134-173); the reference walks all scenes into one node list
+  s->rig.node_of_gltf.assign(jnodes.size(), HALA_INVALID_INDEX);
   std::vector<uint8_t> visited(jnodes.size(), 0);  // glTF node hierarchies are strict trees (glTF 2.0 §3.5.2): a revisit is a cycle or a shared child
   for (const JsonValue& sc : scenes) {
     std::deque<std::pair<int32_t, uint32_t>> queue;
@@ -632,10 +865,13 @@ void load(const std::string& path, hala_scene* s) {
       if (const JsonValue* e = get(n, "extensions")) if (const JsonValue* kl = get(*e, "KHR_lights_punctual")) nd.light_index = index_or_invalid(*kl, "light");
       const int32_t cur = (int32_t)s->nodes.size();
       s->nodes.push_back(nd);
+      s->rig.node_of_gltf[idx] = (uint32_t)cur; s->rig.gltf_of_node.push_back(idx);
+      s->rig.nodes.push_back(rig_node_of(n, nd));
       for (const JsonValue& c : arr(n, "children")) queue.emplace_back(cur, json_index(c));
     }
   }
   for (const JsonValue& m : arr(d.j, "meshes")) load_mesh(d, m, s);
+  load_rig(d, s);
   for (const JsonValue& m : arr(d.j, "materials")) s->materials.push_back(load_material(m));
   uint32_t k = 0;
   for (const JsonValue& t : arr(d.j, "textures")) s->tex2img.push_back(hala_index_pair{k++, index_or_invalid(t, "source")});  // :188-192
@@ -716,6 +952,7 @@ int hala_scene_load_gltf(const char* path, hala_scene** out) {
   return HALA_OK;
 }
 const hala_scene_desc* hala_scene_get_desc(const hala_scene* s) { return s ? &s->desc : nullptr; }
+const hala_rig_desc* hala_scene_get_rig(const hala_scene* s) { return s ? &s->rig.desc : nullptr; }
 void hala_scene_free(hala_scene* s) { delete s; }
 
 }  // extern "C"

@@ -282,6 +282,7 @@ int hala_rt_set_scene(hala_rt_renderer* r, const hala_scene_desc* scene) {
   r->temporal.drop_history();  // RENDER_SPEC §16: the history belongs to the old scene
   r->deform.off();             // RENDER_SPEC §17: so do the deformers
   r->shutter.off();            // RENDER_SPEC §18: and every key, and the shutter
+  r->rig.off();                // RENDER_SPEC §19: and the rig that registered deformers
   const std::string e = r->hs.assign(scene);
   if (!e.empty()) RT_FAIL(e);
   if (upload_packed(r) != HALA_OK) return HALA_ERR;

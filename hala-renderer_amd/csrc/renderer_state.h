@@ -1,6 +1,6 @@
 // renderer_state.h — the renderer object behind the C ABI (struct hala_rt_renderer), shared by the host units that implement it:
 // renderer.hip (life cycle, scene, update), rt_scene.hip (uploads, trees, edits), rt_outputs.hip (views, AOVs, adaptive sampling, light
-// groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_deform.hip (deformers), rt_shutter.hip (shutter motion blur), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
+// groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_deform.hip (deformers), rt_rig.hip (rigs and clips), rt_shutter.hip (shutter motion blur), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
 // Each feature keeps its state in one struct that knows how to turn itself off.  Nothing outside csrc/ includes this header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@
 #include "host_scene.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "rig.h"
 #include "shutter.h"
 #include "temporal.h"
 
@@ -400,6 +401,7 @@ struct hala_rt_renderer {
   TemporalState temporal;      // RENDER_SPEC 16: allocated by hala_rt_set_temporal
   DeformState deform;          // RENDER_SPEC 17: one deformer per primitive (hala_rt_set_deformer)
   ShutterState shutter;        // RENDER_SPEC 18: keys and shutter (hala_rt_set_shutter)
+  RigState rig;                // RENDER_SPEC 19: the rig whose bindings are deformers here (hala_rt_set_rig)
   DeviceArray<P3> ps_lr, ps_le, ps_alb, ps_nrm;
   DeviceArray<hala_ray> q_rays[2];
   DeviceArray<float4> q_state[2];

@@ -37,7 +37,7 @@ static int restore_rest(hala_rt_renderer* r, Deformer& d) {
   return HALA_OK;
 }
 
-static int launch(hala_rt_renderer* r, Deformer& d, const Deformer::Params& p, uint32_t* flag) {
+static DeformTables tables_of(hala_rt_renderer* r, Deformer& d, uint32_t* flag) {
   DeformTables t{};
   t.rest = d.d_rest.ptr; t.out = arena_of(r, d.prim);
   t.dp = d.target_count ? d.d_dp.ptr : nullptr;
@@ -47,6 +47,11 @@ static int launch(hala_rt_renderer* r, Deformer& d, const Deformer::Params& p, u
   t.weights = d.d_weights.ptr; t.palette = d.d_palette.ptr;
   t.vertex_count = d.vertex_count; t.joint_count = d.joint_count;
   t.flag = flag;
+  return t;
+}
+
+static int launch(hala_rt_renderer* r, Deformer& d, const Deformer::Params& p, uint32_t* flag) {
+  const DeformTables t = tables_of(r, d, flag);
   DeformActive a{};
   for (uint32_t k = 0; k < d.target_count; ++k)
     if (p.weights[k] != 0.0f) { a.index[a.count] = k; a.weight[a.count] = p.weights[k]; ++a.count; }
@@ -54,6 +59,68 @@ static int launch(hala_rt_renderer* r, Deformer& d, const Deformer::Params& p, u
   if (d.joint_count) RT_HIP(hipMemcpyAsync(d.d_palette.ptr, p.palette.data(), p.palette.size() * 4, hipMemcpyHostToDevice, r->stream));
   launch_deform(t, a, r->stream);
   RT_HIP(hipGetLastError());
+  return HALA_OK;
+}
+
+// Two or more deformers at once (k_deform_batch): segment table, block map, active targets and palettes are laid out in
+// DeformState::h_stage, copied to the device in one piece and posed by one launch.  Item k raises flags[k].  (The staged bytes stay
+// as they are until the caller has synchronised, as the palettes of the single launch do.)
+struct BatchItem { Deformer* d; const Deformer::Params* p; uint32_t* flag; };
+static int launch_batch(hala_rt_renderer* r, const std::vector<BatchItem>& items) {
+  DeformState& ds = r->deform;
+  size_t blocks = 0, actives = 0, palette_floats = 0;
+  uint32_t max_joints = 0;
+  for (const BatchItem& it : items) {
+    blocks += (it.d->vertex_count + kDeformThreads - 1) / kDeformThreads;
+    for (float w : it.p->weights) actives += w != 0.0f;
+    palette_floats += (size_t)it.d->joint_count * 12u;
+    max_joints = std::max(max_joints, it.d->joint_count);
+  }
+  if (!blocks) return HALA_OK;
+  auto align16 = [](size_t n) { return (n + 15u) & ~(size_t)15u; };
+  const size_t off_blocks = align16(items.size() * sizeof(DeformSegment)), off_active = align16(off_blocks + blocks * sizeof(DeformBlock)),
+               off_palette = align16(off_active + actives * sizeof(DeformActiveEntry)), total = off_palette + palette_floats * 4u;
+  ds.h_stage.assign(total, 0);
+  if (total > ds.d_stage.count) RT_HIP(ds.d_stage.resize(total));
+  DeformSegment* seg = reinterpret_cast<DeformSegment*>(ds.h_stage.data());
+  DeformBlock* blk = reinterpret_cast<DeformBlock*>(ds.h_stage.data() + off_blocks);
+  DeformActiveEntry* act = reinterpret_cast<DeformActiveEntry*>(ds.h_stage.data() + off_active);
+  float* pal = reinterpret_cast<float*>(ds.h_stage.data() + off_palette);
+  const float* d_pal = reinterpret_cast<const float*>(ds.d_stage.ptr + off_palette);
+  uint32_t nb = 0, na = 0;
+  size_t np = 0;
+  for (size_t k = 0; k < items.size(); ++k) {
+    Deformer& d = *items[k].d;
+    const Deformer::Params& p = *items[k].p;
+    seg[k].t = tables_of(r, d, items[k].flag);
+    seg[k].t.palette = d_pal + np;
+    seg[k].active_first = na;
+    for (uint32_t t = 0; t < d.target_count; ++t)
+      if (p.weights[t] != 0.0f) act[na++] = DeformActiveEntry{t, p.weights[t]};
+    seg[k].active_count = na - seg[k].active_first;
+    std::copy(p.palette.begin(), p.palette.begin() + (size_t)d.joint_count * 12u, pal + np);
+    np += (size_t)d.joint_count * 12u;
+    for (uint32_t v = 0; v < d.vertex_count; v += kDeformThreads) blk[nb++] = DeformBlock{(uint32_t)k, v};
+  }
+  RT_HIP(hipMemcpyAsync(ds.d_stage.ptr, ds.h_stage.data(), total, hipMemcpyHostToDevice, r->stream));
+  launch_deform_batch(reinterpret_cast<const DeformSegment*>(ds.d_stage.ptr), reinterpret_cast<const DeformBlock*>(ds.d_stage.ptr + off_blocks),
+                      reinterpret_cast<const DeformActiveEntry*>(ds.d_stage.ptr + off_active), nb, max_joints, r->stream);
+  RT_HIP(hipGetLastError());
+  return HALA_OK;
+}
+
+// one deformer: k_deform as always; kDeformBatchMin or more: one launch of k_deform_batch (DESIGN.md 19 has the measurement behind it)
+static int launch_all(hala_rt_renderer* r, const std::vector<BatchItem>& items, bool count) {
+  if (items.empty()) return HALA_OK;
+  if (items.size() >= kDeformBatchMin) {
+    if (launch_batch(r, items) != HALA_OK) return HALA_ERR;
+    if (count) { r->deform.launches += 1; r->deform.batch_launches += 1; r->deform.segments += items.size(); }
+    return HALA_OK;
+  }
+  for (const BatchItem& it : items) {
+    if (launch(r, *it.d, *it.p, it.flag) != HALA_OK) return HALA_ERR;
+    if (count) { r->deform.launches += 1; r->deform.segments += 1; }
+  }
   return HALA_OK;
 }
 
@@ -80,19 +147,22 @@ static int apply_pending(hala_rt_renderer* r) {
   if (dirty.empty()) return HALA_OK;
   RT_HIP(r->deform.d_flags.resize(dirty.size()));
   RT_HIP(hipMemsetAsync(r->deform.d_flags.ptr, 0, dirty.size() * 4, r->stream));
-  for (size_t k = 0; k < dirty.size(); ++k)
-    if (launch(r, *dirty[k], dirty[k]->pending, r->deform.d_flags.ptr + k) != HALA_OK) return HALA_ERR;
+  std::vector<BatchItem> items;
+  for (size_t k = 0; k < dirty.size(); ++k) items.push_back(BatchItem{dirty[k], &dirty[k]->pending, r->deform.d_flags.ptr + k});
+  if (launch_all(r, items, true) != HALA_OK) return HALA_ERR;
   std::vector<uint32_t> flags(dirty.size());
   RT_HIP(hipMemcpyAsync(flags.data(), r->deform.d_flags.ptr, flags.size() * 4, hipMemcpyDeviceToHost, r->stream));
   RT_HIP(hipStreamSynchronize(r->stream));
   bool overflow = false;
   for (uint32_t f : flags) overflow = overflow || f != 0u;
   if (overflow) {
+    items.clear();
     for (size_t k = 0; k < dirty.size(); ++k) {
       Deformer& d = *dirty[k];
       if (!d.posed) { if (restore_rest(r, d) != HALA_OK) return HALA_ERR; }
-      else if (launch(r, d, d.applied, r->deform.d_flags.ptr + k) != HALA_OK) return HALA_ERR;
+      else items.push_back(BatchItem{&d, &d.applied, r->deform.d_flags.ptr + k});
     }
+    if (launch_all(r, items, false) != HALA_OK) return HALA_ERR;
     RT_HIP(hipStreamSynchronize(r->stream));
     for (size_t k = 0; k < dirty.size(); ++k)
       if (flags[k]) { dirty[k]->pending = dirty[k]->applied; dirty[k]->dirty = false; }
@@ -138,6 +208,7 @@ int hala_rt_set_deformer(hala_rt_renderer* r, const hala_deformer_desc* desc) {
     if (!all_finite(desc->weights, nv * 4u)) RT_FAIL("A skin weight is not finite.");
   }
   std::unique_ptr<Deformer> d(new Deformer());
+  d->id = ++r->deform.next_id;
   d->prim = prim; d->vertex_count = (uint32_t)nv; d->target_count = desc->target_count; d->joint_count = desc->joint_count;
   d->has_dn = has_dn; d->has_dt = has_dt;
   RT_HIP(d->d_rest.upload(p.vertices.data(), nv, r->stream));  // (the host copy is the rest pose: nothing but the upload reads it after commit)

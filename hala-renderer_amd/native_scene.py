@@ -25,6 +25,12 @@ class NativeScene:
     def desc(self) -> A.SceneDesc:
         return self.desc_ptr().contents
 
+    @property
+    def rig(self):
+        """the file's skins, morph targets and clips (docs/RENDER_SPEC.md 19) as a rig.Rig; its counts are 0 when there is nothing to pose"""
+        from .rig import Rig
+        return Rig(self._lib.hala_scene_get_rig(self._h), owner=self)
+
     def close(self):
         if self._h:
             self._lib.hala_scene_free(self._h)

@@ -669,6 +669,44 @@ class HalaRenderer:
         self._check(self._lib.hala_rt_set_vertex_keys(self._h, C.c_uint32(mesh), C.c_uint32(prim), None if o is None else C.c_void_p(o.ctypes.data),
                                                       None if c is None else C.c_void_p(c.ctypes.data), C.c_uint32(n)))
 
+    # -- rigs and clips (docs/RENDER_SPEC.md 19; include/halart.h "Rigs and clips") -----------------------------------------------------
+    def set_rig(self, rig):
+        """register one deformer per binding of a rig.Rig (NativeScene.rig) on the committed scene; None clears the rig and its deformers"""
+        self._check(self._lib.hala_rt_set_rig(self._h, None if rig is None else rig.desc_ptr()))
+        self._rig = rig
+
+    def pose_rig(self, clip, time=0.0):
+        """record clip `clip` (None: the file's own pose) at `time`: node transforms and deformer poses, applied by the next refit()"""
+        from .rig import clip_index
+        self._check(self._lib.hala_rt_pose_rig(self._h, C.c_uint32(clip_index(clip)), C.c_float(time)))
+
+    def key_rig(self, clip, t_open=0.0, t_close=0.0):
+        """the clip's poses at t_open and t_close as shutter keys of its nodes and deformers (None clears them); applied by the next refit()"""
+        from .rig import clip_index
+        self._check(self._lib.hala_rt_key_rig(self._h, C.c_uint32(clip_index(clip)), C.c_float(t_open), C.c_float(t_close)))
+
+    def rig_pose(self, key=0):
+        """what the last pose_rig (key 0) or key_rig (0: open, 1: close) recorded -> Rig.unpack()'s dict plus clip (None: the file's pose) and time"""
+        rig = getattr(self, "_rig", None)
+        if rig is None:
+            from . import HalaRendererError
+            raise HalaRendererError("No rig is set (set_rig).")
+        fp = C.POINTER(C.c_float)
+        l, w, p = rig.buffers()
+        clip, time = C.c_uint32(0), C.c_float(0.0)
+        self._check(self._lib.hala_rt_get_rig_pose(self._h, C.c_uint32(key), C.byref(clip), C.byref(time), l.ctypes.data_as(fp), w.ctypes.data_as(fp),
+                                                   p.ctypes.data_as(fp)))
+        out = rig.unpack(l, w, p)
+        out["clip"], out["time"] = (None if clip.value == 0xFFFFFFFF else clip.value), time.value
+        return out
+
+    def rig_status(self) -> A.RigStatus:
+        """bindings of the rig, deformers registered, and the cumulative pose launches, those of k_deform_batch among them, and the deformers
+        ("segments") they posed"""
+        s = A.RigStatus()
+        self._check(self._lib.hala_rt_get_rig_status(self._h, C.byref(s)))
+        return s
+
     # -- multi-GPU tile sharding ---------------------------------------------------------------------------------------
     def set_tile_shard(self, rank, world, tile_size=32):
         self._check(self._lib.hala_rt_set_tile_shard(self._h, C.c_uint32(rank), C.c_uint32(world), C.c_uint32(tile_size)))

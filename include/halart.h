@@ -265,6 +265,97 @@ const hala_scene_desc* hala_scene_get_desc(const hala_scene* scene);
 void hala_scene_free(hala_scene* scene);
 
 /* ------------------------------------------------------------------------------------------------
+ * The rig of a glTF file (docs/RENDER_SPEC.md 19; no reference equivalent): skins, morph targets and animation clips as plain C
+ * arrays, with every index already a scene index (hala_scene_load_gltf renumbers the file's nodes breadth-first).  A host that has
+ * its own parser fills the same struct.  Every count is 0 when the file has nothing to pose.
+ * ---------------------------------------------------------------------------------------------- */
+#define HALA_RIG_STEP 0u
+#define HALA_RIG_LINEAR 1u
+#define HALA_RIG_CUBICSPLINE 2u
+#define HALA_RIG_TRANSLATION 0u
+#define HALA_RIG_ROTATION 1u
+#define HALA_RIG_SCALE 2u
+#define HALA_RIG_WEIGHTS 3u
+typedef struct hala_rig_node {
+  int32_t parent;            /* scene node index, -1: none (parents precede children) */
+  uint32_t is_matrix;        /* 1: the file gave a `matrix` (no clip may touch the node); 0: the TRS below */
+  float local_transform[16]; /* as hala_node_desc::local_transform: what a node no clip touches keeps, byte for byte */
+  float translation[3];
+  float rotation[4];         /* x y z w */
+  float scale[3];
+} hala_rig_node; /* 112 B */
+typedef struct hala_rig_skin {
+  uint32_t joint_count;
+  uint32_t reserved;
+  const uint32_t* joints;             /* scene node indices */
+  const float* inverse_bind_matrices; /* joint_count column-major 4 x 4; the identity where the file has none */
+} hala_rig_skin; /* 24 B */
+/* one primitive that has a skin or morph targets */
+typedef struct hala_rig_binding {
+  uint32_t mesh_index, primitive_index;
+  uint32_t node;                       /* the scene node that instantiates the mesh (the first one, should there be several) */
+  uint32_t node_count;                 /* how many nodes instantiate it: hala_rt_set_rig accepts 1 */
+  uint32_t skin;                       /* of that node, or HALA_INVALID_INDEX */
+  uint32_t vertex_count;
+  uint32_t influence_sets;             /* JOINTS_n / WEIGHTS_n sets the file has; set 0 is read, the others are counted only */
+  uint32_t target_count;
+  const uint16_t* joints;              /* [vertex][4] (JOINTS_0), NULL without a skin */
+  const float* weights;                /* [vertex][4] (WEIGHTS_0, as given) */
+  const float* target_position_deltas; /* [target][vertex][3], as hala_deformer_desc takes them; NULL when target_count is 0 */
+  const float* target_normal_deltas;   /* or NULL */
+  const float* target_tangent_deltas;  /* or NULL */
+  const float* default_weights;        /* target_count: the mesh's `weights`, or zeros */
+  uint32_t weight_first;               /* where this binding's weights start in a packed pose (floats) */
+  uint32_t palette_first;              /* where its palette starts in a packed pose (floats; 12 per joint) */
+} hala_rig_binding; /* 88 B */
+typedef struct hala_rig_sampler {
+  const float* times;     /* key_count, finite and strictly increasing */
+  const float* values;    /* key_count * width floats; CUBICSPLINE: key_count * 3 * width (in-tangent, value, out-tangent) */
+  uint32_t key_count;     /* >= 1 */
+  uint32_t interpolation; /* HALA_RIG_STEP / LINEAR / CUBICSPLINE */
+  uint32_t width;         /* floats per value: 3, 4, or the target count */
+  uint32_t reserved;
+} hala_rig_sampler; /* 32 B */
+typedef struct hala_rig_channel {
+  uint32_t sampler; /* of the same clip */
+  uint32_t node;    /* scene node index */
+  uint32_t path;    /* HALA_RIG_TRANSLATION / ROTATION / SCALE / WEIGHTS */
+  uint32_t reserved;
+} hala_rig_channel; /* 16 B */
+typedef struct hala_rig_clip {
+  const char* name; /* "" when the file has none */
+  const hala_rig_sampler* samplers;
+  const hala_rig_channel* channels;
+  uint32_t sampler_count, channel_count;
+  float time_first, time_last; /* the first and last key time over the samplers its channels use (0, 0 without channels) */
+} hala_rig_clip; /* 40 B */
+typedef struct hala_rig_desc {
+  uint32_t node_count;      /* the scene's node count, or 0 when there is nothing to pose */
+  uint32_t gltf_node_count; /* length of node_of_gltf */
+  const hala_rig_node* nodes;
+  const uint32_t* node_of_gltf; /* glTF node index -> scene node index; HALA_INVALID_INDEX: in no scene */
+  const hala_rig_skin* skins;
+  const hala_rig_binding* bindings;
+  const hala_rig_clip* clips;
+  uint32_t skin_count, binding_count, clip_count;
+  uint32_t weight_floats;  /* floats of a packed pose's weights: the sum of target_count over the bindings */
+  uint32_t palette_floats; /* floats of a packed pose's palettes: 12 per joint of every skinned binding */
+  uint32_t reserved;
+} hala_rig_desc; /* 72 B */
+/* The rig of a loaded file: borrowed, owned by the scene.  Loading fails ("... glTF rig ...") on a joint or channel node out of range,
+ * an inverse-bind count that differs from the joint count, key times that are not finite or do not strictly increase, a sampler
+ * output whose count does not match its input (3 per key for CUBICSPLINE), a `weights` channel on a node without a mesh or whose
+ * width differs from the mesh's target count, primitives of one mesh with different target counts, target or joint accessors whose
+ * count differs from the vertex count, and a channel on a node given as `matrix`. */
+const hala_rig_desc* hala_scene_get_rig(const hala_scene* scene);
+/* Evaluates clip `clip` at `time` on the host (RENDER_SPEC 19; float64, each result rounded once): the local transform of every
+ * node (node_count * 16 floats, column-major), the morph weights of every binding (weight_floats) and the joint palette of every
+ * binding (palette_floats; row-major 3 x 4 per joint, as hala_rt_update_deformer takes them), each output optional (NULL).
+ * clip == HALA_INVALID_INDEX: the file's own pose.  Fails on a clip that does not exist, a time that is not finite, a malformed
+ * description (an index out of range) and a mesh node whose world transform is singular.  Needs no renderer and no GPU. */
+int hala_rig_sample_clip(const hala_rig_desc* rig, uint32_t clip, float time, float* locals, float* weights, float* palettes);
+
+/* ------------------------------------------------------------------------------------------------
  * Errors
  * ---------------------------------------------------------------------------------------------- */
 /* HalaRendererError::message() (src/error.rs:23) of the last failed call on this thread. */
@@ -782,7 +873,7 @@ int hala_rt_update_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
                             uint32_t weight_count, const float* joint_matrices_3x4, uint32_t joint_count);
 /* Removes the deformer of a primitive: the next hala_rt_refit restores the rest pose and frees the tables.  Refused when the primitive
  * has none.  While a primitive has a deformer, hala_rt_update_vertices on it is refused ("clear it first").
- * The refit contract: hala_rt_refit poses every deformer whose parameters changed (one kernel launch each on the renderer's stream)
+ * The refit contract: hala_rt_refit poses every deformer whose parameters changed (one launch of k_deform for one, one launch of k_deform_batch for two or more, on the renderer's stream)
  * and then refits as it does after hala_rt_update_vertices; every instance of a posed primitive starts without temporal history
  * (hala_rt_set_temporal) unless hala_rt_set_temporal_vertex_motion lets the history follow its triangles.  Finite parameters can still overflow: when a posed position is not finite, hala_rt_refit fails with
  * "Vertex position is not finite.", the vertices and the tree stay exactly as they were, the offending parameters fall back to the last
@@ -858,6 +949,41 @@ int hala_rt_set_deformer_keys(hala_rt_renderer* r, uint32_t mesh_index, uint32_t
  * finite." and the vertices stay exactly as they were. */
 int hala_rt_set_vertex_keys(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, const hala_vertex* open,
                             const hala_vertex* close, uint32_t vertex_count);
+
+/* ------------------------------------------------------------------------------------------------
+ * Rigs and clips (docs/RENDER_SPEC.md 19): a hala_rig_desc drives the deformers, node transforms and shutter keys above.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hala_rig_status {
+  uint32_t bindings;       /* of the rig hala_rt_set_rig registered; 0: none */
+  uint32_t deformers;      /* deformers registered on the renderer, by hala_rt_set_rig or hala_rt_set_deformer */
+  uint64_t pose_launches;  /* kernel launches that posed deformers, since hala_rt_create */
+  uint64_t segments_posed; /* deformers those launches posed: a launch of the batch kernel poses several */
+  uint64_t batch_launches; /* the launches of k_deform_batch among pose_launches; the others are k_deform's, one deformer each */
+} hala_rig_status; /* 32 B */
+/* Registers one deformer (hala_rt_set_deformer) per binding of `rig` on the committed scene and keeps a copy of the rig's tables; the
+ * caller's arrays may go.  NULL clears the rig: the deformers it registered (one that the host cleared or replaced since stays the
+ * host's), the shutter keys hala_rt_key_rig set, and the nodes its poses moved, which go back to the file's transforms at the next
+ * hala_rt_refit; it is refused, changing nothing, while one of its deformers has shutter keys that a refit has not yet cleared
+ * (hala_rt_key_rig with HALA_INVALID_INDEX, then hala_rt_refit, first).  Refused, changing nothing, with a message that names
+ * the mesh and primitive: a binding above HALA_MAX_JOINTS or HALA_MAX_MORPH_TARGETS; a bound mesh that more than one node
+ * instantiates (the posed vertices are per primitive, not per instance); node, mesh, primitive, skin or vertex counts that do not
+ * fit the committed scene; a primitive that already has a deformer or shutter vertex keys; a rig is set already (clear it first).
+ * hala_rt_set_scene drops the rig with the deformers. */
+int hala_rt_set_rig(hala_rt_renderer* r, const hala_rig_desc* rig);
+/* Records the pose of clip `clip` at `time` (hala_rig_sample_clip): hala_rt_update_node_transform for every node a channel of the
+ * clip touches and hala_rt_update_deformer for every binding; a node that an earlier pose of the rig wrote and this clip does not
+ * touch goes back to the file's transform, so the scene stands at the pose hala_rt_get_rig_pose reports.  clip ==
+ * HALA_INVALID_INDEX: the file's own pose, on every node any clip touches.  Takes effect at the next hala_rt_refit.  Refused, changing nothing: no rig; the clip does not exist; a singular
+ * mesh node; a touched node or a binding's deformer that has shutter keys; a binding whose deformer the host cleared or replaced. */
+int hala_rt_pose_rig(hala_rt_renderer* r, uint32_t clip, float time);
+/* Evaluates the clip at t_open and t_close and sets the results as shutter keys (hala_rt_set_node_keys on the touched nodes,
+ * hala_rt_set_deformer_keys on the bindings): with hala_rt_set_shutter the refit and the frames after it blur the clip over that
+ * interval.  clip == HALA_INVALID_INDEX clears the keys this call set.  Refused, changing nothing, as hala_rt_pose_rig is. */
+int hala_rt_key_rig(hala_rt_renderer* r, uint32_t clip, float t_open, float t_close);
+/* What the last hala_rt_pose_rig (key 0) or hala_rt_key_rig (key 0: open, key 1: close) recorded, laid out as
+ * hala_rig_sample_clip's outputs; each may be NULL.  *clip and *time receive what that call was given.  Refused before the first. */
+int hala_rt_get_rig_pose(hala_rt_renderer* r, uint32_t key, uint32_t* clip, float* time, float* locals, float* weights, float* palettes);
+int hala_rt_get_rig_status(hala_rt_renderer* r, hala_rig_status* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Denoising (docs/RENDER_SPEC.md 10; no reference equivalent): an edge-avoiding a-trous wavelet filter over the running
