@@ -48,7 +48,8 @@ struct DeformSegment {
 struct DeformBlock { uint32_t segment, first_vertex; };  // 8 B per workgroup
 static_assert(sizeof(DeformSegment) % 8 == 0 && sizeof(DeformBlock) == 8 && sizeof(DeformActiveEntry) == 8, "the staged sections are 8-byte records");
 
-// The registered deformer of one primitive.  `applied` is what the arena holds, `pending` what the next refit applies.
+// The registered deformer of one primitive.  `applied` and `posed` say what the arena holds (kept by deform_pose, rt_deform.hip);
+// `pending` and `dirty` are what the caller recorded for the next refit (written by the entry points and by that refit alone).
 struct Deformer {
   uint32_t prim = 0, vertex_count = 0, target_count = 0, joint_count = 0;
   uint64_t id = 0;  // unique among the deformers of one renderer (DeformState::next_id): tells a replacement on the same primitive apart
@@ -59,20 +60,19 @@ struct Deformer {
   bool has_dn = false, has_dt = false;
   struct Params { std::vector<float> weights, palette; };
   Params applied, pending;
-  bool dirty = false;  // hala_rt_update_deformer since the last refit
+  bool dirty = false;  // `pending` was recorded since the last refit that posed it
   bool posed = false;  // the arena holds k_deform(applied) and not the rest pose as uploaded
 };
 
 struct DeformState {
   std::map<uint32_t, std::unique_ptr<Deformer>> by_prim;  // key: index into HostScene::prims
-  DeviceArray<uint32_t> d_flags;                           // one overflow word per dirty deformer of a refit
+  DeviceArray<uint32_t> d_flags;                           // one overflow word per deformer of a call of deform_pose
   std::vector<unsigned char> h_stage;                      // the batch launch's tables as laid out on the host, and their device copy
   DeviceArray<unsigned char> d_stage;
   uint64_t launches = 0, segments = 0;                     // pose launches (either kernel) and deformers they posed, since hala_rt_create
   uint64_t batch_launches = 0;                             // those of k_deform_batch among them
   uint64_t next_id = 0;
-  bool restored = false;                                   // (deform_apply_pending: the failing refit put the arena back)
-  bool lost = false;                                       // a device error interrupted a refit's launches: the arena is undefined
+  bool lost = false;                                       // a device error interrupted deform_pose: the arena is undefined
   void off() { by_prim.clear(); d_flags.release(); d_stage.release(); lost = false; }
 };
 

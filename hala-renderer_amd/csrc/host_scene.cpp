@@ -38,13 +38,21 @@ static Mat4 mul(const Mat4& a, const Mat4& b) {
   return r;
 }
 
-void HostScene::update_node_hierarchies() {
+std::vector<Mat4> HostScene::locals() const {
+  std::vector<Mat4> out;
+  out.reserve(nodes.size());
+  for (const auto& n : nodes) out.push_back(n.local);
+  return out;
+}
+
+void HostScene::update_node_hierarchies(const std::vector<Mat4>& locals) {
   // src/scene/cpu/scene.rs:99-114 — single pass in node order, parent's world transform must already be final
   const Mat4 identity = Mat4::identity();
   for (auto& n : nodes) n.world = identity;
-  for (auto& n : nodes) {
-    if (n.parent >= 0) n.world = mul(nodes[(size_t)n.parent].world, n.local);
-    else n.world = n.local;
+  for (size_t k = 0; k < nodes.size(); ++k) {
+    HostNode& n = nodes[k];
+    if (n.parent >= 0) n.world = mul(nodes[(size_t)n.parent].world, locals[k]);
+    else n.world = locals[k];
   }
 }
 
@@ -130,8 +138,8 @@ std::string HostScene::assign(const hala_scene_desc* d) {
   lights_cpu.assign(d->lights, d->lights + d->light_count);
   for (const auto& l : lights_cpu) if (l.light_type > 4u) return "Invalid light type.";  // cpu/light.rs:20
   cameras_cpu.assign(d->cameras, d->cameras + d->camera_count);
-  update_node_hierarchies();
-  return pack();
+  update_node_hierarchies(locals());
+  return pack(materials);
 }
 
 hala_gpu_material HostScene::pack_material(const hala_material_desc& m) {
@@ -166,7 +174,7 @@ hala_gpu_material HostScene::pack_material(const hala_material_desc& m) {
   return o;
 }
 
-std::string HostScene::pack() {
+std::string HostScene::pack(const std::vector<hala_material_desc>& fit_materials) {
   // ---- cameras: gpu_uploader.rs:99-122 + gpu/camera.rs:28-61 --------------------------------------------
   cameras.clear();
   for (size_t index = 0; index < cameras_cpu.size(); ++index) {
@@ -236,7 +244,7 @@ std::string HostScene::pack() {
   }
   // ---- materials: gpu_uploader.rs:306-331 ---------------------------------------------------------------------
   gpu_materials.clear();
-  for (const auto& m : materials) gpu_materials.push_back(pack_material(m));
+  for (const auto& m : fit_materials) gpu_materials.push_back(pack_material(m));
   // ---- instances: gpu_uploader.rs:843-875 (node order, then primitive order) ---------------------------------
   instances.clear(); instance_3x4.clear(); inst_first_tri.clear(); instance_node.clear(); instance_prim.clear();
   uint32_t tri_total = 0;

@@ -64,9 +64,12 @@ struct HostScene {
   std::vector<uint32_t> instance_node, instance_prim;
   uint32_t triangle_count = 0;
 
-  std::string assign(const hala_scene_desc* d);  // copy + update_node_hierarchies + pack; "" on success
-  void update_node_hierarchies();                // src/scene/cpu/scene.rs:99-114
-  std::string pack();
+  // `nodes[].local` and `materials` are what the caller recorded (assign and the edit entry points write them); the packed records and
+  // `nodes[].world` are what the tree stands at: a function of the locals and materials handed to the two calls below
+  std::string assign(const hala_scene_desc* d);  // copy + update_node_hierarchies + pack of the scene's own; "" on success
+  std::vector<Mat4> locals() const;              // nodes[].local
+  void update_node_hierarchies(const std::vector<Mat4>& locals);  // src/scene/cpu/scene.rs:99-114; one local per node
+  std::string pack(const std::vector<hala_material_desc>& fit_materials);
   static hala_gpu_material pack_material(const hala_material_desc& m);
   static void primitive_bounds(const HostPrimitive& p, float center[3], float extents[3]);
 };

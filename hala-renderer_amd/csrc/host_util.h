@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -55,6 +56,12 @@ struct DeviceArray {
   }
   size_t bytes() const { return count * sizeof(T); }
 };
+
+inline bool all_finite(const float* v, size_t n) {
+  for (size_t k = 0; k < n; ++k)
+    if (!std::isfinite(v[k])) return false;
+  return true;
+}
 
 // ---- minimal JSON (for HalaRayTracingProgramDesc, src/raytracing_program.rs:25-55) -------------------------
 struct JsonValue {

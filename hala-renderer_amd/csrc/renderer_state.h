@@ -268,7 +268,8 @@ struct ShutterState {
   uint32_t step = kShutterNoStep;  // the step the scene stands at
   float time = 0.0f;
   unsigned long long steps = 0;    // steps performed since create
-  // the edits as the last refit found them: a step refits from these, so that edits recorded since do not ride along with it
+  // the recorded node transforms and materials as the last refit found them: what a step fits to (RefitInputs), so that edits recorded
+  // since do not ride along with it
   std::vector<Mat4> locals;
   std::vector<hala_material_desc> materials;
   std::vector<uint32_t> stale;     // primitives whose arena range the next refit uploads again from the host copy
@@ -307,6 +308,7 @@ struct hala_rt_renderer {
   DeviceArray<hala_vertex> d_vertices;
   DeviceArray<uint32_t> d_indices;
   std::vector<size_t> prim_vertex_offset, prim_index_offset;
+  hala_vertex* arena(uint32_t prim) const { return d_vertices.ptr + prim_vertex_offset[prim]; }  // the primitive's range of the vertex arena
   DeviceArray<hala_gpu_camera> d_cameras;
   DeviceArray<hala_gpu_light> d_lights;
   DeviceArray<hala_gpu_material> d_materials;
@@ -416,9 +418,9 @@ struct hala_rt_renderer {
   hala_global_uniform last_uniform{};
   TraceEvents ring[kStatRing];
   int ring_pos = 0;
-  bool vertices_dirty = false;  // hala_rt_update_vertices since the last refit
+  // recorded by the edit entry points, read and cleared by hala_rt_refit alone (a step of the shutter passes its own: RefitInputs)
+  bool vertices_dirty = false;       // the vertex arena changed since the tree was fitted to it
   bool materials_dirty_any = false;  // a material edit touched an opacity-0 material (old or new)
-  bool materials_dirty_any_refit = false;  // ... as hala_rt_refit found it
   bool any_invisible = false;   // the scene has invisible or translucent materials: the any-hit launches traverse d_tris_any (RENDER_SPEC 7.1d)
   bool any_translucent = false; // ... translucent ones: the ALPHA variants of the any-hit kernels
   DeviceArray<uint8_t> d_material_any_class;
@@ -573,12 +575,26 @@ int upload_packed(hala_rt_renderer* r, bool geometry = true);
 int upload_textures(hala_rt_renderer* r);
 int update_texture_bundles(hala_rt_renderer* r, bool fresh);
 int build_bvh(hala_rt_renderer* r);
-// rt_deform.hip: poses the deformers whose parameters changed (hala_rt_refit, on an idle stream); is a deformer registered on the primitive
-int deform_apply_pending(hala_rt_renderer* r);
+// rt_deform.hip.  deform_pose: every (deformer, parameters) of `items` posed into the arena, on an idle stream -> HALA_OK; kDeformOverflow:
+// a posed position is not finite, the arena is put back and synchronised, `overflowed` (where given) names the offending items, the
+// message is set; HALA_ERR: a device error (or the refusal after one).  It keeps Deformer::applied / posed, the temporal marks and the
+// launch counters; Deformer::pending and dirty are the callers'.  deform_refit: hala_rt_refit's list — the holders of `keyed` (by
+// primitive: the shutter's state at the refit's time), every other dirty deformer and those of `again` with their pending parameters —
+// and what becomes of dirty and pending; *moved: the arena changed.  deform_registered: is a deformer registered on the primitive
+constexpr int kDeformOverflow = 2;
+struct DeformPose { Deformer* d; const Deformer::Params* p; };
+int deform_pose(hala_rt_renderer* r, const std::vector<DeformPose>& items, std::vector<size_t>* overflowed);
+int deform_refit(hala_rt_renderer* r, const std::map<uint32_t, Deformer::Params>& keyed, const std::vector<uint32_t>& again, bool* moved);
 bool deform_registered(const hala_rt_renderer* r, uint32_t prim);
-int find_primitive(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, uint32_t* prim);
-// rt_scene.hip: hala_rt_refit without the restart — hierarchies, packed records, the tree (rebuilt when the instancing flags change)
-int refit_geometry(hala_rt_renderer* r);
+// rt_scene.hip: hala_rt_refit without the restart — hierarchies, packed records, the tree (rebuilt when the instancing flags change) —
+// fitted to what `in` names; it reads and clears nothing of what the caller recorded
+struct RefitInputs {
+  const std::vector<Mat4>& locals;                    // one per node
+  const std::vector<hala_material_desc>& materials;
+  bool arena_changed;                                 // the vertex arena changed since the tree was fitted
+  bool opacity0_edit;                                 // a material edit touched an opacity-0 material
+};
+int refit_geometry(hala_rt_renderer* r, const RefitInputs& in);
 // rt_shutter.hip (RENDER_SPEC §18).  shutter_refit: hala_rt_refit's geometry part with the recorded keys applied, the scene left at step
 // 0; shutter_step: moves the scene to step `j` between two frames of one accumulation (update_impl, while the shutter is active)
 int shutter_refit(hala_rt_renderer* r);
@@ -587,6 +603,36 @@ int shutter_step(hala_rt_renderer* r, uint32_t j);
 int crypto_prepare(hala_rt_renderer* r);
 // rt_tiles.hip
 void compute_tiling(hala_rt_renderer* r);
+
+// ---- shared by the units that edit and pose vertices (rt_scene.hip, rt_deform.hip, rt_shutter.hip, rt_rig.hip) ---------------------------
+inline int find_primitive(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, uint32_t* prim) {
+  if (mesh_index + 1u >= r->hs.mesh_first_prim.size() || mesh_index == 0xffffffffu) RT_FAIL("The mesh does not exist.");
+  const uint32_t first = r->hs.mesh_first_prim[mesh_index], end = r->hs.mesh_first_prim[mesh_index + 1u];
+  if (primitive_index >= end - first) RT_FAIL("The primitive does not exist.");
+  *prim = first + primitive_index;
+  return HALA_OK;
+}
+// RENDER_SPEC §16: no motion is known under a deformation; every instance of the primitive starts without history
+inline void mark_no_history(hala_rt_renderer* r, uint32_t prim) {
+  if (!r->temporal.enabled) return;
+  for (size_t i = 0; i < r->hs.instance_prim.size() && i < r->temporal.inst_marked.size(); ++i)
+    if (r->hs.instance_prim[i] == prim) { r->temporal.inst_marked[i] = 1; r->temporal.table_dirty = true; }
+}
+// Overflow words of a group of launches (k_deform, k_shutter_lerp: a launch sets its word to 1): `n` words of `words` are cleared,
+// `launch(words.ptr)` queues the kernels on `s`, and where `flags` is given they are read back behind them (one copy, one wait) and
+// *any says whether one is set.  -> HALA_OK, or HALA_ERR with the message set
+template <class Launch>
+int launch_flagged(DeviceArray<uint32_t>& words, size_t n, hipStream_t s, Launch launch, std::vector<uint32_t>* flags, bool* any) {
+  RT_HIP(words.resize(n));
+  RT_HIP(hipMemsetAsync(words.ptr, 0, n * 4, s));
+  if (launch(words.ptr) != HALA_OK) return HALA_ERR;
+  if (!flags) return HALA_OK;
+  flags->resize(n);
+  RT_HIP(hipMemcpyAsync(flags->data(), words.ptr, n * 4, hipMemcpyDeviceToHost, s));
+  RT_HIP(hipStreamSynchronize(s));
+  for (uint32_t f : *flags) *any = *any || f != 0u;
+  return HALA_OK;
+}
 
 }  // namespace rt
 #pragma GCC visibility pop

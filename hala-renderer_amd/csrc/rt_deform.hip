@@ -1,45 +1,23 @@
 // rt_deform.hip — deformers (docs/RENDER_SPEC.md 17; include/halart.h "Deformers"): the registry of one deformer per primitive, the
 // host-side checks of tables and parameters, the launches of k_deform (deform.hip) that hala_rt_refit makes ahead of refitting the
-// tree, and the read-back of a primitive's vertices.  Invariant: the primitive's range of the vertex arena holds the rest pose while
-// Deformer::posed is false, and k_deform(rest, tables, Deformer::applied) otherwise; HostPrimitive::vertices stays the rest pose.
+// tree, and the read-back of a primitive's vertices.  Invariants: the primitive's range of the vertex arena holds the rest pose while
+// Deformer::posed is false, and k_deform(rest, tables, Deformer::applied) otherwise; HostPrimitive::vertices stays the rest pose;
+// Deformer::pending and dirty hold what the caller recorded, and posing (deform_pose) takes its parameters as arguments.
 #include "renderer_state.h"
 
 namespace rt {
 
-int find_primitive(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, uint32_t* prim) {
-  if (mesh_index + 1u >= r->hs.mesh_first_prim.size() || mesh_index == 0xffffffffu) RT_FAIL("The mesh does not exist.");
-  const uint32_t first = r->hs.mesh_first_prim[mesh_index], end = r->hs.mesh_first_prim[mesh_index + 1u];
-  if (primitive_index >= end - first) RT_FAIL("The primitive does not exist.");
-  *prim = first + primitive_index;
-  return HALA_OK;
-}
-
-static bool all_finite(const float* v, size_t n) {
-  for (size_t k = 0; k < n; ++k)
-    if (!std::isfinite(v[k])) return false;
-  return true;
-}
-
-// RENDER_SPEC §16: no motion is known under a deformation; every instance of the primitive starts without history
-static void mark_no_history(hala_rt_renderer* r, uint32_t prim) {
-  if (!r->temporal.enabled) return;
-  for (size_t i = 0; i < r->hs.instance_prim.size() && i < r->temporal.inst_marked.size(); ++i)
-    if (r->hs.instance_prim[i] == prim) { r->temporal.inst_marked[i] = 1; r->temporal.table_dirty = true; }
-}
-
-static hala_vertex* arena_of(hala_rt_renderer* r, uint32_t prim) { return r->d_vertices.ptr + r->prim_vertex_offset[prim]; }
-
 // the arena's range of the primitive <- the rest pose (stream-ordered); the tree follows at the next refit
 static int restore_rest(hala_rt_renderer* r, Deformer& d) {
   if (d.vertex_count)
-    RT_HIP(hipMemcpyAsync(arena_of(r, d.prim), d.d_rest.ptr, (size_t)d.vertex_count * sizeof(hala_vertex), hipMemcpyDeviceToDevice, r->stream));
+    RT_HIP(hipMemcpyAsync(r->arena(d.prim), d.d_rest.ptr, (size_t)d.vertex_count * sizeof(hala_vertex), hipMemcpyDeviceToDevice, r->stream));
   d.posed = false;
   return HALA_OK;
 }
 
 static DeformTables tables_of(hala_rt_renderer* r, Deformer& d, uint32_t* flag) {
   DeformTables t{};
-  t.rest = d.d_rest.ptr; t.out = arena_of(r, d.prim);
+  t.rest = d.d_rest.ptr; t.out = r->arena(d.prim);
   t.dp = d.target_count ? d.d_dp.ptr : nullptr;
   t.dn = d.has_dn ? d.d_dn.ptr : nullptr;
   t.dt = d.has_dt ? d.d_dt.ptr : nullptr;
@@ -65,12 +43,11 @@ static int launch(hala_rt_renderer* r, Deformer& d, const Deformer::Params& p, u
 // Two or more deformers at once (k_deform_batch): segment table, block map, active targets and palettes are laid out in
 // DeformState::h_stage, copied to the device in one piece and posed by one launch.  Item k raises flags[k].  (The staged bytes stay
 // as they are until the caller has synchronised, as the palettes of the single launch do.)
-struct BatchItem { Deformer* d; const Deformer::Params* p; uint32_t* flag; };
-static int launch_batch(hala_rt_renderer* r, const std::vector<BatchItem>& items) {
+static int launch_batch(hala_rt_renderer* r, const std::vector<DeformPose>& items, uint32_t* flags) {
   DeformState& ds = r->deform;
   size_t blocks = 0, actives = 0, palette_floats = 0;
   uint32_t max_joints = 0;
-  for (const BatchItem& it : items) {
+  for (const DeformPose& it : items) {
     blocks += (it.d->vertex_count + kDeformThreads - 1) / kDeformThreads;
     for (float w : it.p->weights) actives += w != 0.0f;
     palette_floats += (size_t)it.d->joint_count * 12u;
@@ -92,7 +69,7 @@ static int launch_batch(hala_rt_renderer* r, const std::vector<BatchItem>& items
   for (size_t k = 0; k < items.size(); ++k) {
     Deformer& d = *items[k].d;
     const Deformer::Params& p = *items[k].p;
-    seg[k].t = tables_of(r, d, items[k].flag);
+    seg[k].t = tables_of(r, d, flags + k);
     seg[k].t.palette = d_pal + np;
     seg[k].active_first = na;
     for (uint32_t t = 0; t < d.target_count; ++t)
@@ -110,70 +87,71 @@ static int launch_batch(hala_rt_renderer* r, const std::vector<BatchItem>& items
 }
 
 // one deformer: k_deform as always; kDeformBatchMin or more: one launch of k_deform_batch (DESIGN.md 19 has the measurement behind it)
-static int launch_all(hala_rt_renderer* r, const std::vector<BatchItem>& items, bool count) {
+static int launch_all(hala_rt_renderer* r, const std::vector<DeformPose>& items, uint32_t* flags, bool count) {
   if (items.empty()) return HALA_OK;
   if (items.size() >= kDeformBatchMin) {
-    if (launch_batch(r, items) != HALA_OK) return HALA_ERR;
+    if (launch_batch(r, items, flags) != HALA_OK) return HALA_ERR;
     if (count) { r->deform.launches += 1; r->deform.batch_launches += 1; r->deform.segments += items.size(); }
     return HALA_OK;
   }
-  for (const BatchItem& it : items) {
-    if (launch(r, *it.d, *it.p, it.flag) != HALA_OK) return HALA_ERR;
+  for (size_t k = 0; k < items.size(); ++k) {
+    if (launch(r, *items[k].d, *items[k].p, flags + k) != HALA_OK) return HALA_ERR;
     if (count) { r->deform.launches += 1; r->deform.segments += 1; }
   }
   return HALA_OK;
 }
 
-// hala_rt_refit, on an idle stream: poses every deformer whose parameters changed.  Overflow to a non-finite position: the arena is put
-// back by running the kernel again with the last applied parameters — it is deterministic, and the common case pays for no spare
-// buffer and no copy —, the offending parameters are dropped, and the refit fails.
-static int apply_pending(hala_rt_renderer* r);
-// A HIP error between the first launch and the bookkeeping leaves some deformers posed on the device and none recorded as such (such
-// errors are sticky: the device is gone).  The invariant above no longer holds, so every later refit is refused until hala_rt_set_scene
-// uploads the arena again.
-int deform_apply_pending(hala_rt_renderer* r) {
-  if (r->deform.lost) RT_FAIL("A device error interrupted an earlier deformation and the vertices on the device are undefined: set the scene again.");
-  r->deform.lost = true;
-  const int e = apply_pending(r);
-  // (the overflow refusal comes back with the arena restored and synchronised: that one is not a loss)
-  if (e == HALA_OK || r->deform.restored) r->deform.lost = false;
-  r->deform.restored = false;
-  return e;
-}
-static int apply_pending(hala_rt_renderer* r) {
-  std::vector<Deformer*> dirty;
-  for (auto& kv : r->deform.by_prim)
-    if (kv.second->dirty) dirty.push_back(kv.second.get());
-  if (dirty.empty()) return HALA_OK;
-  RT_HIP(r->deform.d_flags.resize(dirty.size()));
-  RT_HIP(hipMemsetAsync(r->deform.d_flags.ptr, 0, dirty.size() * 4, r->stream));
-  std::vector<BatchItem> items;
-  for (size_t k = 0; k < dirty.size(); ++k) items.push_back(BatchItem{dirty[k], &dirty[k]->pending, r->deform.d_flags.ptr + k});
-  if (launch_all(r, items, true) != HALA_OK) return HALA_ERR;
-  std::vector<uint32_t> flags(dirty.size());
-  RT_HIP(hipMemcpyAsync(flags.data(), r->deform.d_flags.ptr, flags.size() * 4, hipMemcpyDeviceToHost, r->stream));
-  RT_HIP(hipStreamSynchronize(r->stream));
+// Overflow to a non-finite position: the arena is put back by running the kernel again with the last applied parameters — it is
+// deterministic, and the common case pays for no spare buffer and no copy.  A HIP error between the first launch and the bookkeeping
+// leaves some deformers posed on the device and none recorded as such (such errors are sticky: the device is gone).  The invariant above
+// no longer holds, so every later call is refused until hala_rt_set_scene uploads the arena again: `lost` stands unless the call
+// returns with the arena posed or put back.
+int deform_pose(hala_rt_renderer* r, const std::vector<DeformPose>& items, std::vector<size_t>* overflowed) {
+  DeformState& ds = r->deform;
+  if (ds.lost) RT_FAIL("A device error interrupted an earlier deformation and the vertices on the device are undefined: set the scene again.");
+  if (items.empty()) return HALA_OK;
+  ds.lost = true;
+  std::vector<uint32_t> flags;
   bool overflow = false;
-  for (uint32_t f : flags) overflow = overflow || f != 0u;
+  if (launch_flagged(ds.d_flags, items.size(), r->stream, [&](uint32_t* words) { return launch_all(r, items, words, true); }, &flags, &overflow) != HALA_OK)
+    return HALA_ERR;
   if (overflow) {
-    items.clear();
-    for (size_t k = 0; k < dirty.size(); ++k) {
-      Deformer& d = *dirty[k];
-      if (!d.posed) { if (restore_rest(r, d) != HALA_OK) return HALA_ERR; }
-      else items.push_back(BatchItem{&d, &d.applied, r->deform.d_flags.ptr + k});
+    std::vector<DeformPose> back;
+    for (const DeformPose& it : items) {
+      if (!it.d->posed) { if (restore_rest(r, *it.d) != HALA_OK) return HALA_ERR; }
+      else back.push_back(DeformPose{it.d, &it.d->applied});
     }
-    if (launch_all(r, items, false) != HALA_OK) return HALA_ERR;
+    if (launch_all(r, back, ds.d_flags.ptr, false) != HALA_OK) return HALA_ERR;
     RT_HIP(hipStreamSynchronize(r->stream));
-    for (size_t k = 0; k < dirty.size(); ++k)
-      if (flags[k]) { dirty[k]->pending = dirty[k]->applied; dirty[k]->dirty = false; }
-    r->deform.restored = true;
-    RT_FAIL("Vertex position is not finite.");
+    for (size_t k = 0; k < items.size() && overflowed; ++k)
+      if (flags[k]) overflowed->push_back(k);
+    ds.lost = false;
+    set_last_error("Vertex position is not finite.");
+    return kDeformOverflow;
   }
-  for (Deformer* d : dirty) {
-    d->applied = d->pending; d->dirty = false; d->posed = true;
-    mark_no_history(r, d->prim);
+  for (const DeformPose& it : items) {
+    it.d->applied = *it.p; it.d->posed = true;
+    mark_no_history(r, it.d->prim);
   }
-  r->vertices_dirty = true;
+  ds.lost = false;
+  return HALA_OK;
+}
+
+// On success nothing of the list is dirty any more; an unkeyed deformer whose pending parameters overflowed drops them, and the refit fails.
+int deform_refit(hala_rt_renderer* r, const std::map<uint32_t, Deformer::Params>& keyed, const std::vector<uint32_t>& again, bool* moved) {
+  std::vector<DeformPose> items;
+  for (auto& kv : r->deform.by_prim) {
+    auto key = keyed.find(kv.first);
+    if (key != keyed.end()) items.push_back(DeformPose{kv.second.get(), &key->second});
+    else if (kv.second->dirty || std::count(again.begin(), again.end(), kv.first)) items.push_back(DeformPose{kv.second.get(), &kv.second->pending});
+  }
+  std::vector<size_t> overflowed;
+  const int e = deform_pose(r, items, &overflowed);
+  for (size_t k : overflowed)
+    if (!keyed.count(items[k].d->prim)) { items[k].d->pending = items[k].d->applied; items[k].d->dirty = false; }
+  if (e != HALA_OK) return HALA_ERR;
+  for (const DeformPose& it : items) it.d->dirty = false;
+  if (!items.empty()) *moved = true;
   return HALA_OK;
 }
 
@@ -285,7 +263,7 @@ int hala_rt_read_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t pri
   *count = (uint32_t)nv;
   const size_t n = std::min<size_t>(capacity, nv);
   if (dst && n) {
-    RT_HIP(hipMemcpyAsync(dst, arena_of(r, prim), n * sizeof(hala_vertex), hipMemcpyDeviceToHost, r->stream));
+    RT_HIP(hipMemcpyAsync(dst, r->arena(prim), n * sizeof(hala_vertex), hipMemcpyDeviceToHost, r->stream));
     RT_HIP(hipStreamSynchronize(r->stream));
   }
   return HALA_OK;

@@ -21,13 +21,13 @@ int upload_packed(hala_rt_renderer* r, bool geometry) {
   RT_HIP(r->d_vertices.resize(nv)); RT_HIP(r->d_indices.resize(ni));
   for (size_t k = 0; k < hs.prims.size(); ++k) {
     const auto& p = hs.prims[k];
-    if (!p.vertices.empty()) RT_HIP(hipMemcpyAsync(r->d_vertices.ptr + r->prim_vertex_offset[k], p.vertices.data(), p.vertices.size() * sizeof(hala_vertex), hipMemcpyHostToDevice, r->stream));
+    if (!p.vertices.empty()) RT_HIP(hipMemcpyAsync(r->arena(k), p.vertices.data(), p.vertices.size() * sizeof(hala_vertex), hipMemcpyHostToDevice, r->stream));
     if (!p.indices.empty()) RT_HIP(hipMemcpyAsync(r->d_indices.ptr + r->prim_index_offset[k], p.indices.data(), p.indices.size() * 4, hipMemcpyHostToDevice, r->stream));
   }
   }
   for (size_t i = 0; i < hs.instances.size(); ++i) {
     const uint32_t p = hs.instance_prim[i];
-    hs.instances[i].vertices = reinterpret_cast<uint64_t>(r->d_vertices.ptr + r->prim_vertex_offset[p]);  // get_device_address (:869)
+    hs.instances[i].vertices = reinterpret_cast<uint64_t>(r->arena(p));  // get_device_address (:869)
     hs.instances[i].indices = reinterpret_cast<uint64_t>(r->d_indices.ptr + r->prim_index_offset[p]);     // (:870)
   }
   RT_HIP(r->d_cameras.upload(hs.cameras.data(), hs.cameras.size(), r->stream));
@@ -627,28 +627,24 @@ int hala_rt_update_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
   if (!r || !vertices) RT_FAIL("Invalid argument.");
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
-  if (mesh_index + 1u >= r->hs.mesh_first_prim.size()) RT_FAIL("The mesh does not exist.");
-  const uint32_t first = r->hs.mesh_first_prim[mesh_index], end = r->hs.mesh_first_prim[mesh_index + 1u];
-  if (primitive_index >= end - first) RT_FAIL("The primitive does not exist.");
-  HostPrimitive& p = r->hs.prims[first + primitive_index];
-  if (deform_registered(r, first + primitive_index)) RT_FAIL("The primitive has a deformer: clear it first (hala_rt_clear_deformer).");
-  if (r->shutter.rec.vertices.count(first + primitive_index)) RT_FAIL("The primitive has shutter keys: clear them first (hala_rt_set_vertex_keys with both keys NULL).");
+  uint32_t prim = 0;
+  if (find_primitive(r, mesh_index, primitive_index, &prim) != HALA_OK) return HALA_ERR;
+  HostPrimitive& p = r->hs.prims[prim];
+  if (deform_registered(r, prim)) RT_FAIL("The primitive has a deformer: clear it first (hala_rt_clear_deformer).");
+  if (r->shutter.rec.vertices.count(prim)) RT_FAIL("The primitive has shutter keys: clear them first (hala_rt_set_vertex_keys with both keys NULL).");
   if (vertex_count != p.vertices.size()) RT_FAIL("The vertex count differs from the primitive's (" + std::to_string(p.vertices.size()) + "): refit keeps the topology, use set_scene + commit.");
   for (uint32_t k = 0; k < vertex_count; ++k)
-    if (!std::isfinite(vertices[k].position[0]) || !std::isfinite(vertices[k].position[1]) || !std::isfinite(vertices[k].position[2])) RT_FAIL("Vertex position is not finite.");
+    if (!all_finite(vertices[k].position, 3)) RT_FAIL("Vertex position is not finite.");
   memcpy(p.vertices.data(), vertices, (size_t)vertex_count * sizeof(hala_vertex));
+  r->vertices_dirty = true;
   if (r->shutter.act.active()) {  // RENDER_SPEC §18: the steps until the refit read the arena; the refit uploads the host copy
-    r->shutter.stale.push_back(first + primitive_index);
-    r->vertices_dirty = true;
+    r->shutter.stale.push_back(prim);
     return HALA_OK;
   }
   // the copy below reads the renderer's own host copy, which outlives it; earlier frames still read the arena: wait for them
   RT_HIP(hipStreamSynchronize(r->stream));
-  r->vertices_dirty = true;
-  if (r->temporal.enabled)  // RENDER_SPEC §16: no motion is known under a deformation; every instance of the primitive starts without history
-    for (size_t i = 0; i < r->hs.instance_prim.size() && i < r->temporal.inst_marked.size(); ++i)
-      if (r->hs.instance_prim[i] == first + primitive_index) { r->temporal.inst_marked[i] = 1; r->temporal.table_dirty = true; }
-  if (vertex_count) RT_HIP(hipMemcpyAsync(r->d_vertices.ptr + r->prim_vertex_offset[first + primitive_index], p.vertices.data(), (size_t)vertex_count * sizeof(hala_vertex), hipMemcpyHostToDevice, r->stream));
+  mark_no_history(r, prim);
+  if (vertex_count) RT_HIP(hipMemcpyAsync(r->arena(prim), p.vertices.data(), (size_t)vertex_count * sizeof(hala_vertex), hipMemcpyHostToDevice, r->stream));
   return HALA_OK;
 }
 int hala_rt_update_material(hala_rt_renderer* r, uint32_t material_index, const hala_material_desc* material) {
@@ -665,13 +661,15 @@ int hala_rt_update_material(hala_rt_renderer* r, uint32_t material_index, const 
 
 namespace rt {
 
-// The geometry part of hala_rt_refit: everything but the restart of the accumulation.  The caller has joined both frame slots, waited,
-// and posed what is posed on the device (deform_apply_pending, k_shutter_lerp).  A step of the shutter (RENDER_SPEC §18) is this alone.
-int refit_geometry(hala_rt_renderer* r) {
+// The geometry part of hala_rt_refit: everything but the restart of the accumulation, fitted to `in` (renderer_state.h).  The caller has
+// joined both frame slots, waited, and posed what is posed on the device (deform_pose, k_shutter_lerp).  A step of the shutter
+// (RENDER_SPEC §18) is this alone.  What the caller recorded — HostNode::local, HostScene::materials, the dirty flags — is neither read
+// nor written here.
+int refit_geometry(hala_rt_renderer* r, const RefitInputs& in) {
   const std::vector<hala_gpu_mesh_data> before = r->hs.instances;  // object -> world of every instance as the tree was fitted to it
   const std::vector<uint8_t> kinds_before = r->material_kind;
-  r->hs.update_node_hierarchies();
-  const std::string e = r->hs.pack();
+  r->hs.update_node_hierarchies(in.locals);
+  const std::string e = r->hs.pack(in.materials);
   if (!e.empty()) RT_FAIL(e);
   if (upload_packed(r, false) != HALA_OK) return HALA_ERR;
   if (update_texture_bundles(r, false) != HALA_OK) return HALA_ERR;  // a material edit may have changed which maps a material references
@@ -680,24 +678,20 @@ int refit_geometry(hala_rt_renderer* r) {
   const bool had_invisible = r->any_invisible;
   const std::vector<uint8_t> classes_before = r->material_any_class;
   if (attach_any_triangles(r) != HALA_OK) return HALA_ERR;
-  if (classes_before != r->material_any_class) r->materials_dirty_any = true;  // the any-hit copy of the triangles must be rewritten
   // (a material edit can change which triangles the shadow rays see: their copy is rewritten by the refit pass)
   // (the BVH-order triangles carry their material's shading kind: rewritten by the refit pass as well)
-  bool geometry_moved = r->vertices_dirty || r->materials_dirty_any || had_invisible != r->any_invisible || before.size() != r->hs.instances.size() ||
-                        kinds_before != r->material_kind;
-  r->materials_dirty_any_refit = r->materials_dirty_any;
-  r->materials_dirty_any = false;
+  // what the trees hold changed: vertices or materials (the any-hit copy of the triangles must be rewritten when a class changed)
+  const bool content = in.arena_changed || in.opacity0_edit || classes_before != r->material_any_class || had_invisible != r->any_invisible ||
+                       kinds_before != r->material_kind;
+  bool geometry_moved = content || before.size() != r->hs.instances.size();
   for (size_t i = 0; i < before.size() && !geometry_moved; ++i) geometry_moved = memcmp(before[i].transform, r->hs.instances[i].transform, 64) != 0;
   // which instances are intersected in object space may have changed (a transform that is no longer invertible, or is again): rebuild
   std::vector<uint8_t> flags;
   classify_instances(r, &flags);
-  if (flags != r->inst_instanced) {
-    if (build_bvh(r) != HALA_OK) return HALA_ERR;
-    r->vertices_dirty = false;
-  } else if (r->two_level) {
+  if (flags != r->inst_instanced) return build_bvh(r);
+  if (r->two_level) {
     // RENDER_SPEC 4.5: a node that moves an instanced primitive only touches the instance levels (rebuilt on the host below).  The trees
-    // underneath are refitted when what THEY hold changed: vertices or materials (any tree), the transform of a flattened instance (the world tree)
-    const bool content = r->vertices_dirty || r->materials_dirty_any_refit || had_invisible != r->any_invisible || kinds_before != r->material_kind;
+    // underneath are refitted when what THEY hold changed: `content` (any tree), the transform of a flattened instance (the world tree)
     r->bvh.tris_any = r->any_invisible ? r->d_tris_any.ptr : nullptr;
     for (auto& bl : r->blas) {
       bool moved = content;
@@ -706,13 +700,12 @@ int refit_geometry(hala_rt_renderer* r) {
       if (moved && blas_build_or_refit(r, *bl, true) != HALA_OK) return HALA_ERR;
     }
     if (build_instance_levels(r) != HALA_OK) return HALA_ERR;
-    if (configure_traversal(r) != HALA_OK) return HALA_ERR;
-    r->vertices_dirty = false;
-  } else if (geometry_moved) {
+    return configure_traversal(r);
+  }
+  if (geometry_moved) {
     const std::string e2 = bvh_refit(r->bvh, r->stream);
     if (!e2.empty()) RT_FAIL(e2);
-    if (configure_traversal(r) != HALA_OK) return HALA_ERR;
-    r->vertices_dirty = false;
+    return configure_traversal(r);
   }
   return HALA_OK;
 }

@@ -1,61 +1,43 @@
 // rt_shutter.hip — shutter motion blur (docs/RENDER_SPEC.md 18; include/halart.h "Shutter"): the keys the setters record, the refit
 // that applies them and leaves the scene at step 0, and the step that moves the scene to another instant of the shutter interval
 // between two frames of one accumulation.  Node and deformer keys are interpolated here, on the host; vertex keys by k_shutter_lerp
-// (shutter.hip).  Invariants: HostNode::local, Deformer::pending and HostPrimitive::vertices always hold what the caller recorded (for a
-// keyed holder: its open key); a step or a refit writes the state at its time over them only while refit_geometry runs.
-// ShutterState::act is what the device stands at, together with ShutterState::step / time.
+// (shutter.hip).  Invariant: HostNode::local, HostScene::materials, Deformer::pending and HostPrimitive::vertices always hold what the
+// caller recorded (for a keyed holder: its open key).  A refit or a step computes the state at its time beside them and hands it to
+// refit_geometry (RefitInputs) and deform_pose as arguments; nothing here writes them.  ShutterState::act is what the device stands at,
+// together with ShutterState::step / time.
 #include "renderer_state.h"
 
 namespace rt {
 
-static bool finite_all(const float* v, size_t n) {
-  for (size_t k = 0; k < n; ++k)
-    if (!std::isfinite(v[k])) return false;
-  return true;
-}
-
-static hala_vertex* arena(hala_rt_renderer* r, uint32_t prim) { return r->d_vertices.ptr + r->prim_vertex_offset[prim]; }
-
 static int upload_host_copy(hala_rt_renderer* r, uint32_t prim) {
   const HostPrimitive& p = r->hs.prims[prim];
   if (!p.vertices.empty())
-    RT_HIP(hipMemcpyAsync(arena(r, prim), p.vertices.data(), p.vertices.size() * sizeof(hala_vertex), hipMemcpyHostToDevice, r->stream));
-  r->vertices_dirty = true;
+    RT_HIP(hipMemcpyAsync(r->arena(prim), p.vertices.data(), p.vertices.size() * sizeof(hala_vertex), hipMemcpyHostToDevice, r->stream));
   return HALA_OK;
 }
 
-// the vertex keys of `k` at `tau` into the arena (in a step: only the ones that move); overflow, where asked for: some interpolated
-// position is not finite (one read-back and one wait).  Only the refit asks: `b - a` does not depend on tau and the state lies between
-// the keys, so keys that overflow do so at step 0 already, and a step queues its launches without waiting for them
-static int lerp_vertices(hala_rt_renderer* r, const ShutterKeys& k, float tau, bool step, bool* overflow) {
-  if (overflow) *overflow = false;
+// the vertex keys of `k` at `tau` into the arena (in a step: only the ones that move; *moved: some were); overflow, where asked for: some
+// interpolated position is not finite (one read-back and one wait).  Only the refit asks: `b - a` does not depend on tau and the state
+// lies between the keys, so keys that overflow do so at step 0 already, and a step queues its launches without waiting for them
+static int lerp_vertices(hala_rt_renderer* r, const ShutterKeys& k, float tau, bool step, bool* moved, bool* overflow) {
   if (k.vertices.empty()) return HALA_OK;
-  ShutterState& sh = r->shutter;
-  RT_HIP(sh.d_flags.resize(k.vertices.size()));
-  RT_HIP(hipMemsetAsync(sh.d_flags.ptr, 0, k.vertices.size() * 4, r->stream));
-  size_t at = 0, launched = 0;
-  for (const auto& kv : k.vertices) {
-    const ShutterVertexKeys& vk = *kv.second;
-    uint32_t* flag = sh.d_flags.ptr + at++;
-    if (step && !vk.moving) continue;  // the arena holds it since the refit
-    ShutterLerp t{};
-    t.open = reinterpret_cast<const float*>(vk.d_open.ptr); t.close = reinterpret_cast<const float*>(vk.d_close.ptr);
-    t.out = reinterpret_cast<float*>(arena(r, kv.first));
-    t.words = (size_t)vk.vertex_count * (sizeof(hala_vertex) / 4);
-    t.tau = tau; t.flag = flag;
-    launch_shutter_lerp(t, r->stream);
-    ++launched;
-  }
-  RT_HIP(hipGetLastError());
-  if (!launched) return HALA_OK;
-  r->vertices_dirty = true;
-  if (overflow) {
-    std::vector<uint32_t> flags(k.vertices.size());
-    RT_HIP(hipMemcpyAsync(flags.data(), sh.d_flags.ptr, flags.size() * 4, hipMemcpyDeviceToHost, r->stream));
-    RT_HIP(hipStreamSynchronize(r->stream));
-    for (uint32_t f : flags) *overflow = *overflow || f != 0u;
-  }
-  return HALA_OK;
+  std::vector<uint32_t> flags;
+  return launch_flagged(r->shutter.d_flags, k.vertices.size(), r->stream, [&](uint32_t* flag) {
+    for (const auto& kv : k.vertices) {
+      const ShutterVertexKeys& vk = *kv.second;
+      ShutterLerp t{};
+      t.flag = flag++;
+      if (step && !vk.moving) continue;  // the arena holds it since the refit
+      t.open = reinterpret_cast<const float*>(vk.d_open.ptr); t.close = reinterpret_cast<const float*>(vk.d_close.ptr);
+      t.out = reinterpret_cast<float*>(r->arena(kv.first));
+      t.words = (size_t)vk.vertex_count * (sizeof(hala_vertex) / 4);
+      t.tau = tau;
+      launch_shutter_lerp(t, r->stream);
+      *moved = true;
+    }
+    RT_HIP(hipGetLastError());
+    return HALA_OK;
+  }, overflow ? &flags : nullptr, overflow);
 }
 
 // the arena ranges that `k` wrote, back to what they held: `prev` at `prev_tau` (the kernel again: it is deterministic, as in
@@ -67,67 +49,65 @@ static int restore_vertices(hala_rt_renderer* r, const ShutterKeys& k, const Shu
     if (it != prev.vertices.end()) again.vertices[kv.first] = it->second;
     else if (upload_host_copy(r, kv.first) != HALA_OK) return HALA_ERR;
   }
-  if (lerp_vertices(r, again, prev_tau, false, nullptr) != HALA_OK) return HALA_ERR;
+  bool moved = false;
+  if (lerp_vertices(r, again, prev_tau, false, &moved, nullptr) != HALA_OK) return HALA_ERR;
   RT_HIP(hipStreamSynchronize(r->stream));
   return HALA_OK;
 }
 
-static void mix_params(const ShutterDeformKeys& k, float tau, Deformer::Params* out) {
-  out->weights.resize(k.open.weights.size()); out->palette.resize(k.open.palette.size());
-  for (size_t i = 0; i < out->weights.size(); ++i) out->weights[i] = shutter_mix(k.open.weights[i], k.close.weights[i], tau);
-  for (size_t i = 0; i < out->palette.size(); ++i) out->palette[i] = shutter_mix(k.open.palette[i], k.close.palette[i], tau);
+static Deformer::Params mix_params(const ShutterDeformKeys& k, float tau) {
+  Deformer::Params out;
+  out.weights.resize(k.open.weights.size()); out.palette.resize(k.open.palette.size());
+  for (size_t i = 0; i < out.weights.size(); ++i) out.weights[i] = shutter_mix(k.open.weights[i], k.close.weights[i], tau);
+  for (size_t i = 0; i < out.palette.size(); ++i) out.palette[i] = shutter_mix(k.open.palette[i], k.close.palette[i], tau);
+  return out;
 }
 
-// What lives on the device, at `tau`: the vertex keys, then the keyed deformers through Deformer::pending and deform_apply_pending (k_deform
-// as it is).  step: the deformers without keys wait for the refit.  A position that is not finite: the arena is put back to `prev` at
-// `prev_tau`, the call fails, and every Deformer::pending is what the caller recorded, as on success.
-static int pose_device(hala_rt_renderer* r, const ShutterKeys& k, float tau, bool step, const ShutterKeys& prev, float prev_tau) {
+// What lives on the device, at `tau`: the vertex keys, then the keyed deformers at their mix (deform_pose: k_deform as it is).  A refit
+// poses every keyed deformer and what the caller recorded for the others; a step the moving keyed ones only: the deformers without keys
+// wait for the refit.  *moved: the arena changed.  A position that is not finite: the arena is put back to `prev` at `prev_tau` and the
+// call fails.
+static int pose_device(hala_rt_renderer* r, const ShutterKeys& k, float tau, bool step, const ShutterKeys& prev, float prev_tau, bool* moved) {
   bool overflow = false;
-  if (lerp_vertices(r, k, tau, step, step ? nullptr : &overflow) != HALA_OK) return HALA_ERR;
+  if (lerp_vertices(r, k, tau, step, moved, step ? nullptr : &overflow) != HALA_OK) return HALA_ERR;
   if (overflow) {
     if (restore_vertices(r, k, prev, prev_tau) != HALA_OK) return HALA_ERR;
     RT_FAIL("Vertex position is not finite.");
   }
-  if (!step) {
+  std::map<uint32_t, Deformer::Params> keyed;
+  for (const auto& kv : k.deformers)
+    if (!step || kv.second->moving) keyed[kv.first] = mix_params(*kv.second, tau);
+  int e;
+  if (step) {
+    std::vector<DeformPose> items;
+    for (const auto& kv : keyed) {
+      auto d = r->deform.by_prim.find(kv.first);
+      if (d != r->deform.by_prim.end()) items.push_back(DeformPose{d->second.get(), &kv.second});
+    }
+    e = deform_pose(r, items, nullptr);
+    if (e == HALA_OK && !items.empty()) *moved = true;
+  } else {
     // the refit: primitives whose vertex keys were cleared, or that hala_rt_update_vertices edited while steps were reading the arena, get
     // the host copy — ahead of k_deform, which poses over it where such a primitive has a deformer by now.  (The list is kept until the
     // refit succeeds: uploading again is harmless.)
     ShutterState& sh = r->shutter;
+    std::vector<uint32_t> again;  // deformers that are posed with the recorded parameters whether or not they are dirty
     for (const auto& kv : prev.vertices) sh.stale.push_back(kv.first);
     std::sort(sh.stale.begin(), sh.stale.end());
     sh.stale.erase(std::unique(sh.stale.begin(), sh.stale.end()), sh.stale.end());
     for (uint32_t prim : sh.stale) {
       if (prim >= r->hs.prims.size() || k.vertices.count(prim)) continue;
       if (upload_host_copy(r, prim) != HALA_OK) return HALA_ERR;
+      *moved = true;
       auto d = r->deform.by_prim.find(prim);  // its deformer's pose went with the range
-      if (d != r->deform.by_prim.end() && d->second->posed) d->second->dirty = true;
+      if (d != r->deform.by_prim.end() && d->second->posed) again.push_back(prim);
     }
     // a deformer whose keys were cleared or replaced since the last refit stands at some step's pose: the recorded pose is due
     for (const auto& kv : prev.deformers) {
       auto now = k.deformers.find(kv.first);
-      auto d = r->deform.by_prim.find(kv.first);
-      if (d != r->deform.by_prim.end() && (now == k.deformers.end() || now->second != kv.second)) d->second->dirty = true;
+      if (now == k.deformers.end() || now->second != kv.second) again.push_back(kv.first);
     }
-  }
-  struct Saved { Deformer* d; Deformer::Params pending; bool dirty, keyed; };
-  std::vector<Saved> saved;
-  for (auto& kv : r->deform.by_prim) {
-    Deformer& d = *kv.second;
-    auto it = k.deformers.find(kv.first);
-    if (it == k.deformers.end()) {
-      if (step) { saved.push_back(Saved{&d, {}, d.dirty, false}); d.dirty = false; }
-      continue;
-    }
-    saved.push_back(Saved{&d, d.pending, d.dirty, true});
-    if (step && !it->second->moving) { d.dirty = false; continue; }
-    mix_params(*it->second, tau, &d.pending);
-    d.dirty = true;
-  }
-  const int e = deform_apply_pending(r);
-  for (Saved& s : saved) {
-    if (!s.keyed) { s.d->dirty = s.dirty; continue; }
-    s.d->pending = std::move(s.pending);
-    s.d->dirty = e == HALA_OK ? false : s.dirty;  // (the next refit poses every deformer keyed now or at the last refit again)
+    e = deform_refit(r, keyed, again, moved);
   }
   if (e != HALA_OK) {
     const std::string msg = get_last_error();
@@ -137,40 +117,42 @@ static int pose_device(hala_rt_renderer* r, const ShutterKeys& k, float tau, boo
   return HALA_OK;
 }
 
-// HostNode::local of the keyed nodes at `tau`
-static void write_node_keys(hala_rt_renderer* r, const ShutterKeys& k, float tau) {
+// `locals` with the keyed nodes at `tau`
+static std::vector<Mat4> mix_node_keys(std::vector<Mat4> locals, const ShutterKeys& k, float tau) {
   for (const auto& kv : k.nodes) {
-    if (kv.first >= r->hs.nodes.size()) continue;
-    float* m = r->hs.nodes[kv.first].local.m;
-    for (int i = 0; i < 16; ++i) m[i] = shutter_mix(kv.second.open[i], kv.second.close[i], tau);
+    if (kv.first >= locals.size()) continue;
+    for (int i = 0; i < 16; ++i) locals[kv.first].m[i] = shutter_mix(kv.second.open[i], kv.second.close[i], tau);
   }
+  return locals;
+}
+
+// hala_rt_refit's geometry part: the tree to what the caller recorded, the keyed nodes at `tau`; the recorded flags go once it stands
+static int refit_recorded(hala_rt_renderer* r, const ShutterKeys& k, float tau, bool moved) {
+  r->vertices_dirty = r->vertices_dirty || moved;
+  if (refit_geometry(r, RefitInputs{mix_node_keys(r->hs.locals(), k, tau), r->hs.materials, r->vertices_dirty, r->materials_dirty_any}) != HALA_OK) return HALA_ERR;
+  r->vertices_dirty = false; r->materials_dirty_any = false;
+  return HALA_OK;
 }
 
 int shutter_refit(hala_rt_renderer* r) {
   ShutterState& sh = r->shutter;
+  bool moved = false;
   if (!sh.rec.any() && !sh.act.any() && sh.stale.empty()) {  // no key anywhere: the refit as it always was
     sh.act = sh.rec;
     sh.step = kShutterNoStep; sh.time = 0.0f;
-    if (deform_apply_pending(r) != HALA_OK) return HALA_ERR;
-    return refit_geometry(r);
+    if (deform_refit(r, {}, {}, &moved) != HALA_OK) return HALA_ERR;
+    return refit_recorded(r, sh.rec, 0.0f, moved);
   }
   const float tau = sh.rec.time(0);
-  if (pose_device(r, sh.rec, tau, false, sh.act, sh.time) != HALA_OK) return HALA_ERR;
+  if (pose_device(r, sh.rec, tau, false, sh.act, sh.time, &moved) != HALA_OK) return HALA_ERR;
   sh.stale.clear();
-  std::vector<std::pair<uint32_t, Mat4>> recorded;
-  for (const auto& kv : sh.rec.nodes)
-    if (kv.first < r->hs.nodes.size()) recorded.emplace_back(kv.first, r->hs.nodes[kv.first].local);
-  write_node_keys(r, sh.rec, tau);
-  const int e = refit_geometry(r);
-  for (const auto& nl : recorded) r->hs.nodes[nl.first].local = nl.second;
-  if (e != HALA_OK) return HALA_ERR;
+  if (refit_recorded(r, sh.rec, tau, moved) != HALA_OK) return HALA_ERR;
   sh.act = sh.rec;
   sh.step = sh.act.any() ? 0u : kShutterNoStep;
   sh.time = tau;
   sh.locals.clear(); sh.materials.clear();
-  if (sh.act.active()) {  // what a step refits from
-    sh.locals.reserve(r->hs.nodes.size());
-    for (const HostNode& n : r->hs.nodes) sh.locals.push_back(n.local);
+  if (sh.act.active()) {  // what a step fits to
+    sh.locals = r->hs.locals();
     sh.materials = r->hs.materials;
   }
   return HALA_OK;
@@ -183,21 +165,10 @@ int shutter_step(hala_rt_renderer* r, uint32_t j) {
   RT_HIP(hipStreamSynchronize(r->stream));
   if (sh.locals.size() != r->hs.nodes.size()) RT_FAIL("internal: the shutter's node snapshot does not belong to the scene");
   const float tau = sh.act.time(j);
-  // the edits recorded since the refit wait for the next one: the step refits from the state the refit found
-  const bool vertices_dirty = r->vertices_dirty, materials_dirty = r->materials_dirty_any;
-  r->vertices_dirty = false; r->materials_dirty_any = false;
-  int e = pose_device(r, sh.act, tau, true, sh.act, sh.time);
-  if (e == HALA_OK) {
-    std::vector<Mat4> recorded(r->hs.nodes.size());
-    for (size_t n = 0; n < recorded.size(); ++n) { recorded[n] = r->hs.nodes[n].local; r->hs.nodes[n].local = sh.locals[n]; }
-    write_node_keys(r, sh.act, tau);
-    std::swap(r->hs.materials, sh.materials);
-    e = refit_geometry(r);
-    std::swap(r->hs.materials, sh.materials);
-    for (size_t n = 0; n < recorded.size(); ++n) r->hs.nodes[n].local = recorded[n];
-  }
-  r->vertices_dirty = vertices_dirty; r->materials_dirty_any = materials_dirty;
-  if (e != HALA_OK) return HALA_ERR;
+  // the edits recorded since the refit wait for the next one: the step fits to the state the refit found, and the recorded flags stay
+  bool moved = false;
+  if (pose_device(r, sh.act, tau, true, sh.act, sh.time, &moved) != HALA_OK) return HALA_ERR;
+  if (refit_geometry(r, RefitInputs{mix_node_keys(sh.locals, sh.act, tau), sh.materials, moved, false}) != HALA_OK) return HALA_ERR;
   sh.step = j; sh.time = tau; ++sh.steps;
   return HALA_OK;
 }
@@ -245,7 +216,7 @@ int hala_rt_set_node_keys(hala_rt_renderer* r, uint32_t node_index, const float 
   if ((open == nullptr) != (close == nullptr)) RT_FAIL("hala_rt_set_node_keys: both keys, or both NULL to clear them.");
   ShutterKeys& k = r->shutter.rec;
   if (!open) { k.nodes.erase(node_index); k.recount(); return HALA_OK; }
-  if (!finite_all(open, 16) || !finite_all(close, 16)) RT_FAIL("A node key is not finite.");
+  if (!all_finite(open, 16) || !all_finite(close, 16)) RT_FAIL("A node key is not finite.");
   ShutterNodeKeys nk;
   memcpy(nk.open, open, 64); memcpy(nk.close, close, 64);
   nk.moving = memcmp(open, close, 64) != 0;
@@ -276,9 +247,9 @@ int hala_rt_set_deformer_keys(hala_rt_renderer* r, uint32_t mesh_index, uint32_t
     RT_FAIL("The weight count differs from the deformer's target count (" + std::to_string(d.target_count) + ").");
   if (palette_open && joint_count != d.joint_count)
     RT_FAIL("The joint count differs from the deformer's joint count (" + std::to_string(d.joint_count) + ").");
-  if (weights_open && (!finite_all(weights_open, weight_count) || !finite_all(weights_close, weight_count))) RT_FAIL("A morph weight is not finite.");
+  if (weights_open && (!all_finite(weights_open, weight_count) || !all_finite(weights_close, weight_count))) RT_FAIL("A morph weight is not finite.");
   const size_t np = (size_t)joint_count * 12u;
-  if (palette_open && (!finite_all(palette_open, np) || !finite_all(palette_close, np))) RT_FAIL("A joint matrix is not finite.");
+  if (palette_open && (!all_finite(palette_open, np) || !all_finite(palette_close, np))) RT_FAIL("A joint matrix is not finite.");
   std::shared_ptr<ShutterDeformKeys> dk(new ShutterDeformKeys());
   dk->open = d.pending; dk->close = d.pending;  // a part without keys keeps the recorded pose at both ends
   if (weights_open) { dk->open.weights.assign(weights_open, weights_open + weight_count); dk->close.weights.assign(weights_close, weights_close + weight_count); }
@@ -311,7 +282,7 @@ int hala_rt_set_vertex_keys(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
   if (vertex_count != p.vertices.size()) RT_FAIL("The vertex count differs from the primitive's (" + std::to_string(p.vertices.size()) + ").");
   for (const hala_vertex* key : {open, close})
     for (uint32_t v = 0; v < vertex_count; ++v)
-      if (!finite_all(key[v].position, 3)) RT_FAIL("Vertex position is not finite.");
+      if (!all_finite(key[v].position, 3)) RT_FAIL("Vertex position is not finite.");
   std::shared_ptr<ShutterVertexKeys> vk(new ShutterVertexKeys());
   vk->vertex_count = vertex_count;
   vk->moving = vertex_count && memcmp(open, close, (size_t)vertex_count * sizeof(hala_vertex)) != 0;

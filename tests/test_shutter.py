@@ -676,6 +676,45 @@ def test_vertices_edited_under_an_active_shutter_then_deformed(halart):
 
 
 @gpu
+@TREE
+def test_edits_recorded_under_an_active_shutter_wait_for_the_refit(halart, oracle, two_level):
+    """node, material and unkeyed-deformer edits recorded between a refit and later steps do not ride along with a step: the frames stay
+    E1's chain, the short block stays at the rest pose and the tree is the scene at the step's time with none of the edits; the refit
+    then applies all four.  (Node edits take another branch of the refit on the two-level tree.)"""
+    s = cornell().scene
+    lights, _ = E.edit_ops("E2-move-lights", s)
+    invisible, _ = E.edit_ops("E6-invisible", s)
+    diffuse, _ = E.edit_ops("E5-glass-to-diffuse", s)
+    pose = {TD.SHORT: TD.cornell_pose(1)[TD.SHORT]}
+    with SE.tree_form(oracle, two_level) as build:
+        r = SE.make(halart, cornell(), build=build)
+        try:
+            TD.register(r)
+            S.apply_keys(r, KEYS["E1"]())
+            r.set_shutter()
+            r.refit()
+            r.update(); r.update()
+            E.apply_to_renderer(r, lights)
+            E.apply_to_renderer(r, invisible)
+            E.apply_to_renderer(r, diffuse)
+            TD.pose(r, pose)
+            r.update(); r.update()
+            SE.assert_images(r, chain_of(oracle, "E1", two_level=two_level), f"before the refit, two_level={two_level}")
+            assert r.read_vertices(TD.SHORT, 0).tobytes() == s.meshes[TD.SHORT].primitives[0].vertices.tobytes()
+            assert status(r) == (1, 1, 3, 0.75, 3)
+            check_scene(oracle, r, S.scene_at(s, KEYS["E1"](), 0.75), "the scene at step 3, none of the edits applied")
+            r.refit()
+            assert status(r) == (1, 1, 0, 0.0, 3)
+            r.update_batch(FRAMES)
+            edited = E.apply_to_scene(s, lights + invisible + diffuse + TD.posed_ops(pose))
+            SE.assert_images(r, S.chain(render_one(oracle), edited, KEYS["E1"](), FRAMES), f"after the refit, two_level={two_level}")
+            assert r.read_vertices(TD.SHORT, 0).tobytes() == TD.posed_ops(pose)[0][3].tobytes()
+            assert status(r) == (1, 1, 3, 0.75, 6)
+        finally:
+            r.close()
+
+
+@gpu
 def test_lifetime(halart, oracle):
     """14: a second commit keeps the keys and the shutter; set_scene drops them"""
     r = keyed(halart, "E1", shutter={})
