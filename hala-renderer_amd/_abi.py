@@ -281,6 +281,12 @@ class RigStatus(C.Structure):  # hala_rig_status, 32 B
                 ("batch_launches", C.c_uint64)]
 
 
+class DeformerNormalsInfo(C.Structure):  # hala_deformer_normals_info, 24 B (docs/RENDER_SPEC.md 17 "Recomputed normals")
+    _fields_ = [("mode", C.c_uint32), ("class_count", C.c_uint32), ("entry_count", C.c_uint32), ("reserved", C.c_uint32), ("launches", C.c_uint64)]
+
+
+DEFORM_NORMALS_AS_POSED, DEFORM_NORMALS_RECOMPUTED = 0, 1
+
 # argtypes / restype of the denoise, adaptive sampling, view and AOV entry points (load_library installs them)
 PROTOTYPES = {
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
@@ -325,6 +331,8 @@ PROTOTYPES = {
     "hala_rt_update_deformer": ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float), C.c_uint32], C.c_int),
     "hala_rt_clear_deformer": ([C.c_void_p, C.c_uint32, C.c_uint32], C.c_int),
     "hala_rt_read_vertices": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)], C.c_int),
+    "hala_rt_set_deformer_normals": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32], C.c_int),
+    "hala_rt_get_deformer_normals": ([C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DeformerNormalsInfo)], C.c_int),
     "hala_shutter_default_params": ([C.POINTER(ShutterParams)], None),
     "hala_rt_set_shutter": ([C.c_void_p, C.POINTER(ShutterParams)], C.c_int),
     "hala_rt_get_shutter_status": ([C.c_void_p, C.POINTER(ShutterStatus)], C.c_int),
@@ -385,6 +393,7 @@ EXPORTS = [
     "hala_temporal_clamp_default_params", "hala_rt_set_temporal_clamp",
     "hala_rt_texture_bundle_info",
     "hala_rt_set_deformer", "hala_rt_update_deformer", "hala_rt_clear_deformer", "hala_rt_read_vertices",
+    "hala_rt_set_deformer_normals", "hala_rt_get_deformer_normals",
     "hala_shutter_default_params", "hala_rt_set_shutter", "hala_rt_get_shutter_status", "hala_rt_set_node_keys", "hala_rt_set_deformer_keys",
     "hala_rt_set_vertex_keys",
     "hala_scene_get_rig", "hala_rig_sample_clip", "hala_rt_set_rig", "hala_rt_pose_rig", "hala_rt_key_rig", "hala_rt_get_rig_pose",

@@ -48,6 +48,18 @@ struct DeformSegment {
 struct DeformBlock { uint32_t segment, first_vertex; };  // 8 B per workgroup
 static_assert(sizeof(DeformSegment) % 8 == 0 && sizeof(DeformBlock) == 8 && sizeof(DeformActiveEntry) == 8, "the staged sections are 8-byte records");
 
+// "Recomputed normals" (RENDER_SPEC 17; deform_normals.hip): what the face pass and the vertex pass read and write of one primitive
+struct NormalsTables {
+  const uint32_t* indices;   // the primitive's triangles in the index arena, 3 per triangle, relative to `vertices`
+  hala_vertex* vertices;     // the primitive's range of the vertex arena, as k_deform just wrote it
+  float4* faces;             // one 16-B face record per triangle (x, y, z, 0): written by the face pass, read by the vertex pass
+  const uint32_t* class_of;  // [vertex]
+  const uint32_t* offsets;   // [class + 1] into `entries`
+  const uint32_t* entries;   // triangle numbers, per class in ascending 3 * triangle + corner
+  uint32_t triangle_count, vertex_count;
+};
+static_assert(sizeof(NormalsTables) == 56, "segments of the batch form are 8-byte records");
+
 // The registered deformer of one primitive.  `applied` and `posed` say what the arena holds (kept by deform_pose, rt_deform.hip);
 // `pending` and `dirty` are what the caller recorded for the next refit (written by the entry points and by that refit alone).
 struct Deformer {
@@ -58,6 +70,15 @@ struct Deformer {
   DeviceArray<uint2> d_joints;
   DeviceArray<float4> d_weights;
   bool has_dn = false, has_dt = false;
+  // Recomputed normals (hala_rt_set_deformer_normals).  normals_mode is what the caller asked for and the next pose uses;
+  // normals_applied says whether the arena holds recomputed normals, which is what a put-back after an overflow reproduces.  The tables
+  // exist while either is set (a switch back to mode 0 frees them once a pose without them has been applied).
+  uint32_t normals_mode = 0, triangle_count = 0, class_count = 0;
+  bool normals_applied = false;
+  DeviceArray<uint32_t> d_class_of, d_class_offsets, d_class_entries;
+  DeviceArray<float4> d_faces;
+  bool has_normals_tables() const { return d_class_of.ptr != nullptr; }
+  void release_normals_tables() { d_class_of.release(); d_class_offsets.release(); d_class_entries.release(); d_faces.release(); class_count = 0; }
   struct Params { std::vector<float> weights, palette; };
   Params applied, pending;
   bool dirty = false;  // `pending` was recorded since the last refit that posed it
@@ -71,9 +92,12 @@ struct DeformState {
   DeviceArray<unsigned char> d_stage;
   uint64_t launches = 0, segments = 0;                     // pose launches (either kernel) and deformers they posed, since hala_rt_create
   uint64_t batch_launches = 0;                             // those of k_deform_batch among them
+  std::vector<unsigned char> h_normals_stage;              // the batch form of the normals passes: segments and block maps, staged like h_stage
+  DeviceArray<unsigned char> d_normals_stage;
+  uint64_t normals_launches = 0;                           // launches of the two normals kernels (either form), since hala_rt_create
   uint64_t next_id = 0;
   bool lost = false;                                       // a device error interrupted deform_pose: the arena is undefined
-  void off() { by_prim.clear(); d_flags.release(); d_stage.release(); lost = false; }
+  void off() { by_prim.clear(); d_flags.release(); d_stage.release(); d_normals_stage.release(); lost = false; }
 };
 
 // one lane per vertex, one launch on `s`
@@ -81,5 +105,10 @@ void launch_deform(const DeformTables& t, const DeformActive& a, hipStream_t s);
 // the same for every segment at once: device pointers, block_count workgroups, LDS for the largest palette of the launch
 void launch_deform_batch(const DeformSegment* segments, const DeformBlock* blocks, const DeformActiveEntry* active, uint32_t block_count,
                          uint32_t max_joint_count, hipStream_t s);
+// deform_normals.hip: the face pass and the vertex pass of one primitive (two launches on `s`), and of every segment at once (two
+// launches: face_blocks / vertex_blocks map workgroups to (segment, first triangle / first vertex))
+void launch_deform_normals(const NormalsTables& t, hipStream_t s);
+void launch_deform_normals_batch(const NormalsTables* segments, const DeformBlock* face_blocks, uint32_t face_block_count,
+                                 const DeformBlock* vertex_blocks, uint32_t vertex_block_count, hipStream_t s);
 
 }  // namespace rt

@@ -3,6 +3,9 @@
 // tree, and the read-back of a primitive's vertices.  Invariants: the primitive's range of the vertex arena holds the rest pose while
 // Deformer::posed is false, and k_deform(rest, tables, Deformer::applied) otherwise; HostPrimitive::vertices stays the rest pose;
 // Deformer::pending and dirty hold what the caller recorded, and posing (deform_pose) takes its parameters as arguments.
+// Recomputed normals (Deformer::normals_mode 1; deform_normals.hip) are part of posing: launch_all queues the two passes behind the
+// pose launch, so the arena of a posed deformer with Deformer::normals_applied holds them too.
+#include "deform_adjacency.h"
 #include "renderer_state.h"
 
 namespace rt {
@@ -11,7 +14,7 @@ namespace rt {
 static int restore_rest(hala_rt_renderer* r, Deformer& d) {
   if (d.vertex_count)
     RT_HIP(hipMemcpyAsync(r->arena(d.prim), d.d_rest.ptr, (size_t)d.vertex_count * sizeof(hala_vertex), hipMemcpyDeviceToDevice, r->stream));
-  d.posed = false;
+  d.posed = false; d.normals_applied = false;
   return HALA_OK;
 }
 
@@ -86,19 +89,75 @@ static int launch_batch(hala_rt_renderer* r, const std::vector<DeformPose>& item
   return HALA_OK;
 }
 
-// one deformer: k_deform as always; kDeformBatchMin or more: one launch of k_deform_batch (DESIGN.md 19 has the measurement behind it)
-static int launch_all(hala_rt_renderer* r, const std::vector<DeformPose>& items, uint32_t* flags, bool count) {
-  if (items.empty()) return HALA_OK;
-  if (items.size() >= kDeformBatchMin) {
-    if (launch_batch(r, items, flags) != HALA_OK) return HALA_ERR;
-    if (count) { r->deform.launches += 1; r->deform.batch_launches += 1; r->deform.segments += items.size(); }
+static NormalsTables normals_tables_of(hala_rt_renderer* r, Deformer& d) {
+  NormalsTables t{};
+  t.indices = r->d_indices.ptr + r->prim_index_offset[d.prim]; t.vertices = r->arena(d.prim); t.faces = d.d_faces.ptr;
+  t.class_of = d.d_class_of.ptr; t.offsets = d.d_class_offsets.ptr; t.entries = d.d_class_entries.ptr;
+  t.triangle_count = d.triangle_count; t.vertex_count = d.vertex_count;
+  return t;
+}
+
+// The face pass and the vertex pass (deform_normals.hip) of `list`, behind the pose launch on the stream: two launches for one deformer,
+// two launches of the batch forms for several (segments and both block maps staged and copied in one piece, as launch_batch does).
+static int launch_normals(hala_rt_renderer* r, const std::vector<Deformer*>& list, bool batch, bool count) {
+  DeformState& ds = r->deform;
+  std::vector<Deformer*> work;
+  for (Deformer* d : list)
+    if (d->triangle_count && d->vertex_count) work.push_back(d);  // (no triangle: every list is empty, nothing would be written)
+  if (work.empty()) return HALA_OK;
+  if (!batch) {
+    for (Deformer* d : work) {
+      launch_deform_normals(normals_tables_of(r, *d), r->stream);
+      RT_HIP(hipGetLastError());
+      if (count) ds.normals_launches += 2;
+    }
     return HALA_OK;
   }
-  for (size_t k = 0; k < items.size(); ++k) {
-    if (launch(r, *items[k].d, *items[k].p, flags + k) != HALA_OK) return HALA_ERR;
-    if (count) { r->deform.launches += 1; r->deform.segments += 1; }
+  size_t face_blocks = 0, vertex_blocks = 0;
+  for (Deformer* d : work) {
+    face_blocks += (d->triangle_count + kDeformThreads - 1) / kDeformThreads;
+    vertex_blocks += (d->vertex_count + kDeformThreads - 1) / kDeformThreads;
   }
+  const size_t off_face = work.size() * sizeof(NormalsTables), off_vertex = off_face + face_blocks * sizeof(DeformBlock),
+               total = off_vertex + vertex_blocks * sizeof(DeformBlock);
+  ds.h_normals_stage.assign(total, 0);
+  if (total > ds.d_normals_stage.count) RT_HIP(ds.d_normals_stage.resize(total));
+  NormalsTables* seg = reinterpret_cast<NormalsTables*>(ds.h_normals_stage.data());
+  DeformBlock* fb = reinterpret_cast<DeformBlock*>(ds.h_normals_stage.data() + off_face);
+  DeformBlock* vb = reinterpret_cast<DeformBlock*>(ds.h_normals_stage.data() + off_vertex);
+  uint32_t nf = 0, nv = 0;
+  for (size_t k = 0; k < work.size(); ++k) {
+    seg[k] = normals_tables_of(r, *work[k]);
+    for (uint32_t t = 0; t < work[k]->triangle_count; t += kDeformThreads) fb[nf++] = DeformBlock{(uint32_t)k, t};
+    for (uint32_t v = 0; v < work[k]->vertex_count; v += kDeformThreads) vb[nv++] = DeformBlock{(uint32_t)k, v};
+  }
+  RT_HIP(hipMemcpyAsync(ds.d_normals_stage.ptr, ds.h_normals_stage.data(), total, hipMemcpyHostToDevice, r->stream));
+  launch_deform_normals_batch(reinterpret_cast<const NormalsTables*>(ds.d_normals_stage.ptr), reinterpret_cast<const DeformBlock*>(ds.d_normals_stage.ptr + off_face), nf,
+                              reinterpret_cast<const DeformBlock*>(ds.d_normals_stage.ptr + off_vertex), nv, r->stream);
+  RT_HIP(hipGetLastError());
+  if (count) ds.normals_launches += 2;
   return HALA_OK;
+}
+
+// one deformer: k_deform as always; kDeformBatchMin or more: one launch of k_deform_batch (DESIGN.md 19 has the measurement behind it).
+// Behind either, the normals passes of the deformers that want them: those in mode 1, or, where the launch puts an applied pose back
+// (`applied`), those whose applied pose had them.  Deformers in mode 0 make no launch and are no segment of the batch forms.
+static int launch_all(hala_rt_renderer* r, const std::vector<DeformPose>& items, uint32_t* flags, bool count, bool applied) {
+  if (items.empty()) return HALA_OK;
+  const bool batch = items.size() >= kDeformBatchMin;
+  if (batch) {
+    if (launch_batch(r, items, flags) != HALA_OK) return HALA_ERR;
+    if (count) { r->deform.launches += 1; r->deform.batch_launches += 1; r->deform.segments += items.size(); }
+  } else {
+    for (size_t k = 0; k < items.size(); ++k) {
+      if (launch(r, *items[k].d, *items[k].p, flags + k) != HALA_OK) return HALA_ERR;
+      if (count) { r->deform.launches += 1; r->deform.segments += 1; }
+    }
+  }
+  std::vector<Deformer*> normals;
+  for (const DeformPose& it : items)
+    if (applied ? it.d->normals_applied : it.d->normals_mode == HALA_DEFORM_NORMALS_RECOMPUTED) normals.push_back(it.d);
+  return launch_normals(r, normals, batch, count);
 }
 
 // Overflow to a non-finite position: the arena is put back by running the kernel again with the last applied parameters — it is
@@ -113,7 +172,7 @@ int deform_pose(hala_rt_renderer* r, const std::vector<DeformPose>& items, std::
   ds.lost = true;
   std::vector<uint32_t> flags;
   bool overflow = false;
-  if (launch_flagged(ds.d_flags, items.size(), r->stream, [&](uint32_t* words) { return launch_all(r, items, words, true); }, &flags, &overflow) != HALA_OK)
+  if (launch_flagged(ds.d_flags, items.size(), r->stream, [&](uint32_t* words) { return launch_all(r, items, words, true, false); }, &flags, &overflow) != HALA_OK)
     return HALA_ERR;
   if (overflow) {
     std::vector<DeformPose> back;
@@ -121,7 +180,7 @@ int deform_pose(hala_rt_renderer* r, const std::vector<DeformPose>& items, std::
       if (!it.d->posed) { if (restore_rest(r, *it.d) != HALA_OK) return HALA_ERR; }
       else back.push_back(DeformPose{it.d, &it.d->applied});
     }
-    if (launch_all(r, back, ds.d_flags.ptr, false) != HALA_OK) return HALA_ERR;
+    if (launch_all(r, back, ds.d_flags.ptr, false, true) != HALA_OK) return HALA_ERR;
     RT_HIP(hipStreamSynchronize(r->stream));
     for (size_t k = 0; k < items.size() && overflowed; ++k)
       if (flags[k]) overflowed->push_back(k);
@@ -131,6 +190,8 @@ int deform_pose(hala_rt_renderer* r, const std::vector<DeformPose>& items, std::
   }
   for (const DeformPose& it : items) {
     it.d->applied = *it.p; it.d->posed = true;
+    it.d->normals_applied = it.d->normals_mode == HALA_DEFORM_NORMALS_RECOMPUTED;
+    if (!it.d->normals_applied && it.d->has_normals_tables()) it.d->release_normals_tables();  // (hipFree waits for the device)
     mark_no_history(r, it.d->prim);
   }
   ds.lost = false;
@@ -250,6 +311,55 @@ int hala_rt_clear_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t pr
     mark_no_history(r, prim);
   }
   r->deform.by_prim.erase(it);
+  return HALA_OK;
+}
+
+int hala_rt_set_deformer_normals(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, uint32_t mode) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  uint32_t prim = 0;
+  if (find_primitive(r, mesh_index, primitive_index, &prim) != HALA_OK) return HALA_ERR;
+  auto it = r->deform.by_prim.find(prim);
+  if (it == r->deform.by_prim.end()) RT_FAIL("The primitive has no deformer.");
+  if (mode > HALA_DEFORM_NORMALS_RECOMPUTED) RT_FAIL("The normals mode is neither HALA_DEFORM_NORMALS_AS_POSED nor HALA_DEFORM_NORMALS_RECOMPUTED.");
+  if (r->shutter.rec.deformers.count(prim) || r->shutter.act.deformers.count(prim)) RT_FAIL("The deformer has shutter keys: clear them and refit first (hala_rt_set_deformer_keys).");
+  if (r->deform.lost) RT_FAIL("A device error interrupted an earlier deformation and the vertices on the device are undefined: set the scene again.");
+  Deformer& d = *it->second;
+  if (mode == d.normals_mode) return HALA_OK;
+  if (mode == HALA_DEFORM_NORMALS_RECOMPUTED && !d.has_normals_tables()) {
+    const HostPrimitive& p = r->hs.prims[prim];  // (HostPrimitive::vertices is the rest pose the deformer took)
+    DeformAdjacency adj;
+    if (!build_deform_adjacency(p.vertices.data(), sizeof(hala_vertex), p.vertices.size(), p.indices.data(), p.indices.size(), &adj))
+      RT_FAIL("A vertex index of the primitive is not below its vertex count.");
+    const size_t triangles = p.indices.size() / 3u;
+    hipError_t e = d.d_class_of.upload(adj.class_of.data(), adj.class_of.size(), r->stream);
+    if (e == hipSuccess) e = d.d_class_offsets.upload(adj.offsets.data(), adj.offsets.size(), r->stream);
+    if (e == hipSuccess) e = d.d_class_entries.upload(adj.entries.data(), adj.entries.size(), r->stream);
+    if (e == hipSuccess) e = d.d_faces.resize(triangles);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);  // the tables above go with this scope
+    if (e != hipSuccess) {
+      d.release_normals_tables();
+      RT_FAIL(std::string("hala_rt_set_deformer_normals: ") + hipGetErrorString(e));
+    }
+    d.triangle_count = (uint32_t)triangles; d.class_count = adj.class_count();
+  }
+  if (mode == HALA_DEFORM_NORMALS_AS_POSED && !d.normals_applied) d.release_normals_tables();  // nothing on the device was made with them
+  d.normals_mode = mode;
+  d.dirty = true;
+  return HALA_OK;
+}
+
+int hala_rt_get_deformer_normals(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, hala_deformer_normals_info* out) {
+  if (!r || !out) RT_FAIL("Invalid argument.");
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  uint32_t prim = 0;
+  if (find_primitive(r, mesh_index, primitive_index, &prim) != HALA_OK) return HALA_ERR;
+  auto it = r->deform.by_prim.find(prim);
+  if (it == r->deform.by_prim.end()) RT_FAIL("The primitive has no deformer.");
+  const Deformer& d = *it->second;
+  const bool on = d.normals_mode == HALA_DEFORM_NORMALS_RECOMPUTED;
+  out->mode = d.normals_mode; out->class_count = on ? d.class_count : 0u; out->entry_count = on ? d.triangle_count * 3u : 0u; out->reserved = 0u;
+  out->launches = r->deform.normals_launches;
   return HALA_OK;
 }
 

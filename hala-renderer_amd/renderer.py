@@ -607,6 +607,18 @@ class HalaRenderer:
         """remove the primitive's deformer: the rest pose is back at the next refit()"""
         self._check(self._lib.hala_rt_clear_deformer(self._h, C.c_uint32(mesh), C.c_uint32(prim)))
 
+    def set_deformer_normals(self, mesh, prim, mode):
+        """mode 1 (A.DEFORM_NORMALS_RECOMPUTED): every pose of the primitive's deformer is followed on the device by the normals from the
+        posed triangles and the tangent re-orthogonalised against them; mode 0: normal and tangent as k_deform poses them.  Takes effect
+        at the next refit()"""
+        self._check(self._lib.hala_rt_set_deformer_normals(self._h, C.c_uint32(mesh), C.c_uint32(prim), C.c_uint32(mode)))
+
+    def get_deformer_normals(self, mesh, prim) -> A.DeformerNormalsInfo:
+        """mode, classes and list entries of the deformer's adjacency tables, and the renderer's cumulative normals launches"""
+        info = A.DeformerNormalsInfo()
+        self._check(self._lib.hala_rt_get_deformer_normals(self._h, C.c_uint32(mesh), C.c_uint32(prim), C.byref(info)))
+        return info
+
     def read_vertices(self, mesh, prim) -> np.ndarray:
         """a primitive's vertices as the device holds them (VERTEX_DTYPE records): the posed mesh of a deformed primitive"""
         n = C.c_uint32(0)

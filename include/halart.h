@@ -885,6 +885,35 @@ int hala_rt_clear_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t pr
 int hala_rt_read_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, hala_vertex* dst, uint32_t capacity,
                           uint32_t* count);
 
+/* Recomputed normals (docs/RENDER_SPEC.md 17 "Recomputed normals"), per deformer and opt-in.  In mode HALA_DEFORM_NORMALS_AS_POSED
+ * (the default) a posed vertex carries the normal and tangent k_deform gives it: rest value plus deltas, times the skinning matrix.  In
+ * mode HALA_DEFORM_NORMALS_RECOMPUTED every pose of the deformer — a refit, the batched launch of a rig, a shutter step — is followed
+ * on the device by two more launches that derive each vertex's normal from the posed triangles around it (area-weighted; vertices whose
+ * rest position and rest normal are bit-equal share one normal, so UV seams shade closed and hard edges stay hard) and re-orthogonalise
+ * the tangent against it.  Position and tex_coord are unaffected. */
+#define HALA_DEFORM_NORMALS_AS_POSED 0u
+#define HALA_DEFORM_NORMALS_RECOMPUTED 1u
+/* Switches the mode of the deformer on a primitive.  Mode 1 builds the adjacency tables from the rest pose on the host and uploads them;
+ * mode 0 frees them (once a pose without them is on the device).  A call that changes the mode marks the deformer dirty: like every
+ * edit it takes effect at the next hala_rt_refit, which poses the deformer again with its pending parameters; a call with the mode the
+ * deformer already has does nothing.  A mode-1 refit under the identity pose does rewrite the normals from the triangles: it does not
+ * give the rest normals back (mode 0, or hala_rt_clear_deformer, does).  The mode lives with the deformer: a replacing
+ * hala_rt_set_deformer starts at mode 0, hala_rt_clear_deformer and hala_rt_set_scene drop it, a repeated hala_rt_commit keeps it.  The
+ * deformers of a rig are switched one by one with this call after hala_rt_set_rig (hala_rig_binding::target_normal_deltas == NULL names
+ * the ones that want it).  Refused, changing nothing, each with a message: no committed scene; the mesh or primitive does not exist;
+ * the primitive has no deformer; a mode above HALA_DEFORM_NORMALS_RECOMPUTED; the deformer has shutter keys recorded or active ("clear
+ * them and refit first"); an earlier device error left the vertex arena undefined ("set the scene again"). */
+int hala_rt_set_deformer_normals(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, uint32_t mode);
+typedef struct hala_deformer_normals_info {
+  uint32_t mode;        /* as last set */
+  uint32_t class_count; /* classes of the primitive's vertices; 0 in mode 0 */
+  uint32_t entry_count; /* (triangle, corner) pairs in the classes' lists: 3 x triangles; 0 in mode 0 */
+  uint32_t reserved;
+  uint64_t launches;    /* launches of the two normals kernels by this renderer since hala_rt_create, all deformers: a pose adds 2 */
+} hala_deformer_normals_info; /* 24 B */
+/* Refused when there is no committed scene, the mesh or primitive does not exist, or the primitive has no deformer. */
+int hala_rt_get_deformer_normals(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, hala_deformer_normals_info* out);
+
 /* ------------------------------------------------------------------------------------------------
  * Shutter (docs/RENDER_SPEC.md 18; no reference equivalent): motion blur by accumulation.  Holders — a node's local transform, a
  * deformer's parameters, a primitive's vertices — carry two keys, the state at time 0 and at time 1.  While the shutter is on, frame k

@@ -78,6 +78,11 @@ pub mod sys {
   pub struct hala_shutter_params { pub shutter_open: f32, pub shutter_close: f32, pub time_stride: u32, pub reserved: [u32; 5] }
   #[repr(C)] #[derive(Default, Clone, Copy)]
   pub struct hala_shutter_status { pub enabled: u32, pub time_stride: u32, pub step: u32, pub time: f32, pub steps: u64, pub reserved: [u32; 2] }
+  /// hala_deformer_normals_info, 24 B (RENDER_SPEC 17 "Recomputed normals")
+  #[repr(C)] #[derive(Default, Clone, Copy)]
+  pub struct hala_deformer_normals_info { pub mode: u32, pub class_count: u32, pub entry_count: u32, pub reserved: u32, pub launches: u64 }
+  pub const HALA_DEFORM_NORMALS_AS_POSED: u32 = 0;
+  pub const HALA_DEFORM_NORMALS_RECOMPUTED: u32 = 1;
   #[repr(C)] pub struct hala_scene { _private: [u8; 0] }
   #[repr(C)] pub struct hala_rtprog { _private: [u8; 0] }
   extern "C" {
@@ -155,6 +160,9 @@ pub mod sys {
     pub fn hala_rt_set_node_keys(r: *mut hala_rt_renderer, node_index: u32, open: *const f32, close: *const f32) -> c_int;
     pub fn hala_rt_set_deformer_keys(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, weights_open: *const f32, weights_close: *const f32,
                                      weight_count: u32, palette_open: *const f32, palette_close: *const f32, joint_count: u32) -> c_int;
+    // recomputed normals of a deformer (RENDER_SPEC 17): an edit like the others, applied by hala_rt_refit
+    pub fn hala_rt_set_deformer_normals(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, mode: u32) -> c_int;
+    pub fn hala_rt_get_deformer_normals(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, out: *mut hala_deformer_normals_info) -> c_int;
     pub fn hala_rt_set_vertex_keys(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, open: *const c_void, close: *const c_void,
                                    vertex_count: u32) -> c_int;
     pub fn hala_rt_temporal_capture(r: *mut hala_rt_renderer) -> c_int;

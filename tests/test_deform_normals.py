@@ -1,0 +1,630 @@
+"""Recomputed normals of deformed meshes (docs/RENDER_SPEC.md 17 "Recomputed normals"; include/halart.h hala_rt_set_deformer_normals): per
+deformer and opt-in, every pose is followed on the device by the face pass and the vertex pass of csrc/deform_normals.hip.
+
+CPU tier: the numpy-float32 twin (tests/deform_normals_ref.py) against a float64 evaluation of the same formulas on well-conditioned
+meshes and on its exact cases; csrc/deform_adjacency.cpp built alone with the host sanitizers against the twin's tables; the layout of
+hala_deformer_normals_info and the header's contract; the oracle's render with recomputed normals differs from the one without.
+GPU tier, every comparison by bytes: the kernels equal the twin (read_vertices) across wave and workgroup edges, a lane that loops past
+64 entries, degenerate lists, a UV seam and hard edges; the render equals the oracle's of the scene holding the twin's vertices on both
+tree forms; the batch form with a mode-0 deformer in its middle; a rig; a shutter; an overflow; mode changes, lifetime and refusals.
+(The refusal after a device error cannot be provoked without one: the header test names it, no GPU test reaches it.)"""
+import ctypes as C
+import os
+import re
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import deform_normals_ref as N
+import deform_ref as D
+import scene_edits as E
+import shutter_ref as S
+import test_deformers as TD
+import test_scene_edits as SE
+from conftest import ROOT
+from hala_renderer_amd import _abi as A
+from hala_renderer_amd import scenes
+from hala_renderer_amd.scene import HalaMesh, HalaNode, HalaPrimitive
+
+gpu = pytest.mark.gpu
+f32 = np.float32
+TALL, SHORT = TD.TALL, TD.SHORT
+ON, OFF = 1, 0
+
+
+def cornell():
+    return SE.base_of("cornell")
+
+
+_CLASSES = {}
+
+
+def cornell_classes(mesh):
+    if mesh not in _CLASSES:
+        p = cornell().scene.meshes[mesh].primitives[0]
+        _CLASSES[mesh] = N.classes(p.vertices, p.indices)
+    return _CLASSES[mesh]
+
+
+def cornell_vertices(mesh, pose, mode):
+    """the twin's vertices of a Cornell block under `pose`: k_deform's, then the recomputed normals in mode 1"""
+    p = cornell().scene.meshes[mesh].primitives[0]
+    v = D.pose_vertices(p.vertices, TD.cornell_rigs()[mesh], pose)
+    return N.recompute(v, p.indices, cornell_classes(mesh)) if mode else v
+
+
+def cornell_ops(poses, modes):
+    return [("vertices", mesh, 0, cornell_vertices(mesh, pose, modes.get(mesh, OFF))) for mesh, pose in sorted(poses.items())]
+
+
+_IMAGES = {}
+
+
+def cornell_images(oracle, k, mode, frames, two_level=False):
+    """the oracle's images of pose k of tests/test_deformers.py with both blocks in `mode`, rendered once and shared"""
+    key = (k, mode, frames, two_level)
+    if key not in _IMAGES:
+        scene = E.apply_to_scene(cornell().scene, cornell_ops(TD.cornell_pose(k), {TALL: mode, SHORT: mode}))
+        _IMAGES[key] = SE.oracle_images(oracle, cornell(), scene, frames)
+    return _IMAGES[key]
+
+
+def differing_words(got, want):
+    bad = np.nonzero(got.view(np.uint32).reshape(-1, 11) != want.view(np.uint32).reshape(-1, 11))
+    return f"{len(bad[0])} words differ, first (vertex, word) {bad[0][:4]}, {bad[1][:4]}"
+
+
+# ---- CPU tier ---------------------------------------------------------------------------------------------------------------------------
+def smooth_mesh(seed):
+    """a grid whose height is a sum of a few low-frequency waves (slopes below ~0.6: no class's face vectors come near cancelling) or,
+    for odd seeds, a seam cylinder whose radius swells smoothly"""
+    rs = np.random.RandomState(4000 + seed)
+    if seed % 2 == 0:
+        amp, fx, fy, ph = rs.uniform(0.2, 0.6, 3), rs.uniform(0.1, 0.45, 3), rs.uniform(0.1, 0.45, 3), rs.uniform(0.0, 6.0, 3)
+        idx, v = N.grid(19 + seed, 14, height=lambda x, y: sum(a * np.sin(u * x + w * y + p) for a, u, w, p in zip(amp, fx, fy, ph)), seed=seed)
+        return idx, v, v
+    idx, rest, _ = N.cylinder(24, 9, seed=seed)
+    posed = rest.copy()
+    z = rest["position"][:, 2].astype(np.float64)
+    swell = 1.0 + rs.uniform(0.1, 0.3) * np.sin(rs.uniform(1.0, 2.0) * z + rs.uniform(0.0, 3.0))
+    posed["position"][:, :2] = (rest["position"][:, :2] * swell[:, None]).astype(f32)
+    return idx, rest, posed
+
+
+MEASURED_TWIN_ERROR = 2.432e-7  # the largest |recompute - recompute64| over the six inputs below, normal and tangent (printed by the test)
+TWIN_BOUND = 4.0 * MEASURED_TWIN_ERROR
+
+
+def test_twin_agrees_with_float64():
+    """componentwise |twin - float64| of normal and tangent on six smooth meshes stays below 4 x the error measured when the test was
+    written (2.432e-7, about 4 units of float32 roundoff on components below 1).  The error has no bound where a class's face vectors
+    nearly cancel, so the inputs are first checked, in float64: |sum f| >= 0.1 * sum |f| for every class of every input"""
+    worst = 0.0
+    for seed in range(6):
+        idx, rest, posed = smooth_mesh(seed)
+        cl = N.classes(rest, idx)
+        total, mag = N.conditioning(posed, idx, cl)
+        assert len(total) == len(cl["offsets"]) - 1 and (np.diff(cl["offsets"].astype(np.int64)) > 0).all(), "a class without a triangle"
+        assert (total >= 0.1 * mag).all(), (seed, float((total / mag).min()))
+        got = N.recompute(posed, idx, cl)
+        n64, t64, _ = N.recompute64(posed, idx, cl)
+        err = max(float(np.abs(got["normal"].astype(np.float64) - n64).max()), float(np.abs(got["tangent"].astype(np.float64) - t64).max()))
+        print(f"seed {seed}: V {len(rest)} classes {len(total)} min |sum f| / sum |f| {float((total / mag).min()):.3f} max error {err:.3e}")
+        worst = max(worst, err)
+        assert got["position"].tobytes() == posed["position"].tobytes() and got["tex_coord"].tobytes() == posed["tex_coord"].tobytes()
+        assert got["normal"].tobytes() != posed["normal"].tobytes()
+    print(f"largest error {worst:.3e}, bound {TWIN_BOUND:.3e}")
+    assert 0.0 < worst <= TWIN_BOUND
+
+
+def test_twin_exact_cases():
+    # a flat grid: every normal is (0, 0, 1) exactly, whatever the rest normals were
+    idx, v = N.grid(7, 5)
+    v["normal"] = np.tile(np.array([0.6, 0.0, 0.8], f32), (len(v), 1))
+    got = N.recompute(v, idx, N.classes(v, idx))
+    assert np.array_equal(got["normal"], np.tile(np.array([0.0, 0.0, 1.0], f32), (len(v), 1)))
+    assert np.allclose(np.einsum("ij,ij->i", got["tangent"].astype(np.float64), got["normal"].astype(np.float64)), 0.0, atol=1e-6)
+    # the cube under the identity keeps its six face normals: the three vertices of a corner are three classes
+    idx, v = N.cube(2.0)
+    cl = N.classes(v, idx)
+    assert len(cl["offsets"]) - 1 == 24
+    got = N.recompute(v, idx, cl)
+    assert np.array_equal(got["normal"], v["normal"]) and np.array_equal(got["tangent"], v["tangent"])
+    # the seam cylinder: the duplicates share a class and get bit-equal normals; class_count = V - seam duplicates
+    idx, v, dup = N.cylinder(12, 5)
+    cl = N.classes(v, idx)
+    assert len(cl["offsets"]) - 1 == len(v) - dup == 12 * 5
+    w = 13
+    posed = v.copy(); posed["position"][:, 0] *= f32(1.5)  # a non-uniform stretch: rest normals would be wrong
+    got = N.recompute(posed, idx, cl)
+    for row in range(5):
+        assert cl["class_of"][row * w] == cl["class_of"][row * w + 12]
+        assert got["normal"][row * w].tobytes() == got["normal"][row * w + 12].tobytes()
+        assert v["tex_coord"][row * w].tobytes() != v["tex_coord"][row * w + 12].tobytes()
+    assert got["normal"].tobytes() != posed["normal"].tobytes()
+    # -0.0 and +0.0 are different patterns: two vertices that differ in nothing else are two classes
+    two = np.zeros(2, dtype=A.VERTEX_DTYPE); two["normal"] = [[0.0, 0.0, 1.0], [-0.0, 0.0, 1.0]]
+    assert list(N.classes(two, np.zeros(0, np.uint32))["class_of"]) == [0, 1]
+    # an isolated vertex and a repeated-index triangle; a fan of zero-area triangles; a tangent parallel to the new normal
+    idx, v = N.with_oddities(*N.grid(4, 4))
+    cl = N.classes(v, idx)
+    got = N.recompute(v, idx, cl)
+    assert got[-1].tobytes() == v[-1].tobytes(), "the isolated vertex"
+    assert cl["offsets"][cl["class_of"][1] + 1] - cl["offsets"][cl["class_of"][1]] == 3 + 2, "vertex 1: three grid corners and the repeated index twice"
+    idx, v = N.fan(8)
+    flat = v.copy(); flat["position"][:] = flat["position"][0]  # every triangle has zero area
+    got = N.recompute(flat, idx, N.classes(v, idx))
+    assert got.tobytes() == flat.tobytes()
+    idx, v = N.grid(3, 3)
+    v["tangent"] = np.tile(np.array([0.0, 0.0, 2.0], f32), (len(v), 1))
+    got = N.recompute(v, idx, N.classes(v, idx))
+    assert np.array_equal(got["normal"][:, 2], np.ones(len(v), f32)) and got["tangent"].tobytes() == v["tangent"].tobytes()
+    # positions that are not finite: the vertex keeps both
+    idx, v = N.grid(3, 3)
+    bad = v.copy(); bad["position"][4, 0] = np.inf
+    got = N.recompute(bad, idx, N.classes(v, idx))
+    assert got[4].tobytes() == bad[4].tobytes()
+
+
+def adjacency_cases():
+    rs = np.random.RandomState(11)
+    out = []
+    empty = np.zeros(0, dtype=A.VERTEX_DTYPE)
+    out.append((empty, np.zeros(0, np.uint32)))
+    out.append((N.grid(2, 2)[1][:3], np.array([0, 1, 2], np.uint32)))
+    out.append((N.grid(2, 2)[1], np.array([0, 0, 0, 1, 1, 2, 3, 2, 3, 0, 1], np.uint32)))  # repeated indices, a trailing partial triangle
+    idx, v = N.fan(300)
+    out.append((v, idx))
+    idx, v, _ = N.cylinder(9, 4)
+    out.append((v, idx))
+    idx, v = N.cube()
+    out.append((v, idx))
+    for k in range(3):  # random buffers over vertices many of which are duplicates of one another
+        nv = int(rs.randint(1, 60))
+        v = N.grid(8, 8)[1][rs.randint(0, 12, nv)]
+        out.append((v, rs.randint(0, nv, 3 * int(rs.randint(0, 90))).astype(np.uint32)))
+    out.append((N.grid(2, 2)[1], np.array([0, 1, 4], np.uint32)))  # an index that is not below the vertex count: refused
+    return out
+
+
+def test_adjacency_under_host_sanitizers(tmp_path):
+    """csrc/deform_adjacency.cpp and tests/deform_adjacency_check.cpp, built with -fsanitize=address,undefined, run as their own process on
+    empty, one-triangle, repeated-index, valence-300, seam, hard-edge and random buffers: the tables equal the twin's"""
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host compiler"
+    csrc = os.path.join(ROOT, "hala-renderer_amd", "csrc")
+    flags = ["-std=c++17", "-g1", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
+    static = ["-static-libasan", "-static-libubsan"] if os.path.basename(cxx).startswith("g++") else []
+    exe = str(tmp_path / "deform_adjacency_check")
+    subprocess.run([cxx, *flags, *static, "-I", csrc, os.path.join(csrc, "deform_adjacency.cpp"), os.path.join(ROOT, "tests", "deform_adjacency_check.cpp"), "-o", exe],
+                   check=True, capture_output=True, text=True)
+    cases = adjacency_cases()
+    path = tmp_path / "cases.bin"
+    with open(path, "wb") as f:
+        for v, idx in cases:
+            f.write(struct.pack("<II", len(v), len(idx)) + np.ascontiguousarray(v, dtype=A.VERTEX_DTYPE).tobytes() + np.ascontiguousarray(idx, dtype=np.uint32).tobytes())
+    run = subprocess.run([exe, str(path)], capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr[-3000:]
+    lines = run.stdout.splitlines()
+    assert len(lines) == len(cases)
+    assert lines[-1] == "refused" and "refused" not in lines[:-1]
+    for k, ((v, idx), line) in enumerate(zip(cases[:-1], lines)):
+        cl = N.classes(v, idx)
+        parts = [[int(x) for x in p.split()] for p in line.split("|")]
+        assert parts[0] == [len(cl["offsets"]) - 1], k
+        assert parts[1] == list(cl["class_of"]) and parts[2] == list(cl["offsets"]) and parts[3] == list(cl["entries"]), k
+    assert max(np.diff(N.classes(*cases[3])["offsets"].astype(np.int64))) == 300
+
+
+def test_info_layout_matches_the_header(tmp_path):
+    fields = [n for n, _ in A.DeformerNormalsInfo._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "halart.h"\nint main(void) {\n  printf("%zu", sizeof(hala_deformer_normals_info));\n' +
+                   "".join(f'  printf(" %zu", offsetof(hala_deformer_normals_info, {n}));\n' for n in fields) +
+                   '  printf(" %u %u", HALA_DEFORM_NORMALS_AS_POSED, HALA_DEFORM_NORMALS_RECOMPUTED);\n  return 0;\n}\n')
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True, capture_output=True, text=True)
+    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    assert out[0] == C.sizeof(A.DeformerNormalsInfo) == 24
+    assert out[1:-2] == [getattr(A.DeformerNormalsInfo, n).offset for n in fields] == [0, 4, 8, 12, 16]
+    assert out[-2:] == [A.DEFORM_NORMALS_AS_POSED, A.DEFORM_NORMALS_RECOMPUTED] == [0, 1]
+    assert C.sizeof(A.DeformerDesc) == 64 and C.sizeof(A.RigStatus) == 32, "the existing layouts stand"
+    for fn in ("hala_rt_set_deformer_normals", "hala_rt_get_deformer_normals"):
+        assert fn in A.EXPORTS and fn in A.PROTOTYPES, fn
+    rust = open(os.path.join(ROOT, "rust", "hala-renderer-halart", "src", "lib.rs")).read()
+    assert "fn hala_rt_set_deformer_normals(" in rust and "fn hala_rt_get_deformer_normals(" in rust and "struct hala_deformer_normals_info" in rust
+
+
+def test_header_states_the_contract_and_every_refusal():
+    text = open(os.path.join(ROOT, "include", "halart.h")).read()
+    m = re.search(r"/\*((?:(?!\*/).)*)\*/\s*int hala_rt_set_deformer_normals\(", text, flags=re.S)
+    assert m
+    c = re.sub(r"\s*\n \*\s*", " ", m.group(1))
+    for w in ("takes effect at the next hala_rt_refit", "marks the deformer dirty", "does not give the rest normals back", "starts at mode 0",
+              "hala_rt_clear_deformer and hala_rt_set_scene drop it", "a repeated hala_rt_commit keeps it", "target_normal_deltas == NULL",
+              "no committed scene", "mesh or primitive does not exist", "has no deformer", "a mode above HALA_DEFORM_NORMALS_RECOMPUTED",
+              "shutter keys recorded or active", "clear them and refit first", "set the scene again"):
+        assert w in c, w
+
+
+def test_the_oracle_render_with_recomputed_normals_is_not_vacuous(oracle):
+    """the Cornell blocks of tests/test_deformers.py, pose 1: the twin's normals differ from k_deform's, and so do the oracle's images"""
+    for mesh in (TALL, SHORT):
+        a, b = (cornell_vertices(mesh, TD.cornell_pose(1)[mesh], mode) for mode in (ON, OFF))
+        assert a["normal"].tobytes() != b["normal"].tobytes() and a["position"].tobytes() == b["position"].tobytes()
+    with_normals, without = cornell_images(oracle, 1, ON, 3), cornell_images(oracle, 1, OFF, 3)
+    assert int(np.any(with_normals[0] != without[0], axis=-1).sum()) > 30
+    assert without[0].tobytes() == TD.posed_images(oracle, 1, 3)[0].tobytes()
+
+
+# ---- GPU tier ---------------------------------------------------------------------------------------------------------------------------
+def mesh_scene(primitives):
+    """the Cornell box plus mesh 3 holding `primitives` [(indices, vertices)], under one translated node"""
+    s = scenes.cornell_box(aspect=E.W / E.H_)
+    s.meshes = list(s.meshes) + [HalaMesh([HalaPrimitive(idx, v, material_index=k % 5) for k, (idx, v) in enumerate(primitives)])]
+    s.nodes = list(s.nodes) + [HalaNode(name="posed", mesh_index=3, local_transform=E._translate((20.0, 200.0, 150.0)))]
+    return s
+
+
+MESHES = {
+    "strip3": lambda: D.strip(3, seed=3), "strip64": lambda: D.strip(64, seed=64), "strip65": lambda: D.strip(65, seed=65),
+    "strip257": lambda: D.strip(257, seed=257), "strip1000": lambda: D.strip(1000, seed=1000),
+    "fan100": lambda: N.fan(100, seed=1),                             # the hub's lane loops over 100 entries, its neighbours over 3
+    "oddities": lambda: N.with_oddities(*N.grid(9, 8, seed=2)),       # an isolated vertex, a repeated-index triangle
+    "cylinder": lambda: N.cylinder(16, 6, seed=3)[:2],                # 17 x 6 vertices, 6 of them seam duplicates
+    "cube": lambda: N.cube(2.0, seed=4),
+    "grid40x25": lambda: N.grid(40, 25, seed=5, height=lambda x, y: 0.4 * np.sin(0.3 * x) * np.cos(0.2 * y)),  # 1000 vertices, 4 workgroups
+}
+KINDS = {"morph": dict(targets=2, joint_count=0), "skin": dict(targets=0, joint_count=3), "both": dict(targets=3, joint_count=2)}
+KERNEL_CASES = [("strip3", "morph"), ("strip64", "skin"), ("strip65", "both"), ("strip257", "morph"), ("strip257", "skin"), ("strip1000", "both"),
+                ("fan100", "morph"), ("fan100", "both"), ("oddities", "morph"), ("oddities", "skin"), ("cylinder", "skin"), ("cylinder", "both"),
+                ("cube", "morph"), ("cube", "skin"), ("grid40x25", "both")]
+
+
+def rig_of(name, kind, nv):
+    """morph targets carry no normal deltas (the case the feature is for); the skin's palettes are scaled non-uniformly by random_pose"""
+    return D.random_rig(nv, normals=False, tangents=kind == "both", seed=len(name) + nv, **KINDS[kind])
+
+
+@gpu
+@pytest.mark.parametrize("case", KERNEL_CASES, ids=lambda c: f"{c[0]}-{c[1]}")
+def test_kernels_equal_the_twin(halart, case):
+    """read_vertices after set_deformer / set_deformer_normals(1) / update_deformer / refit equals the twin byte for byte, two poses in a
+    row and the identity pose (which rewrites the normals too); position and tex_coord are tests/deform_ref.py's; the info struct reports the
+    twin's table sizes and two launches per pose"""
+    name, kind = case
+    idx, rest = MESHES[name]()
+    nv = len(rest)
+    rig = rig_of(name, kind, nv)
+    cl = N.classes(rest, idx)
+    r = SE.make(halart, cornell(), scene=mesh_scene([(idx, rest)]))
+    try:
+        r.set_deformer(3, 0, **rig)
+        assert r.get_deformer_normals(3, 0).mode == 0
+        r.set_deformer_normals(3, 0, ON)
+        info = r.get_deformer_normals(3, 0)
+        assert (info.mode, info.class_count, info.entry_count) == (1, len(cl["offsets"]) - 1, len(cl["entries"]))
+        assert r.read_vertices(3, 0).tobytes() == rest.tobytes(), "nothing happens before the refit"
+        launches = info.launches
+        poses = [D.random_pose(rig, seed=k, zero_some=k > 0, centre=(10.0, 0.5, 0.0)) for k in range(2)] + [{}]
+        for k, p in enumerate(poses):
+            if p:
+                r.update_deformer(3, 0, **p)
+            else:
+                r.update_deformer(3, 0, morph_weights=np.zeros(KINDS[kind]["targets"], f32) if KINDS[kind]["targets"] else None,
+                                  joint_matrices=D.identity_palette(rig["joint_count"]) if rig["joint_count"] else None)
+            r.refit()
+            posed = D.pose_vertices(rest, rig, p)
+            assert np.isfinite(posed["position"]).all()
+            want = N.recompute(posed, idx, cl)
+            got = r.read_vertices(3, 0)
+            assert got["position"].tobytes() == posed["position"].tobytes() and got["tex_coord"].tobytes() == posed["tex_coord"].tobytes(), (case, k)
+            if got.tobytes() != want.tobytes():
+                raise AssertionError(f"{case} pose {k}: {differing_words(got, want)}")
+            assert k == 2 or want["normal"].tobytes() != posed["normal"].tobytes(), "the case exercises the rule"
+            launches += 2
+            assert r.get_deformer_normals(3, 0).launches == launches
+        for m in range(3):
+            assert r.read_vertices(m, 0).tobytes() == cornell().scene.meshes[m].primitives[0].vertices.tobytes(), ("neighbour", m)
+    finally:
+        r.close()
+
+
+@gpu
+@pytest.mark.parametrize("two_level", [False, True], ids=["one_level", "two_level"])
+def test_render_equals_the_oracle_of_the_twins_vertices(halart, oracle, two_level):
+    """tall and short block of the Cornell scene posed in mode 1: images 0-3 equal the oracle's render of the scene that holds the twin's
+    vertices, recomputed normals included, on both tree forms"""
+    base = cornell()
+    poses = TD.cornell_pose(1)
+    with SE.tree_form(oracle, two_level) as build:
+        r = SE.make(halart, base, build=build)
+        try:
+            assert (r.bvh_info().instance_ref_count > 0) == two_level
+            r.update_batch(2); r.render()
+            TD.register(r)
+            for mesh in (TALL, SHORT):
+                r.set_deformer_normals(mesh, 0, ON)
+            TD.pose(r, poses)
+            r.refit()
+            for mesh in (TALL, SHORT):
+                assert r.read_vertices(mesh, 0).tobytes() == cornell_vertices(mesh, poses[mesh], ON).tobytes(), mesh
+            r.update_batch(2); r.update(); r.render()
+            edited = E.apply_to_scene(base.scene, cornell_ops(poses, {TALL: ON, SHORT: ON}))
+            SE.assert_images(r, SE.oracle_images(oracle, base, edited, 3), f"two_level={two_level}")
+            assert r.statistics().total_frames == 3
+        finally:
+            r.close()
+
+
+@gpu
+def test_batch_equals_single(halart):
+    """three deformers in modes (1, 0, 1) posed by one refit: one pose launch, two normals launches, every primitive the twin's bytes
+    (tests/deform_ref.py's alone for the one in mode 0); then the first alone, by the single-deformer launches: the same bytes"""
+    prims = [MESHES["strip257"](), MESHES["cylinder"](), MESHES["fan100"]()]
+    kinds = ["both", "skin", "morph"]
+    modes = [ON, OFF, ON]
+    rigs = [rig_of("batch", kind, len(v)) for kind, (_, v) in zip(kinds, prims)]
+    cls = [N.classes(v, idx) for idx, v in prims]
+    r = SE.make(halart, cornell(), scene=mesh_scene(prims))
+    try:
+        for k in range(3):
+            r.set_deformer(3, k, **rigs[k])
+            r.set_deformer_normals(3, k, modes[k])
+        r.refit()  # the mode switches made 0 and 2 dirty: posed at the identity pose
+        poses = [D.random_pose(rig, seed=5 + k, centre=(10.0, 0.5, 0.0)) for k, rig in enumerate(rigs)]
+
+        def want(k, p):
+            v = D.pose_vertices(prims[k][1], rigs[k], p)
+            return N.recompute(v, prims[k][0], cls[k]) if modes[k] else v
+
+        before, normals_before = r.rig_status(), r.get_deformer_normals(3, 1).launches
+        for k in range(3):
+            r.update_deformer(3, k, **poses[k])
+        r.refit()
+        after = r.rig_status()
+        assert (after.pose_launches - before.pose_launches, after.segments_posed - before.segments_posed, after.batch_launches - before.batch_launches) == (1, 3, 1)
+        assert [r.get_deformer_normals(3, k).launches - normals_before for k in range(3)] == [2, 2, 2]
+        batch = [r.read_vertices(3, k) for k in range(3)]
+        for k in range(3):
+            if batch[k].tobytes() != want(k, poses[k]).tobytes():
+                raise AssertionError(f"primitive {k}: {differing_words(batch[k], want(k, poses[k]))}")
+        other = D.random_pose(rigs[0], seed=9, centre=(10.0, 0.5, 0.0))
+        for p in (other, poses[0]):
+            r.update_deformer(3, 0, **p)
+            r.refit()
+            assert r.read_vertices(3, 0).tobytes() == want(0, p).tobytes()
+        assert r.rig_status().batch_launches == after.batch_launches and r.get_deformer_normals(3, 0).launches == normals_before + 6
+        assert r.read_vertices(3, 0).tobytes() == batch[0].tobytes()
+    finally:
+        r.close()
+
+
+@gpu
+def test_rig(halart, tmp_path):
+    """set_rig, mode 1 on the bindings whose targets carry no normal deltas and no skin, pose_rig, refit: those primitives hold the twin's
+    recomputed normals, the others tests/deform_ref.py's vertices"""
+    import hala_renderer_amd as H
+    import rig_ref as R
+    import test_rig as TR
+    from hala_renderer_amd.native_scene import NativeScene
+    path = R.save(R.character_doc(), tmp_path / "character.gltf")
+    nat = NativeScene(path)
+    py = H.HalaScene.new(path)
+    rig = nat.rig
+    r = SE.make(halart, cornell(), scene=nat)
+    try:
+        r.set_rig(rig)
+        wanted = [k for k, b in enumerate(rig.bindings) if b["targets"] is not None and b["normal_targets"] is None and not b["joint_count"]]
+        assert wanted, "the character has a morph-only binding without normal deltas"
+        for k in wanted:
+            r.set_deformer_normals(rig.bindings[k]["mesh_index"], rig.bindings[k]["primitive_index"], ON)
+        before = r.rig_status().pose_launches
+        r.pose_rig(0, 0.625)
+        r.refit()
+        assert r.rig_status().pose_launches == before + 1
+        pose = r.rig_pose()
+        for k, (b, w, p) in enumerate(zip(rig.bindings, pose["weights"], pose["palettes"])):
+            prim = py.meshes[b["mesh_index"]].primitives[b["primitive_index"]]
+            v = D.pose_vertices(prim.vertices, TR.tables_of(b), dict(morph_weights=w, joint_matrices=p))
+            if k in wanted:
+                v2 = N.recompute(v, prim.indices, N.classes(prim.vertices, prim.indices))
+                assert v2["normal"].tobytes() != v["normal"].tobytes()
+                v = v2
+            got = r.read_vertices(b["mesh_index"], b["primitive_index"])
+            if got.tobytes() != v.tobytes():
+                raise AssertionError(f"binding {k}: {differing_words(got, v)}")
+    finally:
+        r.close()
+    nat.close()
+
+
+@gpu
+def test_shutter(halart, oracle):
+    """deformer keys (poses 1 -> 2 on both blocks), mode 1, time_stride 1, four frames: the accumulated images equal the fold of oracle
+    frames whose posed vertices carry the twin's normals at each step's mix"""
+    base = cornell()
+    p1, p2 = TD.cornell_pose(1), TD.cornell_pose(2)
+    r = SE.make(halart, base)
+    try:
+        TD.register(r)
+        for mesh in (TALL, SHORT):
+            r.set_deformer_normals(mesh, 0, ON)
+            r.set_deformer_keys(mesh, 0, open=p1[mesh], close=p2[mesh])
+        r.set_shutter(time_stride=1)
+        r.refit()
+        r.update_batch(3); r.update()
+        images = None
+        for k in range(4):
+            tau = S.frame_time(k, 0.0, 1.0, 1)
+            at = {mesh: S.pose_at(p1[mesh], p2[mesh], tau) for mesh in (TALL, SHORT)}
+            scene = E.apply_to_scene(base.scene, cornell_ops(at, {TALL: ON, SHORT: ON}))
+            images = SE.oracle_images(oracle, base, scene, 1, first_frame=k, images=images)
+        SE.assert_images(r, images, "deformer keys in mode 1")
+        at = {mesh: S.pose_at(p1[mesh], p2[mesh], S.frame_time(3, 0.0, 1.0, 1)) for mesh in (TALL, SHORT)}
+        for mesh in (TALL, SHORT):
+            assert r.read_vertices(mesh, 0).tobytes() == cornell_vertices(mesh, at[mesh], ON).tobytes(), mesh
+        with pytest.raises(halart.HalaRendererError, match="clear them and refit first"):
+            r.set_deformer_normals(TALL, 0, OFF)
+        assert r.get_deformer_normals(TALL, 0).mode == 1
+    finally:
+        r.close()
+
+
+@gpu
+def test_overflow(halart, oracle):
+    """a pose that overflows: the refit fails with the stated message, read_vertices returns the bytes of the last applied pose, recomputed
+    normals included (the put-back launch is followed by the normals passes too), and the next valid refit works"""
+    poses = TD.cornell_pose(1)
+    r = SE.make(halart, cornell())
+    try:
+        TD.register(r)
+        for mesh in (TALL, SHORT):
+            r.set_deformer_normals(mesh, 0, ON)
+        TD.pose(r, poses)
+        r.refit()
+        held = {m: r.read_vertices(m, 0).tobytes() for m in (TALL, SHORT)}
+        assert held == {m: cornell_vertices(m, poses[m], ON).tobytes() for m in (TALL, SHORT)}
+        tree = [x.tobytes() for x in r.download_bvh()]
+        huge = D.identity_palette(3); huge[:, 0, 0] = 3.0e38; huge[:, 0, 1] = 3.0e38
+        for both in (True, False):  # the batch form with a valid second pose beside the offender, then the offender alone
+            r.update_deformer(TALL, 0, joint_matrices=huge)
+            if both:
+                r.update_deformer(SHORT, 0, morph_weights=TD.cornell_pose(2)[SHORT]["morph_weights"])
+            with pytest.raises(halart.HalaRendererError, match="Vertex position is not finite."):
+                r.refit()
+            assert {m: r.read_vertices(m, 0).tobytes() for m in (TALL, SHORT)} == held, both
+            assert [x.tobytes() for x in r.download_bvh()] == tree
+            if both:
+                r.update_deformer(SHORT, 0, morph_weights=poses[SHORT]["morph_weights"])
+                r.refit()
+                assert {m: r.read_vertices(m, 0).tobytes() for m in (TALL, SHORT)} == held
+        # an overflow in the same refit as a mode switch: the arena goes back to what it held, in the mode it was made in
+        r.set_deformer_normals(TALL, 0, OFF)
+        r.update_deformer(TALL, 0, joint_matrices=huge)
+        with pytest.raises(halart.HalaRendererError, match="Vertex position is not finite."):
+            r.refit()
+        assert r.read_vertices(TALL, 0).tobytes() == held[TALL]
+        r.set_deformer_normals(TALL, 0, ON)
+        TD.pose(r, TD.cornell_pose(3))
+        r.refit()
+        for m in (TALL, SHORT):
+            assert r.read_vertices(m, 0).tobytes() == cornell_vertices(m, TD.cornell_pose(3)[m], ON).tobytes(), m
+        r.update_batch(3)
+        SE.assert_images(r, cornell_images(oracle, 3, ON, 3), "a valid pose after the overflow")
+    finally:
+        r.close()
+
+
+@gpu
+def test_mode_and_lifetime(halart, oracle):
+    """mode back to 0 + refit gives tests/deform_ref.py's bytes; a second commit keeps mode and pose; a replacing set_deformer starts at mode
+    0; clear_deformer + refit gives the rest pose; set_scene drops both"""
+    base = cornell()
+    s = base.scene
+    poses = TD.cornell_pose(2)
+    r = SE.make(halart, base)
+    try:
+        TD.register(r)
+        TD.pose(r, poses)
+        r.refit()
+        plain = {m: cornell_vertices(m, poses[m], OFF).tobytes() for m in (TALL, SHORT)}
+        normals = {m: cornell_vertices(m, poses[m], ON).tobytes() for m in (TALL, SHORT)}
+        assert {m: r.read_vertices(m, 0).tobytes() for m in (TALL, SHORT)} == plain
+        for m in (TALL, SHORT):
+            r.set_deformer_normals(m, 0, ON)
+        assert {m: r.read_vertices(m, 0).tobytes() for m in (TALL, SHORT)} == plain, "takes effect at the refit"
+        r.refit()  # the pending parameters are the applied ones: the same pose, now with recomputed normals
+        assert {m: r.read_vertices(m, 0).tobytes() for m in (TALL, SHORT)} == normals
+        r.commit()
+        assert {m: r.read_vertices(m, 0).tobytes() for m in (TALL, SHORT)} == normals
+        assert [r.get_deformer_normals(m, 0).mode for m in (TALL, SHORT)] == [1, 1]
+        r.update_batch(3)
+        SE.assert_images(r, cornell_images(oracle, 2, ON, 3), "after a repeated commit")
+        r.set_deformer_normals(SHORT, 0, OFF)
+        r.refit()
+        assert r.read_vertices(SHORT, 0).tobytes() == plain[SHORT] and r.read_vertices(TALL, 0).tobytes() == normals[TALL]
+        info = r.get_deformer_normals(SHORT, 0)
+        assert (info.mode, info.class_count, info.entry_count) == (0, 0, 0)
+        r.set_deformer(TALL, 0, **TD.cornell_rigs()[TALL])  # a replacement: mode 0, the rest pose at the next refit
+        assert r.get_deformer_normals(TALL, 0).mode == 0
+        r.refit()
+        assert r.read_vertices(TALL, 0).tobytes() == s.meshes[TALL].primitives[0].vertices.tobytes()
+        r.update_deformer(TALL, 0, **poses[TALL])
+        r.refit()
+        assert r.read_vertices(TALL, 0).tobytes() == plain[TALL]
+        r.set_deformer_normals(TALL, 0, ON)
+        r.refit()
+        assert r.read_vertices(TALL, 0).tobytes() == normals[TALL]
+        r.clear_deformer(TALL, 0)
+        r.refit()
+        assert r.read_vertices(TALL, 0).tobytes() == s.meshes[TALL].primitives[0].vertices.tobytes(), "the rest normals come back with the copy"
+        with pytest.raises(halart.HalaRendererError, match="no deformer"):
+            r.get_deformer_normals(TALL, 0)
+        r.set_deformer_normals(SHORT, 0, ON)
+        r.refit()
+        r.set_scene(s)
+        r.commit()
+        for call in (lambda: r.get_deformer_normals(SHORT, 0), lambda: r.set_deformer_normals(SHORT, 0, ON)):
+            with pytest.raises(halart.HalaRendererError, match="no deformer"):
+                call()
+        r.update_batch(3)
+        SE.assert_images(r, TD.rest_images(oracle, 3), "after set_scene")
+    finally:
+        r.close()
+
+
+@gpu
+def test_refusals_change_nothing(halart):
+    base = cornell()
+    s = base.scene
+    err = halart.HalaRendererError
+    fresh = halart.HalaRenderer("normals", base.kw["width"], base.kw["height"], 5, 3, False, False, False, 0)
+    try:
+        for prepare in (lambda: None, lambda: fresh.set_scene(s)):  # nothing set; set, not committed
+            prepare()
+            for call in (lambda: fresh.set_deformer_normals(TALL, 0, ON), lambda: fresh.get_deformer_normals(TALL, 0)):
+                with pytest.raises(err, match="none"):
+                    call()
+    finally:
+        fresh.close()
+    poses = TD.cornell_pose(1)
+    r = SE.make(halart, base)
+    try:
+        TD.register(r)
+        r.set_deformer_normals(TALL, 0, ON)
+        TD.pose(r, poses)
+        r.refit()
+        r.update_batch(2)
+        images = [r.read_image(k).tobytes() for k in range(4)]
+        verts = {m: r.read_vertices(m, 0).tobytes() for m in (TALL, SHORT, 0)}
+        assert verts[TALL] == cornell_vertices(TALL, poses[TALL], ON).tobytes()
+
+        def state():
+            return [r.get_deformer_normals(m, 0).mode for m in (TALL, SHORT)], {m: r.read_vertices(m, 0).tobytes() for m in (TALL, SHORT, 0)}
+
+        r.set_deformer_keys(SHORT, 0, open=poses[SHORT], close=TD.cornell_pose(2)[SHORT])  # recorded, not yet active
+        refusals = [
+            (lambda: r.set_deformer_normals(len(s.meshes), 0, ON), "mesh"),
+            (lambda: r.set_deformer_normals(TALL, 1, ON), "primitive"),
+            (lambda: r.set_deformer_normals(0, 0, ON), "no deformer"),
+            (lambda: r.get_deformer_normals(0, 0), "no deformer"),
+            (lambda: r.set_deformer_normals(TALL, 0, 2), "mode"),
+            (lambda: r.set_deformer_normals(TALL, 0, 0xffffffff), "mode"),
+            (lambda: r.set_deformer_normals(SHORT, 0, ON), "clear them and refit first"),
+        ]
+        for k, (call, word) in enumerate(refusals):
+            with pytest.raises(err, match=word):
+                call()
+            assert state() == ([1, 0], verts), f"refusal {k} ({word})"
+        r.set_deformer_keys(SHORT, 0, None, None)
+        r.refit()  # nothing but the cleared keys is pending: the short block is posed again with the same parameters
+        r.reset_accumulation()
+        r.update_batch(2)
+        assert state() == ([1, 0], verts)
+        assert [r.read_image(k).tobytes() for k in range(4)] == images
+    finally:
+        r.close()
