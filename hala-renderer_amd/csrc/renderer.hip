@@ -15,55 +15,41 @@ int ensure_device(hala_rt_renderer* r, bool join) {
   return HALA_OK;
 }
 
-// wavefront state for `paths` paths per pixel slot in flight (samples x views, hala_rt_update_batch): everything indexed by path slot
-static int alloc_wavefront(hala_rt_renderer* r, uint32_t paths) {
-  const size_t n = (size_t)r->slot_count * paths;
-  if (n > 0xfffffff0ull) RT_FAIL("The sample batch is too large for 32-bit path slots.");
-  RT_HIP(r->ps_lr.resize(n)); RT_HIP(r->ps_le.resize(n)); RT_HIP(r->ps_alb.resize(n)); RT_HIP(r->ps_nrm.resize(n));
-  RT_HIP(r->q_rays[0].resize(n)); RT_HIP(r->q_rays[1].resize(n)); RT_HIP(r->q_state[0].resize(n)); RT_HIP(r->q_state[1].resize(n));
-  RT_HIP(r->q_hits.resize(n)); RT_HIP(r->q_perm.resize(n)); RT_HIP(r->q_shadow[0].resize(n)); RT_HIP(r->q_shadow[1].resize(n));
-  // first-hit AOVs (RENDER_SPEC §13): 16 B per path slot each, only while on (the ids also while Cryptomatte is on, §15)
-  if (r->aov_mask & 1u) RT_HIP(r->ps_aov_pos.resize(n)); else r->ps_aov_pos.release();
-  if (r->wants_ids()) RT_HIP(r->ps_aov_ids.resize(n)); else r->ps_aov_ids.release();
-  // light groups (RENDER_SPEC §14): 12 B per path slot and group; light connections carry the group in the top bits of the slot word
-  if (r->groups.count) {
-    if (n > kGroupSlotMask) RT_FAIL("Light groups need fewer than 2^29 path slots (pixels x samples x views).");
-    RT_HIP(r->groups.ps.resize(n * r->groups.count));
-  } else r->groups.ps.release();
-  r->batch_capacity = paths;
-  // the second frame slot follows (callers have joined it and waited); if it cannot, the renderer works with one slot
-  r->slots.second_failed = false;
-  if (r->slots.second.paths && r->slots.second.alloc(n, (r->aov_mask & 1u) != 0u, r->wants_ids(), r->groups.count) != hipSuccess) {
-    (void)hipGetLastError();
-    r->slots.second_failed = true;
-  }
+// slot 1's set, all or nothing: without it the renderer works with one slot until the sets are sized again
+static bool fit_second(FrameSlots& fs, const PathShape& want) {
+  fs.second_failed = fs.slot[1].set.fit(want) != hipSuccess;
+  if (fs.second_failed) { (void)hipGetLastError(); fs.slot[1].set.release(); }
+  return !fs.second_failed;
+}
+
+// wavefront state for `capacity` paths per pixel slot in flight (samples x views, hala_rt_update_batch)
+static int alloc_wavefront(hala_rt_renderer* r, uint32_t capacity) {
+  FrameSlots& fs = r->slots;
+  const PathShape want = r->path_shape(capacity);
+  if (want.paths > 0xfffffff0ull) RT_FAIL("The sample batch is too large for 32-bit path slots.");
+  if (want.groups && want.paths > kGroupSlotMask) RT_FAIL("Light groups need fewer than 2^29 path slots (pixels x samples x views).");
+  RT_HIP(fs.slot[0].set.fit(want));
+  r->batch_capacity = capacity;
+  fs.second_failed = false;
+  if (fs.slot[1].set.shape.paths) (void)fit_second(fs, want);  // the second frame slot follows (callers have joined it and waited)
   return HALA_OK;
 }
 
-// The slot of an overlapped update: the other one than the latest update's — slot 1 only once its buffers exist, which are allocated the
-// first time slot 0 is found busy (and again after a feature changed what a path slot holds).  Never fails: without them slot 0, serial.
+// The slot of an overlapped update: the other one than the latest update's — slot 1 only once its set exists, which is allocated the
+// first time slot 0 is found busy (and again after a feature changed what a path slot holds).  Never fails: without it slot 0, serial.
 static int pick_slot(hala_rt_renderer* r) {
   FrameSlots& fs = r->slots;
   if (fs.last == 1) return 0;
-  if (r->staged) return 1;  // slot 1's stream and control block, slot 0's buffers (update_impl)
-  WavefrontSet& w = fs.second;
-  const size_t n = (size_t)r->slot_count * r->batch_capacity;
-  const bool pos = (r->aov_mask & 1u) != 0u, ids = r->wants_ids();
-  if (w.paths == n && w.aov_pos == pos && w.aov_ids == ids && w.groups == r->groups.count) return 1;
+  if (r->staged) return 1;  // slot 1's stream and control block, slot 0's set (begin_update)
+  const PathShape want = r->path_shape(), &second = fs.slot[1].set.shape;
+  if (second == want) return 1;
   if (fs.second_failed) return 0;
-  if (w.paths == 0) {  // not yet: only when it would help
-    const bool busy = fs.busy && hipEventQuery(fs.busy) == hipErrorNotReady;
+  if (second.paths == 0) {  // not yet: only when it would help
+    const bool busy = fs.slot[0].end && hipEventQuery(fs.slot[0].end) == hipErrorNotReady;
     (void)hipGetLastError();
     if (!busy) return 0;
-  } else {  // sized for other features (their setters joined and waited)
-    if (fs.join(r->stream) != HALA_OK || hipStreamSynchronize(r->stream) != hipSuccess) return 0;
-  }
-  if (w.alloc(n, pos, ids, r->groups.count) != hipSuccess) {
-    (void)hipGetLastError();
-    fs.second_failed = true;
-    return 0;
-  }
-  return 1;
+  } else if (fs.join(r->stream) != HALA_OK || hipStreamSynchronize(r->stream) != hipSuccess) return 0;  // stale: fitted to other features (their setters joined and waited)
+  return fit_second(fs, want) ? 1 : 0;
 }
 
 int alloc_frame_buffers(hala_rt_renderer* r) {
@@ -213,8 +199,10 @@ int hala_rt_create(const char* name, uint32_t width, uint32_t height, int device
   RT_HIP(hipGetDeviceProperties(&prop, device_ordinal));
   r->cu_count = (uint32_t)prop.multiProcessorCount;
   RT_HIP(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-  RT_HIP(hipStreamCreateWithFlags(&r->slots.stream, hipStreamNonBlocking));
-  for (hipEvent_t* e : {&r->slots.folded[0], &r->slots.folded[1], &r->slots.lead[0], &r->slots.lead[1], &r->slots.forked}) RT_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  FrameSlots& fs = r->slots;
+  fs.slot[0].stream = r->stream;
+  RT_HIP(hipStreamCreateWithFlags(&fs.slot[1].stream, hipStreamNonBlocking));
+  for (hipEvent_t* e : {&fs.slot[0].folded, &fs.slot[1].folded, &fs.slot[0].lead, &fs.slot[1].lead, &fs.forked}) RT_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
   compute_tiling(r.get());
   // create_storage_images (src/rt_renderer.rs:818-917): final, accum, albedo, normal
   if (alloc_frame_buffers(r.get()) != HALA_OK) return HALA_ERR;
@@ -346,12 +334,26 @@ int hala_rt_commit(hala_rt_renderer* r) {
   return HALA_OK;
 }
 
-// `frames` consecutive update()s in one wavefront pass.  Bookkeeping per frame as in the reference: total_frames is
-// incremented first (pre_update, src/renderer.rs:278) and a frame whose number exceeds max_frames is skipped
+// ---- update: `frames` consecutive update()s in one wavefront pass, in four steps (update_impl) ---------------------------------------------
+// what prepare_update decided; samples == 0: the frames count, nothing is launched
+struct UpdatePlan {
+  uint64_t first = 0;           // frame_index of the first frame of the batch
+  uint32_t samples = 0;         // frames that render
+  uint32_t primary_pixels = 0;  // camera rays per frame, all views
+  bool timed = false;           // the update carries per-launch timing events
+  FrameConst fc{}; SceneView sv{};  // (fc.u: the uniform)
+};
+// where begin_update put the update: its entry of the statistics ring, its frame slot and what a launch on that slot takes
+struct SlotRun {
+  TraceEvents* te; int slot; hipStream_t stream; Control* ctl; Queues q; PathState ps; LaunchCfg lc;
+  hipEvent_t lead;        // the slot's, to record
+  hipEvent_t before_end;  // LDS-staged trees: the end of the update before this one, which the depth-0 shade waits for (else null)
+};
+
+// Step 1, host side: validation, the shutter's step, the frame counter, capacity, tables, the uniform.  Bookkeeping per frame as in the
+// reference: total_frames is incremented first (pre_update, src/renderer.rs:278) and a frame whose number exceeds max_frames is skipped
 // (src/rt_renderer.rs:394-396); the frames that do render share one kernel sequence with `samples` paths per pixel.
-static int update_impl(hala_rt_renderer* r, uint32_t frames) {
-  RtRange range("halart::update");
-  if (ensure_device(r, false) != HALA_OK) return HALA_ERR;
+static int prepare_update(hala_rt_renderer* r, uint32_t frames, UpdatePlan* p) {
   if (!r->committed) RT_FAIL("The pipeline is none!");  // src/rt_renderer.rs:443
   const uint32_t V = r->view_count();
   for (uint32_t v = 0; v < V; ++v)  // RENDER_SPEC §12: a scene set or committed after hala_rt_set_views may have fewer cameras
@@ -411,109 +413,132 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
     r->stats.rays_last_update = 0;
     return HALA_OK;
   }
-  const uint32_t primary_pixels = (ad.enabled ? ad.active_pixels : r->real_pixels) * V;  // camera rays per frame, all views
+  p->first = first; p->samples = samples;
+  p->primary_pixels = (ad.enabled ? ad.active_pixels : r->real_pixels) * V;
+  p->fc = r->frame_const(u, samples);
+  p->sv = r->view();
+  // per-launch HIP events (statistics: traverse_*_ms_total) on every launch_event_period-th update; each record is a barrier
+  // packet on the stream, i.e. a few microseconds between two launches
+  p->timed = r->launch_event_period == 1u || (r->launch_event_period > 1u && (r->update_counter % r->launch_event_period) == 0u);
+  r->update_counter++;
+  return HALA_OK;
+}
 
-  TraceEvents& te = r->ring[r->ring_pos];
+// Step 2: the update's frame slot, and its stream put behind everything the update has to follow.  Untimed updates alternate between the
+// two frame slots (FrameSlots), each wholly on its slot's stream.  Updates that carry per-launch timing events or counting kernels join
+// both slots and run alone, so that every measured launch has the chip to itself.
+static int begin_update(hala_rt_renderer* r, const UpdatePlan& p, SlotRun* run) {
+  TraceEvents& te = r->ring[r->ring_pos];  // the update's entry of the statistics ring: what it held before is folded into the totals first
   r->ring_pos = (r->ring_pos + 1) % kStatRing;
   resolve_slot(r, te);
   if (!te.frame_begin) { RT_HIP(hipEventCreate(&te.frame_begin)); RT_HIP(hipEventCreate(&te.frame_end)); RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&te.host_totals), sizeof(Totals), hipHostMallocDefault)); }
   te.used = 0; te.counted = r->counting; te.shadow_launches = 0; te.fused_mask = 0; te.traced_mask = 0;
-
-  te.samples = samples;
-  te.primary_pixels = primary_pixels;
-  const FrameConst fc = r->frame_const(u, samples);
-  const SceneView sv = r->view();
-  // per-launch HIP events (statistics: traverse_*_ms_total) on every launch_event_period-th update; each record is a barrier
-  // packet on the stream, i.e. a few microseconds between two launches
-  const bool timed = r->launch_event_period == 1u || (r->launch_event_period > 1u && (r->update_counter % r->launch_event_period) == 0u);
-  r->update_counter++;
-  // Untimed updates alternate between the two frame slots (FrameSlots), each wholly on its slot's stream.  Updates that carry per-launch
-  // timing events or counting kernels join both slots and run alone, so that every measured launch has the chip to itself.
+  te.samples = p.samples; te.primary_pixels = p.primary_pixels;
   FrameSlots& fs = r->slots;
-  const bool overlapped = fs.in_flight == 2u && !timed && !r->counting;
+  const bool overlapped = fs.in_flight == 2u && !p.timed && !r->counting;
   if (!overlapped && fs.join(r->stream) != HALA_OK) return HALA_ERR;
   const int slot = overlapped ? pick_slot(r) : 0;
   // LDS-staged trees (small scenes): two workgroups of their traversal kernels fill a CU's LDS, so the traversal launches of two updates
   // cannot share the chip, and a second set of buffers only halves what the caches keep from frame to frame (profiles/frames_in_flight.txt).
-  // Their updates alternate between the streams and control blocks but share slot 0's buffers: the camera-ray launch, which touches
+  // Their updates alternate between the streams and control blocks but share slot 0's set: the camera-ray launch, which touches
   // none of what the end of the update before it reads or writes, starts behind that update's last shade, the depth-0 shade behind its end
   const bool shared = overlapped && r->staged;
-  const Queues q = r->queues(shared ? 0 : slot);
-  const PathState ps = r->path_state(shared ? 0 : slot);
-  hipEvent_t const before_end = fs.last == 0 ? fs.busy : fs.done;  // frame_end of the update before this one
-  Control* ctl = r->d_ctl.ptr + slot;
-  const hipStream_t s = slot == 1 ? fs.stream : r->stream;
+  const hipStream_t s = fs.slot[slot].stream;
+  const int set = shared ? 0 : slot;
+  *run = SlotRun{&te, slot, s, r->d_ctl.ptr + slot, r->queues(set), r->path_state(set), r->launch_cfg(slot), fs.slot[slot].lead,
+                 shared && fs.last != slot ? fs.slot[fs.last].end : nullptr};
   if (slot == 1 && fs.fork) {  // whatever the renderer's stream did since the last join (edits, restarts, serial updates) comes first
     RT_HIP(hipEventRecord(fs.forked, r->stream));
     RT_HIP(hipStreamWaitEvent(s, fs.forked, 0));
     fs.fork = false;
   }
   // the camera-ray launch starts beside the last bounces of the update before it (kLeadBounces), which runs on the other slot
-  if (overlapped && fs.last != slot) RT_HIP(hipStreamWaitEvent(s, fs.lead[fs.last], 0));
+  if (overlapped && fs.last != slot) RT_HIP(hipStreamWaitEvent(s, fs.slot[fs.last].lead, 0));
   // slot 0 shares its control block and spill area with external trace_rays calls (which join both slots)
   if (slot == 0 && r->scratch.acquire(s) != HALA_OK) return HALA_ERR;
   RT_HIP(hipEventRecord(te.frame_begin, s));
-  RT_HIP(hipMemsetAsync(ctl, 0, sizeof(Control), s));
+  RT_HIP(hipMemsetAsync(run->ctl, 0, sizeof(Control), s));
+  return HALA_OK;
+}
+
+// Step 3: the kernel sequence of the bounces on the stream of `run`, with the timing events of a timed update.
+static int issue_bounces(hala_rt_renderer* r, const UpdatePlan& p, const SlotRun& run) {
+  TraceEvents& te = *run.te;
+  const hala_global_uniform& u = p.fc.u;
+  Control* ctl = run.ctl;
+  const hipStream_t s = run.stream;
+  const bool timed = p.timed;
   // The shadow passes of bounce d and the closest-hit traversal of bounce d + 1 are independent: untimed updates issue them as ONE
   // persistent launch (k_trace_shadow_then_batch: one tail of long rays instead of three).  Updates that carry per-launch timing events or
   // counting kernels keep one launch per pass, so that every measured launch is one kernel symbol with the chip to itself.
   const bool fuse = (r->fuse_mode == 2u || (r->fuse_mode == 1u && !timed)) && !r->counting && (u.num_of_lights > 0 || u.env_type == 1u);
   if (timed && !te.host_sizes) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&te.host_sizes), sizeof(QueueSizes), hipHostMallocDefault));
   bool traced = false;  // the closest-hit pass of this depth already ran inside the previous depth's fused launch
-  const LaunchCfg lc = r->launch_cfg(slot);
-  // LDS-staged trees: the next update starts behind the last shade (beside the last shadow launches and the resolve only)
+  // where the next update may start (run.lead).  LDS-staged trees: behind the last shade (beside the last shadow launches and the resolve only)
   const uint32_t lead_bounces = r->staged ? 0u : std::min(kLeadBounces, r->max_depth - 1u);
   for (uint32_t depth = 0; depth < r->max_depth; ++depth) {
     if (timed) { hipEvent_t a = next_event(te); RT_HIP(hipEventRecord(a, s)); }
     // depth 0: the camera rays are generated inside the traversal kernel, there is no ray-generation pass
     if (depth == 0) {
-      launch_trace_primary(lc, sv, fc, q.hits, &ctl->work_closest, ctl, primary_pixels * samples, r->counting, s);
+      launch_trace_primary(run.lc, p.sv, p.fc, run.q.hits, &ctl->work_closest, ctl, p.primary_pixels * p.samples, r->counting, s);
       if (r->counting) RT_HIP(hipMemcpyAsync(ctl->totals.primary_steps, ctl->totals.steps[0], 16, hipMemcpyDeviceToDevice, s));
-      if (shared && fs.last != slot && before_end) RT_HIP(hipStreamWaitEvent(s, before_end, 0));
+      if (run.before_end) RT_HIP(hipStreamWaitEvent(s, run.before_end, 0));
     }
-    else if (!traced) launch_trace_batch(lc, sv, q.rays[depth & 1u], q.hits, &ctl->sizes.n_active[depth], 0, &ctl->work_closest, ctl, false, r->counting, true, s);
+    else if (!traced) launch_trace_batch(run.lc, p.sv, run.q.rays[depth & 1u], run.q.hits, &ctl->sizes.n_active[depth], 0, &ctl->work_closest, ctl, false, r->counting, true, s);
     traced = false;
     if (timed) { hipEvent_t b = next_event(te); RT_HIP(hipEventRecord(b, s)); }
-    launch_shade(fc, sv, q, ps, ctl, depth, s);
-    if (depth + 1u + lead_bounces == r->max_depth) RT_HIP(hipEventRecord(fs.lead[slot], s));
+    launch_shade(p.fc, p.sv, run.q, run.ps, ctl, depth, s);
+    if (depth + 1u + lead_bounces == r->max_depth) RT_HIP(hipEventRecord(run.lead, s));
     if (timed) { hipEvent_t c = next_event(te); RT_HIP(hipEventRecord(c, s)); }
     // light connections add to the path's L, environment connections to its Le (RENDER_SPEC §6): the two passes are independent of each
     // other and of the next bounce's closest-hit pass
     const uint32_t kinds = (u.num_of_lights > 0 ? 1u : 0u) | (u.env_type == 1u ? 2u : 0u);
     const bool last = depth + 1u >= r->max_depth;  // no closest-hit pass follows: only worth one launch when there are two shadow passes
-    if (fuse && kinds && (!last || kinds == 3u) && launch_trace_shadow_then_batch(lc, sv, q, ps, ctl, depth, kinds, !last, s)) {
+    if (fuse && kinds && (!last || kinds == 3u) && launch_trace_shadow_then_batch(run.lc, p.sv, run.q, run.ps, ctl, depth, kinds, !last, s)) {
       traced = !last;
       if (timed) { te.fused_mask |= 1ull << depth; if (traced) te.traced_mask |= 1ull << (depth + 1u); }
     }
     else
       for (uint32_t kind = 0; kind < 2u; ++kind) {
         if (!((kinds >> kind) & 1u)) continue;
-        launch_trace_shadow(lc, sv, q, ps, ctl, depth, kind, r->counting, s);
+        launch_trace_shadow(run.lc, p.sv, run.q, run.ps, ctl, depth, kind, r->counting, s);
         te.shadow_launches += timed ? 1u : 0u;
       }
     if (timed) { hipEvent_t d = next_event(te); RT_HIP(hipEventRecord(d, s)); }
   }
+  return HALA_OK;
+}
+
+// Step 4: the samples folded into the accumulated images in frame order, the read-backs, the end of the update and what the slots
+// remember of it; then the snapshot and check frames of adaptive sampling.
+static int finish_update(hala_rt_renderer* r, const UpdatePlan& p, const SlotRun& run) {
+  FrameSlots& fs = r->slots;
+  TraceEvents& te = *run.te;
+  const int slot = run.slot;
+  const hipStream_t s = run.stream;
   // everything that folds into the accumulated images stays in frame order: behind the fold of the update before this one
-  if (fs.last_folded >= 0 && fs.last_folded != slot) RT_HIP(hipStreamWaitEvent(s, fs.folded[fs.last_folded], 0));
-  launch_resolve(fc, ps, r->img_local[0].ptr, r->img_local[1].ptr, r->img_local[2].ptr, r->img_local[3].ptr, r->has_image(4) ? r->img_local[4].ptr : nullptr,
+  if (fs.last_folded >= 0 && fs.last_folded != slot) RT_HIP(hipStreamWaitEvent(s, fs.slot[fs.last_folded].folded, 0));
+  launch_resolve(p.fc, run.ps, r->img_local[0].ptr, r->img_local[1].ptr, r->img_local[2].ptr, r->img_local[3].ptr, r->has_image(4) ? r->img_local[4].ptr : nullptr,
                  r->has_image(5) ? reinterpret_cast<uint4*>(r->img_local[5].ptr) : nullptr, r->groups.img.ptr, r->image_alloc(), s);
   if (r->crypto.mask) {  // RENDER_SPEC §15: fold the batch's first hits right behind the resolve
-    launch_crypto_fold(fc, ps.aov_ids, r->crypto.view(r->slot_count), r->crypto.rec.ptr, s);
+    launch_crypto_fold(p.fc, run.ps.aov_ids, r->crypto.view(r->slot_count), r->crypto.rec.ptr, s);
     r->crypto.ready = true;
   }
-  RT_HIP(hipEventRecord(fs.folded[slot], s));
+  RT_HIP(hipEventRecord(fs.slot[slot].folded, s));
   fs.last_folded = slot; fs.last = slot;
-  RT_HIP(hipMemcpyAsync(te.host_totals, &ctl->totals, sizeof(Totals), hipMemcpyDeviceToHost, s));
-  if (timed) RT_HIP(hipMemcpyAsync(te.host_sizes, &ctl->sizes, sizeof(QueueSizes), hipMemcpyDeviceToHost, s));
+  RT_HIP(hipMemcpyAsync(te.host_totals, &run.ctl->totals, sizeof(Totals), hipMemcpyDeviceToHost, s));
+  if (p.timed) RT_HIP(hipMemcpyAsync(te.host_sizes, &run.ctl->sizes, sizeof(QueueSizes), hipMemcpyDeviceToHost, s));
   // frame_begin -> frame_end spans the whole update
   RT_HIP(hipEventRecord(te.frame_end, s));
-  if (slot == 0) { r->scratch.event = te.frame_end; r->scratch.stream = s; fs.busy = te.frame_end; }
-  else { fs.done = te.frame_end; fs.open = true; fs.second_updates++; }
+  fs.slot[slot].end = te.frame_end;
+  if (slot == 0) { r->scratch.event = te.frame_end; r->scratch.stream = s; }
+  else { fs.open = true; fs.second_updates++; }
   RT_HIP(hipGetLastError());
   te.pending = true;
   for (bool& v : r->full_valid) v = false;
   // RENDER_SPEC 11: hala_rt_update_batch ends its chunks on these frames, so n is the snapshot or check frame itself
-  const uint32_t n = (uint32_t)(first + samples);
+  AdaptiveState& ad = r->adaptive;
+  const uint32_t n = (uint32_t)(p.first + p.samples);
   if (ad.enabled && (n == ad.p.min_samples / 2u || adaptive_is_check(ad.p, n)) && fs.join(r->stream) != HALA_OK) return HALA_ERR;  // they read the accumulation
   if (ad.enabled && n == ad.p.min_samples / 2u) {
     RT_HIP(hipMemcpyAsync(ad.snapshot.ptr, r->img_local[0].ptr, ad.snapshot.bytes(), hipMemcpyDeviceToDevice, r->stream));
@@ -525,6 +550,16 @@ static int update_impl(hala_rt_renderer* r, uint32_t frames) {
     adaptive_finish_check(ad, n);
   }
   return HALA_OK;
+}
+
+static int update_impl(hala_rt_renderer* r, uint32_t frames) {
+  RtRange range("halart::update");
+  if (ensure_device(r, false) != HALA_OK) return HALA_ERR;
+  UpdatePlan plan; SlotRun run;
+  if (prepare_update(r, frames, &plan) != HALA_OK) return HALA_ERR;
+  if (plan.samples == 0) return HALA_OK;  // frames past max_frames, or every block has converged
+  if (begin_update(r, plan, &run) != HALA_OK || issue_bounces(r, plan, run) != HALA_OK) return HALA_ERR;
+  return finish_update(r, plan, run);
 }
 
 int hala_rt_update(hala_rt_renderer* r, double, uint32_t, uint32_t) { return update_impl(r, 1); }
@@ -625,14 +660,14 @@ int hala_rt_set_frames_in_flight(hala_rt_renderer* r, uint32_t n) {
   r->slots.second_failed = false;
   if (n == 1u) {  // strictly serial: one slot, one stream, one set of buffers
     RT_HIP(hipStreamSynchronize(r->stream));
-    r->slots.second.release();
+    r->slots.slot[1].set.release();
   }
   return HALA_OK;
 }
 int hala_rt_frames_in_flight_info(hala_rt_renderer* r, unsigned long long* second_slot_updates, uint32_t* second_buffers) {
   if (!r) RT_FAIL("The renderer handle is null!");
   if (second_slot_updates) *second_slot_updates = r->slots.second_updates;
-  if (second_buffers) *second_buffers = r->slots.second.paths ? 1u : 0u;
+  if (second_buffers) *second_buffers = r->slots.slot[1].set.shape.paths ? 1u : 0u;
   return HALA_OK;
 }
 int hala_rt_set_pass_fusion(hala_rt_renderer* r, uint32_t mode) {

@@ -1,7 +1,10 @@
 // renderer_state.h — the renderer object behind the C ABI (struct hala_rt_renderer), shared by the host units that implement it:
 // renderer.hip (life cycle, scene, update), rt_scene.hip (uploads, trees, edits), rt_outputs.hip (views, AOVs, adaptive sampling, light
 // groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_deform.hip (deformers), rt_rig.hip (rigs and clips), rt_shutter.hip (shutter motion blur), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
-// Each feature keeps its state in one struct that knows how to turn itself off.  Nothing outside csrc/ includes this header.
+// Each feature keeps its state in one struct that knows how to turn itself off.  What is indexed by path slot (per-path state, queues)
+// lives in the WavefrontSet of a frame slot (FrameSlots::slot[2]: two updates in flight), sized by WavefrontSet::fit to the one PathShape
+// that hala_rt_renderer::path_shape() computes: a feature with per-path state adds a field to the shape and an array to the set.
+// Nothing outside csrc/ includes this header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -130,21 +133,20 @@ struct LightGroupState {
   uint32_t count = 0, env_group = 0;
   std::vector<uint32_t> light_group, material_group;
   DeviceArray<uint32_t> d_light_group, d_material_group;
-  DeviceArray<P3> ps;    // count x path slots (slot_count x batch_capacity), group-major
   DeviceArray<float4> img;
   DeviceArray<float4> relit[2];  // hala_rt_relight: linear, tonemapped (W x H)
   bool relit_valid = false;
-  void off() {
+  void off() {  // (the per-path sums belong to the frame slots: hala_rt_renderer::fit_paths)
     count = 0; env_group = 0;
     light_group.clear(); material_group.clear();
-    d_light_group.release(); d_material_group.release(); ps.release(); img.release();
+    d_light_group.release(); d_material_group.release(); img.release();
     relit[0].release(); relit[1].release(); relit_valid = false;
   }
 };
 
 // Cryptomatte (RENDER_SPEC §15; hala_rt_set_cryptomatte): layer mask 0 = off.  rec holds one 64-B record (4 quads) per pixel slot,
 // view and enabled layer (cryptomatte.h: CryptoTables); the id tables are filled by the first update after commit, refit or the call.
-// While on, the depth-0 shade writes the 16-B first-hit record of every path slot (ps_aov_ids) whether or not image 5 is on.
+// While on, the depth-0 shade writes the 16-B first-hit record of every path slot (WavefrontSet::aov_ids) whether or not image 5 is on.
 struct CryptoState {
   uint32_t mask = 0;
   std::vector<std::string> material_names;  // the caller's names ("" = material<m>)
@@ -157,7 +159,7 @@ struct CryptoState {
   CryptoTables view(uint32_t slot_count) const {
     return CryptoTables{d_object.ptr, d_asset.ptr, d_material.ptr, (uint32_t)object.size(), (uint32_t)material.size(), mask, slot_count};
   }
-  void off() {  // (the first-hit records belong to the renderer: hala_rt_renderer::crypto_off)
+  void off() {  // (the first-hit records belong to the frame slots: hala_rt_renderer::fit_paths)
     mask = 0; material_names.clear(); tables = false;
     rec.release(); d_object.release(); d_asset.release(); d_material.release();
   }
@@ -192,73 +194,89 @@ struct ExchangeState {
   }
 };
 
+// What a path slot holds: `paths` path slots (slot_count x batch_capacity), each with the mandatory per-path state and queue entries, the
+// first-hit position and id records while wanted (RENDER_SPEC §13, §15) and one radiance sum per light group (§14).  Computed by
+// hala_rt_renderer::path_shape() alone; a feature that adds a per-path array adds a field here and an array to WavefrontSet::fit
+struct PathShape {
+  size_t paths = 0;  // 0: nothing
+  bool aov_pos = false, aov_ids = false;  // the 16-B first-hit position / id record of every path slot
+  uint32_t groups = 0;                    // light groups: one radiance sum per path slot each
+  bool operator==(const PathShape& o) const { return paths == o.paths && aov_pos == o.aov_pos && aov_ids == o.aov_ids && groups == o.groups; }
+};
+// The per-path state and the queues of one update in flight: everything indexed by path slot.  Each frame slot has one.
+struct WavefrontSet {
+  DeviceArray<P3> lr, le, alb, nrm;
+  DeviceArray<P3> groups;       // shape.groups x path slots, group-major; light connections carry the group in the top bits of the slot word
+  DeviceArray<float4> aov_pos;  // 16 B per path slot each, only while wanted
+  DeviceArray<uint4> aov_ids;
+  DeviceArray<hala_ray> rays[2];
+  DeviceArray<float4> state[2];
+  DeviceArray<hala_hit> hits;
+  DeviceArray<uint32_t> perm;
+  DeviceArray<ShadowEntry> shadow[2];
+  PathShape shape;  // what the last successful fit gave it
+  // Sizes every array for `want` and frees the optional ones it does not name.  Arrays that already have their size are kept as they are,
+  // also when a later allocation fails: the caller then fits again to a shape it can have (a setter: without its feature, which only
+  // frees) or releases the set (slot 1: all or nothing).
+  hipError_t fit(const PathShape& want) {
+    hipError_t e = hipSuccess;
+    auto get = [&](auto& a, size_t count) { if (!count) a.release(); else if (e == hipSuccess) e = a.resize(count); };
+    const size_t n = want.paths;
+    shape = PathShape();
+    get(lr, n); get(le, n); get(alb, n); get(nrm, n);
+    for (int k = 0; k < 2; ++k) { get(rays[k], n); get(state[k], n); get(shadow[k], n); }
+    get(hits, n); get(perm, n);
+    get(aov_pos, want.aov_pos ? n : 0); get(aov_ids, want.aov_ids ? n : 0); get(groups, n * want.groups);
+    if (e == hipSuccess) shape = want;
+    return e;
+  }
+  void release() { (void)fit(PathShape()); }
+  Queues queues() const { return Queues{{rays[0].ptr, rays[1].ptr}, {state[0].ptr, state[1].ptr}, hits.ptr, perm.ptr, {shadow[0].ptr, shadow[1].ptr}}; }
+  void fill(PathState* ps) const {  // the pointers of a PathState that differ between the slots (an array that is off is null)
+    ps->radiance = lr.ptr; ps->radiance_env = le.ptr; ps->albedo = alb.ptr; ps->normal = nrm.ptr;
+    ps->aov_pos = aov_pos.ptr; ps->aov_ids = aov_ids.ptr; ps->groups = groups.ptr;
+  }
+};
+
 // Two frame slots: consecutive updates are independent except for the order in which their samples are folded into the
 // accumulated images, so untimed updates alternate between two slots and the start of one runs beside the end of the other (`lead`).  A
-// slot owns what one update in flight needs: a stream (slot 0 the
-// renderer's, slot 1 `stream`), a control block (d_ctl[slot]), a stack spill area, the per-path state and the queues (slot 0 the renderer's
-// members, slot 1 `second`).  An update waits for the previous use of its slot by stream order; between the slots there is one dependency:
-// the resolve (and the Cryptomatte fold) of an update waits for `folded` of the update before it.  While slot 1 is open the renderer's
-// stream has not waited for it: every entry point joins it first (ensure_device), except update and render.
-struct WavefrontSet {  // slot 1's copy of what alloc_wavefront gives slot 0; allocated when an update first finds slot 0 busy
-  DeviceArray<P3> ps_lr, ps_le, ps_alb, ps_nrm, groups_ps;
-  DeviceArray<float4> ps_aov_pos;
-  DeviceArray<uint4> ps_aov_ids;
-  DeviceArray<hala_ray> q_rays[2];
-  DeviceArray<float4> q_state[2];
-  DeviceArray<hala_hit> q_hits;
-  DeviceArray<uint32_t> q_perm;
-  DeviceArray<ShadowEntry> q_shadow[2];
-  size_t paths = 0;  // path slots it holds; 0: not allocated
-  bool aov_pos = false, aov_ids = false;
-  uint32_t groups = 0;
-  void release() {
-    ps_lr.release(); ps_le.release(); ps_alb.release(); ps_nrm.release(); groups_ps.release(); ps_aov_pos.release(); ps_aov_ids.release();
-    for (int k = 0; k < 2; ++k) { q_rays[k].release(); q_state[k].release(); q_shadow[k].release(); }
-    q_hits.release(); q_perm.release();
-    paths = 0;
-  }
-  hipError_t alloc(size_t n, bool pos, bool ids, uint32_t group_count) {
-    hipError_t e = hipSuccess;
-    auto get = [&](auto& a, size_t count) { if (e == hipSuccess) e = a.resize(count); };
-    get(ps_lr, n); get(ps_le, n); get(ps_alb, n); get(ps_nrm, n);
-    for (int k = 0; k < 2; ++k) { get(q_rays[k], n); get(q_state[k], n); get(q_shadow[k], n); }
-    get(q_hits, n); get(q_perm, n);
-    if (pos) get(ps_aov_pos, n); else ps_aov_pos.release();
-    if (ids) get(ps_aov_ids, n); else ps_aov_ids.release();
-    if (group_count) get(groups_ps, n * group_count); else groups_ps.release();
-    if (e != hipSuccess) { release(); return e; }
-    paths = n; aov_pos = pos; aov_ids = ids; groups = group_count;
-    return hipSuccess;
-  }
+// slot owns what one update in flight needs: a stream, a stack spill area, the per-path state and the queues (`set`), and a control block
+// (hala_rt_renderer::d_ctl[slot]).  An update waits for the previous use of its slot by stream order; between the slots there is one
+// dependency: the resolve (and the Cryptomatte fold) of an update waits for `folded` of the update before it.  While slot 1 is open the
+// renderer's stream has not waited for it: every entry point joins it first (ensure_device), except update and render.
+// Slot 1's set is allocated when an update first finds slot 0 busy, and fitted again when it is found stale (pick_slot); LDS-staged trees
+// never allocate it: their updates on slot 1 use slot 0's set.
+struct FrameSlot {
+  hipStream_t stream = nullptr;  // slot 0: hala_rt_renderer::stream, which the renderer creates and destroys; slot 1: owned here
+  WavefrontSet set;
+  DeviceArray<uint2> spill;      // stack spill area of the slot's traversal launches (slot 0's also serves hala_rt_trace_rays: ScratchOrder)
+  hipEvent_t folded = nullptr;   // behind the resolve and the Cryptomatte fold of the slot's latest update
+  hipEvent_t lead = nullptr;     // behind the shade kLeadBounces before the last of the slot's latest update: where the next update starts
+  // not owned: the frame_end event of the slot's latest update, which lives in the statistics ring.  A ring entry is recorded again 16
+  // updates later; by then its slot has run a newer update (updates alternate, and every serial one runs on slot 0, so no slot sits out
+  // 16 updates while the other runs) and `end` has moved on — except slot 1's while slot 1 is unused, which is waited for only while
+  // `open` (before the first join after slot 1's latest update) or as the end of the update before this one (`last` == 1: it is the
+  // latest update's, recorded once since)
+  hipEvent_t end = nullptr;
 };
 struct FrameSlots {
   uint32_t in_flight = 2;          // hala_rt_set_frames_in_flight: 1 = one slot, one stream
-  hipStream_t stream = nullptr;    // slot 1's
-  hipEvent_t folded[2] = {nullptr, nullptr};  // behind the resolve and the Cryptomatte fold of the slot's latest update
-  hipEvent_t lead[2] = {nullptr, nullptr};    // behind the shade kLeadBounces before the last of the slot's latest update: where the next update starts
+  FrameSlot slot[2];
   hipEvent_t forked = nullptr;     // the renderer's stream as the last join left it: where slot 1 starts again
-  // not owned: the frame_end events of the two slots' latest updates, which live in the statistics ring.  A ring entry is recorded
-  // again 16 updates later; by then its slot has run a newer update (updates alternate, and every serial one runs on slot 0, so no
-  // slot sits out 16 updates while the other runs) and the pointer has moved on — except `done` while slot 1 is unused, which is only
-  // waited for while `open`, i.e. before the first join after slot 1's latest update
-  hipEvent_t done = nullptr;       // slot 1's
-  hipEvent_t busy = nullptr;       // slot 0's
   bool open = false;               // slot 1 holds work the renderer's stream has not waited for
   bool fork = true;                // the renderer's stream holds work slot 1 has not waited for
-  bool second_failed = false;      // slot 1's buffers could not be had: one slot until the buffers are sized again
+  bool second_failed = false;      // slot 1's set could not be had: one slot until the sets are sized again
   int last = 1;                    // slot of the latest update (the next overlapped one takes the other)
   unsigned long long second_updates = 0;  // updates that ran on slot 1 (hala_rt_frames_in_flight_info)
   int last_folded = -1;            // slot whose `folded` is the latest
-  WavefrontSet second;
-  DeviceArray<uint2> d_spill;      // slot 1's stack spill area
   int join(hipStream_t renderer_stream) {
-    if (open) RT_HIP(hipStreamWaitEvent(renderer_stream, done, 0));
+    if (open) RT_HIP(hipStreamWaitEvent(renderer_stream, slot[1].end, 0));
     open = false; fork = true;
     return HALA_OK;
   }
-  void release() {
-    for (hipEvent_t e : {folded[0], folded[1], lead[0], lead[1], forked}) if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
+  void release() {  // the events and slot 1's stream; slot 0's stream is the renderer's, `end` the statistics ring's
+    for (hipEvent_t e : {slot[0].folded, slot[1].folded, slot[0].lead, slot[1].lead, forked}) if (e) (void)hipEventDestroy(e);
+    if (slot[1].stream) (void)hipStreamDestroy(slot[1].stream);
   }
 };
 
@@ -292,7 +310,7 @@ struct hala_rt_renderer {
   uint32_t max_depth = 0, rr_depth = 0;
   bool enable_tonemap = false, enable_aces = false, use_simple_aces = false;
   uint64_t max_frames = 0;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;  // the renderer's stream, which is frame slot 0's (slots.slot[0].stream)
   uint32_t cu_count = 256;
 
   float ground[4] = {1.0f, 1.0f, 1.0f, 1.0f};  // src/rt_renderer.rs:799
@@ -356,8 +374,7 @@ struct hala_rt_renderer {
   bool staged = false;  // whole BVH staged in LDS by the traversal kernels
   uint32_t leaf_max_built = 0;
   float ray_eps = 0.0f;
-  DeviceArray<uint2> d_spill;
-  LaunchCfg lcfg{};
+  LaunchCfg lcfg{};  // (spill: frame slot 0's area)
   uint32_t fuse_mode = 1;  // hala_rt_set_pass_fusion: 0 never, 1 untimed updates, 2 always (shadow passes of bounce d + closest-hit pass of bounce d + 1 in one launch)
 
   bool has_env = false;
@@ -387,16 +404,10 @@ struct hala_rt_renderer {
   // first-hit AOVs (RENDER_SPEC §13): bit 0 position (image 4), bit 1 ids (image 5); hala_rt_set_aovs
   uint32_t aov_mask = 0;
   bool has_image(int which) const { return which >= 0 && (which < 4 || (which < 6 && ((aov_mask >> (which - 4)) & 1u))); }
-  DeviceArray<float4> ps_aov_pos;
-  DeviceArray<uint4> ps_aov_ids;
   DeviceArray<uint32_t> d_inst_node, d_light_node;  // per instance / per light: the scene node it came from
   LightGroupState groups;
   CryptoState crypto;
   bool wants_ids() const { return (aov_mask & 2u) || crypto.mask; }
-  void crypto_off() {
-    crypto.off();
-    if (!(aov_mask & 2u)) ps_aov_ids.release();
-  }
   DenoiseBuffers denoise;      // RENDER_SPEC 10: allocated by the first hala_rt_denoise
   bool denoised = false;       // denoise.out holds a result
   AdaptiveState adaptive;      // RENDER_SPEC 11: allocated by the first hala_rt_set_adaptive_sampling that enables it
@@ -404,13 +415,7 @@ struct hala_rt_renderer {
   DeformState deform;          // RENDER_SPEC 17: one deformer per primitive (hala_rt_set_deformer)
   ShutterState shutter;        // RENDER_SPEC 18: keys and shutter (hala_rt_set_shutter)
   RigState rig;                // RENDER_SPEC 19: the rig whose bindings are deformers here (hala_rt_set_rig)
-  DeviceArray<P3> ps_lr, ps_le, ps_alb, ps_nrm;
-  DeviceArray<hala_ray> q_rays[2];
-  DeviceArray<float4> q_state[2];
-  DeviceArray<hala_hit> q_hits;
-  DeviceArray<uint32_t> q_perm;
-  DeviceArray<ShadowEntry> q_shadow[2];
-  DeviceArray<Control> d_ctl;
+  DeviceArray<Control> d_ctl;  // one per frame slot
   DeviceArray<WorkCounters> d_batch_work;
 
   uint64_t total_frames = 0;
@@ -434,8 +439,7 @@ struct hala_rt_renderer {
 
   ~hala_rt_renderer() {
     if (device >= 0) (void)hipSetDevice(device);
-    if (stream) (void)hipStreamSynchronize(stream);
-    if (slots.stream) (void)hipStreamSynchronize(slots.stream);
+    for (const FrameSlot& s : slots.slot) if (s.stream) (void)hipStreamSynchronize(s.stream);
     for (auto& t : ring) {
       for (auto e : t.ev) (void)hipEventDestroy(e);
       if (t.frame_begin) (void)hipEventDestroy(t.frame_begin);
@@ -472,37 +476,23 @@ struct hala_rt_renderer {
   // the traversal launches of an update on frame slot `slot`: with the slot's spill area
   LaunchCfg launch_cfg(int slot) const {
     LaunchCfg lc = lcfg;
-    if (slot == 1 && lcfg.spill) lc.spill = slots.d_spill.ptr;
+    if (lcfg.spill) lc.spill = slots.slot[slot].spill.ptr;
     return lc;
   }
-  Queues queues(int slot = 0) const {
-    Queues q{};
-    if (slot == 1) {
-      const WavefrontSet& w = slots.second;
-      q.rays[0] = w.q_rays[0].ptr; q.rays[1] = w.q_rays[1].ptr; q.state[0] = w.q_state[0].ptr; q.state[1] = w.q_state[1].ptr;
-      q.hits = w.q_hits.ptr; q.perm = w.q_perm.ptr; q.shadow[0] = w.q_shadow[0].ptr; q.shadow[1] = w.q_shadow[1].ptr;
-      return q;
-    }
-    q.rays[0] = q_rays[0].ptr; q.rays[1] = q_rays[1].ptr; q.state[0] = q_state[0].ptr; q.state[1] = q_state[1].ptr;
-    q.hits = q_hits.ptr; q.perm = q_perm.ptr; q.shadow[0] = q_shadow[0].ptr; q.shadow[1] = q_shadow[1].ptr;
-    return q;
-  }
-  PathState path_state(int slot = 0) const {
-    PathState ps = path_state0();
-    if (slot == 1) {
-      const WavefrontSet& w = slots.second;
-      ps.radiance = w.ps_lr.ptr; ps.radiance_env = w.ps_le.ptr; ps.albedo = w.ps_alb.ptr; ps.normal = w.ps_nrm.ptr;
-      if (ps.aov_pos) ps.aov_pos = w.ps_aov_pos.ptr;
-      if (ps.aov_ids) ps.aov_ids = w.ps_aov_ids.ptr;
-      if (ps.groups) ps.groups = w.groups_ps.ptr;
-    }
+  // what a path slot holds with `capacity` paths per pixel slot in flight: the one place that says so
+  PathShape path_shape(uint32_t capacity) const { return PathShape{(size_t)slot_count * capacity, (aov_mask & 1u) != 0u, wants_ids(), groups.count}; }
+  PathShape path_shape() const { return path_shape(batch_capacity); }
+  // Slot 0's set follows a setter that changed the shape (the setters have joined slot 1 and waited; slot 1's set catches up when an
+  // update next wants it: pick_slot).  It fails only where the new shape adds an array: the setter then turns its feature off and fits again
+  hipError_t fit_paths() { return slots.slot[0].set.fit(path_shape()); }
+  Queues queues(int slot) const { return slots.slot[slot].set.queues(); }
+  PathState path_state(int slot) const {
+    PathState ps{};  // what the slots share: the node tables and the light groups' tables (null and 0 while the groups are off)
+    ps.inst_node = d_inst_node.ptr; ps.light_node = d_light_node.ptr;
+    ps.light_group = groups.d_light_group.ptr; ps.material_group = groups.d_material_group.ptr;
+    ps.group_count = groups.count; ps.group_stride = groups.count ? (uint32_t)path_shape().paths : 0u; ps.env_group = groups.env_group;
+    slots.slot[slot].set.fill(&ps);
     return ps;
-  }
-  PathState path_state0() const {
-    return PathState{ps_lr.ptr, ps_le.ptr, ps_alb.ptr, ps_nrm.ptr, (aov_mask & 1u) ? ps_aov_pos.ptr : nullptr, wants_ids() ? ps_aov_ids.ptr : nullptr,
-                     d_inst_node.ptr, d_light_node.ptr,
-                     groups.count ? groups.ps.ptr : nullptr, groups.count ? groups.d_light_group.ptr : nullptr, groups.count ? groups.d_material_group.ptr : nullptr,
-                     groups.count, groups.count ? (uint32_t)((size_t)slot_count * batch_capacity) : 0u, groups.env_group};
   }
 
   // RENDER_SPEC §5 / §7.4 for packed camera `cam`: tan(yfov / 2) and the angular size of one pixel

@@ -44,7 +44,7 @@ static std::map<std::string, uint32_t> crypto_names(const hala_rt_renderer* r, u
 // before an update's device work: the id tables of the committed scene (first update after commit, refit or hala_rt_set_cryptomatte) and
 // records sized for the current views (hala_rt_set_views may have changed them); nothing in flight may still read the old ones
 int crypto_prepare(hala_rt_renderer* r) {
-  if (!r->ps_aov_ids.ptr || r->ps_aov_ids.count < (size_t)r->slot_count * r->batch_capacity)
+  if (!(r->slots.slot[0].set.shape == r->path_shape()))  // (a fit that failed)
     RT_FAIL("hala_rt_update: the first-hit records Cryptomatte folds are not allocated (call hala_rt_set_cryptomatte again).");
   const size_t quads = r->crypto.quads(r->view_count(), r->slot_count);
   if (r->crypto.tables && r->crypto.rec.count == quads) return HALA_OK;
@@ -94,14 +94,14 @@ int hala_rt_set_cryptomatte(hala_rt_renderer* r, const hala_cryptomatte_desc* d)
   for (size_t m = 0; m < names.size(); ++m) names[m] = d->material_names[m] ? d->material_names[m] : "";
   if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins the second frame slot
   RT_HIP(hipStreamSynchronize(r->stream));
-  r->crypto_off();
+  r->crypto.off();
+  if (d) r->crypto.mask = d->layer_mask;
+  hipError_t e = r->fit_paths();  // the first-hit records of every path slot; off: freed unless image 5 wants them
   if (d) {
-    r->crypto.mask = d->layer_mask;
-    hipError_t e = r->ps_aov_ids.resize((size_t)r->slot_count * r->batch_capacity);
     if (e == hipSuccess) e = r->crypto.rec.resize(r->crypto.quads(r->view_count(), r->slot_count));
     if (e == hipSuccess) e = hipMemsetAsync(r->crypto.rec.ptr, 0, r->crypto.rec.bytes(), r->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-    if (e != hipSuccess) { r->crypto_off(); RT_HIP(e); }  // out of memory: the feature is off, everything else untouched
+    if (e != hipSuccess) { r->crypto.off(); (void)r->fit_paths(); RT_HIP(e); }  // out of memory: the feature is off, everything else untouched
     r->crypto.material_names = std::move(names);
   }
   r->reset_accumulation();

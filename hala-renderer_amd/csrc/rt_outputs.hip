@@ -73,21 +73,19 @@ int hala_rt_set_aovs(hala_rt_renderer* r, uint32_t mask) {
   r->aov_mask = mask;
   r->invalidate(Changed::Aovs);
   hipError_t e = hipSuccess;
-  const size_t n = r->image_alloc(), paths = (size_t)r->slot_count * r->batch_capacity;
+  const size_t n = r->image_alloc();
   for (int k = 4; k < 6 && e == hipSuccess; ++k) {
     if (!r->has_image(k)) { r->img_local[k].release(); r->img_full[k].release(); r->exchange.stage[k].release(); r->exchange.recv[k].release(); continue; }
     if (r->img_local[k].count == n && ((old >> (k - 4)) & 1u)) continue;  // stays on: kept (the accumulation restarts below)
     e = r->img_local[k].resize(n);
     if (e == hipSuccess) e = hipMemsetAsync(r->img_local[k].ptr, 0, n * sizeof(float4), r->stream);
   }
-  if (e == hipSuccess) { if (mask & 1u) e = r->ps_aov_pos.resize(paths); else r->ps_aov_pos.release(); }
-  if (e == hipSuccess) { if (r->wants_ids()) e = r->ps_aov_ids.resize(paths); else r->ps_aov_ids.release(); }  // §15 keeps them
+  if (e == hipSuccess) e = r->fit_paths();  // the first-hit records of every path slot (§15 keeps the ids)
   if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
   if (e != hipSuccess) {  // out of memory: the AOVs are off, the other images are untouched
     r->aov_mask = 0;
     for (int k = 4; k < 6; ++k) r->img_local[k].release();
-    r->ps_aov_pos.release();
-    if (!r->crypto.mask) r->ps_aov_ids.release();
+    (void)r->fit_paths();
     RT_HIP(e);
   }
   r->reset_accumulation();
@@ -176,21 +174,21 @@ int hala_rt_set_light_groups(hala_rt_renderer* r, const hala_light_groups* g) {
   }
   if (!r) RT_FAIL("The renderer handle is null!");
   if (g && r->world > 1) RT_FAIL("hala_rt_set_light_groups: light groups are not available on a sharded renderer (world > 1).");
-  if (g && (size_t)r->slot_count * r->batch_capacity > kGroupSlotMask)
+  if (g && r->path_shape().paths > kGroupSlotMask)
     RT_FAIL("hala_rt_set_light_groups: light groups need fewer than 2^29 path slots (pixels x samples x views).");
   if (ensure_device(r) != HALA_OK) return HALA_ERR;  // joins the second frame slot
   RT_HIP(hipStreamSynchronize(r->stream));
   r->groups.off();
+  if (g) r->groups.count = g->group_count;
+  hipError_t e = r->fit_paths();  // one radiance sum per path slot and group; off: freed
   if (g) {
-    const size_t G = g->group_count, paths = (size_t)r->slot_count * r->batch_capacity, n = r->image_alloc();
-    hipError_t e = r->groups.ps.resize(paths * G);
-    if (e == hipSuccess) e = r->groups.img.resize(n * G);
+    if (e == hipSuccess) e = r->groups.img.resize(r->image_alloc() * g->group_count);
     if (e == hipSuccess) e = hipMemsetAsync(r->groups.img.ptr, 0, r->groups.img.bytes(), r->stream);
     if (e == hipSuccess) e = r->groups.d_light_group.upload(g->light_group, g->light_count, r->stream);
     if (e == hipSuccess) e = r->groups.d_material_group.upload(g->material_group, g->material_count, r->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-    if (e != hipSuccess) { r->groups.off(); RT_HIP(e); }  // out of memory: the groups are off, the other images are untouched
-    r->groups.count = g->group_count; r->groups.env_group = g->environment_group;
+    if (e != hipSuccess) { r->groups.off(); (void)r->fit_paths(); RT_HIP(e); }  // out of memory: the groups are off, the other images are untouched
+    r->groups.env_group = g->environment_group;
     r->groups.light_group.assign(g->light_group, g->light_group + g->light_count);
     r->groups.material_group.assign(g->material_group, g->material_group + g->material_count);
   }

@@ -247,9 +247,9 @@ static int configure_traversal(hala_rt_renderer* r) {
     }
     if (r->bvh.stack_need > traverse_stack_lds_levels(tree) + traverse_stack_spill_levels())
       RT_FAIL("The BVH is deeper than the traversal stack supports (" + std::to_string(r->bvh.max_depth) + " levels, " + std::to_string(r->bvh.stack_need) + " stack entries).");
-    RT_HIP(r->d_spill.resize((size_t)r->lcfg.persistent_blocks * 256 * traverse_stack_spill_levels()));
-    RT_HIP(r->slots.d_spill.resize(r->d_spill.count));  // the second frame slot's launches, which run beside the first's
-    r->lcfg.spill = r->d_spill.ptr;
+    for (FrameSlot& s : r->slots.slot)  // one area per frame slot: the slots' launches run beside each other
+      RT_HIP(s.spill.resize((size_t)r->lcfg.persistent_blocks * 256 * traverse_stack_spill_levels()));
+    r->lcfg.spill = r->slots.slot[0].spill.ptr;
   }
   const float ex = r->bvh.scene_max[0] - r->bvh.scene_min[0], ey = r->bvh.scene_max[1] - r->bvh.scene_min[1], ez = r->bvh.scene_max[2] - r->bvh.scene_min[2];
   r->ray_eps = std::sqrt(std::fmaf(ez, ez, std::fmaf(ey, ey, ex * ex))) * 1e-5f;  // RENDER_SPEC §3

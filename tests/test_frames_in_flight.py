@@ -238,6 +238,49 @@ def test_features_in_flight(halart, name):
     both(halart, FEATURES[name])
 
 
+# ---- case 4: what a path slot holds changes while slot 1 owns buffers ----------------------------------------------------------------
+def shape_changes(r):
+    """five segments, each behind a setter that restarts the accumulation: the per-path arrays grow and shrink (AOVs, light groups, the
+    Cryptomatte first-hit records, the batch capacity) while the second slot is already sized for what came before"""
+    crypto = lambda: [r.read_cryptomatte_records(layer) for layer in ("object", "material", "asset")]
+    groups = lambda: [r.read_light_group(g) for g in range(r.light_group_count)]
+    out = []
+    for _ in range(3):
+        r.update()
+    out += images(r) + [totals(r)]
+    r.set_aovs(position=True, ids=True)
+    for _ in range(3):
+        r.update()
+    out += images(r, 6) + [totals(r)]
+    r.set_light_groups(environment=1)
+    r.update_batch(3); r.update(); r.update()  # the batch grows the capacity while slot 1 is sized
+    out += images(r, 6) + groups() + [totals(r)]
+    r.set_aovs(position=False, ids=False)
+    r.set_cryptomatte()
+    for _ in range(3):
+        r.update()
+    out += images(r) + groups() + crypto() + [totals(r)]
+    r.set_light_groups()
+    r.update_batch(2); r.update()
+    return out + crypto() + [totals(r)] + images(r)  # last: three frames, images 0-3 as with every feature off
+
+
+@gpu
+@pytest.mark.parametrize("which", ["atrium", "cornell"])
+def test_shape_changes_in_flight(halart, oracle, which):
+    used = []
+    got = both(halart, shape_changes, which, used=used)
+    assert used[0][0] >= 1 and used[0][1] == (which == "atrium"), used
+    assert used[1] == (0, False), used
+    if which == "atrium":
+        scene, env = atrium()
+        w, h = W, H
+    else:
+        scene, env, w, h = scenes.cornell_box(aspect=67 / 45), None, 67, 45
+    want, _ = oracle.OracleScene(scene, envmap=env).render(w, h, frames=3, max_depth=MAX_DEPTH, rr_depth=RR_DEPTH)
+    same(got[-4:], want, f"{which}: the last segment against the oracle")
+
+
 @gpu
 def test_tile_shard_in_flight(halart):
     """two emulated ranks of a 2-rank shard, 16 x 16 tiles: each rank's tile buffers with two slots against one"""
