@@ -1,5 +1,7 @@
 // deform.h — GPU-resident deformers of docs/RENDER_SPEC.md 17: morph targets and a four-influence skin per primitive, their tables on
-// the device, the parameters the host records per frame, and the host side of the kernel of deform.hip.
+// the device, the parameters the host records per frame, and the host side of the kernels of deform.hip and deform_normals.hip.  A call
+// of the posing function (rt_deform.hip) poses any number of deformers, from one up, with one launch of each kernel: a segment per
+// deformer, a map from workgroups to segments, all of it in one staged buffer that is copied once.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,7 +18,6 @@ namespace rt {
 constexpr uint32_t kMaxMorphTargets = HALA_MAX_MORPH_TARGETS;
 constexpr uint32_t kMaxJoints = HALA_MAX_JOINTS;
 constexpr uint32_t kDeformThreads = 256;  // one lane per vertex
-constexpr size_t kDeformBatchMin = 2;     // dirty deformers from which a refit poses them all with one launch
 
 // what k_deform reads and writes of one primitive
 struct DeformTables {
@@ -27,25 +28,17 @@ struct DeformTables {
   const float* dt;          // tangent deltas, same shape, or null
   const uint2* joints;      // four uint16 per vertex; null: no skin
   const float4* weights;    // four floats per vertex
-  const float* palette;     // joint_count row-major 3 x 4 matrices
+  const float* palette;     // joint_count row-major 3 x 4 matrices, in the staged buffer
   uint32_t vertex_count, joint_count;
-  uint32_t* flag;           // set to 1 when a posed position is not finite
+  uint32_t* flag;           // the deformer's own overflow word: set to 1 when a posed position is not finite
 };
-// the targets whose weight is not 0, in ascending order (RENDER_SPEC 17): passed by value, read with scalar loads
-struct DeformActive {
-  uint32_t count;
-  uint32_t index[kMaxMorphTargets];
-  float weight[kMaxMorphTargets];
-};
-
-// The batch form (k_deform_batch: two or more dirty deformers, one launch).  One segment per deformer, a map from workgroups to
-// segments, and the active targets of all segments packed; with the palettes they make one staged buffer, copied once.
+// a target whose weight is not 0; a deformer's are packed in ascending order (RENDER_SPEC 17) and read with scalar loads
 struct DeformActiveEntry { uint32_t index; float weight; };
 struct DeformSegment {
-  DeformTables t;                       // palette: into the staged buffer; flag: the segment's own overflow word
-  uint32_t active_first, active_count;  // into the packed active-target list
+  DeformTables t;
+  uint32_t active_first, active_count;  // into the packed active-target list of the launch
 };
-struct DeformBlock { uint32_t segment, first_vertex; };  // 8 B per workgroup
+struct DeformBlock { uint32_t segment, first_vertex; };  // 8 B per workgroup: its segment and the first of its 256 items (vertices or triangles)
 static_assert(sizeof(DeformSegment) % 8 == 0 && sizeof(DeformBlock) == 8 && sizeof(DeformActiveEntry) == 8, "the staged sections are 8-byte records");
 
 // "Recomputed normals" (RENDER_SPEC 17; deform_normals.hip): what the face pass and the vertex pass read and write of one primitive
@@ -58,7 +51,7 @@ struct NormalsTables {
   const uint32_t* entries;   // triangle numbers, per class in ascending 3 * triangle + corner
   uint32_t triangle_count, vertex_count;
 };
-static_assert(sizeof(NormalsTables) == 56, "segments of the batch form are 8-byte records");
+static_assert(sizeof(NormalsTables) == 56, "the staged sections are 8-byte records");
 
 // The registered deformer of one primitive.  `applied` and `posed` say what the arena holds (kept by deform_pose, rt_deform.hip);
 // `pending` and `dirty` are what the caller recorded for the next refit (written by the entry points and by that refit alone).
@@ -66,7 +59,7 @@ struct Deformer {
   uint32_t prim = 0, vertex_count = 0, target_count = 0, joint_count = 0;
   uint64_t id = 0;  // unique among the deformers of one renderer (DeformState::next_id): tells a replacement on the same primitive apart
   DeviceArray<hala_vertex> d_rest;
-  DeviceArray<float> d_dp, d_dn, d_dt, d_palette;
+  DeviceArray<float> d_dp, d_dn, d_dt;
   DeviceArray<uint2> d_joints;
   DeviceArray<float4> d_weights;
   bool has_dn = false, has_dt = false;
@@ -88,27 +81,23 @@ struct Deformer {
 struct DeformState {
   std::map<uint32_t, std::unique_ptr<Deformer>> by_prim;  // key: index into HostScene::prims
   DeviceArray<uint32_t> d_flags;                           // one overflow word per deformer of a call of deform_pose
-  std::vector<unsigned char> h_stage;                      // the batch launch's tables as laid out on the host, and their device copy
-  DeviceArray<unsigned char> d_stage;
-  uint64_t launches = 0, segments = 0;                     // pose launches (either kernel) and deformers they posed, since hala_rt_create
-  uint64_t batch_launches = 0;                             // those of k_deform_batch among them
-  std::vector<unsigned char> h_normals_stage;              // the batch form of the normals passes: segments and block maps, staged like h_stage
-  DeviceArray<unsigned char> d_normals_stage;
-  uint64_t normals_launches = 0;                           // launches of the two normals kernels (either form), since hala_rt_create
+  std::vector<unsigned char> h_stage;                      // what the launches of one call read (segments, block maps, active targets,
+  DeviceArray<unsigned char> d_stage;                      // palettes) as laid out on the host, and its device copy
+  uint64_t launches = 0, segments = 0;                     // launches of k_deform and deformers they posed, since hala_rt_create
+  uint64_t batch_launches = 0;                             // those among them that posed two or more deformers
+  uint64_t normals_launches = 0;                           // launches of the two normals kernels, since hala_rt_create
   uint64_t next_id = 0;
   bool lost = false;                                       // a device error interrupted deform_pose: the arena is undefined
-  void off() { by_prim.clear(); d_flags.release(); d_stage.release(); d_normals_stage.release(); lost = false; }
+  void off() { by_prim.clear(); d_flags.release(); d_stage.release(); lost = false; }
 };
 
-// one lane per vertex, one launch on `s`
-void launch_deform(const DeformTables& t, const DeformActive& a, hipStream_t s);
-// the same for every segment at once: device pointers, block_count workgroups, LDS for the largest palette of the launch
-void launch_deform_batch(const DeformSegment* segments, const DeformBlock* blocks, const DeformActiveEntry* active, uint32_t block_count,
-                         uint32_t max_joint_count, hipStream_t s);
-// deform_normals.hip: the face pass and the vertex pass of one primitive (two launches on `s`), and of every segment at once (two
-// launches: face_blocks / vertex_blocks map workgroups to (segment, first triangle / first vertex))
-void launch_deform_normals(const NormalsTables& t, hipStream_t s);
-void launch_deform_normals_batch(const NormalsTables* segments, const DeformBlock* face_blocks, uint32_t face_block_count,
-                                 const DeformBlock* vertex_blocks, uint32_t vertex_block_count, hipStream_t s);
+// k_deform, one lane per vertex, one launch on `s` for every segment: device pointers, block_count workgroups, LDS for the largest
+// palette of the launch
+void launch_deform(const DeformSegment* segments, const DeformBlock* blocks, const DeformActiveEntry* active, uint32_t block_count,
+                   uint32_t max_joint_count, hipStream_t s);
+// deform_normals.hip: the face pass and the vertex pass of every segment, two launches on `s` (face_blocks / vertex_blocks map
+// workgroups to (segment, first triangle / first vertex))
+void launch_deform_normals(const NormalsTables* segments, const DeformBlock* face_blocks, uint32_t face_block_count,
+                           const DeformBlock* vertex_blocks, uint32_t vertex_block_count, hipStream_t s);
 
 }  // namespace rt

@@ -1,14 +1,12 @@
-// deform.hip — docs/RENDER_SPEC.md 17: morph targets and skinning on the GPU.  k_deform poses the vertices of one primitive from its
-// rest pose into the vertex arena, just ahead of the refit that reads them: one lane per vertex, 256-thread workgroups, wave64.
-// k_deform_batch does the same for every dirty deformer of a refit in one launch (a segment per deformer, a workgroup inside one
-// segment); both call pose_vertex, so the arithmetic is one piece of code.  Every
-// `*` and `+` is the one the spec writes, each rounded (-ffp-contract=off: no fma), so that tests/deform_ref.py reproduces the
-// vertices bit for bit.
+// deform.hip — docs/RENDER_SPEC.md 17: morph targets and skinning on the GPU.  k_deform poses the vertices of every dirty deformer of
+// a refit, one or many, from their rest poses into the vertex arena, just ahead of the refit that reads them: one launch, a segment per
+// deformer, a workgroup inside one segment, one lane per vertex, 256-thread workgroups, wave64.  Every `*` and `+` is the one the spec
+// writes, each rounded (-ffp-contract=off: no fma), so that tests/deform_ref.py reproduces the vertices bit for bit.
 //
 // Memory per vertex: 44 B of the rest record read and 44 B of the posed record written, 12 B per active target and attribute that has
 // deltas (a wave's 64 vertices of one target are one contiguous 768-B run), 8 B of joint indices and 16 B of weights when there is a
 // skin.  The joint palette (at most 256 x 48 B) is staged in LDS once per workgroup; each lane reads its four matrices from there as
-// 16-B quads.  The active targets come in by value and are walked by a wave-uniform loop (scalar loads).
+// 16-B quads.  The segment's active targets are walked by a wave-uniform loop (scalar loads).
 //
 // The 44-B records are an array of structures and are read and written in place: 11 dword accesses per lane, 44 B apart from the
 // neighbour's, a wave's 64 records being one contiguous 2816-B run that the caches serve whole.  The other form — the workgroup moves
@@ -25,8 +23,8 @@ namespace rt {
 namespace {
 
 #define DF_LDS __attribute__((address_space(3)))
-// Device memory, said so: a pointer that k_deform_batch reads from its segment table is generic to the compiler, which would address it
-// with flat instructions; a kernel argument's is global already and the cast changes nothing.
+// Device memory, said so: a pointer that k_deform reads from its segment table is generic to the compiler, which would address it with
+// flat instructions.
 #define DF_GLOBAL __attribute__((address_space(1)))
 typedef float df_f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t df_u32x2 __attribute__((ext_vector_type(2)));
@@ -45,10 +43,10 @@ __device__ __forceinline__ void morph(float* a, const DF_GLOBAL float* deltas, s
 __device__ __forceinline__ float affine(const Row& m, const float* p) { return ((m.x * p[0] + m.y * p[1]) + m.z * p[2]) + m.w; }
 __device__ __forceinline__ float linear(const Row& m, const float* p) { return (m.x * p[0] + m.y * p[1]) + m.z * p[2]; }
 
-// RENDER_SPEC 17 for vertex `v` of the primitive `t` describes: the arithmetic both kernels share.  `active(i, &index, &weight)` names the
-// i-th active target (wave-uniform); `palette` is the primitive's palette in LDS.  -> whether the posed position is not finite
-template <class Active>
-__device__ __forceinline__ bool pose_vertex(const DeformTables& t, uint32_t active_count, const Active& active, DF_LDS df_f32x4* palette, uint32_t v) {
+// RENDER_SPEC 17 for vertex `v` of the primitive `t` describes.  `active` lists its active_count active targets (wave-uniform);
+// `palette` is the primitive's palette in LDS.  -> whether the posed position is not finite
+__device__ __forceinline__ bool pose_vertex(const DeformTables& t, uint32_t active_count, const DeformActiveEntry* __restrict__ active, DF_LDS df_f32x4* palette,
+                                            uint32_t v) {
   const uint32_t n = t.vertex_count;
   float r[kRecordWords];  // position, normal, tangent, tex_coord
   const DF_GLOBAL float* src = (const DF_GLOBAL float*)(t.rest + v);
@@ -57,8 +55,8 @@ __device__ __forceinline__ bool pose_vertex(const DeformTables& t, uint32_t acti
   const DF_GLOBAL float* dt = (const DF_GLOBAL float*)t.dt;
   for (uint32_t k = 0; k < kRecordWords; ++k) r[k] = src[k];
   for (uint32_t i = 0; i < active_count; ++i) {
-    uint32_t index; float w;
-    active(i, &index, &w);
+    const uint32_t index = active[i].index;
+    const float w = active[i].weight;
     const size_t at = ((size_t)index * n + v) * 3u;
     morph(r, dp, at, w);
     if (dn) morph(r + 3, dn, at, w);
@@ -104,23 +102,11 @@ __device__ __forceinline__ void raise_flag(bool bad, uint32_t tid, uint32_t* fla
     __hip_atomic_fetch_or((DF_GLOBAL uint32_t*)flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (atomicOr, on global memory)
 }
 
-__global__ __launch_bounds__(kDeformThreads) void k_deform(const DeformTables t, const DeformActive a) {
-  extern __shared__ df_f32x4 smem[];  // the palette: 48 B per joint
-  DF_LDS df_f32x4* palette = (DF_LDS df_f32x4*)smem;
-  const uint32_t tid = threadIdx.x;
-  const uint32_t v = blockIdx.x * kDeformThreads + tid;
-  stage_palette(palette, t.palette, t.joint_count, tid);
-  bool bad = false;
-  if (v < t.vertex_count)
-    bad = pose_vertex(t, a.count, [&a](uint32_t i, uint32_t* index, float* w) { *index = a.index[i]; *w = a.weight[i]; }, palette, v);
-  raise_flag(bad, tid, t.flag);
-}
-
-// The batch form: every dirty deformer of a refit in one launch.  Workgroup b poses the 256 vertices from DeformBlock::first_vertex on of
-// segment DeformBlock::segment; no workgroup spans two segments, so the segment, its tables and its active targets are uniform over
-// the workgroup: their addresses derive from blockIdx.x alone and nothing the launch writes aliases them, so the loads are scalar.
-__global__ __launch_bounds__(kDeformThreads) void k_deform_batch(const DeformSegment* __restrict__ segments, const DeformBlock* __restrict__ blocks,
-                                                                  const DeformActiveEntry* __restrict__ active) {
+// Workgroup b poses the 256 vertices from DeformBlock::first_vertex on of segment DeformBlock::segment; no workgroup spans two
+// segments, so the segment, its tables and its active targets are uniform over the workgroup: their addresses derive from blockIdx.x
+// alone and nothing the launch writes aliases them, so the loads are scalar.
+__global__ __launch_bounds__(kDeformThreads) void k_deform(const DeformSegment* __restrict__ segments, const DeformBlock* __restrict__ blocks,
+                                                            const DeformActiveEntry* __restrict__ active) {
   extern __shared__ df_f32x4 smem[];  // the palette of this workgroup's segment
   DF_LDS df_f32x4* palette = (DF_LDS df_f32x4*)smem;
   const uint32_t tid = threadIdx.x;
@@ -132,22 +118,16 @@ __global__ __launch_bounds__(kDeformThreads) void k_deform_batch(const DeformSeg
   stage_palette(palette, t.palette, t.joint_count, tid);
   bool bad = false;
   if (v < t.vertex_count)
-    bad = pose_vertex(t, active_count, [act](uint32_t i, uint32_t* index, float* w) { *index = act[i].index; *w = act[i].weight; }, palette, v);
+    bad = pose_vertex(t, active_count, act, palette, v);
   raise_flag(bad, tid, t.flag);
 }
 
 }  // namespace
 
-void launch_deform(const DeformTables& t, const DeformActive& a, hipStream_t s) {
-  if (!t.vertex_count) return;
-  const uint32_t blocks = (t.vertex_count + kDeformThreads - 1) / kDeformThreads;
-  hipLaunchKernelGGL(k_deform, dim3(blocks), dim3(kDeformThreads), (size_t)t.joint_count * 48, s, t, a);
-}
-
-void launch_deform_batch(const DeformSegment* segments, const DeformBlock* blocks, const DeformActiveEntry* active, uint32_t block_count,
-                         uint32_t max_joint_count, hipStream_t s) {
+void launch_deform(const DeformSegment* segments, const DeformBlock* blocks, const DeformActiveEntry* active, uint32_t block_count,
+                   uint32_t max_joint_count, hipStream_t s) {
   if (!block_count) return;
-  hipLaunchKernelGGL(k_deform_batch, dim3(block_count), dim3(kDeformThreads), (size_t)max_joint_count * 48, s, segments, blocks, active);
+  hipLaunchKernelGGL(k_deform, dim3(block_count), dim3(kDeformThreads), (size_t)max_joint_count * 48, s, segments, blocks, active);
 }
 
 }  // namespace rt

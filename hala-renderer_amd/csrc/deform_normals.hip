@@ -13,8 +13,9 @@
 // correctly rounded ones, so tests/deform_normals_ref.py reproduces the vertices bit for bit.  A vertex whose sum has no usable length
 // (empty list, zero, overflow, NaN from positions that overflowed) is not written at all: it keeps what k_deform wrote.
 //
-// The batch forms serve the k_deform_batch path: a segment per mode-1 deformer, a map from workgroups to (segment, first item), no
-// workgroup spanning two segments, so the segment's tables are uniform over the workgroup and come in by scalar loads.
+// Like k_deform, each pass is one launch for all the deformers of a refit that want it: a segment per deformer, a map from workgroups to
+// (segment, first item), no workgroup spanning two segments, so the segment's tables are uniform over the workgroup and come in by
+// scalar loads.
 #include <hip/hip_runtime.h>
 
 #include "deform.h"
@@ -74,24 +75,14 @@ __device__ __forceinline__ void vertex_pass(const NormalsTables& t, uint32_t v) 
   rec[6] = tx; rec[7] = ty; rec[8] = tz;
 }
 
-__global__ __launch_bounds__(kDeformThreads) void k_deform_faces(const NormalsTables t) {
-  const uint32_t tri = blockIdx.x * kDeformThreads + threadIdx.x;
-  if (tri < t.triangle_count) face_pass(t, tri);
-}
-
-__global__ __launch_bounds__(kDeformThreads) void k_deform_vertex_normals(const NormalsTables t) {
-  const uint32_t v = blockIdx.x * kDeformThreads + threadIdx.x;
-  if (v < t.vertex_count) vertex_pass(t, v);
-}
-
-__global__ __launch_bounds__(kDeformThreads) void k_deform_faces_batch(const NormalsTables* __restrict__ segments, const DeformBlock* __restrict__ blocks) {
+__global__ __launch_bounds__(kDeformThreads) void k_deform_faces(const NormalsTables* __restrict__ segments, const DeformBlock* __restrict__ blocks) {
   const DeformBlock b = blocks[blockIdx.x];
   const NormalsTables t = segments[b.segment];
   const uint32_t tri = b.first_vertex + threadIdx.x;  // (the block map's second word: the first triangle here)
   if (tri < t.triangle_count) face_pass(t, tri);
 }
 
-__global__ __launch_bounds__(kDeformThreads) void k_deform_vertex_normals_batch(const NormalsTables* __restrict__ segments, const DeformBlock* __restrict__ blocks) {
+__global__ __launch_bounds__(kDeformThreads) void k_deform_vertex_normals(const NormalsTables* __restrict__ segments, const DeformBlock* __restrict__ blocks) {
   const DeformBlock b = blocks[blockIdx.x];
   const NormalsTables t = segments[b.segment];
   const uint32_t v = b.first_vertex + threadIdx.x;
@@ -100,17 +91,11 @@ __global__ __launch_bounds__(kDeformThreads) void k_deform_vertex_normals_batch(
 
 }  // namespace
 
-void launch_deform_normals(const NormalsTables& t, hipStream_t s) {
-  if (!t.triangle_count || !t.vertex_count) return;  // no triangle: every list is empty and every vertex keeps its values
-  hipLaunchKernelGGL(k_deform_faces, dim3((t.triangle_count + kDeformThreads - 1) / kDeformThreads), dim3(kDeformThreads), 0, s, t);
-  hipLaunchKernelGGL(k_deform_vertex_normals, dim3((t.vertex_count + kDeformThreads - 1) / kDeformThreads), dim3(kDeformThreads), 0, s, t);
-}
-
-void launch_deform_normals_batch(const NormalsTables* segments, const DeformBlock* face_blocks, uint32_t face_block_count,
-                                 const DeformBlock* vertex_blocks, uint32_t vertex_block_count, hipStream_t s) {
+void launch_deform_normals(const NormalsTables* segments, const DeformBlock* face_blocks, uint32_t face_block_count,
+                           const DeformBlock* vertex_blocks, uint32_t vertex_block_count, hipStream_t s) {
   if (!face_block_count || !vertex_block_count) return;
-  hipLaunchKernelGGL(k_deform_faces_batch, dim3(face_block_count), dim3(kDeformThreads), 0, s, segments, face_blocks);
-  hipLaunchKernelGGL(k_deform_vertex_normals_batch, dim3(vertex_block_count), dim3(kDeformThreads), 0, s, segments, vertex_blocks);
+  hipLaunchKernelGGL(k_deform_faces, dim3(face_block_count), dim3(kDeformThreads), 0, s, segments, face_blocks);
+  hipLaunchKernelGGL(k_deform_vertex_normals, dim3(vertex_block_count), dim3(kDeformThreads), 0, s, segments, vertex_blocks);
 }
 
 }  // namespace rt

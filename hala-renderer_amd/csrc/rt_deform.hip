@@ -1,9 +1,9 @@
 // rt_deform.hip — deformers (docs/RENDER_SPEC.md 17; include/halart.h "Deformers"): the registry of one deformer per primitive, the
-// host-side checks of tables and parameters, the launches of k_deform (deform.hip) that hala_rt_refit makes ahead of refitting the
+// host-side checks of tables and parameters, the launch of k_deform (deform.hip) that hala_rt_refit makes ahead of refitting the
 // tree, and the read-back of a primitive's vertices.  Invariants: the primitive's range of the vertex arena holds the rest pose while
 // Deformer::posed is false, and k_deform(rest, tables, Deformer::applied) otherwise; HostPrimitive::vertices stays the rest pose;
 // Deformer::pending and dirty hold what the caller recorded, and posing (deform_pose) takes its parameters as arguments.
-// Recomputed normals (Deformer::normals_mode 1; deform_normals.hip) are part of posing: launch_all queues the two passes behind the
+// Recomputed normals (Deformer::normals_mode 1; deform_normals.hip) are part of posing: launch_poses queues the two passes behind the
 // pose launch, so the arena of a posed deformer with Deformer::normals_applied holds them too.
 #include "deform_adjacency.h"
 #include "renderer_state.h"
@@ -18,75 +18,17 @@ static int restore_rest(hala_rt_renderer* r, Deformer& d) {
   return HALA_OK;
 }
 
-static DeformTables tables_of(hala_rt_renderer* r, Deformer& d, uint32_t* flag) {
+static DeformTables tables_of(hala_rt_renderer* r, Deformer& d, const float* palette, uint32_t* flag) {
   DeformTables t{};
   t.rest = d.d_rest.ptr; t.out = r->arena(d.prim);
   t.dp = d.target_count ? d.d_dp.ptr : nullptr;
   t.dn = d.has_dn ? d.d_dn.ptr : nullptr;
   t.dt = d.has_dt ? d.d_dt.ptr : nullptr;
   t.joints = d.joint_count ? d.d_joints.ptr : nullptr;
-  t.weights = d.d_weights.ptr; t.palette = d.d_palette.ptr;
+  t.weights = d.d_weights.ptr; t.palette = palette;
   t.vertex_count = d.vertex_count; t.joint_count = d.joint_count;
   t.flag = flag;
   return t;
-}
-
-static int launch(hala_rt_renderer* r, Deformer& d, const Deformer::Params& p, uint32_t* flag) {
-  const DeformTables t = tables_of(r, d, flag);
-  DeformActive a{};
-  for (uint32_t k = 0; k < d.target_count; ++k)
-    if (p.weights[k] != 0.0f) { a.index[a.count] = k; a.weight[a.count] = p.weights[k]; ++a.count; }
-  // (the palette lives in the Deformer, which outlives the copy: every caller synchronises before it changes the parameters)
-  if (d.joint_count) RT_HIP(hipMemcpyAsync(d.d_palette.ptr, p.palette.data(), p.palette.size() * 4, hipMemcpyHostToDevice, r->stream));
-  launch_deform(t, a, r->stream);
-  RT_HIP(hipGetLastError());
-  return HALA_OK;
-}
-
-// Two or more deformers at once (k_deform_batch): segment table, block map, active targets and palettes are laid out in
-// DeformState::h_stage, copied to the device in one piece and posed by one launch.  Item k raises flags[k].  (The staged bytes stay
-// as they are until the caller has synchronised, as the palettes of the single launch do.)
-static int launch_batch(hala_rt_renderer* r, const std::vector<DeformPose>& items, uint32_t* flags) {
-  DeformState& ds = r->deform;
-  size_t blocks = 0, actives = 0, palette_floats = 0;
-  uint32_t max_joints = 0;
-  for (const DeformPose& it : items) {
-    blocks += (it.d->vertex_count + kDeformThreads - 1) / kDeformThreads;
-    for (float w : it.p->weights) actives += w != 0.0f;
-    palette_floats += (size_t)it.d->joint_count * 12u;
-    max_joints = std::max(max_joints, it.d->joint_count);
-  }
-  if (!blocks) return HALA_OK;
-  auto align16 = [](size_t n) { return (n + 15u) & ~(size_t)15u; };
-  const size_t off_blocks = align16(items.size() * sizeof(DeformSegment)), off_active = align16(off_blocks + blocks * sizeof(DeformBlock)),
-               off_palette = align16(off_active + actives * sizeof(DeformActiveEntry)), total = off_palette + palette_floats * 4u;
-  ds.h_stage.assign(total, 0);
-  if (total > ds.d_stage.count) RT_HIP(ds.d_stage.resize(total));
-  DeformSegment* seg = reinterpret_cast<DeformSegment*>(ds.h_stage.data());
-  DeformBlock* blk = reinterpret_cast<DeformBlock*>(ds.h_stage.data() + off_blocks);
-  DeformActiveEntry* act = reinterpret_cast<DeformActiveEntry*>(ds.h_stage.data() + off_active);
-  float* pal = reinterpret_cast<float*>(ds.h_stage.data() + off_palette);
-  const float* d_pal = reinterpret_cast<const float*>(ds.d_stage.ptr + off_palette);
-  uint32_t nb = 0, na = 0;
-  size_t np = 0;
-  for (size_t k = 0; k < items.size(); ++k) {
-    Deformer& d = *items[k].d;
-    const Deformer::Params& p = *items[k].p;
-    seg[k].t = tables_of(r, d, flags + k);
-    seg[k].t.palette = d_pal + np;
-    seg[k].active_first = na;
-    for (uint32_t t = 0; t < d.target_count; ++t)
-      if (p.weights[t] != 0.0f) act[na++] = DeformActiveEntry{t, p.weights[t]};
-    seg[k].active_count = na - seg[k].active_first;
-    std::copy(p.palette.begin(), p.palette.begin() + (size_t)d.joint_count * 12u, pal + np);
-    np += (size_t)d.joint_count * 12u;
-    for (uint32_t v = 0; v < d.vertex_count; v += kDeformThreads) blk[nb++] = DeformBlock{(uint32_t)k, v};
-  }
-  RT_HIP(hipMemcpyAsync(ds.d_stage.ptr, ds.h_stage.data(), total, hipMemcpyHostToDevice, r->stream));
-  launch_deform_batch(reinterpret_cast<const DeformSegment*>(ds.d_stage.ptr), reinterpret_cast<const DeformBlock*>(ds.d_stage.ptr + off_blocks),
-                      reinterpret_cast<const DeformActiveEntry*>(ds.d_stage.ptr + off_active), nb, max_joints, r->stream);
-  RT_HIP(hipGetLastError());
-  return HALA_OK;
 }
 
 static NormalsTables normals_tables_of(hala_rt_renderer* r, Deformer& d) {
@@ -97,67 +39,79 @@ static NormalsTables normals_tables_of(hala_rt_renderer* r, Deformer& d) {
   return t;
 }
 
-// The face pass and the vertex pass (deform_normals.hip) of `list`, behind the pose launch on the stream: two launches for one deformer,
-// two launches of the batch forms for several (segments and both block maps staged and copied in one piece, as launch_batch does).
-static int launch_normals(hala_rt_renderer* r, const std::vector<Deformer*>& list, bool batch, bool count) {
-  DeformState& ds = r->deform;
-  std::vector<Deformer*> work;
-  for (Deformer* d : list)
-    if (d->triangle_count && d->vertex_count) work.push_back(d);  // (no triangle: every list is empty, nothing would be written)
-  if (work.empty()) return HALA_OK;
-  if (!batch) {
-    for (Deformer* d : work) {
-      launch_deform_normals(normals_tables_of(r, *d), r->stream);
-      RT_HIP(hipGetLastError());
-      if (count) ds.normals_launches += 2;
-    }
-    return HALA_OK;
-  }
-  size_t face_blocks = 0, vertex_blocks = 0;
-  for (Deformer* d : work) {
-    face_blocks += (d->triangle_count + kDeformThreads - 1) / kDeformThreads;
-    vertex_blocks += (d->vertex_count + kDeformThreads - 1) / kDeformThreads;
-  }
-  const size_t off_face = work.size() * sizeof(NormalsTables), off_vertex = off_face + face_blocks * sizeof(DeformBlock),
-               total = off_vertex + vertex_blocks * sizeof(DeformBlock);
-  ds.h_normals_stage.assign(total, 0);
-  if (total > ds.d_normals_stage.count) RT_HIP(ds.d_normals_stage.resize(total));
-  NormalsTables* seg = reinterpret_cast<NormalsTables*>(ds.h_normals_stage.data());
-  DeformBlock* fb = reinterpret_cast<DeformBlock*>(ds.h_normals_stage.data() + off_face);
-  DeformBlock* vb = reinterpret_cast<DeformBlock*>(ds.h_normals_stage.data() + off_vertex);
-  uint32_t nf = 0, nv = 0;
-  for (size_t k = 0; k < work.size(); ++k) {
-    seg[k] = normals_tables_of(r, *work[k]);
-    for (uint32_t t = 0; t < work[k]->triangle_count; t += kDeformThreads) fb[nf++] = DeformBlock{(uint32_t)k, t};
-    for (uint32_t v = 0; v < work[k]->vertex_count; v += kDeformThreads) vb[nv++] = DeformBlock{(uint32_t)k, v};
-  }
-  RT_HIP(hipMemcpyAsync(ds.d_normals_stage.ptr, ds.h_normals_stage.data(), total, hipMemcpyHostToDevice, r->stream));
-  launch_deform_normals_batch(reinterpret_cast<const NormalsTables*>(ds.d_normals_stage.ptr), reinterpret_cast<const DeformBlock*>(ds.d_normals_stage.ptr + off_face), nf,
-                              reinterpret_cast<const DeformBlock*>(ds.d_normals_stage.ptr + off_vertex), nv, r->stream);
-  RT_HIP(hipGetLastError());
-  if (count) ds.normals_launches += 2;
-  return HALA_OK;
+static size_t blocks_of(uint32_t count) { return (count + kDeformThreads - 1) / kDeformThreads; }
+// the block map of one segment: (segment, first item) per 256 items of `count`, appended at blocks[*n]
+static void append_blocks(DeformBlock* blocks, uint32_t* n, uint32_t segment, uint32_t count) {
+  for (uint32_t first = 0; first < count; first += kDeformThreads) blocks[(*n)++] = DeformBlock{segment, first};
 }
 
-// one deformer: k_deform as always; kDeformBatchMin or more: one launch of k_deform_batch (DESIGN.md 19 has the measurement behind it).
-// Behind either, the normals passes of the deformers that want them: those in mode 1, or, where the launch puts an applied pose back
-// (`applied`), those whose applied pose had them.  Deformers in mode 0 make no launch and are no segment of the batch forms.
-static int launch_all(hala_rt_renderer* r, const std::vector<DeformPose>& items, uint32_t* flags, bool count, bool applied) {
+// Poses `items`, one or many, with one launch of k_deform, item k raising flags[k]; behind it the face pass and the vertex pass
+// (deform_normals.hip) of the items that want them, one launch each: those in mode 1, or, where the call puts an applied pose back
+// (`applied`), those whose applied pose had them.  The others are no segment of the two passes.  What the launches read — the pose
+// segments, the normals segments, the block maps of the three launches, the active targets and the palettes, each section 16-B aligned —
+// is laid out in DeformState::h_stage and copied to the device in one piece.  (The staged bytes stay as they are until the caller
+// has synchronised: deform_pose does, inside launch_flagged before it stages the put-back and again behind the put-back.)
+static int launch_poses(hala_rt_renderer* r, const std::vector<DeformPose>& items, uint32_t* flags, bool count, bool applied) {
   if (items.empty()) return HALA_OK;
-  const bool batch = items.size() >= kDeformBatchMin;
-  if (batch) {
-    if (launch_batch(r, items, flags) != HALA_OK) return HALA_ERR;
-    if (count) { r->deform.launches += 1; r->deform.batch_launches += 1; r->deform.segments += items.size(); }
-  } else {
-    for (size_t k = 0; k < items.size(); ++k) {
-      if (launch(r, *items[k].d, *items[k].p, flags + k) != HALA_OK) return HALA_ERR;
-      if (count) { r->deform.launches += 1; r->deform.segments += 1; }
-    }
+  DeformState& ds = r->deform;
+  auto wants_normals = [applied](const Deformer& d) {  // (no triangle: every list is empty, nothing would be written)
+    return (applied ? d.normals_applied : d.normals_mode == HALA_DEFORM_NORMALS_RECOMPUTED) && d.triangle_count && d.vertex_count;
+  };
+  size_t normals = 0, pose_blocks = 0, face_blocks = 0, vertex_blocks = 0, actives = 0, palette_floats = 0;
+  uint32_t max_joints = 0;
+  for (const DeformPose& it : items) {
+    pose_blocks += blocks_of(it.d->vertex_count);
+    if (wants_normals(*it.d)) { ++normals; face_blocks += blocks_of(it.d->triangle_count); vertex_blocks += blocks_of(it.d->vertex_count); }
+    for (float w : it.p->weights) actives += w != 0.0f;
+    palette_floats += (size_t)it.d->joint_count * 12u;
+    max_joints = std::max(max_joints, it.d->joint_count);
   }
-  std::vector<Deformer*> normals;
-  for (const DeformPose& it : items)
-    if (applied ? it.d->normals_applied : it.d->normals_mode == HALA_DEFORM_NORMALS_RECOMPUTED) normals.push_back(it.d);
-  return launch_normals(r, normals, batch, count);
+  if (pose_blocks) {
+    size_t total = 0;
+    auto section = [&total](size_t bytes) { const size_t at = total; total = (total + bytes + 15u) & ~(size_t)15u; return at; };
+    const size_t off_seg = section(items.size() * sizeof(DeformSegment)), off_nseg = section(normals * sizeof(NormalsTables)),
+                 off_pose = section(pose_blocks * sizeof(DeformBlock)), off_face = section(face_blocks * sizeof(DeformBlock)),
+                 off_vertex = section(vertex_blocks * sizeof(DeformBlock)), off_active = section(actives * sizeof(DeformActiveEntry)),
+                 off_palette = section(palette_floats * 4u);
+    ds.h_stage.assign(total, 0);
+    if (total > ds.d_stage.count) RT_HIP(ds.d_stage.resize(total));
+    unsigned char *h = ds.h_stage.data(), *d = ds.d_stage.ptr;
+    DeformSegment* seg = reinterpret_cast<DeformSegment*>(h + off_seg);
+    NormalsTables* nseg = reinterpret_cast<NormalsTables*>(h + off_nseg);
+    DeformBlock *pb = reinterpret_cast<DeformBlock*>(h + off_pose), *fb = reinterpret_cast<DeformBlock*>(h + off_face), *vb = reinterpret_cast<DeformBlock*>(h + off_vertex);
+    DeformActiveEntry* act = reinterpret_cast<DeformActiveEntry*>(h + off_active);
+    float* pal = reinterpret_cast<float*>(h + off_palette);
+    uint32_t npb = 0, nfb = 0, nvb = 0, na = 0, nn = 0;
+    size_t np = 0;
+    for (size_t k = 0; k < items.size(); ++k) {
+      Deformer& df = *items[k].d;
+      const Deformer::Params& p = *items[k].p;
+      seg[k].t = tables_of(r, df, reinterpret_cast<const float*>(d + off_palette) + np, flags + k);
+      seg[k].active_first = na;
+      for (uint32_t t = 0; t < df.target_count; ++t)
+        if (p.weights[t] != 0.0f) act[na++] = DeformActiveEntry{t, p.weights[t]};
+      seg[k].active_count = na - seg[k].active_first;
+      std::copy(p.palette.begin(), p.palette.begin() + (size_t)df.joint_count * 12u, pal + np);
+      np += (size_t)df.joint_count * 12u;
+      append_blocks(pb, &npb, (uint32_t)k, df.vertex_count);
+      if (!wants_normals(df)) continue;
+      nseg[nn] = normals_tables_of(r, df);
+      append_blocks(fb, &nfb, nn, df.triangle_count);
+      append_blocks(vb, &nvb, nn, df.vertex_count);
+      ++nn;
+    }
+    RT_HIP(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, r->stream));
+    launch_deform(reinterpret_cast<const DeformSegment*>(d + off_seg), reinterpret_cast<const DeformBlock*>(d + off_pose),
+                  reinterpret_cast<const DeformActiveEntry*>(d + off_active), npb, max_joints, r->stream);
+    launch_deform_normals(reinterpret_cast<const NormalsTables*>(d + off_nseg), reinterpret_cast<const DeformBlock*>(d + off_face), nfb,
+                          reinterpret_cast<const DeformBlock*>(d + off_vertex), nvb, r->stream);
+    RT_HIP(hipGetLastError());
+  }
+  if (count) {
+    ds.launches += 1; ds.batch_launches += items.size() >= 2; ds.segments += items.size();
+    if (normals) ds.normals_launches += 2;
+  }
+  return HALA_OK;
 }
 
 // Overflow to a non-finite position: the arena is put back by running the kernel again with the last applied parameters — it is
@@ -172,7 +126,7 @@ int deform_pose(hala_rt_renderer* r, const std::vector<DeformPose>& items, std::
   ds.lost = true;
   std::vector<uint32_t> flags;
   bool overflow = false;
-  if (launch_flagged(ds.d_flags, items.size(), r->stream, [&](uint32_t* words) { return launch_all(r, items, words, true, false); }, &flags, &overflow) != HALA_OK)
+  if (launch_flagged(ds.d_flags, items.size(), r->stream, [&](uint32_t* words) { return launch_poses(r, items, words, true, false); }, &flags, &overflow) != HALA_OK)
     return HALA_ERR;
   if (overflow) {
     std::vector<DeformPose> back;
@@ -180,7 +134,7 @@ int deform_pose(hala_rt_renderer* r, const std::vector<DeformPose>& items, std::
       if (!it.d->posed) { if (restore_rest(r, *it.d) != HALA_OK) return HALA_ERR; }
       else back.push_back(DeformPose{it.d, &it.d->applied});
     }
-    if (launch_all(r, back, ds.d_flags.ptr, false, true) != HALA_OK) return HALA_ERR;
+    if (launch_poses(r, back, ds.d_flags.ptr, false, true) != HALA_OK) return HALA_ERR;
     RT_HIP(hipStreamSynchronize(r->stream));
     for (size_t k = 0; k < items.size() && overflowed; ++k)
       if (flags[k]) overflowed->push_back(k);
@@ -257,7 +211,6 @@ int hala_rt_set_deformer(hala_rt_renderer* r, const hala_deformer_desc* desc) {
   if (desc->joint_count) {
     RT_HIP(d->d_joints.upload(reinterpret_cast<const uint2*>(desc->joints), nv, r->stream));
     RT_HIP(d->d_weights.upload(reinterpret_cast<const float4*>(desc->weights), nv, r->stream));
-    RT_HIP(d->d_palette.resize((size_t)desc->joint_count * 12u));
   }
   d->applied.weights.assign(desc->target_count, 0.0f);
   d->applied.palette.assign((size_t)desc->joint_count * 12u, 0.0f);

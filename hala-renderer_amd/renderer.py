@@ -713,8 +713,8 @@ class HalaRenderer:
         return out
 
     def rig_status(self) -> A.RigStatus:
-        """bindings of the rig, deformers registered, and the cumulative pose launches, those of k_deform_batch among them, and the deformers
-        ("segments") they posed"""
+        """bindings of the rig, deformers registered, and the cumulative pose launches, those among them that posed two or more deformers, and the
+        deformers ("segments") they posed"""
         s = A.RigStatus()
         self._check(self._lib.hala_rt_get_rig_status(self._h, C.byref(s)))
         return s

@@ -873,7 +873,7 @@ int hala_rt_update_deformer(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
                             uint32_t weight_count, const float* joint_matrices_3x4, uint32_t joint_count);
 /* Removes the deformer of a primitive: the next hala_rt_refit restores the rest pose and frees the tables.  Refused when the primitive
  * has none.  While a primitive has a deformer, hala_rt_update_vertices on it is refused ("clear it first").
- * The refit contract: hala_rt_refit poses every deformer whose parameters changed (one launch of k_deform for one, one launch of k_deform_batch for two or more, on the renderer's stream)
+ * The refit contract: hala_rt_refit poses every deformer whose parameters changed (one launch of k_deform for all of them, one or many, on the renderer's stream)
  * and then refits as it does after hala_rt_update_vertices; every instance of a posed primitive starts without temporal history
  * (hala_rt_set_temporal) unless hala_rt_set_temporal_vertex_motion lets the history follow its triangles.  Finite parameters can still overflow: when a posed position is not finite, hala_rt_refit fails with
  * "Vertex position is not finite.", the vertices and the tree stay exactly as they were, the offending parameters fall back to the last
@@ -986,8 +986,8 @@ typedef struct hala_rig_status {
   uint32_t bindings;       /* of the rig hala_rt_set_rig registered; 0: none */
   uint32_t deformers;      /* deformers registered on the renderer, by hala_rt_set_rig or hala_rt_set_deformer */
   uint64_t pose_launches;  /* kernel launches that posed deformers, since hala_rt_create */
-  uint64_t segments_posed; /* deformers those launches posed: a launch of the batch kernel poses several */
-  uint64_t batch_launches; /* the launches of k_deform_batch among pose_launches; the others are k_deform's, one deformer each */
+  uint64_t segments_posed; /* deformers those launches posed: one launch poses all the dirty ones of a refit */
+  uint64_t batch_launches; /* those among pose_launches that posed two or more deformers */
 } hala_rig_status; /* 32 B */
 /* Registers one deformer (hala_rt_set_deformer) per binding of `rig` on the committed scene and keeps a copy of the rig's tables; the
  * caller's arrays may go.  NULL clears the rig: the deformers it registered (one that the host cleared or replaced since stays the

@@ -66,7 +66,7 @@ def kernel_trace(poses):
             with open(path, newline="") as f:
                 for row in csv.DictReader(f):
                     for k in KERNELS:
-                        if re.search(k + "(?!_batch)", row["Kernel_Name"]):
+                        if re.search(r"\b" + k + r"\(", row["Kernel_Name"]):
                             out[k].append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-6)
     if not all(out.values()):
         raise RuntimeError("the kernel trace lacks a normals kernel")

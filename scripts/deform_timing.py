@@ -15,6 +15,7 @@ import glob
 import json
 import os
 import platform
+import re
 import statistics
 import subprocess
 import sys
@@ -92,7 +93,7 @@ def kernel_trace(poses):
         for path in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
             with open(path, newline="") as f:
                 for row in csv.DictReader(f):
-                    if "k_deform" in row["Kernel_Name"]:
+                    if re.search(r"\bk_deform\(", row["Kernel_Name"]):  # (the name itself: not k_deform_faces, k_deform_vertex_normals)
                         out.append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-6)
     if not out:
         raise RuntimeError("the kernel trace holds no k_deform launch")

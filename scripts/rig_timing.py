@@ -2,17 +2,20 @@
 
 configs[1] plus one mesh of P strip primitives of 2 000 vertices each, every one with a deformer of 2 morph targets (position and normal
 deltas) and 32 joints.  Per pose, over `--poses` poses, host wall time until the renderer's stream is idle of update_deformer on all P +
-refit, for P = 1, 2, 4, 8, 32, 128.  This build poses two or more dirty deformers with one launch of k_deform_batch behind one copy; the
-parent commit's library (`--parent-root`: its tree, built there) makes one copy and one launch of k_deform per primitive.  The two
-alternate as separate processes, and the order alternates from round to round.  Also: k_deform_batch alone from one
-`rocprofv3 --kernel-trace` child run at P = 32, and one shutter run at P = 32 with time_stride = 1 (every frame poses all 32 and
-refits) against the parent."""
+refit, for P = 1, 2, 4, 8, 32, 128.  A refit poses its dirty deformers, one or many, with one launch of k_deform behind one copy.  With
+`--parent-root` (the parent commit's tree, built there) the two libraries alternate as separate processes, and the order alternates
+from round to round.  Also: k_deform alone from one `rocprofv3 --kernel-trace` child run at P = 32, and one shutter run at P = 32 with
+time_stride = 1 (every frame poses all 32 and refits) against the parent.
+
+`--morph-only`: the deformers have no skin (joint_count = 0), P = 1 and 2 only, no shutter run and no trace; the rows are added to the
+output file under "morph_only_by_count"."""
 import argparse
 import csv
 import glob
 import json
 import os
 import platform
+import re
 import statistics
 import subprocess
 import sys
@@ -28,7 +31,7 @@ def summary(xs):
     return {"median": statistics.median(xs), "mean": statistics.fmean(xs), "min": min(xs), "max": max(xs), "stdev": statistics.pstdev(xs), "n": len(xs)}
 
 
-def character(root, count):
+def character(root, count, joints=JOINTS):
     """-> (renderer, mesh index, rigs, poses(k)) of the tree at `root`"""
     sys.path.insert(0, root)
     sys.path.insert(0, os.path.join(root, "tests"))
@@ -48,15 +51,15 @@ def character(root, count):
         r.set_envmap(cfg["env"], 0.0)
     r.set_scene(scene)
     r.commit()
-    rigs = [D.random_rig(VERTICES, targets=TARGETS, joint_count=JOINTS, normals=True, seed=k) for k in range(count)]
+    rigs = [D.random_rig(VERTICES, targets=TARGETS, joint_count=joints, normals=True, seed=k) for k in range(count)]
     for k, rig in enumerate(rigs):
         r.set_deformer(mesh, k, **rig)
     return r, mesh, rigs, lambda k, seed: D.random_pose(rigs[k], seed=seed * 1000 + k, zero_some=False, centre=(500.0, 0.5, 0.0)), np
 
 
-def measure(root, count, poses):
+def measure(root, count, poses, joints=JOINTS):
     """update_deformer on all + refit, `poses` times after two warm-up poses -> ms each"""
-    r, mesh, rigs, pose, _ = character(root, count)
+    r, mesh, rigs, pose, _ = character(root, count, joints)
     out = []
     for n in range(poses + 2):
         ps = [pose(k, n) for k in range(count)]
@@ -104,7 +107,7 @@ def run_child(root, *args):
 
 
 def kernel_trace(count, poses):
-    """-> the durations (ms) of every k_deform_batch launch of a child run of this build under rocprofv3"""
+    """-> the durations (ms) of every k_deform launch of a child run of this build under rocprofv3"""
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "t", "--", sys.executable, os.path.abspath(__file__), "--root", HERE, "--measure", str(count),
                "--poses", str(poses)]
@@ -115,10 +118,10 @@ def kernel_trace(count, poses):
         for path in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
             with open(path, newline="") as f:
                 for row in csv.DictReader(f):
-                    if "k_deform_batch" in row["Kernel_Name"]:
+                    if re.search(r"\bk_deform\(", row["Kernel_Name"]):  # (the name itself: not k_deform_faces, k_deform_vertex_normals)
                         out.append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-6)
     if not out:
-        raise RuntimeError("the kernel trace holds no k_deform_batch launch")
+        raise RuntimeError("the kernel trace holds no k_deform launch")
     return out
 
 
@@ -128,13 +131,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--parent-root", default=None)
     ap.add_argument("--no-trace", action="store_true")
+    ap.add_argument("--morph-only", action="store_true", help="deformers without a skin, P = 1 and 2, added to the output file")
     ap.add_argument("--root", default=None, help="child mode: the tree whose package and library to load")
     ap.add_argument("--measure", type=int, default=0, help="child mode: time this many primitives")
     ap.add_argument("--shutter", type=int, default=0, help="child mode: the shutter run with this many primitives")
     ap.add_argument("--out", default=os.path.join(HERE, "profiles", "rig_timing.json"))
     args = ap.parse_args()
     if args.root:
-        print(json.dumps(measure(args.root, args.measure, args.poses) if args.measure else measure_shutter(args.root, args.shutter, args.poses)))
+        joints = 0 if args.morph_only else JOINTS
+        print(json.dumps(measure(args.root, args.measure, args.poses, joints) if args.measure else measure_shutter(args.root, args.shutter, args.poses)))
         return
     sys.path.insert(0, HERE)
     import torch
@@ -148,14 +153,22 @@ def main():
             json.dump(res, f, indent=1)
 
     trees = [("this", HERE)] + ([("parent", args.parent_root)] if args.parent_root else [])
-    for count in COUNTS:
+    if args.morph_only:
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                res = json.load(f)
+        res["morph_only_by_count"] = {}
+    for count in (1, 2) if args.morph_only else COUNTS:
         runs = {name: [] for name, _ in trees}
         for k in range(args.rounds):
             for name, root in trees[::1 if k % 2 == 0 else -1]:
-                got = run_child(root, "--measure", count, "--poses", args.poses)
+                got = run_child(root, "--measure", count, "--poses", args.poses, *(["--morph-only"] if args.morph_only else []))
                 runs[name].append({"round": k, **summary(got["ms"]), "status": got["status"]})
-        res["by_count"][str(count)] = runs
+        res["morph_only_by_count" if args.morph_only else "by_count"][str(count)] = runs
         save()
+    if args.morph_only:
+        print(json.dumps(res["morph_only_by_count"], indent=1))
+        return
     if args.parent_root:
         sh = {name: [] for name, _ in trees}
         for k in range(args.rounds):
@@ -167,7 +180,7 @@ def main():
     if not args.no_trace:
         ms = kernel_trace(32, args.poses)
         bytes_per_pose = 32 * VERTICES * (44 + 44 + TARGETS * 2 * 12 + 24)
-        res["k_deform_batch_at_32_ms"] = {**summary(ms), "model_bytes": bytes_per_pose, "gb_per_s_at_median": bytes_per_pose / (statistics.median(ms) * 1e-3) / 1e9}
+        res["k_deform_at_32_ms"] = {**summary(ms), "model_bytes": bytes_per_pose, "gb_per_s_at_median": bytes_per_pose / (statistics.median(ms) * 1e-3) / 1e9}
         save()
     print(json.dumps(res, indent=1))
 

@@ -6,7 +6,7 @@ meshes and on its exact cases; csrc/deform_adjacency.cpp built alone with the ho
 hala_deformer_normals_info and the header's contract; the oracle's render with recomputed normals differs from the one without.
 GPU tier, every comparison by bytes: the kernels equal the twin (read_vertices) across wave and workgroup edges, a lane that loops past
 64 entries, degenerate lists, a UV seam and hard edges; the render equals the oracle's of the scene holding the twin's vertices on both
-tree forms; the batch form with a mode-0 deformer in its middle; a rig; a shutter; an overflow; mode changes, lifetime and refusals.
+tree forms; several segments with a mode-0 deformer in their middle; a rig; a shutter; an overflow; mode changes, lifetime and refusals.
 (The refusal after a device error cannot be provoked without one: the header test names it, no GPU test reaches it.)"""
 import ctypes as C
 import os
@@ -363,7 +363,7 @@ def test_render_equals_the_oracle_of_the_twins_vertices(halart, oracle, two_leve
 @gpu
 def test_batch_equals_single(halart):
     """three deformers in modes (1, 0, 1) posed by one refit: one pose launch, two normals launches, every primitive the twin's bytes
-    (tests/deform_ref.py's alone for the one in mode 0); then the first alone, by the single-deformer launches: the same bytes"""
+    (tests/deform_ref.py's alone for the one in mode 0); then the first alone, a launch of one segment: the same bytes"""
     prims = [MESHES["strip257"](), MESHES["cylinder"](), MESHES["fan100"]()]
     kinds = ["both", "skin", "morph"]
     modes = [ON, OFF, ON]
@@ -490,7 +490,7 @@ def test_overflow(halart, oracle):
         assert held == {m: cornell_vertices(m, poses[m], ON).tobytes() for m in (TALL, SHORT)}
         tree = [x.tobytes() for x in r.download_bvh()]
         huge = D.identity_palette(3); huge[:, 0, 0] = 3.0e38; huge[:, 0, 1] = 3.0e38
-        for both in (True, False):  # the batch form with a valid second pose beside the offender, then the offender alone
+        for both in (True, False):  # two segments, a valid second pose beside the offender, then the offender alone
             r.update_deformer(TALL, 0, joint_matrices=huge)
             if both:
                 r.update_deformer(SHORT, 0, morph_weights=TD.cornell_pose(2)[SHORT]["morph_weights"])

@@ -1,5 +1,5 @@
-"""Rigs and clips (docs/RENDER_SPEC.md 19; include/halart.h "The rig of a glTF file", "Rigs and clips") and the batched deformer kernel
-(k_deform_batch, csrc/deform.hip).
+"""Rigs and clips (docs/RENDER_SPEC.md 19; include/halart.h "The rig of a glTF file", "Rigs and clips") and the deformer kernel over many segments
+(k_deform, csrc/deform.hip).
 
 CPU tier: the loader's rig equals what tests/rig_ref.py wrote, array for array, and leaves the scene description alone;
 hala_rig_sample_clip against the float64 twin; every malformed file is refused with its message; the loader and the evaluation under
@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import deform_normals_ref as N
 import deform_ref as D
 import rig_ref as R
 import scene_edits as E
@@ -298,7 +299,7 @@ def assert_posed(r, scene, poses, what):
 @gpu
 def test_batched_kernel_equals_the_twin(halart):
     """eight deformers of mixed kinds registered, all posed, one refit: one launch, eight segments, the twin's bytes — three poses in a
-    row; then exactly two dirty deformers (the smallest batch: a launch of k_deform_batch) and exactly one (a launch that is not)"""
+    row; then exactly two dirty deformers (the smallest batch: a launch counted in batch_launches) and exactly one (a launch that is not)"""
     scene = batch_scene()
     r = SE.make(halart, SE.base_of("cornell"), scene=scene)
     try:
@@ -331,6 +332,62 @@ def test_batched_kernel_equals_the_twin(halart):
             assert tuple(a - b for a, b in zip(after, before)) == (1, len(dirty), 1 if len(dirty) > 1 else 0), (dirty, before, after)
             before = after
             assert_posed(r, scene, poses, f"dirty {dirty}")
+    finally:
+        r.close()
+
+
+# (vertices, targets, joints, normal deltas, normals mode): the staged sections of one launch as unequal as they can be — the largest
+# active list and palette beside a deformer that has neither, the middle one no segment of the normals passes, the last with two of
+# its three weights exactly 0 and more than one workgroup
+UNEQUAL = [(65, 64, 256, True, 1), (1, 0, 1, False, 0), (257, 3, 0, False, 1)]
+
+
+@gpu
+def test_unequal_staged_sections_equal_the_twins(halart):
+    """three deformers whose tables, active targets and palettes differ as far as the limits allow, posed by one refit: every primitive
+    the twins' bytes (tests/deform_ref.py, then tests/deform_normals_ref.py where the mode is 1), one pose launch of three segments, two
+    normals launches; then the middle one alone: one launch of one segment, no normals launch, the same bytes everywhere"""
+    prims = [D.strip(c[0], seed=c[0], origin=(0.0, 3.0 * k, 0.0)) for k, c in enumerate(UNEQUAL)]
+    s = scenes.cornell_box(aspect=E.W / E.H_)
+    s.meshes = list(s.meshes) + [HalaMesh([HalaPrimitive(idx, v, material_index=k % 5) for k, (idx, v) in enumerate(prims)])]
+    s.nodes = list(s.nodes) + [HalaNode(name="strips", mesh_index=BATCH_MESH, local_transform=E._translate((20.0, 200.0, 150.0)))]
+    rigs = [D.random_rig(c[0], targets=c[1], joint_count=c[2], normals=c[3], seed=40 + k) for k, c in enumerate(UNEQUAL)]
+    poses = [D.random_pose(rig, seed=50 + k, zero_some=False, centre=(10.0, 0.5, 0.0)) for k, rig in enumerate(rigs)]
+    poses[2]["morph_weights"][[0, 2]] = 0.0
+    assert np.count_nonzero(poses[0]["morph_weights"]) == 64 and np.count_nonzero(poses[2]["morph_weights"]) == 1
+    want = []
+    for (idx, rest), rig, p, c in zip(prims, rigs, poses, UNEQUAL):
+        v = D.pose_vertices(rest, rig, p)
+        assert np.isfinite(v["position"]).all() and v.tobytes() != rest.tobytes()
+        want.append(N.recompute(v, idx, N.classes(rest, idx)) if c[4] else v)
+    assert want[2]["normal"].tobytes() != D.pose_vertices(prims[2][1], rigs[2], poses[2])["normal"].tobytes(), "the case exercises the passes"
+    r = SE.make(halart, SE.base_of("cornell"), scene=s)
+
+    def assert_all(what):
+        for k in range(3):
+            got = r.read_vertices(BATCH_MESH, k)
+            if got.tobytes() != want[k].tobytes():
+                bad = np.nonzero(got.view(np.uint32).reshape(-1, 11) != want[k].view(np.uint32).reshape(-1, 11))
+                raise AssertionError(f"{what}: primitive {k} {UNEQUAL[k]}: {len(bad[0])} words differ, first (vertex, word) {bad[0][:4]}, {bad[1][:4]}")
+        for m in range(3):  # the primitives without deformers
+            assert r.read_vertices(m, 0).tobytes() == s.meshes[m].primitives[0].vertices.tobytes(), (what, m)
+
+    try:
+        for k, rig in enumerate(rigs):
+            r.set_deformer(BATCH_MESH, k, **rig)
+            r.set_deformer_normals(BATCH_MESH, k, UNEQUAL[k][4])
+        r.refit()  # (the mode switches made 0 and 2 dirty: posed at the identity pose)
+        before, normals_before = counts(r), r.get_deformer_normals(BATCH_MESH, 0).launches
+        for k, p in enumerate(poses):
+            r.update_deformer(BATCH_MESH, k, **p)
+        r.refit()
+        after, normals_after = counts(r), r.get_deformer_normals(BATCH_MESH, 0).launches
+        assert tuple(a - b for a, b in zip(after, before)) == (1, 3, 1) and normals_after - normals_before == 2, (before, after, normals_before, normals_after)
+        assert_all("three at once")
+        r.update_deformer(BATCH_MESH, 1, **poses[1])
+        r.refit()
+        assert tuple(a - b for a, b in zip(counts(r), after)) == (1, 1, 0) and r.get_deformer_normals(BATCH_MESH, 0).launches == normals_after
+        assert_all("the second alone")
     finally:
         r.close()
 
