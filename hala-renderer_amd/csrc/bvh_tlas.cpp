@@ -11,12 +11,13 @@
 #include <cstring>
 #include <vector>
 
+#include "bvh_node_pack.h"
 #include "kernels.h"
 
 namespace rt {
 namespace {
 
-struct Box { float mn[3], mx[3]; };
+using Box = Box6;
 inline Box unite(const Box& a, const Box& b) {
   Box r;
   for (int k = 0; k < 3; ++k) { r.mn[k] = std::min(a.mn[k], b.mn[k]); r.mx[k] = std::max(a.mx[k], b.mx[k]); }
@@ -65,15 +66,6 @@ int build_binary(std::vector<BinNode>& nodes, const std::vector<TlasItem>& items
   const int r = build_binary(nodes, items, ids, best_split, hi);
   nodes[index].left = l; nodes[index].right = r;
   return index;
-}
-
-// quantum exponent of one axis: the smallest power of two s = 2^e with extent / s <= 255 (never below 2^-100) — as bvh_build.hip
-int quantum_exponent(float lo, float hi) {
-  const double q = ((double)hi - (double)lo) / 255.0;
-  if (!(q > 0.0)) return -100;
-  int e = 0;
-  (void)std::frexp(q, &e);  // q = m * 2^e, m in [0.5, 1)
-  return e < -100 ? -100 : (e > 100 ? 100 : e);
 }
 
 }  // namespace
@@ -127,38 +119,16 @@ uint32_t tlas_build(const std::vector<TlasItem>& items, std::vector<BvhNode4>& o
   for (size_t q = 0; q < roots.size(); ++q) node_of[(size_t)roots[q]] = (int)q;
   out.resize(slots.size());
   for (size_t q = 0; q < slots.size(); ++q) {
-    BvhNode4 nd{};
-    Box all{};
+    Child4 ch[4];
     int n = 0;
     for (int k = 0; k < 4; ++k) {
       if (slots[q][k] < 0) continue;
-      all = n == 0 ? bin[(size_t)slots[q][k]].box : unite(all, bin[(size_t)slots[q][k]].box);
+      const BinNode& c = bin[(size_t)slots[q][k]];
+      ch[n].box = c.box;
+      ch[n].ref = c.item >= 0 ? items[(size_t)c.item].ref : (uint32_t)node_of[(size_t)slots[q][k]];
       ++n;
     }
-    int e[3];
-    for (int a = 0; a < 3; ++a) {
-      nd.pmin[a] = all.mn[a];
-      e[a] = quantum_exponent(all.mn[a], all.mx[a]);
-      nd.exps |= (uint32_t)(e[a] + 127) << (8 * a);
-    }
-    int c = 0;
-    for (int k = 0; k < 4; ++k) nd.ref[k] = kAbsent;
-    for (int k = 0; k < 4; ++k) {
-      if (slots[q][k] < 0) continue;
-      const BinNode& ch = bin[(size_t)slots[q][k]];
-      nd.ref[c] = ch.item >= 0 ? items[(size_t)ch.item].ref : (uint32_t)node_of[(size_t)slots[q][k]];
-      for (int a = 0; a < 3; ++a) {
-        const double s = std::ldexp(1.0, e[a]), base = (double)all.mn[a];
-        double lo = std::floor(((double)ch.box.mn[a] - base) / s), hi = std::ceil(((double)ch.box.mx[a] - base) / s);
-        if (base + lo * s > (double)ch.box.mn[a]) lo -= 1.0;  // rounding of the subtraction must not shrink the box
-        if (base + hi * s < (double)ch.box.mx[a]) hi += 1.0;
-        lo = std::min(std::max(lo, 0.0), 255.0); hi = std::min(std::max(hi, 0.0), 255.0);
-        nd.qlo[a] |= (uint32_t)lo << (8 * c);
-        nd.qhi[a] |= (uint32_t)hi << (8 * c);
-      }
-      ++c;
-    }
-    out[q] = nd;
+    out[q] = pack_node4(ch, n);  // the same bytes as the GPU builders give these boxes (bvh_node_pack.h)
   }
   uint32_t lv = 0;
   for (uint32_t d : depth) lv = std::max(lv, d);

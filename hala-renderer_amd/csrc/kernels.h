@@ -57,7 +57,8 @@ void launch_mip_downsample8(const uint32_t* src, uint32_t sw, uint32_t sh, uint3
 // texel bundles: one tiled 8-bit level -> lane `lane` of the bundle level of the same size (dst: its first 16-B texel)
 void launch_bundle_interleave(const uint32_t* src, uint32_t w, uint32_t h, uint4* dst, uint32_t lane, hipStream_t s);
 
-// bvh_build.hip — K1/K3/K4: flatten instances to world space, LBVH build, refit
+// bvh_build.hip (with bvh_sah.hip, bvh_ploc.hip) — K1/K3/K4: flatten instances to world space, build the hierarchy (SAH | PLOC | LBVH),
+// collapse it to 4-wide nodes, pack them level by level; refit re-flattens and re-packs the kept topology
 // How commit() builds the hierarchy (hala_rt_set_build_options; 0 = the default everywhere).  The driver fields only change HOW the
 // host walks the rounds of a build, never the tree (tests/test_gpu_parity.py::test_ploc_drivers_build_the_same_tree).
 struct BuildOptions {

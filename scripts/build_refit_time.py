@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Times commit() (upload + BVH build) and refit() (node transforms -> instance records -> leaf boxes -> fit -> pack) on the
-1M-triangle atrium; run by hand on the GPU box.  The numbers quoted in DESIGN.md section 5 come from here."""
+"""Times commit() (upload + BVH build) and refit() (node transforms -> instance records -> leaf boxes -> level pack) on the
+1M-triangle atrium (or: triangle count, --builder, --instancing); run by hand on the GPU box.  The numbers quoted in DESIGN.md section 5 come from here."""
+import argparse
 import os
 import sys
 import time
@@ -10,9 +11,15 @@ import numpy as np
 import hala_renderer_amd as H
 from hala_renderer_amd import scenes
 
-tris = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
-s = scenes.sponza_class(target_triangles=tris)
+ap = argparse.ArgumentParser()
+ap.add_argument("tris", nargs="?", type=int, default=1_000_000)
+ap.add_argument("--builder", choices=("sah", "ploc", "lbvh"), default=None, help="default: automatic")
+ap.add_argument("--instancing", action="store_true", help="two-level tree: one small tree per instanced primitive")
+a = ap.parse_args()
+s = scenes.sponza_class(target_triangles=a.tris)
 r = H.HalaRenderer("time", 1920, 1080, 5, 3, True, True, False, 0)
+if a.builder or a.instancing:
+    r.set_build_options(builder=a.builder, instancing=True if a.instancing else None)
 r.set_scene(s)
 t0 = time.perf_counter(); r.commit(); t1 = time.perf_counter()
 print("triangles", r.bvh_info().triangle_count, "first commit ms %.2f" % ((t1 - t0) * 1e3), flush=True)

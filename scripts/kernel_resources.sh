@@ -39,7 +39,7 @@ for blk in txt.split('- .agpr_count:')[1:]:
 import shutil
 for r in rows:
     dem = subprocess.run(['/usr/bin/c++filt', r[0]], capture_output=True, text=True).stdout.strip()
-    dem = re.sub(r'\(.*', '', dem)
+    dem = re.sub(r'\(.*', '', dem.replace('(anonymous namespace)::', ''))
     if not pat.search(dem): continue
     print(f'{dem:70s} vgpr {r[2]:>4s} sgpr {r[3]:>4s} scratch {r[4]:>5s} B  lds {r[5]:>6s} B  vspill {r[6]:>3s} sspill {r[7]:>3s} wg {r[8]}')
 "

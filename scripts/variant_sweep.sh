@@ -18,7 +18,7 @@ c=b.get('secondary',{}).get('configs1')
 if c: print('   cornell', c['value'], c['ms_per_frame'], 'batch', c['batch_kernel']['avg_launch_ms'], 'shadow', c['shadow_kernel']['avg_launch_ms'], 'shade', c['shade_kernel']['avg_launch_ms'], '| 4K on 1 GPU', b['secondary']['configs4_on_1_gpu']['ms_per_frame'])"; }
 build() { touch hala-renderer_amd/csrc/integrator.hip hala-renderer_amd/csrc/renderer.hip hala-renderer_amd/csrc/bvh_build.hip; make -C hala-renderer_amd/csrc -j16 EXTRA="$1" > gpurun_out/variant_make.log 2>&1 || { echo "build failed: $1"; tail -n 5 gpurun_out/variant_make.log; }; }
 # every object depends on every header of csrc/: touching one on top rebuilds every host unit, too, with the new defines
-rebuild() { touch hala-renderer_amd/csrc/hala_types.h; build "$1"; }
+rebuild() { touch hala-renderer_amd/csrc/hala_types.h hala-renderer_amd/csrc/bvh_sah.hip hala-renderer_amd/csrc/bvh_ploc.hip; build "$1"; }
 mkdir -p gpurun_out
 rebuild ""
 echo "default"; run

@@ -602,7 +602,7 @@ def test_builders_differ_in_trees_not_in_results(halart, oracle):
 
 def test_sah_build_of_coincident_triangles(halart, oracle):
     """6000 copies of ONE triangle pair among ordinary geometry: every split of the pile costs the same, the sweep peels it a few
-    triangles at a time until the round limit, then halves (bvh_build.hip: kSweepRounds) — the build must end, the tree must be valid
+    triangles at a time until the round limit, then halves (bvh_sah.hip: kSweepRounds) — the build must end, the tree must be valid
     and a ray into the pile must report the copy with the lowest id (RENDER_SPEC 4.2 tie rule), as brute force does"""
     s = scenes.cornell_box()
     quad = ((200.0, 100.0, 300.0), (350.0, 100.0, 300.0), (350.0, 250.0, 300.0), (200.0, 250.0, 300.0))  # inside the box, facing the camera
@@ -629,8 +629,9 @@ def test_sah_build_of_coincident_triangles(halart, oracle):
 
 
 def test_refit_without_change_reproduces_the_build(halart, oracle):
-    """refit re-derives the 4-wide nodes level by level (k_refit_level) instead of fit + pack: with nothing moved the nodes, the
-    triangle order and every box must come out byte for byte as the build (PLOC boxes for the large scene, k_fit for the small)"""
+    """a build and a refit write the 4-wide nodes through the same level-by-level pass (k_refit_level) over the kept topology: with
+    nothing moved the nodes, the triangle order, the counts and the bounds must come out byte for byte as the build left them (boxes
+    fitted by the SAH rounds for the large scene, by k_fit for the small)"""
     for s in (scenes.sponza_class(target_triangles=20_000), scenes.cornell_box()):
         r = make_renderer(halart, s, 16, 16)
         n0, t0 = r.download_bvh()
@@ -642,6 +643,77 @@ def test_refit_without_change_reproduces_the_build(halart, oracle):
         assert (info0.node_count, info0.max_depth) == (info1.node_count, info1.max_depth)
         assert list(info0.scene_min) == list(info1.scene_min) and list(info0.scene_max) == list(info1.scene_max)
         r.close()
+
+
+SMALL_SIZES = (1, 2, 4, 5, 17, 64, 65, 257, 512, 513, 1030)
+SMALL_TREES = [(n, b, {}) for n in SMALL_SIZES for b in ("lbvh", "ploc", "sah")] + [(513, "ploc", dict(ploc_look_every=1)), (513, "ploc", dict(ploc_tail=2))]
+_SMALL = {}
+
+
+def small_scene(n):
+    """one primitive of n random non-degenerate triangles inside the unit cube, seen by a camera in front of it"""
+    rs = np.random.RandomState(7000 + n)
+    pos = (rs.uniform(0.15, 0.85, (n, 1, 3)) + rs.uniform(-0.15, 0.15, (n, 3, 3))).astype(f32)
+    nrm = np.cross(pos[:, 1] - pos[:, 0], pos[:, 2] - pos[:, 0]).astype(np.float64)
+    assert (np.linalg.norm(nrm, axis=1) > 1e-5).all()
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    s = H.HalaScene()
+    s.materials = [H.HalaMaterial(type=0, base_color=(0.7, 0.7, 0.7))]
+    prim = H.HalaPrimitive(indices=np.arange(3 * n, dtype=np.uint32), vertices=scenes._vertices(pos.reshape(-1, 3), np.repeat(nrm, 3, axis=0)))
+    prim.material_index = 0
+    s.meshes = [H.HalaMesh([prim])]
+    s.nodes = [H.HalaNode(name="soup", mesh_index=0),
+               H.HalaNode(name="camera", camera_index=0, local_transform=scenes.look_at_node_transform((0.4, 0.6, 3.0), (0.5, 0.5, 0.5)))]
+    s.cameras = [H.HalaPerspectiveCamera(aspect=1.0, yfov=0.7, znear=0.1)]
+    return s
+
+
+def small_case(oracle, n):
+    """scene, oracle scene, rays and the brute-force hits of both ray kinds: computed once per size, shared by the builders"""
+    if n not in _SMALL:
+        s = small_scene(n)
+        osc = oracle.OracleScene(s)
+        rays = np.concatenate([random_rays(2000, np.array([-0.5, -0.5, -0.5], dtype=f32), np.array([1.5, 1.5, 1.5], dtype=f32), 40 + n), osc.camera_rays(32, 32, 0)])
+        _SMALL[n] = (s, osc, rays, [osc.trace(rays, mode, brute=True) for mode in (0, 1)])
+    return _SMALL[n]
+
+
+@pytest.mark.parametrize("n,builder,drive", SMALL_TREES, ids=lambda v: str(v) if not isinstance(v, dict) else "-".join(f"{k}{x}" for k, x in v.items()) or "default")
+def test_small_trees(halart, oracle, n, builder, drive):
+    """the sizes at which the builder's paths change: one and two triangles, leaf_max (a single node), the first collapsed tree, one more
+    than PLOC's search radius, the edges of a 64-lane wave and a 256-thread block, kPlocTail (the tail kernel alone), one more (global rounds,
+    then the tail, also driven round by round and without the tail) and several blocks — with every builder.  Per tree: the structural
+    check and its depth; closest-hit rays equal brute force by bytes, any-hit rays in t; step counts equal the oracle's on the downloaded
+    tree; a refit of unchanged vertices and a second renderer reproduce nodes, triangle order, counts and bounds byte for byte"""
+    s, osc, rays, brute = small_case(oracle, n)
+    build = dict(builder=builder, instancing=False, **drive)
+    r = make_renderer(halart, s, 16, 16, build=build)
+    info = r.bvh_info()
+    assert info.triangle_count == n and info.instance_ref_count == 0
+    nodes, tris = r.download_bvh()
+    rc, depth = oracle.validate_bvh(nodes, tris, osc.triangles())
+    assert rc == 0 and depth == info.max_depth
+    for mode in (0, 1):
+        hits, cnt = r.trace_rays_host(rays, mode, count_steps=True)
+        if mode == 0:
+            assert hits.tobytes() == brute[0].tobytes()
+        else:
+            assert np.array_equal(hits["t"], brute[1]["t"])
+        assert cnt == oracle.trace_on_bvh(nodes, tris, rays, mode)[1], mode
+
+    def state(x):
+        i = x.bvh_info()
+        nd, tr = x.download_bvh()
+        return nd.tobytes(), tr.tobytes(), i.node_count, i.max_depth, list(i.scene_min), list(i.scene_max)
+
+    built = state(r)
+    r.update_vertices(0, 0, s.meshes[0].primitives[0].vertices)  # the same vertices: nothing moves, but the refit pass runs
+    r.refit()
+    assert state(r) == built
+    r.close()
+    r2 = make_renderer(halart, s, 16, 16, build=build)
+    assert state(r2) == built
+    r2.close()
 
 
 # ---- K5-K7: the integrator -----------------------------------------------------------------------------------------------
