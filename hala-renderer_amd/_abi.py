@@ -164,7 +164,8 @@ class RtStatistics(C.Structure):
 
 class BuildOptions(C.Structure):  # hala_rt_build_options
     _fields_ = [("builder", C.c_uint32), ("ploc_tail", C.c_uint32), ("ploc_look_every", C.c_uint32),
-                ("collapse_look_every", C.c_uint32), ("instancing", C.c_uint32), ("texture_bundles", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+                ("collapse_look_every", C.c_uint32), ("instancing", C.c_uint32), ("texture_bundles", C.c_uint32), ("instance_levels", C.c_uint32),
+                ("reserved", C.c_uint32 * 1)]
 
 
 class TextureBundleInfo(C.Structure):  # hala_texture_bundle_info, 24 B

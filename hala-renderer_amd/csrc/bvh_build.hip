@@ -36,28 +36,6 @@ RT_DI f3 transform_point(const float* m, f3 p) {
              __fmaf_rn(m[10], p.z, __fmaf_rn(m[6], p.y, m[2] * p.x)) + m[14]);
 }
 
-// Folds ord[6] (min xyz, max xyz as ordered integers) over a 256-thread block: wave shuffle reduction, then the four waves through LDS;
-// threads 0..5 leave component threadIdx.x in out[at + threadIdx.x].
-RT_DI void block_bounds_fold(uint32_t (&ord)[6], uint32_t (&wave_ord)[4][6], uint32_t tid, uint32_t* __restrict__ out, uint32_t at) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      ord[k] = min(ord[k], (uint32_t)__shfl_xor((int)ord[k], m, 64));
-      ord[3 + k] = max(ord[3 + k], (uint32_t)__shfl_xor((int)ord[3 + k], m, 64));
-    }
-  }
-  if ((tid & 63u) == 0u) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) wave_ord[tid >> 6][k] = ord[k];
-  }
-  __syncthreads();
-  if (tid < 6u) {
-    uint32_t v = wave_ord[0][tid];
-    for (int w = 1; w < 4; ++w) v = tid < 3u ? min(v, wave_ord[w][tid]) : max(v, wave_ord[w][tid]);
-    out[at + tid] = v;
-  }
-}
 // one thread per global triangle id.  The three records a triangle gets (48-B Tri, 128-B ShadeTri, 24-B Box6) are staged in LDS and
 // leave the block as contiguous 16-B (8-B for the boxes) stores.  Scene bounds: NO global atomics here — a device-scope atomic
 // costs 11.4 ns per 128-B line however many waves issue it (scripts/microbench/atomic_rate.hip), and six of them per wave on one
@@ -280,6 +258,12 @@ __global__ void __launch_bounds__(256) k_keep_flags(const uint32_t* __restrict__
 
 // ---- 4-wide nodes (RENDER_SPEC §4.1b) -----------------------------------------------------------------------------------------------
 RT_DI uint32_t leaf_ref(uint32_t first, uint32_t count) { return kLeafRef | ((count - 1u) << 28) | first; }
+// the one place a leaf's child reference comes from: its sorted positions, or (ITEMS: leaves of one item) the reference of the item there
+template <bool ITEMS>
+RT_DI uint32_t leaf_ref_of(uint32_t first, uint32_t count, const uint32_t* __restrict__ sorted_ids, const uint32_t* __restrict__ item_ref) {
+  if (ITEMS) return item_ref[sorted_ids[first]];
+  return leaf_ref(first, count);
+}
 
 // Top-down collapse of the binary tree into 4-wide nodes, one BFS level per launch, so that node indices come out in
 // breadth-first order (the first `lds_nodes` nodes — the slice the traversal kernels stage in LDS — are the top of the
@@ -372,10 +356,13 @@ __global__ void k_level_advance(const uint32_t* __restrict__ cnt, const uint32_t
 // 4-NODE index (it lives in the binary tree's node_box, whose boxes are not needed once the tree is collapsed): a node leaves the union
 // of its children there for its parent, one level up, which runs in a later launch.  The boxes are the fitted ones (min / max are exact:
 // the union of a collapsed leaf's leaf boxes is the binary node's fitted box), no fences.
+// ITEMS: a leaf's reference is the one its item brings (leaf_ref_of); false: the triangle trees, whose kernel the parameter leaves as it was.
+template <bool ITEMS>
 __global__ void __launch_bounds__(256) k_refit_level(const uint4* __restrict__ refs4, uint32_t base, uint32_t size, const uint32_t* __restrict__ first,
                                                       const uint32_t* __restrict__ last, const uint32_t* __restrict__ keep,
                                                       const uint32_t* __restrict__ index4, const Box6* __restrict__ leaf_box, Box6* box4,
-                                                      BvhNode4* __restrict__ nodes) {
+                                                      BvhNode4* __restrict__ nodes, const uint32_t* __restrict__ sorted_ids,
+                                                      const uint32_t* __restrict__ item_ref) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= size) return;
   const uint32_t idx = base + k;
@@ -386,12 +373,12 @@ __global__ void __launch_bounds__(256) k_refit_level(const uint4* __restrict__ r
   for (int s = 0; s < 4; ++s) {
     const uint32_t r = c[s];
     if (r == kAbsent) continue;
-    if (r & kLeafBit) { ch[n].box = leaf_box[r & ~kLeafBit]; ch[n].ref = leaf_ref(r & ~kLeafBit, 1u); }
+    if (r & kLeafBit) { ch[n].box = leaf_box[r & ~kLeafBit]; ch[n].ref = leaf_ref_of<ITEMS>(r & ~kLeafBit, 1u, sorted_ids, item_ref); }
     else if (!keep[r]) {
       const uint32_t f = first[r], l = last[r];
       Box6 u = leaf_box[f];
       for (uint32_t t = f + 1; t <= l; ++t) u = box_union(u, leaf_box[t]);
-      ch[n].box = u; ch[n].ref = leaf_ref(f, l - f + 1u);
+      ch[n].box = u; ch[n].ref = leaf_ref_of<ITEMS>(f, l - f + 1u, sorted_ids, item_ref);
     } else { ch[n].box = box4[index4[r]]; ch[n].ref = index4[r]; }
     ++n;
   }
@@ -402,7 +389,9 @@ __global__ void __launch_bounds__(256) k_refit_level(const uint4* __restrict__ r
 }
 
 // scene of <= leaf_max triangles: one 4-node with a single leaf child
-__global__ void k_emit_single4(const Box6* __restrict__ leaf_box, uint32_t n, BvhNode4* __restrict__ nodes) {
+template <bool ITEMS>
+__global__ void k_emit_single4(const Box6* __restrict__ leaf_box, uint32_t n, BvhNode4* __restrict__ nodes, const uint32_t* __restrict__ sorted_ids,
+                               const uint32_t* __restrict__ item_ref) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   Child4 ch[1];
   ch[0].box = Box6{};
@@ -410,56 +399,27 @@ __global__ void k_emit_single4(const Box6* __restrict__ leaf_box, uint32_t n, Bv
     ch[0].box = leaf_box[0];
     for (uint32_t k = 1; k < n; ++k) ch[0].box = box_union(ch[0].box, leaf_box[k]);
   }
-  ch[0].ref = n > 0 ? leaf_ref(0u, n) : kAbsent;
+  ch[0].ref = n > 0 ? leaf_ref_of<ITEMS>(0u, n, sorted_ids, item_ref) : kAbsent;
   nodes[0] = pack_node4(ch, 1);
 }
 
-
-constexpr uint32_t kMaxLevels = 96;  // 4-wide levels a tree may have
-
 }  // namespace
 
-// What a build keeps for refit: the 4-wide topology and what flatten, the leaf boxes and the level pack read and write.
-struct BvhTopology {
-  Arena arena;  // first member: destroyed last, after the buffers carved from it
-  uint32_t n = 0, leaf_max = 0;
-  Dev<uint32_t> first, last, keep;  // per binary node: its sorted positions; 1 = has more than leaf_max triangles (an inner 4-node child)
-  Dev<uint4> refs4;                 // per 4-node: the binary references its slots were filled from
-  Dev<uint32_t> index4;             // per kept binary node: the 4-node it is the root of
-  Dev<uint32_t> sorted_ids;         // triangle id of every sorted position
-  Dev<Box6> tri_box, leaf_box;      // by triangle id | by sorted position, widened
-  Dev<Box6> box4;                   // k_refit_level's scratch by 4-node; during the build the binary tree's node_box
-  Dev<uint32_t> scene_ord, block_ord;
-  std::vector<uint32_t> level_base;  // first 4-node of every BFS level, then node_count: the level pack walks them bottom-up
-  bool single_node() const { return n <= leaf_max || n < 2; }
-  DevList plan() {
-    const size_t ni = n > 1 ? n - 1 : 1;
-    return {first.of(ni), last.of(ni), keep.of(ni), refs4.of(ni), index4.of(ni), sorted_ids.of(n), tri_box.of(n), leaf_box.of(n), box4.of(ni),
-            scene_ord.of(6), block_ord.of((size_t)(nblk(n) + 1u) * 6)};
+DevList BuildScratch::plan(uint32_t n, bool morton) {
+  const size_t ni = n > 1 ? n - 1 : 1;
+  size_t scan_bytes = 0, sort_bytes = 0;
+  (void)exclusive_sum(nullptr, scan_bytes, nullptr, nullptr, ni, 0);
+  DevList all = {left.of(ni), right.of(ni), node_parent.of(ni), leaf_parent.of(n), arrivals.of(ni), root_of.of(ni), cnt.of(ni), off.of(ni),
+                 level.of(4), bases.of(kMaxLevels), scan_tmp.of(scan_bytes)};
+  if (morton) {
+    (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr,
+                                    (uint32_t*)nullptr, n, 0, 64, 0);
+    for (DevBytes* d : DevList{keys_in.of(n), keys_out.of(n), ids_in.of(n), sort_tmp.of(sort_bytes)}) all.push_back(d);
   }
-};
+  return all;
+}
 
 namespace {
-
-// What only the build needs, released when it returns: the binary tree but for first / last, the Morton sort, the collapse's counters.
-struct BuildScratch {
-  Dev<uint32_t> left, right, node_parent, leaf_parent, arrivals, root_of, cnt, off, level, bases, ids_in;
-  Dev<unsigned long long> keys_in, keys_out;
-  Dev<char> sort_tmp, scan_tmp;  // rocPRIM's
-  DevList plan(uint32_t n, bool morton) {
-    const size_t ni = n > 1 ? n - 1 : 1;
-    size_t scan_bytes = 0, sort_bytes = 0;
-    (void)exclusive_sum(nullptr, scan_bytes, nullptr, nullptr, ni, 0);
-    DevList all = {left.of(ni), right.of(ni), node_parent.of(ni), leaf_parent.of(n), arrivals.of(ni), root_of.of(ni), cnt.of(ni), off.of(ni),
-                   level.of(4), bases.of(kMaxLevels), scan_tmp.of(scan_bytes)};
-    if (morton) {
-      (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr,
-                                      (uint32_t*)nullptr, n, 0, 64, 0);
-      for (DevBytes* d : DevList{keys_in.of(n), keys_out.of(n), ids_in.of(n), sort_tmp.of(sort_bytes)}) all.push_back(d);
-    }
-    return all;
-  }
-};
 
 // RENDER_SPEC 4.1b: leaf boxes are widened by 2^-19 of the scene's largest coordinate
 float box_pad(const BvhBuffers& b) {
@@ -473,7 +433,7 @@ std::string flatten_and_bounds(BvhBuffers& b, BvhTopology& t, hipStream_t s) {
   if (n) {
     hipLaunchKernelGGL(k_flatten, dim3(nblk(n)), dim3(256), 0, s, b.primitives, b.inst_first_tri, b.instance_count, n, b.tris_by_id, b.shade_tris,
                        t.tri_box, t.block_ord, b.gid_first, b.inst_index, b.object_space ? 1 : 0);
-    hipLaunchKernelGGL(k_bounds_reduce, dim3(1), dim3(256), 0, s, t.block_ord, nblk(n), t.scene_ord);
+    bounds_reduce(t.block_ord, nblk(n), t.scene_ord, s);
   }
   uint32_t ord[6];
   HIP_TRY(hipMemcpyAsync(ord, t.scene_ord, sizeof(ord), hipMemcpyDeviceToHost, s));
@@ -483,6 +443,18 @@ std::string flatten_and_bounds(BvhBuffers& b, BvhTopology& t, hipStream_t s) {
     b.scene_max[k] = n ? ord2f(ord[3 + k]) : 0.0f;
   }
   return "";
+}
+
+void leaf_boxes(BvhBuffers& b, BvhTopology& t, hipStream_t s) {
+  const uint32_t n = b.tri_count;
+  if (n) hipLaunchKernelGGL(k_leaf_boxes, dim3(nblk(n)), dim3(256), 0, s, t.tri_box, t.sorted_ids, n, t.leaf_box, b.tris_by_id, b.tris, box_pad(b), b.tris_any,
+                            b.shade_tris, b.material_any_class, b.material_count, b.material_kind);
+}
+
+}  // namespace
+
+void bounds_reduce(const uint32_t* block_ord, uint32_t blocks, uint32_t* scene_ord, hipStream_t s) {
+  hipLaunchKernelGGL(k_bounds_reduce, dim3(1), dim3(256), 0, s, block_ord, blocks, scene_ord);
 }
 
 // Karras' LBVH, or the Morton order PLOC starts from
@@ -496,10 +468,10 @@ std::string morton_hierarchy(const HierarchyJob& job, BuildScratch& sc, const ui
   return "";
 }
 
-void leaf_boxes(BvhBuffers& b, BvhTopology& t, hipStream_t s) {
-  const uint32_t n = b.tri_count;
-  if (n) hipLaunchKernelGGL(k_leaf_boxes, dim3(nblk(n)), dim3(256), 0, s, t.tri_box, t.sorted_ids, n, t.leaf_box, b.tris_by_id, b.tris, box_pad(b), b.tris_any,
-                            b.shade_tris, b.material_any_class, b.material_count, b.material_kind);
+std::string fit_hierarchy(const BinaryTree& tree, const Box6* leaf_box, uint32_t* arrivals, uint32_t n, hipStream_t s) {
+  HIP_TRY(hipMemsetAsync(arrivals, 0, (size_t)(n - 1) * 4, s));
+  hipLaunchKernelGGL(k_fit, dim3(nblk(n)), dim3(256), 0, s, tree, leaf_box, arrivals, n);
+  return "";
 }
 
 // Chooses the 4-wide topology from the fitted binary tree (keep, refs4, index4, level_base) and with it the node count, the depth and
@@ -543,18 +515,19 @@ std::string collapse(BvhBuffers& b, BvhTopology& t, BuildScratch& sc, const Bina
 // The only writer of the 64-B nodes, after a build and after a refit: levels are contiguous in BFS order, so one launch per level from
 // the deepest up derives every node from its children's boxes (leaf boxes, or the union a child node left in box4[its index]).
 std::string pack_levels(BvhBuffers& b, BvhTopology& t, hipStream_t s) {
-  if (t.single_node()) hipLaunchKernelGGL(k_emit_single4, dim3(1), dim3(64), 0, s, t.leaf_box, t.n, b.nodes);
+  auto* emit = t.item_ref ? k_emit_single4<true> : k_emit_single4<false>;
+  auto* level = t.item_ref ? k_refit_level<true> : k_refit_level<false>;
+  if (t.single_node()) hipLaunchKernelGGL(emit, dim3(1), dim3(64), 0, s, t.leaf_box, t.n, b.nodes, t.sorted_ids, t.item_ref);
   else
     for (size_t l = t.level_base.size() - 1; l-- > 0;) {
       const uint32_t base = t.level_base[l], size = t.level_base[l + 1] - base;
-      hipLaunchKernelGGL(k_refit_level, dim3(nblk(size)), dim3(256), 0, s, t.refs4, base, size, t.first, t.last, t.keep, t.index4, t.leaf_box, t.box4, b.nodes);
+      hipLaunchKernelGGL(level, dim3(nblk(size)), dim3(256), 0, s, t.refs4, base, size, t.first, t.last, t.keep, t.index4, t.leaf_box, t.box4, b.nodes,
+                         t.sorted_ids, t.item_ref);
     }
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipGetLastError());
   return "";
 }
-
-}  // namespace
 
 hipError_t exclusive_sum(void* storage, size_t& bytes, const uint32_t* in, uint32_t* out, size_t n, hipStream_t s) {
   return rocprim::exclusive_scan(storage, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s);
@@ -603,8 +576,7 @@ std::string bvh_build(BvhBuffers& b, uint32_t leaf_max, hipStream_t s) {
     b.stack_need = 1;
   } else {
     if (!sah && !ploc) {  // the Karras hierarchy has no boxes yet
-      HIP_TRY(hipMemsetAsync(sc.arrivals, 0, (size_t)(n - 1) * 4, s));
-      hipLaunchKernelGGL(k_fit, dim3(nblk(n)), dim3(256), 0, s, tree, t.leaf_box, sc.arrivals, n);
+      if (!(e = fit_hierarchy(tree, t.leaf_box, sc.arrivals, n, s)).empty()) return e;
     }
     if (!(e = collapse(b, t, sc, tree, s)).empty()) return e;
   }

@@ -1,4 +1,5 @@
-// bvh_build_impl.h — what bvh_build.hip and its two hierarchy builders (bvh_sah.hip, bvh_ploc.hip) share; included by these three only.
+// bvh_build_impl.h — what bvh_build.hip, its two hierarchy builders (bvh_sah.hip, bvh_ploc.hip) and the builder of the instance levels
+// (bvh_instances.hip) share; included by these four only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -58,6 +59,7 @@ inline uint32_t nblk(uint32_t n) { return (n + 255u) / 256u; }
 struct Arena {
   char* base = nullptr;
   size_t cap = 0, used = 0;
+  bool owned = true;
   Arena* prev = nullptr;
   static Arena*& active() { static thread_local Arena* a = nullptr; return a; }
   static size_t aligned(size_t bytes) { return (bytes + 255u) & ~size_t(255); }
@@ -67,6 +69,11 @@ struct Arena {
     prev = active(); active() = this;
     return "";
   }
+  // carve from memory that somebody else keeps (the instance levels' arena outlives its builds: a rebuild allocates nothing)
+  void adopt(void* memory, size_t bytes) {
+    base = static_cast<char*>(memory); cap = bytes; used = 0; owned = false;
+    prev = active(); active() = this;
+  }
   void close() { if (active() == this) active() = prev; }  // no more carving; the memory lives until the destructor
   void* take(size_t bytes) {
     const size_t at = aligned(used);
@@ -74,7 +81,7 @@ struct Arena {
     used = at + bytes;
     return base + at;
   }
-  ~Arena() { close(); if (base) (void)hipFree(base); }
+  ~Arena() { close(); if (base && owned) (void)hipFree(base); }
 };
 struct DevBytes {
   void* raw = nullptr;
@@ -146,5 +153,66 @@ size_t sah_scratch_bytes(uint32_t n);
 std::string sah_hierarchy(const HierarchyJob& job, hipStream_t s);
 size_t ploc_scratch_bytes(uint32_t n);
 std::string ploc_hierarchy(const HierarchyJob& job, hipStream_t s);
+
+// ---- from the hierarchy to the 64-B nodes (bvh_build.hip) -----------------------------------------------------------------------------
+constexpr uint32_t kMaxLevels = 96;  // 4-wide levels a tree may have
+
+// What a build keeps for refit: the 4-wide topology and what flatten, the leaf boxes and the level pack read and write.
+struct BvhTopology {
+  Arena arena;  // first member: destroyed last, after the buffers carved from it
+  uint32_t n = 0, leaf_max = 0;
+  Dev<uint32_t> first, last, keep;  // per binary node: its sorted positions; 1 = has more than leaf_max triangles (an inner 4-node child)
+  Dev<uint4> refs4;                 // per 4-node: the binary references its slots were filled from
+  Dev<uint32_t> index4;             // per kept binary node: the 4-node it is the root of
+  Dev<uint32_t> sorted_ids;         // triangle id of every sorted position
+  Dev<Box6> tri_box, leaf_box;      // by triangle id | by sorted position, widened
+  Dev<Box6> box4;                   // k_refit_level's scratch by 4-node; during the build the binary tree's node_box
+  Dev<uint32_t> scene_ord, block_ord;
+  // null: a leaf's child reference names its sorted positions (triangles).  Otherwise the tree stands over items that bring their own
+  // reference (the instance levels, leaf_max = 1): the leaf at sorted position k gets item_ref[sorted_ids[k]]
+  const uint32_t* item_ref = nullptr;
+  std::vector<uint32_t> level_base;  // first 4-node of every BFS level, then node_count: the level pack walks them bottom-up
+  bool single_node() const { return n <= leaf_max || n < 2; }
+  DevList plan() {
+    const size_t ni = n > 1 ? n - 1 : 1;
+    return {first.of(ni), last.of(ni), keep.of(ni), refs4.of(ni), index4.of(ni), sorted_ids.of(n), tri_box.of(n), leaf_box.of(n), box4.of(ni),
+            scene_ord.of(6), block_ord.of((size_t)(nblk(n) + 1u) * 6)};
+  }
+};
+// What only the build needs, released when it returns: the binary tree but for first / last, the Morton sort, the collapse's counters.
+struct BuildScratch {
+  Dev<uint32_t> left, right, node_parent, leaf_parent, arrivals, root_of, cnt, off, level, bases, ids_in;
+  Dev<unsigned long long> keys_in, keys_out;
+  Dev<char> sort_tmp, scan_tmp;  // rocPRIM's
+  DevList plan(uint32_t n, bool morton);
+};
+// Folds ord[6] (min xyz, max xyz as ordered integers) over a 256-thread block: wave shuffle reduction, then the four waves through LDS;
+// threads 0..5 leave component threadIdx.x in out[at + threadIdx.x].
+RT_DI void block_bounds_fold(uint32_t (&ord)[6], uint32_t (&wave_ord)[4][6], uint32_t tid, uint32_t* __restrict__ out, uint32_t at) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      ord[k] = min(ord[k], (uint32_t)__shfl_xor((int)ord[k], m, 64));
+      ord[3 + k] = max(ord[3 + k], (uint32_t)__shfl_xor((int)ord[3 + k], m, 64));
+    }
+  }
+  if ((tid & 63u) == 0u) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) wave_ord[tid >> 6][k] = ord[k];
+  }
+  __syncthreads();
+  if (tid < 6u) {
+    uint32_t v = wave_ord[0][tid];
+    for (int w = 1; w < 4; ++w) v = tid < 3u ? min(v, wave_ord[w][tid]) : max(v, wave_ord[w][tid]);
+    out[at + tid] = v;
+  }
+}
+// the steps of bvh_build that a tree over other things than triangles takes as well (bvh_instances.hip); b: tri_count, opt, nodes and the results
+void bounds_reduce(const uint32_t* block_ord, uint32_t blocks, uint32_t* scene_ord, hipStream_t s);  // k_bounds_reduce
+std::string morton_hierarchy(const HierarchyJob& job, BuildScratch& sc, const uint32_t* scene_ord, bool ploc, hipStream_t s);
+std::string fit_hierarchy(const BinaryTree& tree, const Box6* leaf_box, uint32_t* arrivals, uint32_t n, hipStream_t s);  // after the Karras hierarchy only
+std::string collapse(BvhBuffers& b, BvhTopology& t, BuildScratch& sc, const BinaryTree& tree, hipStream_t s);
+std::string pack_levels(BvhBuffers& b, BvhTopology& t, hipStream_t s);
 
 }  // namespace rt

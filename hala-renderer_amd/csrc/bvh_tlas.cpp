@@ -1,6 +1,9 @@
 // bvh_tlas.cpp — the top levels of a two-level tree (RENDER_SPEC 4.5): what the reference asks the driver for with its instance list
-// (src/scene/loader/gpu_uploader.rs:843-885, :937-959).  Host code: a scene has tens to thousands of instances, their tree is rebuilt
-// from scratch in microseconds whenever a node moves (hala_rt_refit), and the big per-primitive trees underneath stay untouched.
+// (src/scene/loader/gpu_uploader.rs:843-885, :937-959).  Host code, one thread: the tree is rebuilt from scratch whenever a node moves
+// (hala_rt_refit, every shutter step of a scene with node keys), and the big per-primitive trees underneath stay untouched.  Every binary
+// node sorts its items on three axes and keeps a copy of the best order, so the time grows faster than the item count: a refit of a
+// scene of 1 024 instances takes 1.2 ms, of 16 384 38 ms, of 131 072 0.96 s (profiles/instance_levels_timing.json).
+// This is hala_rt_build_options::instance_levels = 0, the default; bvh_instances.hip builds the same levels on the GPU (= 1).
 //
 // Items are boxes with a child reference each: an instance leaf (kInstLeafTag | index into the InstRef table) or the root of a subtree
 // that needs no transform (the tree over all triangles that are NOT instanced: flattened to world space as before).  Output: 64-B

@@ -110,6 +110,35 @@ void bvh_free_topology(void* topology);
 struct TlasItem { float mn[3], mx[3]; uint32_t ref, need; };
 uint32_t tlas_build(const std::vector<TlasItem>& items, std::vector<BvhNode4>& out, uint32_t* levels, uint32_t* stack_need);
 
+// bvh_instances.hip — the same levels built on the GPU (hala_rt_build_options::instance_levels = 1): items, scene bounds, hierarchy
+// (BuildOptions::builder as for triangles), collapse and level pack all run on the device, out of an arena the caller keeps.
+// What the host knows of one tree below the instance levels, rewritten only after that tree was built or refitted
+struct InstTree {
+  uint32_t node_off, tri_off;  // its root node; its first shading record (= first stored triangle)
+  uint32_t need, depth;        // traversal stack entries a ray can need in it; its levels
+  float mn[3], mx[3];          // its exact bounds, in its own space
+};
+struct InstItem { uint32_t inst, tree; };  // instance (kAbsent: the item of the world-space tree, which comes first) and its tree
+struct InstanceLevelsJob {
+  uint32_t n, world_item;                // items; 1: item 0 is the world tree's
+  const InstItem* items;                 // [n] device, written at commit
+  const InstTree* trees;                 // device
+  const hala_gpu_mesh_data* instances;   // the packed instances (object -> world), device
+  const uint32_t* inst_first_tri;
+  InstRef* inst_refs;                    // out [n - world_item]
+  BvhNode4* nodes;                       // out, breadth-first, root 0
+  uint32_t node_capacity;
+  void* arena;                           // instance_levels_arena_bytes(n, opt) bytes, reused by every build
+  size_t arena_bytes;
+  BuildOptions opt;
+  // results
+  uint32_t node_count, levels;
+  float scene_min[3], scene_max[3];      // RENDER_SPEC 4.5
+};
+size_t instance_levels_arena_bytes(uint32_t n, const BuildOptions& opt);
+// "" or an error message.  Synchronises the stream before returning.
+std::string instance_levels_build(InstanceLevelsJob& job, hipStream_t s);
+
 // envmap.hip — A1: EnvMap::build_distribution_maps (src/envmap.rs:239-388) on the GPU
 // d_rgba: W*H float4; outputs device pointers: total_sum[1], marginal[H], conditional[W*H]
 std::string envmap_build_distribution(const float4* d_rgba, uint32_t width, uint32_t height, float* d_total_sum, float* d_marginal,

@@ -295,6 +295,21 @@ struct ShutterState {
   void off() { rec = ShutterKeys(); act = ShutterKeys(); step = kShutterNoStep; time = 0.0f; locals.clear(); materials.clear(); stale.clear(); }
 };
 
+// The instance levels of a two-level tree built on the GPU (hala_rt_build_options::instance_levels = 1; bvh_instances.hip): what survives
+// between refits, so that a refit allocates nothing.  Everything releases itself.
+struct InstanceLevels {
+  uint32_t requested = 0;  // hala_rt_build_options::instance_levels as last set
+  uint32_t mode = 0;       // as the last commit applied it: 0 built on the host (bvh_tlas.cpp), 1 on the GPU
+  BuildOptions opt;        // the builder the commit chose: what the arena is sized for
+  uint32_t items = 0, world_item = 0;  // items of the levels; 1: the first one is the world tree's
+  DeviceArray<char> arena;             // all a build carves (item boxes, hierarchy, collapse), sized from the item count
+  DeviceArray<InstItem> d_items;       // per item: its instance and its tree — a pose does not change them
+  DeviceArray<InstTree> d_trees;       // per tree below the levels: where it starts, its bounds, need and depth
+  std::vector<InstTree> trees;         // what d_trees holds
+  bool refs_on_host = true;            // hala_rt_renderer::inst_refs holds what d_inst_refs holds (a GPU build only writes the latter)
+  void release() { arena.release(); d_items.release(); d_trees.release(); trees.clear(); items = world_item = 0; refs_on_host = true; }
+};
+
 enum class Changed { Commit, Refit, Views, Aovs };  // hala_rt_renderer::invalidate
 
 }  // namespace rt
@@ -346,7 +361,7 @@ struct hala_rt_renderer {
   // two-level trees (RENDER_SPEC 4.5): scenes in which some primitive is referenced by several instances.  `bvh` then only carries the
   // totals; the trees live in `blas` — [0] the world-space tree over the triangles of all instances that are NOT instanced (if any), then
   // one object-space tree per instanced primitive — as sub-ranges of the node / triangle / shading-record arrays, behind the instance
-  // levels (the first tlas_capacity nodes), which are rebuilt on the host whenever a node moves.
+  // levels (the first tlas_capacity nodes), which are rebuilt whenever a node moves (on the host, or on the GPU: `levels`).
   struct Blas {
     BvhBuffers b{};
     uint32_t node_off = 0, tri_off = 0, node_cap = 0;
@@ -363,8 +378,9 @@ struct hala_rt_renderer {
   std::vector<uint8_t> inst_instanced;     // per instance: intersected in object space
   std::vector<int32_t> prim_blas;          // per primitive: index into blas, -1
   uint32_t tlas_capacity = 0, tlas_nodes = 0, stored_tris = 0;
-  std::vector<InstRef> inst_refs;
+  std::vector<InstRef> inst_refs;          // (levels.refs_on_host tells whether its contents are current)
   DeviceArray<InstRef> d_inst_refs;
+  InstanceLevels levels;
   DeviceArray<InstInfo> d_inst_info;
   DeviceArray<Tri> d_tris_by_id, d_tris;
   DeviceArray<Tri> d_tris_any;

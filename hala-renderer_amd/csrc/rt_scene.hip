@@ -201,6 +201,7 @@ int update_texture_bundles(hala_rt_renderer* r, bool fresh) {
   return HALA_OK;
 }
 
+static int fetch_instance_refs(hala_rt_renderer* r);
 static int configure_traversal(hala_rt_renderer* r) {
   const size_t nb = (size_t)r->bvh.node_count * 64, tb = (size_t)r->bvh.tri_count * 48;
   // Whole BVH in LDS when it fits the budget (the STAGED kernel variants read it with ds_read only); otherwise nothing
@@ -220,7 +221,11 @@ static int configure_traversal(hala_rt_renderer* r) {
   // refilling once half the wave is idle is best when node fetches go to L2 / Infinity Cache
   r->lcfg.refill = r->staged ? 64u : kRefillThreshold;
   if (r->two_level || r->bvh.stack_need > traverse_stack_lds_levels(tree)) {
-    if (r->two_level || r->bvh.stack_need > traverse_stack_lds_levels(tree) + traverse_stack_spill_levels()) {
+    // (instance levels built on the GPU bring a conservative need and keep their InstRef table on the device: the exact sweep, a download
+    // of all nodes, only runs for them when that need would refuse the tree)
+    const bool over = r->bvh.stack_need > traverse_stack_lds_levels(tree) + traverse_stack_spill_levels();
+    if (over && r->two_level && fetch_instance_refs(r) != HALA_OK) return HALA_ERR;
+    if ((r->two_level && r->levels.mode == 0u) || over) {
       // 3 x levels is a loose bound (every node on the path deferring three siblings).  Before refusing the tree, take the exact
       // one: need(node) = (inner children - 1) + max need(inner child) — the worst order visits the child with the deepest
       // need first while all its siblings wait.  Nodes are in breadth-first order (children behind their parent): one reverse sweep.
@@ -279,6 +284,14 @@ static int attach_any_triangles(hala_rt_renderer* r) {
 }
 
 // ---- two-level trees (RENDER_SPEC 4.5) ---------------------------------------------------------------------------------------------
+// instance levels built on the GPU write the InstRef table on the device: the host copy follows when somebody asks for it
+static int fetch_instance_refs(hala_rt_renderer* r) {
+  if (r->levels.refs_on_host) return HALA_OK;
+  RT_HIP(hipStreamSynchronize(r->stream));
+  if (!r->inst_refs.empty()) RT_HIP(hipMemcpy(r->inst_refs.data(), r->d_inst_refs.ptr, r->inst_refs.size() * sizeof(InstRef), hipMemcpyDeviceToHost));
+  r->levels.refs_on_host = true;
+  return HALA_OK;
+}
 // world -> object of one instance: rows of the inverse of the upper 3x3 (cross products of its columns over the determinant) and the
 // translation; false: not invertible in float (the instance is flattened to world space like a primitive that is referenced once)
 static float h_dot3(const float* a, const float* b) { return std::fmaf(a[2], b[2], std::fmaf(a[1], b[1], a[0] * b[0])); }
@@ -315,9 +328,79 @@ static void classify_instances(hala_rt_renderer* r, std::vector<uint8_t>* flags)
   }
 }
 
+// The instance levels on the GPU (hala_rt_build_options::instance_levels = 1; bvh_instances.hip).  fresh: a commit — the tables a pose does
+// not change (InstInfo, the items' instance and tree) are made and uploaded and the arena is sized; a refit reuses them and allocates
+// nothing.  Per build the host writes the small table of the trees, and only if a tree below was built or refitted since, then launches.
+// (No test for a transform that stopped being invertible here: classify_instances has just made it, on the same transforms, for every
+// instance this build treats as instanced.)
+static int build_instance_levels_gpu(hala_rt_renderer* r, bool fresh) {
+  const HostScene& hs = r->hs;
+  InstanceLevels& lv = r->levels;
+  const bool world = !r->blas.empty() && !r->blas[0]->object_space && r->blas[0]->b.tri_count;
+  std::vector<InstTree> trees(r->blas.size());
+  uint32_t deepest = 0, largest_need = 0;
+  for (size_t t = 0; t < r->blas.size(); ++t) {
+    const hala_rt_renderer::Blas& bl = *r->blas[t];
+    InstTree& tr = trees[t];
+    tr.node_off = bl.node_off; tr.tri_off = bl.tri_off; tr.need = bl.b.stack_need; tr.depth = bl.b.max_depth;
+    memcpy(tr.mn, bl.b.scene_min, 12); memcpy(tr.mx, bl.b.scene_max, 12);
+    if (!bl.object_space && !world) continue;  // a world tree without triangles has no item
+    deepest = std::max(deepest, bl.b.max_depth);
+    // an instance: the world-space ray (3 entries) and the exit mark wait below its own entries
+    largest_need = std::max(largest_need, bl.object_space ? 4u + bl.b.stack_need : bl.b.stack_need);
+  }
+  if (fresh) {
+    std::vector<InstItem> items;
+    std::vector<InstInfo> info(hs.instances.size());
+    std::vector<uint32_t> flat_base(hs.instances.size(), 0u);
+    if (!r->blas.empty() && !r->blas[0]->object_space) {
+      uint32_t at = r->blas[0]->tri_off;
+      for (uint32_t i : r->blas[0]->insts) { flat_base[i] = at; at += hs.inst_first_tri[i + 1] - hs.inst_first_tri[i]; }
+    }
+    if (world) items.push_back(InstItem{kAbsent, 0u});
+    for (size_t i = 0; i < hs.instances.size(); ++i) {
+      info[i].first_tri = hs.inst_first_tri[i];
+      info[i].instanced = r->inst_instanced[i];
+      info[i].pad = 0;
+      if (!r->inst_instanced[i]) { info[i].shade_base = flat_base[i]; continue; }
+      const uint32_t t = (uint32_t)r->prim_blas[hs.instance_prim[i]];
+      info[i].shade_base = r->blas[t]->tri_off;
+      items.push_back(InstItem{(uint32_t)i, t});
+    }
+    if (items.empty() || items.size() > r->tlas_capacity) RT_FAIL("internal: instance levels larger than reserved");
+    lv.items = (uint32_t)items.size(); lv.world_item = world ? 1u : 0u;
+    if (lv.items - lv.world_item >= 0x0ffffff0u) RT_FAIL("Too many instances.");
+    lv.opt = r->bvh.opt;
+    r->inst_refs.assign(lv.items - lv.world_item, InstRef{});
+    RT_HIP(r->d_inst_refs.resize(r->inst_refs.size()));
+    RT_HIP(lv.arena.resize(instance_levels_arena_bytes(lv.items, lv.opt)));
+    RT_HIP(lv.d_items.upload(items.data(), items.size(), r->stream));
+    RT_HIP(r->d_inst_info.upload(info.data(), info.size(), r->stream));
+    RT_HIP(hipStreamSynchronize(r->stream));  // `items`, `info` go out of scope
+  }
+  if (fresh || trees.size() != lv.trees.size() || memcmp(trees.data(), lv.trees.data(), trees.size() * sizeof(InstTree)) != 0) {
+    lv.trees = trees;  // (the copy the upload reads outlives it)
+    RT_HIP(lv.d_trees.upload(lv.trees.data(), lv.trees.size(), r->stream));
+  }
+  InstanceLevelsJob job{};
+  job.n = lv.items; job.world_item = lv.world_item;
+  job.items = lv.d_items.ptr; job.trees = lv.d_trees.ptr; job.instances = r->d_instances.ptr; job.inst_first_tri = r->d_inst_first_tri.ptr;
+  job.inst_refs = r->d_inst_refs.ptr; job.nodes = r->d_nodes.ptr; job.node_capacity = r->tlas_capacity;
+  job.arena = lv.arena.ptr; job.arena_bytes = lv.arena.bytes(); job.opt = lv.opt;
+  const std::string e = instance_levels_build(job, r->stream);
+  if (!e.empty()) RT_FAIL(e);
+  lv.refs_on_host = false;
+  r->tlas_nodes = job.node_count;
+  r->bvh.max_depth = job.levels + deepest;
+  r->bvh.stack_need = 3u * job.levels + largest_need;  // a 4-node visit defers at most three siblings; an item brings its own need
+  memcpy(r->bvh.scene_min, job.scene_min, 12); memcpy(r->bvh.scene_max, job.scene_max, 12);
+  return HALA_OK;
+}
+
 // the instance levels: InstRef per instanced instance, one item per instanced instance + one for the world tree, the host build, the upload;
 // also the scene bounds (RENDER_SPEC 4.5: world tree's exact bounds + the boxes of the transformed corners of the instanced primitives' bounds)
-static int build_instance_levels(hala_rt_renderer* r) {
+static int build_instance_levels(hala_rt_renderer* r, bool fresh) {
+  if (r->levels.mode == 1u) return build_instance_levels_gpu(r, fresh);
   const HostScene& hs = r->hs;
   std::vector<TlasItem> items;
   r->inst_refs.clear();
@@ -380,6 +463,7 @@ static int build_instance_levels(hala_rt_renderer* r) {
   RT_HIP(r->d_inst_refs.upload(r->inst_refs.data(), r->inst_refs.size(), r->stream));
   RT_HIP(r->d_inst_info.upload(info.data(), info.size(), r->stream));
   RT_HIP(hipStreamSynchronize(r->stream));  // `nodes`, `info` go out of scope
+  r->levels.refs_on_host = true;
   r->bvh.max_depth = levels + deepest;
   r->bvh.stack_need = need;
   for (int k = 0; k < 3; ++k) { r->bvh.scene_min[k] = items.empty() ? 0.0f : smin[k]; r->bvh.scene_max[k] = items.empty() ? 0.0f : smax[k]; }
@@ -478,7 +562,7 @@ static int build_two_level(hala_rt_renderer* r) {
   r->bvh.node_count = node_at;  // the node array as a whole (reserved ranges included: hala_rt_download_bvh)
   r->bvh.tris_any = r->any_invisible ? r->d_tris_any.ptr : nullptr;
   r->leaf_max_built = kLeafMax;
-  if (build_instance_levels(r) != HALA_OK) return HALA_ERR;
+  if (build_instance_levels(r, true) != HALA_OK) return HALA_ERR;
   return configure_traversal(r);
 }
 
@@ -488,6 +572,8 @@ int build_bvh(hala_rt_renderer* r) {
   for (uint8_t f : r->inst_instanced) r->two_level = r->two_level || f != 0;
   if (r->bvh.topology) { bvh_free_topology(r->bvh.topology); r->bvh.topology = nullptr; }
   r->blas.clear();
+  r->levels.release();
+  r->levels.mode = r->levels.requested;  // the build option takes effect here: at a commit, or when a refit has to build again
   r->bvh.gid_first = nullptr; r->bvh.inst_index = nullptr; r->bvh.object_space = false;
   if (r->two_level) return build_two_level(r);
   const uint32_t n = r->hs.triangle_count;
@@ -514,9 +600,10 @@ extern "C" {
 int hala_rt_set_build_options(hala_rt_renderer* r, const hala_rt_build_options* o) {
   if (!r) RT_FAIL("The renderer handle is null!");
   if (!o) RT_FAIL("The build options are null!");
-  if (o->builder > 3u || o->ploc_tail > 2u || o->instancing > 2u || o->texture_bundles > 1u) RT_FAIL("Invalid build options.");
+  if (o->builder > 3u || o->ploc_tail > 2u || o->instancing > 2u || o->texture_bundles > 1u || o->instance_levels > 1u) RT_FAIL("Invalid build options.");
   for (uint32_t v : o->reserved) if (v != 0u) RT_FAIL("Invalid build options (reserved fields must be 0).");
   r->instancing_mode = o->instancing;
+  r->levels.requested = o->instance_levels;
   r->bundles.mode = o->texture_bundles;
   r->bvh.opt.builder = o->builder; r->bvh.opt.ploc_tail = o->ploc_tail;
   r->bvh.opt.ploc_look_every = o->ploc_look_every; r->bvh.opt.collapse_look_every = o->collapse_look_every;
@@ -612,6 +699,7 @@ int hala_rt_download_instance_refs(hala_rt_renderer* r, void* refs_64B, uint32_t
   if (!r || !count) RT_FAIL("Invalid argument.");
   if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
   *count = r->two_level ? (uint32_t)r->inst_refs.size() : 0u;
+  if (refs_64B && r->two_level && fetch_instance_refs(r) != HALA_OK) return HALA_ERR;
   if (refs_64B && r->two_level) memcpy(refs_64B, r->inst_refs.data(), std::min<size_t>(capacity, r->inst_refs.size()) * sizeof(InstRef));
   return HALA_OK;
 }
@@ -690,7 +778,7 @@ int refit_geometry(hala_rt_renderer* r, const RefitInputs& in) {
   classify_instances(r, &flags);
   if (flags != r->inst_instanced) return build_bvh(r);
   if (r->two_level) {
-    // RENDER_SPEC 4.5: a node that moves an instanced primitive only touches the instance levels (rebuilt on the host below).  The trees
+    // RENDER_SPEC 4.5: a node that moves an instanced primitive only touches the instance levels (rebuilt below, on the host or on the GPU).  The trees
     // underneath are refitted when what THEY hold changed: `content` (any tree), the transform of a flattened instance (the world tree)
     r->bvh.tris_any = r->any_invisible ? r->d_tris_any.ptr : nullptr;
     for (auto& bl : r->blas) {
@@ -699,7 +787,7 @@ int refit_geometry(hala_rt_renderer* r, const RefitInputs& in) {
         for (uint32_t i : bl->insts) moved = moved || memcmp(before[i].transform, r->hs.instances[i].transform, 64) != 0;
       if (moved && blas_build_or_refit(r, *bl, true) != HALA_OK) return HALA_ERR;
     }
-    if (build_instance_levels(r) != HALA_OK) return HALA_ERR;
+    if (build_instance_levels(r, false) != HALA_OK) return HALA_ERR;
     return configure_traversal(r);
   }
   if (geometry_moved) {

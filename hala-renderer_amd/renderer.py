@@ -119,16 +119,20 @@ class HalaRenderer:
         self._check(self._lib.hala_rt_commit(self._h))
 
     BUILDERS = {None: 0, "auto": 0, "sah": 1, "ploc": 2, "lbvh": 3}
+    INSTANCE_LEVELS = {None: 0, "host": 0, "gpu": 1}
 
-    def set_build_options(self, builder=None, ploc_tail=0, ploc_look_every=0, collapse_look_every=0, instancing=None, texture_bundles=None):
+    def set_build_options(self, builder=None, ploc_tail=0, ploc_look_every=0, collapse_look_every=0, instancing=None, texture_bundles=None,
+                          instance_levels=None):
         """how the next commit() builds the acceleration structure (hala_rt_set_build_options): builder = None | "sah" | "ploc" | "lbvh";
         instancing = True: two-level tree (RENDER_SPEC 4.5: primitives referenced by several instances are stored once), False: every
         instance flattened to world space (one tree), None: automatic (flattened up to 2^26 triangles); the other fields only change how the
         host drives the build rounds (same tree); texture_bundles = None / True: the co-sized 8-bit maps of a material are also stored
-        interleaved and fetched together (same images, faster shading), False: off"""
+        interleaved and fetched together (same images, faster shading), False: off; instance_levels = None | "host" | "gpu": where the
+        instance levels of a two-level tree are built at commit and rebuilt by every refit and shutter step (same images)"""
         o = A.BuildOptions(builder=self.BUILDERS[builder], ploc_tail=ploc_tail, ploc_look_every=ploc_look_every, collapse_look_every=collapse_look_every,
                            instancing=0 if instancing is None else (2 if instancing else 1),
-                           texture_bundles=0 if texture_bundles is None or texture_bundles else 1)
+                           texture_bundles=0 if texture_bundles is None or texture_bundles else 1,
+                           instance_levels=self.INSTANCE_LEVELS[instance_levels])
         self._check(self._lib.hala_rt_set_build_options(self._h, C.byref(o)))
 
     def update(self, delta_time=0.0, width=None, height=None, ui_fn=None):

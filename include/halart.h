@@ -445,7 +445,25 @@ typedef struct hala_rt_build_options {
                                  * 7.4); costs 16 B per texel of every bundled tuple beside the textures themselves.
                                  *  0: automatic — on, unless the bundle memory cannot be had (then silently off);  1: off.
                                  * hala_rt_texture_bundle_info tells what a commit built. */
-  uint32_t reserved[2];         /* must be 0 */
+  uint32_t instance_levels;     /* where the instance levels of a two-level tree are built, at commit and again at every refit and shutter
+                                 * step of such a scene (RENDER_SPEC 4.5 fixes their format, not their shape; images do not depend on it):
+                                 *  0: on the host (one thread, full-sweep SAH over the instances);
+                                 *  1: on the GPU, by the builder `builder` selects with instances in the place of triangles (automatic:
+                                 *     LBVH below 4096 instances, full-sweep SAH from there).  A refit then allocates nothing.
+                                 * Choose 1 from a few thousand instances (MI355X; profiles/instance_levels_timing.json: N instances of a
+                                 * 1 280-triangle primitive; host build against GPU build, ms):
+                                 *    N        commit         refit, one node moved   refit, all moved   1080p frame
+                                 *    1 024    1.6 / 0.9      1.2 / 0.45              1.2 / 0.43         3.03 / 3.39
+                                 *   16 384    39 / 4.0       38 / 3.8                39 / 3.5           4.35 / 4.40
+                                 *  131 072    952 / 7.6      962 / 10.9              855 / 10.6         5.11 / 5.16
+                                 * From 4096 instances, where the automatic builder is SAH, the GPU-built tree renders like the host's
+                                 * (+0.05 ms, 1 %, with the automatic builder; +0.004 ms with builder = 1 on both sides; repeated host-tree
+                                 * frames spread by 0.02 ms).  Below 4096 the automatic builder is LBVH: builds win from the smallest count
+                                 * measured, but at 1 024 its tree renders 12 % slower than the host's; builder = 1 there gives the host's
+                                 * frame time (2.86 / 2.85 ms) and a slower build than the host's (refit 1.8 against 1.2 ms), so small scenes
+                                 * keep 0.  builder = 2 and 3 (PLOC, LBVH) build the levels fastest (131 072: refit 7.9 and 6.7 ms, most of
+                                 * it the host's own work per instance) and render 38 % and 15 % slower there: for edits, not for stills. */
+  uint32_t reserved[1];         /* must be 0 */
 } hala_rt_build_options;
 int hala_rt_set_build_options(hala_rt_renderer* r, const hala_rt_build_options* options);
 

@@ -66,7 +66,7 @@ pub mod sys {
 
   /// hala_rt_build_options (include/halart.h): every field 0 = the default
   #[repr(C)] #[derive(Default, Clone, Copy)]
-  pub struct hala_rt_build_options { pub builder: u32, pub ploc_tail: u32, pub ploc_look_every: u32, pub collapse_look_every: u32, pub instancing: u32, pub texture_bundles: u32, pub reserved: [u32; 2] }
+  pub struct hala_rt_build_options { pub builder: u32, pub ploc_tail: u32, pub ploc_look_every: u32, pub collapse_look_every: u32, pub instancing: u32, pub texture_bundles: u32, pub instance_levels: u32, pub reserved: [u32; 1] }
   /// hala_temporal_params (include/halart.h, docs/RENDER_SPEC.md 16; 32 B): fill it with hala_temporal_default_params
   #[repr(C)] #[derive(Default, Clone, Copy)]
   pub struct hala_temporal_params { pub max_history: f32, pub tol: f32, pub min_weight: f32, pub reserved: [u32; 5] }
