@@ -149,6 +149,7 @@ __host__ __device__
 inline uint32_t bundle_texel_index(uint32_t x, uint32_t y, uint32_t w) { return (((y >> 1) * ((w + 1u) >> 1) + (x >> 1)) << 2) + ((y & 1u) << 1) + (x & 1u); }
 inline uint32_t bundle_level_lines(uint32_t w, uint32_t h) { return ((w + 1u) >> 1) * ((h + 1u) >> 1); }
 
+constexpr float kRebaseK = 16.0f;  // RENDER_SPEC 4.2: an origin beyond K x the scene's largest absolute coordinate is re-based (a power of two)
 // What every kernel of one update() sees (the "descriptor sets" of src/rt_renderer.rs:141-209, :671-745 as
 // plain device pointers).
 struct SceneView {
@@ -188,7 +189,10 @@ struct SceneView {
   uint32_t scatter_media;     // 1: some material holds a scattering medium (RENDER_SPEC 7.1f): the SCATTER shade kernels apply
   uint32_t simple_materials;  // 1: every material is an untextured, opaque DIFFUSE one without a medium (the SIMPLE shade kernels apply)
   float ray_eps;
-  uint32_t staged;  // 1: the whole BVH fits the LDS budget (lds_nodes == node_count, lds_tris == tri_count) and is staged per workgroup
+  // RENDER_SPEC 4.2, far origins: the unpadded scene box, kRebaseK x its largest absolute coordinate (the amax of the builders' box pad)
+  // and the float length of its diagonal — what ray setup re-bases a far origin with (traverse.h: rebase_ray)
+  float box_min[3], box_max[3], far_limit, box_diag;
+  uint32_t staged;// 1: the whole BVH fits the LDS budget (lds_nodes == node_count, lds_tris == tri_count) and is staged per workgroup
 };
 
 // Shading kinds: what decides most of k_shade's control flow.  Bounce paths reach the shade kernel in arbitrary order; inside a

@@ -246,23 +246,33 @@ RT_DI float view_pixel_spread(const FrameConst& fc, uint32_t slot) {
   const uint32_t q = slot / fc.pixel_slots;
   return fc.view_table[q % fc.views].pixel_spread;
 }
-template <bool VIEWS>
+// FAR: a camera ray may start beyond the scene's far limit (RENDER_SPEC 4.2; the host decides from the camera records): every ray is
+// tested and, if far, re-based as it is set up; the distance it was moved travels with the lane and comes back on the hit's t.  A
+// separate variant: the kernels of every other frame stay as they are, to the register.
+template <bool FAR> struct CameraPayload {};
+template <> struct CameraPayload<true> { float ts; };
+template <bool VIEWS, bool FAR>
 struct CameraSource {
-  struct Payload {};
+  typedef CameraPayload<FAR> Payload;
   const FrameConst& fc;
   const SceneView& sv;
   hala_hit* hits;
   bool streaming;
-  RT_DI bool load(uint32_t i, f3* o, f3* d, float* tmin, float* tmax, uint32_t*, Payload*) const {
+  RT_DI bool load(uint32_t i, f3* o, f3* d, float* tmin, float* tmax, uint32_t*, Payload* p) const {
     uint32_t rng;
     *tmin = 0.0f; *tmax = kTMax;
-    if (primary_ray<VIEWS>(fc, sv, i, o, d, &rng)) return true;
+    if (primary_ray<VIEWS>(fc, sv, i, o, d, &rng)) {
+      if constexpr (FAR) p->ts = rebase_ray(sv, *o, *d, *tmin, *tmax);
+      return true;
+    }
     reinterpret_cast<float4*>(hits)[i] = make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(kAbsent));  // padding slot: no ray
     return false;
   }
-  RT_DI void done(uint32_t i, const Trav& t, const Payload&) const {
+  RT_DI void done(uint32_t i, const Trav& t, const Payload& p) const {
     const bool found = t.best.prim != kAbsent;
-    const float4 out = found ? make_float4(t.best.t, t.best.u, t.best.v, __uint_as_float(t.best.prim)) : make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(kAbsent));
+    float bt = t.best.t;
+    if constexpr (FAR) bt += p.ts;
+    const float4 out = found ? make_float4(bt, t.best.u, t.best.v, __uint_as_float(t.best.prim)) : make_float4(-1.0f, 0.0f, 0.0f, __uint_as_float(kAbsent));
     if (streaming) st4(reinterpret_cast<float4*>(hits) + i, out);
     else reinterpret_cast<float4*>(hits)[i] = out;
   }
@@ -344,7 +354,7 @@ k_trace_batch(SceneView sv, const hala_ray* __restrict__ rays, hala_hit* __restr
 
 // K5a at depth 0: the camera rays are generated in the lanes that trace them (RENDER_SPEC §5) — no ray-generation kernel,
 // no primary-ray queue in HBM; entry i of the hit queue belongs to path slot i.  `n_account` = real (non-padding) paths.  VIEWS: fc.views > 1.
-template <bool COUNT, bool STAGED, bool INST, bool VIEWS>
+template <bool COUNT, bool STAGED, bool INST, bool VIEWS, bool FAR>
 __global__ void __launch_bounds__(kTraverseThreads, STAGED ? kTraverseWavesPerSimdStaged : kTraverseWavesPerSimd)
 k_trace_primary(SceneView sv, FrameConst fc, hala_hit* __restrict__ hits, WorkCounters* __restrict__ work, uint2* __restrict__ spill_base,
                 Control* __restrict__ ctl, uint32_t n_account, uint32_t refill) {
@@ -352,7 +362,7 @@ k_trace_primary(SceneView sv, FrameConst fc, hala_hit* __restrict__ hits, WorkCo
   uint2* spill = spill_base ? spill_base + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * kStackSpill : nullptr;
   StepCounters sc;
   if (blockIdx.x == 0 && threadIdx.x == 0) ctl->totals.rays_closest += n_account;
-  CameraSource<VIEWS> src{fc, sv, hits, STAGED && refill == 64u};
+  CameraSource<VIEWS, FAR> src{fc, sv, hits, STAGED && refill == 64u};
   persistent_trace<false, COUNT, STAGED, false, INST>(sv, lds, spill, work, fc.slot_count, refill, src, sc);
   if (COUNT) flush_counters(ctl, 0, sc);
 }
@@ -952,15 +962,45 @@ bool launch_trace_shadow_then_batch(const LaunchCfg& lc, const SceneView& sv, co
 }
 
 void launch_trace_primary(const LaunchCfg& lc, const SceneView& sv, const FrameConst& fc, hala_hit* hits, WorkCounters* work, Control* ctl,
-                          uint32_t n_account, bool count, hipStream_t s) {
+                          uint32_t n_account, bool count, bool far_camera, hipStream_t s) {
   const TreeForm tree = tree_form(sv);
   // camera rays of neighbouring pixels are about equally long: larger refills (40 idle lanes instead of 24) keep the 8 x 8 pixel blocks together
   const uint32_t refill = tree == TreeForm::Staged ? lc.refill : std::max(lc.refill, 40u);
-  with_flags([&](auto COUNT, auto STAGED, auto INST, auto VIEWS) {
+  with_flags([&](auto COUNT, auto STAGED, auto INST, auto VIEWS, auto FAR) {
     if constexpr (!(STAGED && INST))
-      hipLaunchKernelGGL((k_trace_primary<COUNT, STAGED, INST, VIEWS>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, fc, hits, work,
+      hipLaunchKernelGGL((k_trace_primary<COUNT, STAGED, INST, VIEWS, FAR>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, fc, hits, work,
                          lc.spill, ctl, n_account, refill);
-  }, count, tree == TreeForm::Staged, tree == TreeForm::TwoLevel, fc.views > 1u);
+  }, count, tree == TreeForm::Staged, tree == TreeForm::TwoLevel, fc.views > 1u, far_camera);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// RENDER_SPEC 4.2, far origins, for a caller's ray batch: the rule runs at the batch's entry and exit, around the traversal launch, not
+// inside it.  Entry: a copy of the batch with every far origin re-based, and per ray the distance it was moved; exit (closest hit):
+// that distance back on the hit's t.  A batch without far origins is copied as it is and gets +0 on every t: the same bits.
+// ---------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_rebase_batch(SceneView sv, const hala_ray* __restrict__ rays, hala_ray* __restrict__ out, float* __restrict__ moved, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4* rp = reinterpret_cast<const float4*>(rays + i);
+  const float4 ro = rp[0], rd = rp[1];
+  f3 o = mk3(ro.x, ro.y, ro.z);
+  const f3 d = mk3(rd.x, rd.y, rd.z);
+  float tmin = ro.w, tmax = rd.w;
+  moved[i] = rebase_ray(sv, o, d, tmin, tmax);
+  float4* op = reinterpret_cast<float4*>(out + i);
+  op[0] = make_float4(o.x, o.y, o.z, tmin); op[1] = make_float4(rd.x, rd.y, rd.z, tmax);
+}
+__global__ void __launch_bounds__(256) k_unbase_hits(hala_hit* __restrict__ hits, const float* __restrict__ moved, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float* t = reinterpret_cast<float*>(hits + i);
+  if (reinterpret_cast<const uint32_t*>(t)[3] != kAbsent) *t = *t + moved[i];
+}
+void launch_rebase_batch(const SceneView& sv, const hala_ray* rays, hala_ray* out, float* moved, uint32_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_rebase_batch, dim3(blocks_for(n, 256)), dim3(256), 0, s, sv, rays, out, moved, n);
+}
+void launch_unbase_hits(hala_hit* hits, const float* moved, uint32_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_unbase_hits, dim3(blocks_for(n, 256)), dim3(256), 0, s, hits, moved, n);
 }
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s) {
   const uint32_t threads = sv.simple_materials ? (uint32_t)kShadeThreads : (uint32_t)kShadeThreadsGeneric;

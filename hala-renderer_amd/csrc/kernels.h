@@ -35,7 +35,10 @@ void launch_trace_shadow(const LaunchCfg& lc, const SceneView& sv, const Queues&
 bool launch_trace_shadow_then_batch(const LaunchCfg& lc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth,
                                     uint32_t kinds /* bit 0 light, bit 1 environment connections */, bool with_closest, hipStream_t s);
 void launch_trace_primary(const LaunchCfg& lc, const SceneView& sv, const FrameConst& fc, hala_hit* hits, WorkCounters* work, Control* ctl,
-                          uint32_t n_account /* real paths among fc.slot_count */, bool count, hipStream_t s);
+                          uint32_t n_account /* real paths among fc.slot_count */, bool count, bool far_camera /* RENDER_SPEC 4.2 */, hipStream_t s);
+// RENDER_SPEC 4.2 around a caller's batch: out = the batch with far origins re-based, moved[i] = how far; then moved[i] back on the closest hits' t
+void launch_rebase_batch(const SceneView& sv, const hala_ray* rays, hala_ray* out, float* moved, uint32_t n, hipStream_t s);
+void launch_unbase_hits(hala_hit* hits, const float* moved, uint32_t n, hipStream_t s);
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s);
 // pos / ids: the first-hit AOV images of RENDER_SPEC §13 (nullptr: off; both off: the kernel variant without them).  group_images: the
 // light-group images of §14, group g at group_images + g * group_stride (read only while ps.groups is set: the GROUPS variants)

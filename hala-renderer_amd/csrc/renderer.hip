@@ -342,7 +342,17 @@ struct UpdatePlan {
   uint32_t primary_pixels = 0;  // camera rays per frame, all views
   bool timed = false;           // the update carries per-launch timing events
   FrameConst fc{}; SceneView sv{};  // (fc.u: the uniform)
+  bool far_camera = false;      // RENDER_SPEC 4.2: a camera ray of some view may start beyond the scene's far limit
 };
+// RENDER_SPEC 4.2: can a ray of this camera (§5: the position, moved over the lens or the orthographic window) start beyond `far_limit`?
+// A bound, not the test: the camera-ray kernel built for far cameras tests every ray itself; the ordinary one tests none.
+static bool camera_may_be_far(const hala_gpu_camera& c, float far_limit) {
+  const float m = std::max({std::fabs(c.position[0]), std::fabs(c.position[1]), std::fabs(c.position[2])});
+  const float len = std::max(std::sqrt(c.right[0] * c.right[0] + c.right[1] * c.right[1] + c.right[2] * c.right[2]),
+                             std::sqrt(c.up[0] * c.up[0] + c.up[1] * c.up[1] + c.up[2] * c.up[2]));
+  const float window = std::fabs(c.aperture_or_ymag) + (c.type == 0u ? 0.0f : std::fabs(c.focal_distance_or_xmag));
+  return !((m + 2.0f * window * len) * 1.001f <= far_limit);  // (a NaN anywhere: far)
+}
 // where begin_update put the update: its entry of the statistics ring, its frame slot and what a launch on that slot takes
 struct SlotRun {
   TraceEvents* te; int slot; hipStream_t stream; Control* ctl; Queues q; PathState ps; LaunchCfg lc;
@@ -417,6 +427,7 @@ static int prepare_update(hala_rt_renderer* r, uint32_t frames, UpdatePlan* p) {
   p->primary_pixels = (ad.enabled ? ad.active_pixels : r->real_pixels) * V;
   p->fc = r->frame_const(u, samples);
   p->sv = r->view();
+  for (uint32_t v = 0; v < V; ++v) p->far_camera = p->far_camera || camera_may_be_far(r->hs.cameras[r->views[v]], p->sv.far_limit);
   // per-launch HIP events (statistics: traverse_*_ms_total) on every launch_event_period-th update; each record is a barrier
   // packet on the stream, i.e. a few microseconds between two launches
   p->timed = r->launch_event_period == 1u || (r->launch_event_period > 1u && (r->update_counter % r->launch_event_period) == 0u);
@@ -480,7 +491,7 @@ static int issue_bounces(hala_rt_renderer* r, const UpdatePlan& p, const SlotRun
     if (timed) { hipEvent_t a = next_event(te); RT_HIP(hipEventRecord(a, s)); }
     // depth 0: the camera rays are generated inside the traversal kernel, there is no ray-generation pass
     if (depth == 0) {
-      launch_trace_primary(run.lc, p.sv, p.fc, run.q.hits, &ctl->work_closest, ctl, p.primary_pixels * p.samples, r->counting, s);
+      launch_trace_primary(run.lc, p.sv, p.fc, run.q.hits, &ctl->work_closest, ctl, p.primary_pixels * p.samples, r->counting, p.far_camera, s);
       if (r->counting) RT_HIP(hipMemcpyAsync(ctl->totals.primary_steps, ctl->totals.steps[0], 16, hipMemcpyDeviceToDevice, s));
       if (run.before_end) RT_HIP(hipStreamWaitEvent(s, run.before_end, 0));
     }

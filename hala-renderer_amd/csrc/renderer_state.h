@@ -433,6 +433,9 @@ struct hala_rt_renderer {
   RigState rig;                // RENDER_SPEC 19: the rig whose bindings are deformers here (hala_rt_set_rig)
   DeviceArray<Control> d_ctl;  // one per frame slot
   DeviceArray<WorkCounters> d_batch_work;
+  // hala_rt_trace_rays, RENDER_SPEC 4.2: the caller's batch with far origins re-based, and how far each was moved (grown on demand)
+  DeviceArray<hala_ray> d_batch_rays;
+  DeviceArray<float> d_batch_moved;
 
   uint64_t total_frames = 0;
   bool counting = false;
@@ -486,6 +489,16 @@ struct hala_rt_renderer {
     sv.node_count = bvh.node_count; sv.tri_count = bvh.tri_count; sv.lds_nodes = lds_nodes; sv.lds_tris = lds_tris;
     sv.inst_refs = d_inst_refs.ptr; sv.inst_info = d_inst_info.ptr; sv.instance_count = (uint32_t)hs.instances.size(); sv.two_level = two_level ? 1u : 0u;
     sv.ray_eps = ray_eps;
+    {  // RENDER_SPEC 4.2, far origins: from the bounds as they stand (a refit moves them, and the builders' pad with them)
+      float amax = 0.0f;
+      for (int k = 0; k < 3; ++k) {
+        sv.box_min[k] = bvh.scene_min[k]; sv.box_max[k] = bvh.scene_max[k];
+        amax = std::max(amax, std::max(std::fabs(bvh.scene_min[k]), std::fabs(bvh.scene_max[k])));
+      }
+      const float ex = bvh.scene_max[0] - bvh.scene_min[0], ey = bvh.scene_max[1] - bvh.scene_min[1], ez = bvh.scene_max[2] - bvh.scene_min[2];
+      sv.far_limit = kRebaseK * amax;
+      sv.box_diag = std::sqrt(std::fmaf(ez, ez, std::fmaf(ey, ey, ex * ex)));
+    }
     sv.staged = staged ? 1u : 0u;
     return sv;
   }

@@ -16,7 +16,13 @@ int hala_rt_trace_rays(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_
   RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
   // counters: the kernel accumulates into the control block's 64-bit fields; copy them out if requested
   if (d_counters) RT_HIP(hipMemsetAsync(&r->d_ctl.ptr->totals.steps[mode][0], 0, 16, s));
-  launch_trace_batch(r->lcfg, r->view(), d_rays, d_hits, nullptr, count, r->d_batch_work.ptr, r->d_ctl.ptr, mode == 1, d_counters != nullptr, false, s);
+  // RENDER_SPEC 4.2: far origins are re-based where the batch enters, and the distance comes back on the closest hits where it leaves —
+  // the traversal launch in between sees ordinary rays.  (Growing the copy frees the old one, which waits for whoever still reads it.)
+  if (r->d_batch_rays.count < count) { RT_HIP(r->d_batch_rays.resize(count)); RT_HIP(r->d_batch_moved.resize(count)); }
+  const SceneView sv = r->view();
+  launch_rebase_batch(sv, d_rays, r->d_batch_rays.ptr, r->d_batch_moved.ptr, count, s);
+  launch_trace_batch(r->lcfg, sv, r->d_batch_rays.ptr, d_hits, nullptr, count, r->d_batch_work.ptr, r->d_ctl.ptr, mode == 1, d_counters != nullptr, false, s);
+  if (mode == 0) launch_unbase_hits(d_hits, r->d_batch_moved.ptr, count, s);
   if (d_counters) RT_HIP(hipMemcpyAsync(d_counters, &r->d_ctl.ptr->totals.steps[mode][0], 16, hipMemcpyDeviceToDevice, s));
   if (!r->scratch.batch_done) RT_HIP(hipEventCreateWithFlags(&r->scratch.batch_done, hipEventDisableTiming));
   RT_HIP(hipEventRecord(r->scratch.batch_done, s));

@@ -101,6 +101,25 @@ RT_DI RayPre make_ray(f3 o, f3 d, float tmin) {
   r.ood = r.o * r.idir;
   return r;
 }
+// RENDER_SPEC §4.2, far origins: a world-space ray whose origin lies beyond kRebaseK x the scene's largest absolute coordinate is moved
+// along itself to within one scene diagonal of the scene box before it is set up — the slab and triangle tests round at ulp(origin),
+// which the builders' box pad (2^-19 of the SCENE's largest coordinate) cannot cover out there.  Returns ts, the distance moved, which
+// the caller adds to a reported hit's t; 0 for every other ray, whose (o, tmin, tmax) stay as they are.  Ray setup only: nothing of
+// this reaches trav_step, and the rays the renderer starts on surfaces (bounces, connections) lie inside the box: never far.
+RT_DI float rebase_ray(const SceneView& sv, f3& o, const f3& d, float& tmin, float& tmax) {
+  if (!(hw_maxf(hw_maxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z)) > sv.far_limit)) return 0.0f;
+  const f3 idir = mk3(safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
+  const f3 ood = o * idir;
+  const float x0 = __fmaf_rn(sv.box_min[0], idir.x, -ood.x), x1 = __fmaf_rn(sv.box_max[0], idir.x, -ood.x);
+  const float y0 = __fmaf_rn(sv.box_min[1], idir.y, -ood.y), y1 = __fmaf_rn(sv.box_max[1], idir.y, -ood.y);
+  const float z0 = __fmaf_rn(sv.box_min[2], idir.z, -ood.z), z1 = __fmaf_rn(sv.box_max[2], idir.z, -ood.z);
+  const float tn = hw_maxf(hw_maxf(hw_minf(x0, x1), hw_minf(y0, y1)), hw_maxf(hw_minf(z0, z1), 0.0f));
+  const float ts = hw_maxf(tn - sv.box_diag, 0.0f);
+  o = madd3(d, ts, o);
+  tmin = hw_maxf(tmin - ts, 0.0f);
+  tmax = tmax - ts;
+  return ts;
+}
 // §4.2 Möller–Trumbore, straight-line: the same operations in the same order as the early-out form of the spec (an accepted hit
 // has the same t, u, v bit for bit; a rejected one is rejected by the same comparisons, evaluated at the end).  No branch sits
 // between the three 16-B loads of the triangle and their uses, so the loads leave together — with early-outs hipcc sank the load of

@@ -802,7 +802,10 @@ typedef struct hala_hit {
  * step counters, the traversal-stack spill area) that update() uses too, so all update / trace_rays launches of ONE
  * renderer are serialised on the device: a call on another stream first makes that stream wait (hipStreamWaitEvent)
  * for the previous such launch, wherever it ran, and records an event behind its own.  Calls may come from one host
- * thread at a time (the reference's renderer is !Send / !Sync too). */
+ * thread at a time (the reference's renderer is !Send / !Sync too).
+ * Far origins (RENDER_SPEC 4.2): a ray that starts beyond 16x the scene's largest absolute coordinate is traced from a point within one
+ * scene diagonal of the scene box, and its hit carries the distance from the origin as given; the batch itself is not written to (the
+ * renderer keeps a re-based copy of `count` rays, 36 B each). */
 int hala_rt_trace_rays(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_hits, uint32_t count,
                        int mode, uint64_t* d_counters, void* hip_stream);
 /* trace_rays_indirect (src/raytracing_program.rs:338-340): d_indirect points at a device-resident

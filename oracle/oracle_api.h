@@ -158,6 +158,12 @@ void orc_scene_use_bvh4_two_level(orc_scene* s, const void* nodes64, uint32_t no
                                   const void* refs64, uint32_t ref_count);
 void orc_trace_rays_on_bvh4_two_level(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const void* refs64,
                                       const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters);
+/* ... of a scene with the bounds bounds6 (min, max: orc_scene_bounds): far origins are re-based before traversal (RENDER_SPEC 4.2), as
+ * orc_trace_rays and orc_trace_rays_brute do with their scene's bounds.  refs64 NULL: a one-level tree. */
+void orc_trace_rays_on_bvh4_in_bounds(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const void* refs64,
+                                      const float* bounds6, const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters);
+/* test-only probe: 0 switches the re-basing of far origins off in every oracle entry point (to measure what the rule changes), 1 on again */
+void orc_probe_set_rebase(int on);
 int orc_validate_bvh4_two_level(const orc_scene* s, const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count,
                                 const void* refs64, uint32_t ref_count, uint32_t* max_depth);
 /* scenes created from now on: 0 = instanced primitives are intersected in object space (RENDER_SPEC 4.5; hala_rt_build_options::instancing

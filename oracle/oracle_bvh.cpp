@@ -352,6 +352,38 @@ static inline RayPre make_ray(V3 o, V3 d, float tmin) {
   r.ood = r.o * r.idir;
   return r;
 }
+// RENDER_SPEC §4.2, far origins: an origin more than K times the scene's largest absolute coordinate away from the world origin is moved
+// along the ray to within one scene diagonal of the (unpadded) scene box before anything else looks at the ray; the distance comes
+// back on the reported hit.  Everything that takes a world-space ray goes through this: both traversals, brute force, orc_render.
+struct Rebase { float mn[3], mx[3], far_limit, diag; bool on; };
+static int g_rebase_off = 0;  // test-only probe (orc_probe_set_rebase): what the rule changes is measured against a run without it
+static constexpr float kRebaseK = 16.0f;  // (hala_types.h has the product's)
+static inline Rebase rebase_of(const float* mn, const float* mx) {
+  Rebase rb;
+  float amax = 0.0f;
+  for (int k = 0; k < 3; ++k) { rb.mn[k] = mn[k]; rb.mx[k] = mx[k]; amax = std::max(amax, std::max(std::fabs(mn[k]), std::fabs(mx[k]))); }
+  const V3 ext = v3(mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2]);
+  rb.far_limit = kRebaseK * amax; rb.diag = sqrtf(dot3(ext, ext)); rb.on = !g_rebase_off;
+  return rb;
+}
+static inline float hw_minf(float a, float b);
+static inline float hw_maxf(float a, float b);
+// moves (o, tmin, tmax) and returns ts, the distance moved (0: the ray stays as it is, bit for bit)
+static inline float rebase_ray(const Rebase* rb, V3* o, V3 d, float* tmin, float* tmax) {
+  if (!rb || !rb->on) return 0.0f;
+  if (!(hw_maxf(hw_maxf(fabsf(o->x), fabsf(o->y)), fabsf(o->z)) > rb->far_limit)) return 0.0f;
+  const V3 idir = v3(safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
+  const V3 ood = *o * idir;
+  const float x0 = fmaf(rb->mn[0], idir.x, -ood.x), x1 = fmaf(rb->mx[0], idir.x, -ood.x);
+  const float y0 = fmaf(rb->mn[1], idir.y, -ood.y), y1 = fmaf(rb->mx[1], idir.y, -ood.y);
+  const float z0 = fmaf(rb->mn[2], idir.z, -ood.z), z1 = fmaf(rb->mx[2], idir.z, -ood.z);
+  const float tn = hw_maxf(hw_maxf(hw_minf(x0, x1), hw_minf(y0, y1)), hw_maxf(hw_minf(z0, z1), 0.0f));
+  const float ts = hw_maxf(tn - rb->diag, 0.0f);
+  *o = madd3(d, ts, *o);
+  *tmin = hw_maxf(*tmin - ts, 0.0f);
+  *tmax = *tmax - ts;
+  return ts;
+}
 // returns true and the entry distance if the (padded) slab interval is non-empty against [tmin, tlimit]
 static inline bool box_test(const RayPre& r, const float* mn, const float* mx, float tlimit, float* tnear) {
   float x0 = fmaf(mn[0], r.idir.x, -r.ood.x), x1 = fmaf(mx[0], r.idir.x, -r.ood.x);
@@ -605,13 +637,19 @@ static inline bool traverse4(const Node4* nodes, const Tri* tris, bool small_tre
   }
 }
 
+static inline Rebase scene_rebase(const orc_scene* s) { return rebase_of(s->bounds_min, s->bounds_max); }
 Hit trace_closest(const orc_scene* s, const Node* nodes, const Tri* tris, V3 o, V3 d, float tmin, float tmax, Counters* c) {
+  const Rebase rb = scene_rebase(s);
+  const float ts = rebase_ray(&rb, &o, d, &tmin, &tmax);
   RayPre r = make_ray(o, d, tmin);
   Hit h;
   if (!traverse<false>(s, nodes, tris, r, tmax, nullptr, &h, c)) { h.t = -1.0f; h.u = 0.0f; h.v = 0.0f; h.prim = ORC_NONE; }
+  else h.t += ts;
   return h;
 }
 bool trace_any(const orc_scene* s, const Node* nodes, const Tri* tris, V3 o, V3 d, float tmin, float tmax, AnyCtx* ax, Counters* c) {
+  const Rebase rb = scene_rebase(s);
+  rebase_ray(&rb, &o, d, &tmin, &tmax);
   RayPre r = make_ray(o, d, tmin);
   Hit h;
   return traverse<true>(s, nodes, tris, r, tmax, ax, &h, c);
@@ -620,9 +658,12 @@ bool trace_any(const orc_scene* s, const Node* nodes, const Tri* tris, V3 o, V3 
 static inline bool ext_small(const orc_scene* s) { return s->ext_refs.empty() && is_small_tree(s->ext_nodes.size(), s->ext_tris.size()); }
 Hit scene_trace_closest(const orc_scene* s, V3 o, V3 d, float tmin, float tmax, Counters* c) {
   if (s->ext_nodes.empty()) return trace_closest(s, s->nodes.data(), s->tris.data(), o, d, tmin, tmax, c);
+  const Rebase rb = scene_rebase(s);
+  const float ts = rebase_ray(&rb, &o, d, &tmin, &tmax);
   RayPre r = make_ray(o, d, tmin);
   Hit h;
   if (!traverse4<false>(s->ext_nodes.data(), s->ext_tris.data(), ext_small(s), r, tmax, nullptr, &h, c, s->ext_refs.empty() ? nullptr : s->ext_refs.data())) { h.t = -1.0f; h.u = 0.0f; h.v = 0.0f; h.prim = ORC_NONE; }
+  else h.t += ts;
   return h;
 }
 // RENDER_SPEC 7.1d / 7.1g: how an any-hit ray treats the triangles of a material
@@ -653,6 +694,8 @@ bool scene_trace_any(const orc_scene* s, V3 o, V3 d, float tmin, float tmax, uin
   bool occ;
   if (s->ext_nodes.empty()) occ = trace_any(s, s->nodes.data(), (s->tris_any.empty() ? s->tris : s->tris_any).data(), o, d, tmin, tmax, &ax, c);
   else {
+    const Rebase rb = scene_rebase(s);
+    rebase_ray(&rb, &o, d, &tmin, &tmax);
     RayPre r = make_ray(o, d, tmin);
     Hit h;
     occ = traverse4<true>(s->ext_nodes.data(), (s->ext_tris_any.empty() ? s->ext_tris : s->ext_tris_any).data(), ext_small(s), r, tmax, &ax, &h, c,
@@ -719,18 +762,26 @@ static void trace_batch(const orc_scene* s, const Node* nodes, const Tri* tris, 
 extern "C" void orc_trace_rays(const orc_scene* s, const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters) {
   trace_batch(s, s->nodes.data(), (mode == 1 && !s->tris_any.empty() ? s->tris_any : s->tris).data(), rays, hits, count, mode, counters);
 }
-static void trace_rays_on_bvh4(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const InstRef* refs, const orc_ray* rays,
-                               orc_hit* hits, uint32_t count, int mode, uint64_t* counters);
+static void trace_rays_on_bvh4(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const InstRef* refs, const float* bounds6,
+                               const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters);
 extern "C" void orc_trace_rays_on_bvh4(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const orc_ray* rays,
                                        orc_hit* hits, uint32_t count, int mode, uint64_t* counters) {
-  trace_rays_on_bvh4(nodes64, node_count, tris48, tri_count, nullptr, rays, hits, count, mode, counters);
+  trace_rays_on_bvh4(nodes64, node_count, tris48, tri_count, nullptr, nullptr, rays, hits, count, mode, counters);
 }
 extern "C" void orc_trace_rays_on_bvh4_two_level(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const void* refs64,
                                                  const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters) {
-  trace_rays_on_bvh4(nodes64, node_count, tris48, tri_count, (const InstRef*)refs64, rays, hits, count, mode, counters);
+  trace_rays_on_bvh4(nodes64, node_count, tris48, tri_count, (const InstRef*)refs64, nullptr, rays, hits, count, mode, counters);
 }
-static void trace_rays_on_bvh4(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const InstRef* refs, const orc_ray* rays,
-                               orc_hit* hits, uint32_t count, int mode, uint64_t* counters) {
+// ... of a scene whose bounds (min, max: what orc_scene_bounds gives) are known: far origins are re-based (RENDER_SPEC §4.2); refs64 may be NULL
+extern "C" void orc_trace_rays_on_bvh4_in_bounds(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const void* refs64,
+                                                 const float* bounds6, const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters) {
+  trace_rays_on_bvh4(nodes64, node_count, tris48, tri_count, (const InstRef*)refs64, bounds6, rays, hits, count, mode, counters);
+}
+extern "C" void orc_probe_set_rebase(int on) { g_rebase_off = on ? 0 : 1; }
+static void trace_rays_on_bvh4(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const InstRef* refs, const float* bounds6,
+                               const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters) {
+  Rebase rb{};
+  if (bounds6) rb = rebase_of(bounds6, bounds6 + 3);
   const Node4* nodes = (const Node4*)nodes64;
   const Tri* tris = (const Tri*)tris48;
   const bool small_tree = !refs && orc::is_small_tree(node_count, tri_count);
@@ -739,13 +790,17 @@ static void trace_rays_on_bvh4(const void* nodes64, uint32_t node_count, const v
   for (int64_t i = 0; i < (int64_t)count; ++i) {
     const orc_ray& ry = rays[i];
     Counters c;
-    RayPre r = make_ray(v3(ry.origin[0], ry.origin[1], ry.origin[2]), v3(ry.direction[0], ry.direction[1], ry.direction[2]), ry.tmin);
+    V3 o = v3(ry.origin[0], ry.origin[1], ry.origin[2]);
+    const V3 d = v3(ry.direction[0], ry.direction[1], ry.direction[2]);
+    float tmin = ry.tmin, tmax = ry.tmax;
+    const float ts = rebase_ray(bounds6 ? &rb : nullptr, &o, d, &tmin, &tmax);
+    RayPre r = make_ray(o, d, tmin);
     Hit h;
     if (mode == 0) {
-      if (traverse4<false>(nodes, tris, small_tree, r, ry.tmax, nullptr, &h, &c, refs)) hits[i] = orc_hit{h.t, h.u, h.v, h.prim};
+      if (traverse4<false>(nodes, tris, small_tree, r, tmax, nullptr, &h, &c, refs)) hits[i] = orc_hit{h.t + ts, h.u, h.v, h.prim};
       else hits[i] = orc_hit{-1.0f, 0.0f, 0.0f, ORC_NONE};
     } else {
-      hits[i] = orc_hit{traverse4<true>(nodes, tris, small_tree, r, ry.tmax, nullptr, &h, &c, refs) ? 1.0f : -1.0f, 0.0f, 0.0f, ORC_NONE};
+      hits[i] = orc_hit{traverse4<true>(nodes, tris, small_tree, r, tmax, nullptr, &h, &c, refs) ? 1.0f : -1.0f, 0.0f, 0.0f, ORC_NONE};
     }
     cn += c.nodes; ct += c.tris;
   }
@@ -756,8 +811,13 @@ extern "C" void orc_trace_rays_brute(const orc_scene* s, const orc_ray* rays, or
 #pragma omp parallel for schedule(dynamic, 256)
   for (int64_t i = 0; i < (int64_t)count; ++i) {
     const orc_ray& ry = rays[i];
-    RayPre r = make_ray(v3(ry.origin[0], ry.origin[1], ry.origin[2]), v3(ry.direction[0], ry.direction[1], ry.direction[2]), ry.tmin);
-    Hit best{ry.tmax, 0.0f, 0.0f, ORC_NONE};
+    V3 o = v3(ry.origin[0], ry.origin[1], ry.origin[2]);
+    const V3 d = v3(ry.direction[0], ry.direction[1], ry.direction[2]);
+    float tmin = ry.tmin, tmax = ry.tmax;
+    const Rebase rb = scene_rebase(s);
+    const float ts = rebase_ray(&rb, &o, d, &tmin, &tmax);
+    RayPre r = make_ray(o, d, tmin);
+    Hit best{tmax, 0.0f, 0.0f, ORC_NONE};
     bool any = false;
     RayCtx rc{s, r, r};
     for (const Tri& tr : s->tris_by_id) {
@@ -767,13 +827,13 @@ extern "C" void orc_trace_rays_brute(const orc_scene* s, const orc_ray* rays, or
         const int k = orc::any_class(s, s->instances[s->tri_instance[tr.id]].material_index);
         Tri flagged = tr; flagged.pad1 = k == 2 ? 1u : (k == 3 ? 2u : (k == 4 ? 3u : 0u));
         AnyCtx ax{s, pcg_hash((uint32_t)i ^ kAnyKeyBatch), {0u, 0u, 0u}};
-        if (t > r.tmin && t < ry.tmax && k != 1 && any_hit_event(&ax, flagged, t, 1.0f, u, v)) { any = true; break; }
+        if (t > r.tmin && t < tmax && k != 1 && any_hit_event(&ax, flagged, t, 1.0f, u, v)) { any = true; break; }
       }
       else if (t > r.tmin && (t < best.t || (t == best.t && tr.id < best.prim))) best = Hit{t, u, v, tr.id};
     }
     if (mode == 1) hits[i] = orc_hit{any ? 1.0f : -1.0f, 0.0f, 0.0f, ORC_NONE};
     else if (best.prim == ORC_NONE) hits[i] = orc_hit{-1.0f, 0.0f, 0.0f, ORC_NONE};
-    else hits[i] = orc_hit{best.t, best.u, best.v, best.prim};
+    else hits[i] = orc_hit{best.t + ts, best.u, best.v, best.prim};
   }
 }
 

@@ -263,10 +263,26 @@ def set_instancing(on=False):
     lib().orc_set_instancing_off(C.c_int(0 if on else 1))
 
 
-def trace_on_bvh(nodes_u32, tris_u32, rays, mode=0, refs_u32=None):
+def set_rebase(on=True):
+    """test-only probe: off = no oracle entry point re-bases far origins (RENDER_SPEC 4.2), to measure what the rule changes"""
+    lib().orc_probe_set_rebase(C.c_int(1 if on else 0))
+
+
+def trace_on_bvh(nodes_u32, tris_u32, rays, mode=0, refs_u32=None, bounds=None):
+    """bounds: (min, max) of the scene the tree belongs to (OracleScene.bounds()) — far origins are then re-based as RENDER_SPEC 4.2
+    says; None: rays are traced as given (the same thing for origins within 16x the scene's largest coordinate)"""
     rays = np.ascontiguousarray(rays, dtype=A.RAY_DTYPE)
     hits = np.empty(rays.shape[0], dtype=A.HIT_DTYPE)
     ctr = (C.c_uint64 * 2)(0, 0)
+    if bounds is not None:
+        b6 = np.ascontiguousarray(np.concatenate([bounds[0], bounds[1]]), dtype=np.float32)
+        two = refs_u32 is not None and len(refs_u32)
+        if two:
+            refs_u32 = np.ascontiguousarray(refs_u32)
+        lib().orc_trace_rays_on_bvh4_in_bounds(C.c_void_p(nodes_u32.ctypes.data), C.c_uint32(nodes_u32.size // 16), C.c_void_p(tris_u32.ctypes.data),
+                                               C.c_uint32(tris_u32.size // 12), C.c_void_p(refs_u32.ctypes.data if two else 0), fptr(b6),
+                                               C.c_void_p(rays.ctypes.data), C.c_void_p(hits.ctypes.data), C.c_uint32(rays.shape[0]), C.c_int(mode), ctr)
+        return hits, (ctr[0], ctr[1])
     if refs_u32 is not None and len(refs_u32):  # two-level tree (RENDER_SPEC 4.5)
         refs_u32 = np.ascontiguousarray(refs_u32)
         lib().orc_trace_rays_on_bvh4_two_level(C.c_void_p(nodes_u32.ctypes.data), C.c_uint32(nodes_u32.size // 16), C.c_void_p(tris_u32.ctypes.data),
