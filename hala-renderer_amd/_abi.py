@@ -349,7 +349,18 @@ PROTOTYPES = {
     "hala_rt_get_rig_pose": ([C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                               C.POINTER(C.c_float)], C.c_int),
     "hala_rt_get_rig_status": ([C.c_void_p, C.POINTER(RigStatus)], C.c_int),
+    "hala_rt_variant_ledger": ([C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int], C.c_int),
 }
+
+# hala_rt_variant_ledger: the kernel families in the order of its `family`, each with its flags, first flag = bit 0 of a combination's index
+VARIANT_FAMILIES = [
+    ("k_trace_primary", ("COUNT", "STAGED", "INST", "VIEWS", "FAR")),
+    ("k_trace_batch", ("ANY", "COUNT", "ALPHA", "STAGED", "INST")),
+    ("k_trace_shadow", ("COUNT", "ALPHA", "STAGED", "INST", "GROUPS")),
+    ("k_trace_shadow_then_batch", ("ALPHA", "STAGED", "INST", "GROUPS")),
+    ("k_shade", ("PRIMARY", "SIMPLE", "SCATTER", "AOV", "GROUPS")),
+    ("k_resolve", ("AOV", "GROUPS")),
+]
 
 
 # numpy dtypes of the batch records
@@ -399,4 +410,5 @@ EXPORTS = [
     "hala_rt_set_vertex_keys",
     "hala_scene_get_rig", "hala_rig_sample_clip", "hala_rt_set_rig", "hala_rt_pose_rig", "hala_rt_key_rig", "hala_rt_get_rig_pose",
     "hala_rt_get_rig_status",
+    "hala_rt_variant_ledger",
 ]

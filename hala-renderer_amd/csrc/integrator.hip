@@ -8,7 +8,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
+#include <utility>
 
 #include "kernels.h"
 #include "shading.h"
@@ -896,6 +898,47 @@ static void with_flags(F&& f, bool flag, Flags... flags) {
   else with_flags([&](auto... c) { f(std::false_type{}, c...); }, flags...);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The variant ledger (hala_rt_variant_ledger): which instantiations of the six flag-dispatched kernel families exist and which of them
+// this process has launched.  Host bookkeeping only.  One predicate per family says which flag combinations a kernel is built for, in the
+// launcher's with_flags order; the launcher's `if constexpr` and the family's `built` mask both come from it.  Bit index of a combination:
+// its flags read as a binary number, first flag least significant.
+// ---------------------------------------------------------------------------------------------------------
+constexpr bool trace_primary_built(bool /*COUNT*/, bool STAGED, bool INST, bool /*VIEWS*/, bool /*FAR*/) { return !(STAGED && INST); }
+constexpr bool trace_batch_built(bool ANY, bool /*COUNT*/, bool ALPHA, bool STAGED, bool INST) { return (ANY || !ALPHA) && !(STAGED && INST); }
+constexpr bool trace_shadow_built(bool /*COUNT*/, bool /*ALPHA*/, bool STAGED, bool INST, bool /*GROUPS*/) { return !(STAGED && INST); }
+constexpr bool trace_shadow_then_batch_built(bool /*ALPHA*/, bool STAGED, bool INST, bool /*GROUPS*/) { return !(STAGED && INST); }
+constexpr bool shade_built(bool PRIMARY, bool SIMPLE, bool SCATTER, bool AOV, bool /*GROUPS*/) { return !(SIMPLE && SCATTER) && (PRIMARY || !AOV); }
+constexpr bool resolve_built(bool /*AOV*/, bool /*GROUPS*/) { return true; }
+
+// the family's `built` mask, by the enumeration the launchers dispatch with
+template <auto Built, size_t... I>
+static uint64_t built_mask(std::index_sequence<I...>) {
+  uint64_t mask = 0;
+  for (uint32_t i = 0; i < (1u << sizeof...(I)); ++i)
+    with_flags([&](auto... c) { if constexpr (Built(c...)) mask |= 1ull << i; }, (((i >> I) & 1u) != 0u)...);
+  return mask;
+}
+static std::atomic<uint64_t> g_launched[kVariantFamilies];
+
+template <class... Flags>
+static void note_launch(uint32_t family, Flags... flags) {  // the with_flags constants of the launch, in order
+  uint64_t index = 0, bit = 1;
+  ((index |= flags ? bit : 0, bit <<= 1), ...);
+  g_launched[family].fetch_or(1ull << index, std::memory_order_relaxed);
+}
+bool variant_ledger(uint32_t family, uint64_t* launched, uint64_t* built, bool reset) {
+  static const uint64_t all[kVariantFamilies] = {
+      built_mask<trace_primary_built>(std::make_index_sequence<5>{}), built_mask<trace_batch_built>(std::make_index_sequence<5>{}),
+      built_mask<trace_shadow_built>(std::make_index_sequence<5>{}),  built_mask<trace_shadow_then_batch_built>(std::make_index_sequence<4>{}),
+      built_mask<shade_built>(std::make_index_sequence<5>{}),         built_mask<resolve_built>(std::make_index_sequence<2>{})};
+  if (family >= kVariantFamilies) return false;
+  const uint64_t seen = reset ? g_launched[family].exchange(0, std::memory_order_relaxed) : g_launched[family].load(std::memory_order_relaxed);
+  if (launched) *launched = seen;
+  if (built) *built = all[family];
+  return true;
+}
+
 uint32_t traverse_stack_lds_levels(TreeForm tree) {
   return tree == TreeForm::Staged ? kStackLdsStaged : (tree == TreeForm::TwoLevel ? kStackLdsInst : kStackLdsGlobal);
 }
@@ -927,9 +970,11 @@ void launch_trace_batch(const LaunchCfg& lc, const SceneView& sv, const hala_ray
   if (any) sva.tris = sv.tris_any;  // RENDER_SPEC 7.1d
   const TreeForm tree = tree_form(sv);
   with_flags([&](auto ANY, auto COUNT, auto ALPHA, auto STAGED, auto INST) {
-    if constexpr ((ANY || !ALPHA) && !(STAGED && INST))
+    if constexpr (trace_batch_built(ANY, COUNT, ALPHA, STAGED, INST)) {
+      note_launch(kFamilyTraceBatch, ANY, COUNT, ALPHA, STAGED, INST);
       hipLaunchKernelGGL((k_trace_batch<ANY, COUNT, STAGED, ALPHA, INST>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sva, rays,
                          hits, n_ptr, n_imm, work, lc.spill, ctl, account ? 1 : 0, lc.refill);
+    }
   }, any, count, any && sv.any_translucent, tree == TreeForm::Staged, tree == TreeForm::TwoLevel);
 }
 
@@ -940,9 +985,11 @@ void launch_trace_shadow(const LaunchCfg& lc, const SceneView& sv0, const Queues
   const TreeForm tree = tree_form(sv);
   // light groups (RENDER_SPEC §14): only the light connections carry a group
   with_flags([&](auto COUNT, auto ALPHA, auto STAGED, auto INST, auto GROUPS) {
-    if constexpr (!(STAGED && INST))
+    if constexpr (trace_shadow_built(COUNT, ALPHA, STAGED, INST, GROUPS)) {
+      note_launch(kFamilyTraceShadow, COUNT, ALPHA, STAGED, INST, GROUPS);
       hipLaunchKernelGGL((k_trace_shadow<COUNT, STAGED, ALPHA, INST, GROUPS>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, q, ps,
                          ctl, depth, kind, lc.spill, lc.refill);
+    }
   }, count, sv.any_translucent != 0u, tree == TreeForm::Staged, tree == TreeForm::TwoLevel, kind == 0u && ps.groups != nullptr);
 }
 
@@ -954,9 +1001,11 @@ bool launch_trace_shadow_then_batch(const LaunchCfg& lc, const SceneView& sv, co
   if (tree == TreeForm::Staged && sv.tris_any != sv.tris) return false;
   const hala_ray* rays = with_closest ? q.rays[(depth + 1u) & 1u] : nullptr;
   with_flags([&](auto ALPHA, auto STAGED, auto INST, auto GROUPS) {
-    if constexpr (!(STAGED && INST))
+    if constexpr (trace_shadow_then_batch_built(ALPHA, STAGED, INST, GROUPS)) {
+      note_launch(kFamilyTraceShadowThenBatch, ALPHA, STAGED, INST, GROUPS);
       hipLaunchKernelGGL((k_trace_shadow_then_batch<STAGED, ALPHA, INST, GROUPS>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv,
                          sv.tris_any, q, ps, ctl, depth, kinds, rays, q.hits, lc.spill, lc.refill);
+    }
   }, sv.any_translucent != 0u, tree == TreeForm::Staged, tree == TreeForm::TwoLevel, (kinds & 1u) != 0u && ps.groups != nullptr);
   return true;
 }
@@ -967,9 +1016,11 @@ void launch_trace_primary(const LaunchCfg& lc, const SceneView& sv, const FrameC
   // camera rays of neighbouring pixels are about equally long: larger refills (40 idle lanes instead of 24) keep the 8 x 8 pixel blocks together
   const uint32_t refill = tree == TreeForm::Staged ? lc.refill : std::max(lc.refill, 40u);
   with_flags([&](auto COUNT, auto STAGED, auto INST, auto VIEWS, auto FAR) {
-    if constexpr (!(STAGED && INST))
+    if constexpr (trace_primary_built(COUNT, STAGED, INST, VIEWS, FAR)) {
+      note_launch(kFamilyTracePrimary, COUNT, STAGED, INST, VIEWS, FAR);
       hipLaunchKernelGGL((k_trace_primary<COUNT, STAGED, INST, VIEWS, FAR>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, fc, hits, work,
                          lc.spill, ctl, n_account, refill);
+    }
   }, count, tree == TreeForm::Staged, tree == TreeForm::TwoLevel, fc.views > 1u, far_camera);
 }
 
@@ -1013,15 +1064,20 @@ void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, co
   }
   // the first-hit AOVs (RENDER_SPEC §13) are written by the depth-0 shade only; the light groups (§14) by every shade
   with_flags([&](auto PRIMARY, auto SIMPLE, auto SCATTER, auto AOV, auto GROUPS) {
-    if constexpr (!(SIMPLE && SCATTER) && (PRIMARY || !AOV))
+    if constexpr (shade_built(PRIMARY, SIMPLE, SCATTER, AOV, GROUPS)) {
+      note_launch(kFamilyShade, PRIMARY, SIMPLE, SCATTER, AOV, GROUPS);
       hipLaunchKernelGGL((k_shade<PRIMARY, SIMPLE, SCATTER, AOV, GROUPS>), grid, block, 0, s, fc, sv, q, ps, ctl, depth);
+    }
   }, depth == 0u, sv.simple_materials != 0u, !sv.simple_materials && sv.scatter_media, depth == 0u && (ps.aov_pos || ps.aov_ids), ps.groups != nullptr);
 }
 void launch_resolve(const FrameConst& fc, const PathState& ps, float4* accum, float4* albedo, float4* normal, float4* final_img, float4* pos,
                     uint4* ids, float4* group_images, size_t group_stride, hipStream_t s) {
   with_flags([&](auto AOV, auto GROUPS) {
-    hipLaunchKernelGGL((k_resolve<AOV, GROUPS>), dim3(blocks_for(fc.pixel_slots * fc.views, 256)), dim3(256), 0, s, fc, ps, accum, albedo, normal, final_img,
-                       pos, ids, group_images, group_stride);
+    if constexpr (resolve_built(AOV, GROUPS)) {
+      note_launch(kFamilyResolve, AOV, GROUPS);
+      hipLaunchKernelGGL((k_resolve<AOV, GROUPS>), dim3(blocks_for(fc.pixel_slots * fc.views, 256)), dim3(256), 0, s, fc, ps, accum, albedo, normal, final_img,
+                         pos, ids, group_images, group_stride);
+    }
   }, pos != nullptr || ids != nullptr, ps.groups != nullptr);
 }
 void launch_relight(const hala_global_uniform& u, const float4* group_images, size_t group_stride, uint32_t group_count, const RelightScales& sc, uint32_t n,

@@ -51,6 +51,11 @@ void launch_relight(const hala_global_uniform& u, const float4* group_images, si
 void launch_scatter_tiles(const FrameConst& fc, const float4* gathered, float4* full, hipStream_t s);
 void launch_sample_texture(const SceneView& sv, uint32_t tex, const float* uvl, uint32_t n, float4* out, hipStream_t s);
 
+// The variant ledger (hala_rt_variant_ledger): the families in the order of the entry point's `family`; the flags of each in the order of
+// its launcher's with_flags call.  false: no such family.  Per process; `reset` clears the family's launched mask after reading it.
+enum : uint32_t { kFamilyTracePrimary, kFamilyTraceBatch, kFamilyTraceShadow, kFamilyTraceShadowThenBatch, kFamilyShade, kFamilyResolve, kVariantFamilies };
+bool variant_ledger(uint32_t family, uint64_t* launched, uint64_t* built, bool reset);
+
 // texture.hip — K8: one level of the mip chain (2x2 box filter over linear RGBA32F texels)
 void launch_mip_downsample(const float4* src, uint32_t sw, uint32_t sh, float4* dst, uint32_t dw, uint32_t dh, hipStream_t s);
 // 8-bit images: row-major bytes -> 4x4-tiled level 0; tiled level l - 1 -> tiled level l (decode, box filter, encode)

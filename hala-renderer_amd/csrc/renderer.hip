@@ -687,6 +687,11 @@ int hala_rt_set_pass_fusion(hala_rt_renderer* r, uint32_t mode) {
   r->fuse_mode = mode;
   return HALA_OK;
 }
+int hala_rt_variant_ledger(uint32_t family, uint64_t* launched, uint64_t* built, int reset) {
+  if (!variant_ledger(family, launched, built, reset != 0))
+    RT_FAIL("hala_rt_variant_ledger: there is no kernel family " + std::to_string(family) + " (0 ... " + std::to_string(kVariantFamilies - 1u) + ").");
+  return HALA_OK;
+}
 int hala_rt_set_counting(hala_rt_renderer* r, int enable) {
   if (!r) RT_FAIL("The renderer handle is null!");
   r->counting = enable != 0;

@@ -829,6 +829,15 @@ def temporal_clamp_default_params(**overrides) -> A.TemporalClampParams:
     return p
 
 
+def variant_ledger(family, reset=False):
+    """hala_rt_variant_ledger -> (launched, built): bit masks over the flag combinations of kernel family `family` (_abi.VARIANT_FAMILIES:
+    the first flag is bit 0 of a combination's index); per process; reset clears `launched` after reading.  Needs no GPU."""
+    from . import check, load_library
+    launched, built = C.c_uint64(0), C.c_uint64(0)
+    check(load_library().hala_rt_variant_ledger(C.c_uint32(family), C.byref(launched), C.byref(built), C.c_int(bool(reset))))
+    return launched.value, built.value
+
+
 def denoise_images(color, albedo, normal, device_ordinal=0, **params) -> np.ndarray:
     """hala_denoise_images: the RENDER_SPEC 10 filter on host images [H, W, 3 or 4] (e.g. the PFM trio of save_images); returns the
     denoised RGBA32F [H, W, 4].  params: iterations, sigma_color, sigma_albedo, normal_power, demodulate."""

@@ -673,6 +673,20 @@ int hala_rt_set_launch_timing_period(hala_rt_renderer* r, uint32_t period);
  * keep one launch per pass so that every measured launch is one kernel symbol with the chip to itself; 2: always — timed updates then
  * fill the traverse_fused_* statistics.  Counting updates (hala_rt_set_counting) never fuse.  Images do not depend on the mode. */
 int hala_rt_set_pass_fusion(hala_rt_renderer* r, uint32_t mode);
+/* The variant ledger.  The traversal, shade and resolve kernels are compiled once per combination of launch-time flags; the library
+ * notes on the host which combinations it has launched, so that a test suite can tell which of the compiled kernels it ran.
+ * family and its flags, first flag = bit 0 of a combination's index:
+ *   0 k_trace_primary            COUNT, STAGED, INST, VIEWS, FAR
+ *   1 k_trace_batch              ANY, COUNT, ALPHA, STAGED, INST
+ *   2 k_trace_shadow             COUNT, ALPHA, STAGED, INST, GROUPS
+ *   3 k_trace_shadow_then_batch  ALPHA, STAGED, INST, GROUPS
+ *   4 k_shade                    PRIMARY, SIMPLE, SCATTER, AOV, GROUPS
+ *   5 k_resolve                  AOV, GROUPS
+ * *launched: bit i is set if the kernel of combination i has been launched; *built: bit i is set if such a kernel exists (no kernel is
+ * both STAGED and INST, ALPHA needs ANY, SIMPLE has no SCATTER, AOV needs PRIMARY).  Either pointer may be null.  reset != 0 clears the
+ * family's launched bits after they were read.  The ledger is per process, not per renderer: every renderer of the process, on any
+ * thread, adds to the same bits, and no call needs a renderer or a device.  An unknown family is an error. */
+int hala_rt_variant_ledger(uint32_t family, uint64_t* launched, uint64_t* built, int reset);
 /* Frames in flight.  Consecutive updates are independent except for the order in which their samples are folded into the accumulated
  * images, so updates without per-launch timing or counting alternate between two frame slots, each with its own stream, control block,
  * stack spill area, per-path state and queues: update k + 1 starts beside the last bounces of update k (its dense camera-ray launch and

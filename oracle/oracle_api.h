@@ -158,6 +158,10 @@ void orc_scene_use_bvh4_two_level(orc_scene* s, const void* nodes64, uint32_t no
                                   const void* refs64, uint32_t ref_count);
 void orc_trace_rays_on_bvh4_two_level(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const void* refs64,
                                       const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters);
+/* orc_trace_rays on the tree orc_scene_use_bvh4(_two_level) handed over (the scene's own while there is none), walked as the integrator
+ * walks it: any-hit rays see the scene's materials (RENDER_SPEC 7.1d), so the step counts of an any-hit batch in a scene with translucent
+ * materials can be compared with the product's on the product's tree. */
+void orc_trace_rays_scene_bvh(const orc_scene* s, const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters);
 /* ... of a scene with the bounds bounds6 (min, max: orc_scene_bounds): far origins are re-based before traversal (RENDER_SPEC 4.2), as
  * orc_trace_rays and orc_trace_rays_brute do with their scene's bounds.  refs64 NULL: a one-level tree. */
 void orc_trace_rays_on_bvh4_in_bounds(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const void* refs64,

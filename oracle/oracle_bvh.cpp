@@ -762,6 +762,27 @@ static void trace_batch(const orc_scene* s, const Node* nodes, const Tri* tris, 
 extern "C" void orc_trace_rays(const orc_scene* s, const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters) {
   trace_batch(s, s->nodes.data(), (mode == 1 && !s->tris_any.empty() ? s->tris_any : s->tris).data(), rays, hits, count, mode, counters);
 }
+// ... on the tree orc_scene_use_bvh4 handed over (the scene's own while there is none), as the integrator walks it: any-hit rays see the
+// scene's materials (RENDER_SPEC 7.1d), which a tree traced on its own (orc_trace_rays_on_bvh4) cannot — the step counts of a batch of
+// any-hit rays in a scene with translucent materials are compared here
+extern "C" void orc_trace_rays_scene_bvh(const orc_scene* s, const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters) {
+  uint64_t cn = 0, ct = 0;
+#pragma omp parallel for schedule(dynamic, 4096) reduction(+ : cn, ct)
+  for (int64_t i = 0; i < (int64_t)count; ++i) {
+    const orc_ray& r = rays[i];
+    Counters c;
+    const V3 o = v3(r.origin[0], r.origin[1], r.origin[2]), d = v3(r.direction[0], r.direction[1], r.direction[2]);
+    if (mode == 0) {
+      const Hit h = orc::scene_trace_closest(s, o, d, r.tmin, r.tmax, &c);
+      hits[i].t = h.t; hits[i].u = h.u; hits[i].v = h.v; hits[i].prim = h.prim;
+    } else {
+      const bool occ = orc::scene_trace_any(s, o, d, r.tmin, r.tmax, pcg_hash((uint32_t)i ^ kAnyKeyBatch), &c, nullptr);  // the key of ray i of a batch
+      hits[i].t = occ ? 1.0f : -1.0f; hits[i].u = 0.0f; hits[i].v = 0.0f; hits[i].prim = ORC_NONE;
+    }
+    cn += c.nodes; ct += c.tris;
+  }
+  if (counters) { counters[0] += cn; counters[1] += ct; }
+}
 static void trace_rays_on_bvh4(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const InstRef* refs, const float* bounds6,
                                const orc_ray* rays, orc_hit* hits, uint32_t count, int mode, uint64_t* counters);
 extern "C" void orc_trace_rays_on_bvh4(const void* nodes64, uint32_t node_count, const void* tris48, uint32_t tri_count, const orc_ray* rays,

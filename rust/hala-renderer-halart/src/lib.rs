@@ -140,6 +140,7 @@ pub mod sys {
     pub fn hala_rt_get_stream(r: *mut hala_rt_renderer, hip_stream: *mut *mut c_void) -> c_int;
     pub fn hala_rt_set_launch_timing_period(r: *mut hala_rt_renderer, period: u32) -> c_int;
     pub fn hala_rt_set_pass_fusion(r: *mut hala_rt_renderer, mode: u32) -> c_int;
+    pub fn hala_rt_variant_ledger(family: u32, launched: *mut u64, built: *mut u64, reset: c_int) -> c_int;
     pub fn hala_rt_set_frames_in_flight(r: *mut hala_rt_renderer, n: u32) -> c_int;
     pub fn hala_rt_frames_in_flight_info(r: *mut hala_rt_renderer, second_slot_updates: *mut u64, second_buffers: *mut u32) -> c_int;
     pub fn hala_rt_set_build_options(r: *mut hala_rt_renderer, options: *const hala_rt_build_options) -> c_int;

@@ -216,6 +216,15 @@ class OracleScene:
         lib().orc_trace_rays(self._h, C.c_void_p(rays.ctypes.data), C.c_void_p(hits.ctypes.data), C.c_uint32(rays.shape[0]), C.c_int(mode), ctr)
         return (hits, (ctr[0], ctr[1])) if count_steps else hits
 
+    def trace_on_used_bvh(self, rays, mode=0):
+        """(hits, (nodes visited, triangles tested)) on the tree use_bvh handed over, walked as render() walks it: any-hit rays see the
+        scene's materials (RENDER_SPEC 7.1d), which trace_on_bvh — a tree without its scene — cannot"""
+        rays = np.ascontiguousarray(rays, dtype=A.RAY_DTYPE)
+        hits = np.empty(rays.shape[0], dtype=A.HIT_DTYPE)
+        ctr = (C.c_uint64 * 2)(0, 0)
+        lib().orc_trace_rays_scene_bvh(self._h, C.c_void_p(rays.ctypes.data), C.c_void_p(hits.ctypes.data), C.c_uint32(rays.shape[0]), C.c_int(mode), ctr)
+        return hits, (ctr[0], ctr[1])
+
     def texture_info(self, tex):
         w, h, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
         assert lib().orc_scene_texture_info(self._h, C.c_uint32(tex), C.byref(w), C.byref(h), C.byref(m)) == 0
