@@ -350,6 +350,8 @@ PROTOTYPES = {
                               C.POINTER(C.c_float)], C.c_int),
     "hala_rt_get_rig_status": ([C.c_void_p, C.POINTER(RigStatus)], C.c_int),
     "hala_rt_variant_ledger": ([C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int], C.c_int),
+    "hala_rt_selftest_math": ([C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)], C.c_int),
+    "hala_rt_selftest_math_values": ([C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)], C.c_int),
 }
 
 # hala_rt_variant_ledger: the kernel families in the order of its `family`, each with its flags, first flag = bit 0 of a combination's index
@@ -411,4 +413,5 @@ EXPORTS = [
     "hala_scene_get_rig", "hala_rig_sample_clip", "hala_rt_set_rig", "hala_rt_pose_rig", "hala_rt_key_rig", "hala_rt_get_rig_pose",
     "hala_rt_get_rig_status",
     "hala_rt_variant_ledger",
+    "hala_rt_selftest_math", "hala_rt_selftest_math_values",
 ]

@@ -584,7 +584,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
     if (hit_light >= 0) {
       const f3 le = ld3(sv.lights[hit_light].intensity);
       float w = 1.0f;
-      if (!PRIMARY) w = power_heuristic(prev_pdf, light_pdf * (1.0f / (float)nl));
+      if (!PRIMARY) w = power_heuristic(prev_pdf, light_pdf * rcp_rn((float)nl));
       L = L + T * le * w;
       if (GROUPS) gL = ps.light_group[hit_light];
       if (PRIMARY) {
@@ -683,7 +683,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
             f3 contrib;
             if (ls.delta) contrib = fb * ls.le * (cosl * (float)nl);
             else {
-              const float pl = ls.pdf * (1.0f / (float)nl);
+              const float pl = ls.pdf * rcp_rn((float)nl);
               const float w = power_heuristic(pl, pdf_b);
               contrib = fb * ls.le * (cosl * w / pl);
             }
@@ -734,7 +734,7 @@ __global__ void __launch_bounds__(SIMPLE ? kShadeThreads : kShadeThreadsGeneric,
         if (depth >= fc.u.rr_depth) {
           const float qq = minf(max3f(T), 0.95f);
           const float rr = rng_next(rng);
-          if (!(rr < qq)) alive = false; else T = T * (1.0f / qq);
+          if (!(rr < qq)) alive = false; else T = T * rcp_rn(qq);
         }
         if (depth + 1u >= fc.u.max_depth) alive = false;
         keep[0] = alive;

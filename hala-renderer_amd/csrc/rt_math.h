@@ -25,6 +25,38 @@ RT_DI f3 operator*(f3 a, f3 b) { return f3{a.x * b.x, a.y * b.y, a.z * b.z}; }
 RT_DI f3 operator*(f3 a, float s) { return f3{a.x * s, a.y * s, a.z * s}; }
 RT_DI f3 operator-(f3 a) { return f3{-a.x, -a.y, -a.z}; }
 
+// 1.0f / x and sqrtf(x), bit for bit, in fewer issue slots.  hipcc's correctly rounded `/` is a dozen vector instructions (two
+// v_div_scale, v_rcp_f32, a chain of fma, v_div_fmas, v_div_fixup); one Newton step on v_rcp_f32, with the residual taken by an fma, already
+// rounds correctly wherever x, 1/x and the residual stay normal.  That is decided by enumeration, not by argument:
+// hala_rt_selftest_math runs all 2^32 inputs through the helper and through the plain expression (tests/test_exact_math.py), and
+// profiles/exact_math.txt holds the sweep of the unguarded forms from which the windows below were read.  Inputs outside the window
+// (zeros, denormals, infinities, NaNs, quotients that are denormal) take the plain expression, behind a branch that a wave skips unless
+// one of its lanes needs it.
+//
+// rcp_rn: the unguarded form differs from 1.0f / x for biased exponents 0, 253 (all but +-2^126), 254 and for +-inf, and for no other
+// input, all-ones mantissas included: the window is 2^-126 <= |x| < 2^126.  The shift drops the sign; one unsigned compare tests both ends.
+// v_rcp_f32 counted double, the fast path is 6 issue slots (v_rcp_f32, v_lshl_add_u32, v_cmp_gt_u32, two fma) against 12.
+RT_DI float rcp_rn(float x) {
+  const float r0 = __builtin_amdgcn_rcpf(x);
+  const float e = __fmaf_rn(-x, r0, 1.0f);
+  float r = __fmaf_rn(e, r0, r0);
+  if (__builtin_expect(((__float_as_uint(x) << 1) - 0x01000000u) >= 0xfc000000u, 0)) r = 1.0f / x;
+  return r;
+}
+// sqrt_rn: y = v_rsq_f32(x), g = x y, then one step on the residual x - g g (exact in the fma) with slope y / 2.  The unguarded form
+// differs from sqrtf(x) for biased exponents 0 ... 24 (the residual, about 2^-24 x, leaves the normal range), for +inf, and for no other
+// input (negative inputs give NaN on both sides); the window starts a little above that, at 2^-95, and ends below +inf: one subtraction
+// and one unsigned compare, which negative inputs fail as well.  8 issue slots against the 17 of hipcc's correctly rounded sqrtf.
+RT_DI float sqrt_rn(float x) {
+  const float y = __builtin_amdgcn_rsqf(x);
+  const float g = x * y;
+  const float h = 0.5f * y;
+  const float d = __fmaf_rn(-g, g, x);
+  float s = __fmaf_rn(d, h, g);
+  if (__builtin_expect((__float_as_uint(x) - 0x10000000u) >= 0x6f800000u, 0)) s = sqrtf(x);
+  return s;
+}
+
 // §2.1
 RT_DI float dot3(f3 a, f3 b) { return __fmaf_rn(a.z, b.z, __fmaf_rn(a.y, b.y, a.x * b.x)); }
 RT_DI f3 cross3(f3 a, f3 b) {
@@ -32,7 +64,7 @@ RT_DI f3 cross3(f3 a, f3 b) {
 }
 RT_DI f3 madd3(f3 d, float t, f3 o) { return f3{__fmaf_rn(d.x, t, o.x), __fmaf_rn(d.y, t, o.y), __fmaf_rn(d.z, t, o.z)}; }
 RT_DI f3 normalize3(f3 a) {
-  float inv = 1.0f / sqrtf(dot3(a, a));
+  float inv = rcp_rn(sqrt_rn(dot3(a, a)));
   return a * inv;
 }
 RT_DI float maxf(float a, float b) { return a > b ? a : b; }
@@ -128,7 +160,7 @@ RT_DI float acos_poly(float x) {
   p = __fmaf_rn(p, ax, 0.0889789874f);
   p = __fmaf_rn(p, ax, -0.2145988016f);
   p = __fmaf_rn(p, ax, 1.5707963050f);
-  float r = sqrtf(1.0f - ax) * p;
+  float r = sqrt_rn(1.0f - ax) * p;
   return x < 0.0f ? kPi - r : r;
 }
 RT_DI float atan_poly01(float z) {
@@ -182,10 +214,10 @@ RT_DI f3 to_world(f3 l, f3 t, f3 b, f3 n) {
             __fmaf_rn(n.z, l.z, __fmaf_rn(b.z, l.y, t.z * l.x))};
 }
 RT_DI f3 cosine_hemisphere(float u1, float u2) {
-  float r = sqrtf(u1);
+  float r = sqrt_rn(u1);
   float s, c;
   sincos_2pi(u2, &s, &c);
-  return f3{r * c, r * s, sqrtf(maxf(0.0f, 1.0f - u1))};
+  return f3{r * c, r * s, sqrt_rn(maxf(0.0f, 1.0f - u1))};
 }
 // Henyey-Greenstein direction around the unit vector d (RENDER_SPEC §7.1f)
 RT_DI f3 hg_sample(f3 d, float g, float u1, float u2) {
@@ -197,7 +229,7 @@ RT_DI f3 hg_sample(f3 d, float g, float u1, float u2) {
     ct = ((1.0f + g * g) - q * q) / (2.0f * g);
   }
   ct = minf(maxf(ct, -1.0f), 1.0f);
-  const float st = sqrtf(maxf(0.0f, 1.0f - ct * ct));
+  const float st = sqrt_rn(maxf(0.0f, 1.0f - ct * ct));
   float s, c;
   sincos_2pi(u2, &s, &c);
   f3 t, b;
@@ -211,7 +243,7 @@ RT_DI float hg_phase(float g, float c) {
   c = minf(maxf(c, -1.0f), 1.0f);
   const float g2 = g * g;
   const float x = (1.0f + g2) - (2.0f * g) * c;
-  return (1.0f - g2) / (12.566370614359172f * (x * sqrtf(x)));
+  return (1.0f - g2) / (12.566370614359172f * (x * sqrt_rn(x)));
 }
 RT_DI float luminance(f3 c) { return 0.212671f * c.x + 0.715160f * c.y + 0.072169f * c.z; }
 RT_DI float power_heuristic(float a, float b) {
@@ -222,7 +254,7 @@ RT_DI float power_heuristic(float a, float b) {
 // §4.3 ray preparation shared by both traversal kernels
 RT_DI float safe_inv(float d) {
   float dd = fabsf(d) < 1e-20f ? copysignf(1e-20f, d) : d;
-  return 1.0f / dd;
+  return rcp_rn(dd);
 }
 
 }  // namespace rt

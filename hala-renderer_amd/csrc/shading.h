@@ -68,7 +68,7 @@ RT_DI void camera_ray(const FrameConst& fc, const hala_gpu_camera& cam, float ta
     if (aperture > 0.0f) {
       float ft = cam.focal_distance_or_xmag / dot3(dir, fwd);
       f3 focus = madd3(dir, ft, pos);
-      float r = aperture * sqrtf(r3);
+      float r = aperture * sqrt_rn(r3);
       float s, c;
       sincos_2pi(r4, &s, &c);
       f3 org = madd3(up, r * s, madd3(right, r * c, pos));
@@ -125,7 +125,7 @@ RT_DI float env_map_pdf(const FrameConst& fc, const SceneView& sv, f3 d) {
   int ix = wrapi((int)floorf(uu * (float)W), W);
   int iy = min((int)(vv * (float)H), H - 1);
   float lum = luminance(env_texel(sv, W, ix, iy));
-  float st = sqrtf(maxf(0.0f, 1.0f - d.y * d.y));
+  float st = sqrt_rn(maxf(0.0f, 1.0f - d.y * d.y));
   if (!(st > 0.0f) || !(lum > 0.0f)) return 0.0f;
   return (lum * (float)(fc.u.env_map_width * fc.u.env_map_height)) / (fc.u.env_total_sum * kTwoPiSq * st);
 }
@@ -185,26 +185,26 @@ RT_DI float mixf(float a, float b, float t) { return a * (1.0f - t) + b * t; }
 RT_DI float ggx_d(f3 h, float ax, float ay) {
   float hx = h.x / ax, hy = h.y / ay;
   float k = hx * hx + hy * hy + h.z * h.z;
-  return 1.0f / (kPi * ax * ay * k * k);
+  return rcp_rn(kPi * ax * ay * k * k);
 }
 RT_DI float ggx_g1(f3 w, float ax, float ay) {
   float a = ax * w.x, b = ay * w.y;
   float l = (a * a + b * b) / (w.z * w.z);
-  return 2.0f / (1.0f + sqrtf(1.0f + l));
+  return 2.0f / (1.0f + sqrt_rn(1.0f + l));
 }
 RT_DI f3 ggx_sample_vndf(f3 v, float ax, float ay, float r1, float r2) {
   f3 vh = normalize3(mk3(ax * v.x, ay * v.y, v.z));
   float lensq = vh.x * vh.x + vh.y * vh.y;
   f3 t1 = mk3(1.0f, 0.0f, 0.0f);
-  if (lensq > 0.0f) { float il = 1.0f / sqrtf(lensq); t1 = mk3(-vh.y * il, vh.x * il, 0.0f); }
+  if (lensq > 0.0f) { float il = rcp_rn(sqrt_rn(lensq)); t1 = mk3(-vh.y * il, vh.x * il, 0.0f); }
   f3 t2 = cross3(vh, t1);
-  float r = sqrtf(r1);
+  float r = sqrt_rn(r1);
   float s, c;
   sincos_2pi(r2, &s, &c);
   float a = r * c, b = r * s;
   float sn = 0.5f * (1.0f + vh.z);
-  b = (1.0f - sn) * sqrtf(maxf(0.0f, 1.0f - a * a)) + sn * b;
-  float cz = sqrtf(maxf(0.0f, 1.0f - a * a - b * b));
+  b = (1.0f - sn) * sqrt_rn(maxf(0.0f, 1.0f - a * a)) + sn * b;
+  float cz = sqrt_rn(maxf(0.0f, 1.0f - a * a - b * b));
   f3 nh = t1 * a + t2 * b + vh * cz;
   return normalize3(mk3(ax * nh.x, ay * nh.y, maxf(0.0f, nh.z)));
 }
@@ -217,7 +217,7 @@ struct DisneyLobes {
 RT_DI float fresnel_dielectric(float c, float eta) {
   float g2 = eta * eta - 1.0f + c * c;
   if (!(g2 > 0.0f)) return 1.0f;  // total internal reflection
-  float g = sqrtf(g2);
+  float g = sqrt_rn(g2);
   float a = (g - c) / (g + c);
   float b = (c * (g + c) - 1.0f) / (c * (g - c) + 1.0f);
   return 0.5f * a * a * (1.0f + b * b);
@@ -225,7 +225,7 @@ RT_DI float fresnel_dielectric(float c, float eta) {
 RT_DI DisneyLobes disney_lobes(const MatView& m, float nv) {
   DisneyLobes d;
   float lb = luminance(m.base);
-  f3 tint = lb > 0.0f ? m.base * (1.0f / lb) : splat3(1.0f);
+  f3 tint = lb > 0.0f ? m.base * rcp_rn(lb) : splat3(1.0f);
   float f0 = (m.ior - 1.0f) / (m.ior + 1.0f);
   f0 = f0 * f0;
   d.cspec0 = mix3(mix3(splat3(1.0f), tint, m.specular_tint) * f0, m.base, m.metallic);
@@ -243,7 +243,7 @@ RT_DI DisneyLobes disney_lobes(const MatView& m, float nv) {
   }
   float sum = wd + ws + wc + wt;
   if (!(sum > 0.0f)) { d.pd = d.ps = d.pc = d.pt = 0.0f; return d; }
-  float inv = 1.0f / sum;
+  float inv = rcp_rn(sum);
   d.pd = wd * inv; d.ps = ws * inv; d.pc = wc * inv; d.pt = wt * inv;
   return d;
 }
@@ -282,7 +282,7 @@ RT_DI void disney_eval(const MatView& m, const BsdfCtx& c, f3 wi, f3 n, f3* f, f
     f3 h = lo + li * m.eta;
     float h2 = dot3(h, h);
     if (!(h2 > 0.0f)) return;
-    h = h * (1.0f / sqrtf(h2));
+    h = h * rcp_rn(sqrt_rn(h2));
     if (h.z < 0.0f) h = -h;
     float odh = dot3(lo, h), idh = dot3(li, h);
     if (!(odh > 0.0f && idh < 0.0f)) return;  // both directions must see the front / the back of the same facet
@@ -292,7 +292,7 @@ RT_DI void disney_eval(const MatView& m, const BsdfCtx& c, f3 wi, f3 n, f3* f, f
     float den = odh + m.eta * idh;
     float jac = m.eta * m.eta * (-idh) / (den * den);  // |dh/dwi|
     float w = m.trans * (1.0f - fr) * ds * g1o * g1i * odh * jac / (-nl * nv);
-    *f = mk3(sqrtf(m.base.x), sqrtf(m.base.y), sqrtf(m.base.z)) * w;
+    *f = mk3(sqrt_rn(m.base.x), sqrt_rn(m.base.y), sqrt_rn(m.base.z)) * w;
     *pdf = d.pt * (g1o * odh * ds / nv) * jac;
     return;
   }
@@ -300,7 +300,7 @@ RT_DI void disney_eval(const MatView& m, const BsdfCtx& c, f3 wi, f3 n, f3* f, f
   f3 h = normalize3(lo + li);
   float ldh = dot3(li, h);
   float fl = schlick5(nl), fv = c.fv, fh = schlick5(ldh);
-  float fd90 = 0.5f + 2.0f * sqrtf(m.roughness) * ldh * ldh;
+  float fd90 = 0.5f + 2.0f * sqrt_rn(m.roughness) * ldh * ldh;
   float fd = mixf(1.0f, fd90, fl) * mixf(1.0f, fd90, fv);
   float dw = (1.0f - m.metallic) * (1.0f - m.trans);
   f3 fs = mix3(d.cspec0, splat3(1.0f), fh);
@@ -315,7 +315,7 @@ RT_DI void disney_eval(const MatView& m, const BsdfCtx& c, f3 wi, f3 n, f3* f, f
   float fc = mixf(0.04f, 1.0f, fh);
   fr = fr + splat3(0.25f * m.clearcoat * fc * dc * c1o * c1i / denom);
   *f = fr;
-  float inv4nv = 1.0f / (4.0f * nv);
+  float inv4nv = rcp_rn(4.0f * nv);
   *pdf = d.pd * (nl * kInvPi) + d.ps * (g1o * ds * inv4nv) + d.pc * (c1o * dc * inv4nv);
 }
 
@@ -341,10 +341,10 @@ RT_DI bool bsdf_sample(const MatView& m, const BsdfCtx& c, f3 wo, f3 n, float r1
       f3 lo = c.lo;
       f3 h = ggx_sample_vndf(lo, m.ax, m.ay, r1, r2);
       float cc = dot3(lo, h);
-      float ie = 1.0f / m.eta;
+      float ie = rcp_rn(m.eta);
       float k = 1.0f - (1.0f - cc * cc) * (ie * ie);
       if (!(k > 0.0f)) { *f = splat3(0.0f); *pdf = 0.0f; return false; }
-      f3 li = h * (cc * ie - sqrtf(k)) - lo * ie;
+      f3 li = h * (cc * ie - sqrt_rn(k)) - lo * ie;
       *wi = to_world(li, t, b, n);
     } else {
       bool spec = r3 < d.pd + d.ps;
@@ -378,10 +378,10 @@ RT_DI LightSample sample_light(const hala_gpu_light& l, f3 P, float r1, float r2
     f3 to = pos - P;
     float d2 = dot3(to, to);
     if (!(d2 > 0.0f)) return s;
-    float dist = sqrtf(d2);
-    s.wi = to * (1.0f / dist);
+    float dist = sqrt_rn(d2);
+    s.wi = to * rcp_rn(dist);
     s.dist = dist;
-    s.le = inten * (1.0f / d2);
+    s.le = inten * rcp_rn(d2);
     if (l.type == 2u) {
       f3 axis = normalize3(ld3(l.u));
       float cosang = -dot3(s.wi, axis);
@@ -398,7 +398,7 @@ RT_DI LightSample sample_light(const hala_gpu_light& l, f3 P, float r1, float r2
     if (cosmax >= 1.0f) s.wi = axis;
     else {
       float ct = 1.0f - r1 * (1.0f - cosmax);
-      float st = sqrtf(maxf(0.0f, 1.0f - ct * ct));
+      float st = sqrt_rn(maxf(0.0f, 1.0f - ct * ct));
       float sp, cp;
       sincos_2pi(r2, &sp, &cp);
       f3 t, b;
@@ -415,14 +415,14 @@ RT_DI LightSample sample_light(const hala_gpu_light& l, f3 P, float r1, float r2
     f3 to = pt - P;
     float d2 = dot3(to, to);
     if (!(d2 > 0.0f)) return s;
-    float dist = sqrtf(d2);
-    s.wi = to * (1.0f / dist);
+    float dist = sqrt_rn(d2);
+    s.wi = to * rcp_rn(dist);
     float cosl = -dot3(s.wi, n);
     if (!(cosl > 0.0f)) return s;
     s.dist = dist; s.le = inten; s.pdf = d2 / (l.area * cosl); s.delta = false; s.valid = true;
   } else if (l.type == 4u) {  // SPHERE
     float z = 1.0f - 2.0f * r1;
-    float rr = sqrtf(maxf(0.0f, 1.0f - z * z));
+    float rr = sqrt_rn(maxf(0.0f, 1.0f - z * z));
     float sp, cp;
     sincos_2pi(r2, &sp, &cp);
     f3 nl = mk3(rr * cp, rr * sp, z);
@@ -430,8 +430,8 @@ RT_DI LightSample sample_light(const hala_gpu_light& l, f3 P, float r1, float r2
     f3 to = pt - P;
     float d2 = dot3(to, to);
     if (!(d2 > 0.0f)) return s;
-    float dist = sqrtf(d2);
-    s.wi = to * (1.0f / dist);
+    float dist = sqrt_rn(d2);
+    s.wi = to * rcp_rn(dist);
     float cosl = -dot3(s.wi, nl);
     if (!(cosl > 0.0f)) return s;
     s.dist = dist; s.le = inten; s.pdf = d2 / (l.area * cosl); s.delta = false; s.valid = true;
@@ -460,9 +460,9 @@ RT_DI float intersect_light(const hala_gpu_light& l, f3 o, f3 d, float* pdf) {
     float c = dot3(oc, oc) - l.radius * l.radius;
     float disc = b * b - c;
     if (!(disc > 0.0f)) return -1.0f;
-    float t = -b - sqrtf(disc);
+    float t = -b - sqrt_rn(disc);
     if (!(t > 0.0f)) return -1.0f;
-    f3 nl = (madd3(d, t, o) - pos) * (1.0f / l.radius);
+    f3 nl = (madd3(d, t, o) - pos) * rcp_rn(l.radius);
     float cosl = -dot3(d, nl);
     if (!(cosl > 0.0f)) return -1.0f;
     *pdf = (t * t) / (l.area * cosl);
@@ -735,7 +735,7 @@ RT_DI Surface make_surface(const SceneView& sv, LUT lut, float pixel_spread, f3 
     const float du1 = b.tex_coord[0] - a.tex_coord[0], dv1 = b.tex_coord[1] - a.tex_coord[1];
     const float du2 = c.tex_coord[0] - a.tex_coord[0], dv2 = c.tex_coord[1] - a.tex_coord[1];
     const float uv_area = fabsf(du1 * dv2 - dv1 * du2);
-    const float world_area = sqrtf(dot3(gcross, gcross));
+    const float world_area = sqrt_rn(dot3(gcross, gcross));
     const float cosi = maxf(fabsf(dot3(d, sf.ng)), 0.1f);
     const float foot = t * pixel_spread / cosi;
     const float ratio = foot * foot * uv_area / world_area;
@@ -749,9 +749,9 @@ RT_DI Surface make_surface(const SceneView& sv, LUT lut, float pixel_spread, f3 
     const auto apply_mr = [&](const float4 s) {  // glTF: G = roughness, B = metallic
       sf.mat.metallic = sf.mat.metallic * s.z;
       if (m.type == 1u) {  // re-derive the packed alphas exactly like src/scene/gpu/material.rs:61-69
-        const float rl = sqrtf(m.roughness) * s.y;
+        const float rl = sqrt_rn(m.roughness) * s.y;
         const float r2 = rl * rl;
-        const float aspect = sqrtf(1.0f - clampf(m.anisotropic, 0.0f, 1.0f) * 0.9f);
+        const float aspect = sqrt_rn(1.0f - clampf(m.anisotropic, 0.0f, 1.0f) * 0.9f);
         sf.mat.roughness = r2;
         sf.mat.ax = maxf(0.001f, r2 / aspect);
         sf.mat.ay = maxf(0.001f, r2 * aspect);
@@ -764,12 +764,12 @@ RT_DI Surface make_surface(const SceneView& sv, LUT lut, float pixel_spread, f3 
       tw = tw - sf.ns * dot3(sf.ns, tw);  // Gram-Schmidt against the shading normal
       const float tl2 = dot3(tw, tw);
       if (tl2 > 0.0f) {
-        tw = tw * (1.0f / sqrtf(tl2));
+        tw = tw * rcp_rn(sqrt_rn(tl2));
         const f3 bw = cross3(sf.ns, tw);
         const f3 nts = mk3(s.x * 2.0f - 1.0f, s.y * 2.0f - 1.0f, s.z * 2.0f - 1.0f);
         const f3 nn = to_world(nts, tw, bw, sf.ns);
         const float nn2 = dot3(nn, nn);
-        if (nn2 > 0.0f) sf.ns = nn * (1.0f / sqrtf(nn2));
+        if (nn2 > 0.0f) sf.ns = nn * rcp_rn(sqrt_rn(nn2));
       }
     };
     if (bundle != kAbsent) {
@@ -817,7 +817,7 @@ RT_DI Surface make_surface(const SceneView& sv, LUT lut, float pixel_spread, f3 
   sf.sigma = 0.0f; sf.hg = 0.0f; sf.scol = splat3(1.0f);
   if (dot3(sf.ng, d) > 0.0f) {  // the path arrives from behind the surface: it is leaving the object
     sf.ns = -sf.ns; sf.ng = -sf.ng;
-    sf.mat.eta = 1.0f / sf.mat.ior;
+    sf.mat.eta = rcp_rn(sf.mat.ior);
     // §7.1e: the segment ran through the object's medium (closed, non-nested objects: no per-path medium state needed)
     const float dt = m.medium_density * t;
     if (SIMPLE) {

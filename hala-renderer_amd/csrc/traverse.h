@@ -128,7 +128,7 @@ RT_DI bool tri_test_od(f3 o, f3 d, float4 a, float4 b, float4 c, float* t, float
   const f3 e1 = mk3(b.x, b.y, b.z), e2 = mk3(c.x, c.y, c.z);
   const f3 p = cross3(d, e2);
   const float det = dot3(e1, p);
-  const float inv = 1.0f / det;
+  const float inv = rcp_rn(det);
   const f3 tv = o - mk3(a.x, a.y, a.z);
   const float uu = dot3(tv, p) * inv;
   const f3 q = cross3(tv, e1);
@@ -191,7 +191,7 @@ RT_DI void tri_test2(const RayPre& r, float4 a0, float4 b0, float4 c0, float4 a1
   // p = cross3(d, e2)
   const v2f px = pk_fma(dy, e2z, -(dz * e2y)), py = pk_fma(dz, e2x, -(dx * e2z)), pz = pk_fma(dx, e2y, -(dy * e2x));
   const v2f det = pk_dot3(e1x, e1y, e1z, px, py, pz);
-  const v2f inv = pk2(1.0f / det.x, 1.0f / det.y);
+  const v2f inv = pk2(rcp_rn(det.x), rcp_rn(det.y));
   const v2f tvx = pk2(r.o.x, r.o.x) - pk2(a0.x, a1.x), tvy = pk2(r.o.y, r.o.y) - pk2(a0.y, a1.y), tvz = pk2(r.o.z, r.o.z) - pk2(a0.z, a1.z);
   const v2f uu = pk_dot3(tvx, tvy, tvz, px, py, pz) * inv;
   // q = cross3(tv, e1)

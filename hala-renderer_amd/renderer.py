@@ -838,6 +838,30 @@ def variant_ledger(family, reset=False):
     return launched.value, built.value
 
 
+SELFTEST_RCP, SELFTEST_SQRT = 0, 1
+
+
+def selftest_math(which, first, count):
+    """hala_rt_selftest_math -> (mismatches, first_bad): the exact-math helper `which` (SELFTEST_RCP: rcp_rn against 1.0f / x, SELFTEST_SQRT:
+    sqrt_rn against sqrtf) on the `count` consecutive binary32 bit patterns from `first`; first_bad is None when nothing differs."""
+    from . import check, load_library
+    bad, low = C.c_uint64(0), C.c_uint32(0)
+    check(load_library().hala_rt_selftest_math(C.c_int(which), C.c_uint32(first), C.c_uint64(count), C.byref(bad), C.byref(low)))
+    return bad.value, (low.value if bad.value else None)
+
+
+def selftest_math_values(which, patterns):
+    """hala_rt_selftest_math_values -> (helper_bits, reference_bits, mismatches): what the helper and the plain IEEE expression give, as
+    uint32 bit patterns, for each of the uint32 bit patterns in `patterns`."""
+    from . import check, load_library
+    p = np.ascontiguousarray(patterns, dtype=np.uint32)
+    helper, ref = np.empty_like(p), np.empty_like(p)
+    bad = C.c_uint64(0)
+    check(load_library().hala_rt_selftest_math_values(C.c_int(which), C.c_void_p(p.ctypes.data), C.c_uint32(p.size), C.c_void_p(helper.ctypes.data),
+                                                      C.c_void_p(ref.ctypes.data), C.byref(bad), None))
+    return helper, ref, bad.value
+
+
 def denoise_images(color, albedo, normal, device_ordinal=0, **params) -> np.ndarray:
     """hala_denoise_images: the RENDER_SPEC 10 filter on host images [H, W, 3 or 4] (e.g. the PFM trio of save_images); returns the
     denoised RGBA32F [H, W, 4].  params: iterations, sigma_color, sigma_albedo, normal_power, demodulate."""

@@ -687,6 +687,17 @@ int hala_rt_set_pass_fusion(hala_rt_renderer* r, uint32_t mode);
  * family's launched bits after they were read.  The ledger is per process, not per renderer: every renderer of the process, on any
  * thread, adds to the same bits, and no call needs a renderer or a device.  An unknown family is an error. */
 int hala_rt_variant_ledger(uint32_t family, uint64_t* launched, uint64_t* built, int reset);
+/* Self-test of the exact-math helpers.  The kernels compute 1.0f / x and sqrtf(x) by a short sequence on the hardware's approximate
+ * reciprocal and reciprocal square root (csrc/rt_math.h rcp_rn, sqrt_rn) that must give the bits of the IEEE expression for EVERY input.
+ * which 0: the reciprocal, 1: the square root.  One kernel evaluates the helper and the plain expression for the `count` consecutive
+ * binary32 bit patterns from `first` (first + count <= 2^32; the whole sweep is 2^32 patterns, in as many calls as the caller likes) and
+ * returns through *mismatches how many patterns differ (two NaNs count as equal) and through *first_bad the lowest differing pattern,
+ * 0xffffffff if there is none.  Either pointer may be null.  Runs on the calling thread's current device and needs no renderer.
+ * _values: the same kernel on a list of `count` patterns in host memory (at most 2^28); it also writes, where the pointer is not null,
+ * the bits the helper and the plain expression gave for each pattern to host arrays of `count` entries. */
+int hala_rt_selftest_math(int which, uint32_t first, uint64_t count, uint64_t* mismatches, uint32_t* first_bad);
+int hala_rt_selftest_math_values(int which, const uint32_t* patterns, uint32_t count, uint32_t* helper_bits, uint32_t* reference_bits,
+                                 uint64_t* mismatches, uint32_t* first_bad);
 /* Frames in flight.  Consecutive updates are independent except for the order in which their samples are folded into the accumulated
  * images, so updates without per-launch timing or counting alternate between two frame slots, each with its own stream, control block,
  * stack spill area, per-path state and queues: update k + 1 starts beside the last bounces of update k (its dense camera-ray launch and

@@ -141,6 +141,9 @@ pub mod sys {
     pub fn hala_rt_set_launch_timing_period(r: *mut hala_rt_renderer, period: u32) -> c_int;
     pub fn hala_rt_set_pass_fusion(r: *mut hala_rt_renderer, mode: u32) -> c_int;
     pub fn hala_rt_variant_ledger(family: u32, launched: *mut u64, built: *mut u64, reset: c_int) -> c_int;
+    pub fn hala_rt_selftest_math(which: c_int, first: u32, count: u64, mismatches: *mut u64, first_bad: *mut u32) -> c_int;
+    pub fn hala_rt_selftest_math_values(which: c_int, patterns: *const u32, count: u32, helper_bits: *mut u32, reference_bits: *mut u32,
+                                        mismatches: *mut u64, first_bad: *mut u32) -> c_int;
     pub fn hala_rt_set_frames_in_flight(r: *mut hala_rt_renderer, n: u32) -> c_int;
     pub fn hala_rt_frames_in_flight_info(r: *mut hala_rt_renderer, second_slot_updates: *mut u64, second_buffers: *mut u32) -> c_int;
     pub fn hala_rt_set_build_options(r: *mut hala_rt_renderer, options: *const hala_rt_build_options) -> c_int;
