@@ -234,6 +234,14 @@ class ShutterStatus(C.Structure):  # hala_shutter_status, 32 B
                 ("reserved", C.c_uint32 * 2)]
 
 
+class NodeRefitStatus(C.Structure):  # hala_node_refit_status, 40 B (docs/RENDER_SPEC.md 20)
+    _fields_ = [("bound_nodes", C.c_uint32), ("affected_nodes", C.c_uint32), ("affected_instances", C.c_uint32), ("levels", C.c_uint32),
+                ("last_path", C.c_uint32), ("last_reason", C.c_uint32), ("device_refits", C.c_uint64), ("host_refits", C.c_uint64)]
+
+
+NODE_REFIT_PATH_NONE, NODE_REFIT_PATH_DEVICE, NODE_REFIT_PATH_HOST = 0, 1, 2
+NODE_REFIT_PENDING_EDIT, NODE_REFIT_SHUTTER_KEYS, NODE_REFIT_CAMERA_OR_LIGHT, NODE_REFIT_HOST_LEVELS, NODE_REFIT_CLASSIFICATION = 1, 2, 3, 4, 5
+
 # the rig of a glTF file (docs/RENDER_SPEC.md 19; include/halart.h "The rig of a glTF file")
 RIG_STEP, RIG_LINEAR, RIG_CUBICSPLINE = 0, 1, 2
 RIG_TRANSLATION, RIG_ROTATION, RIG_SCALE, RIG_WEIGHTS = 0, 1, 2, 3
@@ -349,6 +357,9 @@ PROTOTYPES = {
     "hala_rt_get_rig_pose": ([C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                               C.POINTER(C.c_float)], C.c_int),
     "hala_rt_get_rig_status": ([C.c_void_p, C.POINTER(RigStatus)], C.c_int),
+    "hala_rt_bind_nodes": ([C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32], C.c_int),
+    "hala_rt_refit_nodes": ([C.c_void_p, C.c_void_p, C.c_int], C.c_int),
+    "hala_rt_get_node_refit_status": ([C.c_void_p, C.POINTER(NodeRefitStatus)], C.c_int),
     "hala_rt_variant_ledger": ([C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int], C.c_int),
     "hala_rt_selftest_math": ([C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)], C.c_int),
     "hala_rt_selftest_math_values": ([C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)], C.c_int),
@@ -412,6 +423,7 @@ EXPORTS = [
     "hala_rt_set_vertex_keys",
     "hala_scene_get_rig", "hala_rig_sample_clip", "hala_rt_set_rig", "hala_rt_pose_rig", "hala_rt_key_rig", "hala_rt_get_rig_pose",
     "hala_rt_get_rig_status",
+    "hala_rt_bind_nodes", "hala_rt_refit_nodes", "hala_rt_get_node_refit_status",
     "hala_rt_variant_ledger",
     "hala_rt_selftest_math", "hala_rt_selftest_math_values",
 ]

@@ -272,6 +272,15 @@ std::string HostScene::pack(const std::vector<hala_material_desc>& fit_materials
   return "";
 }
 
+void HostScene::pack_instance_transforms() {
+  for (size_t i = 0; i < instances.size(); ++i) {
+    const float* w = nodes[instance_node[i]].world.m;
+    memcpy(instances[i].transform, w, 64);
+    float* t = &instance_3x4[12 * i];
+    for (int r = 0; r < 3; ++r) { t[4 * r] = w[r]; t[4 * r + 1] = w[4 + r]; t[4 * r + 2] = w[8 + r]; t[4 * r + 3] = w[12 + r]; }
+  }
+}
+
 void HostScene::primitive_bounds(const HostPrimitive& p, float center[3], float extents[3]) {
   // gpu_uploader.rs:460-467 + src/scene/bounds.rs:46-108 (encapsulate_point per vertex, drift and all)
   for (int i = 0; i < 3; ++i) { center[i] = p.vertices.empty() ? 0.0f : p.vertices[0].position[i]; extents[i] = 0.0f; }

@@ -70,6 +70,7 @@ struct HostScene {
   std::vector<Mat4> locals() const;              // nodes[].local
   void update_node_hierarchies(const std::vector<Mat4>& locals);  // src/scene/cpu/scene.rs:99-114; one local per node
   std::string pack(const std::vector<hala_material_desc>& fit_materials);
+  void pack_instance_transforms();  // the part of pack that follows nodes[].world alone: instances[].transform and instance_3x4
   static hala_gpu_material pack_material(const hala_material_desc& m);
   static void primitive_bounds(const HostPrimitive& p, float center[3], float extents[3]);
 };

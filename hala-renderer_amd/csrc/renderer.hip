@@ -271,6 +271,8 @@ int hala_rt_set_scene(hala_rt_renderer* r, const hala_scene_desc* scene) {
   r->deform.off();             // RENDER_SPEC §17: so do the deformers
   r->shutter.off();            // RENDER_SPEC §18: and every key, and the shutter
   r->rig.off();                // RENDER_SPEC §19: and the rig that registered deformers
+  r->nodes.release();          // RENDER_SPEC §20: and the bound node set (the host mirror is replaced whole below)
+  r->nodes_dirty = false; r->materials_dirty = false;
   const std::string e = r->hs.assign(scene);
   if (!e.empty()) RT_FAIL(e);
   if (upload_packed(r) != HALA_OK) return HALA_ERR;
@@ -327,6 +329,8 @@ int hala_rt_commit(hala_rt_renderer* r) {
   if (r->hs.instances.empty()) RT_FAIL("The scene has no mesh primitive.");  // `primitives[0]` panics in the reference (gpu_uploader.rs:888)
   RT_HIP(hipStreamSynchronize(r->stream));  // (a recommit: earlier frames may still read the bundles)
   if (update_texture_bundles(r, true) != HALA_OK) return HALA_ERR;
+  r->sync_host_mirror();
+  r->nodes.release();  // RENDER_SPEC §20: a commit drops the binding
   if (build_bvh(r) != HALA_OK) return HALA_ERR;
   r->committed = true;
   r->invalidate(Changed::Commit);
@@ -733,6 +737,7 @@ int hala_rt_get_packed_primitives(hala_rt_renderer* r, hala_gpu_mesh_data* dst, 
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (!r->has_scene || !count) RT_FAIL("The scene in GPU is none!");
   RT_READBACK(r->d_instances, hala_gpu_mesh_data, dst, capacity, count);
+  r->sync_host_mirror();
   if (t3x4) memcpy(t3x4, r->hs.instance_3x4.data(), std::min<size_t>(capacity, r->hs.instances.size()) * 12 * sizeof(float));
   return HALA_OK;
 }

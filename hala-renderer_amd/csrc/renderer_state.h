@@ -1,6 +1,6 @@
 // renderer_state.h — the renderer object behind the C ABI (struct hala_rt_renderer), shared by the host units that implement it:
 // renderer.hip (life cycle, scene, update), rt_scene.hip (uploads, trees, edits), rt_outputs.hip (views, AOVs, adaptive sampling, light
-// groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_deform.hip (deformers), rt_rig.hip (rigs and clips), rt_shutter.hip (shutter motion blur), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
+// groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_deform.hip (deformers), rt_rig.hip (rigs and clips), rt_shutter.hip (shutter motion blur), rt_nodes.hip (node batches), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
 // Each feature keeps its state in one struct that knows how to turn itself off.  What is indexed by path slot (per-path state, queues)
 // lives in the WavefrontSet of a frame slot (FrameSlots::slot[2]: two updates in flight), sized by WavefrontSet::fit to the one PathShape
 // that hala_rt_renderer::path_shape() computes: a feature with per-path state adds a field to the shape and an array to the set.
@@ -28,6 +28,7 @@
 #include "host_scene.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "node_batch.h"
 #include "rig.h"
 #include "shutter.h"
 #include "temporal.h"
@@ -310,6 +311,39 @@ struct InstanceLevels {
   void release() { arena.release(); d_items.release(); d_trees.release(); trees.clear(); items = world_item = 0; refs_on_host = true; }
 };
 
+// node batches (RENDER_SPEC §20; hala_rt_bind_nodes, hala_rt_refit_nodes): the bound set, what the bind-time analysis found, the device
+// tables of the kernels in node_batch.hip, and the two flags that keep host and device copies honest.  `mirror_stale`: a device-path call
+// moved the world transforms on the device only — HostNode::world, HostScene::instances[].transform and instance_3x4 lag behind until
+// hala_rt_renderer::sync_host_mirror recomputes them from the locals (which the call keeps current).  `tables_current`: d_locals / d_worlds
+// hold what the trees stand at; every host refit clears it (refit_geometry), the next device-path call uploads them again.  Never both stale.
+struct NodeBatchState {
+  std::vector<uint32_t> bound;          // node indices in the bound order; empty: nothing bound
+  bool analysed = false;                // the tables below belong to the trees as they stand (build_bvh clears it)
+  std::vector<uint32_t> level_first;    // [levels + 1] into d_levels
+  uint32_t affected_nodes = 0, affected_instances = 0;
+  bool moves_camera_or_light = false;   // a camera or a light hangs at or below a bound node
+  bool moves_flattened = false;         // two-level trees: an affected instance lies in the world tree
+  DeviceArray<uint32_t> d_bound, d_mismatch;
+  DeviceArray<NodeBatchNode> d_levels;
+  DeviceArray<NodeBatchInst> d_insts;
+  DeviceArray<float> d_locals, d_worlds, d_in;  // 16 floats per node / per node / per bound node (host input staged)
+  float* h_stage = nullptr;             // pinned, 16 floats per bound node: host input on its way up, device input on its way down
+  uint32_t* h_word = nullptr;           // pinned: the classification word as the call's one look found it
+  bool tables_current = false, mirror_stale = false;
+  uint32_t last_path = 0, last_reason = 0;
+  unsigned long long device_refits = 0, host_refits = 0;
+  uint32_t levels() const { return level_first.empty() ? 0u : (uint32_t)level_first.size() - 1u; }
+  void release() {  // drops the binding; the counters are the renderer's (the caller has made the host mirror current)
+    bound.clear(); analysed = false; level_first.clear(); affected_nodes = affected_instances = 0;
+    moves_camera_or_light = moves_flattened = false;
+    d_bound.release(); d_mismatch.release(); d_levels.release(); d_insts.release(); d_locals.release(); d_worlds.release(); d_in.release();
+    if (h_stage) (void)hipHostFree(h_stage);
+    if (h_word) (void)hipHostFree(h_word);
+    h_stage = nullptr; h_word = nullptr;
+    tables_current = false; mirror_stale = false;
+  }
+};
+
 enum class Changed { Commit, Refit, Views, Aovs };  // hala_rt_renderer::invalidate
 
 }  // namespace rt
@@ -431,6 +465,7 @@ struct hala_rt_renderer {
   DeformState deform;          // RENDER_SPEC 17: one deformer per primitive (hala_rt_set_deformer)
   ShutterState shutter;        // RENDER_SPEC 18: keys and shutter (hala_rt_set_shutter)
   RigState rig;                // RENDER_SPEC 19: the rig whose bindings are deformers here (hala_rt_set_rig)
+  NodeBatchState nodes;        // RENDER_SPEC 20: the bound node set (hala_rt_bind_nodes)
   DeviceArray<Control> d_ctl;  // one per frame slot
   DeviceArray<WorkCounters> d_batch_work;
   // hala_rt_trace_rays, RENDER_SPEC 4.2: the caller's batch with far origins re-based, and how far each was moved (grown on demand)
@@ -445,6 +480,9 @@ struct hala_rt_renderer {
   // recorded by the edit entry points, read and cleared by hala_rt_refit alone (a step of the shutter passes its own: RefitInputs)
   bool vertices_dirty = false;       // the vertex arena changed since the tree was fitted to it
   bool materials_dirty_any = false;  // a material edit touched an opacity-0 material (old or new)
+  bool nodes_dirty = false;          // a node's local transform was written outside hala_rt_refit_nodes (which then takes the host path)
+  bool materials_dirty = false;      // ... or a material was
+  bool build_options_dirty = false;  // hala_rt_set_build_options since the trees were built or refitted: a refit may rebuild by them
   bool any_invisible = false;   // the scene has invisible or translucent materials: the any-hit launches traverse d_tris_any (RENDER_SPEC 7.1d)
   bool any_translucent = false; // ... translucent ones: the ALPHA variants of the any-hit kernels
   DeviceArray<uint8_t> d_material_any_class;
@@ -468,6 +506,7 @@ struct hala_rt_renderer {
     }
     scratch.release();
     exchange.release();
+    nodes.release();
     // images first, then everything else (src/rt_renderer.rs:620-633)
     for (auto& i : img_local) i.release();
     for (auto& i : img_full) i.release();
@@ -565,6 +604,17 @@ struct hala_rt_renderer {
   // frames folded into the pixels that are still traced (every pixel with adaptive sampling off)
   uint32_t rendered_frames() const { return (uint32_t)std::min(total_frames, max_frames); }
 
+  // RENDER_SPEC §20: the host copies of the world transforms, made current again after device-path calls of hala_rt_refit_nodes — the
+  // hierarchy and the instance records recomputed from the locals, which is what the device computed, bit for bit.  Every reader of
+  // HostNode::world, HostScene::instances[].transform or instance_3x4 calls it first, and so does every writer of HostNode::local: the
+  // locals must still be the ones the trees stand at when it runs.
+  void sync_host_mirror() {
+    if (!nodes.mirror_stale) return;
+    hs.update_node_hierarchies(hs.locals());
+    hs.pack_instance_transforms();
+    nodes.mirror_stale = false;
+  }
+
   // What a change makes stale, feature by feature; the caller restarts the accumulation.  A new feature hooks in here.
   void invalidate(Changed c) {
     // RENDER_SPEC §15: the next update hashes the committed scene's names
@@ -614,6 +664,11 @@ struct RefitInputs {
   bool opacity0_edit;                                 // a material edit touched an opacity-0 material
 };
 int refit_geometry(hala_rt_renderer* r, const RefitInputs& in);
+// rt_scene.hip, for hala_rt_refit_nodes (rt_nodes.hip; RENDER_SPEC §20).  instancing_candidates: per instance, would classify_instances test
+// its transform.  refit_posed_on_device: the tree part of refit_geometry when d_instances (and the world tree's own instance table) were
+// posed on the device: the existing refits, the instance levels on the GPU, the traversal configuration
+void instancing_candidates(const hala_rt_renderer* r, std::vector<uint8_t>* considered);
+int refit_posed_on_device(hala_rt_renderer* r, bool world_tree_moved);
 // rt_shutter.hip (RENDER_SPEC §18).  shutter_refit: hala_rt_refit's geometry part with the recorded keys applied, the scene left at step
 // 0; shutter_step: moves the scene to step `j` between two frames of one accumulation (update_impl, while the shutter is active)
 int shutter_refit(hala_rt_renderer* r);

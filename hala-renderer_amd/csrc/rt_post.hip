@@ -97,6 +97,7 @@ static int temporal_ready(hala_rt_renderer* r, const char* fn) {
 // old one; every other resolve is the launch alone.
 static int temporal_enqueue_resolve(hala_rt_renderer* r, hipEvent_t before = nullptr) {
   TemporalState& t = r->temporal;
+  r->sync_host_mirror();  // RENDER_SPEC §20: the motion of an instance is read off the host's instance transforms
   const HostScene& hs = r->hs;
   const uint32_t cam = r->views[0];
   const bool hist = t.has_history && t.world.size() == 16 * hs.instances.size() && t.inst_marked.size() == hs.instances.size() &&

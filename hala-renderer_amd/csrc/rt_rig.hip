@@ -74,6 +74,8 @@ int hala_rt_set_rig(hala_rt_renderer* r, const hala_rig_desc* rig) {
       if (own_deformer(r, b) && (r->shutter.rec.deformers.count(rg.prims[b]) || r->shutter.act.deformers.count(rg.prims[b])))
         RT_FAIL("A deformer of the rig has shutter keys: clear them and refit first (hala_rt_key_rig with HALA_INVALID_INDEX).");
     if (clear_rig_keys(r) != HALA_OK) return HALA_ERR;
+    r->sync_host_mirror();  // RENDER_SPEC §20: before a local changes
+    r->nodes_dirty = true;
     for (uint32_t n = 0; n < rg.posed_nodes.size(); ++n)  // the nodes the rig's poses moved: back to the file's transforms
       if (rg.posed_nodes[n] && n < r->hs.nodes.size() && !r->shutter.rec.nodes.count(n)) memcpy(r->hs.nodes[n].local.m, rg.copy.nodes[n].local_transform, 64);
     for (size_t b = 0; b < rg.prims.size(); ++b)  // the deformers the rig registered; one the host put there since is the host's

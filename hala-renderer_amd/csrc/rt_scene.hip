@@ -314,17 +314,24 @@ static void h_transform_point(const float* m, const float* p, float* o) {  // RE
   for (int k = 0; k < 3; ++k) o[k] = std::fmaf(m[8 + k], p[2], std::fmaf(m[4 + k], p[1], m[k] * p[0])) + m[12 + k];
 }
 // which instances are intersected in object space: those of a primitive that several instances reference, if their transform can be inverted
-static void classify_instances(hala_rt_renderer* r, std::vector<uint8_t>* flags) {
+// (the first half of it: which instances the rule considers at all; hala_rt_refit_nodes runs the second half on the device)
+void instancing_candidates(const hala_rt_renderer* r, std::vector<uint8_t>* considered) {
   const HostScene& hs = r->hs;
-  flags->assign(hs.instances.size(), 0);
+  considered->assign(hs.instances.size(), 0);
   // automatic: the flattened tree is the faster one (no moves into object space, no instance levels to walk) while it fits comfortably
   constexpr uint32_t kFlattenLimit = 1u << 26;  // triangles: ~15 GB of nodes, triangles and shading records
   if (r->instancing_mode == 1u || (r->instancing_mode == 0u && hs.triangle_count <= kFlattenLimit)) return;
   std::vector<uint32_t> refs(hs.prims.size(), 0u);
   for (uint32_t p : hs.instance_prim) refs[p]++;
+  for (size_t i = 0; i < hs.instances.size(); ++i)
+    (*considered)[i] = refs[hs.instance_prim[i]] >= 2u && hs.prims[hs.instance_prim[i]].indices.size() >= 3 ? 1 : 0;
+}
+static void classify_instances(hala_rt_renderer* r, std::vector<uint8_t>* flags) {
+  const HostScene& hs = r->hs;
+  instancing_candidates(r, flags);
   for (size_t i = 0; i < hs.instances.size(); ++i) {
     InstRef tmp;
-    (*flags)[i] = refs[hs.instance_prim[i]] >= 2u && hs.prims[hs.instance_prim[i]].indices.size() >= 3 && world_to_object(hs.instances[i].transform, &tmp) ? 1 : 0;
+    (*flags)[i] = (*flags)[i] && world_to_object(hs.instances[i].transform, &tmp) ? 1 : 0;
   }
 }
 
@@ -567,6 +574,9 @@ static int build_two_level(hala_rt_renderer* r) {
 }
 
 int build_bvh(hala_rt_renderer* r) {
+  r->sync_host_mirror();
+  r->nodes.analysed = false;  // RENDER_SPEC §20: the bind-time tables name the trees and the flags of the build before this one
+  r->build_options_dirty = false;  // (they take effect here)
   classify_instances(r, &r->inst_instanced);
   r->two_level = false;
   for (uint8_t f : r->inst_instanced) r->two_level = r->two_level || f != 0;
@@ -607,6 +617,10 @@ int hala_rt_set_build_options(hala_rt_renderer* r, const hala_rt_build_options* 
   r->bundles.mode = o->texture_bundles;
   r->bvh.opt.builder = o->builder; r->bvh.opt.ploc_tail = o->ploc_tail;
   r->bvh.opt.ploc_look_every = o->ploc_look_every; r->bvh.opt.collapse_look_every = o->collapse_look_every;
+  // RENDER_SPEC §20: the next hala_rt_refit classifies by the new rule and may build anew by these options; hala_rt_refit_nodes leaves
+  // that to it (the host path), and the bind-time tables, which hold the old rule's candidates, are made again
+  r->build_options_dirty = true;
+  r->nodes.analysed = false;
   return HALA_OK;
 }
 
@@ -708,7 +722,9 @@ int hala_rt_update_node_transform(hala_rt_renderer* r, uint32_t node_index, cons
   if (!r->committed) RT_FAIL("The top level acceleration structure is none!");  // commit builds from what set_scene packed: an edit before it would not reach it
   if (node_index >= r->hs.nodes.size()) RT_FAIL("The node does not exist.");
   if (r->shutter.rec.nodes.count(node_index)) RT_FAIL("The node has shutter keys: clear them first (hala_rt_set_node_keys with both keys NULL).");
+  r->sync_host_mirror();  // RENDER_SPEC §20: from the locals the trees stand at, before one of them changes
   memcpy(r->hs.nodes[node_index].local.m, local_transform, 64);
+  r->nodes_dirty = true;
   return HALA_OK;
 }
 int hala_rt_update_vertices(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, const hala_vertex* vertices, uint32_t vertex_count) {
@@ -742,6 +758,7 @@ int hala_rt_update_material(hala_rt_renderer* r, uint32_t material_index, const 
   if (material->type > 1u) RT_FAIL("Invalid material type.");  // cpu/material.rs:14
   if (r->hs.materials[material_index].opacity == 0.0f || material->opacity == 0.0f) r->materials_dirty_any = true;
   r->hs.materials[material_index] = *material;
+  r->materials_dirty = true;
   if (r->temporal.enabled && material_index < r->temporal.mat_marked.size()) { r->temporal.mat_marked[material_index] = 1; r->temporal.table_dirty = true; }  // RENDER_SPEC §16
   return HALA_OK;
 }
@@ -754,6 +771,10 @@ namespace rt {
 // (RENDER_SPEC §18) is this alone.  What the caller recorded — HostNode::local, HostScene::materials, the dirty flags — is neither read
 // nor written here.
 int refit_geometry(hala_rt_renderer* r, const RefitInputs& in) {
+  // RENDER_SPEC §20: `before` must describe the state the trees are fitted to, also after hala_rt_refit_nodes posed it on the device; and
+  // what follows moves the world transforms on the host, so the device tables of the node batch lag from here on
+  r->sync_host_mirror();
+  r->nodes.tables_current = false;
   const std::vector<hala_gpu_mesh_data> before = r->hs.instances;  // object -> world of every instance as the tree was fitted to it
   const std::vector<uint8_t> kinds_before = r->material_kind;
   r->hs.update_node_hierarchies(in.locals);
@@ -796,6 +817,32 @@ int refit_geometry(hala_rt_renderer* r, const RefitInputs& in) {
     return configure_traversal(r);
   }
   return HALA_OK;
+}
+
+// RENDER_SPEC §20, the device path of hala_rt_refit_nodes: refit_geometry's tree part when nothing but transforms changed and the kernels
+// of node_batch.hip have written them — into d_instances, and into the world tree's own instance table (Blas::d_md) for the flattened
+// instances of a two-level tree, so that no table is uploaded.  The refits are the ones refit_geometry runs; a refit of unmoved content
+// reproduces its bytes, so running one where refit_geometry would have found nothing moved changes nothing.
+// The world tree is refitted without blas_build_or_refit's uploads: everything else that function sets — the rest of Blas::d_md (material,
+// addresses), d_first / d_gid / d_inst, and every field of Blas::b (tris_any, the material tables, the sub-ranges, opt) — must still be
+// what its last run left.  That holds because hala_rt_refit_nodes takes the host path for every edit that changes one of them (a
+// material, vertices, a deformer, build options) and a reclassification rebuilds.  A change to blas_build_or_refit has to be mirrored here.
+int refit_posed_on_device(hala_rt_renderer* r, bool world_tree_moved) {
+  if (r->two_level) {
+    if (r->levels.mode != 1u) RT_FAIL("internal: the instance levels are built on the host");
+    if (world_tree_moved && !r->blas.empty() && !r->blas[0]->object_space) {
+      hala_rt_renderer::Blas& bl = *r->blas[0];
+      const std::string e = bvh_refit(bl.b, r->stream);
+      if (!e.empty()) RT_FAIL(e);
+      const std::string e2 = bvh_relocate(bl.b, bl.node_off, bl.tri_off, r->stream);
+      if (!e2.empty()) RT_FAIL(e2);
+    }
+    if (build_instance_levels_gpu(r, false) != HALA_OK) return HALA_ERR;
+    return configure_traversal(r);
+  }
+  const std::string e = bvh_refit(r->bvh, r->stream);
+  if (!e.empty()) RT_FAIL(e);
+  return configure_traversal(r);
 }
 
 }  // namespace rt

@@ -130,7 +130,7 @@ static std::vector<Mat4> mix_node_keys(std::vector<Mat4> locals, const ShutterKe
 static int refit_recorded(hala_rt_renderer* r, const ShutterKeys& k, float tau, bool moved) {
   r->vertices_dirty = r->vertices_dirty || moved;
   if (refit_geometry(r, RefitInputs{mix_node_keys(r->hs.locals(), k, tau), r->hs.materials, r->vertices_dirty, r->materials_dirty_any}) != HALA_OK) return HALA_ERR;
-  r->vertices_dirty = false; r->materials_dirty_any = false;
+  r->vertices_dirty = false; r->materials_dirty_any = false; r->nodes_dirty = false; r->materials_dirty = false; r->build_options_dirty = false;
   return HALA_OK;
 }
 
@@ -222,7 +222,9 @@ int hala_rt_set_node_keys(hala_rt_renderer* r, uint32_t node_index, const float 
   nk.moving = memcmp(open, close, 64) != 0;
   k.nodes[node_index] = nk;
   k.recount();
+  r->sync_host_mirror();  // RENDER_SPEC §20: before a local changes
   memcpy(r->hs.nodes[node_index].local.m, open, 64);
+  r->nodes_dirty = true;
   return HALA_OK;
 }
 

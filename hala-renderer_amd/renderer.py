@@ -22,6 +22,7 @@ class HalaRenderer:
         from . import check, load_library
         self._lib = load_library()
         self._check = check
+        self._device_ordinal = int(device_ordinal)
         self._h = C.c_void_p()
         check(self._lib.hala_rt_create(name.encode(), C.c_uint32(width), C.c_uint32(height), C.c_int(device_ordinal),
                                        C.c_uint32(max_depth), C.c_uint32(rr_depth), C.c_int(bool(enable_tonemap)),
@@ -556,6 +557,46 @@ class HalaRenderer:
     def refit(self):
         self._check(self._lib.hala_rt_refit(self._h))
 
+    # -- node batches (docs/RENDER_SPEC.md 20; include/halart.h "Node batches") --------------------------------------------------------
+    def bind_nodes(self, indices):
+        """binds an ordered set of nodes of the committed scene (None or empty: unbinds); refit_nodes() then poses them from one array"""
+        idx = np.ascontiguousarray([] if indices is None else indices, dtype=np.uint32).reshape(-1)
+        self._check(self._lib.hala_rt_bind_nodes(self._h, idx.ctypes.data_as(C.POINTER(C.c_uint32)) if idx.size else None, C.c_uint32(idx.size)))
+
+    def refit_nodes(self, locals):
+        """update_node_transform(indices[k], locals[k]) for every bound node + refit(), with the per-node and per-instance work on the
+        device where that gives the same state (node_refit_status() tells).  locals: a numpy [n, 4, 4] float32 array, row-major as
+        update_node_transform takes it, or a torch float32 tensor of n x 16 elements on the renderer's device holding the column-major
+        floats (produced on the stream of get_stream(), or synchronised)"""
+        n = self.node_refit_status().bound_nodes
+        if hasattr(locals, "data_ptr"):  # a torch tensor: device input, read in place
+            import torch
+            if locals.dtype != torch.float32:
+                raise TypeError(f"refit_nodes: the tensor must be float32, not {locals.dtype}")
+            if locals.device.type != "cuda":
+                raise ValueError("refit_nodes: a tensor must live on the renderer's device (pass a numpy array for host memory)")
+            mine = getattr(self, "_device_ordinal", 0)
+            if locals.device.index is not None and locals.device.index != mine:
+                raise ValueError(f"refit_nodes: the tensor lives on device {locals.device.index}, the renderer on device {mine}")
+            if locals.numel() != n * 16 or not locals.is_contiguous():
+                raise ValueError(f"refit_nodes: expected a contiguous tensor of {n} x 16 floats, got shape {tuple(locals.shape)}")
+            self._check(self._lib.hala_rt_refit_nodes(self._h, C.c_void_p(locals.data_ptr()), C.c_int(1)))
+            return
+        m = np.asarray(locals)
+        if m.dtype != np.float32:
+            raise TypeError(f"refit_nodes: the array must be float32, not {m.dtype}")
+        if m.shape != (n, 4, 4):
+            raise ValueError(f"refit_nodes: expected shape ({n}, 4, 4) for the bound nodes, got {m.shape}")
+        cols = np.ascontiguousarray(m.transpose(0, 2, 1))  # column-major, as the C ABI takes it
+        self._check(self._lib.hala_rt_refit_nodes(self._h, C.c_void_p(cols.ctypes.data), C.c_int(0)))
+
+    def node_refit_status(self) -> A.NodeRefitStatus:
+        """bound_nodes, affected_nodes, affected_instances, levels; last_path (0 none, 1 device, 2 host) and last_reason
+        (A.NODE_REFIT_*) of the last refit_nodes(); device_refits, host_refits"""
+        s = A.NodeRefitStatus()
+        self._check(self._lib.hala_rt_get_node_refit_status(self._h, C.byref(s)))
+        return s
+
     # -- deformers (docs/RENDER_SPEC.md 17; include/halart.h "Deformers") ---------------------------------------------------------------
     def set_deformer(self, mesh, prim, targets=None, normal_targets=None, tangent_targets=None, joints=None, weights=None, joint_count=0):
         """register morph targets ([T, V, 3] position deltas, optionally normal / tangent deltas of the same shape) and / or a skin
@@ -732,6 +773,10 @@ class HalaRenderer:
         p = C.c_void_p()
         self._check(self._lib.hala_rt_get_stream(self._h, C.byref(p)))
         return p.value or 0
+
+    def get_stream(self):
+        """hala_rt_get_stream: the same handle under the C entry point's name (device arrays for refit_nodes are produced on it)"""
+        return self.stream_handle()
 
     def tile_buffer(self, which=0):
         p = C.c_void_p(); n = C.c_size_t()

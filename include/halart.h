@@ -1026,6 +1026,47 @@ int hala_rt_set_vertex_keys(hala_rt_renderer* r, uint32_t mesh_index, uint32_t p
                             const hala_vertex* close, uint32_t vertex_count);
 
 /* ------------------------------------------------------------------------------------------------
+ * Node batches (docs/RENDER_SPEC.md 20; no reference equivalent): a crowd, a particle system or a rigid-body simulation binds its
+ * nodes once and hands over one array of local transforms per frame, in host or in device memory.  hala_rt_refit_nodes(locals)
+ * leaves the renderer in exactly the state that hala_rt_update_node_transform(indices[k], &locals[16 k]) for every k followed by
+ * hala_rt_refit leaves it in: trees, instance references, bounds, packed primitives, images, the restarted accumulation, and the
+ * behaviour of every later call.  Where it can, the library computes the node hierarchy and the instance transforms on the device
+ * and runs its refits on them (the device path); otherwise it runs the ordinary sequence itself (the host path) and names the
+ * reason in the status.  Both paths give the same bytes.
+ * ---------------------------------------------------------------------------------------------- */
+#define HALA_NODE_REFIT_PATH_NONE 0u
+#define HALA_NODE_REFIT_PATH_DEVICE 1u
+#define HALA_NODE_REFIT_PATH_HOST 2u
+/* hala_node_refit_status::last_reason: why the host path was taken */
+#define HALA_NODE_REFIT_PENDING_EDIT 1u    /* an edit waits for a refit: a node moved by another call, a material, vertices, a deformer,
+                                              build options set since the trees were built */
+#define HALA_NODE_REFIT_SHUTTER_KEYS 2u    /* shutter keys are recorded or active */
+#define HALA_NODE_REFIT_CAMERA_OR_LIGHT 3u /* a camera or a light hangs at or below a bound node */
+#define HALA_NODE_REFIT_HOST_LEVELS 4u     /* a two-level tree whose instance levels are built on the host (instance_levels = 0) */
+#define HALA_NODE_REFIT_CLASSIFICATION 5u  /* a transform stopped being invertible, or is again: the trees are built anew */
+typedef struct hala_node_refit_status {
+  uint32_t bound_nodes, affected_nodes, affected_instances, levels; /* the binding: nodes bound; they and all below them; their
+                                                                       instances; depth levels among the affected nodes */
+  uint32_t last_path;   /* HALA_NODE_REFIT_PATH_*: of the last hala_rt_refit_nodes */
+  uint32_t last_reason; /* why the host path was taken; 0 on the device path */
+  unsigned long long device_refits, host_refits; /* calls by path since hala_rt_create */
+} hala_node_refit_status; /* 40 B */
+/* Binds an ordered set of nodes of the committed scene; node_indices NULL or count 0 unbinds.  The host analyses the set once — the
+ * bound nodes and all their descendants by depth, their instances and the tree each sits in, whether a camera or a light rides
+ * along — and uploads the tables.  hala_rt_set_scene and hala_rt_commit drop the binding.  Refused, changing nothing: no committed
+ * scene; an index that does not exist; an index given twice; a node with shutter keys (hala_rt_update_node_transform's message). */
+int hala_rt_bind_nodes(hala_rt_renderer* r, const uint32_t* node_indices, uint32_t count);
+/* locals: one column-major 4 x 4 per bound node, in the bound order, as hala_rt_update_node_transform takes it.  where: 0 host
+ * memory, 1 device memory of the renderer's device.  A device array is read on the renderer's stream (hala_rt_get_stream) behind the
+ * join and the wait that hala_rt_refit performs: the caller produces it on that stream, orders its producer against it, or
+ * synchronises before the call; the array may be reused when the call returns.  Refused, changing nothing: no committed scene;
+ * nothing bound; locals NULL; a bound node that has got shutter keys since.  A call that fails later fails where hala_rt_refit
+ * would: the recorded locals and the instance records are the new ones, the trees are not fitted to them and the status does not
+ * count the call; the next successful hala_rt_refit, hala_rt_refit_nodes or hala_rt_commit fits them. */
+int hala_rt_refit_nodes(hala_rt_renderer* r, const float* locals, int where);
+int hala_rt_get_node_refit_status(hala_rt_renderer* r, hala_node_refit_status* out);
+
+/* ------------------------------------------------------------------------------------------------
  * Rigs and clips (docs/RENDER_SPEC.md 19): a hala_rig_desc drives the deformers, node transforms and shutter keys above.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct hala_rig_status {

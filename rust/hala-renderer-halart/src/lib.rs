@@ -78,6 +78,9 @@ pub mod sys {
   pub struct hala_shutter_params { pub shutter_open: f32, pub shutter_close: f32, pub time_stride: u32, pub reserved: [u32; 5] }
   #[repr(C)] #[derive(Default, Clone, Copy)]
   pub struct hala_shutter_status { pub enabled: u32, pub time_stride: u32, pub step: u32, pub time: f32, pub steps: u64, pub reserved: [u32; 2] }
+  /// hala_node_refit_status, 40 B (include/halart.h "Node batches", docs/RENDER_SPEC.md 20)
+  #[repr(C)] #[derive(Default, Clone, Copy)]
+  pub struct hala_node_refit_status { pub bound_nodes: u32, pub affected_nodes: u32, pub affected_instances: u32, pub levels: u32, pub last_path: u32, pub last_reason: u32, pub device_refits: u64, pub host_refits: u64 }
   /// hala_deformer_normals_info, 24 B (RENDER_SPEC 17 "Recomputed normals")
   #[repr(C)] #[derive(Default, Clone, Copy)]
   pub struct hala_deformer_normals_info { pub mode: u32, pub class_count: u32, pub entry_count: u32, pub reserved: u32, pub launches: u64 }
@@ -116,6 +119,10 @@ pub mod sys {
     pub fn hala_rt_update_material(r: *mut hala_rt_renderer, material_index: u32, material: *const hala_material_desc) -> c_int;
     pub fn hala_rt_update_vertices(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, vertices: *const hala_vertex, vertex_count: u32) -> c_int;
     pub fn hala_rt_refit(r: *mut hala_rt_renderer) -> c_int;
+    // node batches (RENDER_SPEC 20): a bound node set posed from one array of column-major locals; where 0 = host memory, 1 = device memory
+    pub fn hala_rt_bind_nodes(r: *mut hala_rt_renderer, node_indices: *const u32, count: u32) -> c_int;
+    pub fn hala_rt_refit_nodes(r: *mut hala_rt_renderer, locals: *const f32, where_: c_int) -> c_int;
+    pub fn hala_rt_get_node_refit_status(r: *mut hala_rt_renderer, out: *mut hala_node_refit_status) -> c_int;
     pub fn hala_rt_load_blue_noise_texture(r: *mut hala_rt_renderer, path: *const c_char) -> c_int;
     pub fn hala_rt_set_tile_shard(r: *mut hala_rt_renderer, rank: u32, world: u32, tile_size: u32) -> c_int;
     // the exchange step (RCCL all-gather + de-interleave) inside the library
@@ -299,6 +306,22 @@ impl HalaRenderer {
     check(unsafe { sys::hala_rt_update_vertices(self.h, mesh_index, primitive_index, vertices.as_ptr(), vertices.len() as u32) })
   }
   pub fn refit(&mut self) -> Result<(), HalaRendererError> { check(unsafe { sys::hala_rt_refit(self.h) }) }
+  /// binds an ordered node set (empty: unbinds); refit_nodes then takes one local transform per bound node, in that order
+  pub fn bind_nodes(&mut self, node_indices: &[u32]) -> Result<(), HalaRendererError> {
+    check(unsafe { sys::hala_rt_bind_nodes(self.h, node_indices.as_ptr(), node_indices.len() as u32) })
+  }
+  /// update_node_transform for every bound node + refit, with the per-node and per-instance work on the device where it can be
+  pub fn refit_nodes(&mut self, locals: &[glam::Mat4]) -> Result<(), HalaRendererError> {
+    let flat: Vec<f32> = locals.iter().flat_map(|m| m.to_cols_array()).collect();
+    check(unsafe { sys::hala_rt_refit_nodes(self.h, flat.as_ptr(), 0) })
+  }
+  /// the same from device memory of the renderer's device (16 floats per bound node, column-major), read on the renderer's stream
+  pub unsafe fn refit_nodes_device(&mut self, d_locals: *const f32) -> Result<(), HalaRendererError> { check(sys::hala_rt_refit_nodes(self.h, d_locals, 1)) }
+  pub fn node_refit_status(&self) -> Result<sys::hala_node_refit_status, HalaRendererError> {
+    let mut s = sys::hala_node_refit_status::default();
+    check(unsafe { sys::hala_rt_get_node_refit_status(self.h, &mut s) })?;
+    Ok(s)
+  }
   /// the hipStream_t of this renderer, for stream-ordered hand-overs of the tile buffer (multi-GPU gather)
   pub fn stream(&self) -> Result<*mut c_void, HalaRendererError> {
     let mut s: *mut c_void = std::ptr::null_mut();
