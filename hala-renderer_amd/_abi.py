@@ -241,6 +241,19 @@ class NodeRefitStatus(C.Structure):  # hala_node_refit_status, 40 B (docs/RENDER
 
 NODE_REFIT_PATH_NONE, NODE_REFIT_PATH_DEVICE, NODE_REFIT_PATH_HOST = 0, 1, 2
 NODE_REFIT_PENDING_EDIT, NODE_REFIT_SHUTTER_KEYS, NODE_REFIT_CAMERA_OR_LIGHT, NODE_REFIT_HOST_LEVELS, NODE_REFIT_CLASSIFICATION = 1, 2, 3, 4, 5
+NODE_REFIT_POLICY_REBUILD = 6
+
+
+class RefitPolicy(C.Structure):  # hala_refit_policy, 16 B (docs/RENDER_SPEC.md 4.6)
+    _fields_ = [("mode", C.c_uint32), ("max_inflation", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class TreeQuality(C.Structure):  # hala_tree_quality, 48 B
+    _fields_ = [("first_node", C.c_uint32), ("node_count", C.c_uint32), ("valid", C.c_uint32), ("rebuilt_last_refit", C.c_uint32),
+                ("node_q_built", C.c_uint64), ("tri_q_built", C.c_uint64), ("node_q_now", C.c_uint64), ("tri_q_now", C.c_uint64)]
+
+
+REFIT_POLICY_OFF, REFIT_POLICY_THRESHOLD, REFIT_POLICY_ALWAYS, REFIT_POLICY_MEASURE = 0, 1, 2, 3
 
 # the rig of a glTF file (docs/RENDER_SPEC.md 19; include/halart.h "The rig of a glTF file")
 RIG_STEP, RIG_LINEAR, RIG_CUBICSPLINE = 0, 1, 2
@@ -360,6 +373,9 @@ PROTOTYPES = {
     "hala_rt_bind_nodes": ([C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32], C.c_int),
     "hala_rt_refit_nodes": ([C.c_void_p, C.c_void_p, C.c_int], C.c_int),
     "hala_rt_get_node_refit_status": ([C.c_void_p, C.POINTER(NodeRefitStatus)], C.c_int),
+    "hala_rt_set_refit_policy": ([C.c_void_p, C.POINTER(RefitPolicy)], C.c_int),
+    "hala_rt_get_tree_quality": ([C.c_void_p, C.POINTER(TreeQuality), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_uint64)], C.c_int),
     "hala_rt_variant_ledger": ([C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int], C.c_int),
     "hala_rt_selftest_math": ([C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)], C.c_int),
     "hala_rt_selftest_math_values": ([C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)], C.c_int),
@@ -424,6 +440,7 @@ EXPORTS = [
     "hala_scene_get_rig", "hala_rig_sample_clip", "hala_rt_set_rig", "hala_rt_pose_rig", "hala_rt_key_rig", "hala_rt_get_rig_pose",
     "hala_rt_get_rig_status",
     "hala_rt_bind_nodes", "hala_rt_refit_nodes", "hala_rt_get_node_refit_status",
+    "hala_rt_set_refit_policy", "hala_rt_get_tree_quality",
     "hala_rt_variant_ledger",
     "hala_rt_selftest_math", "hala_rt_selftest_math_values",
 ]

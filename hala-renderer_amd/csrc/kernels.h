@@ -112,6 +112,13 @@ std::string bvh_refit(BvhBuffers& b, hipStream_t s);
 std::string bvh_relocate(BvhBuffers& b, uint32_t node_offset, uint32_t tri_offset, hipStream_t s);
 void bvh_free_topology(void* topology);
 
+// bvh_quality.hip — the tree cost of RENDER_SPEC 4.6 of the tree of `node_count` nodes whose root is `root` (references may be absolute:
+// only boxes, presence, the leaf bit and the leaf counts are read): out3[0] = node_q, out3[1] = tri_q, out3[2] = valid (all three 0 for
+// an invalid tree; out3 is left alone when node_count is 0).  partials: kTreeCostPartialWords words of scratch, free again once the
+// launches have run (calls on one stream may share it).  Nothing is synchronised.
+constexpr uint32_t kTreeCostPartialWords = 2048;
+void launch_tree_cost(const BvhNode4* root, uint32_t node_count, unsigned long long* partials, unsigned long long* out3, hipStream_t s);
+
 // bvh_tlas.cpp — the instance levels of a two-level tree (RENDER_SPEC 4.5), built on the host.  An item is a world-space box with the
 // child reference a node slot gets for it: an instance leaf (kInstLeafTag | InstRef index) or the root node of a subtree that needs no
 // transform; `need` = traversal stack entries a ray can need behind it.  Returns the node count (nodes in breadth-first order, root 0).

@@ -22,8 +22,12 @@ void launch_node_locals(const float* in, const uint32_t* bound, uint32_t count, 
 // one depth level of the affected nodes, parents before children: launched level by level
 void launch_node_worlds(const NodeBatchNode* level, uint32_t n, const float* locals, float* worlds, uint32_t node_count, hipStream_t s);
 // the 64-B transform of every affected instance (in `instances`, and in `world_md` where it has a slot there), and the test of
-// world_to_object against `check`: a mismatch is ORed into *mismatch
+// world_to_object against `check`: a mismatch is ORed into *mismatch (kNodeBatchMismatch).  detect_moved (the refit policy is on,
+// RENDER_SPEC 4.6): an instance whose new transform differs bitwise from the one it had ORs kNodeBatchMoved, and kNodeBatchMovedWorldTree
+// with it where the instance has a slot in `world_md`
+constexpr uint32_t kNodeBatchMismatch = 1u, kNodeBatchMoved = 2u, kNodeBatchMovedWorldTree = 4u;
 void launch_instance_transforms(const NodeBatchInst* items, uint32_t n, const float* worlds, uint32_t node_count, hala_gpu_mesh_data* instances,
-                                uint32_t instance_count, hala_gpu_mesh_data* world_md, uint32_t world_md_count, uint32_t* mismatch, hipStream_t s);
+                                uint32_t instance_count, hala_gpu_mesh_data* world_md, uint32_t world_md_count, uint32_t* mismatch, bool detect_moved,
+                                hipStream_t s);
 
 }  // namespace rt

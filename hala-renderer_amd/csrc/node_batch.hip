@@ -78,17 +78,25 @@ RT_DI bool invertible(const float* m) {
 __global__ void __launch_bounds__(256) k_instance_transforms(const NodeBatchInst* __restrict__ items, uint32_t n, const float* __restrict__ worlds,
                                                               uint32_t node_count, hala_gpu_mesh_data* __restrict__ instances, uint32_t instance_count,
                                                               hala_gpu_mesh_data* __restrict__ world_md, uint32_t world_md_count,
-                                                              uint32_t* __restrict__ mismatch) {
+                                                              uint32_t* __restrict__ mismatch, uint32_t detect_moved) {
   const uint32_t k = blockIdx.x * 256u + threadIdx.x;
   if (k >= n) return;
   const NodeBatchInst it = items[k];
   if (it.inst >= instance_count || it.node >= node_count) return;
   alignas(16) float m[16];
   copy64(m, worlds + (size_t)it.node * 16u);
+  if (detect_moved) {  // RENDER_SPEC 4.6: what refit_geometry's comparison of the transforms would find, bit for bit
+    const uint4* was = reinterpret_cast<const uint4*>(instances[it.inst].transform);
+    const uint4* is = reinterpret_cast<const uint4*>(m);
+    bool same = true;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) same = same && was[q].x == is[q].x && was[q].y == is[q].y && was[q].z == is[q].z && was[q].w == is[q].w;
+    if (!same) atomicOr(mismatch, it.md_slot < world_md_count ? (kNodeBatchMoved | kNodeBatchMovedWorldTree) : kNodeBatchMoved);
+  }
   copy64(instances[it.inst].transform, m);  // the other 32 bytes of the record stand
   if (it.md_slot < world_md_count) copy64(world_md[it.md_slot].transform, m);
   const uint32_t now = (it.check & 1u) && invertible(m) ? 1u : 0u;
-  if (now != ((it.check >> 1) & 1u)) atomicOr(mismatch, 1u);
+  if (now != ((it.check >> 1) & 1u)) atomicOr(mismatch, kNodeBatchMismatch);
 }
 
 inline uint32_t blocks(uint32_t n) { return (n + 255u) / 256u; }
@@ -102,9 +110,10 @@ void launch_node_worlds(const NodeBatchNode* level, uint32_t n, const float* loc
   if (n) hipLaunchKernelGGL(k_node_worlds, dim3(blocks(n)), dim3(256), 0, s, level, n, locals, worlds, node_count);
 }
 void launch_instance_transforms(const NodeBatchInst* items, uint32_t n, const float* worlds, uint32_t node_count, hala_gpu_mesh_data* instances,
-                                uint32_t instance_count, hala_gpu_mesh_data* world_md, uint32_t world_md_count, uint32_t* mismatch, hipStream_t s) {
+                                uint32_t instance_count, hala_gpu_mesh_data* world_md, uint32_t world_md_count, uint32_t* mismatch, bool detect_moved,
+                                hipStream_t s) {
   if (n) hipLaunchKernelGGL(k_instance_transforms, dim3(blocks(n)), dim3(256), 0, s, items, n, worlds, node_count, instances, instance_count, world_md,
-                            world_md_count, mismatch);
+                            world_md_count, mismatch, detect_moved ? 1u : 0u);
 }
 
 }  // namespace rt

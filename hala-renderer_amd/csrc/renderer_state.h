@@ -344,6 +344,20 @@ struct NodeBatchState {
   }
 };
 
+// tree quality and the refit policy (RENDER_SPEC §4.6; hala_rt_set_refit_policy, hala_rt_get_tree_quality).  `trees` is empty while the
+// policy is off or nothing is committed; otherwise one entry per measured tree in the order of hala_rt_renderer::blas (one-level: one).
+struct QualityState {
+  uint32_t mode = 0;
+  float max_inflation = 0.0f;
+  std::vector<hala_tree_quality> trees;
+  unsigned long long refits_measured = 0, trees_rebuilt = 0;
+  DeviceArray<unsigned long long> d_out;  // three words per tree (launch_tree_cost)
+  DeviceArray<unsigned long long> d_partials;  // its scratch, shared by the launches of one measurement
+  unsigned long long* h_out = nullptr;    // pinned, as many words: the copy back needs no staging
+  size_t h_words = 0;
+  ~QualityState() { if (h_out) (void)hipHostFree(h_out); }
+};
+
 enum class Changed { Commit, Refit, Views, Aovs };  // hala_rt_renderer::invalidate
 
 }  // namespace rt
@@ -466,6 +480,7 @@ struct hala_rt_renderer {
   ShutterState shutter;        // RENDER_SPEC 18: keys and shutter (hala_rt_set_shutter)
   RigState rig;                // RENDER_SPEC 19: the rig whose bindings are deformers here (hala_rt_set_rig)
   NodeBatchState nodes;        // RENDER_SPEC 20: the bound node set (hala_rt_bind_nodes)
+  QualityState quality;        // RENDER_SPEC 4.6: the refit policy and what it measured (hala_rt_set_refit_policy)
   DeviceArray<Control> d_ctl;  // one per frame slot
   DeviceArray<WorkCounters> d_batch_work;
   // hala_rt_trace_rays, RENDER_SPEC 4.2: the caller's batch with far origins re-based, and how far each was moved (grown on demand)
@@ -662,13 +677,16 @@ struct RefitInputs {
   const std::vector<hala_material_desc>& materials;
   bool arena_changed;                                 // the vertex arena changed since the tree was fitted
   bool opacity0_edit;                                 // a material edit touched an opacity-0 material
+  bool policy = false;                                // RENDER_SPEC 4.6: hala_rt_refit's own call — measure what was refitted, rebuild if due
 };
 int refit_geometry(hala_rt_renderer* r, const RefitInputs& in);
 // rt_scene.hip, for hala_rt_refit_nodes (rt_nodes.hip; RENDER_SPEC §20).  instancing_candidates: per instance, would classify_instances test
 // its transform.  refit_posed_on_device: the tree part of refit_geometry when d_instances (and the world tree's own instance table) were
 // posed on the device: the existing refits, the instance levels on the GPU, the traversal configuration
 void instancing_candidates(const hala_rt_renderer* r, std::vector<uint8_t>* considered);
-int refit_posed_on_device(hala_rt_renderer* r, bool world_tree_moved);
+// `moved`: the transform of some instance changed / of one that the world tree of a two-level scene holds (what refit_geometry compares);
+// *rebuilt: the refit policy (RENDER_SPEC 4.6) built the trees anew behind the refit
+int refit_posed_on_device(hala_rt_renderer* r, bool moved, bool world_tree_moved, bool* rebuilt);
 // rt_shutter.hip (RENDER_SPEC §18).  shutter_refit: hala_rt_refit's geometry part with the recorded keys applied, the scene left at step
 // 0; shutter_step: moves the scene to step `j` between two frames of one accumulation (update_impl, while the shutter is active)
 int shutter_refit(hala_rt_renderer* r);

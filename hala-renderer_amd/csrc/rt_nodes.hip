@@ -169,12 +169,13 @@ int hala_rt_refit_nodes(hala_rt_renderer* r, const float* locals, int where) {
     launch_node_worlds(nb.d_levels.ptr + nb.level_first[l], nb.level_first[l + 1u] - nb.level_first[l], nb.d_locals.ptr, nb.d_worlds.ptr, node_count, r->stream);
   const bool world_tree = r->two_level && !r->blas.empty() && !r->blas[0]->object_space;
   launch_instance_transforms(nb.d_insts.ptr, nb.affected_instances, nb.d_worlds.ptr, node_count, r->d_instances.ptr, (uint32_t)r->d_instances.count,
-                             world_tree ? r->blas[0]->d_md.ptr : nullptr, world_tree ? (uint32_t)r->blas[0]->d_md.count : 0u, nb.d_mismatch.ptr, r->stream);
+                             world_tree ? r->blas[0]->d_md.ptr : nullptr, world_tree ? (uint32_t)r->blas[0]->d_md.count : 0u, nb.d_mismatch.ptr,
+                             r->quality.mode != HALA_REFIT_POLICY_OFF, r->stream);
   RT_HIP(hipGetLastError());
   // the one look, before anything is built on the new transforms
   RT_HIP(hipMemcpyAsync(nb.h_word, nb.d_mismatch.ptr, 4, hipMemcpyDeviceToHost, r->stream));
   RT_HIP(hipStreamSynchronize(r->stream));
-  if (*nb.h_word) return host_path(r, nb.h_stage, HALA_NODE_REFIT_CLASSIFICATION);  // (refit_geometry publishes every instance record again)
+  if (*nb.h_word & kNodeBatchMismatch) return host_path(r, nb.h_stage, HALA_NODE_REFIT_CLASSIFICATION);  // (refit_geometry publishes every instance record again)
   for (uint32_t k = 0; k < count; ++k) memcpy(r->hs.nodes[nb.bound[k]].local.m, nb.h_stage + 16u * (size_t)k, 64);
   nb.mirror_stale = true;
   {  // what hala_rt_refit does when no key is anywhere (shutter_refit)
@@ -182,8 +183,14 @@ int hala_rt_refit_nodes(hala_rt_renderer* r, const float* locals, int where) {
     sh.act = sh.rec;
     sh.step = kShutterNoStep; sh.time = 0.0f;
   }
-  if (refit_posed_on_device(r, nb.moves_flattened) != HALA_OK) return HALA_ERR;
-  restart(r, kPathDevice, 0u);
+  // RENDER_SPEC 4.6: with a policy the refit measures what it moved, as the ordinary sequence would, and builds anew when that is due —
+  // the ordinary sequence's end, reported as the host path with its own reason
+  const bool moved = (*nb.h_word & kNodeBatchMoved) != 0u, moved_world = (*nb.h_word & kNodeBatchMovedWorldTree) != 0u;
+  const bool policy = r->quality.mode != HALA_REFIT_POLICY_OFF;
+  bool rebuilt = false;
+  if (refit_posed_on_device(r, moved, policy ? moved_world : nb.moves_flattened, &rebuilt) != HALA_OK) return HALA_ERR;
+  if (rebuilt) restart(r, kPathHost, HALA_NODE_REFIT_POLICY_REBUILD);
+  else restart(r, kPathDevice, 0u);
   return HALA_OK;
 }
 

@@ -573,7 +573,87 @@ static int build_two_level(hala_rt_renderer* r) {
   return configure_traversal(r);
 }
 
-int build_bvh(hala_rt_renderer* r) {
+// ---- tree quality (RENDER_SPEC §4.6) ------------------------------------------------------------------------------------------------
+// the cost of the trees `which` (indices into QualityState::trees) as the node array stands -> their `now` fields.  Waits for the stream.
+static int quality_measure(hala_rt_renderer* r, const std::vector<uint32_t>& which) {
+  QualityState& q = r->quality;
+  if (which.empty()) return HALA_OK;
+  const size_t words = q.trees.size() * 3u;
+  if (q.d_out.count < words) RT_HIP(q.d_out.resize(words));
+  if (q.d_partials.count < kTreeCostPartialWords) RT_HIP(q.d_partials.resize(kTreeCostPartialWords));
+  if (q.h_words < words) {
+    if (q.h_out) (void)hipHostFree(q.h_out);
+    q.h_out = nullptr; q.h_words = 0;
+    RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&q.h_out), words * sizeof(unsigned long long), hipHostMallocDefault));
+    q.h_words = words;
+  }
+  RT_HIP(hipMemsetAsync(q.d_out.ptr, 0, words * sizeof(unsigned long long), r->stream));
+  for (uint32_t k : which) {
+    const hala_tree_quality& t = q.trees[k];
+    if ((size_t)t.first_node + t.node_count > r->d_nodes.count) RT_FAIL("internal: a measured tree lies outside the node array");
+    launch_tree_cost(r->d_nodes.ptr + t.first_node, t.node_count, q.d_partials.ptr, q.d_out.ptr + 3u * (size_t)k, r->stream);
+  }
+  RT_HIP(hipGetLastError());
+  RT_HIP(hipMemcpyAsync(q.h_out, q.d_out.ptr, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, r->stream));
+  RT_HIP(hipStreamSynchronize(r->stream));
+  for (uint32_t k : which) {
+    hala_tree_quality& t = q.trees[k];
+    t.node_q_now = q.h_out[3u * (size_t)k]; t.tri_q_now = q.h_out[3u * (size_t)k + 1u]; t.valid = q.h_out[3u * (size_t)k + 2u] ? 1u : 0u;
+  }
+  return HALA_OK;
+}
+
+// behind a build: the trees as they were just built become the baseline (built = now).  Policy off: nothing is kept, nothing runs
+static int quality_built(hala_rt_renderer* r) {
+  QualityState& q = r->quality;
+  q.trees.clear();
+  if (q.mode == HALA_REFIT_POLICY_OFF) return HALA_OK;
+  std::vector<uint32_t> all;
+  if (r->two_level) {
+    for (const auto& bl : r->blas) {
+      hala_tree_quality t{};
+      t.first_node = bl->node_off; t.node_count = bl->b.node_count;
+      all.push_back((uint32_t)q.trees.size());
+      q.trees.push_back(t);
+    }
+  } else {
+    hala_tree_quality t{};
+    t.first_node = 0u; t.node_count = r->bvh.node_count;
+    all.push_back(0u);
+    q.trees.push_back(t);
+  }
+  if (quality_measure(r, all) != HALA_OK) { q.trees.clear(); return HALA_ERR; }
+  for (hala_tree_quality& t : q.trees) { t.node_q_built = t.node_q_now; t.tri_q_built = t.tri_q_now; }
+  return HALA_OK;
+}
+
+// behind the refits of a refit: `refitted` (indices as in hala_rt_renderer::blas; {0} for a one-level tree) are measured and the policy
+// is applied.  *rebuilt: build_bvh ran (all trees anew, traversal configured); the caller has nothing left to do for the trees
+static int quality_after_refit(hala_rt_renderer* r, const std::vector<uint32_t>& refitted, bool* rebuilt) {
+  QualityState& q = r->quality;
+  *rebuilt = false;
+  if (q.mode == HALA_REFIT_POLICY_OFF) return HALA_OK;
+  if (q.trees.size() != (r->two_level ? r->blas.size() : (size_t)1)) RT_FAIL("internal: the measured trees are not the scene's");
+  for (hala_tree_quality& t : q.trees) t.rebuilt_last_refit = 0u;
+  if (refitted.empty()) return HALA_OK;  // cameras, lights, nodes of instanced primitives: no tree moved
+  if (quality_measure(r, refitted) != HALA_OK) return HALA_ERR;
+  ++q.refits_measured;
+  bool due = q.mode == HALA_REFIT_POLICY_ALWAYS;
+  if (q.mode == HALA_REFIT_POLICY_THRESHOLD)
+    for (uint32_t k : refitted) {
+      const hala_tree_quality& t = q.trees[k];
+      const double built = (double)(t.node_q_built + t.tri_q_built), now = (double)(t.node_q_now + t.tri_q_now);
+      due = due || (t.valid && built > 0.0 && now / built > (double)q.max_inflation);
+    }
+  if (!due) return HALA_OK;
+  if (build_bvh(r) != HALA_OK) return HALA_ERR;  // (measures what it built: built = now)
+  for (hala_tree_quality& t : q.trees) t.rebuilt_last_refit = 1u;
+  q.trees_rebuilt += q.trees.size();
+  *rebuilt = true;
+  return HALA_OK;
+}
+
+static int build_trees(hala_rt_renderer* r) {
   r->sync_host_mirror();
   r->nodes.analysed = false;  // RENDER_SPEC §20: the bind-time tables name the trees and the flags of the build before this one
   r->build_options_dirty = false;  // (they take effect here)
@@ -601,6 +681,11 @@ int build_bvh(hala_rt_renderer* r) {
   if (!e.empty()) RT_FAIL(e);
   r->leaf_max_built = leaf_max;
   return configure_traversal(r);
+}
+
+int build_bvh(hala_rt_renderer* r) {
+  if (build_trees(r) != HALA_OK) return HALA_ERR;
+  return quality_built(r);  // RENDER_SPEC §4.6 (nothing with the policy off)
 }
 
 }  // namespace rt
@@ -798,25 +883,33 @@ int refit_geometry(hala_rt_renderer* r, const RefitInputs& in) {
   std::vector<uint8_t> flags;
   classify_instances(r, &flags);
   if (flags != r->inst_instanced) return build_bvh(r);
+  std::vector<uint32_t> refitted;  // RENDER_SPEC §4.6: what the policy measures
+  bool rebuilt = false;
   if (r->two_level) {
     // RENDER_SPEC 4.5: a node that moves an instanced primitive only touches the instance levels (rebuilt below, on the host or on the GPU).  The trees
     // underneath are refitted when what THEY hold changed: `content` (any tree), the transform of a flattened instance (the world tree)
     r->bvh.tris_any = r->any_invisible ? r->d_tris_any.ptr : nullptr;
-    for (auto& bl : r->blas) {
+    for (size_t k = 0; k < r->blas.size(); ++k) {
+      hala_rt_renderer::Blas& bl = *r->blas[k];
       bool moved = content;
-      if (!bl->object_space)
-        for (uint32_t i : bl->insts) moved = moved || memcmp(before[i].transform, r->hs.instances[i].transform, 64) != 0;
-      if (moved && blas_build_or_refit(r, *bl, true) != HALA_OK) return HALA_ERR;
+      if (!bl.object_space)
+        for (uint32_t i : bl.insts) moved = moved || memcmp(before[i].transform, r->hs.instances[i].transform, 64) != 0;
+      if (!moved) continue;
+      if (blas_build_or_refit(r, bl, true) != HALA_OK) return HALA_ERR;
+      refitted.push_back((uint32_t)k);
     }
+    if (in.policy && quality_after_refit(r, refitted, &rebuilt) != HALA_OK) return HALA_ERR;
+    if (rebuilt) return HALA_OK;
     if (build_instance_levels(r, false) != HALA_OK) return HALA_ERR;
     return configure_traversal(r);
   }
   if (geometry_moved) {
     const std::string e2 = bvh_refit(r->bvh, r->stream);
     if (!e2.empty()) RT_FAIL(e2);
-    return configure_traversal(r);
+    refitted.push_back(0u);
   }
-  return HALA_OK;
+  if (in.policy && quality_after_refit(r, refitted, &rebuilt) != HALA_OK) return HALA_ERR;
+  return geometry_moved && !rebuilt ? configure_traversal(r) : HALA_OK;
 }
 
 // RENDER_SPEC §20, the device path of hala_rt_refit_nodes: refit_geometry's tree part when nothing but transforms changed and the kernels
@@ -827,22 +920,29 @@ int refit_geometry(hala_rt_renderer* r, const RefitInputs& in) {
 // addresses), d_first / d_gid / d_inst, and every field of Blas::b (tris_any, the material tables, the sub-ranges, opt) — must still be
 // what its last run left.  That holds because hala_rt_refit_nodes takes the host path for every edit that changes one of them (a
 // material, vertices, a deformer, build options) and a reclassification rebuilds.  A change to blas_build_or_refit has to be mirrored here.
-int refit_posed_on_device(hala_rt_renderer* r, bool world_tree_moved) {
+int refit_posed_on_device(hala_rt_renderer* r, bool moved, bool world_tree_moved, bool* rebuilt) {
+  *rebuilt = false;
   if (r->two_level) {
     if (r->levels.mode != 1u) RT_FAIL("internal: the instance levels are built on the host");
+    std::vector<uint32_t> refitted;
     if (world_tree_moved && !r->blas.empty() && !r->blas[0]->object_space) {
       hala_rt_renderer::Blas& bl = *r->blas[0];
       const std::string e = bvh_refit(bl.b, r->stream);
       if (!e.empty()) RT_FAIL(e);
       const std::string e2 = bvh_relocate(bl.b, bl.node_off, bl.tri_off, r->stream);
       if (!e2.empty()) RT_FAIL(e2);
+      refitted.push_back(0u);
     }
+    if (quality_after_refit(r, refitted, rebuilt) != HALA_OK) return HALA_ERR;
+    if (*rebuilt) return HALA_OK;
     if (build_instance_levels_gpu(r, false) != HALA_OK) return HALA_ERR;
     return configure_traversal(r);
   }
   const std::string e = bvh_refit(r->bvh, r->stream);
   if (!e.empty()) RT_FAIL(e);
-  return configure_traversal(r);
+  // (with the policy on `moved` is what refit_geometry's comparison would have found: an unmoved tree is not measured)
+  if (quality_after_refit(r, moved ? std::vector<uint32_t>{0u} : std::vector<uint32_t>{}, rebuilt) != HALA_OK) return HALA_ERR;
+  return *rebuilt ? HALA_OK : configure_traversal(r);
 }
 
 }  // namespace rt
@@ -858,6 +958,35 @@ int hala_rt_refit(hala_rt_renderer* r) {
   if (shutter_refit(r) != HALA_OK) return HALA_ERR;
   r->invalidate(Changed::Refit);
   r->reset_accumulation();  // like the device-lost path: accumulation restarts (src/rt_renderer.rs:557)
+  return HALA_OK;
+}
+
+int hala_rt_set_refit_policy(hala_rt_renderer* r, const hala_refit_policy* p) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  if (!p) RT_FAIL("The refit policy is null!");
+  if (p->mode > HALA_REFIT_POLICY_MEASURE) RT_FAIL("Invalid refit policy (mode).");
+  if (p->mode == HALA_REFIT_POLICY_THRESHOLD ? !(std::isfinite(p->max_inflation) && p->max_inflation >= 1.0f) : !(p->max_inflation == 0.0f))
+    RT_FAIL("Invalid refit policy (max_inflation: finite and >= 1 with mode 1, 0 otherwise).");
+  for (uint32_t v : p->reserved) if (v != 0u) RT_FAIL("Invalid refit policy (reserved fields must be 0).");
+  QualityState& q = r->quality;
+  q.mode = p->mode; q.max_inflation = p->max_inflation;
+  if (q.mode == HALA_REFIT_POLICY_OFF) { q.trees.clear(); return HALA_OK; }
+  if (!r->committed || !q.trees.empty()) return HALA_OK;
+  // the trees as they stand become the baseline
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipStreamSynchronize(r->stream));
+  return quality_built(r);
+}
+
+int hala_rt_get_tree_quality(hala_rt_renderer* r, hala_tree_quality* dst, uint32_t capacity, uint32_t* tree_count,
+                             unsigned long long* refits_measured, unsigned long long* trees_rebuilt_by_policy) {
+  if (!r) RT_FAIL("The renderer handle is null!");
+  const QualityState& q = r->quality;
+  const size_t n = r->committed ? q.trees.size() : 0u;
+  if (dst) memcpy(dst, q.trees.data(), std::min<size_t>(capacity, n) * sizeof(hala_tree_quality));
+  if (tree_count) *tree_count = (uint32_t)n;
+  if (refits_measured) *refits_measured = q.refits_measured;
+  if (trees_rebuilt_by_policy) *trees_rebuilt_by_policy = q.trees_rebuilt;
   return HALA_OK;
 }
 

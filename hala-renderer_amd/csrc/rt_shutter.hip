@@ -129,7 +129,7 @@ static std::vector<Mat4> mix_node_keys(std::vector<Mat4> locals, const ShutterKe
 // hala_rt_refit's geometry part: the tree to what the caller recorded, the keyed nodes at `tau`; the recorded flags go once it stands
 static int refit_recorded(hala_rt_renderer* r, const ShutterKeys& k, float tau, bool moved) {
   r->vertices_dirty = r->vertices_dirty || moved;
-  if (refit_geometry(r, RefitInputs{mix_node_keys(r->hs.locals(), k, tau), r->hs.materials, r->vertices_dirty, r->materials_dirty_any}) != HALA_OK) return HALA_ERR;
+  if (refit_geometry(r, RefitInputs{mix_node_keys(r->hs.locals(), k, tau), r->hs.materials, r->vertices_dirty, r->materials_dirty_any, /* policy */ true}) != HALA_OK) return HALA_ERR;
   r->vertices_dirty = false; r->materials_dirty_any = false; r->nodes_dirty = false; r->materials_dirty = false; r->build_options_dirty = false;
   return HALA_OK;
 }

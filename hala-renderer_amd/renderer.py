@@ -597,6 +597,25 @@ class HalaRenderer:
         self._check(self._lib.hala_rt_get_node_refit_status(self._h, C.byref(s)))
         return s
 
+    # -- tree quality and the refit policy (docs/RENDER_SPEC.md 4.6; include/halart.h "Tree quality and the refit policy") -------------
+    def set_refit_policy(self, mode, max_inflation=0.0):
+        """mode: A.REFIT_POLICY_OFF (0, the default: nothing is measured), _THRESHOLD (1: measure, rebuild the trees when a refitted
+        tree's cost has grown beyond max_inflation times its cost when built; finite, >= 1), _ALWAYS (2: rebuild at every refit that
+        refitted a tree), _MEASURE (3: measure only).  max_inflation must be 0 unless mode is 1"""
+        p = A.RefitPolicy()
+        p.mode = int(mode)
+        p.max_inflation = float(max_inflation)
+        self._check(self._lib.hala_rt_set_refit_policy(self._h, C.byref(p)))
+
+    def tree_quality(self):
+        """-> (trees, refits_measured, trees_rebuilt_by_policy): trees is a list of A.TreeQuality (first_node, node_count, valid,
+        rebuilt_last_refit, node_q_built, tri_q_built, node_q_now, tri_q_now; the sums in units of 2^-32), empty with the policy off"""
+        n, measured, rebuilt = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.hala_rt_get_tree_quality(self._h, None, C.c_uint32(0), C.byref(n), C.byref(measured), C.byref(rebuilt)))
+        trees = (A.TreeQuality * max(1, n.value))()
+        self._check(self._lib.hala_rt_get_tree_quality(self._h, trees, C.c_uint32(n.value), C.byref(n), C.byref(measured), C.byref(rebuilt)))
+        return list(trees[:n.value]), measured.value, rebuilt.value
+
     # -- deformers (docs/RENDER_SPEC.md 17; include/halart.h "Deformers") ---------------------------------------------------------------
     def set_deformer(self, mesh, prim, targets=None, normal_targets=None, tangent_targets=None, joints=None, weights=None, joint_count=0):
         """register morph targets ([T, V, 3] position deltas, optionally normal / tangent deltas of the same shape) and / or a skin

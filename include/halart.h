@@ -1065,6 +1065,52 @@ int hala_rt_bind_nodes(hala_rt_renderer* r, const uint32_t* node_indices, uint32
  * count the call; the next successful hala_rt_refit, hala_rt_refit_nodes or hala_rt_commit fits them. */
 int hala_rt_refit_nodes(hala_rt_renderer* r, const float* locals, int where);
 int hala_rt_get_node_refit_status(hala_rt_renderer* r, hala_node_refit_status* out);
+#define HALA_NODE_REFIT_POLICY_REBUILD 6u  /* last_reason beside the five above: the device path posed and refitted, the refit policy
+                                              (below) then found a rebuild due and the trees were built anew, as hala_rt_refit would */
+
+/* ------------------------------------------------------------------------------------------------
+ * Tree quality and the refit policy (docs/RENDER_SPEC.md 4.6; no reference equivalent).  hala_rt_refit keeps the topology the last
+ * build gave the tree and only re-derives its boxes; far from the pose it was built for the boxes grow and overlap, images stay
+ * what they are and rays cost more.  The tree cost of RENDER_SPEC 4.6 — computed on the device from the published node format
+ * alone (k_tree_cost), reproducible from hala_rt_download_bvh — tells, and a policy may build the trees anew when it has grown.
+ * A tree: the whole node array of a one-level scene; of a two-level scene the world tree and each object-space tree (the instance
+ * levels are built anew by every refit and are not measured).
+ * ---------------------------------------------------------------------------------------------- */
+#define HALA_REFIT_POLICY_OFF 0u          /* never measure, never rebuild: the default */
+#define HALA_REFIT_POLICY_THRESHOLD 1u    /* measure; rebuild when a refitted tree's inflation exceeds max_inflation */
+#define HALA_REFIT_POLICY_ALWAYS 2u       /* measure; rebuild at every refit that refitted a tree */
+#define HALA_REFIT_POLICY_MEASURE 3u      /* measure only */
+typedef struct hala_refit_policy {
+  uint32_t mode;          /* HALA_REFIT_POLICY_* */
+  float max_inflation;    /* mode 1: finite, >= 1; every other mode: must be 0.  inflation = cost_now / cost_built in double, cost =
+                             node_q + tri_q.  There is no default on purpose.  Measured once (DESIGN.md 23,
+                             profiles/tree_quality_timing.json: 1.0 M triangles, a 120 k-triangle floor displaced by noise, 1080p, a
+                             rebuild of 18 - 21 ms against a refit of 0.4 ms): a rebuild repaid itself within about 80 frames
+                             from inflation 2.3, 40 from 8.8, 10 from 60; above 200 the geometry itself had become the cost and
+                             a rebuild won nothing.  For any other scene the value is unmeasured: measure with mode 3 first. */
+  uint32_t reserved[2];   /* 0 */
+} hala_refit_policy; /* 16 B */
+/* Takes effect at once: on a committed renderer with mode != 0 whose trees are not yet measured, the trees as they stand are measured
+ * and become the baseline (built = now); mode 0 forgets the numbers (the two counters stay).  Refused, changing nothing and doing no
+ * device work: policy NULL; mode > 3; mode 1 with max_inflation not finite or < 1; another mode with max_inflation != 0; a reserved
+ * word != 0. */
+int hala_rt_set_refit_policy(hala_rt_renderer* r, const hala_refit_policy* policy);
+typedef struct hala_tree_quality {
+  uint32_t first_node, node_count; /* the tree: nodes [first_node, first_node + node_count) of hala_rt_download_bvh, root first */
+  uint32_t valid;                  /* 0: the root box has no area; all sums 0, never rebuilt by the policy */
+  uint32_t rebuilt_last_refit;     /* 1: the last hala_rt_refit / hala_rt_refit_nodes built this tree anew because the policy said so */
+  unsigned long long node_q_built, tri_q_built; /* RENDER_SPEC 4.6, units of 2^-32: right after the tree was last built */
+  unsigned long long node_q_now, tri_q_now;     /* ... and after the last refit that refitted it */
+} hala_tree_quality; /* 48 B */
+/* With mode != 0: hala_rt_commit and every rebuild measure the trees they built (built = now); hala_rt_refit and hala_rt_refit_nodes
+ * measure every tree they refitted (now), then apply the policy: a rebuild builds ALL trees of the scene anew (build options that
+ * wait take effect, as when a refit reclassifies instances) and invalidates what that rebuild invalidates.  A refit that moved only
+ * cameras, lights or nodes of instanced primitives refits no tree and measures nothing; a step of the shutter never measures.
+ * dst may be NULL; at most `capacity` trees are written, *tree_count is the number there are (0 with mode 0 or before a commit);
+ * refits_measured: refits that measured at least one tree; trees_rebuilt_by_policy: trees built anew by policy rebuilds; both since
+ * hala_rt_create.  Any of the three pointers may be NULL. */
+int hala_rt_get_tree_quality(hala_rt_renderer* r, hala_tree_quality* dst, uint32_t capacity, uint32_t* tree_count,
+                             unsigned long long* refits_measured, unsigned long long* trees_rebuilt_by_policy);
 
 /* ------------------------------------------------------------------------------------------------
  * Rigs and clips (docs/RENDER_SPEC.md 19): a hala_rig_desc drives the deformers, node transforms and shutter keys above.

@@ -81,6 +81,11 @@ pub mod sys {
   /// hala_node_refit_status, 40 B (include/halart.h "Node batches", docs/RENDER_SPEC.md 20)
   #[repr(C)] #[derive(Default, Clone, Copy)]
   pub struct hala_node_refit_status { pub bound_nodes: u32, pub affected_nodes: u32, pub affected_instances: u32, pub levels: u32, pub last_path: u32, pub last_reason: u32, pub device_refits: u64, pub host_refits: u64 }
+  /// hala_refit_policy (16 B) / hala_tree_quality (48 B): include/halart.h "Tree quality and the refit policy", docs/RENDER_SPEC.md 4.6
+  #[repr(C)] #[derive(Default, Clone, Copy)]
+  pub struct hala_refit_policy { pub mode: u32, pub max_inflation: f32, pub reserved: [u32; 2] }
+  #[repr(C)] #[derive(Default, Clone, Copy)]
+  pub struct hala_tree_quality { pub first_node: u32, pub node_count: u32, pub valid: u32, pub rebuilt_last_refit: u32, pub node_q_built: u64, pub tri_q_built: u64, pub node_q_now: u64, pub tri_q_now: u64 }
   /// hala_deformer_normals_info, 24 B (RENDER_SPEC 17 "Recomputed normals")
   #[repr(C)] #[derive(Default, Clone, Copy)]
   pub struct hala_deformer_normals_info { pub mode: u32, pub class_count: u32, pub entry_count: u32, pub reserved: u32, pub launches: u64 }
@@ -123,6 +128,10 @@ pub mod sys {
     pub fn hala_rt_bind_nodes(r: *mut hala_rt_renderer, node_indices: *const u32, count: u32) -> c_int;
     pub fn hala_rt_refit_nodes(r: *mut hala_rt_renderer, locals: *const f32, where_: c_int) -> c_int;
     pub fn hala_rt_get_node_refit_status(r: *mut hala_rt_renderer, out: *mut hala_node_refit_status) -> c_int;
+    // tree quality (RENDER_SPEC 4.6): mode 0 off | 1 rebuild above max_inflation | 2 rebuild at every refit | 3 measure only
+    pub fn hala_rt_set_refit_policy(r: *mut hala_rt_renderer, policy: *const hala_refit_policy) -> c_int;
+    pub fn hala_rt_get_tree_quality(r: *mut hala_rt_renderer, dst: *mut hala_tree_quality, capacity: u32, tree_count: *mut u32,
+                                    refits_measured: *mut u64, trees_rebuilt_by_policy: *mut u64) -> c_int;
     pub fn hala_rt_load_blue_noise_texture(r: *mut hala_rt_renderer, path: *const c_char) -> c_int;
     pub fn hala_rt_set_tile_shard(r: *mut hala_rt_renderer, rank: u32, world: u32, tile_size: u32) -> c_int;
     // the exchange step (RCCL all-gather + de-interleave) inside the library
@@ -321,6 +330,21 @@ impl HalaRenderer {
     let mut s = sys::hala_node_refit_status::default();
     check(unsafe { sys::hala_rt_get_node_refit_status(self.h, &mut s) })?;
     Ok(s)
+  }
+  /// the refit policy (RENDER_SPEC 4.6): mode 0 off, 1 rebuild when a refitted tree's cost exceeds max_inflation times its cost when built,
+  /// 2 rebuild at every refit, 3 measure only; max_inflation is 0 unless mode is 1
+  pub fn set_refit_policy(&mut self, mode: u32, max_inflation: f32) -> Result<(), HalaRendererError> {
+    let p = sys::hala_refit_policy { mode, max_inflation, reserved: [0; 2] };
+    check(unsafe { sys::hala_rt_set_refit_policy(self.h, &p) })
+  }
+  /// (trees, refits_measured, trees_rebuilt_by_policy)
+  pub fn tree_quality(&self) -> Result<(Vec<sys::hala_tree_quality>, u64, u64), HalaRendererError> {
+    let (mut n, mut measured, mut rebuilt) = (0u32, 0u64, 0u64);
+    check(unsafe { sys::hala_rt_get_tree_quality(self.h, std::ptr::null_mut(), 0, &mut n, &mut measured, &mut rebuilt) })?;
+    let mut trees = vec![sys::hala_tree_quality::default(); n as usize];
+    check(unsafe { sys::hala_rt_get_tree_quality(self.h, trees.as_mut_ptr(), n, &mut n, &mut measured, &mut rebuilt) })?;
+    trees.truncate(n as usize);
+    Ok((trees, measured, rebuilt))
   }
   /// the hipStream_t of this renderer, for stream-ordered hand-overs of the tile buffer (multi-GPU gather)
   pub fn stream(&self) -> Result<*mut c_void, HalaRendererError> {
