@@ -8,7 +8,7 @@
 //              4096 items, full-sweep SAH from there)
 //   collapse, pack levels   bvh_build.hip's, leaf_max = 1; a leaf's reference is the item's (BvhTopology::item_ref)
 // Everything a build carves comes out of one arena that the renderer keeps between builds (InstanceLevelsJob::arena), so a refit
-// allocates nothing.  The arithmetic of the items is the host path's (rt_scene.hip: world_to_object, build_instance_levels), operation
+// allocates nothing.  The arithmetic of the items is the host path's (rt_trees.hip: world_to_object, build_instance_levels), operation
 // for operation: the InstRef records and the scene bounds are the same bits whichever path built them; the tree above them is not.
 #include <hip/hip_runtime.h>
 

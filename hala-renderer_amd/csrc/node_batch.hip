@@ -1,7 +1,7 @@
 // node_batch.hip — the device half of hala_rt_refit_nodes (docs/RENDER_SPEC.md 20): the caller's array of local transforms scattered
 // into the table of all node locals, the world matrices of the affected nodes level by level, and the transforms of the affected
 // instances with the test that decides whether an instance can be intersected in object space.  The arithmetic is the host's
-// (host_scene.cpp: mul; rt_scene.hip: world_to_object), operation for operation: __fmul_rn / __fadd_rn keep the four-term sums in the
+// (host_scene.cpp: mul; rt_trees.hip: world_to_object), operation for operation: __fmul_rn / __fadd_rn keep the four-term sums in the
 // host's order and unfused whatever the compiler is told, the division is IEEE.  The host looks at one word afterwards.
 #include "node_batch.h"
 
@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(256) k_node_worlds(const NodeBatchNode* __rest
 
 RT_DI bool finite_f(float v) { return fabsf(v) <= 3.402823466e+38f; }  // false for NaN and the infinities
 
-// rt_scene.hip::world_to_object's verdict: can the transform be inverted in float, with every entry of the result finite
+// rt_trees.hip::world_to_object's verdict: can the transform be inverted in float, with every entry of the result finite
 RT_DI bool invertible(const float* m) {
   const f3 c0 = mk3(m[0], m[1], m[2]), c1 = mk3(m[4], m[5], m[6]), c2 = mk3(m[8], m[9], m[10]);
   const f3 k0 = cross3(c1, c2), k1 = cross3(c2, c0), k2 = cross3(c0, c1);

@@ -1,5 +1,5 @@
 // renderer_state.h — the renderer object behind the C ABI (struct hala_rt_renderer), shared by the host units that implement it:
-// renderer.hip (life cycle, scene, update), rt_scene.hip (uploads, trees, edits), rt_outputs.hip (views, AOVs, adaptive sampling, light
+// renderer.hip (life cycle, scene, update), rt_scene.hip (uploads, edits), rt_trees.hip (trees, refit sequence), rt_outputs.hip (views, AOVs, adaptive sampling, light
 // groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_deform.hip (deformers), rt_rig.hip (rigs and clips), rt_shutter.hip (shutter motion blur), rt_nodes.hip (node batches), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
 // Each feature keeps its state in one struct that knows how to turn itself off.  What is indexed by path slot (per-path state, queues)
 // lives in the WavefrontSet of a frame slot (FrameSlots::slot[2]: two updates in flight), sized by WavefrontSet::fit to the one PathShape
@@ -345,7 +345,7 @@ struct NodeBatchState {
 };
 
 // tree quality and the refit policy (RENDER_SPEC §4.6; hala_rt_set_refit_policy, hala_rt_get_tree_quality).  `trees` is empty while the
-// policy is off or nothing is committed; otherwise one entry per measured tree in the order of hala_rt_renderer::blas (one-level: one).
+// policy is off or nothing is committed; otherwise one entry per measured tree in the order of hala_rt_renderer::trees.
 struct QualityState {
   uint32_t mode = 0;
   float max_inflation = 0.0f;
@@ -405,12 +405,21 @@ struct hala_rt_renderer {
   std::vector<TexDesc> host_textures;
   BundleState bundles;
 
-  BvhBuffers bvh{};
-  // two-level trees (RENDER_SPEC 4.5): scenes in which some primitive is referenced by several instances.  `bvh` then only carries the
-  // totals; the trees live in `blas` — [0] the world-space tree over the triangles of all instances that are NOT instanced (if any), then
-  // one object-space tree per instanced primitive — as sub-ranges of the node / triangle / shading-record arrays, behind the instance
-  // levels (the first tlas_capacity nodes), which are rebuilt whenever a node moves (on the host, or on the GPU: `levels`).
-  struct Blas {
+  // The scene's trees as a whole: what the readers outside the builder want of them (configure_traversal, view(), hala_rt_get_bvh_info,
+  // rt_post.hip) and the build options (hala_rt_set_build_options), which every tree and the instance levels are built by
+  struct TreeTotals {
+    uint32_t node_count = 0, tri_count = 0;  // of the node / triangle arrays (two-level: the reserved ranges included)
+    uint32_t max_depth = 0, stack_need = 0;  // from the root, through the instance levels
+    float scene_min[3] = {}, scene_max[3] = {};
+    BuildOptions opt;
+  } bvh;
+  // Every tree of the scene lives in `trees`, as a sub-range of the node / triangle / shading-record arrays: [0] the world-space tree
+  // over the triangles of all instances that are NOT instanced (if any), then one object-space tree per instanced primitive.  A scene in
+  // which some primitive is referenced by several instances is two-level (RENDER_SPEC 4.5): its trees stand behind the instance levels
+  // (the first tlas_capacity nodes), which are rebuilt whenever a node moves (on the host, or on the GPU: `levels`).  Any other scene is
+  // one-level: one world tree at node 0 and triangle 0 that holds every instance and reads the scene's own instance tables (d_instances,
+  // d_inst_first_tri) in place of the four below.
+  struct Tree {
     BvhBuffers b{};
     uint32_t node_off = 0, tri_off = 0, node_cap = 0;
     bool object_space = false;
@@ -418,13 +427,15 @@ struct hala_rt_renderer {
     std::vector<uint32_t> insts;            // world tree: the instances it holds, in instance order
     DeviceArray<hala_gpu_mesh_data> d_md;
     DeviceArray<uint32_t> d_first, d_gid, d_inst;
-    ~Blas() { if (b.topology) bvh_free_topology(b.topology); }
+    ~Tree() { if (b.topology) bvh_free_topology(b.topology); }
   };
-  std::vector<std::unique_ptr<Blas>> blas;
+  std::vector<std::unique_ptr<Tree>> trees;
   bool two_level = false;
+  // the world tree of a two-level scene, which has instance tables of its own; null: every instance is instanced, or the scene is one-level
+  Tree* world_tree() const { return two_level && !trees.empty() && !trees[0]->object_space ? trees[0].get() : nullptr; }
   uint32_t instancing_mode = 0;            // hala_rt_build_options::instancing: 0 automatic (by size), 1 never (everything flattened), 2 by the rule of RENDER_SPEC 4.5
   std::vector<uint8_t> inst_instanced;     // per instance: intersected in object space
-  std::vector<int32_t> prim_blas;          // per primitive: index into blas, -1
+  std::vector<int32_t> prim_tree;          // per primitive: index into trees, -1
   uint32_t tlas_capacity = 0, tlas_nodes = 0, stored_tris = 0;
   std::vector<InstRef> inst_refs;          // (levels.refs_on_host tells whether its contents are current)
   DeviceArray<InstRef> d_inst_refs;
@@ -525,8 +536,7 @@ struct hala_rt_renderer {
     // images first, then everything else (src/rt_renderer.rs:620-633)
     for (auto& i : img_local) i.release();
     for (auto& i : img_full) i.release();
-    if (bvh.topology) bvh_free_topology(bvh.topology);
-    blas.clear();
+    trees.clear();
     slots.release();
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -658,7 +668,19 @@ std::string file_stem(const char* path);
 int upload_packed(hala_rt_renderer* r, bool geometry = true);
 int upload_textures(hala_rt_renderer* r);
 int update_texture_bundles(hala_rt_renderer* r, bool fresh);
+// rt_trees.hip.  build_bvh: all trees anew from the packed scene, the instance levels, the traversal configuration, the quality baseline.
+// attach_any_triangles, classify_instances: the records half of a refit (refit_geometry) runs them again to see what an edit changed.
+// instancing_candidates: per instance, would classify_instances test its transform (hala_rt_refit_nodes runs that test on the device)
 int build_bvh(hala_rt_renderer* r);
+int attach_any_triangles(hala_rt_renderer* r);
+void classify_instances(hala_rt_renderer* r, std::vector<uint8_t>* flags);
+void instancing_candidates(const hala_rt_renderer* r, std::vector<uint8_t>* considered);
+// The refit sequence: the trees `moved` (indices into hala_rt_renderer::trees) are fitted to what the device tables hold, measured and,
+// with `policy` (RENDER_SPEC 4.6), rebuilt when due (*rebuilt: build_bvh ran, nothing is left to do); then the instance levels
+// (two-level) and the traversal configuration.  published: the caller's kernels wrote the moved transforms into the trees' instance
+// tables (hala_rt_refit_nodes), so nothing is uploaded and no field of Tree::b is set again — every edit that changes anything else a
+// tree is published with takes that call's host path (rt_nodes.hip: host_reason).
+int refit_trees(hala_rt_renderer* r, const std::vector<uint32_t>& moved, bool published, bool policy, bool* rebuilt);
 // rt_deform.hip.  deform_pose: every (deformer, parameters) of `items` posed into the arena, on an idle stream -> HALA_OK; kDeformOverflow:
 // a posed position is not finite, the arena is put back and synchronised, `overflowed` (where given) names the offending items, the
 // message is set; HALA_ERR: a device error (or the refusal after one).  It keeps Deformer::applied / posed, the temporal marks and the
@@ -670,8 +692,8 @@ struct DeformPose { Deformer* d; const Deformer::Params* p; };
 int deform_pose(hala_rt_renderer* r, const std::vector<DeformPose>& items, std::vector<size_t>* overflowed);
 int deform_refit(hala_rt_renderer* r, const std::map<uint32_t, Deformer::Params>& keyed, const std::vector<uint32_t>& again, bool* moved);
 bool deform_registered(const hala_rt_renderer* r, uint32_t prim);
-// rt_scene.hip: hala_rt_refit without the restart — hierarchies, packed records, the tree (rebuilt when the instancing flags change) —
-// fitted to what `in` names; it reads and clears nothing of what the caller recorded
+// rt_scene.hip: hala_rt_refit without the restart — hierarchies, packed records, the trees that moved (refit_trees; all rebuilt when the
+// instancing flags change) — fitted to what `in` names; it reads and clears nothing of what the caller recorded
 struct RefitInputs {
   const std::vector<Mat4>& locals;                    // one per node
   const std::vector<hala_material_desc>& materials;
@@ -680,13 +702,6 @@ struct RefitInputs {
   bool policy = false;                                // RENDER_SPEC 4.6: hala_rt_refit's own call — measure what was refitted, rebuild if due
 };
 int refit_geometry(hala_rt_renderer* r, const RefitInputs& in);
-// rt_scene.hip, for hala_rt_refit_nodes (rt_nodes.hip; RENDER_SPEC §20).  instancing_candidates: per instance, would classify_instances test
-// its transform.  refit_posed_on_device: the tree part of refit_geometry when d_instances (and the world tree's own instance table) were
-// posed on the device: the existing refits, the instance levels on the GPU, the traversal configuration
-void instancing_candidates(const hala_rt_renderer* r, std::vector<uint8_t>* considered);
-// `moved`: the transform of some instance changed / of one that the world tree of a two-level scene holds (what refit_geometry compares);
-// *rebuilt: the refit policy (RENDER_SPEC 4.6) built the trees anew behind the refit
-int refit_posed_on_device(hala_rt_renderer* r, bool moved, bool world_tree_moved, bool* rebuilt);
 // rt_shutter.hip (RENDER_SPEC §18).  shutter_refit: hala_rt_refit's geometry part with the recorded keys applied, the scene left at step
 // 0; shutter_step: moves the scene to step `j` between two frames of one accumulation (update_impl, while the shutter is active)
 int shutter_refit(hala_rt_renderer* r);

@@ -1,7 +1,7 @@
 // rt_nodes.hip — node batches (docs/RENDER_SPEC.md 20; include/halart.h "Node batches"): a set of nodes bound once and posed from one
 // array of local transforms per frame, in host or device memory.  hala_rt_refit_nodes leaves the renderer where
 // hala_rt_update_node_transform per bound node + hala_rt_refit would: on the device path the kernels of node_batch.hip compute the
-// hierarchy and the instance transforms and the existing refits run on them (refit_posed_on_device); whenever that cannot guarantee the
+// hierarchy and the instance transforms and the one refit sequence runs on them (refit_trees, published); whenever that cannot guarantee the
 // same state the call writes the locals into the host scene and runs hala_rt_refit's own code (the host path), and says why in the status.
 #include "renderer_state.h"
 
@@ -38,9 +38,8 @@ static int analyse(hala_rt_renderer* r) {
   std::vector<uint8_t> considered;
   instancing_candidates(r, &considered);
   std::vector<uint32_t> md_slot(hs.instances.size(), kAbsent);
-  const bool world_tree = r->two_level && !r->blas.empty() && !r->blas[0]->object_space;
-  if (world_tree)
-    for (size_t k = 0; k < r->blas[0]->insts.size(); ++k) md_slot[r->blas[0]->insts[k]] = (uint32_t)k;
+  if (const hala_rt_renderer::Tree* w = r->world_tree())
+    for (size_t k = 0; k < w->insts.size(); ++k) md_slot[w->insts[k]] = (uint32_t)k;
   std::vector<NodeBatchInst> insts;
   nb.moves_flattened = false;
   for (size_t i = 0; i < hs.instances.size(); ++i) {
@@ -167,10 +166,10 @@ int hala_rt_refit_nodes(hala_rt_renderer* r, const float* locals, int where) {
   launch_node_locals(d_in, nb.d_bound.ptr, count, nb.d_locals.ptr, node_count, r->stream);
   for (uint32_t l = 0; l < nb.levels(); ++l)
     launch_node_worlds(nb.d_levels.ptr + nb.level_first[l], nb.level_first[l + 1u] - nb.level_first[l], nb.d_locals.ptr, nb.d_worlds.ptr, node_count, r->stream);
-  const bool world_tree = r->two_level && !r->blas.empty() && !r->blas[0]->object_space;
+  const hala_rt_renderer::Tree* w = r->world_tree();
+  const bool policy = r->quality.mode != HALA_REFIT_POLICY_OFF;
   launch_instance_transforms(nb.d_insts.ptr, nb.affected_instances, nb.d_worlds.ptr, node_count, r->d_instances.ptr, (uint32_t)r->d_instances.count,
-                             world_tree ? r->blas[0]->d_md.ptr : nullptr, world_tree ? (uint32_t)r->blas[0]->d_md.count : 0u, nb.d_mismatch.ptr,
-                             r->quality.mode != HALA_REFIT_POLICY_OFF, r->stream);
+                             w ? w->d_md.ptr : nullptr, w ? (uint32_t)w->d_md.count : 0u, nb.d_mismatch.ptr, policy, r->stream);
   RT_HIP(hipGetLastError());
   // the one look, before anything is built on the new transforms
   RT_HIP(hipMemcpyAsync(nb.h_word, nb.d_mismatch.ptr, 4, hipMemcpyDeviceToHost, r->stream));
@@ -183,12 +182,15 @@ int hala_rt_refit_nodes(hala_rt_renderer* r, const float* locals, int where) {
     sh.act = sh.rec;
     sh.step = kShutterNoStep; sh.time = 0.0f;
   }
-  // RENDER_SPEC 4.6: with a policy the refit measures what it moved, as the ordinary sequence would, and builds anew when that is due —
-  // the ordinary sequence's end, reported as the host path with its own reason
-  const bool moved = (*nb.h_word & kNodeBatchMoved) != 0u, moved_world = (*nb.h_word & kNodeBatchMovedWorldTree) != 0u;
-  const bool policy = r->quality.mode != HALA_REFIT_POLICY_OFF;
+  // The tree that holds flattened instances, [0], moved if one of them did.  RENDER_SPEC 4.6: with a policy the kernels have compared the
+  // transforms as the ordinary sequence would, so the refit fits and measures what that one would, and builds anew when that is due — the
+  // ordinary sequence's end, reported as the host path with its own reason.  Without one the bind-time analysis answers: an affected
+  // instance lies in the tree (in a one-level tree: always; a refit of unmoved content reproduces its bytes)
+  const uint32_t moved_bit = r->two_level ? kNodeBatchMovedWorldTree : kNodeBatchMoved;
+  std::vector<uint32_t> moved;
+  if (policy ? (*nb.h_word & moved_bit) != 0u : (!r->two_level || nb.moves_flattened)) moved.push_back(0u);
   bool rebuilt = false;
-  if (refit_posed_on_device(r, moved, policy ? moved_world : nb.moves_flattened, &rebuilt) != HALA_OK) return HALA_ERR;
+  if (refit_trees(r, moved, true, true, &rebuilt) != HALA_OK) return HALA_ERR;
   if (rebuilt) restart(r, kPathHost, HALA_NODE_REFIT_POLICY_REBUILD);
   else restart(r, kPathDevice, 0u);
   return HALA_OK;

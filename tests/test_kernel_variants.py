@@ -38,7 +38,7 @@ NAMES = ("accum", "albedo", "normal", "final")
 UNREACHABLE = {
     3: {
         # k_trace_shadow_then_batch<ALPHA, STAGED, !INST, GROUPS>, flags in with_flags order (ALPHA, STAGED, INST, GROUPS)
-        0b0011: "ALPHA = sv.any_translucent: a material of any-hit class >= 2, which also sets any_invisible (rt_scene.hip attach_any_triangles: "
+        0b0011: "ALPHA = sv.any_translucent: a material of any-hit class >= 2, which also sets any_invisible (rt_trees.hip attach_any_triangles: "
                 "`r->any_invisible = r->any_invisible || cls[i] != 0`), so sv.tris_any is the separate d_tris_any copy (renderer_state.h view(): "
                 "`sv.tris_any = any_invisible ? d_tris_any.ptr : d_tris.ptr`) and integrator.hip launch_trace_shadow_then_batch returns false "
                 "before it launches: `if (tree == TreeForm::Staged && sv.tris_any != sv.tris) return false;`",

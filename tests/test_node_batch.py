@@ -262,19 +262,56 @@ def test_flattened_instance_moves_the_world_tree(halart, oracle):
 
 
 @gpu
-def test_unmoved_transforms_reproduce_the_tree(halart):
+def test_host_refit_that_changes_what_a_tree_is_published_with_then_the_device_path(halart, oracle):
+    """The one material, which the flattened ground and box carry too, becomes invisible: the scene gains the any-hit copy of its
+    triangles, which every tree learns of when the host path publishes it again (the pending edit).  The next call takes the device
+    path, which publishes nothing, and moves the world tree; then the same with the material opaque again.  (The oracle's accumulated
+    and final images of the invisible scene differ from the opaque one's in 199 of the 768 pixels: the images tell the two apart.)"""
+    s = copy.deepcopy(instance_scene(17, True))
+    ground = [k for k, n in enumerate(s.nodes) if n.name == "ground"][0]
+    a, b = twins(halart, s)
+    try:
+        a.bind_nodes([ground, 4])
+        step = 0
+        for opacity in (0.0, 1.0):
+            s.materials[0] = H.HalaMaterial(type=0, base_color=(0.7, 0.6, 0.5), opacity=opacity)
+            for r in (a, b):
+                r.update_material(0, s.materials[0])
+            for path, reason in ((HOST, A.NODE_REFIT_PENDING_EDIT), (DEVICE, 0)):
+                step += 1
+                m = np.eye(4, dtype=f32)
+                m[:3, 3] = (0.25 * step, -0.5, 0.125 * step)
+                move(a, b, s, [(ground, m), (4, _moved(s.nodes[4].local_transform, 4 + step))])
+                assert_path(a, path, reason)
+                check(a, b, oracle, s, f"opacity {opacity}, path {path}")
+    finally:
+        a.close(); b.close()
+
+
+@gpu
+@pytest.mark.parametrize("policy", [A.REFIT_POLICY_OFF, A.REFIT_POLICY_MEASURE], ids=["policy_off", "measure_only"])
+def test_unmoved_transforms_reproduce_the_tree(halart, policy):
+    """with a policy on nothing moved means nothing is refitted and nothing measured; a moved tree is measured as on the twin"""
     for instancing in (True, False):
-        s = instance_scene(17, True)
-        r = make_renderer(halart, s, W, HGT, build=dict(instancing=instancing, instance_levels="gpu"))
+        s = copy.deepcopy(instance_scene(17, True))
+        a, b = twins(halart, s, instancing=instancing)
         try:
-            before = state(r)
+            for r in (a, b):
+                r.set_refit_policy(policy)
+            before, measured = state(a), a.tree_quality()[1]
             idx = list(range(19))
-            r.bind_nodes(idx)
-            r.refit_nodes(np.stack([s.nodes[k].local_transform for k in idx]))
-            assert_path(r, DEVICE)
-            assert state(r) == before
+            a.bind_nodes(idx)
+            a.refit_nodes(np.stack([s.nodes[k].local_transform for k in idx]))
+            assert_path(a, DEVICE)
+            assert state(a) == before
+            assert a.tree_quality()[1] == measured
+            if policy != A.REFIT_POLICY_OFF:
+                move(a, b, s, [(k, _moved(s.nodes[k].local_transform, k)) for k in idx])
+                assert_path(a, DEVICE)
+                assert_same_state(a, b, f"moved, instancing {instancing}")
+                assert a.tree_quality()[1] == b.tree_quality()[1] == measured + 1  # one refit that moved a tree: one measurement
         finally:
-            r.close()
+            a.close(); b.close()
 
 
 # ---- reclassification -------------------------------------------------------------------------------------------------------------------
