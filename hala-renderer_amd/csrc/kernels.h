@@ -21,7 +21,7 @@ struct LaunchCfg {
 enum class TreeForm { Large, Staged, TwoLevel };
 inline TreeForm tree_form(const SceneView& sv) { return sv.staged ? TreeForm::Staged : (sv.two_level ? TreeForm::TwoLevel : TreeForm::Large); }
 
-// integrator.hip
+// trace_closest.hip (the traverse_* answers, the closest-hit launches, the RENDER_SPEC 4.2 pair) and trace_shadow.hip (the two shadow launches)
 size_t traverse_fixed_lds_bytes(TreeForm tree);  // LDS bytes of one workgroup besides a staged BVH: per-lane stacks (+ leaf work lists)
 uint32_t traverse_stack_lds_levels(TreeForm tree);  // stack entries kept in LDS
 uint32_t traverse_max_leaf(TreeForm tree);  // largest leaf (triangles) the traversal variant accepts
@@ -39,7 +39,9 @@ void launch_trace_primary(const LaunchCfg& lc, const SceneView& sv, const FrameC
 // RENDER_SPEC 4.2 around a caller's batch: out = the batch with far origins re-based, moved[i] = how far; then moved[i] back on the closest hits' t
 void launch_rebase_batch(const SceneView& sv, const hala_ray* rays, hala_ray* out, float* moved, uint32_t n, hipStream_t s);
 void launch_unbase_hits(hala_hit* hits, const float* moved, uint32_t n, hipStream_t s);
+// shade.hip
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s);
+// resolve.hip
 // pos / ids: the first-hit AOV images of RENDER_SPEC §13 (nullptr: off; both off: the kernel variant without them).  group_images: the
 // light-group images of §14, group g at group_images + g * group_stride (read only while ps.groups is set: the GROUPS variants)
 void launch_resolve(const FrameConst& fc, const PathState& ps, float4* accum, float4* albedo, float4* normal, float4* final_img, float4* pos,
@@ -51,8 +53,8 @@ void launch_relight(const hala_global_uniform& u, const float4* group_images, si
 void launch_scatter_tiles(const FrameConst& fc, const float4* gathered, float4* full, hipStream_t s);
 void launch_sample_texture(const SceneView& sv, uint32_t tex, const float* uvl, uint32_t n, float4* out, hipStream_t s);
 
-// The variant ledger (hala_rt_variant_ledger): the families in the order of the entry point's `family`; the flags of each in the order of
-// its launcher's with_flags call.  false: no such family.  Per process; `reset` clears the family's launched mask after reading it.
+// variants.cpp — the variant ledger (hala_rt_variant_ledger): the families in the order of the entry point's `family`; the flags of each in the order of
+// its launcher's dispatch call (variants.h).  false: no such family.  Per process; `reset` clears the family's launched mask after reading it.
 enum : uint32_t { kFamilyTracePrimary, kFamilyTraceBatch, kFamilyTraceShadow, kFamilyTraceShadowThenBatch, kFamilyShade, kFamilyResolve, kVariantFamilies };
 bool variant_ledger(uint32_t family, uint64_t* launched, uint64_t* built, bool reset);
 

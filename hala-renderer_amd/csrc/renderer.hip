@@ -1,6 +1,6 @@
 // renderer.hip — HalaRenderer (src/rt_renderer.rs:568-1353) re-designed for one MI355X: the C++ object behind the
 // C ABI of include/halart.h.  Descriptor sets become a struct of device pointers (rt::SceneView), trace_rays becomes the
-// wavefront kernel sequence of integrator.hip, timestamp queries become HIP events, staging buffers become
+// wavefront kernel sequence of trace_closest.hip, timestamp queries become HIP events, staging buffers become
 // hipMemcpyAsync from the caller's memory.  Everything that computes runs on the GPU; the host units only orchestrate.
 // This unit: create / destroy, settings, scene, envmap and commit, the update itself, render and the read-backs of the frame,
 // statistics.  The object and the other host units: renderer_state.h.

@@ -257,4 +257,24 @@ RT_DI float safe_inv(float d) {
   return rcp_rn(dd);
 }
 
+// Streaming stores (queue entries, hit records): written once, read by the next launch at the earliest — nontemporal stores keep
+// them from displacing what the traversal and shading gathers want in L2 (+1.4 ... 2.2 % on the headline).  The 12-B per-path
+// records stay ordinary stores: three scalar nontemporal stores each measured slower.
+typedef float v4f_nt __attribute__((ext_vector_type(4)));
+RT_DI void st4(float4* p, float4 v) { __builtin_nontemporal_store(v4f_nt{v.x, v.y, v.z, v.w}, reinterpret_cast<v4f_nt*>(p)); }
+
+// wave64 helpers ------------------------------------------------------------------------------------------
+RT_DI uint32_t lane_id() { return threadIdx.x & 63u; }
+RT_DI uint32_t wave_sum(uint32_t v) {
+  for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_down((int)v, off);
+  return v;  // valid in lane 0
+}
+RT_DI uint32_t mbcnt64(unsigned long long m) {  // number of set bits of m below this lane
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// LDS is addressed through explicit address-space-3 pointers to builtin vectors: a generic pointer kept in a struct makes hipcc emit
+// flat_load / flat_store (both memory pipes, both wait counters) instead of ds_read / ds_write.
+#define RT_LDS __attribute__((address_space(3)))
+
 }  // namespace rt

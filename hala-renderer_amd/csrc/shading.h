@@ -83,6 +83,34 @@ RT_DI void camera_ray(const FrameConst& fc, const hala_gpu_camera& cam, float ta
     *d = normalize3(fwd);
   }
 }
+// The camera ray of path slot `slot` (RENDER_SPEC §5) and the RNG state after it; false for the padding slots of a
+// sharded frame.  Primary rays are never stored: the depth-0 traversal and the depth-0 shading both evaluate this.
+// VIEWS (fc.views > 1, RENDER_SPEC §12): slot = (sample * views + view) * pixel_slots + pixel slot; the view picks the camera and its
+// tan_half, the RNG state is the single-view one (keyed by pixel and frame only).  A compile-time flag: the single-view code stays as it
+// was (a run-time merge of the two turned the camera index and tan_half into vector registers and added scratch to the traversal kernels).
+template <bool VIEWS>
+RT_DI bool primary_ray(const FrameConst& fc, const SceneView& sv, uint32_t slot, f3* o, f3* d, uint32_t* rng) {
+  uint32_t sample = slot / fc.pixel_slots;
+  const uint32_t pslot = slot - sample * fc.pixel_slots;
+  uint32_t view = 0;
+  if (VIEWS) { const uint32_t q = sample; sample = q / fc.views; view = q - sample * fc.views; }
+  uint32_t px = 0, py = 0;
+  *o = splat3(0.0f); *d = mk3(0.0f, 0.0f, 1.0f); *rng = 0u;
+  if (!slot_to_pixel(fc, pslot, &px, &py)) return false;
+  uint32_t state = rng_init(py * fc.width + px, fc.u.frame_index + sample);
+  if (VIEWS) {
+    const ViewConst vc = fc.view_table[view];
+    camera_ray(fc, sv.cameras[vc.camera], vc.tan_half, px, py, state, o, d);
+  } else camera_ray(fc, sv.cameras[fc.u.camera_index], fc.tan_half, px, py, state, o, d);
+  *rng = state;
+  return true;
+}
+
+// the texture-LOD spread of the view that path slot `slot` belongs to (RENDER_SPEC §7.4, §12); several views only
+RT_DI float view_pixel_spread(const FrameConst& fc, uint32_t slot) {
+  const uint32_t q = slot / fc.pixel_slots;
+  return fc.view_table[q % fc.views].pixel_spread;
+}
 
 // ---- §7.3 environment ----------------------------------------------------------------------------------------
 RT_DI int wrapi(int i, int n) {

@@ -1,0 +1,85 @@
+// trace_shadow.hip — the any-hit traversal of the wavefront path tracer's NEE connections, alone and fused with the next bounce's
+// closest-hit pass (trace_closest.hip has the frame's kernel sequence).
+#include "trace_loop.h"
+#include "variants.h"
+
+namespace rt {
+// ---------------------------------------------------------------------------------------------------------
+// K5c: shadow traversal of the NEE connections of one bounce; unoccluded contributions are added to the
+// path's radiance in the fixed order light, environment (RENDER_SPEC §6)
+// ---------------------------------------------------------------------------------------------------------
+template <bool COUNT, bool STAGED, bool ALPHA, bool INST, bool GROUPS>
+__global__ void __launch_bounds__(kTraverseThreads, STAGED ? kTraverseWavesPerSimdStaged : kTraverseWavesPerSimd)
+k_trace_shadow(SceneView sv, Queues q, PathState ps, Control* __restrict__ ctl, uint32_t depth, uint32_t kind, uint2* __restrict__ spill_base,
+               uint32_t refill) {
+  const TraverseLds lds = stage_bvh<STAGED, INST>(sv, g_smem);
+  const uint32_t n = ctl->sizes.n_shadow[kind][depth];
+  uint2* spill = lane_spill(spill_base);
+  StepCounters sc;
+  auto src = shadow_source<ALPHA, GROUPS>(q, ps, kind);
+  persistent_trace<true, COUNT, STAGED, ALPHA, INST>(sv, lds, spill, &ctl->work_shadow[kind], n, refill, src, sc);
+  if (COUNT) flush_counters(ctl, 1, sc);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// K5c + K5a in one launch: the shadow passes of bounce d and the closest-hit traversal of bounce d + 1.  They are independent (a light
+// connection only adds to its path's L, an environment connection to its Le, the closest-hit pass only reads the ray queue shade(d)
+// wrote) and every persistent launch ends in a tail of a few long rays during which most of the chip idles — a fixed cost that weighs
+// more the smaller the launch (late bounces, a rank's share of a strong-scaled frame; 10-20 % of the wave slots of a configs[3] launch).
+// Here a wave that finds one queue dry moves straight on to the next: one tail instead of three.  (Launches side by side on two streams
+// do not achieve this: each takes the chip from the other all the time, profiles/r02_experiments.txt.)  Not used by updates that carry
+// per-launch timing events or counting kernels.
+// ---------------------------------------------------------------------------------------------------------
+template <bool STAGED, bool ALPHA, bool INST, bool GROUPS>
+__global__ void __launch_bounds__(kTraverseThreads, STAGED ? kTraverseWavesPerSimdStaged : kTraverseWavesPerSimd)
+k_trace_shadow_then_batch(SceneView sv, const Tri* __restrict__ tris_any, Queues q, PathState ps, Control* __restrict__ ctl, uint32_t depth,
+                          uint32_t kinds, const hala_ray* __restrict__ rays, hala_hit* __restrict__ hits, uint2* __restrict__ spill_base, uint32_t refill) {
+  const TraverseLds lds = stage_bvh<STAGED, INST>(sv, g_smem);
+  uint2* spill = lane_spill(spill_base);
+  StepCounters sc;
+  {
+    SceneView sva = sv;
+    sva.tris = tris_any;  // RENDER_SPEC 7.1d (STAGED: the launcher only fuses when both passes traverse the same triangles)
+    for (uint32_t kind = 0; kind < 2u; ++kind) {  // bit 0: light connections, bit 1: environment connections
+      if (!((kinds >> kind) & 1u)) continue;
+      auto src = shadow_source<ALPHA, GROUPS>(q, ps, kind);
+      persistent_trace<true, false, STAGED, ALPHA, INST>(sva, lds, spill, &ctl->work_shadow[kind], ctl->sizes.n_shadow[kind][depth], refill, src, sc);
+    }
+  }
+  if (rays == nullptr) return;  // the last bounce: its two shadow passes share the launch, no closest-hit pass follows
+  const uint32_t n = ctl->sizes.n_active[depth + 1u];
+  if (blockIdx.x == 0 && threadIdx.x == 0) ctl->totals.rays_closest += n;
+  BatchSource src{rays, hits, false, true, STAGED && refill == 64u};
+  persistent_trace<false, false, STAGED, false, INST>(sv, lds, spill, &ctl->work_closest, n, refill, src, sc);
+}
+uint32_t trace_shadow_blocks_per_cu(size_t dynamic_lds_bytes, TreeForm tree) {
+  return tree_blocks_per_cu([](auto STAGED, auto INST) { return k_trace_shadow<false, STAGED, false, INST, false>; }, tree, kTraverseThreads, dynamic_lds_bytes);
+}
+
+void launch_trace_shadow(const LaunchCfg& lc, const SceneView& sv0, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth,
+                         uint32_t kind, bool count, hipStream_t s) {
+  SceneView sv = sv0;
+  sv.tris = sv0.tris_any;  // RENDER_SPEC 7.1d: shadow rays traverse the copy in which invisible surfaces are degenerate and translucent ones flagged
+  const TreeForm tree = tree_form(sv);
+  // light groups (RENDER_SPEC §14): only the light connections carry a group
+  dispatch<kFamilyTraceShadow>([&](auto COUNT, auto ALPHA, auto STAGED, auto INST, auto GROUPS) {
+    hipLaunchKernelGGL((k_trace_shadow<COUNT, STAGED, ALPHA, INST, GROUPS>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv, q, ps,
+                       ctl, depth, kind, lc.spill, lc.refill);
+  }, count, sv.any_translucent != 0u, tree == TreeForm::Staged, tree == TreeForm::TwoLevel, kind == 0u && ps.groups != nullptr);
+}
+
+// the fused launch; false: the caller must issue the two launches separately (an LDS-staged scene whose any-hit rays traverse a
+// different triangle copy than its closest-hit rays: only one of them is staged)
+bool launch_trace_shadow_then_batch(const LaunchCfg& lc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth,
+                                    uint32_t kinds, bool with_closest, hipStream_t s) {
+  const TreeForm tree = tree_form(sv);
+  if (tree == TreeForm::Staged && sv.tris_any != sv.tris) return false;
+  const hala_ray* rays = with_closest ? q.rays[(depth + 1u) & 1u] : nullptr;
+  dispatch<kFamilyTraceShadowThenBatch>([&](auto ALPHA, auto STAGED, auto INST, auto GROUPS) {
+    hipLaunchKernelGGL((k_trace_shadow_then_batch<STAGED, ALPHA, INST, GROUPS>), dim3(lc.persistent_blocks), dim3(kTraverseThreads), lc.smem, s, sv,
+                       sv.tris_any, q, ps, ctl, depth, kinds, rays, q.hits, lc.spill, lc.refill);
+  }, sv.any_translucent != 0u, tree == TreeForm::Staged, tree == TreeForm::TwoLevel, (kinds & 1u) != 0u && ps.groups != nullptr);
+  return true;
+}
+
+}  // namespace rt

@@ -52,9 +52,7 @@ constexpr int kLeafSlots = RT_LEAF_SLOTS;  // consumer lanes per leaf item = the
 constexpr int kCoopItems = 64 * 4;
 constexpr size_t kCoopBytesPerWave = (size_t)kCoopItems * 8 + 64 * 16;
 
-// LDS is addressed through explicit address-space-3 pointers to builtin vectors: a generic pointer kept in a struct makes hipcc emit
-// flat_load / flat_store (both memory pipes, both wait counters) instead of ds_read / ds_write.
-#define RT_LDS __attribute__((address_space(3)))
+// the RT_LDS pointers of rt_math.h, to builtin vectors
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -245,9 +243,6 @@ struct StepCounters {
   uint32_t nodes = 0, tris = 0, leaf_lanes = 0, leaf_passes = 0, wave_steps = 0;
 };
 
-RT_DI uint32_t mbcnt64(unsigned long long m) {  // number of set bits of m below this lane
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 RT_DI float lane_read(uint32_t src_lane_x4, float v) {  // v of lane src_lane_x4 / 4 (ds_bpermute_b32: every lane of the wave must take part)
   return __int_as_float(__builtin_amdgcn_ds_bpermute((int)src_lane_x4, __float_as_int(v)));
 }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Static instruction census of one kernel of integrator.hip, attributed to source functions and lines (no GPU needed).
-Compiles the translation unit with -gline-tables-only into a scratch directory, disassembles the gfx950 code object with source
+"""Static instruction census of one kernel of the path tracer (trace_closest.hip, trace_shadow.hip, shade.hip, resolve.hip),
+attributed to source functions and lines (no GPU needed).
+Compiles the unit that defines the kernel with -gline-tables-only into a scratch directory, disassembles the gfx950 code object with source
 line markers and counts vector / LDS / memory instructions per inlined function and per line.  This is how the node step of
 traverse.h was put on its diet in round 3 (profiles/r03_experiments.txt): the counts are static — a branch that is rarely taken
 counts in full — so read them next to the PMC figures of profiles/*_pmc_*.txt.
@@ -21,6 +22,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hala-renderer_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
+UNITS = ("trace_closest.hip", "trace_shadow.hip", "shade.hip", "resolve.hip")
 
 
 def code_object(obj, out):
@@ -46,15 +48,24 @@ def functions(path):
     return out
 
 
+def unit_of(want):
+    """the unit that defines the kernel `want` names (a mangled name holds the kernel's name, too)"""
+    m = re.search(r"k_[a-z_]+", want)
+    for unit in UNITS:
+        if m and re.search(r"\b%s\(" % m.group(0), open(os.path.join(CSRC, unit)).read()):
+            return unit
+    raise SystemExit("no unit of " + ", ".join(UNITS) + " defines a kernel named in " + want)
+
+
 def main():
     if len(sys.argv) < 2:
         raise SystemExit(__doc__)
     want = sys.argv[1]
     tmp = tempfile.mkdtemp(prefix="isa_attr_")
-    obj = os.path.join(tmp, "integrator.o")
+    obj = os.path.join(tmp, "unit.o")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-mfma",
-                           "-gline-tables-only", "-x", "hip", "-c", os.path.join(CSRC, "integrator.hip"), "-o", obj])
-    co = os.path.join(tmp, "integrator.co")
+                           "-gline-tables-only", "-x", "hip", "-c", os.path.join(CSRC, unit_of(want)), "-o", obj])
+    co = os.path.join(tmp, "unit.co")
     code_object(obj, co)
     dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "-l", "--mcpu=gfx950", co], capture_output=True, text=True, check=True).stdout.split("\n")
     start = end = None

@@ -1,4 +1,4 @@
-"""Every compiled instantiation of the six flag-dispatched kernel families (csrc/integrator.hip `with_flags`: k_trace_primary,
+"""Every compiled instantiation of the six flag-dispatched kernel families (csrc/variants.h `dispatch`: k_trace_primary,
 k_trace_batch, k_trace_shadow, k_trace_shadow_then_batch, k_shade, k_resolve) is launched here on the smallest scene that selects it and
 compared with the oracle bit for bit.  Which instantiations exist and which a process has launched comes from the library's own ledger
 (hala_rt_variant_ledger), so a new launch flag doubles a `built` mask and the closing test of this module fails until a case reaches
@@ -37,10 +37,10 @@ NAMES = ("accum", "albedo", "normal", "final")
 # Built instantiations no scene can select: {family: {bit: the lines that make the combination impossible}}.  At most 4 bits.
 UNREACHABLE = {
     3: {
-        # k_trace_shadow_then_batch<ALPHA, STAGED, !INST, GROUPS>, flags in with_flags order (ALPHA, STAGED, INST, GROUPS)
+        # k_trace_shadow_then_batch<ALPHA, STAGED, !INST, GROUPS>, flags in dispatch order (ALPHA, STAGED, INST, GROUPS)
         0b0011: "ALPHA = sv.any_translucent: a material of any-hit class >= 2, which also sets any_invisible (rt_trees.hip attach_any_triangles: "
                 "`r->any_invisible = r->any_invisible || cls[i] != 0`), so sv.tris_any is the separate d_tris_any copy (renderer_state.h view(): "
-                "`sv.tris_any = any_invisible ? d_tris_any.ptr : d_tris.ptr`) and integrator.hip launch_trace_shadow_then_batch returns false "
+                "`sv.tris_any = any_invisible ? d_tris_any.ptr : d_tris.ptr`) and trace_shadow.hip launch_trace_shadow_then_batch returns false "
                 "before it launches: `if (tree == TreeForm::Staged && sv.tris_any != sv.tris) return false;`",
         0b1011: "the same with GROUPS: the refusal comes before the flags are looked at",
     },
@@ -100,7 +100,7 @@ def possible(c):
 
 
 def expected_bits(c):
-    """per family, the instantiations the case launches (renderer.hip issue_bounces / finish_update, rt_rays.hip, integrator.hip launchers)"""
+    """per family, the instantiations the case launches (renderer.hip issue_bounces / finish_update, rt_rays.hip, the launchers of trace_closest.hip, trace_shadow.hip, shade.hip, resolve.hip)"""
     staged, inst = c.tree == "staged", c.tree == "inst"
     simple, scatter = c.mode == "simple", c.mode == "scatter"
     e = [0] * len(FAMILIES)
