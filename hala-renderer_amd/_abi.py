@@ -311,6 +311,9 @@ DEFORM_NORMALS_AS_POSED, DEFORM_NORMALS_RECOMPUTED = 0, 1
 
 # argtypes / restype of the denoise, adaptive sampling, view and AOV entry points (load_library installs them)
 PROTOTYPES = {
+    "hala_rt_trace_rays_multi": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
+    "hala_rt_trace_rays_multi_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32], C.c_int),
+    "hala_rtprog_trace_rays_multi": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
     "hala_rt_denoise": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
     "hala_rt_read_denoised": ([C.c_void_p, C.POINTER(C.c_float)], C.c_int),
@@ -443,4 +446,6 @@ EXPORTS = [
     "hala_rt_set_refit_policy", "hala_rt_get_tree_quality",
     "hala_rt_variant_ledger",
     "hala_rt_selftest_math", "hala_rt_selftest_math_values",
+    "hala_rt_trace_rays_multi", "hala_rt_trace_rays_multi_host", "hala_rtprog_trace_rays_multi",
 ]
+MAX_MULTI_HITS = 16  # HALA_MAX_MULTI_HITS (RENDER_SPEC 4.7)

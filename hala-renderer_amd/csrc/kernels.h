@@ -39,6 +39,11 @@ void launch_trace_primary(const LaunchCfg& lc, const SceneView& sv, const FrameC
 // RENDER_SPEC 4.2 around a caller's batch: out = the batch with far origins re-based, moved[i] = how far; then moved[i] back on the closest hits' t
 void launch_rebase_batch(const SceneView& sv, const hala_ray* rays, hala_ray* out, float* moved, uint32_t n, hipStream_t s);
 void launch_unbase_hits(hala_hit* hits, const float* moved, uint32_t n, hipStream_t s);
+// trace_multi.hip — RENDER_SPEC 4.7: the k nearest hits of each of n rays, sorted, at hits[i * k ..]; counts (or null) gets the number found.
+// The kernel has its own LDS size and occupancy; its grid never exceeds lc.persistent_blocks (the spill area).  false: it fits no compute unit.
+bool launch_trace_multi(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_count, const hala_ray* rays, hala_hit* hits, uint32_t* counts,
+                        uint32_t n, uint32_t k, WorkCounters* work, hipStream_t s);
+void launch_unbase_multi(hala_hit* hits, const float* moved, uint32_t n, uint32_t k, hipStream_t s);  // moved[i] back on every record of ray i
 // shade.hip
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s);
 // resolve.hip

@@ -30,6 +30,49 @@ int hala_rt_trace_rays(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_
   RT_HIP(hipGetLastError());
   return HALA_OK;
 }
+// RENDER_SPEC 4.7: the contract of hala_rt_trace_rays (scratch, stream order, the renderer's own re-based copy of the batch) around the
+// multi-hit kernel; the distance a far ray was moved comes back on every record of its list
+int hala_rt_trace_rays_multi(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_hits, uint32_t* d_counts, uint32_t count, uint32_t k, void* hip_stream) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  if (k == 0 || k > HALA_MAX_MULTI_HITS) RT_FAIL("The multi-hit capacity must be 1.." + std::to_string(HALA_MAX_MULTI_HITS) + ".");
+  if (count == 0) return HALA_OK;
+  if (!d_rays || !d_hits) RT_FAIL("The ray batch is null!");
+  if ((uint64_t)count * k > (1ull << 32)) RT_FAIL("The multi-hit batch is too large.");
+  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : r->stream;
+  if (r->scratch.acquire(s) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
+  if (r->d_batch_rays.count < count) { RT_HIP(r->d_batch_rays.resize(count)); RT_HIP(r->d_batch_moved.resize(count)); }
+  const SceneView sv = r->view();
+  launch_rebase_batch(sv, d_rays, r->d_batch_rays.ptr, r->d_batch_moved.ptr, count, s);
+  const bool fits = launch_trace_multi(r->lcfg, sv, r->cu_count, r->d_batch_rays.ptr, d_hits, d_counts, count, k, r->d_batch_work.ptr, s);
+  if (fits) launch_unbase_multi(d_hits, r->d_batch_moved.ptr, count, k, s);
+  if (!r->scratch.batch_done) RT_HIP(hipEventCreateWithFlags(&r->scratch.batch_done, hipEventDisableTiming));
+  RT_HIP(hipEventRecord(r->scratch.batch_done, s));
+  r->scratch.event = r->scratch.batch_done; r->scratch.stream = s;
+  if (!fits) RT_FAIL("The multi-hit traversal kernel does not fit on a compute unit.");
+  RT_HIP(hipGetLastError());
+  return HALA_OK;
+}
+int hala_rt_trace_rays_multi_host(hala_rt_renderer* r, const hala_ray* rays, hala_hit* hits, uint32_t* counts, uint32_t count, uint32_t k) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  if (k == 0 || k > HALA_MAX_MULTI_HITS) RT_FAIL("The multi-hit capacity must be 1.." + std::to_string(HALA_MAX_MULTI_HITS) + ".");
+  if (count == 0) return HALA_OK;
+  if (!rays || !hits) RT_FAIL("The ray batch is null!");
+  if ((uint64_t)count * k > (1ull << 32)) RT_FAIL("The multi-hit batch is too large.");
+  DeviceArray<hala_ray> d_rays;
+  DeviceArray<hala_hit> d_hits;
+  DeviceArray<uint32_t> d_counts;
+  RT_HIP(d_rays.upload(rays, count, r->stream));
+  RT_HIP(d_hits.resize((size_t)count * k));
+  if (counts) RT_HIP(d_counts.resize(count));
+  if (hala_rt_trace_rays_multi(r, d_rays.ptr, d_hits.ptr, counts ? d_counts.ptr : nullptr, count, k, r->stream) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipMemcpyAsync(hits, d_hits.ptr, (size_t)count * k * sizeof(hala_hit), hipMemcpyDeviceToHost, r->stream));
+  if (counts) RT_HIP(hipMemcpyAsync(counts, d_counts.ptr, (size_t)count * 4, hipMemcpyDeviceToHost, r->stream));
+  RT_HIP(hipStreamSynchronize(r->stream));
+  return HALA_OK;
+}
 int hala_rt_trace_rays_indirect(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_hits, const uint32_t* d_indirect, int mode, void* hip_stream) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (!d_indirect) RT_FAIL("The indirect command address is null!");
@@ -218,6 +261,14 @@ int hala_rtprog_trace_rays(hala_rtprog* p, uint32_t width, uint32_t height, uint
   const uint64_t n = (uint64_t)width * height * depth;
   if (n > 0xffffffffull) RT_FAIL("The launch is too large.");
   return hala_rt_trace_rays(p->renderer, p->d_rays, p->d_hits, (uint32_t)n, rtprog_mode(p), nullptr, hip_stream);
+}
+// RENDER_SPEC 4.7 on the bound batch (its hit buffer holds width * height * depth * k records); the constant block is not consulted
+int hala_rtprog_trace_rays_multi(hala_rtprog* p, uint32_t width, uint32_t height, uint32_t depth, uint32_t k, uint32_t* d_counts, void* hip_stream) {
+  if (!p) RT_FAIL("The program handle is null!");
+  if (!p->d_rays || !p->d_hits) RT_FAIL("The program is not bound to a ray batch.");
+  const uint64_t n = (uint64_t)width * height * depth;
+  if (n > 0xffffffffull) RT_FAIL("The launch is too large.");
+  return hala_rt_trace_rays_multi(p->renderer, p->d_rays, p->d_hits, d_counts, (uint32_t)n, k, hip_stream);
 }
 int hala_rtprog_trace_rays_indirect(hala_rtprog* p, const uint32_t* d_indirect, void* hip_stream) {  // :338-340
   if (!p) RT_FAIL("The program handle is null!");

@@ -112,6 +112,11 @@ class HalaRayTracingProgram:
         """:330-332"""
         self._check(self._lib.hala_rtprog_trace_rays(self._h, C.c_uint32(width), C.c_uint32(height), C.c_uint32(depth), C.c_void_p(stream or None)))
 
+    def trace_rays_multi(self, width: int, height: int, depth: int, k: int, d_counts: int = 0, stream: int = 0):
+        """RENDER_SPEC 4.7 on the bound batch: its hit buffer holds width * height * depth * k records; the constant block is not consulted"""
+        self._check(self._lib.hala_rtprog_trace_rays_multi(self._h, C.c_uint32(width), C.c_uint32(height), C.c_uint32(depth), C.c_uint32(k),
+                                                           C.c_void_p(d_counts or None), C.c_void_p(stream or None)))
+
     def trace_rays_indirect(self, indirect_device_address: int, stream: int = 0):
         """:338-340"""
         self._check(self._lib.hala_rtprog_trace_rays_indirect(self._h, C.c_void_p(indirect_device_address), C.c_void_p(stream or None)))

@@ -517,6 +517,22 @@ class HalaRenderer:
         """device-pointer form: the vkCmdTraceRaysKHR analogue for one ray batch (src/rt_renderer.rs:458-464)"""
         self._check(self._lib.hala_rt_trace_rays(self._h, C.c_void_p(d_rays), C.c_void_p(d_hits), C.c_uint32(count), C.c_int(mode), C.c_void_p(d_counters), C.c_void_p(stream)))
 
+    def trace_rays_multi_host(self, rays: np.ndarray, k: int, want_counts=True):
+        """RENDER_SPEC 4.7: (hits[n, k], counts[n]) — the k nearest hits of every ray by (t, triangle id), padded with miss records;
+        counts is None with want_counts=False (the library then gets a null counts pointer)"""
+        rays = np.ascontiguousarray(rays, dtype=A.RAY_DTYPE)
+        n = rays.shape[0]
+        hits = np.empty((n, max(int(k), 0)), dtype=A.HIT_DTYPE)
+        counts = np.zeros(n, dtype=np.uint32) if want_counts else None
+        self._check(self._lib.hala_rt_trace_rays_multi_host(self._h, C.c_void_p(rays.ctypes.data), C.c_void_p(hits.ctypes.data),
+                                                            C.c_void_p(counts.ctypes.data) if want_counts else None, C.c_uint32(n), C.c_uint32(k)))
+        return hits, counts
+
+    def trace_rays_multi(self, d_rays: int, d_hits: int, count: int, k: int, d_counts: int = 0, stream: int = 0):
+        """device-pointer form of RENDER_SPEC 4.7: d_hits holds count * k records, d_counts (or 0) count words"""
+        self._check(self._lib.hala_rt_trace_rays_multi(self._h, C.c_void_p(d_rays), C.c_void_p(d_hits), C.c_void_p(d_counts), C.c_uint32(count), C.c_uint32(k),
+                                                       C.c_void_p(stream)))
+
     def bvh_info(self) -> A.BvhInfo:
         i = A.BvhInfo()
         self._check(self._lib.hala_rt_get_bvh_info(self._h, C.byref(i)))

@@ -841,6 +841,21 @@ int hala_rt_trace_rays_indirect(hala_rt_renderer* r, const hala_ray* d_rays, hal
 int hala_rt_trace_rays_host(hala_rt_renderer* r, const hala_ray* rays, hala_hit* hits, uint32_t count,
                             int mode, uint64_t counters[2]);
 
+/* Multi-hit ray batches (RENDER_SPEC 4.7): the k nearest hits of every ray, 1 <= k <= HALA_MAX_MULTI_HITS.  Ray i gets the records
+ * d_hits[i*k .. i*k + k): every triangle the test of 4.2 accepts inside (tmin, tmax), ascending by t, equal t by ascending triangle id,
+ * cut after k; the rest of the slice are miss records {-1, 0, 0, HALA_INVALID_INDEX}.  d_counts (device, `count` words, or NULL) gets
+ * the number of hit records of each ray; a count equal to k means "possibly more".  Materials play no part (an invisible or translucent
+ * triangle is a triangle), k = 1 is mode 0 of hala_rt_trace_rays bit for bit, and the answer does not depend on how the tree was built.
+ * Everything else is the contract of hala_rt_trace_rays: a committed scene, count == 0 a no-op, the renderer's scratch and its stream
+ * order, the scene as it stands at the renderer's shutter step, far origins re-based in the renderer's own copy of the batch (every
+ * reported t is the distance from the origin as given).  Refused with a message and without touching anything: k outside 1..16, a null
+ * batch, no committed scene, count * k beyond 2^32 records.  A caller who continues a full list with tmin = the last t loses the other
+ * triangles at exactly that t. */
+#define HALA_MAX_MULTI_HITS 16
+int hala_rt_trace_rays_multi(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_hits /* count*k */, uint32_t* d_counts /* or NULL */,
+                             uint32_t count, uint32_t k, void* hip_stream);
+int hala_rt_trace_rays_multi_host(hala_rt_renderer* r, const hala_ray* rays, hala_hit* hits, uint32_t* counts, uint32_t count, uint32_t k);
+
 /* BVH introspection for the oracle cross-check: 64-B nodes + 48-B triangles as laid out in HBM.
  * node_width is 4: compressed 4-wide nodes (docs/RENDER_SPEC.md §4.1b). */
 typedef struct hala_bvh_info {
@@ -1342,6 +1357,9 @@ int hala_rtprog_push_constants(hala_rtprog* p, uint32_t offset, const void* data
 int hala_rtprog_push_constants_f32(hala_rtprog* p, uint32_t offset, const float* data, size_t count);
 int hala_rtprog_trace_rays(hala_rtprog* p, uint32_t width, uint32_t height, uint32_t depth, void* hip_stream);
 int hala_rtprog_trace_rays_indirect(hala_rtprog* p, const uint32_t* d_indirect, void* hip_stream);
+/* hala_rt_trace_rays_multi on the bound batch: width*height*depth rays, k records each (the bound hit buffer holds that many).  The
+ * constant block is not consulted: word 0 keeps selecting the behaviour of hala_rtprog_trace_rays only. */
+int hala_rtprog_trace_rays_multi(hala_rtprog* p, uint32_t width, uint32_t height, uint32_t depth, uint32_t k, uint32_t* d_counts, void* hip_stream);
 
 const char* hala_version(void);
 

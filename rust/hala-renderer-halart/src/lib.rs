@@ -91,6 +91,8 @@ pub mod sys {
   pub struct hala_deformer_normals_info { pub mode: u32, pub class_count: u32, pub entry_count: u32, pub reserved: u32, pub launches: u64 }
   pub const HALA_DEFORM_NORMALS_AS_POSED: u32 = 0;
   pub const HALA_DEFORM_NORMALS_RECOMPUTED: u32 = 1;
+  /// the largest capacity of a multi-hit batch (RENDER_SPEC 4.7)
+  pub const HALA_MAX_MULTI_HITS: u32 = 16;
   #[repr(C)] pub struct hala_scene { _private: [u8; 0] }
   #[repr(C)] pub struct hala_rtprog { _private: [u8; 0] }
   extern "C" {
@@ -120,6 +122,9 @@ pub mod sys {
                               d_counters: *mut u64, hip_stream: *mut c_void) -> c_int;
     pub fn hala_rt_trace_rays_indirect(r: *mut hala_rt_renderer, d_rays: *const hala_ray, d_hits: *mut hala_hit, d_indirect: *const u32,
                                        mode: c_int, hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_trace_rays_multi(r: *mut hala_rt_renderer, d_rays: *const hala_ray, d_hits: *mut hala_hit, d_counts: *mut u32, count: u32, k: u32,
+                                    hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_trace_rays_multi_host(r: *mut hala_rt_renderer, rays: *const hala_ray, hits: *mut hala_hit, counts: *mut u32, count: u32, k: u32) -> c_int;
     pub fn hala_rt_update_node_transform(r: *mut hala_rt_renderer, node_index: u32, local_transform: *const f32) -> c_int;
     pub fn hala_rt_update_material(r: *mut hala_rt_renderer, material_index: u32, material: *const hala_material_desc) -> c_int;
     pub fn hala_rt_update_vertices(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, vertices: *const hala_vertex, vertex_count: u32) -> c_int;
@@ -150,6 +155,7 @@ pub mod sys {
     pub fn hala_rtprog_push_constants_f32(p: *mut hala_rtprog, offset: u32, data: *const f32, count: usize) -> c_int;
     pub fn hala_rtprog_trace_rays(p: *mut hala_rtprog, width: u32, height: u32, depth: u32, hip_stream: *mut c_void) -> c_int;
     pub fn hala_rtprog_trace_rays_indirect(p: *mut hala_rtprog, d_indirect: *const u32, hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rtprog_trace_rays_multi(p: *mut hala_rtprog, width: u32, height: u32, depth: u32, k: u32, d_counts: *mut u32, hip_stream: *mut c_void) -> c_int;
     pub fn hala_rt_tile_buffer(r: *mut hala_rt_renderer, which: c_int, d_ptr: *mut *mut c_void, bytes: *mut usize) -> c_int;
     pub fn hala_rt_scatter_gathered_tiles(r: *mut hala_rt_renderer, which: c_int, d_gathered: *const c_void, bytes: usize) -> c_int;
     pub fn hala_rt_scatter_gathered_tiles_on_stream(r: *mut hala_rt_renderer, which: c_int, d_gathered: *const c_void, bytes: usize, hip_stream: *mut c_void) -> c_int;
@@ -440,6 +446,11 @@ impl<'a> HalaRayTracingProgram<'a> {
   /// :338-340
   pub fn trace_rays_indirect(&self, indirect_device_address: u64) -> Result<(), HalaRendererError> {
     check(unsafe { sys::hala_rtprog_trace_rays_indirect(self.h, indirect_device_address as *const u32, std::ptr::null_mut()) })
+  }
+  /// RENDER_SPEC 4.7: the k nearest hits of every ray of the bound batch (its hit buffer holds width * height * depth * k records);
+  /// `d_counts`: a device array of one word per ray, or null
+  pub fn trace_rays_multi(&self, width: u32, height: u32, depth: u32, k: u32, d_counts: *mut u32) -> Result<(), HalaRendererError> {
+    check(unsafe { sys::hala_rtprog_trace_rays_multi(self.h, width, height, depth, k, d_counts, std::ptr::null_mut()) })
   }
 }
 impl<'a> Drop for HalaRayTracingProgram<'a> { fn drop(&mut self) { unsafe { sys::hala_rtprog_destroy(self.h) } } }
