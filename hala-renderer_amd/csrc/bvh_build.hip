@@ -9,8 +9,10 @@
 //   hierarchy   a binary tree over the triangles (bvh_build_impl.h: HierarchyJob): >= 4096 triangles: top-down full-sweep SAH
 //               (bvh_sah.hip) | below: 60-bit Morton codes -> rocPRIM radix sort -> Karras 2012 LBVH (here) |
 //               hala_rt_build_options::builder = 2: PLOC over the Morton order, the fast large-scene build (bvh_ploc.hip)
-//   collapse    subtrees of <= leaf_max triangles become leaves; top-down into 4-wide nodes, breadth-first, by surface area.  The 4-wide
-//               topology is what is kept; the binary tree is scratch of the build
+//   collapse    the cheapest 4-wide tree the hierarchy holds: a bottom-up pass prices, per binary node and per number of parent slots,
+//               every cut (node visits and leaf items weighted by surface area; a leaf holds <= leaf_max triangles), then the 4-nodes
+//               are filled top-down from the recorded choices, breadth-first.  The same rule for every hierarchy and for the instance
+//               levels.  The 4-wide topology is what is kept; the binary tree is scratch of the build
 //   pack levels one launch per level, deepest first: 64-B compressed nodes (8-bit child boxes quantised conservatively against the
 //               node's own box, RENDER_SPEC §4.1b; bvh_node_pack.h).  The same pass after a build and after a refit
 //   refit       (north_star; the reference only rebuilds) re-flatten + re-pack on the frozen topology
@@ -249,11 +251,114 @@ __global__ void __launch_bounds__(256) k_fit(BinaryTree tree, const Box6* __rest
   }
 }
 
-__global__ void __launch_bounds__(256) k_keep_flags(const uint32_t* __restrict__ first, const uint32_t* __restrict__ last, uint32_t n_internal,
-                                                     uint32_t leaf_max, uint32_t* __restrict__ keep) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_internal) return;
-  keep[i] = (last[i] - first[i] + 1u) > leaf_max ? 1u : 0u;
+// ---- which cut of the binary tree becomes the 4-wide tree -----------------------------------------------------------------------------
+// A ray that enters a 4-node pays one node visit (one lane of the node phase); a ray that enters a leaf pays one leaf item (four lanes of
+// the cooperative pass, however full the leaf is).  With the chance of entering taken as the fitted box's half area, a 4-wide tree costs
+//   sum over inner nodes of A * kCollapseNodeCost  +  sum over leaves of A * kCollapseLeafCost
+// and the cheapest tree over a binary hierarchy is found bottom-up.  For a binary node n of c(n) triangles, C(n, j) = the cheapest way
+// to stand n's subtree in at most j slots of a parent:
+//   D(n, j) = min over 1 <= k < j of C(left, k) + C(right, j - k)                       j = 2, 3, 4: n is opened, its children share the slots
+//   C(n, 1) = min(A(n) * kCollapseLeafCost if c(n) <= leaf_max, A(n) * kCollapseNodeCost + D(n, 4))     one slot: a leaf, or a 4-node of its own
+//   C(n, j) = min(D(n, j), C(n, j - 1))                                                  j = 2, 3
+// A single triangle (item) is a leaf in one slot whatever it is offered.  Ties: the leaf before the inner node, the smaller k, and D(n, j)
+// before C(n, j - 1) (an opened node is one visit fewer) — the tree is a pure function of the hierarchy.  Every sum is one binary32
+// addition of two costs, every product one multiplication (the build has no contraction), so tests/collapse_ref.py repeats it bit for bit.
+// Only the ratio of the two constants matters.  Static counts put it between 1.2 and 2.2 (a node visit: one lane of a ~200-instruction
+// phase that runs at ~52 lanes; a leaf item: four lanes of a ~75-instruction pass at ~36 lanes), but the frame time of configs[3] is flat
+// from 1.2 to 20 (7.77 - 7.82 ms, profiles/collapse_cost.txt): a dearer leaf buys fewer triangle tests with more node visits at the same
+// price.  8 is kept for what the tests need from the trees: from 7 up the 600 000-triangle scene of tests/test_tree_quality.py keeps
+// more nodes than one pass of k_tree_cost's grid, from 10 up the Cornell box gets a sixth node and configs[1] is slower.
+// (make EXTRA="-DRT_COLLAPSE_LEAF_COST=2.0f" VARIANT=_r20 builds another ratio beside the library, like every tuning build.)
+#ifndef RT_COLLAPSE_LEAF_COST
+#define RT_COLLAPSE_LEAF_COST 8.0f
+#endif
+constexpr float kCollapseNodeCost = 1.0f, kCollapseLeafCost = RT_COLLAPSE_LEAF_COST;
+// choice word of a binary node: bit 0 = C(n, 1) is the inner node (keep); bits 2-3 / 4-5 = the k of C(n, 2) / C(n, 3), 0 = "as with one
+// slot fewer"; bits 6-7 = the k of D(n, 4)
+constexpr uint32_t kChoiceInner = 1u, kChoiceShift2 = 2u, kChoiceShift3 = 4u, kChoiceShift4 = 6u;
+
+// cost[3 * p + j - 1] = C(p, j), choice[p], keep[p] (1 where the node, offered one slot, is an inner 4-node) of one binary node whose
+// children are done
+RT_DI void collapse_cost_node(const BinaryTree& tree, const Box6* __restrict__ leaf_box, uint32_t p, uint32_t leaf_max, float* cost,
+                              uint32_t* __restrict__ choice, uint32_t* __restrict__ keep) {
+  const uint32_t ref[2] = {tree.left[p], tree.right[p]};
+  float c[2][3];
+#pragma unroll
+  for (int side = 0; side < 2; ++side) {
+    if (ref[side] & kLeafBit) {
+      c[side][0] = c[side][1] = c[side][2] = half_area(leaf_box[ref[side] & ~kLeafBit]) * kCollapseLeafCost;
+    } else {
+      const volatile float* src = cost + 3u * (size_t)ref[side];
+      c[side][0] = src[0]; c[side][1] = src[1]; c[side][2] = src[2];
+    }
+  }
+  const float d2 = c[0][0] + c[1][0];
+  float d3 = c[0][0] + c[1][1], d4 = c[0][0] + c[1][2];
+  uint32_t k3 = 1u, k4 = 1u;
+  { const float v = c[0][1] + c[1][0]; if (v < d3) { d3 = v; k3 = 2u; } }
+  { const float v = c[0][1] + c[1][1]; if (v < d4) { d4 = v; k4 = 2u; } }
+  { const float v = c[0][2] + c[1][0]; if (v < d4) { d4 = v; k4 = 3u; } }
+  const float area = half_area(tree.node_box[p]);
+  const float as_leaf = area * kCollapseLeafCost, as_inner = area * kCollapseNodeCost + d4;
+  const bool inner = !((tree.last[p] - tree.first[p] + 1u) <= leaf_max && as_leaf <= as_inner);
+  const float c1 = inner ? as_inner : as_leaf;
+  const bool open2 = d2 <= c1;
+  const float c2 = open2 ? d2 : c1;
+  const bool open3 = d3 <= c2;
+  const float c3 = open3 ? d3 : c2;
+  volatile float* dst = cost + 3u * (size_t)p;
+  dst[0] = c1; dst[1] = c2; dst[2] = c3;
+  choice[p] = (inner ? kChoiceInner : 0u) | ((open2 ? 1u : 0u) << kChoiceShift2) | ((open3 ? k3 : 0u) << kChoiceShift3) | (k4 << kChoiceShift4);
+  keep[p] = inner ? 1u : 0u;
+}
+
+// Bottom-up over the binary tree, every node once.  With one fenced device-scope arrival per leaf and per node the pass took 5.09 ms
+// for 1 M triangles, as it stands 0.85 ms (profiles/collapse_cost.txt): the bottom of the tree goes without arrivals.  A treelet = a
+// node of at most kTreeletMax triangles whose parent has more; ONE thread walks it in post-order along the parent links (no stack, no
+// fence: it reads what it wrote).  Above the treelets k_fit's pattern: whoever finishes a child arrives at the parent, the second to arrive owns it and goes on;
+// nobody waits.  Producer: stores -> __threadfence -> atomic arrival; consumer: atomic arrival -> __threadfence -> loads.
+// Threads 0 .. n - 1 stand for the leaves (a leaf arrives for itself where its parent is above the treelets), n .. 2 n - 2 for the nodes.
+constexpr uint32_t kTreeletMax = 32u;
+__global__ void __launch_bounds__(256) k_collapse_cost(BinaryTree tree, const Box6* __restrict__ leaf_box, uint32_t* arrivals, uint32_t n,
+                                                        uint32_t leaf_max, float* cost, uint32_t* __restrict__ choice, uint32_t* __restrict__ keep) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= 2u * n - 1u) return;
+  uint32_t p;
+  if (g < n) {
+    p = tree.leaf_parent[g];
+    if (tree.last[p] - tree.first[p] + 1u <= kTreeletMax) return;  // inside a treelet
+  } else {
+    const uint32_t root = g - n;
+    if (tree.last[root] - tree.first[root] + 1u > kTreeletMax) return;
+    p = tree.node_parent[root];
+    if (p != kAbsent && tree.last[p] - tree.first[p] + 1u <= kTreeletMax) return;  // inside a treelet, not its root
+    uint32_t node = root;
+    int from = 0;  // 0: from the parent, 1: the left child is done, 2: both are
+    for (;;) {
+      if (from == 0) {
+        const uint32_t l = tree.left[node];
+        if (!(l & kLeafBit)) { node = l; continue; }
+        from = 1;
+      }
+      if (from == 1) {
+        const uint32_t r = tree.right[node];
+        if (!(r & kLeafBit)) { node = r; from = 0; continue; }
+      }
+      collapse_cost_node(tree, leaf_box, node, leaf_max, cost, choice, keep);
+      if (node == root) break;
+      const uint32_t up = tree.node_parent[node];
+      from = tree.left[up] == node ? 1 : 2;
+      node = up;
+    }
+  }
+  while (p != kAbsent) {
+    __threadfence();
+    const uint32_t old = atomicAdd(&arrivals[p], 1u);
+    if (old == 0u) return;
+    __threadfence();
+    collapse_cost_node(tree, leaf_box, p, leaf_max, cost, choice, keep);
+    p = tree.node_parent[p];
+  }
 }
 
 // ---- 4-wide nodes (RENDER_SPEC §4.1b) -----------------------------------------------------------------------------------------------
@@ -267,15 +372,15 @@ RT_DI uint32_t leaf_ref_of(uint32_t first, uint32_t count, const uint32_t* __res
 
 // Top-down collapse of the binary tree into 4-wide nodes, one BFS level per launch, so that node indices come out in
 // breadth-first order (the first `lds_nodes` nodes — the slice the traversal kernels stage in LDS — are the top of the
-// tree, which every ray visits).  The 4-node rooted at binary node i starts with i's two children and opens, while a
-// slot is free, (1) the kept inner child of largest surface area, then (2) the collapsed leaf of largest surface area
-// (splitting a leaf costs no bytes: the slot exists anyway, and two tighter boxes cull more triangle tests).
+// tree, which every ray visits).  The 4-node rooted at binary node i is the cut k_collapse_cost recorded for D(i, 4): i's children
+// share the four slots as its choice word says, and every child that was given more than one slot is opened, or not, as its own
+// word says for that many — at most three openings, left to right.  A child left in one slot is a leaf or the root of a 4-node (keep).
 // refs4[node] = the binary-tree references its slots were filled from — the frozen topology refit re-packs from.
 // The level kernels take the level's first node and size from device memory (level[0], level[1]; k_level_advance closes a level):
 // the host only knows an upper bound of the size — the grid — and looks at the counters every few levels.
 __global__ void __launch_bounds__(256) k_collapse_level(const uint32_t* __restrict__ root_of, const uint32_t* __restrict__ level, uint32_t bound,
-                                                         BinaryTree tree, const uint32_t* __restrict__ keep, uint4* __restrict__ refs4,
-                                                         uint32_t* __restrict__ cnt) {
+                                                         BinaryTree tree, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ choice,
+                                                         uint4* __restrict__ refs4, uint32_t* __restrict__ cnt) {
   const uint32_t* left = tree.left;
   const uint32_t* right = tree.right;
   const Box6* node_box = tree.node_box;
@@ -284,25 +389,29 @@ __global__ void __launch_bounds__(256) k_collapse_level(const uint32_t* __restri
   const uint32_t base = level[0], size = level[1];
   if (j >= size) { cnt[j] = 0u; return; }  // the scan runs over the host's bound
   const uint32_t i = root_of[base + j];
-  uint32_t c[4] = {left[i], right[i], kAbsent, kAbsent};
-  int n = 2;
-  for (int phase = 0; phase < 2; ++phase) {
-    while (n < 4) {
-      int pick = -1;
-      float best = -1.0f;
-      for (int k = 0; k < n; ++k) {
-        const uint32_t r = c[k];
-        if (r & kLeafBit) continue;
-        if ((keep[r] != 0u) != (phase == 0)) continue;
-        const float a = half_area(node_box[r]);
-        if (a > best) { best = a; pick = k; }
-      }
-      if (pick < 0) break;
-      const uint32_t r = c[pick];
-      for (int k = n; k > pick + 1; --k) c[k] = c[k - 1];
-      c[pick] = left[r]; c[pick + 1] = right[r];
-      ++n;
+  uint32_t c[4] = {kAbsent, kAbsent, kAbsent, kAbsent};
+  int n = 0;
+  uint32_t wait_ref[4], wait_slots[4];  // right siblings and the slots they were given
+  int waiting = 0;
+  uint32_t r = i, slots = 4u;
+  bool opened = false;  // the root of the 4-node is opened whatever it says of itself
+  for (;;) {
+    uint32_t k = 0u;
+    if (!(r & kLeafBit) && slots > 1u) {
+      const uint32_t w = choice[r];
+      k = (w >> (slots == 2u ? kChoiceShift2 : (slots == 3u ? kChoiceShift3 : kChoiceShift4))) & 3u;
+      if (k == 0u && opened) { --slots; continue; }  // as with one slot fewer
+      if (k == 0u || k >= slots) k = 1u;             // (no word the cost pass writes comes here)
     }
+    if (k != 0u && waiting < 4) {
+      wait_ref[waiting] = right[r]; wait_slots[waiting] = slots - k; ++waiting;
+      r = left[r]; slots = k; opened = true;
+      continue;
+    }
+    if (n < 4) c[n++] = r;
+    if (waiting == 0) break;
+    --waiting;
+    r = wait_ref[waiting]; slots = wait_slots[waiting];
   }
   // Slot order = the order in which an any-hit ray of a large tree takes the inner children (RENDER_SPEC 4.4c): the kept inner children
   // by descending surface area, then the leaves in the order the opening left them.  configs[3]: 9.09 instead of 9.40 node visits per
@@ -410,7 +519,7 @@ DevList BuildScratch::plan(uint32_t n, bool morton) {
   size_t scan_bytes = 0, sort_bytes = 0;
   (void)exclusive_sum(nullptr, scan_bytes, nullptr, nullptr, ni, 0);
   DevList all = {left.of(ni), right.of(ni), node_parent.of(ni), leaf_parent.of(n), arrivals.of(ni), root_of.of(ni), cnt.of(ni), off.of(ni),
-                 level.of(4), bases.of(kMaxLevels), scan_tmp.of(scan_bytes)};
+                 cost.of(3 * ni), choice.of(ni), level.of(4), bases.of(kMaxLevels), scan_tmp.of(scan_bytes)};
   if (morton) {
     (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr,
                                     (uint32_t*)nullptr, n, 0, 64, 0);
@@ -475,11 +584,13 @@ std::string fit_hierarchy(const BinaryTree& tree, const Box6* leaf_box, uint32_t
 }
 
 // Chooses the 4-wide topology from the fitted binary tree (keep, refs4, index4, level_base) and with it the node count, the depth and
-// the stack a ray can need.  Levels are driven like PLOC's rounds: {first node, size, level} on the device, the host looks every few
+// the stack a ray can need: the cost pass prices every cut, the level launches walk the cheapest one down from the root.  Levels are driven like PLOC's rounds: {first node, size, level} on the device, the host looks every few
 // levels; between two looks the grid covers the largest size the level can have reached (a level is at most 4 times the one above, and < n).
 std::string collapse(BvhBuffers& b, BvhTopology& t, BuildScratch& sc, const BinaryTree& tree, hipStream_t s) {
   const uint32_t ni = b.tri_count - 1;
-  hipLaunchKernelGGL(k_keep_flags, dim3(nblk(ni)), dim3(256), 0, s, t.first, t.last, ni, t.leaf_max, t.keep);
+  HIP_TRY(hipMemsetAsync(sc.arrivals, 0, (size_t)ni * 4, s));
+  hipLaunchKernelGGL(k_collapse_cost, dim3(nblk(2u * b.tri_count - 1u)), dim3(256), 0, s, tree, t.leaf_box, sc.arrivals, b.tri_count, t.leaf_max, sc.cost, sc.choice,
+                     t.keep);
   static const uint32_t zero = 0;
   HIP_TRY(hipMemcpyAsync(sc.root_of, &zero, 4, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(t.index4, &zero, 4, hipMemcpyHostToDevice, s));
@@ -491,7 +602,7 @@ std::string collapse(BvhBuffers& b, BvhTopology& t, BuildScratch& sc, const Bina
     unsigned long long bound = now[1];
     for (uint32_t k = 0; k < look_every; ++k) {
       const uint32_t bd = (uint32_t)std::min<unsigned long long>(bound, ni);
-      hipLaunchKernelGGL(k_collapse_level, dim3(nblk(bd)), dim3(256), 0, s, sc.root_of, sc.level, bd, tree, t.keep, t.refs4, sc.cnt);
+      hipLaunchKernelGGL(k_collapse_level, dim3(nblk(bd)), dim3(256), 0, s, sc.root_of, sc.level, bd, tree, t.keep, sc.choice, t.refs4, sc.cnt);
       size_t tb = sc.scan_tmp.bytes;
       HIP_TRY(exclusive_sum(sc.scan_tmp.raw, tb, sc.cnt.get(), sc.off.get(), bd, s));
       hipLaunchKernelGGL(k_scatter_level, dim3(nblk(bd)), dim3(256), 0, s, sc.root_of, sc.level, t.refs4, t.keep, sc.off, t.index4);
@@ -534,6 +645,39 @@ hipError_t exclusive_sum(void* storage, size_t& bytes, const uint32_t* in, uint3
 }
 
 void bvh_free_topology(void* topo) { delete static_cast<BvhTopology*>(topo); }
+
+// the buffers of a build, the caller's tree in the place of a builder's, then collapse() as every build calls it
+std::string collapse_selftest(const CollapseSelftest& job) {
+  const uint32_t n = job.n, ni = n - 1;
+  hipStream_t s = nullptr;
+  BvhTopology t;
+  t.n = n; t.leaf_max = job.leaf_max;
+  BuildScratch sc;
+  std::string e = alloc_all(t.plan());
+  if (e.empty()) e = alloc_all(sc.plan(n, false));
+  if (!e.empty()) return e;
+  HIP_TRY(hipMemcpyAsync(sc.left, job.left, (size_t)ni * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(sc.right, job.right, (size_t)ni * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(sc.node_parent, job.node_parent, (size_t)ni * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(sc.leaf_parent, job.leaf_parent, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(t.first, job.first, (size_t)ni * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(t.last, job.last, (size_t)ni * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(t.box4, job.node_boxes, (size_t)ni * sizeof(Box6), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(t.leaf_box, job.leaf_boxes, (size_t)n * sizeof(Box6), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(t.refs4, 0xff, (size_t)ni * sizeof(uint4), s));
+  BvhBuffers b{};
+  b.tri_count = n;
+  const BinaryTree tree{sc.left, sc.right, t.first, t.last, sc.node_parent, sc.leaf_parent, t.box4};
+  if (!(e = collapse(b, t, sc, tree, s)).empty()) return e;
+  HIP_TRY(hipGetLastError());
+  if (job.costs) HIP_TRY(hipMemcpy(job.costs, sc.cost, (size_t)ni * 12, hipMemcpyDeviceToHost));
+  if (job.choices) HIP_TRY(hipMemcpy(job.choices, sc.choice, (size_t)ni * 4, hipMemcpyDeviceToHost));
+  if (job.keep) HIP_TRY(hipMemcpy(job.keep, t.keep, (size_t)ni * 4, hipMemcpyDeviceToHost));
+  if (job.refs4) HIP_TRY(hipMemcpy(job.refs4, t.refs4, (size_t)ni * sizeof(uint4), hipMemcpyDeviceToHost));
+  if (job.node_count) *job.node_count = b.node_count;
+  if (job.levels) *job.levels = b.max_depth;
+  return "";
+}
 
 std::string bvh_build(BvhBuffers& b, uint32_t leaf_max, hipStream_t s) {
   const uint32_t n = b.tri_count;

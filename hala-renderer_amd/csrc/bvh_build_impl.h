@@ -161,7 +161,7 @@ constexpr uint32_t kMaxLevels = 96;  // 4-wide levels a tree may have
 struct BvhTopology {
   Arena arena;  // first member: destroyed last, after the buffers carved from it
   uint32_t n = 0, leaf_max = 0;
-  Dev<uint32_t> first, last, keep;  // per binary node: its sorted positions; 1 = has more than leaf_max triangles (an inner 4-node child)
+  Dev<uint32_t> first, last, keep;  // per binary node: its sorted positions; 1 = in one slot of a parent it is an inner 4-node, 0 = a leaf (k_collapse_cost)
   Dev<uint4> refs4;                 // per 4-node: the binary references its slots were filled from
   Dev<uint32_t> index4;             // per kept binary node: the 4-node it is the root of
   Dev<uint32_t> sorted_ids;         // triangle id of every sorted position
@@ -182,6 +182,8 @@ struct BvhTopology {
 // What only the build needs, released when it returns: the binary tree but for first / last, the Morton sort, the collapse's counters.
 struct BuildScratch {
   Dev<uint32_t> left, right, node_parent, leaf_parent, arrivals, root_of, cnt, off, level, bases, ids_in;
+  Dev<float> cost;       // [3 (n - 1)] k_collapse_cost: C(node, 1..3)
+  Dev<uint32_t> choice;  // [n - 1] ... and the cut that gives them
   Dev<unsigned long long> keys_in, keys_out;
   Dev<char> sort_tmp, scan_tmp;  // rocPRIM's
   DevList plan(uint32_t n, bool morton);

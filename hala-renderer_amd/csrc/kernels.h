@@ -118,6 +118,15 @@ std::string bvh_refit(BvhBuffers& b, hipStream_t s);
 // absolute (inner: += node_offset, leaf: first triangle += tri_offset).  After every bvh_build / bvh_refit of such a tree.
 std::string bvh_relocate(BvhBuffers& b, uint32_t node_offset, uint32_t tri_offset, hipStream_t s);
 void bvh_free_topology(void* topology);
+// hala_rt_selftest_collapse (halart.h): the collapse of a build on a binary tree from host memory, already checked by the caller
+struct CollapseSelftest {
+  uint32_t n, leaf_max;
+  const uint32_t *left, *right, *node_parent, *leaf_parent, *first, *last;
+  const float *node_boxes, *leaf_boxes;
+  float* costs;
+  uint32_t *choices, *keep, *refs4, *node_count, *levels;
+};
+std::string collapse_selftest(const CollapseSelftest& job);
 
 // bvh_quality.hip — the tree cost of RENDER_SPEC 4.6 of the tree of `node_count` nodes whose root is `root` (references may be absolute:
 // only boxes, presence, the leaf bit and the leaf counts are read): out3[0] = node_q, out3[1] = tri_q, out3[2] = valid (all three 0 for

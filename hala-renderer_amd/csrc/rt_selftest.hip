@@ -1,10 +1,14 @@
 // rt_selftest.hip — hala_rt_selftest_math: the exact-math helpers of rt_math.h (rcp_rn, sqrt_rn) against the plain IEEE expressions they
 // stand for, over any range of the 2^32 binary32 bit patterns.  A unary float function has few enough inputs to be proven by enumeration;
-// tests/test_exact_math.py runs all of them.
+// tests/test_exact_math.py runs all of them.  hala_rt_selftest_collapse: the collapse of bvh_build.hip on a binary tree the caller hands over
+// (tests/test_collapse_cost.py against tests/collapse_ref.py).
 #include <algorithm>
+#include <string>
+#include <vector>
 
 #include "../../include/halart.h"
 #include "host_util.h"
+#include "kernels.h"
 #include "rt_math.h"
 
 namespace rt {
@@ -72,9 +76,59 @@ static int selftest_math(int which, uint32_t first, uint64_t count, const uint32
   return HALA_OK;
 }
 
+// The kernels index by what the tree says: nothing is uploaded before every reference, parent and range has been followed here.
+static int selftest_collapse(const CollapseSelftest& job) {
+  const uint32_t n = job.n;
+  if (n < 2u || n > (1u << 20)) RT_FAIL("hala_rt_selftest_collapse: the tree must have 2 .. 2^20 leaves.");
+  if (job.leaf_max < 1u || job.leaf_max > 8u || job.leaf_max >= n) RT_FAIL("hala_rt_selftest_collapse: leaf_max must be 1 .. 8 and below the leaf count.");
+  if (!job.left || !job.right || !job.node_parent || !job.leaf_parent || !job.first || !job.last || !job.node_boxes || !job.leaf_boxes)
+    RT_FAIL("hala_rt_selftest_collapse: an input array is null!");
+  if (!all_finite(job.node_boxes, (size_t)(n - 1u) * 6u) || !all_finite(job.leaf_boxes, (size_t)n * 6u))
+    RT_FAIL("hala_rt_selftest_collapse: a box is not finite.");
+  const uint32_t leaf_bit = 0x80000000u;
+  std::vector<uint8_t> node_seen(n - 1u, 0), leaf_seen(n, 0);
+  std::vector<uint32_t> todo{0u};
+  if (job.node_parent[0] != 0xffffffffu) RT_FAIL("hala_rt_selftest_collapse: node 0 must be the root.");
+  node_seen[0] = 1;
+  uint32_t nodes = 0, leaves = 0;
+  while (!todo.empty()) {
+    const uint32_t i = todo.back();
+    todo.pop_back();
+    ++nodes;
+    uint32_t lo[2], hi[2];
+    const uint32_t ref[2] = {job.left[i], job.right[i]};
+    for (int side = 0; side < 2; ++side) {
+      const uint32_t c = ref[side] & ~leaf_bit;
+      if (ref[side] & leaf_bit) {
+        if (c >= n || leaf_seen[c] || job.leaf_parent[c] != i) RT_FAIL("hala_rt_selftest_collapse: a leaf reference is out of range, repeated or has another parent.");
+        leaf_seen[c] = 1; ++leaves;
+        lo[side] = hi[side] = c;
+      } else {
+        if (c >= n - 1u || node_seen[c] || job.node_parent[c] != i) RT_FAIL("hala_rt_selftest_collapse: a node reference is out of range, repeated or has another parent.");
+        node_seen[c] = 1; todo.push_back(c);
+        lo[side] = job.first[c]; hi[side] = job.last[c];
+      }
+    }
+    if (job.first[i] != lo[0] || job.last[i] != hi[1] || hi[0] + 1u != lo[1] || lo[0] > hi[0] || lo[1] > hi[1] || hi[1] >= n)
+      RT_FAIL("hala_rt_selftest_collapse: a node's sorted positions are not those of its children, left then right.");
+  }
+  if (nodes != n - 1u || leaves != n) RT_FAIL("hala_rt_selftest_collapse: the root does not reach every node and leaf.");
+  const std::string e = collapse_selftest(job);
+  if (!e.empty()) RT_FAIL(e);
+  return HALA_OK;
+}
+
 }  // namespace rt
 
 extern "C" {
+
+int hala_rt_selftest_collapse(uint32_t leaves, uint32_t leaf_max, const uint32_t* left, const uint32_t* right, const uint32_t* node_parent,
+                              const uint32_t* leaf_parent, const uint32_t* first, const uint32_t* last, const float* node_boxes,
+                              const float* leaf_boxes, float* costs, uint32_t* choices, uint32_t* keep, uint32_t* refs4, uint32_t* node_count,
+                              uint32_t* levels) {
+  return rt::selftest_collapse(rt::CollapseSelftest{leaves, leaf_max, left, right, node_parent, leaf_parent, first, last, node_boxes, leaf_boxes, costs,
+                                                    choices, keep, refs4, node_count, levels});
+}
 
 int hala_rt_selftest_math(int which, uint32_t first, uint64_t count, uint64_t* mismatches, uint32_t* first_bad) {
   return rt::selftest_math(which, first, count, nullptr, nullptr, nullptr, mismatches, first_bad);

@@ -942,6 +942,28 @@ def selftest_math_values(which, patterns):
     return helper, ref, bad.value
 
 
+def selftest_collapse(left, right, node_parent, leaf_parent, first, last, node_boxes, leaf_boxes, leaf_max):
+    """hala_rt_selftest_collapse: the collapse of a build (cost pass, then the level launches) on a binary tree from host arrays — child
+    references with bit 31 for a leaf, parents (0xffffffff: the root, node 0), sorted positions first .. last per node, boxes [.., 6].
+    -> dict(costs [n - 1, 3] float32 = C(node, 1 .. 3), choices [n - 1], keep [n - 1], refs4 [node_count, 4], levels)."""
+    from . import check, load_library
+    u32 = lambda x: np.ascontiguousarray(x, dtype=np.uint32)  # noqa: E731
+    left, right, node_parent, leaf_parent, first, last = (u32(x) for x in (left, right, node_parent, leaf_parent, first, last))
+    node_boxes, leaf_boxes = (np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 6) for x in (node_boxes, leaf_boxes))
+    n = leaf_parent.size
+    if n < 2 or any(x.size != n - 1 for x in (left, right, node_parent, first, last)) or len(node_boxes) != n - 1 or len(leaf_boxes) != n:
+        raise ValueError("a tree of n leaves has n - 1 inner nodes")
+    costs = np.zeros((n - 1, 3), dtype=np.float32)
+    choices, keep = np.zeros(n - 1, dtype=np.uint32), np.zeros(n - 1, dtype=np.uint32)
+    refs4 = np.zeros((n - 1, 4), dtype=np.uint32)
+    count, levels = C.c_uint32(0), C.c_uint32(0)
+    ptr = lambda x: C.c_void_p(x.ctypes.data)  # noqa: E731
+    check(load_library().hala_rt_selftest_collapse(C.c_uint32(n), C.c_uint32(leaf_max), ptr(left), ptr(right), ptr(node_parent), ptr(leaf_parent),
+                                                   ptr(first), ptr(last), ptr(node_boxes), ptr(leaf_boxes), ptr(costs), ptr(choices), ptr(keep),
+                                                   ptr(refs4), C.byref(count), C.byref(levels)))
+    return dict(costs=costs, choices=choices, keep=keep, refs4=refs4[:count.value].copy(), levels=levels.value)
+
+
 def denoise_images(color, albedo, normal, device_ordinal=0, **params) -> np.ndarray:
     """hala_denoise_images: the RENDER_SPEC 10 filter on host images [H, W, 3 or 4] (e.g. the PFM trio of save_images); returns the
     denoised RGBA32F [H, W, 4].  params: iterations, sigma_color, sigma_albedo, normal_power, demodulate."""

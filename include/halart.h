@@ -698,6 +698,19 @@ int hala_rt_variant_ledger(uint32_t family, uint64_t* launched, uint64_t* built,
 int hala_rt_selftest_math(int which, uint32_t first, uint64_t count, uint64_t* mismatches, uint32_t* first_bad);
 int hala_rt_selftest_math_values(int which, const uint32_t* patterns, uint32_t count, uint32_t* helper_bits, uint32_t* reference_bits,
                                  uint64_t* mismatches, uint32_t* first_bad);
+/* Self-test of the collapse of a binary hierarchy into 4-wide nodes (csrc/bvh_build.hip: k_collapse_cost, k_collapse_level) on a small
+ * tree from host memory: `leaves` >= 2 leaves at sorted positions 0 .. leaves - 1 and leaves - 1 inner nodes, node 0 the root.
+ * left / right [leaves - 1]: child references (bit 31 set: the leaf at that sorted position, else an inner node); node_parent
+ * [leaves - 1] (0xffffffff for the root) and leaf_parent [leaves]; first / last [leaves - 1]: the sorted positions below each node;
+ * node_boxes [leaves - 1][6] and leaf_boxes [leaves][6]: min xyz, max xyz.  The tree is checked on the host (every node and leaf reached
+ * once from the root, parents and ranges consistent, finite boxes); 1 <= leaf_max <= 8, leaf_max < leaves <= 2^20.  Runs the cost pass
+ * and the level launches exactly as a build does and returns, where the pointer is not null: costs [leaves - 1][3] = C(node, 1 .. 3),
+ * choices [leaves - 1] (the choice words), keep [leaves - 1], refs4 [leaves - 1][4] of which the first *node_count rows are the 4-nodes
+ * in breadth-first order (0xffffffff: an empty slot), *levels.  Runs on the calling thread's current device and needs no renderer. */
+int hala_rt_selftest_collapse(uint32_t leaves, uint32_t leaf_max, const uint32_t* left, const uint32_t* right, const uint32_t* node_parent,
+                              const uint32_t* leaf_parent, const uint32_t* first, const uint32_t* last, const float* node_boxes,
+                              const float* leaf_boxes, float* costs, uint32_t* choices, uint32_t* keep, uint32_t* refs4, uint32_t* node_count,
+                              uint32_t* levels);
 /* Frames in flight.  Consecutive updates are independent except for the order in which their samples are folded into the accumulated
  * images, so updates without per-launch timing or counting alternate between two frame slots, each with its own stream, control block,
  * stack spill area, per-path state and queues: update k + 1 starts beside the last bounces of update k (its dense camera-ray launch and

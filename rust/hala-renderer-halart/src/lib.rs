@@ -166,6 +166,10 @@ pub mod sys {
     pub fn hala_rt_selftest_math(which: c_int, first: u32, count: u64, mismatches: *mut u64, first_bad: *mut u32) -> c_int;
     pub fn hala_rt_selftest_math_values(which: c_int, patterns: *const u32, count: u32, helper_bits: *mut u32, reference_bits: *mut u32,
                                         mismatches: *mut u64, first_bad: *mut u32) -> c_int;
+    pub fn hala_rt_selftest_collapse(leaves: u32, leaf_max: u32, left: *const u32, right: *const u32, node_parent: *const u32,
+                                     leaf_parent: *const u32, first: *const u32, last: *const u32, node_boxes: *const f32,
+                                     leaf_boxes: *const f32, costs: *mut f32, choices: *mut u32, keep: *mut u32, refs4: *mut u32,
+                                     node_count: *mut u32, levels: *mut u32) -> c_int;
     pub fn hala_rt_set_frames_in_flight(r: *mut hala_rt_renderer, n: u32) -> c_int;
     pub fn hala_rt_frames_in_flight_info(r: *mut hala_rt_renderer, second_slot_updates: *mut u64, second_buffers: *mut u32) -> c_int;
     pub fn hala_rt_set_build_options(r: *mut hala_rt_renderer, options: *const hala_rt_build_options) -> c_int;
