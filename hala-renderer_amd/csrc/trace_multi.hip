@@ -1,7 +1,8 @@
 // trace_multi.hip — multi-hit ray batches (RENDER_SPEC 4.7): the k nearest hits of every ray of a batch, ordered by (t, triangle id).
-// One persistent traversal kernel in the three tree forms of trace_closest.hip (LDS-staged, large one-level, two-level), over the same
-// dequeue (trace_loop.h: work_begin / work_take), the same LDS layout and stack with its spill (stage_bvh, lane_spill), the same slab test
-// and key order (4.4b) and the same triangle tests (tri_test2 on staged trees, tri_test_od on the others).  What differs from the
+// One persistent traversal kernel in the three tree forms of trace_closest.hip (LDS-staged, large one-level, two-level), over the dequeue
+// of trace_loop.h (work_begin / work_take) and the building blocks of traverse.h: the LDS layout (stage_bvh), the per-lane stack with its
+// spill (LaneStack), the instance transitions (enter_instance / leave_instance), the child test with the key order of 4.4b
+// (test_children) and the triangle tests (leaf_walk_staged on staged trees, tri_test_od on the others).  What differs from the
 // closest-hit traversal is the limit a ray culls with: the t of its k-th entry once it holds k hits, its tmax until then.
 //
 // Where the k entries live: in the ray's own slice of the output array, hits[i * k .. i * k + k), kept sorted while the ray is traced;
@@ -64,75 +65,18 @@ RT_DI void multi_done(const MultiTrav& t, uint32_t k, uint32_t* counts) {
   if (counts) counts[t.idx] = t.n;
 }
 
-// One node visit of a lane that holds a ray (traverse.h: trav_step without the any-hit, counting and wave-cooperative parts); true when
-// the ray is finished.  The children are tested, keyed and sorted exactly as there; every leaf in reach is tested by the lane itself,
-// nearest first, while it stays in reach of the limit.
+// One node visit of a lane that holds a ray; true when the ray is finished.  The stack, the way into and out of an instance, the child
+// test with its keys and order, and the paired leaf walk of staged trees are traverse.h's (LaneStack, enter_instance / leave_instance,
+// test_children, leaf_walk_staged), with the list's limit where the closest-hit traversal culls with best.t; every leaf in reach is
+// tested by the lane itself, nearest first, while it stays in reach of the limit.
 template <bool STAGED, bool INST>
 RT_DI bool multi_step(const SceneView& sv, const TraverseLds& lds, uint2* spill, MultiTrav& t, uint32_t k) {
   static_assert(!(INST && STAGED), "LDS-staged trees have no instance levels");
-  constexpr int kS = stack_lds<STAGED, INST>();
-  RT_LDS u32x2* stack = lds.stack + threadIdx.x;
-  int sp = t.sp;
-  auto pop = [&]() -> uint2 {
-    --sp;
-    if (sp < kS) { const u32x2 v = stack[sp * kTraverseThreads]; return make_uint2(v.x, v.y); }
-    return spill[sp - kS];
-  };
-  auto push = [&](uint32_t a, uint32_t b) {
-    if (sp < kS) stack[sp * kTraverseThreads] = u32x2{a, b}; else spill[sp - kS] = make_uint2(a, b);
-    ++sp;
-  };
-  // RENDER_SPEC 4.5, as in trav_step: the world-space ray is parked under an exit mark while the lane is inside an instance
-  auto enter_instance = [&](uint32_t leaf) -> uint32_t {
-    const float4* ip = reinterpret_cast<const float4*>(sv.inst_refs + (leaf & 0x0fffffffu));
-    const float4 i0 = ip[0], i1 = ip[1], i2 = ip[2], i3 = ip[3];
-    push(__float_as_uint(t.r.o.x), __float_as_uint(t.r.o.y));
-    push(__float_as_uint(t.r.o.z), __float_as_uint(t.r.d.x));
-    push(__float_as_uint(t.r.d.y), __float_as_uint(t.r.d.z));
-    push(0u, kExitRef);
-    const f3 r0 = mk3(i0.x, i0.y, i0.z), r1 = mk3(i0.w, i1.x, i1.y), r2 = mk3(i1.z, i1.w, i2.x), tr = mk3(i2.y, i2.z, i2.w);
-    const f3 tv = t.r.o - tr, d = t.r.d;
-    t.r = make_ray(mk3(dot3(r0, tv), dot3(r1, tv), dot3(r2, tv)), mk3(dot3(r0, d), dot3(r1, d), dot3(r2, d)), t.r.tmin);
-    t.gid_base = __float_as_uint(i3.y);
-    return __float_as_uint(i3.x);
-  };
-  auto leave_instance = [&]() {
-    const uint2 c2 = pop(), c1 = pop(), c0 = pop();
-    t.r = make_ray(mk3(__uint_as_float(c0.x), __uint_as_float(c0.y), __uint_as_float(c1.x)),
-                   mk3(__uint_as_float(c1.y), __uint_as_float(c2.x), __uint_as_float(c2.y)), t.r.tmin);
-    t.gid_base = 0u;
-  };
+  LaneStack<STAGED, INST> st{lds.stack + threadIdx.x, spill, t.sp};
+  uint32_t shade_base;  // (the records of 4.7 carry triangle ids only)
   const RayPre r = t.r;
   uint32_t ref[4], key[4];
-  {
-    float4 q0, q1, q2, q3;
-    if (STAGED) { const RT_LDS f32x4* p = lds.nodes + (size_t)t.cur * 4; q0 = ld4(p); q1 = ld4(p + 1); q2 = ld4(p + 2); q3 = ld4(p + 3); }
-    else { const float4* p = reinterpret_cast<const float4*>(sv.nodes) + (size_t)t.cur * 4; q0 = p[0]; q1 = p[1]; q2 = p[2]; q3 = p[3]; }
-    const uint32_t ex = __float_as_uint(q0.w);
-    const float kx = __uint_as_float((ex & 0xffu) << 23) * r.idir.x, ky = __uint_as_float(((ex >> 8) & 0xffu) << 23) * r.idir.y,
-                kz = __uint_as_float(((ex >> 16) & 0xffu) << 23) * r.idir.z;
-    const float ax = __fmaf_rn(q0.x, r.idir.x, -r.ood.x), ay = __fmaf_rn(q0.y, r.idir.y, -r.ood.y), az = __fmaf_rn(q0.z, r.idir.z, -r.ood.z);
-    const uint32_t lox = __float_as_uint(q1.x), loy = __float_as_uint(q1.y), loz = __float_as_uint(q1.z);
-    const uint32_t hix = __float_as_uint(q1.w), hiy = __float_as_uint(q2.x), hiz = __float_as_uint(q2.y);
-    ref[0] = __float_as_uint(q3.x); ref[1] = __float_as_uint(q3.y); ref[2] = __float_as_uint(q3.z); ref[3] = __float_as_uint(q3.w);
-    const bool px = r.idir.x >= 0.0f, py = r.idir.y >= 0.0f, pz = r.idir.z >= 0.0f;
-    const uint32_t nx = px ? lox : hix, fx = px ? hix : lox, ny = py ? loy : hiy, fy = py ? hiy : loy, nz = pz ? loz : hiz, fz = pz ? hiz : loz;
-    const v2f kx2 = {kx, kx}, ky2 = {ky, ky}, kz2 = {kz, kz}, ax2 = {ax, ax}, ay2 = {ay, ay}, az2 = {az, az};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {  // the slab test of 4.3b with the list's limit where the closest-hit traversal has best.t
-      const v2f tx = __builtin_elementwise_fma(v2f{ubyte_f32(nx, c), ubyte_f32(fx, c)}, kx2, ax2);
-      const v2f ty = __builtin_elementwise_fma(v2f{ubyte_f32(ny, c), ubyte_f32(fy, c)}, ky2, ay2);
-      const v2f tz = __builtin_elementwise_fma(v2f{ubyte_f32(nz, c), ubyte_f32(fz, c)}, kz2, az2);
-      const float tn = hw_maxf(hw_maxf(tx.x, ty.x), hw_maxf(tz.x, r.tmin));
-      const float tf = hw_minf(hw_minf(tx.y, ty.y), hw_minf(tz.y, t.limit));
-      const bool hit = ref[c] != kAbsent && tn <= tf * 1.0000004f;
-      const uint32_t inner_bit = INST ? ((!(ref[c] >> 31) || (ref[c] >> 28) == 0xFu) ? kInnerKey : 0u) : (~ref[c] & kInnerKey);
-      const uint32_t kc = (__float_as_uint(tn) & 0xfffffffcu) | ((uint32_t)c | inner_bit);
-      key[c] = hit ? kc : kMissKey;
-    }
-  }
-  sort2kv(key[0], key[1], ref[0], ref[1]); sort2kv(key[2], key[3], ref[2], ref[3]); sort2kv(key[0], key[2], ref[0], ref[2]);
-  sort2kv(key[1], key[3], ref[1], ref[3]); sort2kv(key[1], key[2], ref[1], ref[2]);
+  test_children<STAGED, INST>(sv, lds, r, t.cur, t.limit, ref, key);
   // the inner children that were hit: the nearest is visited next, the others wait on the stack with their keys
   bool in[4];
 #pragma unroll
@@ -140,7 +84,7 @@ RT_DI bool multi_step(const SceneView& sv, const TraverseLds& lds, uint2* spill,
 #pragma unroll
   for (int c = 3; c >= 1; --c) {
     const bool left = c == 3 ? (in[0] | in[1] | in[2]) : (c == 2 ? (in[0] | in[1]) : in[0]);
-    if (in[c] & left) push(key[c], ref[c]);
+    if (in[c] & left) st.push(key[c], ref[c]);
   }
   uint32_t next = in[0] ? ref[0] : (in[1] ? ref[1] : (in[2] ? ref[2] : (in[3] ? ref[3] : kAbsent)));
   const uint32_t next_key = in[0] ? key[0] : (in[1] ? key[1] : (in[2] ? key[2] : key[3]));
@@ -150,18 +94,11 @@ RT_DI bool multi_step(const SceneView& sv, const TraverseLds& lds, uint2* spill,
     if ((int32_t)key[c] < 0) break;
     if (!(key_tn(key[c]) <= t.limit)) break;  // a hit in a nearer leaf may have filled the list: everything behind is out of reach
     const uint32_t first = ref[c] & 0x0fffffffu, count = ((ref[c] >> 28) & 7u) + 1u;
-    if (STAGED) {  // two triangles per packed test (leaf_test_staged)
-      for (uint32_t i = 0; i < count; i += 2u) {
-        const bool two = i + 1u < count;
-        const RT_LDS f32x4* p = lds.tris + (size_t)(first + i) * 3;
-        const float4 a0 = ld4(p), b0 = ld4(p + 1), c0 = ld4(p + 2);
-        float4 a1 = a0, b1 = b0, c1 = c0;
-        if (two) { a1 = ld4(p + 3); b1 = ld4(p + 4); c1 = ld4(p + 5); }
-        bool ok[2]; float tt[2], uu[2], vv[2], dd[2];
-        tri_test2(r, a0, b0, c0, a1, b1, c1, ok, tt, uu, vv, dd);
-        if (ok[0]) multi_offer(t, k, tt[0], uu[0], vv[0], __float_as_uint(a0.w));
-        if (two && ok[1]) multi_offer(t, k, tt[1], uu[1], vv[1], __float_as_uint(a1.w));
-      }
+    if (STAGED) {
+      leaf_walk_staged(lds, r, first, count, [&](float tt, float uu, float vv, float, uint32_t id, uint32_t, uint32_t) -> bool {
+        multi_offer(t, k, tt, uu, vv, id);
+        return false;
+      });
     } else {
       const float4* tris = reinterpret_cast<const float4*>(sv.tris);
       for (uint32_t i = 0; i < count; ++i) {
@@ -176,22 +113,23 @@ RT_DI bool multi_step(const SceneView& sv, const TraverseLds& lds, uint2* spill,
   if (next != kAbsent && !(key_tn(next_key) <= t.limit)) next = kAbsent;
   for (;;) {
     if (next == kAbsent) {
-      if (sp == 0) { t.sp = 0; return true; }
-      const uint2 e = pop();
-      if (INST && e.y == kExitRef) { leave_instance(); continue; }  // the instance's tree is done: back to the world-space ray
+      if (st.sp == 0) return true;
+      const uint2 e = st.pop();
+      if (INST && e.y == kExitRef) { leave_instance(st, t.r, t.gid_base, shade_base); continue; }  // the instance's tree is done
       if (key_tn(e.x) <= t.limit) next = e.y;
       continue;
     }
-    if (INST && is_inst_leaf(next)) next = enter_instance(next);
+    if (INST && is_inst_leaf(next)) next = enter_instance(sv, st, t.r, t.gid_base, shade_base, next);
     break;
   }
   t.cur = next;
-  t.sp = sp;
+  t.sp = st.sp;
   return false;
 }
 
-// The persistent loop of trace_loop.h (persistent_trace) around multi_step: the same sharded dequeue and ballot-rank refill.  A finished
-// ray pads its slice and writes its count at once: its records are in memory already.
+// The persistent loop of trace_loop.h (persistent_trace) around multi_step, written out: the same sharded dequeue and ballot-rank refill
+// (through persistent_trace's loop made generic, frame kernels came out with other machine code: profiles/traverse_shared.txt).  A
+// finished ray pads its slice and writes its count at once: its records are in memory already.
 // (The two-level form carries the instance transitions next to the list state: at the 96 registers of 5 waves per SIMD it spilled 8 of
 // them to scratch, so it is built for 4 like the staged form.)
 template <bool STAGED, bool INST>

@@ -10,6 +10,8 @@
 // The per-lane traversal stack lives in LDS as [entry][thread] (8-B entries, conflict-free), deeper entries spill to a
 // global scratch area.  No MFMA: this is branchy scalar-per-ray work, and it is VALU-issue bound (profiles/r01_h_pmc_*):
 // what counts is the number of vector instructions per node visit and per triangle test.
+// The rules of a node visit that every ray kind must follow bit for bit (stack and spill, instance entry and exit, child test with keys and
+// order, paired LDS leaf walk) are functions of their own below, used by trav_step and by the multi-hit stepper of trace_multi.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -202,12 +204,100 @@ RT_DI void tri_test2(const RayPre& r, float4 a0, float4 b0, float4 c0, float4 a1
   t[0] = tt.x; t[1] = tt.y; u[0] = uu.x; u[1] = uu.y; v[0] = vv.x; v[1] = vv.y; dt[0] = det.x; dt[1] = det.y;
 }
 
-// LDS-staged scenes: closest-hit / any-hit test of one leaf (count <= 8 triangles from `first`, storage order; fetched and tested
-// two at a time on the packed FP32 pipe: a leaf costs ceil(count/2) LDS round trips and ceil(count/2) packed tests; 4 waves/SIMD,
-// 128 VGPRs).  ANY: true on the first accepted triangle.
-template <bool ANY, bool ALPHA>
-RT_DI bool leaf_test_staged(const SceneView& sv, const TraverseLds& lds, const RayPre& r, float tmax, uint32_t key, uint32_t tau[3], HitRec& best, uint32_t first,
-                            uint32_t count) {
+// ---- The building blocks of a node visit: each rule of RENDER_SPEC 4.3b-4.5 stands here once, for trav_step below and for the
+// multi-hit stepper (trace_multi.hip: multi_step) ----
+
+// The per-lane traversal stack: the first stack_lds<STAGED, INST>() entries in LDS ([entry][thread]), deeper ones in the lane's slice of
+// the global spill area.  `sp` is a working copy of the lane's depth: the steppers load it from their state and write it back.
+template <bool STAGED, bool INST>
+struct LaneStack {
+  RT_LDS u32x2* lds;
+  uint2* spill;
+  int sp;
+  RT_DI void push(uint32_t a, uint32_t b) {
+    constexpr int kS = stack_lds<STAGED, INST>();
+    if (sp < kS) lds[sp * kTraverseThreads] = u32x2{a, b}; else spill[sp - kS] = make_uint2(a, b);
+    ++sp;
+  }
+  RT_DI uint2 pop() {
+    constexpr int kS = stack_lds<STAGED, INST>();
+    --sp;
+    if (sp < kS) { const u32x2 v = lds[sp * kTraverseThreads]; return make_uint2(v.x, v.y); }
+    return spill[sp - kS];
+  }
+};
+// Moving a ray into an instance's object space (RENDER_SPEC 4.5): the world-space ray is parked on the stack, three entries under an exit
+// mark; returns the root of the primitive's tree.  Ids inside are local to the primitive: + gid_base = global id, + (shade_base &
+// 0x7fffffff) = shading record (bit 31 of shade_base: inside an instance).
+template <class Stack>
+RT_DI uint32_t enter_instance(const SceneView& sv, Stack& st, RayPre& r, uint32_t& gid_base, uint32_t& shade_base, uint32_t leaf) {
+  const float4* ip = reinterpret_cast<const float4*>(sv.inst_refs + (leaf & 0x0fffffffu));
+  const float4 i0 = ip[0], i1 = ip[1], i2 = ip[2], i3 = ip[3];  // r0 | r1 | r2 | tr, then root, gid_base, shade_base, inst
+  st.push(__float_as_uint(r.o.x), __float_as_uint(r.o.y));
+  st.push(__float_as_uint(r.o.z), __float_as_uint(r.d.x));
+  st.push(__float_as_uint(r.d.y), __float_as_uint(r.d.z));
+  st.push(0u, kExitRef);  // key 0: never culled (parking 1 / d as well, to spare the exit its three divisions, measured no gain: 11.86 vs 11.83 ms)
+  const f3 r0 = mk3(i0.x, i0.y, i0.z), r1 = mk3(i0.w, i1.x, i1.y), r2 = mk3(i1.z, i1.w, i2.x), tr = mk3(i2.y, i2.z, i2.w);
+  const f3 tv = r.o - tr, d = r.d;
+  r = make_ray(mk3(dot3(r0, tv), dot3(r1, tv), dot3(r2, tv)), mk3(dot3(r0, d), dot3(r1, d), dot3(r2, d)), r.tmin);
+  gid_base = __float_as_uint(i3.y); shade_base = __float_as_uint(i3.z) | 0x80000000u;
+  return __float_as_uint(i3.x);
+}
+template <class Stack>
+RT_DI void leave_instance(Stack& st, RayPre& r, uint32_t& gid_base, uint32_t& shade_base) {  // the exit mark has been popped: the world-space ray lies under it
+  const uint2 c2 = st.pop(), c1 = st.pop(), c0 = st.pop();
+  r = make_ray(mk3(__uint_as_float(c0.x), __uint_as_float(c0.y), __uint_as_float(c1.x)),
+               mk3(__uint_as_float(c1.y), __uint_as_float(c2.x), __uint_as_float(c2.y)), r.tmin);
+  gid_base = 0u; shade_base = 0u;
+}
+
+// The child test of node `node` (from LDS or from memory) against `limit`, the distance the ray culls with: ref / key come back sorted —
+// the leaves that were hit first, nearest first, then the inner children that were hit, nearest first, then the misses (kMissKey).
+template <bool STAGED, bool INST>
+RT_DI void test_children(const SceneView& sv, const TraverseLds& lds, const RayPre& r, uint32_t node, const float& limit, uint32_t (&ref)[4], uint32_t (&key)[4]) {
+  float4 q0, q1, q2, q3;
+  if (STAGED) { const RT_LDS f32x4* p = lds.nodes + (size_t)node * 4; q0 = ld4(p); q1 = ld4(p + 1); q2 = ld4(p + 2); q3 = ld4(p + 3); }
+  else { const float4* p = reinterpret_cast<const float4*>(sv.nodes) + (size_t)node * 4; q0 = p[0]; q1 = p[1]; q2 = p[2]; q3 = p[3]; }
+  // plane distances without materialising the planes: t = q * (2^e * idir) + (pmin * idir - o * idir)
+  const uint32_t ex = __float_as_uint(q0.w);
+  const float kx = __uint_as_float((ex & 0xffu) << 23) * r.idir.x, ky = __uint_as_float(((ex >> 8) & 0xffu) << 23) * r.idir.y,
+              kz = __uint_as_float(((ex >> 16) & 0xffu) << 23) * r.idir.z;
+  const float ax = __fmaf_rn(q0.x, r.idir.x, -r.ood.x), ay = __fmaf_rn(q0.y, r.idir.y, -r.ood.y), az = __fmaf_rn(q0.z, r.idir.z, -r.ood.z);
+  const uint32_t lox = __float_as_uint(q1.x), loy = __float_as_uint(q1.y), loz = __float_as_uint(q1.z);
+  const uint32_t hix = __float_as_uint(q1.w), hiy = __float_as_uint(q2.x), hiz = __float_as_uint(q2.y);
+  ref[0] = __float_as_uint(q3.x); ref[1] = __float_as_uint(q3.y); ref[2] = __float_as_uint(q3.z); ref[3] = __float_as_uint(q3.w);
+  // Slab test (§4.3b): tn = max(min(x0,x1), min(y0,y1), min(z0,z1), tmin), tf = min(max(x0,x1), ..., limit) with
+  // x0/x1 = fma(qlo/qhi, k, a).  qlo <= qhi and fma rounding is monotonic, so min(x0,x1) is simply the plane picked by the
+  // sign of the direction: select the near / far byte words once per node (6 v_cndmask) instead of 6 min/max per child,
+  // and compute (near, far) of one axis with one packed v_pk_fma_f32.  Bit-identical to the min/max form.
+  const bool px = r.idir.x >= 0.0f, py = r.idir.y >= 0.0f, pz = r.idir.z >= 0.0f;
+  const uint32_t nx = px ? lox : hix, fx = px ? hix : lox, ny = py ? loy : hiy, fy = py ? hiy : loy, nz = pz ? loz : hiz, fz = pz ? hiz : loz;
+  const v2f kx2 = {kx, kx}, ky2 = {ky, ky}, kz2 = {kz, kz}, ax2 = {ax, ax}, ay2 = {ay, ay}, az2 = {az, az};
+  // ordering key: entry distance (>= tmin >= +0, so its sign bit is free) with the child slot in its two low mantissa
+  // bits (ties -> lower slot) and the sign bit set for inner children: one sort puts the leaves first, nearest first,
+  // then the inner children, nearest first, then the misses.  hw_minf / hw_maxf are the one-instruction IEEE minNum / maxNum
+  // (v_min3 / v_max3 fuse them).
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const v2f tx = __builtin_elementwise_fma(v2f{ubyte_f32(nx, c), ubyte_f32(fx, c)}, kx2, ax2);
+    const v2f ty = __builtin_elementwise_fma(v2f{ubyte_f32(ny, c), ubyte_f32(fy, c)}, ky2, ay2);
+    const v2f tz = __builtin_elementwise_fma(v2f{ubyte_f32(nz, c), ubyte_f32(fz, c)}, kz2, az2);
+    const float tn = hw_maxf(hw_maxf(tx.x, ty.x), hw_maxf(tz.x, r.tmin));
+    const float tf = hw_minf(hw_minf(tx.y, ty.y), hw_minf(tz.y, limit));
+    const bool hit = ref[c] != kAbsent && tn <= tf * 1.0000004f;
+    const uint32_t inner_bit = INST ? ((!(ref[c] >> 31) || (ref[c] >> 28) == 0xFu) ? kInnerKey : 0u) : (~ref[c] & kInnerKey);  // instance leaves wait like inner children
+    uint32_t kc;  // (tn & ~3) | (slot | inner bit): one v_and_or_b32 (hipcc emits v_and + v_or for the C form)
+    asm("v_and_or_b32 %0, %1, -4, %2" : "=v"(kc) : "v"(__float_as_uint(tn)), "v"((uint32_t)c | inner_bit));
+    key[c] = hit ? kc : kMissKey;
+  }
+  sort2kv(key[0], key[1], ref[0], ref[1]); sort2kv(key[2], key[3], ref[2], ref[3]); sort2kv(key[0], key[2], ref[0], ref[2]);
+  sort2kv(key[1], key[3], ref[1], ref[3]); sort2kv(key[1], key[2], ref[1], ref[2]);
+}
+// LDS-staged scenes: the triangles of one leaf (count <= 8 from `first`, storage order), fetched and tested two at a time on the packed
+// FP32 pipe: a leaf costs ceil(count/2) LDS round trips and ceil(count/2) packed tests (4 waves/SIMD, 128 VGPRs).  Every triangle that
+// passes the test of 4.2 goes to accept(t, u, v, det, w of v0, w of e1, w of e2); true from it ends the walk (and is returned).
+template <class Accept>
+RT_DI bool leaf_walk_staged(const TraverseLds& lds, const RayPre& r, uint32_t first, uint32_t count, Accept&& accept) {
   for (uint32_t i = 0; i < count; i += 2u) {
     const bool two = i + 1u < count;
     const RT_LDS f32x4* p = lds.tris + (size_t)(first + i) * 3;
@@ -219,19 +309,39 @@ RT_DI bool leaf_test_staged(const SceneView& sv, const TraverseLds& lds, const R
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       if (!ok[j] || (j == 1 && !two)) continue;
+      if (accept(tt[j], uu[j], vv[j], dd[j], __float_as_uint(j ? a1.w : a0.w), __float_as_uint(j ? b1.w : b0.w), __float_as_uint(j ? c1.w : c0.w))) return true;
+    }
+  }
+  return false;
+}
+// closest-hit / any-hit test of one such leaf.  ANY: true on the first accepted triangle; its walk is written out, because through
+// leaf_walk_staged hipcc compiles the any-hit kernels differently (profiles/traverse_shared.txt).
+template <bool ANY, bool ALPHA>
+RT_DI bool leaf_test_staged(const SceneView& sv, const TraverseLds& lds, const RayPre& r, float tmax, uint32_t key, uint32_t tau[3], HitRec& best, uint32_t first,
+                            uint32_t count) {
+  if (!ANY) return leaf_walk_staged(lds, r, first, count, [&](float tt, float uu, float vv, float, uint32_t id, uint32_t, uint32_t kind) -> bool {
+    const uint32_t enc = hit_encode(id, kind);  // the record carries id << 3 | shading kind (hala_types.h; ordered like the ids)
+    if (tt > r.tmin && (tt < best.t || (tt == best.t && enc < best.prim))) { best.t = tt; best.u = uu; best.v = vv; best.prim = enc; }
+    return false;
+  });
+  for (uint32_t i = 0; i < count; i += 2u) {
+    const bool two = i + 1u < count;
+    const RT_LDS f32x4* p = lds.tris + (size_t)(first + i) * 3;
+    const float4 a0 = ld4(p), b0 = ld4(p + 1), c0 = ld4(p + 2);
+    float4 a1 = a0, b1 = b0, c1 = c0;
+    if (two) { a1 = ld4(p + 3); b1 = ld4(p + 4); c1 = ld4(p + 5); }
+    bool ok[2]; float tt[2], uu[2], vv[2], dd[2];
+    tri_test2(r, a0, b0, c0, a1, b1, c1, ok, tt, uu, vv, dd);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (!ok[j] || (j == 1 && !two)) continue;
       const uint32_t id = __float_as_uint(j ? a1.w : a0.w);
-      if (ANY) {
-        if (tt[j] > r.tmin && tt[j] < tmax) {
-          if (ALPHA && __float_as_uint(j ? b1.w : b0.w) != 0u) {  // translucent and / or the boundary of a medium (7.1d, 7.1g)
-            uint32_t q[3];
-            if (!any_hit_event(sv, key, id, id, __float_as_uint(j ? b1.w : b0.w), tt[j], dd[j], uu[j], vv[j], q)) { tau[0] += q[0]; tau[1] += q[1]; tau[2] += q[2]; continue; }
-          }
-          best.t = tt[j]; best.u = uu[j]; best.v = vv[j]; best.prim = id; return true;
+      if (tt[j] > r.tmin && tt[j] < tmax) {
+        if (ALPHA && __float_as_uint(j ? b1.w : b0.w) != 0u) {  // translucent and / or the boundary of a medium (7.1d, 7.1g)
+          uint32_t q[3];
+          if (!any_hit_event(sv, key, id, id, __float_as_uint(j ? b1.w : b0.w), tt[j], dd[j], uu[j], vv[j], q)) { tau[0] += q[0]; tau[1] += q[1]; tau[2] += q[2]; continue; }
         }
-      } else {
-        // closest hit: the record carries id << 3 | shading kind (hala_types.h: hit_encode; ordered like the ids)
-        const uint32_t enc = hit_encode(id, __float_as_uint(j ? c1.w : c0.w));
-        if (tt[j] > r.tmin && (tt[j] < best.t || (tt[j] == best.t && enc < best.prim))) { best.t = tt[j]; best.u = uu[j]; best.v = vv[j]; best.prim = enc; }
+        best.t = tt[j]; best.u = uu[j]; best.v = vv[j]; best.prim = id; return true;
       }
     }
   }
@@ -266,48 +376,17 @@ RT_DI float lane_read(uint32_t src_lane_x4, float v) {  // v of lane src_lane_x4
 template <bool ANY, bool COUNT, bool STAGED, bool ALPHA, bool INST = false>
 RT_DI bool trav_step(const SceneView& sv, const TraverseLds& lds, uint2* spill, Trav& t, bool has, StepCounters& sc) {
   static_assert(!(INST && STAGED), "LDS-staged trees have no instance levels");
-  constexpr int kS = stack_lds<STAGED, INST>();
   constexpr bool kSlotOrder = ANY;  // RENDER_SPEC 4.4c
 #ifndef RT_INST_BATCH
 #define RT_INST_BATCH 8  // configs[3] as a two-level tree: 11.05 -> 10.88 ms per frame (4 / 8 / 12 / 16 / 24: 10.94 / 10.88 / 10.88 / 10.90 / 11.04); any-hit rays lose by waiting (their paths are short): they move at once
 #endif
   constexpr int kInstBatch = (INST && !ANY) ? RT_INST_BATCH : 0;  // two-level trees: lanes per batch of instance transitions (0: each lane on its own, at once)
-  RT_LDS u32x2* stack = lds.stack + threadIdx.x;
+  LaneStack<STAGED, INST> st{lds.stack + threadIdx.x, spill, t.sp};
   const RayPre& r = t.r;
   HitRec& best = t.best;
-  int sp = t.sp;
   uint32_t ref[4] = {kAbsent, kAbsent, kAbsent, kAbsent}, key[4] = {kMissKey, kMissKey, kMissKey, kMissKey};
   uint32_t next = kAbsent, next_key = 0;
   bool lf[4] = {false, false, false, false};  // lf[k]: the k-th sorted child is a leaf in reach (a prefix: lf[k] implies lf[k - 1])
-  auto pop = [&]() -> uint2 {
-    --sp;
-    if (sp < kS) { const u32x2 v = stack[sp * kTraverseThreads]; return make_uint2(v.x, v.y); }
-    return spill[sp - kS];
-  };
-  auto push = [&](uint32_t a, uint32_t b) {
-    if (sp < kS) stack[sp * kTraverseThreads] = u32x2{a, b}; else spill[sp - kS] = make_uint2(a, b);
-    ++sp;
-  };
-  // moving a ray into an instance's object space (RENDER_SPEC 4.5): the world-space ray is parked under an exit mark; returns the root of the primitive's tree
-  auto enter_instance = [&](uint32_t leaf) -> uint32_t {
-    const float4* ip = reinterpret_cast<const float4*>(sv.inst_refs + (leaf & 0x0fffffffu));
-    const float4 i0 = ip[0], i1 = ip[1], i2 = ip[2], i3 = ip[3];  // r0 | r1 | r2 | tr, then root, gid_base, shade_base, inst
-    push(__float_as_uint(t.r.o.x), __float_as_uint(t.r.o.y));
-    push(__float_as_uint(t.r.o.z), __float_as_uint(t.r.d.x));
-    push(__float_as_uint(t.r.d.y), __float_as_uint(t.r.d.z));
-    push(0u, kExitRef);  // key 0: never culled (parking 1 / d as well, to spare the exit its three divisions, measured no gain: 11.86 vs 11.83 ms)
-    const f3 r0 = mk3(i0.x, i0.y, i0.z), r1 = mk3(i0.w, i1.x, i1.y), r2 = mk3(i1.z, i1.w, i2.x), tr = mk3(i2.y, i2.z, i2.w);
-    const f3 tv = t.r.o - tr, d = t.r.d;
-    t.r = make_ray(mk3(dot3(r0, tv), dot3(r1, tv), dot3(r2, tv)), mk3(dot3(r0, d), dot3(r1, d), dot3(r2, d)), t.r.tmin);
-    t.gid_base = __float_as_uint(i3.y); t.shade_base = __float_as_uint(i3.z) | 0x80000000u;  // bit 31: inside an instance
-    return __float_as_uint(i3.x);
-  };
-  auto leave_instance = [&]() {  // the exit mark has been popped: the world-space ray lies under it
-    const uint2 c2 = pop(), c1 = pop(), c0 = pop();
-    t.r = make_ray(mk3(__uint_as_float(c0.x), __uint_as_float(c0.y), __uint_as_float(c1.x)),
-                   mk3(__uint_as_float(c1.y), __uint_as_float(c2.x), __uint_as_float(c2.y)), t.r.tmin);
-    t.gid_base = 0u; t.shade_base = 0u;
-  };
   bool work = has;         // the lane visits a node in this step
   bool done_early = false;  // INST, batched transitions: the ray ended while leaving an instance
   if (INST && kInstBatch > 0) {
@@ -321,65 +400,50 @@ RT_DI bool trav_step(const SceneView& sv, const TraverseLds& lds, uint2* spill, 
     if ((mo | mi) != 0ull && ((uint32_t)__popcll(mo) + (uint32_t)__popcll(mi) >= (uint32_t)kInstBatch || mw == 0ull)) {
       uint32_t c = t.cur;
       if (w_out) {
-        leave_instance();
+        leave_instance(st, t.r, t.gid_base, t.shade_base);
         c = kAbsent;
         while (c == kAbsent) {  // the first entry still in reach (world level: no exit mark can follow)
-          if (sp == 0) { done_early = true; break; }
-          const uint2 e = pop();
+          if (st.sp == 0) { done_early = true; break; }
+          const uint2 e = st.pop();
           if (kSlotOrder || key_tn(e.x) <= best.t) c = e.y;
         }
       }
-      if (has && !done_early && is_inst_leaf(c)) c = enter_instance(c);
+      if (has && !done_early && is_inst_leaf(c)) c = enter_instance(sv, st, t.r, t.gid_base, t.shade_base, c);
       if (has && !done_early) t.cur = c;
     }
     work = has && !done_early && (int32_t)t.cur >= 0;
   }
   if (work) {
-    float4 q0, q1, q2, q3;
-    if (STAGED) { const RT_LDS f32x4* p = lds.nodes + (size_t)t.cur * 4; q0 = ld4(p); q1 = ld4(p + 1); q2 = ld4(p + 2); q3 = ld4(p + 3); }
-    else { const float4* p = reinterpret_cast<const float4*>(sv.nodes) + (size_t)t.cur * 4; q0 = p[0]; q1 = p[1]; q2 = p[2]; q3 = p[3]; }
     if (COUNT) sc.nodes++;
-    // plane distances without materialising the planes: t = q * (2^e * idir) + (pmin * idir - o * idir)
-    const uint32_t ex = __float_as_uint(q0.w);
-    const float kx = __uint_as_float((ex & 0xffu) << 23) * r.idir.x, ky = __uint_as_float(((ex >> 8) & 0xffu) << 23) * r.idir.y,
-                kz = __uint_as_float(((ex >> 16) & 0xffu) << 23) * r.idir.z;
-    const float ax = __fmaf_rn(q0.x, r.idir.x, -r.ood.x), ay = __fmaf_rn(q0.y, r.idir.y, -r.ood.y), az = __fmaf_rn(q0.z, r.idir.z, -r.ood.z);
-    const uint32_t lox = __float_as_uint(q1.x), loy = __float_as_uint(q1.y), loz = __float_as_uint(q1.z);
-    const uint32_t hix = __float_as_uint(q1.w), hiy = __float_as_uint(q2.x), hiz = __float_as_uint(q2.y);
-    ref[0] = __float_as_uint(q3.x); ref[1] = __float_as_uint(q3.y); ref[2] = __float_as_uint(q3.z); ref[3] = __float_as_uint(q3.w);
-    // Slab test (§4.3b): tn = max(min(x0,x1), min(y0,y1), min(z0,z1), tmin), tf = min(max(x0,x1), ..., best.t) with
-    // x0/x1 = fma(qlo/qhi, k, a).  qlo <= qhi and fma rounding is monotonic, so min(x0,x1) is simply the plane picked by the
-    // sign of the direction: select the near / far byte words once per node (6 v_cndmask) instead of 6 min/max per child,
-    // and compute (near, far) of one axis with one packed v_pk_fma_f32.  Bit-identical to the min/max form.
-    const bool px = r.idir.x >= 0.0f, py = r.idir.y >= 0.0f, pz = r.idir.z >= 0.0f;
-    const uint32_t nx = px ? lox : hix, fx = px ? hix : lox, ny = py ? loy : hiy, fy = py ? hiy : loy, nz = pz ? loz : hiz, fz = pz ? hiz : loz;
-    const v2f kx2 = {kx, kx}, ky2 = {ky, ky}, kz2 = {kz, kz}, ax2 = {ax, ax}, ay2 = {ay, ay}, az2 = {az, az};
-    // ordering key: entry distance (>= tmin >= +0, so its sign bit is free) with the child slot in its two low mantissa
-    // bits (ties -> lower slot) and the sign bit set for inner children: one sort puts the leaves first, nearest first,
-    // then the inner children, nearest first, then the misses.  hw_minf / hw_maxf are the one-instruction IEEE minNum / maxNum
-    // (v_min3 / v_max3 fuse them).
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const v2f tx = __builtin_elementwise_fma(v2f{ubyte_f32(nx, c), ubyte_f32(fx, c)}, kx2, ax2);
-      const v2f ty = __builtin_elementwise_fma(v2f{ubyte_f32(ny, c), ubyte_f32(fy, c)}, ky2, ay2);
-      const v2f tz = __builtin_elementwise_fma(v2f{ubyte_f32(nz, c), ubyte_f32(fz, c)}, kz2, az2);
-      const float tn = hw_maxf(hw_maxf(tx.x, ty.x), hw_maxf(tz.x, r.tmin));
-      const float tf = hw_minf(hw_minf(tx.y, ty.y), hw_minf(tz.y, best.t));
-      const bool hit = ref[c] != kAbsent && tn <= tf * 1.0000004f;
-      if (kSlotOrder) { ref[c] = hit ? ref[c] : kAbsent; continue; }  // no keys (4.4c): a child that was missed is an absent child from here on
-      const uint32_t inner_bit = INST ? ((!(ref[c] >> 31) || (ref[c] >> 28) == 0xFu) ? kInnerKey : 0u) : (~ref[c] & kInnerKey);  // instance leaves wait like inner children
-      uint32_t kc;  // (tn & ~3) | (slot | inner bit): one v_and_or_b32 (hipcc emits v_and + v_or for the C form)
-      asm("v_and_or_b32 %0, %1, -4, %2" : "=v"(kc) : "v"(__float_as_uint(tn)), "v"((uint32_t)c | inner_bit));
-      key[c] = hit ? kc : kMissKey;
-    }
-    // Any-hit rays (kSlotOrder, RENDER_SPEC 4.4c): nothing they find moves their limit, so no order of the children saves
-    // them a visit that another order would not have cost, and a child that passed the slab test never needs a second look: they take
-    // the children in slot order, without sort and without keys (45 of the ~290 vector instructions of a node step).  All other rays:
-    // leaves first, nearest first, then the inner children, nearest first, then the misses.
-    if (!kSlotOrder) {
-      sort2kv(key[0], key[1], ref[0], ref[1]); sort2kv(key[2], key[3], ref[2], ref[3]); sort2kv(key[0], key[2], ref[0], ref[2]);
-      sort2kv(key[1], key[3], ref[1], ref[3]); sort2kv(key[1], key[2], ref[1], ref[2]);
-    }
+    if (kSlotOrder) {
+      float4 q0, q1, q2, q3;
+      if (STAGED) { const RT_LDS f32x4* p = lds.nodes + (size_t)t.cur * 4; q0 = ld4(p); q1 = ld4(p + 1); q2 = ld4(p + 2); q3 = ld4(p + 3); }
+      else { const float4* p = reinterpret_cast<const float4*>(sv.nodes) + (size_t)t.cur * 4; q0 = p[0]; q1 = p[1]; q2 = p[2]; q3 = p[3]; }
+      // Any-hit rays (RENDER_SPEC 4.4c): nothing they find moves their limit, so no order of the children saves them a visit that another
+      // order would not have cost, and a child that passed the slab test never needs a second look: slot order, no keys, no sort (45 of
+      // the ~290 vector instructions of a node step).  The fetch, node setup and slab test of test_children, written out: through the
+      // function boundary hipcc schedules the any-hit kernels differently (profiles/traverse_shared.txt)
+      const uint32_t ex = __float_as_uint(q0.w);
+      const float kx = __uint_as_float((ex & 0xffu) << 23) * r.idir.x, ky = __uint_as_float(((ex >> 8) & 0xffu) << 23) * r.idir.y,
+                  kz = __uint_as_float(((ex >> 16) & 0xffu) << 23) * r.idir.z;
+      const float ax = __fmaf_rn(q0.x, r.idir.x, -r.ood.x), ay = __fmaf_rn(q0.y, r.idir.y, -r.ood.y), az = __fmaf_rn(q0.z, r.idir.z, -r.ood.z);
+      const uint32_t lox = __float_as_uint(q1.x), loy = __float_as_uint(q1.y), loz = __float_as_uint(q1.z);
+      const uint32_t hix = __float_as_uint(q1.w), hiy = __float_as_uint(q2.x), hiz = __float_as_uint(q2.y);
+      ref[0] = __float_as_uint(q3.x); ref[1] = __float_as_uint(q3.y); ref[2] = __float_as_uint(q3.z); ref[3] = __float_as_uint(q3.w);
+      const bool px = r.idir.x >= 0.0f, py = r.idir.y >= 0.0f, pz = r.idir.z >= 0.0f;
+      const uint32_t nx = px ? lox : hix, fx = px ? hix : lox, ny = py ? loy : hiy, fy = py ? hiy : loy, nz = pz ? loz : hiz, fz = pz ? hiz : loz;
+      const v2f kx2 = {kx, kx}, ky2 = {ky, ky}, kz2 = {kz, kz}, ax2 = {ax, ax}, ay2 = {ay, ay}, az2 = {az, az};
+  #pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const v2f tx = __builtin_elementwise_fma(v2f{ubyte_f32(nx, c), ubyte_f32(fx, c)}, kx2, ax2);
+        const v2f ty = __builtin_elementwise_fma(v2f{ubyte_f32(ny, c), ubyte_f32(fy, c)}, ky2, ay2);
+        const v2f tz = __builtin_elementwise_fma(v2f{ubyte_f32(nz, c), ubyte_f32(fz, c)}, kz2, az2);
+        const float tn = hw_maxf(hw_maxf(tx.x, ty.x), hw_maxf(tz.x, r.tmin));
+        const float tf = hw_minf(hw_minf(tx.y, ty.y), hw_minf(tz.y, best.t));
+        const bool hit = ref[c] != kAbsent && tn <= tf * 1.0000004f;
+        ref[c] = hit ? ref[c] : kAbsent;  // no keys (4.4c): a child that was missed is an absent child from here on
+      }
+    } else test_children<STAGED, INST>(sv, lds, r, t.cur, best.t, ref, key);
     // inner children: the first of them (sorted: the nearest) is visited next, the others go on the stack last first, each with its key
     // so that a pop can drop entries that a hit found in the meantime has put out of reach.  "An inner child that was hit" is ONE signed
     // compare (0x80000000 <= key < 0xffffffff; slot order: a reference without the leaf bit, or an instance leaf); such a child is pushed
@@ -394,8 +458,7 @@ RT_DI bool trav_step(const SceneView& sv, const TraverseLds& lds, uint2* spill, 
       const bool left = k == 3 ? (in0 | in1 | in2) : (k == 2 ? (in0 | in1) : in0), self = k == 3 ? in3 : (k == 2 ? in2 : in1);
       if (self & left) {
         const uint32_t ek = kSlotOrder ? 0u : key[k];
-        if (sp < kS) stack[sp * kTraverseThreads] = u32x2{ek, ref[k]}; else spill[sp - kS] = make_uint2(ek, ref[k]);
-        ++sp;
+        st.push(ek, ref[k]);
       }
     }
     next = in0 ? ref[0] : (in1 ? ref[1] : (in2 ? ref[2] : (in3 ? ref[3] : kAbsent)));
@@ -538,38 +601,28 @@ RT_DI bool trav_step(const SceneView& sv, const TraverseLds& lds, uint2* spill, 
         } else { best.prim = w4.x; best.t = __uint_as_float(w4.y); best.u = __uint_as_float(w4.z); best.v = __uint_as_float(w4.w); }
       }
     }
-    if (!work) { if (kInstBatch > 0) t.sp = sp; return done_early; }  // no ray, or a lane that waits at an instance transition (or ended in one)
+    if (!work) { if (kInstBatch > 0) t.sp = st.sp; return done_early; }  // no ray, or a lane that waits at an instance transition (or ended in one)
   }
   if (ANY && found) return true;  // (best.prim != kAbsent: the blocker)
   // go on with the nearest inner child if it is still in reach, else with the first stack entry that is
   if (!kSlotOrder && next != kAbsent && !(key_tn(next_key) <= best.t)) next = kAbsent;
-  if (!INST) {
-    while (next == kAbsent) {
-      if (sp == 0) return true;
-      --sp;
-      uint2 e;
-      if (sp < kS) { const u32x2 v = stack[sp * kTraverseThreads]; e = make_uint2(v.x, v.y); } else e = spill[sp - kS];
-      if (kSlotOrder || key_tn(e.x) <= best.t) next = e.y;
-    }
-  } else {
-    for (;;) {
-      if (next == kAbsent) {
-        if (sp == 0) return true;
-        const uint2 e = pop();
-        if (e.y == kExitRef) {  // the instance's tree is done: back to the world-space ray parked under the mark
-          if (kInstBatch > 0) { next = kExitRef; break; }  // ... with the wave's next batch of transitions
-          leave_instance();
-          continue;
-        }
-        if (kSlotOrder || key_tn(e.x) <= best.t) next = e.y;
+  for (;;) {
+    if (next == kAbsent) {
+      if (st.sp == 0) return true;
+      const uint2 e = st.pop();
+      if (INST && e.y == kExitRef) {  // the instance's tree is done: back to the world-space ray parked under the mark
+        if (kInstBatch > 0) { next = kExitRef; break; }  // ... with the wave's next batch of transitions
+        leave_instance(st, t.r, t.gid_base, t.shade_base);
         continue;
       }
-      if (kInstBatch == 0 && is_inst_leaf(next)) next = enter_instance(next);  // (batched: the lane waits at the leaf)
-      break;
+      if (kSlotOrder || key_tn(e.x) <= best.t) next = e.y;
+      continue;
     }
+    if (INST && kInstBatch == 0 && is_inst_leaf(next)) next = enter_instance(sv, st, t.r, t.gid_base, t.shade_base, next);  // (batched: the lane waits at the leaf)
+    break;
   }
   t.cur = next;
-  t.sp = sp;
+  t.sp = st.sp;
   return false;
 }
 

@@ -9,9 +9,12 @@ Variants, all on device buffers, each between two HIP events on one stream:
   peel k       what a caller had to do before: k closest-hit batches, tmin of every ray advanced to its last t on the device between
                two batches (a ray that missed is closed: tmax = -1), on the PARENT's library (--parent-root: the parent commit's tree,
                built there; without it the peel runs on this tree's library and the JSON says so)
+  parent k     hala_rt_trace_rays_multi at the same k on the PARENT's library (only with --parent-root)
 The two libraries live in one process and the variants alternate, `--rounds` times after `--warmup` rounds; the JSON keeps every round,
 the medians, the spread (max - min) of each variant's rounds and Mrays/s.  The summary compares one multi-hit batch with the peel per k:
 "wins" only where the gap exceeds the spread of the parent's own repeated runs; and k = 1 with mode 0 (the cost of the list machinery).
+With a parent it also compares this tree's multi-hit batch with the parent's per k: "no slower" unless this tree's median exceeds the
+parent's by more than the spread of the parent's rounds.
 The peel returns the same lists only on rays without ties (4.7); the script counts the rays on which the two differ, it does not mind them."""
 import argparse
 import ctypes as C
@@ -115,6 +118,9 @@ def main():
         def multi(k):
             mine.trace_rays_multi(d_rays.data_ptr(), d_hits.data_ptr(), n, k, d_counts.data_ptr(), stream.cuda_stream)
 
+        def parent_multi(k):
+            other.trace_rays_multi(d_rays.data_ptr(), d_hits.data_ptr(), n, k, d_counts.data_ptr(), stream.cuda_stream)
+
         def peel(k):
             with torch.cuda.stream(stream):
                 d_work.copy_(d_rays)
@@ -135,6 +141,8 @@ def main():
             return e0.elapsed_time(e1)
 
         variants = [("mode0", mode0)] + [(f"multi_{k}", lambda k=k: multi(k)) for k in KS] + [(f"peel_{k}", lambda k=k: peel(k)) for k in KS]
+        if parent_lib:
+            variants += [(f"parent_{k}", lambda k=k: parent_multi(k)) for k in KS]
         ms = {v: [] for v, _ in variants}
         for rnd in range(args.warmup + args.rounds):
             for v, fn in variants:  # the variants alternate: one call each per round
@@ -158,6 +166,10 @@ def main():
             gap = p["median_ms"] - m["median_ms"]
             summary[str(k)] = {"multi_ms": m["median_ms"], "peel_ms": p["median_ms"], "peel_spread_ms": p["spread_ms"], "peel_over_multi": p["median_ms"] / m["median_ms"],
                                "verdict": "multi wins" if gap > p["spread_ms"] else ("peel wins" if -gap > p["spread_ms"] else "within the peel's spread")}
+            if parent_lib:
+                q = rows[f"parent_{k}"]
+                summary[str(k)].update(parent_multi_ms=q["median_ms"], parent_multi_spread_ms=q["spread_ms"], multi_minus_parent_ms=m["median_ms"] - q["median_ms"],
+                                       against_parent="no slower" if m["median_ms"] - q["median_ms"] <= q["spread_ms"] else "SLOWER than the parent")
         summary["k1_over_mode0"] = rows["multi_1"]["median_ms"] / rows["mode0"]["median_ms"]
         res["sets"][name] = {"rays": n, "variants": rows, "lists": differ, "summary": summary}
         print(name, json.dumps(summary, indent=1), flush=True)

@@ -58,6 +58,8 @@ SCENES = {
     "blob_dup": lambda: duplicated(RC.blob_scene(3)),
     "sheets512": lambda: scenes.stacked_sheets(512),
     "two_blobs": two_blobs,
+    "sheets4096": lambda: scenes.stacked_sheets(4096),               # a stack deeper than the large form's LDS entries
+    "sheets512_dup": lambda: duplicated(scenes.stacked_sheets(512)),  # ... and, two-level, deeper with a world-space ray parked on it
 }
 
 
@@ -79,15 +81,18 @@ RAYS = {
     "probe": probe_rays,
     "far_2_4": far_rays((2, 4), 300),   # every ray re-based
     "probe_far_3": lambda osc: np.concatenate([probe_rays(osc, 150), far_rays((3,), 150)(osc)]),
+    "probe_600": lambda osc: probe_rays(osc)[:600],
 }
 
 # (scene, instancing, ray set) -> capacities, per tree form: the table of the issue
 CASES = {
     "staged": [("cornell", False, "probe", (1, 2, 3, 5, 16)), ("cornell_dup", False, "probe", (1, 2, 3, 5, 16)), ("sheets64", False, "far_2_4", (8, 16))],
-    "large": [("blob", False, "probe", (1, 3, 4)), ("blob_dup", False, "probe", (1, 3, 4)), ("sheets512", False, "probe", (1, 8, 16))],
-    "two_level": [("two_blobs", True, "probe_far_3", (1, 2, 3, 4)), ("blob_dup", True, "probe_far_3", (1, 2, 3, 4))],
+    "large": [("blob", False, "probe", (1, 3, 4)), ("blob_dup", False, "probe", (1, 3, 4)), ("sheets512", False, "probe", (1, 8, 16)),
+              ("sheets4096", False, "probe_600", (16,))],
+    "two_level": [("two_blobs", True, "probe_far_3", (1, 2, 3, 4)), ("blob_dup", True, "probe_far_3", (1, 2, 3, 4)),
+                  ("sheets512_dup", True, "probe_600", (16,))],
 }
-BUILDER_K = {"blob": 3, "blob_dup": 3, "sheets512": 8, "two_blobs": 2}  # the one capacity each large / two-level case runs at with every builder
+BUILDER_K = {"blob": 3, "blob_dup": 3, "sheets512": 8, "two_blobs": 2, "sheets4096": 16, "sheets512_dup": 16}  # the one capacity each large / two-level case runs at with every builder
 
 _REF = {}
 
@@ -232,6 +237,17 @@ def assert_form(r, form):
         assert i.lds_node_count == 0 and i.instance_ref_count == 0
     else:
         assert i.instance_ref_count > 0
+    return i
+
+
+def assert_spills(r, form, scene):
+    """the deep-stack cases: up to three entries a level (and, two-level, the four of a parked world-space ray) outgrow the form's LDS
+    entries — the proxy of test_gpu_parity.test_deep_stack_spills_to_global_scratch"""
+    if scene in ("sheets4096", "sheets512_dup"):
+        i = assert_form(r, form)
+        macro = "RT_STACK_LDS_INST" if form == "two_level" else "RT_STACK_LDS"  # the form's LDS entries per lane, as the library is built by default
+        levels = int(re.search(rf"#define {macro} (\d+)", open(os.path.join(ROOT, "hala-renderer_amd", "csrc", "traverse.h")).read()).group(1))
+        assert 3 * i.max_depth + (4 if form == "two_level" else 0) > levels, (scene, i.max_depth, levels)
 
 
 def assert_equals_twin(r, rays, full, k, what):
@@ -253,6 +269,7 @@ def test_lists_equal_the_twin(halart, oracle, renderers, form, scene, instancing
     _, _, rays, full = reference(oracle, scene, instancing, rays_key)
     r = renderers(scene, instancing)
     assert_form(r, form)
+    assert_spills(r, form, scene)
     assert_equals_twin(r, rays, full, k, f"{form} {scene} k={k}")
 
 
