@@ -57,7 +57,7 @@ def check(status: int):
 
 
 from .renderer import (HalaRenderer, adaptive_default_params, cryptomatte_matte, denoise_images, denoise_default_params,  # noqa: E402,F401
-                       selftest_collapse, selftest_math, selftest_math_values, temporal_clamp_default_params, temporal_default_params, variant_ledger,
+                       selftest_collapse, selftest_hierarchy, selftest_math, selftest_math_values, temporal_clamp_default_params, temporal_default_params, variant_ledger,
                        view_depth, SELFTEST_RCP, SELFTEST_SQRT)
 from .raytracing_program import (HalaRayTracingProgram, HalaRayTracingProgramDesc,  # noqa: E402,F401
                                  HalaRayTracingHitShaderDesc)

@@ -383,6 +383,8 @@ PROTOTYPES = {
     "hala_rt_selftest_math": ([C.c_int, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)], C.c_int),
     "hala_rt_selftest_math_values": ([C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)], C.c_int),
     "hala_rt_selftest_collapse": ([C.c_uint32, C.c_uint32] + [C.c_void_p] * 12 + [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], C.c_int),
+    # count, boxes, pad, builder, ploc_tail, ploc_look_every | sorted_ids, left, right, first, last, node_parent, leaf_parent, node_boxes
+    "hala_rt_selftest_hierarchy": ([C.c_uint32, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 8, C.c_int),
 }
 
 # hala_rt_variant_ledger: the kernel families in the order of its `family`, each with its flags, first flag = bit 0 of a combination's index
@@ -446,7 +448,7 @@ EXPORTS = [
     "hala_rt_bind_nodes", "hala_rt_refit_nodes", "hala_rt_get_node_refit_status",
     "hala_rt_set_refit_policy", "hala_rt_get_tree_quality",
     "hala_rt_variant_ledger",
-    "hala_rt_selftest_math", "hala_rt_selftest_math_values", "hala_rt_selftest_collapse",
+    "hala_rt_selftest_math", "hala_rt_selftest_math_values", "hala_rt_selftest_collapse", "hala_rt_selftest_hierarchy",
     "hala_rt_trace_rays_multi", "hala_rt_trace_rays_multi_host", "hala_rtprog_trace_rays_multi",
 ]
 MAX_MULTI_HITS = 16  # HALA_MAX_MULTI_HITS (RENDER_SPEC 4.7)

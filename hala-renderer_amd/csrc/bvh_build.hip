@@ -679,6 +679,65 @@ std::string collapse_selftest(const CollapseSelftest& job) {
   return "";
 }
 
+namespace {
+
+// what k_flatten leaves of the scene bounds, from boxes that are already there: every block its bounds, as ordered integers
+__global__ void __launch_bounds__(256) k_box_bounds(const Box6* __restrict__ tri_box, uint32_t n, uint32_t* __restrict__ block_ord) {
+  __shared__ uint32_t wave_ord[4][6];
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  uint32_t ord[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+  if (g < n) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { ord[k] = f2ord(tri_box[g].mn[k]); ord[3 + k] = f2ord(tri_box[g].mx[k]); }
+  }
+  block_bounds_fold(ord, wave_ord, threadIdx.x, block_ord, blockIdx.x * 6u);
+}
+// k_leaf_boxes without the triangles
+__global__ void __launch_bounds__(256) k_widen_boxes(const Box6* __restrict__ tri_box, const uint32_t* __restrict__ sorted_ids, uint32_t n, float pad,
+                                                      Box6* __restrict__ leaf_box) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) leaf_box[k] = widen(tri_box[sorted_ids[k]], pad);
+}
+
+}  // namespace
+
+// the buffers of a build, the caller's boxes in the place of flatten's, then the builder as bvh_build calls it; the Karras hierarchy is
+// fitted as there, so that node_box means the same for every builder
+std::string hierarchy_selftest(const HierarchySelftest& job) {
+  const uint32_t n = job.n, ni = n - 1;
+  hipStream_t s = nullptr;
+  const bool sah = job.builder == 1u, ploc = job.builder == 2u;
+  BvhTopology t;
+  t.n = n; t.leaf_max = 1;
+  BuildScratch sc;
+  std::string e = alloc_all(t.plan());
+  if (e.empty()) e = alloc_all(sc.plan(n, !sah));
+  if (!e.empty()) return e;
+  HIP_TRY(hipMemcpyAsync(t.tri_box, job.boxes, (size_t)n * sizeof(Box6), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_box_bounds, dim3(nblk(n)), dim3(256), 0, s, t.tri_box, n, t.block_ord);
+  bounds_reduce(t.block_ord, nblk(n), t.scene_ord, s);
+  const BinaryTree tree{sc.left, sc.right, t.first, t.last, sc.node_parent, sc.leaf_parent, t.box4};
+  BuildOptions opt;
+  opt.builder = job.builder; opt.ploc_tail = job.ploc_tail; opt.ploc_look_every = job.ploc_look_every;
+  const HierarchyJob hj{n, job.pad, opt, t.tri_box, t.sorted_ids, tree};
+  if (!(e = sah ? sah_hierarchy(hj, s) : morton_hierarchy(hj, sc, t.scene_ord, ploc, s)).empty()) return e;
+  if (!sah && !ploc) {
+    hipLaunchKernelGGL(k_widen_boxes, dim3(nblk(n)), dim3(256), 0, s, t.tri_box, t.sorted_ids, n, job.pad, t.leaf_box);
+    if (!(e = fit_hierarchy(tree, t.leaf_box, sc.arrivals, n, s)).empty()) return e;
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(job.sorted_ids, t.sorted_ids, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(job.left, sc.left, (size_t)ni * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(job.right, sc.right, (size_t)ni * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(job.first, t.first, (size_t)ni * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(job.last, t.last, (size_t)ni * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(job.node_parent, sc.node_parent, (size_t)ni * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(job.leaf_parent, sc.leaf_parent, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(job.node_boxes, t.box4, (size_t)ni * sizeof(Box6), hipMemcpyDeviceToHost));
+  return "";
+}
+
 std::string bvh_build(BvhBuffers& b, uint32_t leaf_max, hipStream_t s) {
   const uint32_t n = b.tri_count;
   if (b.topology) { bvh_free_topology(b.topology); b.topology = nullptr; }

@@ -127,6 +127,17 @@ struct CollapseSelftest {
   uint32_t *choices, *keep, *refs4, *node_count, *levels;
 };
 std::string collapse_selftest(const CollapseSelftest& job);
+// hala_rt_selftest_hierarchy (halart.h): one hierarchy builder of a build on boxes from host memory, already checked by the caller;
+// what it leaves is what collapse_selftest takes
+struct HierarchySelftest {
+  uint32_t n;
+  const float* boxes;  // [n][6] by id
+  float pad;
+  uint32_t builder, ploc_tail, ploc_look_every;  // BuildOptions; builder 1 .. 3
+  uint32_t *sorted_ids, *left, *right, *first, *last, *node_parent, *leaf_parent;
+  float* node_boxes;
+};
+std::string hierarchy_selftest(const HierarchySelftest& job);
 
 // bvh_quality.hip — the tree cost of RENDER_SPEC 4.6 of the tree of `node_count` nodes whose root is `root` (references may be absolute:
 // only boxes, presence, the leaf bit and the leaf counts are read): out3[0] = node_q, out3[1] = tri_q, out3[2] = valid (all three 0 for

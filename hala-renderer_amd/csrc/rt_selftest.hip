@@ -1,8 +1,10 @@
 // rt_selftest.hip — hala_rt_selftest_math: the exact-math helpers of rt_math.h (rcp_rn, sqrt_rn) against the plain IEEE expressions they
 // stand for, over any range of the 2^32 binary32 bit patterns.  A unary float function has few enough inputs to be proven by enumeration;
 // tests/test_exact_math.py runs all of them.  hala_rt_selftest_collapse: the collapse of bvh_build.hip on a binary tree the caller hands over
-// (tests/test_collapse_cost.py against tests/collapse_ref.py).
+// (tests/test_collapse_cost.py against tests/collapse_ref.py).  hala_rt_selftest_hierarchy: one of its hierarchy builders on boxes the
+// caller hands over (tests/test_hierarchy_builders.py against tests/hierarchy_ref.py).
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -118,9 +120,34 @@ static int selftest_collapse(const CollapseSelftest& job) {
   return HALA_OK;
 }
 
+// The builders take any finite boxes; what they cannot take (an empty box, a pad that shrinks) is refused here, before any device call.
+static int selftest_hierarchy(const HierarchySelftest& job) {
+  const uint32_t n = job.n;
+  if (n < 2u || n > (1u << 20)) RT_FAIL("hala_rt_selftest_hierarchy: there must be 2 .. 2^20 boxes.");
+  if (!job.boxes || !job.sorted_ids || !job.left || !job.right || !job.first || !job.last || !job.node_parent || !job.leaf_parent || !job.node_boxes)
+    RT_FAIL("hala_rt_selftest_hierarchy: an array is null!");
+  if (!all_finite(job.boxes, (size_t)n * 6u)) RT_FAIL("hala_rt_selftest_hierarchy: a box is not finite.");
+  for (size_t k = 0; k < n; ++k)
+    for (int c = 0; c < 3; ++c)
+      if (job.boxes[6 * k + c] > job.boxes[6 * k + 3 + c]) RT_FAIL("hala_rt_selftest_hierarchy: a box has min > max.");
+  if (!std::isfinite(job.pad) || job.pad < 0.0f) RT_FAIL("hala_rt_selftest_hierarchy: pad must be finite and not negative.");
+  if (job.builder < 1u || job.builder > 3u) RT_FAIL("hala_rt_selftest_hierarchy: builder must be 1 (SAH), 2 (PLOC) or 3 (LBVH).");
+  if (job.ploc_tail > 2u || job.ploc_look_every > 64u) RT_FAIL("hala_rt_selftest_hierarchy: ploc_tail must be 0 .. 2 and ploc_look_every 0 .. 64.");
+  const std::string e = hierarchy_selftest(job);
+  if (!e.empty()) RT_FAIL(e);
+  return HALA_OK;
+}
+
 }  // namespace rt
 
 extern "C" {
+
+int hala_rt_selftest_hierarchy(uint32_t count, const float* boxes, float pad, uint32_t builder, uint32_t ploc_tail, uint32_t ploc_look_every,
+                               uint32_t* sorted_ids, uint32_t* left, uint32_t* right, uint32_t* first, uint32_t* last, uint32_t* node_parent,
+                               uint32_t* leaf_parent, float* node_boxes) {
+  return rt::selftest_hierarchy(rt::HierarchySelftest{count, boxes, pad, builder, ploc_tail, ploc_look_every, sorted_ids, left, right, first, last,
+                                                      node_parent, leaf_parent, node_boxes});
+}
 
 int hala_rt_selftest_collapse(uint32_t leaves, uint32_t leaf_max, const uint32_t* left, const uint32_t* right, const uint32_t* node_parent,
                               const uint32_t* leaf_parent, const uint32_t* first, const uint32_t* last, const float* node_boxes,

@@ -964,6 +964,26 @@ def selftest_collapse(left, right, node_parent, leaf_parent, first, last, node_b
     return dict(costs=costs, choices=choices, keep=keep, refs4=refs4[:count.value].copy(), levels=levels.value)
 
 
+def selftest_hierarchy(boxes, pad, builder, ploc_tail=0, ploc_look_every=0):
+    """hala_rt_selftest_hierarchy: the binary tree that builder 1 (SAH), 2 (PLOC) or 3 (LBVH) of a build makes over boxes [n, 6] (min xyz,
+    max xyz by id), fitted boxes widened by pad.  -> dict(sorted_ids [n], left, right, first, last, node_parent [n - 1], leaf_parent [n],
+    node_boxes [n - 1, 6]): the arrays selftest_collapse takes, with sorted_ids before them."""
+    from . import check, load_library
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32)
+    if boxes.ndim != 2 or boxes.shape[1] != 6:
+        raise ValueError("expected boxes of shape [n, 6]")
+    n = len(boxes)
+    ni = max(n - 1, 1)
+    out = {k: np.zeros(ni, dtype=np.uint32) for k in ("left", "right", "first", "last", "node_parent")}
+    out["sorted_ids"], out["leaf_parent"] = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+    out["node_boxes"] = np.zeros((ni, 6), dtype=np.float32)
+    ptr = lambda x: C.c_void_p(x.ctypes.data)  # noqa: E731
+    check(load_library().hala_rt_selftest_hierarchy(C.c_uint32(n), ptr(boxes), C.c_float(pad), C.c_uint32(builder), C.c_uint32(ploc_tail),
+                                                    C.c_uint32(ploc_look_every), *(ptr(out[k]) for k in ("sorted_ids", "left", "right", "first", "last",
+                                                                                                         "node_parent", "leaf_parent", "node_boxes"))))
+    return out
+
+
 def denoise_images(color, albedo, normal, device_ordinal=0, **params) -> np.ndarray:
     """hala_denoise_images: the RENDER_SPEC 10 filter on host images [H, W, 3 or 4] (e.g. the PFM trio of save_images); returns the
     denoised RGBA32F [H, W, 4].  params: iterations, sigma_color, sigma_albedo, normal_power, demodulate."""

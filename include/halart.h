@@ -711,6 +711,19 @@ int hala_rt_selftest_collapse(uint32_t leaves, uint32_t leaf_max, const uint32_t
                               const uint32_t* leaf_parent, const uint32_t* first, const uint32_t* last, const float* node_boxes,
                               const float* leaf_boxes, float* costs, uint32_t* choices, uint32_t* keep, uint32_t* refs4, uint32_t* node_count,
                               uint32_t* levels);
+/* Self-test of the hierarchy builders (csrc/bvh_sah.hip, bvh_ploc.hip, and k_morton, the radix sort, k_hierarchy and k_fit of
+ * bvh_build.hip): the binary tree one of them builds over `count` boxes from host memory, boxes [count][6] = min xyz, max xyz by id.
+ * builder 1: SAH, 2: PLOC, 3: LBVH; ploc_tail / ploc_look_every as in hala_rt_build_options (0: the default; they change how PLOC's
+ * rounds are driven, never the tree).  The call runs the functions a build runs, on the scene bounds a build would find: the exact union
+ * of the boxes.  Out, to host arrays, in the form hala_rt_selftest_collapse takes: sorted_ids [count] (the id at every sorted position),
+ * left / right / first / last / node_parent [count - 1] and leaf_parent [count] as described there (node 0 is the root), node_boxes
+ * [count - 1][6]: per node the union of the boxes at its sorted positions first .. last, every min lowered and every max raised by `pad`
+ * in one binary32 operation each.  The same boxes, pad and builder give the same bytes in every call.  Refused before anything runs on
+ * the device: count < 2 or > 2^20, a null array, a box that is not finite or has min > max, a pad that is negative or not finite, a
+ * builder outside 1 .. 3, ploc_tail > 2, ploc_look_every > 64.  Runs on the calling thread's current device and needs no renderer. */
+int hala_rt_selftest_hierarchy(uint32_t count, const float* boxes, float pad, uint32_t builder, uint32_t ploc_tail, uint32_t ploc_look_every,
+                               uint32_t* sorted_ids, uint32_t* left, uint32_t* right, uint32_t* first, uint32_t* last, uint32_t* node_parent,
+                               uint32_t* leaf_parent, float* node_boxes);
 /* Frames in flight.  Consecutive updates are independent except for the order in which their samples are folded into the accumulated
  * images, so updates without per-launch timing or counting alternate between two frame slots, each with its own stream, control block,
  * stack spill area, per-path state and queues: update k + 1 starts beside the last bounces of update k (its dense camera-ray launch and

@@ -170,6 +170,11 @@ pub mod sys {
                                      leaf_parent: *const u32, first: *const u32, last: *const u32, node_boxes: *const f32,
                                      leaf_boxes: *const f32, costs: *mut f32, choices: *mut u32, keep: *mut u32, refs4: *mut u32,
                                      node_count: *mut u32, levels: *mut u32) -> c_int;
+    // one hierarchy builder (1 SAH, 2 PLOC, 3 LBVH) on `count` boxes [count][6] from host memory; out: the binary tree in the arrays
+    // hala_rt_selftest_collapse takes, sorted_ids [count] and node_boxes [count - 1][6] widened by pad (include/halart.h)
+    pub fn hala_rt_selftest_hierarchy(count: u32, boxes: *const f32, pad: f32, builder: u32, ploc_tail: u32, ploc_look_every: u32,
+                                      sorted_ids: *mut u32, left: *mut u32, right: *mut u32, first: *mut u32, last: *mut u32,
+                                      node_parent: *mut u32, leaf_parent: *mut u32, node_boxes: *mut f32) -> c_int;
     pub fn hala_rt_set_frames_in_flight(r: *mut hala_rt_renderer, n: u32) -> c_int;
     pub fn hala_rt_frames_in_flight_info(r: *mut hala_rt_renderer, second_slot_updates: *mut u64, second_buffers: *mut u32) -> c_int;
     pub fn hala_rt_set_build_options(r: *mut hala_rt_renderer, options: *const hala_rt_build_options) -> c_int;
