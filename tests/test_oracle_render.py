@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+import first_hit_ref
 import hala_renderer_amd as H
 from conftest import GOLDEN
 from hala_renderer_amd import scenes
@@ -256,7 +257,6 @@ def test_texture_mips_and_fetch_vs_independent_numpy(oracle):
     osc = oracle.OracleScene(s)
     lut = osc.texture_level(k, 0)[0, :, 0].copy()
     assert lut[0] == 0.0 and lut[255] == 1.0 and np.all(np.diff(lut) > 0)
-    thr = ((lut[:-1] + lut[1:]) * f32(0.5)).astype(f32)  # midpoints between neighbouring codes
     for tex in (0, 1, 6, 7):
         w, h, mips = osc.texture_info(tex)
         img = s.image_data[tex]
@@ -281,22 +281,9 @@ def test_texture_mips_and_fetch_vs_independent_numpy(oracle):
         # every further level is the 2x2 box filter of the previous one (edge-clamped), bit-exact
         prev = got0
         for l in range(1, mips):
-            sh, sw = prev.shape[:2]
-            dh, dw = max(1, h >> l), max(1, w >> l)
-            ys0 = np.minimum(2 * np.arange(dh), sh - 1); ys1 = np.minimum(2 * np.arange(dh) + 1, sh - 1)
-            xs0 = np.minimum(2 * np.arange(dw), sw - 1); xs1 = np.minimum(2 * np.arange(dw) + 1, sw - 1)
-            a, b = prev[ys0][:, xs0], prev[ys0][:, xs1]
-            c, dd = prev[ys1][:, xs0], prev[ys1][:, xs1]
-            exp = (((a + b).astype(f32) + (c + dd).astype(f32)).astype(f32) * f32(0.25)).astype(f32)
-            if img.format != scenes.A_FORMAT_FLOAT:
-                # 8-bit images stay 8-bit at every level: UNORM floor(x * 255 + 0.5), sRGB the nearest code (the number of midpoints
-                # below x); the level holds what those bytes decode to
-                un = (np.clip(np.floor(exp * f32(255) + f32(0.5)), 0, 255).astype(np.uint32).astype(f32) / f32(255)).astype(f32)
-                if img.format == scenes.A_FORMAT_SRGB:
-                    code = np.searchsorted(thr, exp[..., :3], side="left")
-                    exp = np.concatenate([lut[code], un[..., 3:]], -1).astype(f32)
-                else:
-                    exp = un
+            # 8-bit images stay 8-bit at every level: UNORM floor(x * 255 + 0.5), sRGB the nearest code (the number of midpoints
+            # below x); the level holds what those bytes decode to (the float32 emulation lives in tests/first_hit_ref.py)
+            exp = first_hit_ref.mip_level_f32(prev, w, h, l, img.format, lut)
             cur = osc.texture_level(tex, l)
             assert cur.tobytes() == exp.astype(f32).tobytes(), (tex, l)
             prev = cur
