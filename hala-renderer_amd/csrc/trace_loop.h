@@ -11,6 +11,12 @@ struct WorkCursor {
   uint32_t shard, per;
   unsigned long long dead;  // shards that lie wholly beyond the queue's end: never probed
 };
+// Lane 0's value, to the whole wave.  Every caller runs with all 64 lanes of its wave active (the persistent loop is wave-uniform), so
+// the first active lane IS lane 0 and the value comes back in a scalar register: what is decided from it (is the shard dry, is the
+// queue dry) branches on the scalar unit instead of being carried as a lane mask through exec regions, as a ds_bpermute result was.
+RT_DI uint32_t lane0_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+RT_DI unsigned long long lane0_u64(unsigned long long v) { return ((unsigned long long)lane0_u32((uint32_t)(v >> 32)) << 32) | lane0_u32((uint32_t)v); }
+RT_DI bool lane_in(unsigned long long mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }  // this lane's bit of a wave-uniform mask, as a predicate: no instruction
 RT_DI WorkCursor work_begin(uint32_t n) {
   WorkCursor c;
   const uint32_t batches = (n + kWorkBatch - 1u) / kWorkBatch;
@@ -27,7 +33,7 @@ RT_DI uint32_t work_take(WorkCounters* wc, WorkCursor& c, uint32_t n, uint32_t w
   for (;;) {
     uint32_t v = 0;
     if (lane_id() == 0u) v = atomicAdd(&wc->c[c.shard * kWorkStride], want);
-    v = (uint32_t)__shfl((int)v, 0);
+    v = lane0_u32(v);
     const unsigned long long lo = (unsigned long long)c.shard * c.per + v;
     const unsigned long long hi = min((unsigned long long)(c.shard + 1u) * c.per, (unsigned long long)n);
     if (v < c.per && lo < hi) {
@@ -42,7 +48,7 @@ RT_DI uint32_t work_take(WorkCounters* wc, WorkCursor& c, uint32_t n, uint32_t w
       m = __hip_atomic_load(&wc->dry[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (!(m & (1ull << c.shard))) { atomicOr(&wc->dry[0], 1ull << c.shard); m |= 1ull << c.shard; }
     }
-    m = (unsigned long long)__shfl((long long)m, 0) | c.dead;
+    m = lane0_u64(m) | c.dead;
     if ((m & kAll) == kAll) { *got = 0; return kAbsent; }
     const unsigned long long avail = ~m & kAll;
     const uint32_t rot = (c.shard + 1u) & (kWorkShards - 1u);
@@ -60,7 +66,11 @@ RT_DI void persistent_trace(const SceneView& sv, const TraverseLds& lds, uint2* 
                             Source& src, StepCounters& sc) {
   WorkCursor cur = work_begin(n);
   bool more = n > 0u;  // wave-uniform: some shard may still hold rays
-  bool has = false;
+  // Which lanes hold a ray (`has`) and which hold a finished ray's result (`fin`) are 64-bit wave masks in scalar registers: the loop's
+  // decisions (idle lanes, refill, end) are scalar arithmetic on them and scalar branches, and a lane's own bit is its predicate as it
+  // stands (lane_in).  As per-lane bools they were merged through exec regions at every join and turned into masks and back through
+  // the vector unit: ~25 scalar instructions per wave step.
+  unsigned long long has = 0ull;
   uint32_t idx = 0;
   Trav t;
   typename Source::Payload pay;
@@ -73,14 +83,17 @@ RT_DI void persistent_trace(const SceneView& sv, const TraverseLds& lds, uint2* 
   // A finished ray keeps its result in the lane until the wave next refills (or ends): the results of all lanes that finished in
   // between leave in ONE store instruction — whole 1-KB runs for the whole-wave batches of the LDS-staged kernels (64 consecutive
   // queue entries: full lines for the nontemporal stores) — instead of one divergent store per lane and step.
-  bool fin = false;
+  unsigned long long fin = 0ull;
   for (;;) {
-    const unsigned long long idle = __ballot(!has);
+    const unsigned long long idle = ~has;
     if (more && idle) {
-      if (fin) { src.done(idx, t, pay); fin = false; }
+      if (fin) {
+        if (lane_in(fin)) src.done(idx, t, pay);
+        fin = 0ull;
+      }
       uint32_t got = 0, base = kAbsent;
       if (pre_out) {
-        const uint32_t v = (uint32_t)__shfl((int)pre_raw, 0);
+        const uint32_t v = lane0_u32(pre_raw);
         const unsigned long long lo = (unsigned long long)pre_shard * cur.per + v;
         const unsigned long long hi = min((unsigned long long)(pre_shard + 1u) * cur.per, (unsigned long long)n);
         if (v < cur.per && lo < hi) { base = (uint32_t)lo; got = (uint32_t)min(64ull, hi - lo); }
@@ -93,29 +106,33 @@ RT_DI void persistent_trace(const SceneView& sv, const TraverseLds& lds, uint2* 
           if (lane_id() == 0u) pre_raw = atomicAdd(&work->c[cur.shard * kWorkStride], 64u);
           pre_shard = cur.shard; pre_out = true;
         }
-        if (!has) {
-          const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane_id()) - 1ull));
+        bool took = false;
+        if (lane_in(idle)) {
+          const uint32_t rank = mbcnt64(idle);  // idle lanes below this one
           if (rank < got) {
             idx = base + rank;
             f3 o, d; float tmin, tmax; uint32_t key = 0u;
             if (src.load(idx, &o, &d, &tmin, &tmax, &key, &pay)) {  // false: the source had no ray for this entry and has dealt with it
               trav_begin(t, make_ray(o, d, tmin), tmax, key);
-              has = true;
+              took = true;
             }
           }
         }
+        has |= __builtin_amdgcn_ballot_w64(took);
       }
     }
-    if (__ballot(has) == 0ull) { if (!more) break; continue; }
+    if (has == 0ull) { if (!more) break; continue; }
     for (;;) {
       if (COUNT && lane_id() == 0u) sc.wave_steps++;  // lane 0 runs every iteration of this wave-uniform loop
       // every lane calls it: the large-scene variant deals the wave's leaf work out over all 64 lanes (traverse.h)
-      if (trav_step<ANY, COUNT, STAGED, ALPHA, INST>(sv, lds, spill, t, has, sc)) { fin = true; has = false; }
-      const uint32_t nidle = (uint32_t)__popcll(__ballot(!has));
+      trav_step<ANY, COUNT, STAGED, ALPHA, INST>(sv, lds, spill, t, lane_in(has), sc);
+      const unsigned long long ended = __builtin_amdgcn_ballot_w64(t.cur == kAbsent) & has;  // a finished ray's mark (traverse.h); a lane without a ray holds anything
+      fin |= ended; has &= ~ended;
+      const uint32_t nidle = 64u - (uint32_t)__popcll(has);
       if (nidle == 64u || (more && nidle >= refill)) break;
     }
   }
-  if (fin) src.done(idx, t, pay);
+  if (lane_in(fin)) src.done(idx, t, pay);
 }
 
 struct BatchSource {

@@ -8,8 +8,9 @@
 // triangles straight from L2 / Infinity Cache / HBM (a partially staged top-of-tree slice measured no gain:
 // profiles/r01_h_experiments.txt, and mixing both sources in one variant turns every fetch into a flat_load).
 // The per-lane traversal stack lives in LDS as [entry][thread] (8-B entries, conflict-free), deeper entries spill to a
-// global scratch area.  No MFMA: this is branchy scalar-per-ray work, and it is VALU-issue bound (profiles/r01_h_pmc_*):
-// what counts is the number of vector instructions per node visit and per triangle test.
+// global scratch area.  No MFMA: this is branchy scalar-per-ray work.  It is bound by how fast each wave gets through its own instruction
+// stream (plus its memory waits), not by the vector pipes: a wave issues one instruction of ANY kind at a time, so what counts is the
+// number of instructions per node visit and per triangle test, scalar and branch instructions included (profiles/scalar_diet.txt).
 // The rules of a node visit that every ray kind must follow bit for bit (stack and spill, instance entry and exit, child test with keys and
 // order, paired LDS leaf walk) are functions of their own below, used by trav_step and by the multi-hit stepper of trace_multi.hip.
 #pragma once
@@ -225,6 +226,11 @@ struct LaneStack {
     if (sp < kS) { const u32x2 v = lds[sp * kTraverseThreads]; return make_uint2(v.x, v.y); }
     return spill[sp - kS];
   }
+  // The forms without the LDS / spill split, for a wave that has established (one ballot) that none of its lanes is near the spill area:
+  // no branch, no change of the exec mask.  put() stores at the top WITHOUT moving it — an entry above `sp` is dead, so a lane that
+  // does not push may store there all the same and then simply keeps its `sp`.
+  RT_DI void put_lds(int at, uint32_t a, uint32_t b) { lds[at * kTraverseThreads] = u32x2{a, b}; }
+  RT_DI uint2 pop_lds() { --sp; const u32x2 v = lds[sp * kTraverseThreads]; return make_uint2(v.x, v.y); }
 };
 // Moving a ray into an instance's object space (RENDER_SPEC 4.5): the world-space ray is parked on the stack, three entries under an exit
 // mark; returns the root of the primitive's tree.  Ids inside are local to the primitive: + gid_base = global id, + (shade_base &
@@ -243,9 +249,11 @@ RT_DI uint32_t enter_instance(const SceneView& sv, Stack& st, RayPre& r, uint32_
   gid_base = __float_as_uint(i3.y); shade_base = __float_as_uint(i3.z) | 0x80000000u;
   return __float_as_uint(i3.x);
 }
-template <class Stack>
+template <bool LDS_ONLY = false, class Stack>
 RT_DI void leave_instance(Stack& st, RayPre& r, uint32_t& gid_base, uint32_t& shade_base) {  // the exit mark has been popped: the world-space ray lies under it
-  const uint2 c2 = st.pop(), c1 = st.pop(), c0 = st.pop();
+  uint2 c2, c1, c0;
+  if constexpr (LDS_ONLY) { c2 = st.pop_lds(); c1 = st.pop_lds(); c0 = st.pop_lds(); }  // (the caller knows: no lane of the wave stands above the LDS entries)
+  else { c2 = st.pop(); c1 = st.pop(); c0 = st.pop(); }
   r = make_ray(mk3(__uint_as_float(c0.x), __uint_as_float(c0.y), __uint_as_float(c1.x)),
                mk3(__uint_as_float(c1.y), __uint_as_float(c2.x), __uint_as_float(c2.y)), r.tmin);
   gid_base = 0u; shade_base = 0u;
@@ -358,7 +366,7 @@ RT_DI float lane_read(uint32_t src_lane_x4, float v) {  // v of lane src_lane_x4
 }
 
 // One node visit of every lane that holds a ray (`has`); returns true when the lane's ray is finished (ANY: also on the first hit
-// inside (tmin, tmax)).  The whole wave must call it together: the large-scene variant (!STAGED) tests the leaves the wave's lanes
+// inside (tmin, tmax)) and then, and only then, leaves t.cur == kAbsent: the wave loop reads that mark, not the return value.  The whole wave must call it together: the large-scene variant (!STAGED) tests the leaves the wave's lanes
 // reached in this step COOPERATIVELY — the (ray, triangle) pairs are dealt out over all 64 lanes, whoever owns the ray:
 //   lane with n leaves in reach -> n items {leaf reference, owner lane} in the wave's LDS work list (position by a ballot prefix sum),
 //                                   its best hit so far as a 64-bit key (t bits | triangle id) in its merge slot;
@@ -409,7 +417,7 @@ RT_DI bool trav_step(const SceneView& sv, const TraverseLds& lds, uint2* spill, 
         }
       }
       if (has && !done_early && is_inst_leaf(c)) c = enter_instance(sv, st, t.r, t.gid_base, t.shade_base, c);
-      if (has && !done_early) t.cur = c;
+      if (has) t.cur = done_early ? kAbsent : c;  // (kAbsent: the mark of a finished ray, see below)
     }
     work = has && !done_early && (int32_t)t.cur >= 0;
   }
@@ -453,13 +461,21 @@ RT_DI bool trav_step(const SceneView& sv, const TraverseLds& lds, uint2* spill, 
     for (int k = 0; k < 4; ++k)
       in[k] = !kSlotOrder ? (int32_t)key[k] < -1 : (INST ? (int32_t)ref[k] >= (int32_t)kInstLeafTag && ref[k] < kExitRef : (int32_t)ref[k] >= 0);
     const bool in0 = in[0], in1 = in[1], in2 = in[2], in3 = in[3];
-#pragma unroll
-    for (int k = 3; k >= 1; --k) {
-      const bool left = k == 3 ? (in0 | in1 | in2) : (k == 2 ? (in0 | in1) : in0), self = k == 3 ? in3 : (k == 2 ? in2 : in1);
-      if (self & left) {
-        const uint32_t ek = kSlotOrder ? 0u : key[k];
-        st.push(ek, ref[k]);
-      }
+    const bool p3 = in3 & (in0 | in1 | in2), p2 = in2 & (in0 | in1), p1 = in1 & in0;
+    // Decided once per wave step, wave-uniformly: can a visiting lane come near the spill area?  If none can (the common case) the three
+    // stores go to LDS unconditionally — child 3 at sp, child 2 above it if 3 was pushed, else over it, and so on: what lies above the
+    // final sp is dead — and the depth moves by three add-with-carry on the predicates' lane masks: no branch, no exec change.  (A
+    // dead store lands at most AT the final sp, hence `>=`: entry stack_lds() belongs to another array.)
+    const int sp3 = st.sp + (p3 ? 1 : 0), sp2 = sp3 + (p2 ? 1 : 0), sp1 = sp2 + (p1 ? 1 : 0);
+    if (__builtin_amdgcn_ballot_w64(sp1 >= stack_lds<STAGED, INST>()) == 0ull) {
+      st.put_lds(st.sp, kSlotOrder ? 0u : key[3], ref[3]);
+      st.put_lds(sp3, kSlotOrder ? 0u : key[2], ref[2]);
+      st.put_lds(sp2, kSlotOrder ? 0u : key[1], ref[1]);
+      st.sp = sp1;
+    } else {
+      if (p3) st.push(kSlotOrder ? 0u : key[3], ref[3]);
+      if (p2) st.push(kSlotOrder ? 0u : key[2], ref[2]);
+      if (p1) st.push(kSlotOrder ? 0u : key[1], ref[1]);
     }
     next = in0 ? ref[0] : (in1 ? ref[1] : (in2 ? ref[2] : (in3 ? ref[3] : kAbsent)));
     if (!kSlotOrder) next_key = in0 ? key[0] : (in1 ? key[1] : (in2 ? key[2] : key[3]));
@@ -603,27 +619,37 @@ RT_DI bool trav_step(const SceneView& sv, const TraverseLds& lds, uint2* spill, 
     }
     if (!work) { if (kInstBatch > 0) t.sp = st.sp; return done_early; }  // no ray, or a lane that waits at an instance transition (or ended in one)
   }
-  if (ANY && found) return true;  // (best.prim != kAbsent: the blocker)
+  // A finished ray leaves the step with t.cur == kAbsent — no node, exit mark or instance leaf has that reference — which is what the
+  // wave loop reads (trace_loop.h: one compare, instead of a bool merged over the step's exits).  An occluder (ANY) ends the ray as
+  // an empty stack does: two selects, and the pop loop below has nothing to do for the lane.
+  if (ANY) { next = found ? kAbsent : next; st.sp = found ? 0 : st.sp; }  // (best.prim != kAbsent: the blocker)
   // go on with the nearest inner child if it is still in reach, else with the first stack entry that is
-  if (!kSlotOrder && next != kAbsent && !(key_tn(next_key) <= best.t)) next = kAbsent;
-  for (;;) {
-    if (next == kAbsent) {
-      if (st.sp == 0) return true;
-      const uint2 e = st.pop();
-      if (INST && e.y == kExitRef) {  // the instance's tree is done: back to the world-space ray parked under the mark
-        if (kInstBatch > 0) { next = kExitRef; break; }  // ... with the wave's next batch of transitions
-        leave_instance(st, t.r, t.gid_base, t.shade_base);
-        continue;
-      }
-      if (kSlotOrder || key_tn(e.x) <= best.t) next = e.y;
-      continue;
+  // (one select: without a child next_key is the key of a miss or a leaf — whatever the compare says of it, next stays kAbsent)
+  if (!kSlotOrder) next = key_tn(next_key) <= best.t ? next : kAbsent;
+  // The same wave-uniform split as for the pushes: while no lane of the wave stands above the LDS entries (pops only lower `sp`) the
+  // loop reads LDS and nothing else; the general loop, which carries the LDS / spill choice through every iteration, is for the others.
+  // Either loop has ONE exit condition (nothing found yet, and entries left), so a lane's way out is one compare pair, not two exits
+  // whose lane masks the loop would carry along.
+  if (__builtin_amdgcn_ballot_w64(st.sp > stack_lds<STAGED, INST>()) == 0ull) {
+    while (next == kAbsent && st.sp != 0) {
+      const uint2 e = st.pop_lds();
+      if (INST && e.y == kExitRef) {
+        if (kInstBatch > 0) next = kExitRef; else leave_instance<true>(st, t.r, t.gid_base, t.shade_base);
+      } else if (kSlotOrder || key_tn(e.x) <= best.t) next = e.y;
     }
-    if (INST && kInstBatch == 0 && is_inst_leaf(next)) next = enter_instance(sv, st, t.r, t.gid_base, t.shade_base, next);  // (batched: the lane waits at the leaf)
-    break;
+  } else {
+    while (next == kAbsent && st.sp != 0) {
+      const uint2 e = st.pop();
+      if (INST && e.y == kExitRef) {  // the instance's tree is done: back to the world-space ray parked under the mark ...
+        if (kInstBatch > 0) next = kExitRef;  // ... with the wave's next batch of transitions
+        else leave_instance(st, t.r, t.gid_base, t.shade_base);
+      } else if (kSlotOrder || key_tn(e.x) <= best.t) next = e.y;
+    }
   }
-  t.cur = next;
+  if (INST && kInstBatch == 0 && is_inst_leaf(next)) next = enter_instance(sv, st, t.r, t.gid_base, t.shade_base, next);  // (batched: the lane waits at the leaf)
+  t.cur = next;  // (kAbsent: the stack is empty, the ray is finished)
   t.sp = st.sp;
-  return false;
+  return next == kAbsent;
 }
 
 }  // namespace rt
