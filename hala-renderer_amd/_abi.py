@@ -137,6 +137,14 @@ class Hit(C.Structure):  # 16 B
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("prim", C.c_uint32)]
 
 
+class PointQuery(C.Structure):  # hala_point_query, 16 B (RENDER_SPEC 4.8)
+    _fields_ = [("point", C.c_float * 3), ("radius", C.c_float)]
+
+
+class ClosestPoint(C.Structure):  # hala_closest_point, 32 B
+    _fields_ = [("distance", C.c_float), ("u", C.c_float), ("v", C.c_float), ("prim", C.c_uint32), ("point", C.c_float * 3), ("region", C.c_uint32)]
+
+
 class RtInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -313,6 +321,9 @@ DEFORM_NORMALS_AS_POSED, DEFORM_NORMALS_RECOMPUTED = 0, 1
 PROTOTYPES = {
     "hala_rt_trace_rays_multi": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
     "hala_rt_trace_rays_multi_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32], C.c_int),
+    "hala_rt_closest_points": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
+    "hala_rt_closest_points_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32], C.c_int),
+    "hala_rt_closest_points_counted": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "hala_rtprog_trace_rays_multi": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
     "hala_rt_denoise": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
@@ -403,6 +414,9 @@ import numpy as _np
 
 RAY_DTYPE = _np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4", 3), ("tmax", "<f4")])
 HIT_DTYPE = _np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4")])
+# RENDER_SPEC 4.8: hala_point_query (16 B), hala_closest_point (32 B)
+POINT_QUERY_DTYPE = _np.dtype([("point", "<f4", 3), ("radius", "<f4")])
+CLOSEST_POINT_DTYPE = _np.dtype([("distance", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("point", "<f4", 3), ("region", "<u4")])
 VERTEX_DTYPE = _np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("tex_coord", "<f4", 2)])
 
 # every symbol include/halart.h declares (tests/test_abi.py checks the .so exports all of them)
@@ -450,5 +464,6 @@ EXPORTS = [
     "hala_rt_variant_ledger",
     "hala_rt_selftest_math", "hala_rt_selftest_math_values", "hala_rt_selftest_collapse", "hala_rt_selftest_hierarchy",
     "hala_rt_trace_rays_multi", "hala_rt_trace_rays_multi_host", "hala_rtprog_trace_rays_multi",
+    "hala_rt_closest_points", "hala_rt_closest_points_host", "hala_rt_closest_points_counted",
 ]
 MAX_MULTI_HITS = 16  # HALA_MAX_MULTI_HITS (RENDER_SPEC 4.7)

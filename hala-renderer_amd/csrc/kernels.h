@@ -44,6 +44,11 @@ void launch_unbase_hits(hala_hit* hits, const float* moved, uint32_t n, hipStrea
 bool launch_trace_multi(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_count, const hala_ray* rays, hala_hit* hits, uint32_t* counts,
                         uint32_t n, uint32_t k, WorkCounters* work, hipStream_t s);
 void launch_unbase_multi(hala_hit* hits, const float* moved, uint32_t n, uint32_t k, hipStream_t s);  // moved[i] back on every record of ray i
+// closest_point.hip — RENDER_SPEC 4.8: the nearest surface point of each of n queries on a one-level tree (staged or large), at out[i].
+// Launched like the multi-hit kernel (own LDS size and occupancy, a grid within lc.persistent_blocks).  counters (or null): 2 x uint64,
+// node visits and triangle tests are added to them.  false: it fits no compute unit, or the tree is a two-level one.
+bool launch_closest_point(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_count, const hala_point_query* queries, hala_closest_point* out,
+                          uint32_t n, WorkCounters* work, unsigned long long* counters, hipStream_t s);
 // shade.hip
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s);
 // resolve.hip

@@ -73,6 +73,46 @@ int hala_rt_trace_rays_multi_host(hala_rt_renderer* r, const hala_ray* rays, hal
   RT_HIP(hipStreamSynchronize(r->stream));
   return HALA_OK;
 }
+// RENDER_SPEC 4.8: the contract of hala_rt_trace_rays (scratch, stream order) around the closest-point kernel.  Nothing is re-based: the
+// kernel reads the caller's queries.  d_counters (2 x uint64, or null): node visits and triangle tests of the batch.
+int hala_rt_closest_points_counted(hala_rt_renderer* r, const hala_point_query* d_queries, hala_closest_point* d_out, uint32_t count,
+                                   uint64_t* d_counters, void* hip_stream) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  if (r->two_level) RT_FAIL("Closest-point queries are not built for two-level trees: commit the scene flattened (instancing = 0).");
+  if (count == 0) return HALA_OK;
+  if (!d_queries || !d_out) RT_FAIL("The query batch is null!");
+  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : r->stream;
+  if (r->scratch.acquire(s) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
+  if (d_counters) RT_HIP(hipMemsetAsync(d_counters, 0, 16, s));
+  const bool fits = launch_closest_point(r->lcfg, r->view(), r->cu_count, d_queries, d_out, count, r->d_batch_work.ptr,
+                                         reinterpret_cast<unsigned long long*>(d_counters), s);
+  if (!r->scratch.batch_done) RT_HIP(hipEventCreateWithFlags(&r->scratch.batch_done, hipEventDisableTiming));
+  RT_HIP(hipEventRecord(r->scratch.batch_done, s));
+  r->scratch.event = r->scratch.batch_done; r->scratch.stream = s;
+  if (!fits) RT_FAIL("The closest-point kernel does not fit on a compute unit.");
+  RT_HIP(hipGetLastError());
+  return HALA_OK;
+}
+int hala_rt_closest_points(hala_rt_renderer* r, const hala_point_query* d_queries, hala_closest_point* d_out, uint32_t count, void* hip_stream) {
+  return hala_rt_closest_points_counted(r, d_queries, d_out, count, nullptr, hip_stream);
+}
+int hala_rt_closest_points_host(hala_rt_renderer* r, const hala_point_query* queries, hala_closest_point* out, uint32_t count) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  if (r->two_level) RT_FAIL("Closest-point queries are not built for two-level trees: commit the scene flattened (instancing = 0).");
+  if (count == 0) return HALA_OK;
+  if (!queries || !out) RT_FAIL("The query batch is null!");
+  DeviceArray<hala_point_query> d_queries;
+  DeviceArray<hala_closest_point> d_out;
+  RT_HIP(d_queries.upload(queries, count, r->stream));
+  RT_HIP(d_out.resize(count));
+  if (hala_rt_closest_points(r, d_queries.ptr, d_out.ptr, count, r->stream) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipMemcpyAsync(out, d_out.ptr, (size_t)count * sizeof(hala_closest_point), hipMemcpyDeviceToHost, r->stream));
+  RT_HIP(hipStreamSynchronize(r->stream));
+  return HALA_OK;
+}
 int hala_rt_trace_rays_indirect(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_hits, const uint32_t* d_indirect, int mode, void* hip_stream) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (!d_indirect) RT_FAIL("The indirect command address is null!");

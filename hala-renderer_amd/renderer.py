@@ -533,6 +533,41 @@ class HalaRenderer:
         self._check(self._lib.hala_rt_trace_rays_multi(self._h, C.c_void_p(d_rays), C.c_void_p(d_hits), C.c_void_p(d_counts), C.c_uint32(count), C.c_uint32(k),
                                                        C.c_void_p(stream)))
 
+    def closest_points(self, points, radius=np.inf, out=None, count=None, stream: int = 0, d_counters: int = 0):
+        """RENDER_SPEC 4.8: the nearest surface point of every query point within `radius` (a scalar or one per point), as a structured
+        array of A.CLOSEST_POINT_DTYPE (distance, u, v, prim, point, region; a miss has distance -1 and prim 0xffffffff).  `points` is
+        an [n, 3] array or an array of A.POINT_QUERY_DTYPE (then `radius` is not used).
+        Device form: `points` is a device tensor of 16-B queries (or a device pointer, with `count`) and `out` a device tensor (or
+        pointer) of 32-B records; the batch is launched on `stream` and nothing is returned.  d_counters (device, 2 x uint64): node
+        visits and triangle tests, through the counting variant of the kernel."""
+        if out is not None or isinstance(points, int) or hasattr(points, "data_ptr"):
+            if out is None:
+                raise ValueError("the device form needs `out`")
+            d_q, d_o = (x.data_ptr() if hasattr(x, "data_ptr") else int(x) for x in (points, out))
+            if count is None:
+                if not hasattr(points, "data_ptr"):
+                    raise ValueError("a device pointer needs `count`")
+                count = points.numel() * points.element_size() // A.POINT_QUERY_DTYPE.itemsize
+            if hasattr(out, "data_ptr") and out.numel() * out.element_size() < count * A.CLOSEST_POINT_DTYPE.itemsize:
+                raise ValueError("`out` is too small for the batch")
+            if d_counters:
+                self._check(self._lib.hala_rt_closest_points_counted(self._h, C.c_void_p(d_q), C.c_void_p(d_o), C.c_uint32(count), C.c_void_p(d_counters),
+                                                                     C.c_void_p(stream)))
+            else:
+                self._check(self._lib.hala_rt_closest_points(self._h, C.c_void_p(d_q), C.c_void_p(d_o), C.c_uint32(count), C.c_void_p(stream)))
+            return None
+        pts = np.asarray(points)
+        if pts.dtype == A.POINT_QUERY_DTYPE:
+            q = np.ascontiguousarray(pts).reshape(-1)
+        else:
+            pts = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+            q = np.empty(pts.shape[0], dtype=A.POINT_QUERY_DTYPE)
+            q["point"] = pts
+            q["radius"] = np.broadcast_to(np.asarray(radius, dtype=np.float32), (pts.shape[0],))
+        res = np.empty(q.shape[0], dtype=A.CLOSEST_POINT_DTYPE)
+        self._check(self._lib.hala_rt_closest_points_host(self._h, C.c_void_p(q.ctypes.data), C.c_void_p(res.ctypes.data), C.c_uint32(q.shape[0])))
+        return res
+
     def bvh_info(self) -> A.BvhInfo:
         i = A.BvhInfo()
         self._check(self._lib.hala_rt_get_bvh_info(self._h, C.byref(i)))

@@ -882,6 +882,37 @@ int hala_rt_trace_rays_multi(hala_rt_renderer* r, const hala_ray* d_rays, hala_h
                              uint32_t count, uint32_t k, void* hip_stream);
 int hala_rt_trace_rays_multi_host(hala_rt_renderer* r, const hala_ray* rays, hala_hit* hits, uint32_t* counts, uint32_t count, uint32_t k);
 
+/* Closest-point query batches (RENDER_SPEC 4.8): for every point, the nearest point of the scene's surface within `radius` of it.
+ * Query i is answered in d_out[i]: the distance, the barycentrics (u, v) with the meaning they have in hala_hit, the global triangle id,
+ * the surface point itself and the region of the triangle it lies in (0 face; 1 / 2 / 3 edge AB / AC / BC; 4 / 5 / 6 vertex A / B / C).
+ * Among the triangles whose squared distance is at most radius * radius, the least (squared distance, triangle id) wins: ties go to the
+ * lower id, so the answer does not depend on how the tree was built.  A query that nothing answers (a NaN or negative radius among them)
+ * gets the miss record {-1, 0, 0, HALA_INVALID_INDEX, 0, 0, 0, 0}; a radius of FLT_MAX or +inf means "no limit".  Materials play no part.
+ * Everything else is the contract of hala_rt_trace_rays: a committed scene, count == 0 a no-op, the renderer's scratch and its stream
+ * order, the scene as it stands at the renderer's shutter step, after the last refit.  There is no far-origin re-basing (a point has no
+ * direction to slide along): the per-triangle arithmetic is the spec's at any distance.  Refused with a message and without touching
+ * anything: a null batch, no committed scene, a two-level tree (hala_bvh_info::instance_ref_count > 0: distances in an instance's object
+ * space are not world distances under a non-uniform transform).  Not built: closest points on two-level trees — commit such a scene
+ * flattened (instancing = 0, the automatic and faster form). */
+typedef struct hala_point_query {
+  float point[3];
+  float radius;
+} hala_point_query; /* 16 B */
+typedef struct hala_closest_point {
+  float distance; /* < 0 => miss */
+  float u;
+  float v;
+  uint32_t prim;  /* global triangle id; HALA_INVALID_INDEX on miss */
+  float point[3]; /* the nearest surface point */
+  uint32_t region;
+} hala_closest_point; /* 32 B */
+int hala_rt_closest_points(hala_rt_renderer* r, const hala_point_query* d_queries, hala_closest_point* d_out, uint32_t count, void* hip_stream);
+int hala_rt_closest_points_host(hala_rt_renderer* r, const hala_point_query* queries, hala_closest_point* out, uint32_t count);
+/* The same batch through the counting variant of the kernel: d_counters (device, 2 x uint64, or NULL) is set to the number of BVH nodes
+ * visited and of triangles tested.  For measurements (scripts/closest_point_timing.py); the answers are the same bytes. */
+int hala_rt_closest_points_counted(hala_rt_renderer* r, const hala_point_query* d_queries, hala_closest_point* d_out, uint32_t count,
+                                   uint64_t* d_counters, void* hip_stream);
+
 /* BVH introspection for the oracle cross-check: 64-B nodes + 48-B triangles as laid out in HBM.
  * node_width is 4: compressed 4-wide nodes (docs/RENDER_SPEC.md §4.1b). */
 typedef struct hala_bvh_info {

@@ -62,6 +62,9 @@ pub mod sys {
   }
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_ray { pub origin: [f32; 3], pub tmin: f32, pub direction: [f32; 3], pub tmax: f32 }
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_hit { pub t: f32, pub u: f32, pub v: f32, pub prim: u32 }
+  /// hala_point_query (16 B) / hala_closest_point (32 B): closest-point query batches (include/halart.h, docs/RENDER_SPEC.md 4.8)
+  #[repr(C)] #[derive(Clone, Copy)] pub struct hala_point_query { pub point: [f32; 3], pub radius: f32 }
+  #[repr(C)] #[derive(Clone, Copy)] pub struct hala_closest_point { pub distance: f32, pub u: f32, pub v: f32, pub prim: u32, pub point: [f32; 3], pub region: u32 }
   #[repr(C)] #[derive(Default)] pub struct hala_rt_info { pub width: u32, pub height: u32 }
 
   /// hala_rt_build_options (include/halart.h): every field 0 = the default
@@ -125,6 +128,11 @@ pub mod sys {
     pub fn hala_rt_trace_rays_multi(r: *mut hala_rt_renderer, d_rays: *const hala_ray, d_hits: *mut hala_hit, d_counts: *mut u32, count: u32, k: u32,
                                     hip_stream: *mut c_void) -> c_int;
     pub fn hala_rt_trace_rays_multi_host(r: *mut hala_rt_renderer, rays: *const hala_ray, hits: *mut hala_hit, counts: *mut u32, count: u32, k: u32) -> c_int;
+    pub fn hala_rt_closest_points(r: *mut hala_rt_renderer, d_queries: *const hala_point_query, d_out: *mut hala_closest_point, count: u32,
+                                  hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_closest_points_host(r: *mut hala_rt_renderer, queries: *const hala_point_query, out: *mut hala_closest_point, count: u32) -> c_int;
+    pub fn hala_rt_closest_points_counted(r: *mut hala_rt_renderer, d_queries: *const hala_point_query, d_out: *mut hala_closest_point, count: u32,
+                                          d_counters: *mut u64, hip_stream: *mut c_void) -> c_int;
     pub fn hala_rt_update_node_transform(r: *mut hala_rt_renderer, node_index: u32, local_transform: *const f32) -> c_int;
     pub fn hala_rt_update_material(r: *mut hala_rt_renderer, material_index: u32, material: *const hala_material_desc) -> c_int;
     pub fn hala_rt_update_vertices(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, vertices: *const hala_vertex, vertex_count: u32) -> c_int;
@@ -330,6 +338,17 @@ impl HalaRenderer {
     check(unsafe { sys::hala_rt_update_vertices(self.h, mesh_index, primitive_index, vertices.as_ptr(), vertices.len() as u32) })
   }
   pub fn refit(&mut self) -> Result<(), HalaRendererError> { check(unsafe { sys::hala_rt_refit(self.h) }) }
+  /// closest-point queries (RENDER_SPEC 4.8) from host memory: the nearest surface point within each query's radius; a miss has distance < 0
+  pub fn closest_points(&self, queries: &[sys::hala_point_query]) -> Result<Vec<sys::hala_closest_point>, HalaRendererError> {
+    let miss = sys::hala_closest_point { distance: -1.0, u: 0.0, v: 0.0, prim: u32::MAX, point: [0.0; 3], region: 0 };
+    let mut out = vec![miss; queries.len()];
+    check(unsafe { sys::hala_rt_closest_points_host(self.h, queries.as_ptr(), out.as_mut_ptr(), queries.len() as u32) })?;
+    Ok(out)
+  }
+  /// the device-pointer form, on the renderer's stream
+  pub fn closest_points_device(&self, d_queries: *const sys::hala_point_query, d_out: *mut sys::hala_closest_point, count: u32) -> Result<(), HalaRendererError> {
+    check(unsafe { sys::hala_rt_closest_points(self.h, d_queries, d_out, count, std::ptr::null_mut()) })
+  }
   /// binds an ordered node set (empty: unbinds); refit_nodes then takes one local transform per bound node, in that order
   pub fn bind_nodes(&mut self, node_indices: &[u32]) -> Result<(), HalaRendererError> {
     check(unsafe { sys::hala_rt_bind_nodes(self.h, node_indices.as_ptr(), node_indices.len() as u32) })
