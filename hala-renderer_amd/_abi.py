@@ -145,6 +145,10 @@ class ClosestPoint(C.Structure):  # hala_closest_point, 32 B
     _fields_ = [("distance", C.c_float), ("u", C.c_float), ("v", C.c_float), ("prim", C.c_uint32), ("point", C.c_float * 3), ("region", C.c_uint32)]
 
 
+class DistanceGridDesc(C.Structure):  # hala_distance_grid_desc, 36 B (RENDER_SPEC 4.9)
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float), ("dims", C.c_uint32 * 3), ("band", C.c_float), ("flags", C.c_uint32)]
+
+
 class RtInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -324,6 +328,9 @@ PROTOTYPES = {
     "hala_rt_closest_points": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p], C.c_int),
     "hala_rt_closest_points_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32], C.c_int),
     "hala_rt_closest_points_counted": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
+    "hala_rt_distance_grid": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hala_rt_distance_grid_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hala_rt_distance_grid_counted": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "hala_rtprog_trace_rays_multi": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
     "hala_rt_denoise": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
@@ -465,5 +472,7 @@ EXPORTS = [
     "hala_rt_selftest_math", "hala_rt_selftest_math_values", "hala_rt_selftest_collapse", "hala_rt_selftest_hierarchy",
     "hala_rt_trace_rays_multi", "hala_rt_trace_rays_multi_host", "hala_rtprog_trace_rays_multi",
     "hala_rt_closest_points", "hala_rt_closest_points_host", "hala_rt_closest_points_counted",
+    "hala_rt_distance_grid", "hala_rt_distance_grid_host", "hala_rt_distance_grid_counted",
 ]
 MAX_MULTI_HITS = 16  # HALA_MAX_MULTI_HITS (RENDER_SPEC 4.7)
+GRID_SIGNED, GRID_METHOD_SHIFT, MAX_GRID_DIM = 1, 1, 1024  # HALA_GRID_* (RENDER_SPEC 4.9)

@@ -49,6 +49,20 @@ void launch_unbase_multi(hala_hit* hits, const float* moved, uint32_t n, uint32_
 // node visits and triangle tests are added to them.  false: it fits no compute unit, or the tree is a two-level one.
 bool launch_closest_point(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_count, const hala_point_query* queries, hala_closest_point* out,
                           uint32_t n, WorkCounters* work, unsigned long long* counters, hipStream_t s);
+// distance_grid.hip — RENDER_SPEC 4.9: the distance field of the scene on a voxel grid, on a one-level tree (staged or large).  Launched
+// like the closest-point kernel.  launch_grid_rows leaves in `bits` (zeroed by the caller: ny * nz rows of `words` words) the suffix
+// parities of every row's crossings; launch_distance_grid writes distance[nz][ny][nx] (and prim, or null) by method 1 (a voxel per lane)
+// or 2 (a 4 x 4 x 4 brick per wave), and flips the sign of the voxels that `inside` (those bits, or null: unsigned) marks.  counters (or
+// null): 6 x uint64, see hala_rt_distance_grid_counted.  false: the kernel fits no compute unit, or the tree is a two-level one.
+struct GridView {
+  float origin[3], spacing, band;
+  uint32_t nx, ny, nz;
+  uint32_t words;  // of a row's bit array: (nx + 1 + 31) / 32
+};
+bool launch_grid_rows(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_count, const GridView& g, uint32_t* bits, WorkCounters* work,
+                      unsigned long long* counters, hipStream_t s);
+bool launch_distance_grid(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_count, const GridView& g, uint32_t method, float* distance, uint32_t* prim,
+                          const uint32_t* inside, WorkCounters* work, unsigned long long* counters, hipStream_t s);
 // shade.hip
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s);
 // resolve.hip

@@ -497,6 +497,8 @@ struct hala_rt_renderer {
   // hala_rt_trace_rays, RENDER_SPEC 4.2: the caller's batch with far origins re-based, and how far each was moved (grown on demand)
   DeviceArray<hala_ray> d_batch_rays;
   DeviceArray<float> d_batch_moved;
+  // hala_rt_distance_grid, RENDER_SPEC 4.9: the rows' crossing bits of a signed grid (grown on demand)
+  DeviceArray<uint32_t> d_grid_bits;
 
   uint64_t total_frames = 0;
   bool counting = false;

@@ -113,6 +113,81 @@ int hala_rt_closest_points_host(hala_rt_renderer* r, const hala_point_query* que
   RT_HIP(hipStreamSynchronize(r->stream));
   return HALA_OK;
 }
+// RENDER_SPEC 4.9.  Which distance kernel an automatic grid runs (DESIGN.md 28 has the measurements the rule rests on).  The per-wave
+// walk runs, in every lane, the union of what its 64 voxels need, and saves the wave its node and triangle fetches.  It wins where those
+// fetches come from memory (not a staged tree), where the band does not end a query early (it spans the scene box) and where the voxels
+// are fine against the scene: spacing * sqrt(triangles) <= 4.4 x the box's largest extent.  Everywhere else a voxel per lane.
+static uint32_t grid_auto_method(const SceneView& sv, const hala_distance_grid_desc* g) {
+  if (sv.staged) return 1u;
+  const float extent = std::max(sv.box_max[0] - sv.box_min[0], std::max(sv.box_max[1] - sv.box_min[1], sv.box_max[2] - sv.box_min[2]));
+  if (!(g->band >= extent)) return 1u;
+  return g->spacing * std::sqrt((float)sv.tri_count) <= 4.4f * extent ? 2u : 1u;
+}
+static int grid_check(hala_rt_renderer* r, const hala_distance_grid_desc* g, const void* distance) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!g) RT_FAIL("The distance grid description is null!");
+  if (!distance) RT_FAIL("The distance grid output is null!");
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  if (r->two_level) RT_FAIL("Distance grids are not built for two-level trees: commit the scene flattened (instancing = 0).");
+  for (int a = 0; a < 3; ++a)
+    if (g->dims[a] == 0 || g->dims[a] > 1024u) RT_FAIL("The distance grid's dims must be 1..1024 each.");
+  if (!(std::isfinite(g->spacing) && g->spacing > 0.0f)) RT_FAIL("The distance grid's spacing must be finite and positive.");
+  if (!(g->band >= 0.0f)) RT_FAIL("The distance grid's band must be >= 0 or +inf.");
+  if ((g->flags & ~7u) != 0u || ((g->flags >> HALA_GRID_METHOD_SHIFT) & 3u) == 3u) RT_FAIL("Unknown distance grid flags.");
+  return HALA_OK;
+}
+// The contract of hala_rt_trace_rays (scratch, stream order) around the row pass of a signed grid and the distance pass; the rows' bits
+// live in a buffer the renderer owns (growing it frees the old one, which waits for whoever still reads it).
+int hala_rt_distance_grid_counted(hala_rt_renderer* r, const hala_distance_grid_desc* desc, float* d_distance, uint32_t* d_prim, uint64_t* d_counters,
+                                  void* hip_stream) {
+  if (grid_check(r, desc, d_distance) != HALA_OK) return HALA_ERR;
+  GridView g{};
+  memcpy(g.origin, desc->origin, sizeof(g.origin));
+  g.spacing = desc->spacing; g.band = desc->band; g.nx = desc->dims[0]; g.ny = desc->dims[1]; g.nz = desc->dims[2];
+  g.words = (g.nx + 1u + 31u) / 32u;
+  const bool is_signed = (desc->flags & HALA_GRID_SIGNED) != 0u;
+  uint32_t method = (desc->flags >> HALA_GRID_METHOD_SHIFT) & 3u;
+  const SceneView sv = r->view();
+  if (method == 0u) method = grid_auto_method(sv, desc);
+  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : r->stream;
+  const size_t bit_words = (size_t)g.ny * g.nz * g.words;
+  if (is_signed && r->d_grid_bits.count < bit_words) RT_HIP(r->d_grid_bits.resize(bit_words));
+  if (r->scratch.acquire(s) != HALA_OK) return HALA_ERR;
+  unsigned long long* counters = reinterpret_cast<unsigned long long*>(d_counters);
+  if (d_counters) RT_HIP(hipMemsetAsync(d_counters, 0, 48, s));
+  bool fits = true;
+  if (is_signed) {
+    RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
+    RT_HIP(hipMemsetAsync(r->d_grid_bits.ptr, 0, bit_words * 4, s));
+    fits = launch_grid_rows(r->lcfg, sv, r->cu_count, g, r->d_grid_bits.ptr, r->d_batch_work.ptr, counters, s);
+  }
+  if (fits) {
+    RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
+    fits = launch_distance_grid(r->lcfg, sv, r->cu_count, g, method, d_distance, d_prim, is_signed ? r->d_grid_bits.ptr : nullptr, r->d_batch_work.ptr, counters, s);
+  }
+  if (!r->scratch.batch_done) RT_HIP(hipEventCreateWithFlags(&r->scratch.batch_done, hipEventDisableTiming));
+  RT_HIP(hipEventRecord(r->scratch.batch_done, s));
+  r->scratch.event = r->scratch.batch_done; r->scratch.stream = s;
+  if (!fits) RT_FAIL("The distance grid kernels do not fit on a compute unit.");
+  RT_HIP(hipGetLastError());
+  return HALA_OK;
+}
+int hala_rt_distance_grid(hala_rt_renderer* r, const hala_distance_grid_desc* desc, float* d_distance, uint32_t* d_prim, void* hip_stream) {
+  return hala_rt_distance_grid_counted(r, desc, d_distance, d_prim, nullptr, hip_stream);
+}
+int hala_rt_distance_grid_host(hala_rt_renderer* r, const hala_distance_grid_desc* desc, float* distance, uint32_t* prim) {
+  if (grid_check(r, desc, distance) != HALA_OK) return HALA_ERR;
+  const size_t n = (size_t)desc->dims[0] * desc->dims[1] * desc->dims[2];
+  DeviceArray<float> d_distance;
+  DeviceArray<uint32_t> d_prim;
+  RT_HIP(d_distance.resize(n));
+  if (prim) RT_HIP(d_prim.resize(n));
+  if (hala_rt_distance_grid(r, desc, d_distance.ptr, prim ? d_prim.ptr : nullptr, r->stream) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipMemcpyAsync(distance, d_distance.ptr, n * 4, hipMemcpyDeviceToHost, r->stream));
+  if (prim) RT_HIP(hipMemcpyAsync(prim, d_prim.ptr, n * 4, hipMemcpyDeviceToHost, r->stream));
+  RT_HIP(hipStreamSynchronize(r->stream));
+  return HALA_OK;
+}
 int hala_rt_trace_rays_indirect(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_hits, const uint32_t* d_indirect, int mode, void* hip_stream) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (!d_indirect) RT_FAIL("The indirect command address is null!");

@@ -568,6 +568,36 @@ class HalaRenderer:
         self._check(self._lib.hala_rt_closest_points_host(self._h, C.c_void_p(q.ctypes.data), C.c_void_p(res.ctypes.data), C.c_uint32(q.shape[0])))
         return res
 
+    def distance_grid(self, origin, spacing, dims, band=np.inf, signed=True, method=None, want_prim=False, out=None, out_prim=None, stream: int = 0,
+                      d_counters: int = 0):
+        """RENDER_SPEC 4.9: the scene's distance field on the grid of dims = (nx, ny, nz) cubic voxels of size `spacing` whose voxel
+        (0, 0, 0) is centred at `origin`, as a float32 array [nz, ny, nx]: the closest-point distance within `band`, or `band`;
+        signed=True flips the sign bit of the voxels inside (crossing parity along +x).  method: None automatic, 1 a voxel per lane, 2
+        a brick per wave — the result is the same.  want_prim=True returns (distance, prim), prim a uint32 array of triangle ids
+        (0xffffffff where the band answered).
+        Device form: `out` is a device tensor or pointer of nx * ny * nz floats (and `out_prim` one of as many uint32, or None); the
+        grid is launched on `stream` and nothing is returned.  d_counters (device, 6 x uint64): the counting variants."""
+        nx, ny, nz = (int(d) for d in dims)
+        desc = A.DistanceGridDesc((C.c_float * 3)(*[float(x) for x in origin]), float(spacing), (C.c_uint32 * 3)(nx, ny, nz), float(band),
+                                  (A.GRID_SIGNED if signed else 0) | (int(method or 0) << A.GRID_METHOD_SHIFT))
+        if out is not None:
+            d_o, d_p = (x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0) for x in (out, out_prim))
+            for x in (out, out_prim):
+                if hasattr(x, "data_ptr") and x.numel() * x.element_size() < nx * ny * nz * 4:
+                    raise ValueError("the output is too small for the grid")
+            if d_counters:
+                self._check(self._lib.hala_rt_distance_grid_counted(self._h, C.byref(desc), C.c_void_p(d_o), C.c_void_p(d_p), C.c_void_p(d_counters),
+                                                                    C.c_void_p(stream)))
+            else:
+                self._check(self._lib.hala_rt_distance_grid(self._h, C.byref(desc), C.c_void_p(d_o), C.c_void_p(d_p), C.c_void_p(stream)))
+            return None
+        shape = tuple(max(d, 0) for d in (nz, ny, nx))
+        distance = np.empty(shape, dtype=np.float32)
+        prim = np.empty(shape, dtype=np.uint32) if want_prim else None
+        self._check(self._lib.hala_rt_distance_grid_host(self._h, C.byref(desc), C.c_void_p(distance.ctypes.data),
+                                                         C.c_void_p(prim.ctypes.data) if want_prim else None))
+        return (distance, prim) if want_prim else distance
+
     def bvh_info(self) -> A.BvhInfo:
         i = A.BvhInfo()
         self._check(self._lib.hala_rt_get_bvh_info(self._h, C.byref(i)))

@@ -913,6 +913,43 @@ int hala_rt_closest_points_host(hala_rt_renderer* r, const hala_point_query* que
 int hala_rt_closest_points_counted(hala_rt_renderer* r, const hala_point_query* d_queries, hala_closest_point* d_out, uint32_t count,
                                    uint64_t* d_counters, void* hip_stream);
 
+/* Signed distance grids (RENDER_SPEC 4.9): the scene's distance field on a grid of cubic voxels.  Voxel (i, j, k) stands at
+ * p = fma((float)index, spacing, origin) per axis (`origin` is the centre of voxel (0, 0, 0)); d_distance[(k * ny + j) * nx + i] is the
+ * distance hala_rt_closest_points answers the query (p, band) with, bit for bit, or `band` where it has no answer; d_prim (or NULL) gets
+ * the answer's triangle id, or HALA_INVALID_INDEX.  `band` is >= 0 or +inf and holds for the whole grid; each of dims is 1 .. 1024.
+ * flags: bit 0 HALA_GRID_SIGNED — a voxel is inside iff the ray from it along +x (a mode-0 ray from the row's voxel 0, far-origin rule
+ * included) crosses the scene an odd number of times beyond it, and inside flips the value's sign bit (so -band and -0 occur).  That sign
+ * is exact for closed surfaces, arbitrary but pinned for open ones, and a row that runs exactly through a shared edge counts it twice:
+ * keep `origin` off the vertices' coordinates.  Bits 1-2 choose the kernel of the distance pass: 0 automatic, 1 one voxel per lane, 2 one
+ * 4 x 4 x 4 brick per wave; the result does not depend on it, nor on the builder or the tree form.  Everything else is the contract of
+ * hala_rt_trace_rays: a committed scene, the renderer's scratch and its stream order, the scene as it stands at the renderer's shutter
+ * step, after the last refit.  Refused with a message and without touching anything: a null description or output, no committed scene, a
+ * two-level tree (as for closest points), a dim of 0 or above 1024, a spacing that is not finite and positive, a NaN or negative band, any
+ * other flag bit.  Not built: two-level trees, per-axis spacing, sparse or brick-list output, gradients, a sign from pseudo-normals or
+ * winding numbers, seeding a brick's limit from its neighbour. */
+typedef struct hala_distance_grid_desc {
+  float origin[3];
+  float spacing;
+  uint32_t dims[3]; /* nx, ny, nz */
+  float band;
+  uint32_t flags;
+} hala_distance_grid_desc; /* 36 B */
+#define HALA_GRID_SIGNED 1u
+#define HALA_GRID_METHOD_SHIFT 1 /* (flags >> 1) & 3: 0 automatic, 1 per lane, 2 per wave */
+int hala_rt_distance_grid(hala_rt_renderer* r, const hala_distance_grid_desc* desc, float* d_distance, uint32_t* d_prim /* or NULL */, void* hip_stream);
+int hala_rt_distance_grid_host(hala_rt_renderer* r, const hala_distance_grid_desc* desc, float* distance, uint32_t* prim /* or NULL */);
+/* The same grid through the counting variants of the kernels: d_counters (device, 6 x uint64, or NULL) is set to
+ *   [0] node visits and [1] triangle tests of the distance pass, each counted per lane that holds a voxel: in method 1 a lane's own
+ *       visit of a node / its own test of a triangle; in method 2 every visit (test) of the wave counts once for each of its lanes that
+ *       holds a voxel, since each of them runs the child keys (the triangle's arithmetic) — [0] / voxels and [1] / voxels are the
+ *       arithmetic one voxel costs in either method;
+ *   [2] node visits and [3] triangle tests of the row pass (per lane: one lane owns one row), 0 for an unsigned grid;
+ *   [4] nodes and [5] triangles a wave FETCHED in method 2 (one fetch serves the wave's 64 lanes), 0 in method 1, where every count of
+ *       [0], [1] is a fetch of its own.
+ * For measurements (scripts/distance_grid_timing.py); the grid is the same bytes. */
+int hala_rt_distance_grid_counted(hala_rt_renderer* r, const hala_distance_grid_desc* desc, float* d_distance, uint32_t* d_prim /* or NULL */,
+                                  uint64_t* d_counters, void* hip_stream);
+
 /* BVH introspection for the oracle cross-check: 64-B nodes + 48-B triangles as laid out in HBM.
  * node_width is 4: compressed 4-wide nodes (docs/RENDER_SPEC.md §4.1b). */
 typedef struct hala_bvh_info {

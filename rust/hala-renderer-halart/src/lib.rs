@@ -65,6 +65,8 @@ pub mod sys {
   /// hala_point_query (16 B) / hala_closest_point (32 B): closest-point query batches (include/halart.h, docs/RENDER_SPEC.md 4.8)
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_point_query { pub point: [f32; 3], pub radius: f32 }
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_closest_point { pub distance: f32, pub u: f32, pub v: f32, pub prim: u32, pub point: [f32; 3], pub region: u32 }
+  /// hala_distance_grid_desc (36 B): signed distance grids (include/halart.h, docs/RENDER_SPEC.md 4.9); flags: bit 0 signed, bits 1-2 method
+  #[repr(C)] #[derive(Clone, Copy)] pub struct hala_distance_grid_desc { pub origin: [f32; 3], pub spacing: f32, pub dims: [u32; 3], pub band: f32, pub flags: u32 }
   #[repr(C)] #[derive(Default)] pub struct hala_rt_info { pub width: u32, pub height: u32 }
 
   /// hala_rt_build_options (include/halart.h): every field 0 = the default
@@ -133,6 +135,11 @@ pub mod sys {
     pub fn hala_rt_closest_points_host(r: *mut hala_rt_renderer, queries: *const hala_point_query, out: *mut hala_closest_point, count: u32) -> c_int;
     pub fn hala_rt_closest_points_counted(r: *mut hala_rt_renderer, d_queries: *const hala_point_query, d_out: *mut hala_closest_point, count: u32,
                                           d_counters: *mut u64, hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_distance_grid(r: *mut hala_rt_renderer, desc: *const hala_distance_grid_desc, d_distance: *mut f32, d_prim: *mut u32,
+                                 hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_distance_grid_host(r: *mut hala_rt_renderer, desc: *const hala_distance_grid_desc, distance: *mut f32, prim: *mut u32) -> c_int;
+    pub fn hala_rt_distance_grid_counted(r: *mut hala_rt_renderer, desc: *const hala_distance_grid_desc, d_distance: *mut f32, d_prim: *mut u32,
+                                         d_counters: *mut u64, hip_stream: *mut c_void) -> c_int;
     pub fn hala_rt_update_node_transform(r: *mut hala_rt_renderer, node_index: u32, local_transform: *const f32) -> c_int;
     pub fn hala_rt_update_material(r: *mut hala_rt_renderer, material_index: u32, material: *const hala_material_desc) -> c_int;
     pub fn hala_rt_update_vertices(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, vertices: *const hala_vertex, vertex_count: u32) -> c_int;
@@ -346,6 +353,12 @@ impl HalaRenderer {
     Ok(out)
   }
   /// the device-pointer form, on the renderer's stream
+  /// RENDER_SPEC 4.9: the distance field on a grid, [nz][ny][nx] with x fastest (host memory, synchronous)
+  pub fn distance_grid(&self, desc: &sys::hala_distance_grid_desc) -> Result<Vec<f32>, HalaRendererError> {
+    let mut out = vec![0.0f32; desc.dims[0] as usize * desc.dims[1] as usize * desc.dims[2] as usize];
+    check(unsafe { sys::hala_rt_distance_grid_host(self.h, desc, out.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok(out)
+  }
   pub fn closest_points_device(&self, d_queries: *const sys::hala_point_query, d_out: *mut sys::hala_closest_point, count: u32) -> Result<(), HalaRendererError> {
     check(unsafe { sys::hala_rt_closest_points(self.h, d_queries, d_out, count, std::ptr::null_mut()) })
   }
