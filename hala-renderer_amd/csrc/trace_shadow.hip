@@ -29,7 +29,47 @@ k_trace_shadow(SceneView sv, Queues q, PathState ps, Control* __restrict__ ctl, 
 // Here a wave that finds one queue dry moves straight on to the next: one tail instead of three.  (Launches side by side on two streams
 // do not achieve this: each takes the chip from the other all the time, profiles/r02_experiments.txt.)  Not used by updates that carry
 // per-launch timing events or counting kernels.
+// Roles: a wave leaves a queue only when its last ray has ended, so when all workgroups walk the queues in one order every wave of the
+// grid drains at the moment a queue runs dry, twice in mid-launch, with ever fewer live lanes.  The queues are independent and handed
+// out from shared counters, so any workgroup may take them in any order: a workgroup STARTS on the queue of its role (light, environment
+// or closest hit; own stage first, then the others) and the roles are dealt in proportion to the work each queue holds, so that the
+// three queues run dry together near the launch's end and most waves never drain before its tail.  configs[3]: fused launch 4.57 ->
+// 4.29 ms per frame, frame 7.56 -> 7.35 ms; two roles (any hit / closest hit) gain about half of that (profiles/fused_roles.txt).
 // ---------------------------------------------------------------------------------------------------------
+#ifndef RT_FUSED_ROLES
+#define RT_FUSED_ROLES 3  // tuning builds: 0 = every workgroup takes the queues in the order light, environment, closest; 2 = two roles (any hit, closest hit)
+#endif
+// What a ray of each kind costs the chip, in ps: the time of the launches that trace only that kind, each with the chip to itself, divided
+// by their rays (bench.py on configs[3] with every workgroup on one order, its two frames with one launch per pass: roofline.unfused_kernels,
+// 1000 / grays_per_s_in_kernel: batch 152.3 and 153.7, shadow 128.4 and 129.7 in two runs).  Only the ratio (1.19) matters: the frame is the same to
+// 0.01 ms from 0.89 to 1.3, 0.02 - 0.06 ms shorter near 1.6 and 0.09 ms longer at 2.0 (profiles/fused_roles.txt): kept as measured, not fitted.
+#ifndef RT_ROLE_COST_CLOSEST
+#define RT_ROLE_COST_CLOSEST 153.0f
+#endif
+#ifndef RT_ROLE_COST_ANY
+#define RT_ROLE_COST_ANY 129.0f
+#endif
+constexpr uint32_t kRoleGroup = 16;  // consecutive workgroups that share a role: one per work shard (work_begin), two per XCD
+// The stage a workgroup starts on: 0 light connections, 1 environment connections, 2 closest hit.  Groups of kRoleGroup workgroups take
+// the roles in proportion to the work each queue holds (rays x cost), every role spread evenly over the grid: a share f of the groups
+// is those g at which round(g f) steps.  An empty or absent queue (n == 0) gets no group: role 2 implies a closest-hit queue.  A grid of
+// fewer than kRoleGroup workgroups is one group: closest hit if that is half the work or more, else the larger connection queue.
+// Wave-uniform; nothing a frame computes depends on the roles: every workgroup visits every stage, and a stage whose queue is dry
+// returns through the dry mask.
+RT_DI uint32_t fused_role(uint32_t n_light, uint32_t n_env, uint32_t n_closest) {
+  const float wl = (float)n_light * RT_ROLE_COST_ANY, we = (float)n_env * RT_ROLE_COST_ANY, wc = (float)n_closest * RT_ROLE_COST_CLOSEST;
+  const float wa = wl + we;
+  if (!(wa + wc > 0.0f)) return 0u;
+  const uint32_t g = blockIdx.x / kRoleGroup;
+  const float fc = wc / (wa + wc);
+  const uint32_t c0 = (uint32_t)((float)g * fc + 0.5f), c1 = (uint32_t)((float)(g + 1u) * fc + 0.5f);
+  if (c1 != c0) return 2u;
+  if (RT_FUSED_ROLES == 2 || !(wa > 0.0f)) return 0u;
+  const uint32_t a = g - c0;  // this group's rank among the any-hit groups
+  const float fl = wl / wa;
+  return (uint32_t)((float)(a + 1u) * fl + 0.5f) != (uint32_t)((float)a * fl + 0.5f) ? 0u : 1u;
+}
+
 template <bool STAGED, bool ALPHA, bool INST, bool GROUPS>
 __global__ void __launch_bounds__(kTraverseThreads, STAGED ? kTraverseWavesPerSimdStaged : kTraverseWavesPerSimd)
 k_trace_shadow_then_batch(SceneView sv, const Tri* __restrict__ tris_any, Queues q, PathState ps, Control* __restrict__ ctl, uint32_t depth,
@@ -37,6 +77,29 @@ k_trace_shadow_then_batch(SceneView sv, const Tri* __restrict__ tris_any, Queues
   const TraverseLds lds = stage_bvh<STAGED, INST>(sv, g_smem);
   uint2* spill = lane_spill(spill_base);
   StepCounters sc;
+#if RT_FUSED_ROLES
+  const uint32_t n_light = (kinds & 1u) ? ctl->sizes.n_shadow[0][depth] : 0u, n_env = (kinds & 2u) ? ctl->sizes.n_shadow[1][depth] : 0u;
+  const uint32_t n_closest = rays != nullptr ? ctl->sizes.n_active[depth + 1u] : 0u;
+  const uint32_t role = lane0_u32(fused_role(n_light, n_env, n_closest));
+  auto closest = [&]() {
+    const uint32_t n = ctl->sizes.n_active[depth + 1u];
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->totals.rays_closest += n;
+    BatchSource src{rays, hits, false, true, STAGED && refill == 64u};
+    persistent_trace<false, false, STAGED, false, INST>(sv, lds, spill, &ctl->work_closest, n, refill, src, sc);
+  };
+  if (role == 2u) closest();  // three inlined wave loops, one after the other: a loop over the stages keeps registers live across them (scratch in the ALPHA variants)
+  {
+    SceneView sva = sv;
+    sva.tris = tris_any;  // RENDER_SPEC 7.1d (STAGED: the launcher only fuses when both passes traverse the same triangles)
+    for (uint32_t i = 0; i < 2u; ++i) {
+      const uint32_t kind = i ^ (role & 1u);  // bit 0 of kinds: light connections, bit 1: environment connections
+      if (!((kinds >> kind) & 1u)) continue;
+      auto src = shadow_source<ALPHA, GROUPS>(q, ps, kind);
+      persistent_trace<true, false, STAGED, ALPHA, INST>(sva, lds, spill, &ctl->work_shadow[kind], ctl->sizes.n_shadow[kind][depth], refill, src, sc);
+    }
+  }
+  if (role != 2u && rays != nullptr) closest();
+#else
   {
     SceneView sva = sv;
     sva.tris = tris_any;  // RENDER_SPEC 7.1d (STAGED: the launcher only fuses when both passes traverse the same triangles)
@@ -51,6 +114,7 @@ k_trace_shadow_then_batch(SceneView sv, const Tri* __restrict__ tris_any, Queues
   if (blockIdx.x == 0 && threadIdx.x == 0) ctl->totals.rays_closest += n;
   BatchSource src{rays, hits, false, true, STAGED && refill == 64u};
   persistent_trace<false, false, STAGED, false, INST>(sv, lds, spill, &ctl->work_closest, n, refill, src, sc);
+#endif
 }
 uint32_t trace_shadow_blocks_per_cu(size_t dynamic_lds_bytes, TreeForm tree) {
   return tree_blocks_per_cu([](auto STAGED, auto INST) { return k_trace_shadow<false, STAGED, false, INST, false>; }, tree, kTraverseThreads, dynamic_lds_bytes);
