@@ -149,6 +149,14 @@ class DistanceGridDesc(C.Structure):  # hala_distance_grid_desc, 36 B (RENDER_SP
     _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float), ("dims", C.c_uint32 * 3), ("band", C.c_float), ("flags", C.c_uint32)]
 
 
+class OcclusionSample(C.Structure):  # hala_occlusion_sample, 32 B (RENDER_SPEC 4.10)
+    _fields_ = [("point", C.c_float * 3), ("bias", C.c_float), ("normal", C.c_float * 3), ("reach", C.c_float)]
+
+
+class Occlusion(C.Structure):  # hala_occlusion, 16 B
+    _fields_ = [("visibility", C.c_float), ("bent", C.c_float * 3)]
+
+
 class RtInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -331,6 +339,9 @@ PROTOTYPES = {
     "hala_rt_distance_grid": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "hala_rt_distance_grid_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "hala_rt_distance_grid_counted": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    # renderer, samples, out, masks | count, rays, seed (, stream)
+    "hala_rt_occlusion": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
+    "hala_rt_occlusion_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32], C.c_int),
     "hala_rtprog_trace_rays_multi": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
     "hala_rt_denoise": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
@@ -424,6 +435,9 @@ HIT_DTYPE = _np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4")
 # RENDER_SPEC 4.8: hala_point_query (16 B), hala_closest_point (32 B)
 POINT_QUERY_DTYPE = _np.dtype([("point", "<f4", 3), ("radius", "<f4")])
 CLOSEST_POINT_DTYPE = _np.dtype([("distance", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("point", "<f4", 3), ("region", "<u4")])
+# RENDER_SPEC 4.10: hala_occlusion_sample (32 B), hala_occlusion (16 B)
+OCCLUSION_SAMPLE_DTYPE = _np.dtype([("point", "<f4", 3), ("bias", "<f4"), ("normal", "<f4", 3), ("reach", "<f4")])
+OCCLUSION_DTYPE = _np.dtype([("visibility", "<f4"), ("bent", "<f4", 3)])
 VERTEX_DTYPE = _np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("tex_coord", "<f4", 2)])
 
 # every symbol include/halart.h declares (tests/test_abi.py checks the .so exports all of them)
@@ -473,6 +487,8 @@ EXPORTS = [
     "hala_rt_trace_rays_multi", "hala_rt_trace_rays_multi_host", "hala_rtprog_trace_rays_multi",
     "hala_rt_closest_points", "hala_rt_closest_points_host", "hala_rt_closest_points_counted",
     "hala_rt_distance_grid", "hala_rt_distance_grid_host", "hala_rt_distance_grid_counted",
+    "hala_rt_occlusion", "hala_rt_occlusion_host",
 ]
 MAX_MULTI_HITS = 16  # HALA_MAX_MULTI_HITS (RENDER_SPEC 4.7)
+MAX_OCCLUSION_RAYS = 256  # HALA_MAX_OCCLUSION_RAYS (RENDER_SPEC 4.10)
 GRID_SIGNED, GRID_METHOD_SHIFT, MAX_GRID_DIM = 1, 1, 1024  # HALA_GRID_* (RENDER_SPEC 4.9)

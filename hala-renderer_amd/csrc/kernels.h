@@ -63,6 +63,12 @@ bool launch_grid_rows(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_coun
                       unsigned long long* counters, hipStream_t s);
 bool launch_distance_grid(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_count, const GridView& g, uint32_t method, float* distance, uint32_t* prim,
                           const uint32_t* inside, WorkCounters* work, unsigned long long* counters, hipStream_t s);
+// occlusion.hip — RENDER_SPEC 4.10: `rays` any-hit rays over the hemisphere of each of `count` samples (count * rays < 2^32), generated
+// in the lanes that trace them; masks (count * ceil(rays / 32) words, zeroed by the caller) gets the occluded bits, out[i] the record.
+// Launched like an any-hit batch of launch_trace_batch (sv.tris_any, lc's grid and LDS, the ALPHA variants for translucent materials), on
+// every tree form; then one lane per sample reduces the masks.
+void launch_trace_occlusion(const LaunchCfg& lc, const SceneView& sv, const hala_occlusion_sample* samples, hala_occlusion* out, uint32_t* masks,
+                            uint32_t count, uint32_t rays, uint32_t seed, WorkCounters* work, hipStream_t s);
 // shade.hip
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s);
 // resolve.hip

@@ -499,6 +499,8 @@ struct hala_rt_renderer {
   DeviceArray<float> d_batch_moved;
   // hala_rt_distance_grid, RENDER_SPEC 4.9: the rows' crossing bits of a signed grid (grown on demand)
   DeviceArray<uint32_t> d_grid_bits;
+  // hala_rt_occlusion, RENDER_SPEC 4.10: the mask words of a batch whose caller wants none (grown on demand)
+  DeviceArray<uint32_t> d_occlusion_masks;
 
   uint64_t total_frames = 0;
   bool counting = false;

@@ -188,6 +188,55 @@ int hala_rt_distance_grid_host(hala_rt_renderer* r, const hala_distance_grid_des
   RT_HIP(hipStreamSynchronize(r->stream));
   return HALA_OK;
 }
+// RENDER_SPEC 4.10: the contract of hala_rt_trace_rays (scratch, stream order) around the occlusion kernels.  Nothing is copied or
+// re-based ahead of the launch: the rays are made, far origins included, in the lanes that trace them.  Without the caller's mask array
+// the words live in a buffer the renderer owns (growing it frees the old one, which waits for whoever still reads it).
+static int occlusion_check(hala_rt_renderer* r, const void* samples, const void* out, uint32_t count, uint32_t rays) {
+  if (ensure_device(r) != HALA_OK) return HALA_ERR;
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  if (rays == 0 || rays > HALA_MAX_OCCLUSION_RAYS) RT_FAIL("The occlusion ray count must be 1.." + std::to_string(HALA_MAX_OCCLUSION_RAYS) + ".");
+  if (count == 0) return HALA_OK;
+  if (!samples || !out) RT_FAIL("The occlusion batch is null!");
+  if ((uint64_t)count * rays >= (1ull << 32)) RT_FAIL("The occlusion batch is too large.");
+  return HALA_OK;
+}
+int hala_rt_occlusion(hala_rt_renderer* r, const hala_occlusion_sample* d_samples, hala_occlusion* d_out, uint32_t* d_masks, uint32_t count, uint32_t rays,
+                      uint32_t seed, void* hip_stream) {
+  if (occlusion_check(r, d_samples, d_out, count, rays) != HALA_OK) return HALA_ERR;
+  if (count == 0) return HALA_OK;
+  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : r->stream;
+  const size_t mask_words = (size_t)count * ((rays + 31u) / 32u);
+  if (!d_masks) {
+    if (r->d_occlusion_masks.count < mask_words) RT_HIP(r->d_occlusion_masks.resize(mask_words));
+    d_masks = r->d_occlusion_masks.ptr;
+  }
+  if (r->scratch.acquire(s) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
+  RT_HIP(hipMemsetAsync(d_masks, 0, mask_words * 4, s));
+  launch_trace_occlusion(r->lcfg, r->view(), d_samples, d_out, d_masks, count, rays, seed, r->d_batch_work.ptr, s);
+  if (!r->scratch.batch_done) RT_HIP(hipEventCreateWithFlags(&r->scratch.batch_done, hipEventDisableTiming));
+  RT_HIP(hipEventRecord(r->scratch.batch_done, s));
+  r->scratch.event = r->scratch.batch_done; r->scratch.stream = s;
+  RT_HIP(hipGetLastError());
+  return HALA_OK;
+}
+int hala_rt_occlusion_host(hala_rt_renderer* r, const hala_occlusion_sample* samples, hala_occlusion* out, uint32_t* masks, uint32_t count, uint32_t rays,
+                           uint32_t seed) {
+  if (occlusion_check(r, samples, out, count, rays) != HALA_OK) return HALA_ERR;
+  if (count == 0) return HALA_OK;
+  const size_t mask_words = (size_t)count * ((rays + 31u) / 32u);
+  DeviceArray<hala_occlusion_sample> d_samples;
+  DeviceArray<hala_occlusion> d_out;
+  DeviceArray<uint32_t> d_masks;
+  RT_HIP(d_samples.upload(samples, count, r->stream));
+  RT_HIP(d_out.resize(count));
+  if (masks) RT_HIP(d_masks.resize(mask_words));
+  if (hala_rt_occlusion(r, d_samples.ptr, d_out.ptr, masks ? d_masks.ptr : nullptr, count, rays, seed, r->stream) != HALA_OK) return HALA_ERR;
+  RT_HIP(hipMemcpyAsync(out, d_out.ptr, (size_t)count * sizeof(hala_occlusion), hipMemcpyDeviceToHost, r->stream));
+  if (masks) RT_HIP(hipMemcpyAsync(masks, d_masks.ptr, mask_words * 4, hipMemcpyDeviceToHost, r->stream));
+  RT_HIP(hipStreamSynchronize(r->stream));
+  return HALA_OK;
+}
 int hala_rt_trace_rays_indirect(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_hits, const uint32_t* d_indirect, int mode, void* hip_stream) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (!d_indirect) RT_FAIL("The indirect command address is null!");

@@ -598,6 +598,63 @@ class HalaRenderer:
                                                          C.c_void_p(prim.ctypes.data) if want_prim else None))
         return (distance, prim) if want_prim else distance
 
+    def ray_eps(self) -> np.float32:
+        """RENDER_SPEC 3: sqrt(dot(ext, ext)) * 1e-5 of the committed scene's box, in float32"""
+        i = self.bvh_info()
+        ext = np.array(i.scene_max[:], dtype=np.float32) - np.array(i.scene_min[:], dtype=np.float32)
+        sq = np.float32(ext[0] * ext[0])
+        for a in (1, 2):  # dot(): fma(z, z, fma(y, y, x * x)), each fma rounded once
+            sq = np.float32(np.float64(ext[a]) * np.float64(ext[a]) + np.float64(sq))
+        return np.float32(np.sqrt(sq) * np.float32(1e-5))
+
+    def occlusion(self, points, normals=None, rays=64, reach=np.inf, bias=None, seed=0, want_masks=False, out=None, out_masks=None, count=None,
+                  stream: int = 0):
+        """RENDER_SPEC 4.10: ambient occlusion and the bent normal at surface points.  `rays` cosine-distributed any-hit rays of length
+        `reach` leave each point's hemisphere around its normal; the answer is a structured array of A.OCCLUSION_DTYPE: `visibility`, the
+        share of rays nothing blocks, and `bent`, the unit mean direction of those rays (0 when all are blocked).  A sample with a
+        zero or non-finite normal, point or bias answers visibility -1.  `points` and `normals` are [n, 3] arrays (`reach` and `bias`
+        scalars or one per point), or `points` is an array of A.OCCLUSION_SAMPLE_DTYPE and the rest is not used.  want_masks=True returns
+        (records, masks): masks[i, j >> 5] bit j & 31 is set iff ray j of sample i is occluded.
+        bias: how far along the normal the rays start; None is the scene's ray_eps (1e-5 of the scene box's diagonal).  With a bias of 0
+        the origin lies in the plane of the triangle it was taken from, and of its neighbours: whether their hit distance rounds to
+        t > 0 or not is then decided by the last bit of the arithmetic, so a surface occludes itself in a random pattern.
+        Device form: `points` is a device tensor of 32-B samples (or a device pointer, with `count`), `out` a device tensor (or pointer)
+        of 16-B records and `out_masks` one of count * ceil(rays / 32) words or None (the renderer then keeps the masks to itself);
+        the batch is launched on `stream` and nothing is returned."""
+        words = (int(rays) + 31) // 32
+        if out is not None or isinstance(points, int) or hasattr(points, "data_ptr"):
+            if out is None:
+                raise ValueError("the device form needs `out`")
+            d_s, d_o, d_m = (x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0) for x in (points, out, out_masks))
+            if count is None:
+                if not hasattr(points, "data_ptr"):
+                    raise ValueError("a device pointer needs `count`")
+                count = points.numel() * points.element_size() // A.OCCLUSION_SAMPLE_DTYPE.itemsize
+            if hasattr(out, "data_ptr") and out.numel() * out.element_size() < count * A.OCCLUSION_DTYPE.itemsize:
+                raise ValueError("`out` is too small for the batch")
+            if hasattr(out_masks, "data_ptr") and out_masks.numel() * out_masks.element_size() < count * words * 4:
+                raise ValueError("`out_masks` is too small for the batch")
+            self._check(self._lib.hala_rt_occlusion(self._h, C.c_void_p(d_s), C.c_void_p(d_o), C.c_void_p(d_m), C.c_uint32(count), C.c_uint32(rays),
+                                                    C.c_uint32(seed), C.c_void_p(stream)))
+            return None
+        pts = np.asarray(points)
+        if pts.dtype == A.OCCLUSION_SAMPLE_DTYPE:
+            q = np.ascontiguousarray(pts).reshape(-1)
+        else:
+            pts = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+            n = pts.shape[0]
+            q = np.empty(n, dtype=A.OCCLUSION_SAMPLE_DTYPE)
+            q["point"] = pts
+            q["normal"] = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+            q["bias"] = np.broadcast_to(np.asarray(self.ray_eps() if bias is None else bias, dtype=np.float32), (n,))
+            q["reach"] = np.broadcast_to(np.asarray(reach, dtype=np.float32), (n,))
+        res = np.empty(q.shape[0], dtype=A.OCCLUSION_DTYPE)
+        masks = np.zeros((q.shape[0], max(words, 0)), dtype=np.uint32) if want_masks else None
+        self._check(self._lib.hala_rt_occlusion_host(self._h, C.c_void_p(q.ctypes.data), C.c_void_p(res.ctypes.data),
+                                                     C.c_void_p(masks.ctypes.data) if want_masks else None, C.c_uint32(q.shape[0]), C.c_uint32(rays),
+                                                     C.c_uint32(seed)))
+        return (res, masks) if want_masks else res
+
     def bvh_info(self) -> A.BvhInfo:
         i = A.BvhInfo()
         self._check(self._lib.hala_rt_get_bvh_info(self._h, C.byref(i)))

@@ -950,6 +950,32 @@ int hala_rt_distance_grid_host(hala_rt_renderer* r, const hala_distance_grid_des
 int hala_rt_distance_grid_counted(hala_rt_renderer* r, const hala_distance_grid_desc* desc, float* d_distance, uint32_t* d_prim /* or NULL */,
                                   uint64_t* d_counters, void* hip_stream);
 
+/* Occlusion batches (RENDER_SPEC 4.10): ambient occlusion and the bent normal at surface points.  Sample i is a point with a normal
+ * (any length: it is normalised), a `bias` along that normal to the common origin o = fma(n, bias, point) of its rays, and a `reach`.
+ * `rays` = N directions (1 <= N <= HALA_MAX_OCCLUSION_RAYS) are drawn cosine-distributed over the normal's hemisphere from the stream
+ * (i, seed) of RENDER_SPEC 2.3, in the lanes that trace them: no ray is uploaded, copied or read back.  Ray j of sample i is the mode-1
+ * (any-hit) ray (o, 0, d_j, reach) of hala_rt_trace_rays, entry i * N + j of a batch, and its occlusion bit is what that call answers
+ * for it, ray for ray, on every tree form and builder: `reach` means what tmax means there (FLT_MAX or +inf: no limit; NaN or <= 0:
+ * nothing occludes), far origins are re-based, invisible materials never block and translucent ones block by the ray's key; media play
+ * no part.  d_out[i] = {visibility = unoccluded / N, bent = the normalised sum of the unoccluded directions in ascending j, or 0}.
+ * d_masks (device, count * ceil(N / 32) words, or NULL: the renderer keeps them in a buffer of its own): bit j & 31 of word
+ * i * ceil(N / 32) + (j >> 5) is set iff ray j is occluded, bits >= N are 0.  A sample whose normal has a squared length that is not
+ * positive and finite, or whose point or bias is not finite, traces nothing: its record is {-1, 0, 0, 0} and its words are 0.
+ * A bias of 0 puts the origin into the surface's own triangles, where rounding decides whether t > 0: the surface occludes itself at
+ * random; use the scene's ray_eps (1e-5 of the scene box's diagonal, RENDER_SPEC 3) or more.
+ * Everything else is the contract of hala_rt_trace_rays: a committed scene, count == 0 a no-op, the renderer's scratch and its stream
+ * order, the scene as it stands at the renderer's shutter step, after the last refit.  Refused with a message and without touching
+ * anything: rays outside 1..256, a null sample or output pointer, no committed scene, count * rays >= 2^32.
+ * Not built: stratified or low-discrepancy directions, uniform-hemisphere weighting, a per-ray distance falloff, an AO image of the
+ * frame from the first-hit AOVs, baking into a primitive's vertices or texture in one call. */
+#define HALA_MAX_OCCLUSION_RAYS 256
+typedef struct hala_occlusion_sample { float point[3]; float bias; float normal[3]; float reach; } hala_occlusion_sample; /* 32 B */
+typedef struct hala_occlusion { float visibility; /* < 0: invalid sample */ float bent[3]; } hala_occlusion;               /* 16 B */
+int hala_rt_occlusion(hala_rt_renderer* r, const hala_occlusion_sample* d_samples, hala_occlusion* d_out,
+                      uint32_t* d_masks /* count * ceil(rays/32) words, or NULL */, uint32_t count, uint32_t rays, uint32_t seed, void* hip_stream);
+int hala_rt_occlusion_host(hala_rt_renderer* r, const hala_occlusion_sample* samples, hala_occlusion* out, uint32_t* masks /* or NULL */,
+                           uint32_t count, uint32_t rays, uint32_t seed);
+
 /* BVH introspection for the oracle cross-check: 64-B nodes + 48-B triangles as laid out in HBM.
  * node_width is 4: compressed 4-wide nodes (docs/RENDER_SPEC.md §4.1b). */
 typedef struct hala_bvh_info {

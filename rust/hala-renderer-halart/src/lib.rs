@@ -67,6 +67,9 @@ pub mod sys {
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_closest_point { pub distance: f32, pub u: f32, pub v: f32, pub prim: u32, pub point: [f32; 3], pub region: u32 }
   /// hala_distance_grid_desc (36 B): signed distance grids (include/halart.h, docs/RENDER_SPEC.md 4.9); flags: bit 0 signed, bits 1-2 method
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_distance_grid_desc { pub origin: [f32; 3], pub spacing: f32, pub dims: [u32; 3], pub band: f32, pub flags: u32 }
+  /// hala_occlusion_sample (32 B) / hala_occlusion (16 B): occlusion batches (include/halart.h, docs/RENDER_SPEC.md 4.10)
+  #[repr(C)] #[derive(Clone, Copy)] pub struct hala_occlusion_sample { pub point: [f32; 3], pub bias: f32, pub normal: [f32; 3], pub reach: f32 }
+  #[repr(C)] #[derive(Clone, Copy)] pub struct hala_occlusion { pub visibility: f32, pub bent: [f32; 3] }
   #[repr(C)] #[derive(Default)] pub struct hala_rt_info { pub width: u32, pub height: u32 }
 
   /// hala_rt_build_options (include/halart.h): every field 0 = the default
@@ -98,6 +101,8 @@ pub mod sys {
   pub const HALA_DEFORM_NORMALS_RECOMPUTED: u32 = 1;
   /// the largest capacity of a multi-hit batch (RENDER_SPEC 4.7)
   pub const HALA_MAX_MULTI_HITS: u32 = 16;
+  /// the largest number of rays per sample of an occlusion batch (RENDER_SPEC 4.10)
+  pub const HALA_MAX_OCCLUSION_RAYS: u32 = 256;
   #[repr(C)] pub struct hala_scene { _private: [u8; 0] }
   #[repr(C)] pub struct hala_rtprog { _private: [u8; 0] }
   extern "C" {
@@ -140,6 +145,10 @@ pub mod sys {
     pub fn hala_rt_distance_grid_host(r: *mut hala_rt_renderer, desc: *const hala_distance_grid_desc, distance: *mut f32, prim: *mut u32) -> c_int;
     pub fn hala_rt_distance_grid_counted(r: *mut hala_rt_renderer, desc: *const hala_distance_grid_desc, d_distance: *mut f32, d_prim: *mut u32,
                                          d_counters: *mut u64, hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_occlusion(r: *mut hala_rt_renderer, d_samples: *const hala_occlusion_sample, d_out: *mut hala_occlusion, d_masks: *mut u32, count: u32,
+                             rays: u32, seed: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_occlusion_host(r: *mut hala_rt_renderer, samples: *const hala_occlusion_sample, out: *mut hala_occlusion, masks: *mut u32, count: u32,
+                                  rays: u32, seed: u32) -> c_int;
     pub fn hala_rt_update_node_transform(r: *mut hala_rt_renderer, node_index: u32, local_transform: *const f32) -> c_int;
     pub fn hala_rt_update_material(r: *mut hala_rt_renderer, material_index: u32, material: *const hala_material_desc) -> c_int;
     pub fn hala_rt_update_vertices(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, vertices: *const hala_vertex, vertex_count: u32) -> c_int;
@@ -361,6 +370,18 @@ impl HalaRenderer {
   }
   pub fn closest_points_device(&self, d_queries: *const sys::hala_point_query, d_out: *mut sys::hala_closest_point, count: u32) -> Result<(), HalaRendererError> {
     check(unsafe { sys::hala_rt_closest_points(self.h, d_queries, d_out, count, std::ptr::null_mut()) })
+  }
+  /// occlusion batches (RENDER_SPEC 4.10) from host memory: `rays` (1..=256) any-hit rays over each sample's hemisphere; visibility < 0 marks
+  /// an invalid sample
+  pub fn occlusion(&self, samples: &[sys::hala_occlusion_sample], rays: u32, seed: u32) -> Result<Vec<sys::hala_occlusion>, HalaRendererError> {
+    let mut out = vec![sys::hala_occlusion { visibility: -1.0, bent: [0.0; 3] }; samples.len()];
+    check(unsafe { sys::hala_rt_occlusion_host(self.h, samples.as_ptr(), out.as_mut_ptr(), std::ptr::null_mut(), samples.len() as u32, rays, seed) })?;
+    Ok(out)
+  }
+  /// the device-pointer form, on the renderer's stream; d_masks (count * ceil(rays / 32) words) may be null
+  pub fn occlusion_device(&self, d_samples: *const sys::hala_occlusion_sample, d_out: *mut sys::hala_occlusion, d_masks: *mut u32, count: u32, rays: u32,
+                          seed: u32) -> Result<(), HalaRendererError> {
+    check(unsafe { sys::hala_rt_occlusion(self.h, d_samples, d_out, d_masks, count, rays, seed, std::ptr::null_mut()) })
   }
   /// binds an ordered node set (empty: unbinds); refit_nodes then takes one local transform per bound node, in that order
   pub fn bind_nodes(&mut self, node_indices: &[u32]) -> Result<(), HalaRendererError> {
