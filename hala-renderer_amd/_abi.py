@@ -157,6 +157,15 @@ class Occlusion(C.Structure):  # hala_occlusion, 16 B
     _fields_ = [("visibility", C.c_float), ("bent", C.c_float * 3)]
 
 
+class BakeDesc(C.Structure):  # hala_bake_desc, 28 B (RENDER_SPEC 4.11)
+    _fields_ = [("instance", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("bias", C.c_float), ("reach", C.c_float),
+                ("margin", C.c_uint32)]
+
+
+class BakeTexel(C.Structure):  # hala_bake_texel, 16 B
+    _fields_ = [("u", C.c_float), ("v", C.c_float), ("prim", C.c_uint32), ("source", C.c_uint32)]
+
+
 class RtInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -342,6 +351,11 @@ PROTOTYPES = {
     # renderer, samples, out, masks | count, rays, seed (, stream)
     "hala_rt_occlusion": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p], C.c_int),
     "hala_rt_occlusion_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32], C.c_int),
+    # renderer, desc, samples | out, texels (, stream); the occlusion forms take rays, seed behind desc
+    "hala_rt_bake_samples": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hala_rt_bake_samples_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hala_rt_bake_occlusion": ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hala_rt_bake_occlusion_host": ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "hala_rtprog_trace_rays_multi": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
     "hala_rt_denoise": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
@@ -438,6 +452,8 @@ CLOSEST_POINT_DTYPE = _np.dtype([("distance", "<f4"), ("u", "<f4"), ("v", "<f4")
 # RENDER_SPEC 4.10: hala_occlusion_sample (32 B), hala_occlusion (16 B)
 OCCLUSION_SAMPLE_DTYPE = _np.dtype([("point", "<f4", 3), ("bias", "<f4"), ("normal", "<f4", 3), ("reach", "<f4")])
 OCCLUSION_DTYPE = _np.dtype([("visibility", "<f4"), ("bent", "<f4", 3)])
+# RENDER_SPEC 4.11: hala_bake_texel (16 B)
+BAKE_TEXEL_DTYPE = _np.dtype([("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("source", "<u4")])
 VERTEX_DTYPE = _np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("tex_coord", "<f4", 2)])
 
 # every symbol include/halart.h declares (tests/test_abi.py checks the .so exports all of them)
@@ -488,7 +504,9 @@ EXPORTS = [
     "hala_rt_closest_points", "hala_rt_closest_points_host", "hala_rt_closest_points_counted",
     "hala_rt_distance_grid", "hala_rt_distance_grid_host", "hala_rt_distance_grid_counted",
     "hala_rt_occlusion", "hala_rt_occlusion_host",
+    "hala_rt_bake_samples", "hala_rt_bake_samples_host", "hala_rt_bake_occlusion", "hala_rt_bake_occlusion_host",
 ]
 MAX_MULTI_HITS = 16  # HALA_MAX_MULTI_HITS (RENDER_SPEC 4.7)
 MAX_OCCLUSION_RAYS = 256  # HALA_MAX_OCCLUSION_RAYS (RENDER_SPEC 4.10)
+MAX_BAKE_DIM, MAX_BAKE_MARGIN, BAKE_SHADING_NORMAL, BAKE_FLIP_NORMAL = 4096, 16, 1, 2  # HALA_MAX_BAKE_*, HALA_BAKE_* (RENDER_SPEC 4.11)
 GRID_SIGNED, GRID_METHOD_SHIFT, MAX_GRID_DIM = 1, 1, 1024  # HALA_GRID_* (RENDER_SPEC 4.9)

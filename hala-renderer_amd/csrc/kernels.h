@@ -69,6 +69,29 @@ bool launch_distance_grid(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_
 // every tree form; then one lane per sample reduces the masks.
 void launch_trace_occlusion(const LaunchCfg& lc, const SceneView& sv, const hala_occlusion_sample* samples, hala_occlusion* out, uint32_t* masks,
                             uint32_t count, uint32_t rays, uint32_t seed, WorkCounters* work, hipStream_t s);
+// bake.hip — RENDER_SPEC 4.11: the W x H bake map of one instance of a one-level scene.  launch_bake_samples clears the owner map, folds
+// the instance's triangles in (count, prefix sum, one (triangle, 8 x 8 block) pair per wave step) and writes sample y * W + x (and its
+// texel record, or null); launch_bake_dilate then fills the ownerless texels of `out` (the records of those samples) from the owner map
+// the first call left in `sc`.  The scratch is the caller's: owner bake_owner_words() words (block_bits a 64th of that), counts and offsets tri_count + 1 entries
+// each, scan_tmp bake_scan_bytes(tri_count) bytes.  Nothing is synchronised.
+struct BakeView {
+  uint32_t width, height, blocks_x, blocks_y;  // (blocks: filled in by the launchers)
+  uint32_t first_tri, tri_count;               // the instance's range of global ids
+  uint32_t flags, margin;
+  float bias, reach;
+};
+struct BakeScratch {
+  uint32_t* owner;
+  unsigned long long *counts, *offsets;
+  unsigned long long* block_bits;  // one word per 8 x 8 block of the owner map (the dilation's)
+  void* scan_tmp;
+  size_t scan_bytes;
+};
+size_t bake_owner_words(const BakeView& bv);
+size_t bake_scan_bytes(uint32_t tri_count);
+hipError_t launch_bake_samples(const SceneView& sv, uint32_t cu_count, const BakeView& bv, const BakeScratch& sc, hala_occlusion_sample* samples,
+                               hala_bake_texel* texels, hipStream_t s);
+void launch_bake_dilate(const BakeView& bv, const BakeScratch& sc, hala_occlusion* out, hala_bake_texel* texels, hipStream_t s);
 // shade.hip
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s);
 // resolve.hip

@@ -501,6 +501,12 @@ struct hala_rt_renderer {
   DeviceArray<uint32_t> d_grid_bits;
   // hala_rt_occlusion, RENDER_SPEC 4.10: the mask words of a batch whose caller wants none (grown on demand)
   DeviceArray<uint32_t> d_occlusion_masks;
+  // hala_rt_bake_samples / hala_rt_bake_occlusion, RENDER_SPEC 4.11 (grown on demand): the owner map (tiled 8 x 8) and its blocks' ownership
+  // words, the per-triangle block counts with their prefix sum and its scratch, and the sample buffer of a baked occlusion map
+  DeviceArray<uint32_t> d_bake_owner;
+  DeviceArray<unsigned long long> d_bake_counts, d_bake_offsets, d_bake_block_bits;
+  DeviceArray<uint8_t> d_bake_scan;
+  DeviceArray<hala_occlusion_sample> d_bake_samples;
 
   uint64_t total_frames = 0;
   bool counting = false;

@@ -655,6 +655,62 @@ class HalaRenderer:
                                                      C.c_uint32(seed)))
         return (res, masks) if want_masks else res
 
+    def _bake_desc(self, instance, width, height, shading_normal, flip, bias, reach, margin):
+        flags = (A.BAKE_SHADING_NORMAL if shading_normal else 0) | (A.BAKE_FLIP_NORMAL if flip else 0)
+        return A.BakeDesc(int(instance), int(width), int(height), flags, float(self.ray_eps() if bias is None else bias), float(reach), int(margin))
+
+    @staticmethod
+    def _bake_device_out(x, count, itemsize, name):
+        """the device address of an output tensor (or pointer), checked against the map's size"""
+        if hasattr(x, "data_ptr"):
+            if x.numel() * x.element_size() < count * itemsize:
+                raise ValueError(f"`{name}` is too small for the map")
+            return x.data_ptr()
+        return int(x or 0)
+
+    def bake_samples(self, instance, width, height, *, shading_normal=False, flip=False, bias=None, reach=np.inf, out=None, out_texels=None,
+                     stream: int = 0):
+        """RENDER_SPEC 4.11: instance `instance` (instance order) rasterised into a width x height map of its texture space.  Returns
+        (samples, texels), both shaped (height, width): A.OCCLUSION_SAMPLE_DTYPE, the surface point and normal under each texel centre
+        (all zero where no triangle covers it), and A.BAKE_TEXEL_DTYPE, the barycentrics and the triangle found there (prim 0xffffffff:
+        none).  The normal is cross(e1, e2) of the triangle, or with shading_normal=True the interpolated vertex normal in world space;
+        flip=True negates it.  bias=None is the scene's ray_eps.  Row 0 is the row of the smallest v.
+        Device form: `out` is a device tensor (or pointer) of width * height 32-B samples and `out_texels` one of 16-B records or None;
+        the map is launched on `stream` and nothing is returned."""
+        d = self._bake_desc(instance, width, height, shading_normal, flip, bias, reach, 0)
+        count = int(width) * int(height)
+        if out is not None:
+            d_s = self._bake_device_out(out, count, A.OCCLUSION_SAMPLE_DTYPE.itemsize, "out")
+            d_t = self._bake_device_out(out_texels, count, A.BAKE_TEXEL_DTYPE.itemsize, "out_texels")
+            self._check(self._lib.hala_rt_bake_samples(self._h, C.byref(d), C.c_void_p(d_s), C.c_void_p(d_t), C.c_void_p(stream)))
+            return None
+        samples = np.empty(max(count, 0), dtype=A.OCCLUSION_SAMPLE_DTYPE)
+        texels = np.empty(max(count, 0), dtype=A.BAKE_TEXEL_DTYPE)
+        self._check(self._lib.hala_rt_bake_samples_host(self._h, C.byref(d), C.c_void_p(samples.ctypes.data), C.c_void_p(texels.ctypes.data)))
+        return samples.reshape(int(height), int(width)), texels.reshape(int(height), int(width))
+
+    def bake_occlusion(self, instance, width, height, rays, seed=0, *, margin=0, shading_normal=False, flip=False, bias=None, reach=np.inf, out=None,
+                       out_texels=None, stream: int = 0):
+        """RENDER_SPEC 4.11: the ambient-occlusion map of instance `instance`: what occlusion() answers, with `rays` and `seed`, for the
+        samples of bake_samples(), texel i being sample i; then every texel without a sample takes the record of the nearest texel with
+        one within `margin` texels (0..16) in x and in y.  Returns (records, texels), both shaped (height, width): A.OCCLUSION_DTYPE
+        (visibility -1 where nothing was baked or copied) and A.BAKE_TEXEL_DTYPE, whose `source` names the texel a record came from.
+        Device form: `out` is a device tensor (or pointer) of width * height 16-B records and `out_texels` one of 16-B texel records or
+        None; the bake is launched on `stream`, nothing leaves the device and nothing is returned."""
+        d = self._bake_desc(instance, width, height, shading_normal, flip, bias, reach, margin)
+        count = int(width) * int(height)
+        if out is not None:
+            d_o = self._bake_device_out(out, count, A.OCCLUSION_DTYPE.itemsize, "out")
+            d_t = self._bake_device_out(out_texels, count, A.BAKE_TEXEL_DTYPE.itemsize, "out_texels")
+            self._check(self._lib.hala_rt_bake_occlusion(self._h, C.byref(d), C.c_uint32(rays), C.c_uint32(seed), C.c_void_p(d_o), C.c_void_p(d_t),
+                                                         C.c_void_p(stream)))
+            return None
+        rec = np.empty(max(count, 0), dtype=A.OCCLUSION_DTYPE)
+        texels = np.empty(max(count, 0), dtype=A.BAKE_TEXEL_DTYPE)
+        self._check(self._lib.hala_rt_bake_occlusion_host(self._h, C.byref(d), C.c_uint32(rays), C.c_uint32(seed), C.c_void_p(rec.ctypes.data),
+                                                          C.c_void_p(texels.ctypes.data)))
+        return rec.reshape(int(height), int(width)), texels.reshape(int(height), int(width))
+
     def bvh_info(self) -> A.BvhInfo:
         i = A.BvhInfo()
         self._check(self._lib.hala_rt_get_bvh_info(self._h, C.byref(i)))

@@ -967,7 +967,7 @@ int hala_rt_distance_grid_counted(hala_rt_renderer* r, const hala_distance_grid_
  * order, the scene as it stands at the renderer's shutter step, after the last refit.  Refused with a message and without touching
  * anything: rays outside 1..256, a null sample or output pointer, no committed scene, count * rays >= 2^32.
  * Not built: stratified or low-discrepancy directions, uniform-hemisphere weighting, a per-ray distance falloff, an AO image of the
- * frame from the first-hit AOVs, baking into a primitive's vertices or texture in one call. */
+ * frame from the first-hit AOVs, baking into a primitive's vertices in one call (into its texture: hala_rt_bake_occlusion below). */
 #define HALA_MAX_OCCLUSION_RAYS 256
 typedef struct hala_occlusion_sample { float point[3]; float bias; float normal[3]; float reach; } hala_occlusion_sample; /* 32 B */
 typedef struct hala_occlusion { float visibility; /* < 0: invalid sample */ float bent[3]; } hala_occlusion;               /* 16 B */
@@ -975,6 +975,51 @@ int hala_rt_occlusion(hala_rt_renderer* r, const hala_occlusion_sample* d_sample
                       uint32_t* d_masks /* count * ceil(rays/32) words, or NULL */, uint32_t count, uint32_t rays, uint32_t seed, void* hip_stream);
 int hala_rt_occlusion_host(hala_rt_renderer* r, const hala_occlusion_sample* samples, hala_occlusion* out, uint32_t* masks /* or NULL */,
                            uint32_t count, uint32_t rays, uint32_t seed);
+
+/* Bake maps (RENDER_SPEC 4.11): occlusion baked into the texture space of one instance, without leaving the device.  The instance's
+ * triangles are rasterised into a `width` x `height` map by their texture coordinates (texel (x, y) has index y * width + x, row 0 is the
+ * row of the smallest v, as the texture sampler reads it; no wrap: what lies outside [0, 1] falls off the map).  A texel whose centre a
+ * triangle covers (edges included; of several, the lowest global triangle id) becomes the hala_occlusion_sample at the surface point
+ * and normal found there: `normal` is cross(e1, e2) of the triangle (not normalised), or with HALA_BAKE_SHADING_NORMAL the interpolated
+ * vertex normal moved to world space as the shade path does it; HALA_BAKE_FLIP_NORMAL negates either; `bias` and `reach` are copied
+ * into every sample.  A texel nothing covers gets the all-zero sample, which is invalid and traces nothing.  d_texels (or NULL)
+ * gets, per texel, the barycentrics and the triangle of its sample and `source`, the index of the texel its record came from.
+ * hala_rt_bake_samples writes the samples (and ignores `margin`); they are what any later texture-space operator starts from.
+ * hala_rt_bake_occlusion writes what hala_rt_occlusion answers for exactly that sample buffer with (rays, seed) — sample i is texel i —
+ * and then fills the gutters: a texel without a sample takes the record of the nearest texel with one (least squared distance, then
+ * least index) among those within `margin` texels in x and in y, and names it in `source`; with none, its record stays the invalid one
+ * {-1, 0, 0, 0} and `source` 0xffffffff.  Samples, ownership and masks live in buffers the renderer owns, which grow on demand.
+ * Everything else is the contract of hala_rt_trace_rays: the renderer's scratch and its stream order, no host synchronisation in the
+ * device forms — except where one of the renderer's buffers has to grow (the first call, and the first at a larger map, ray count or
+ * instance): freeing the smaller buffer waits for the device, as it does in hala_rt_occlusion without a mask array —, the scene as it
+ * stands after the last refit.
+ * Cost limit: a UV triangle so thin that rounding decides its coverage anywhere along its lines (|area| within 2^-17 of its box's
+ * larger side squared, in texel units; exactly degenerate ones cover nothing and cost nothing) is tested against every 8 x 8 block of
+ * the map, about 40 us each at 4096 x 4096 on an MI355X, all in one kernel launch that nothing cuts short: weld or drop such triangles
+ * before baking a mesh that has thousands of them.  Refused with a message and without touching anything: a null description
+ * or output, no committed scene, a two-level tree (the records of instanced primitives are in object space: commit with instancing =
+ * 0), `instance` out of range, a dimension of 0 or above HALA_MAX_BAKE_DIM, `margin` above HALA_MAX_BAKE_MARGIN, an unknown flag bit,
+ * a non-finite bias, rays outside 1..256, width * height * rays >= 2^32.
+ * Not built: compaction of empty texels, vertex baking, supersampled or conservative coverage, UV wrap, a second UV set, two-level trees. */
+#define HALA_MAX_BAKE_DIM 4096
+#define HALA_MAX_BAKE_MARGIN 16
+#define HALA_BAKE_SHADING_NORMAL 1u
+#define HALA_BAKE_FLIP_NORMAL 2u
+typedef struct hala_bake_desc {
+  uint32_t instance;      /* index in instance order (RENDER_SPEC 3) */
+  uint32_t width, height; /* 1 .. HALA_MAX_BAKE_DIM */
+  uint32_t flags;         /* HALA_BAKE_* */
+  float bias, reach;      /* of every sample (RENDER_SPEC 4.10) */
+  uint32_t margin;        /* dilation reach in texels, 0 .. HALA_MAX_BAKE_MARGIN */
+} hala_bake_desc;         /* 28 B */
+typedef struct hala_bake_texel { float u, v; uint32_t prim; uint32_t source; } hala_bake_texel; /* 16 B; no sample: {0, 0, ~0, ~0} */
+int hala_rt_bake_samples(hala_rt_renderer* r, const hala_bake_desc* desc, hala_occlusion_sample* d_samples /* width * height */,
+                         hala_bake_texel* d_texels /* width * height, or NULL */, void* hip_stream);
+int hala_rt_bake_samples_host(hala_rt_renderer* r, const hala_bake_desc* desc, hala_occlusion_sample* samples, hala_bake_texel* texels /* or NULL */);
+int hala_rt_bake_occlusion(hala_rt_renderer* r, const hala_bake_desc* desc, uint32_t rays, uint32_t seed, hala_occlusion* d_out /* width * height */,
+                           hala_bake_texel* d_texels /* or NULL */, void* hip_stream);
+int hala_rt_bake_occlusion_host(hala_rt_renderer* r, const hala_bake_desc* desc, uint32_t rays, uint32_t seed, hala_occlusion* out,
+                                hala_bake_texel* texels /* or NULL */);
 
 /* BVH introspection for the oracle cross-check: 64-B nodes + 48-B triangles as laid out in HBM.
  * node_width is 4: compressed 4-wide nodes (docs/RENDER_SPEC.md §4.1b). */

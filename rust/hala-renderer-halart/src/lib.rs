@@ -70,6 +70,9 @@ pub mod sys {
   /// hala_occlusion_sample (32 B) / hala_occlusion (16 B): occlusion batches (include/halart.h, docs/RENDER_SPEC.md 4.10)
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_occlusion_sample { pub point: [f32; 3], pub bias: f32, pub normal: [f32; 3], pub reach: f32 }
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_occlusion { pub visibility: f32, pub bent: [f32; 3] }
+  /// hala_bake_desc (28 B) / hala_bake_texel (16 B): bake maps (include/halart.h, docs/RENDER_SPEC.md 4.11); flags: HALA_BAKE_*
+  #[repr(C)] #[derive(Clone, Copy)] pub struct hala_bake_desc { pub instance: u32, pub width: u32, pub height: u32, pub flags: u32, pub bias: f32, pub reach: f32, pub margin: u32 }
+  #[repr(C)] #[derive(Clone, Copy)] pub struct hala_bake_texel { pub u: f32, pub v: f32, pub prim: u32, pub source: u32 }
   #[repr(C)] #[derive(Default)] pub struct hala_rt_info { pub width: u32, pub height: u32 }
 
   /// hala_rt_build_options (include/halart.h): every field 0 = the default
@@ -103,6 +106,11 @@ pub mod sys {
   pub const HALA_MAX_MULTI_HITS: u32 = 16;
   /// the largest number of rays per sample of an occlusion batch (RENDER_SPEC 4.10)
   pub const HALA_MAX_OCCLUSION_RAYS: u32 = 256;
+  /// the largest side of a bake map, the largest dilation margin and the flag bits of hala_bake_desc (RENDER_SPEC 4.11)
+  pub const HALA_MAX_BAKE_DIM: u32 = 4096;
+  pub const HALA_MAX_BAKE_MARGIN: u32 = 16;
+  pub const HALA_BAKE_SHADING_NORMAL: u32 = 1;
+  pub const HALA_BAKE_FLIP_NORMAL: u32 = 2;
   #[repr(C)] pub struct hala_scene { _private: [u8; 0] }
   #[repr(C)] pub struct hala_rtprog { _private: [u8; 0] }
   extern "C" {
@@ -149,6 +157,14 @@ pub mod sys {
                              rays: u32, seed: u32, hip_stream: *mut c_void) -> c_int;
     pub fn hala_rt_occlusion_host(r: *mut hala_rt_renderer, samples: *const hala_occlusion_sample, out: *mut hala_occlusion, masks: *mut u32, count: u32,
                                   rays: u32, seed: u32) -> c_int;
+    pub fn hala_rt_bake_samples(r: *mut hala_rt_renderer, desc: *const hala_bake_desc, d_samples: *mut hala_occlusion_sample, d_texels: *mut hala_bake_texel,
+                                hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_bake_samples_host(r: *mut hala_rt_renderer, desc: *const hala_bake_desc, samples: *mut hala_occlusion_sample,
+                                     texels: *mut hala_bake_texel) -> c_int;
+    pub fn hala_rt_bake_occlusion(r: *mut hala_rt_renderer, desc: *const hala_bake_desc, rays: u32, seed: u32, d_out: *mut hala_occlusion,
+                                  d_texels: *mut hala_bake_texel, hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_bake_occlusion_host(r: *mut hala_rt_renderer, desc: *const hala_bake_desc, rays: u32, seed: u32, out: *mut hala_occlusion,
+                                       texels: *mut hala_bake_texel) -> c_int;
     pub fn hala_rt_update_node_transform(r: *mut hala_rt_renderer, node_index: u32, local_transform: *const f32) -> c_int;
     pub fn hala_rt_update_material(r: *mut hala_rt_renderer, material_index: u32, material: *const hala_material_desc) -> c_int;
     pub fn hala_rt_update_vertices(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, vertices: *const hala_vertex, vertex_count: u32) -> c_int;
@@ -382,6 +398,32 @@ impl HalaRenderer {
   pub fn occlusion_device(&self, d_samples: *const sys::hala_occlusion_sample, d_out: *mut sys::hala_occlusion, d_masks: *mut u32, count: u32, rays: u32,
                           seed: u32) -> Result<(), HalaRendererError> {
     check(unsafe { sys::hala_rt_occlusion(self.h, d_samples, d_out, d_masks, count, rays, seed, std::ptr::null_mut()) })
+  }
+  /// bake maps (RENDER_SPEC 4.11) to host memory: the occlusion samples and texel records of the desc.width x desc.height map of an
+  /// instance's texture space, row-major from the row of the smallest v; a texel nothing covers has prim 0xffffffff and the all-zero sample
+  pub fn bake_samples(&self, desc: &sys::hala_bake_desc) -> Result<(Vec<sys::hala_occlusion_sample>, Vec<sys::hala_bake_texel>), HalaRendererError> {
+    let n = desc.width as usize * desc.height as usize;
+    let mut samples = vec![sys::hala_occlusion_sample { point: [0.0; 3], bias: 0.0, normal: [0.0; 3], reach: 0.0 }; n];
+    let mut texels = vec![sys::hala_bake_texel { u: 0.0, v: 0.0, prim: u32::MAX, source: u32::MAX }; n];
+    check(unsafe { sys::hala_rt_bake_samples_host(self.h, desc, samples.as_mut_ptr(), texels.as_mut_ptr()) })?;
+    Ok((samples, texels))
+  }
+  /// the baked occlusion map: `rays` (1..=256) any-hit rays per covered texel, then the gutters filled within desc.margin texels; visibility < 0
+  /// marks a texel that neither has a sample nor was filled, texels[i].source the texel a record came from
+  pub fn bake_occlusion(&self, desc: &sys::hala_bake_desc, rays: u32, seed: u32) -> Result<(Vec<sys::hala_occlusion>, Vec<sys::hala_bake_texel>), HalaRendererError> {
+    let n = desc.width as usize * desc.height as usize;
+    let mut out = vec![sys::hala_occlusion { visibility: -1.0, bent: [0.0; 3] }; n];
+    let mut texels = vec![sys::hala_bake_texel { u: 0.0, v: 0.0, prim: u32::MAX, source: u32::MAX }; n];
+    check(unsafe { sys::hala_rt_bake_occlusion_host(self.h, desc, rays, seed, out.as_mut_ptr(), texels.as_mut_ptr()) })?;
+    Ok((out, texels))
+  }
+  /// the device-pointer forms, on the renderer's stream; d_texels (width * height records) may be null
+  pub fn bake_samples_device(&self, desc: &sys::hala_bake_desc, d_samples: *mut sys::hala_occlusion_sample, d_texels: *mut sys::hala_bake_texel) -> Result<(), HalaRendererError> {
+    check(unsafe { sys::hala_rt_bake_samples(self.h, desc, d_samples, d_texels, std::ptr::null_mut()) })
+  }
+  pub fn bake_occlusion_device(&self, desc: &sys::hala_bake_desc, rays: u32, seed: u32, d_out: *mut sys::hala_occlusion, d_texels: *mut sys::hala_bake_texel)
+                               -> Result<(), HalaRendererError> {
+    check(unsafe { sys::hala_rt_bake_occlusion(self.h, desc, rays, seed, d_out, d_texels, std::ptr::null_mut()) })
   }
   /// binds an ordered node set (empty: unbinds); refit_nodes then takes one local transform per bound node, in that order
   pub fn bind_nodes(&mut self, node_indices: &[u32]) -> Result<(), HalaRendererError> {
