@@ -166,6 +166,14 @@ class BakeTexel(C.Structure):  # hala_bake_texel, 16 B
     _fields_ = [("u", C.c_float), ("v", C.c_float), ("prim", C.c_uint32), ("source", C.c_uint32)]
 
 
+class BakeChart(C.Structure):  # hala_bake_chart, 24 B (RENDER_SPEC 4.12)
+    _fields_ = [("instance", C.c_uint32), ("flags", C.c_uint32), ("scale", C.c_float * 2), ("offset", C.c_float * 2)]
+
+
+class BakeAtlasDesc(C.Structure):  # hala_bake_atlas_desc, 24 B
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("bias", C.c_float), ("reach", C.c_float), ("margin", C.c_uint32), ("chart_count", C.c_uint32)]
+
+
 class RtInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -356,6 +364,11 @@ PROTOTYPES = {
     "hala_rt_bake_samples_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "hala_rt_bake_occlusion": ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "hala_rt_bake_occlusion_host": ([C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
+    # the atlas forms (RENDER_SPEC 4.12): the chart table follows the description
+    "hala_rt_bake_atlas_samples": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hala_rt_bake_atlas_samples_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hala_rt_bake_atlas_occlusion": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hala_rt_bake_atlas_occlusion_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "hala_rtprog_trace_rays_multi": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
     "hala_rt_denoise": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
@@ -454,6 +467,8 @@ OCCLUSION_SAMPLE_DTYPE = _np.dtype([("point", "<f4", 3), ("bias", "<f4"), ("norm
 OCCLUSION_DTYPE = _np.dtype([("visibility", "<f4"), ("bent", "<f4", 3)])
 # RENDER_SPEC 4.11: hala_bake_texel (16 B)
 BAKE_TEXEL_DTYPE = _np.dtype([("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("source", "<u4")])
+# RENDER_SPEC 4.12: hala_bake_chart (24 B)
+BAKE_CHART_DTYPE = _np.dtype([("instance", "<u4"), ("flags", "<u4"), ("scale", "<f4", 2), ("offset", "<f4", 2)])
 VERTEX_DTYPE = _np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("tex_coord", "<f4", 2)])
 
 # every symbol include/halart.h declares (tests/test_abi.py checks the .so exports all of them)
@@ -505,6 +520,7 @@ EXPORTS = [
     "hala_rt_distance_grid", "hala_rt_distance_grid_host", "hala_rt_distance_grid_counted",
     "hala_rt_occlusion", "hala_rt_occlusion_host",
     "hala_rt_bake_samples", "hala_rt_bake_samples_host", "hala_rt_bake_occlusion", "hala_rt_bake_occlusion_host",
+    "hala_rt_bake_atlas_samples", "hala_rt_bake_atlas_samples_host", "hala_rt_bake_atlas_occlusion", "hala_rt_bake_atlas_occlusion_host",
 ]
 MAX_MULTI_HITS = 16  # HALA_MAX_MULTI_HITS (RENDER_SPEC 4.7)
 MAX_OCCLUSION_RAYS = 256  # HALA_MAX_OCCLUSION_RAYS (RENDER_SPEC 4.10)

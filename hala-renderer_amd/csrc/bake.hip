@@ -8,6 +8,9 @@
 //   k_bake_sample  one lane per texel: owner -> edge values again -> (u, v), point, normal -> the 32-B sample and the 16-B texel record
 //   k_bake_blocks  one wave per 8 x 8 block: its 64 ownership bits as one word (what the dilation rejects empty windows by)
 //   k_bake_dilate  one lane per texel: an ownerless texel takes the record of the nearest owned texel of its window
+// Bake atlases (RENDER_SPEC 4.12) put several instances into one map, each through a chart (scale, offset, flags): k_bake_atlas_count /
+// _cover / _sample are the first three kernels with the chart between the UVs and the corners, and k_bake_list_count / k_bake_list turn
+// the ownership words into the list of owned texels that the listed occlusion pass of occlusion.hip traces.
 // The owner map is tiled 8 x 8 (a block is 256 B: two lines, one atomic instruction per wave step); its layout is not observable.
 // The library is built with -ffp-contract=off: the only fused operations are the ones written as __fmaf_rn, here the three of `point`
 // and those inside dot3 / cross3 / transform_normal (shading.h, rt_math.h), which the spec names.
@@ -39,6 +42,25 @@ RT_DI BakeTri bake_tri(const SceneView& sv, const BakeView& bv, uint32_t gid) {
   const float w = (float)bv.width, h = (float)bv.height;
   BakeTri t;
   t.a = f2{s4.x * w, s4.y * h}; t.b = f2{s4.z * w, s4.w * h}; t.c = f2{s5.x * w, s5.y * h};
+  t.area = bake_edge(t.a, t.b, t.c);
+  return t;
+}
+// RENDER_SPEC 4.12: the corners through the chart of the triangle's instance (the shading record's s0.w), one fma and then one product per
+// component; an instance without a chart gets area 0, which covers nothing and counts no pairs.  *flags: the chart's.
+RT_DI BakeTri bake_tri_atlas(const SceneView& sv, const BakeView& bv, const BakeChartDev* __restrict__ charts, uint32_t gid) {
+  const float4* sp = reinterpret_cast<const float4*>(sv.shade_tris + gid);
+  const float4* cp = reinterpret_cast<const float4*>(charts + __float_as_uint(sp[0].w));
+  const float4 so = cp[0], fc = cp[1];  // (scale, offset), (-, charted, -, -)
+  BakeTri t;
+  if (__float_as_uint(fc.y) == 0u) {
+    t.a = t.b = t.c = f2{0.0f, 0.0f}; t.area = 0.0f;
+    return t;
+  }
+  const float4 s4 = sp[4], s5 = sp[5];
+  const float w = (float)bv.width, h = (float)bv.height;
+  t.a = f2{__fmaf_rn(s4.x, so.x, so.z) * w, __fmaf_rn(s4.y, so.y, so.w) * h};
+  t.b = f2{__fmaf_rn(s4.z, so.x, so.z) * w, __fmaf_rn(s4.w, so.y, so.w) * h};
+  t.c = f2{__fmaf_rn(s5.x, so.x, so.z) * w, __fmaf_rn(s5.y, so.y, so.w) * h};
   t.area = bake_edge(t.a, t.b, t.c);
   return t;
 }
@@ -180,12 +202,144 @@ __global__ void __launch_bounds__(256) k_bake_sample(SceneView sv, BakeView bv, 
   }
 }
 
+// RENDER_SPEC 4.12: the three kernels above with the corners of bake_tri_atlas, in the sample the flags of the owner's chart, and in the
+// coverage a walk that bisects across long runs of triangles without pairs; nothing else differs.  They are kernels of their own and
+// not a template flag over shared bodies: with the bodies shared, the compiler's report for the 4.11 kernels changed (k_bake_cover
+// 38 -> 42 VGPRs), and those are to compile as they did.
+__global__ void __launch_bounds__(256) k_bake_atlas_count(SceneView sv, BakeView bv, const BakeChartDev* __restrict__ charts,
+                                                          unsigned long long* __restrict__ counts) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > bv.tri_count) return;
+  unsigned long long c = 0ull;
+  if (i < bv.tri_count) {
+    const BakeBox bb = bake_box(bake_tri_atlas(sv, bv, charts, bv.first_tri + i), bv);
+    c = (unsigned long long)bb.nbx * bb.nby;
+  }
+  counts[i] = c;
+}
+
+__global__ void __launch_bounds__(256) k_bake_atlas_cover(SceneView sv, BakeView bv, const BakeChartDev* __restrict__ charts,
+                                                          const unsigned long long* __restrict__ off, uint32_t* __restrict__ owner) {
+  const uint32_t lane = lane_id();
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, waves = (gridDim.x * blockDim.x) >> 6;
+  const unsigned long long total = off[bv.tri_count];
+  const unsigned long long run = (total + waves - 1ull) / waves;
+  unsigned long long p = (unsigned long long)wave * run;
+  const unsigned long long end = p + run < total ? p + run : total;
+  if (p >= end) return;
+  uint32_t lo = 0u, hi = bv.tri_count;  // off[lo] <= p < off[hi]
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (off[mid] <= p) lo = mid; else hi = mid;
+  }
+  uint32_t t = lo;
+  unsigned long long t_begin = off[t], t_end = off[t + 1u];
+  BakeTri tri = bake_tri_atlas(sv, bv, charts, bv.first_tri + t);
+  BakeBox bb = bake_box(tri, bv);
+  for (; p < end; ++p) {
+    if (p >= t_end) {
+      // (t < tri_count: p < total = off[tri_count]).  The span holds the triangles of uncharted instances, which have no pairs: a
+      // wave that walked over 880 000 of them one dependent load at a time took 85 ms, so after a few steps it bisects
+      uint32_t steps = 0u;
+      do { ++t; t_begin = t_end; t_end = off[t + 1u]; } while (p >= t_end && ++steps < 8u);
+      if (p >= t_end) {
+        lo = t + 1u; hi = bv.tri_count;  // off[lo] <= p < off[hi]
+        while (hi - lo > 1u) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if (off[mid] <= p) lo = mid; else hi = mid;
+        }
+        t = lo; t_begin = off[t]; t_end = off[t + 1u];
+      }
+      tri = bake_tri_atlas(sv, bv, charts, bv.first_tri + t);
+      bb = bake_box(tri, bv);
+    }
+    const uint32_t k = (uint32_t)(p - t_begin);
+    const uint32_t row = k / bb.nbx, bx = bb.bx0 + (k - row * bb.nbx), by = bb.by0 + row;
+    const uint32_t x = (bx << 3) + (lane & 7u), y = (by << 3) + (lane >> 3);
+    if (x >= bv.width || y >= bv.height) continue;
+    float w1, w2;
+    if (bake_covers(tri, f2{(float)x + 0.5f, (float)y + 0.5f}, &w1, &w2)) atomicMin(owner + (((size_t)by * bv.blocks_x + bx) << 6) + lane, bv.first_tri + t);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_bake_atlas_sample(SceneView sv, BakeView bv, const BakeChartDev* __restrict__ charts,
+                                                           const uint32_t* __restrict__ owner, float4* __restrict__ samples, uint4* __restrict__ texels) {
+  const uint32_t count = bv.width * bv.height;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, lane = lane_id();
+  float4 pb = make_float4(0.0f, 0.0f, 0.0f, 0.0f), nr = pb;  // the all-zero sample: invalid by RENDER_SPEC 4.10
+  uint4 rec = make_uint4(0u, 0u, kAbsent, kAbsent);
+  if (i < count) {
+    const uint32_t y = i / bv.width, x = i - y * bv.width;
+    const uint32_t gid = owner[bake_tiled(bv, x, y)];
+    if (gid != kAbsent) {
+      const BakeTri tri = bake_tri_atlas(sv, bv, charts, gid);
+      float w1, w2;
+      (void)bake_covers(tri, f2{(float)x + 0.5f, (float)y + 0.5f}, &w1, &w2);
+      const float inv = 1.0f / tri.area;
+      const float u = w1 * inv, v = w2 * inv;
+      const float4* tp = reinterpret_cast<const float4*>(sv.tris_by_id + gid);
+      const float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
+      const f3 v0 = mk3(t0.x, t0.y, t0.z), e1 = mk3(t1.x, t1.y, t1.z), e2 = mk3(t2.x, t2.y, t2.z);
+      const f3 point = madd3(e2, v, madd3(e1, u, v0));  // RENDER_SPEC 4.8's q
+      f3 n;
+      const uint32_t flags = charts[__float_as_uint(reinterpret_cast<const float4*>(sv.shade_tris + gid)[0].w)].flags;  // the chart's
+      if (flags & HALA_BAKE_SHADING_NORMAL) {  // RENDER_SPEC 6 step 4, in the form of make_surface (shading.h)
+        const float4* sp = reinterpret_cast<const float4*>(sv.shade_tris + gid);
+        const float4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
+        const float w0 = 1.0f - u - v;
+        const f3 nl = madd3(mk3(s3.x, s3.y, s3.z), v, madd3(mk3(s2.x, s2.y, s2.z), u, mk3(s1.x, s1.y, s1.z) * w0));
+        n = normalize3(transform_normal(sv.primitives[__float_as_uint(s0.w)].transform, nl));
+      } else n = cross3(e1, e2);
+      if (flags & HALA_BAKE_FLIP_NORMAL) n = -n;
+      pb = make_float4(point.x, point.y, point.z, bv.bias);
+      nr = make_float4(n.x, n.y, n.z, bv.reach);
+      rec = make_uint4(__float_as_uint(u), __float_as_uint(v), gid, i);
+    }
+    if (texels) texels[i] = rec;
+  }
+  // word j of the wave's 128 goes to lane j & 63 of store j >> 6: it is word j & 1 of the sample of lane j >> 1
+  const size_t base = (size_t)(i - lane) * 2u;
+#pragma unroll
+  for (uint32_t h = 0; h < 2u; ++h) {
+    const int src = (int)((lane >> 1) + 32u * h);
+    const float4 a = make_float4(__shfl(pb.x, src), __shfl(pb.y, src), __shfl(pb.z, src), __shfl(pb.w, src));
+    const float4 b = make_float4(__shfl(nr.x, src), __shfl(nr.y, src), __shfl(nr.z, src), __shfl(nr.w, src));
+    const size_t j = base + 64u * h + lane;
+    const bool odd = (lane & 1u) != 0u;  // (per component: a select between two float4 went through scratch)
+    if (j < (size_t)count * 2u) samples[j] = make_float4(odd ? b.x : a.x, odd ? b.y : a.y, odd ? b.z : a.z, odd ? b.w : a.w);
+  }
+}
+
+
 // One wave per 8 x 8 block of the owner map: the block's 64 ownership bits (bit = (y & 7) * 8 + (x & 7)) as one word
 __global__ void __launch_bounds__(256) k_bake_blocks(BakeView bv, const uint32_t* __restrict__ owner, unsigned long long* __restrict__ bits) {
   const uint32_t block = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (block >= bv.blocks_x * bv.blocks_y) return;  // (whole waves leave together)
   const unsigned long long owned = __ballot(owner[((size_t)block << 6) + lane_id()] != kAbsent);
   if (lane_id() == 0u) bits[block] = owned;
+}
+
+// The owned-texel list (RENDER_SPEC 4.12: what the listed occlusion pass of occlusion.hip traces).  k_bake_list_count: one lane per block,
+// the popcount of its ownership word, and a 0 behind the last: the exclusive sum over blocks + 1 entries leaves the number of owned texels
+// at [blocks], on the device.  k_bake_list: one wave per block, one texel per lane: an owned texel writes its row-major index at the
+// block's offset + the owned texels of the block below its lane — block-major, deterministic, and a wave's 64 list entries are neighbours
+// on the map; an ownerless texel of the map writes the invalid record, which no ray and no queue entry is spent on.
+__global__ void __launch_bounds__(256) k_bake_list_count(BakeView bv, const unsigned long long* __restrict__ bits, uint32_t* __restrict__ counts) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, blocks = bv.blocks_x * bv.blocks_y;
+  if (i > blocks) return;
+  counts[i] = i < blocks ? (uint32_t)__popcll(bits[i]) : 0u;
+}
+__global__ void __launch_bounds__(256) k_bake_list(BakeView bv, const unsigned long long* __restrict__ bits, const uint32_t* __restrict__ off,
+                                                   uint32_t* __restrict__ list, float4* __restrict__ out) {
+  const uint32_t block = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = lane_id();
+  if (block >= bv.blocks_x * bv.blocks_y) return;  // (whole waves leave together)
+  const uint32_t by = block / bv.blocks_x, bx = block - by * bv.blocks_x;
+  const uint32_t x = (bx << 3) + (lane & 7u), y = (by << 3) + (lane >> 3);
+  if (x >= bv.width || y >= bv.height) return;  // (never owned: k_bake_cover leaves them out)
+  const unsigned long long owned = bits[block];
+  const uint32_t i = y * bv.width + x;
+  if ((owned >> lane) & 1ull) list[off[block] + (uint32_t)__popcll(owned & ((1ull << lane) - 1ull))] = i;  // (< W * H: at most one entry per texel)
+  else out[i] = make_float4(-1.0f, 0.0f, 0.0f, 0.0f);
 }
 
 // RENDER_SPEC 4.11, dilation: an ownerless texel looks at the owned texels within `margin` in x and in y and takes the record of the one
@@ -243,30 +397,62 @@ size_t bake_scan_bytes(uint32_t tri_count) {
                                 rocprim::plus<unsigned long long>(), 0);
   return bytes;
 }
-hipError_t launch_bake_samples(const SceneView& sv, uint32_t cu_count, const BakeView& view, const BakeScratch& sc, hala_occlusion_sample* samples,
-                               hala_bake_texel* texels, hipStream_t s) {
+size_t bake_list_scan_bytes(size_t blocks) {
+  size_t bytes = 0;
+  (void)rocprim::exclusive_scan(nullptr, bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, blocks + 1u, rocprim::plus<uint32_t>(), 0);
+  return bytes;
+}
+// charts null: RENDER_SPEC 4.11, the instance of the view; else 4.12
+static hipError_t bake_samples(const SceneView& sv, uint32_t cu_count, const BakeView& view, const BakeScratch& sc, const BakeChartDev* charts,
+                               hala_occlusion_sample* samples, hala_bake_texel* texels, hipStream_t s) {
   const BakeView bv = bake_grid(view);
   const uint32_t count = bv.width * bv.height;
   hipError_t e = hipMemsetAsync(sc.owner, 0xff, bake_owner_words(bv) * 4u, s);
   if (e != hipSuccess) return e;
   if (bv.tri_count) {
-    hipLaunchKernelGGL(k_bake_count, dim3(blocks_for(bv.tri_count + 1u, 256)), dim3(256), 0, s, sv, bv, sc.counts);
+    if (charts) hipLaunchKernelGGL(k_bake_atlas_count, dim3(blocks_for(bv.tri_count + 1u, 256)), dim3(256), 0, s, sv, bv, charts, sc.counts);
+    else hipLaunchKernelGGL(k_bake_count, dim3(blocks_for(bv.tri_count + 1u, 256)), dim3(256), 0, s, sv, bv, sc.counts);
     size_t bytes = sc.scan_bytes;
     e = rocprim::exclusive_scan(sc.scan_tmp, bytes, sc.counts, sc.offsets, 0ull, (size_t)bv.tri_count + 1u, rocprim::plus<unsigned long long>(), s);
     if (e != hipSuccess) return e;
     // enough waves to fill the chip several times over, and no more than there can be pairs
     const unsigned long long most = (unsigned long long)bv.blocks_x * bv.blocks_y * bv.tri_count;
     const uint32_t blocks = (uint32_t)std::min<unsigned long long>((unsigned long long)cu_count * 16ull, (most + 3ull) / 4ull);
-    hipLaunchKernelGGL(k_bake_cover, dim3(std::max(blocks, 1u)), dim3(256), 0, s, sv, bv, sc.offsets, sc.owner);
+    if (charts) hipLaunchKernelGGL(k_bake_atlas_cover, dim3(std::max(blocks, 1u)), dim3(256), 0, s, sv, bv, charts, sc.offsets, sc.owner);
+    else hipLaunchKernelGGL(k_bake_cover, dim3(std::max(blocks, 1u)), dim3(256), 0, s, sv, bv, sc.offsets, sc.owner);
   }
-  hipLaunchKernelGGL(k_bake_sample, dim3(blocks_for(count, 256)), dim3(256), 0, s, sv, bv, sc.owner, reinterpret_cast<float4*>(samples),
-                     reinterpret_cast<uint4*>(texels));
+  if (charts)
+    hipLaunchKernelGGL(k_bake_atlas_sample, dim3(blocks_for(count, 256)), dim3(256), 0, s, sv, bv, charts, sc.owner, reinterpret_cast<float4*>(samples),
+                       reinterpret_cast<uint4*>(texels));
+  else
+    hipLaunchKernelGGL(k_bake_sample, dim3(blocks_for(count, 256)), dim3(256), 0, s, sv, bv, sc.owner, reinterpret_cast<float4*>(samples),
+                       reinterpret_cast<uint4*>(texels));
   return hipGetLastError();
 }
-void launch_bake_dilate(const BakeView& view, const BakeScratch& sc, hala_occlusion* out, hala_bake_texel* texels, hipStream_t s) {
+hipError_t launch_bake_samples(const SceneView& sv, uint32_t cu_count, const BakeView& view, const BakeScratch& sc, hala_occlusion_sample* samples,
+                               hala_bake_texel* texels, hipStream_t s) {
+  return bake_samples(sv, cu_count, view, sc, nullptr, samples, texels, s);
+}
+hipError_t launch_bake_samples_atlas(const SceneView& sv, uint32_t cu_count, const BakeView& view, const BakeScratch& sc, const BakeChartDev* charts,
+                                     hala_occlusion_sample* samples, hala_bake_texel* texels, hipStream_t s) {
+  return bake_samples(sv, cu_count, view, sc, charts, samples, texels, s);
+}
+hipError_t launch_bake_list(const BakeView& view, const BakeScratch& sc, const BakeListScratch& ls, hala_occlusion* out, hipStream_t s) {
+  const BakeView bv = bake_grid(view);
+  const uint32_t blocks = bv.blocks_x * bv.blocks_y;
+  hipLaunchKernelGGL(k_bake_blocks, dim3(blocks_for(blocks, 4)), dim3(256), 0, s, bv, sc.owner, sc.block_bits);
+  hipLaunchKernelGGL(k_bake_list_count, dim3(blocks_for(blocks + 1u, 256)), dim3(256), 0, s, bv, sc.block_bits, ls.list_counts);
+  size_t bytes = sc.scan_bytes;
+  const hipError_t e = rocprim::exclusive_scan(sc.scan_tmp, bytes, ls.list_counts, ls.list_offsets, 0u, (size_t)blocks + 1u, rocprim::plus<uint32_t>(), s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_bake_list, dim3(blocks_for(blocks, 4)), dim3(256), 0, s, bv, sc.block_bits, ls.list_offsets, ls.list, reinterpret_cast<float4*>(out));
+  return hipGetLastError();
+}
+void launch_bake_dilate(const BakeView& view, const BakeScratch& sc, hala_occlusion* out, hala_bake_texel* texels, hipStream_t s, bool bits_ready) {
   const BakeView bv = bake_grid(view);
   if (bv.margin == 0u) return;
-  hipLaunchKernelGGL(k_bake_blocks, dim3(blocks_for(bv.blocks_x * bv.blocks_y, 4)), dim3(256), 0, s, bv, sc.owner, sc.block_bits);
+  if (!bits_ready)
+    hipLaunchKernelGGL(k_bake_blocks, dim3(blocks_for(bv.blocks_x * bv.blocks_y, 4)), dim3(256), 0, s, bv, sc.owner, sc.block_bits);
   hipLaunchKernelGGL(k_bake_dilate, dim3(blocks_for(bv.width * bv.height, 256)), dim3(256), 0, s, bv, sc.owner, sc.block_bits,
                      reinterpret_cast<float4*>(out), reinterpret_cast<uint4*>(texels));
 }

@@ -91,7 +91,31 @@ size_t bake_owner_words(const BakeView& bv);
 size_t bake_scan_bytes(uint32_t tri_count);
 hipError_t launch_bake_samples(const SceneView& sv, uint32_t cu_count, const BakeView& bv, const BakeScratch& sc, hala_occlusion_sample* samples,
                                hala_bake_texel* texels, hipStream_t s);
-void launch_bake_dilate(const BakeView& bv, const BakeScratch& sc, hala_occlusion* out, hala_bake_texel* texels, hipStream_t s);
+void launch_bake_dilate(const BakeView& bv, const BakeScratch& sc, hala_occlusion* out, hala_bake_texel* texels, hipStream_t s, bool bits_ready = false);
+// bake.hip — RENDER_SPEC 4.12: the atlas form.  `charts` has one entry per instance of the scene (charted = 0: the instance is not in the
+// atlas); bv.first_tri / tri_count span the charted instances' ranges (the triangles of uncharted instances in between count no pairs) and
+// bv.flags is not read: the flags are each chart's.  launch_bake_list turns the owner map launch_bake_samples_atlas left in `sc` into the
+// list of owned texels — their row-major indices in block-major order at sc.list, their number at sc.list_offsets[blocks] — without a word
+// to the host, leaves the ownership words in sc.block_bits (launch_bake_dilate: bits_ready) and writes the invalid record to every
+// ownerless texel of `out`.  Scratch on top of the above: list W * H words, list_counts and list_offsets blocks + 1 words each, scan_tmp
+// bake_list_scan_bytes(blocks) bytes.
+struct BakeChartDev {
+  float sx, sy, ox, oy;
+  uint32_t flags, charted, pad0, pad1;
+};  // 32 B
+struct BakeListScratch {
+  uint32_t *list, *list_counts, *list_offsets;
+};
+size_t bake_list_scan_bytes(size_t blocks);
+hipError_t launch_bake_samples_atlas(const SceneView& sv, uint32_t cu_count, const BakeView& bv, const BakeScratch& sc, const BakeChartDev* charts,
+                                     hala_occlusion_sample* samples, hala_bake_texel* texels, hipStream_t s);
+hipError_t launch_bake_list(const BakeView& bv, const BakeScratch& sc, const BakeListScratch& ls, hala_occlusion* out, hipStream_t s);
+// occlusion.hip — the listed form of launch_trace_occlusion: only the samples list[0 .. *count) are traced and resolved (out[list[c]]; the
+// other records are not touched), *count read on the device (<= max_count, which sizes the resolve's grid and the masks: max_count *
+// ceil(rays / 32) words, zeroed by the caller).  Stream and any-hit key of a ray are its sample's, not its list position's: the records
+// are those of the unlisted pass.  One-level trees only.
+void launch_trace_occlusion_listed(const LaunchCfg& lc, const SceneView& sv, const hala_occlusion_sample* samples, const uint32_t* list, const uint32_t* count,
+                                   uint32_t max_count, hala_occlusion* out, uint32_t* masks, uint32_t rays, uint32_t seed, WorkCounters* work, hipStream_t s);
 // shade.hip
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s);
 // resolve.hip

@@ -507,6 +507,10 @@ struct hala_rt_renderer {
   DeviceArray<unsigned long long> d_bake_counts, d_bake_offsets, d_bake_block_bits;
   DeviceArray<uint8_t> d_bake_scan;
   DeviceArray<hala_occlusion_sample> d_bake_samples;
+  // hala_rt_bake_atlas_*, RENDER_SPEC 4.12 (grown on demand): the chart of every instance, and the owned-texel list of a baked atlas with
+  // the per-block counts and offsets it is built from
+  DeviceArray<BakeChartDev> d_bake_charts;
+  DeviceArray<uint32_t> d_bake_list, d_bake_list_counts, d_bake_list_offsets;
 
   uint64_t total_frames = 0;
   bool counting = false;

@@ -711,6 +711,64 @@ class HalaRenderer:
                                                           C.c_void_p(texels.ctypes.data)))
         return rec.reshape(int(height), int(width)), texels.reshape(int(height), int(width))
 
+    @staticmethod
+    def _bake_charts(charts):
+        """the chart table of an atlas as a contiguous array of A.BAKE_CHART_DTYPE: such an array as it is, or a sequence of
+        (instance, scale, offset[, shading_normal[, flip]])"""
+        if isinstance(charts, np.ndarray) and charts.dtype == A.BAKE_CHART_DTYPE:
+            return np.ascontiguousarray(charts).reshape(-1)
+        rows = list(charts)
+        table = np.zeros(len(rows), dtype=A.BAKE_CHART_DTYPE)
+        for k, row in enumerate(rows):
+            instance, scale, offset = row[0], row[1], row[2]
+            shading_normal, flip = (row[3] if len(row) > 3 else False), (row[4] if len(row) > 4 else False)
+            table[k] = (int(instance), (A.BAKE_SHADING_NORMAL if shading_normal else 0) | (A.BAKE_FLIP_NORMAL if flip else 0), tuple(scale), tuple(offset))
+        return table
+
+    def _bake_atlas_desc(self, table, width, height, bias, reach, margin):
+        return A.BakeAtlasDesc(int(width), int(height), float(self.ray_eps() if bias is None else bias), float(reach), int(margin), len(table))
+
+    def bake_atlas_samples(self, charts, width, height, *, bias=None, reach=np.inf, out=None, out_texels=None, stream: int = 0):
+        """RENDER_SPEC 4.12: several instances rasterised into one width x height map.  `charts` places them: an array of
+        A.BAKE_CHART_DTYPE, or a sequence of (instance, scale, offset, shading_normal, flip) with scale and offset pairs applied to the
+        instance's texture coordinates (uv * scale + offset, the map being [0, 1]^2) and the normal's choice per chart.  Where charts
+        overlap, the lowest global triangle id owns the texel.  Returns (samples, texels) shaped (height, width) as bake_samples() does;
+        the device form is bake_samples()'s."""
+        table = self._bake_charts(charts)
+        d = self._bake_atlas_desc(table, width, height, bias, reach, 0)
+        count = int(width) * int(height)
+        if out is not None:
+            d_s = self._bake_device_out(out, count, A.OCCLUSION_SAMPLE_DTYPE.itemsize, "out")
+            d_t = self._bake_device_out(out_texels, count, A.BAKE_TEXEL_DTYPE.itemsize, "out_texels")
+            self._check(self._lib.hala_rt_bake_atlas_samples(self._h, C.byref(d), C.c_void_p(table.ctypes.data), C.c_void_p(d_s), C.c_void_p(d_t),
+                                                             C.c_void_p(stream)))
+            return None
+        samples = np.empty(max(count, 0), dtype=A.OCCLUSION_SAMPLE_DTYPE)
+        texels = np.empty(max(count, 0), dtype=A.BAKE_TEXEL_DTYPE)
+        self._check(self._lib.hala_rt_bake_atlas_samples_host(self._h, C.byref(d), C.c_void_p(table.ctypes.data), C.c_void_p(samples.ctypes.data),
+                                                              C.c_void_p(texels.ctypes.data)))
+        return samples.reshape(int(height), int(width)), texels.reshape(int(height), int(width))
+
+    def bake_atlas_occlusion(self, charts, width, height, rays, seed=0, *, margin=0, bias=None, reach=np.inf, out=None, out_texels=None, stream: int = 0):
+        """RENDER_SPEC 4.12: the ambient-occlusion atlas of the charted instances: what occlusion() answers, with `rays` and `seed`, for
+        the samples of bake_atlas_samples(), texel i being sample i, then the dilation of bake_occlusion() over the whole atlas.  Only
+        the texels that have a sample are traced: a texel of the gutter costs next to nothing.  Returns (records, texels) shaped
+        (height, width) as bake_occlusion() does; the device form is bake_occlusion()'s."""
+        table = self._bake_charts(charts)
+        d = self._bake_atlas_desc(table, width, height, bias, reach, margin)
+        count = int(width) * int(height)
+        if out is not None:
+            d_o = self._bake_device_out(out, count, A.OCCLUSION_DTYPE.itemsize, "out")
+            d_t = self._bake_device_out(out_texels, count, A.BAKE_TEXEL_DTYPE.itemsize, "out_texels")
+            self._check(self._lib.hala_rt_bake_atlas_occlusion(self._h, C.byref(d), C.c_void_p(table.ctypes.data), C.c_uint32(rays), C.c_uint32(seed),
+                                                               C.c_void_p(d_o), C.c_void_p(d_t), C.c_void_p(stream)))
+            return None
+        rec = np.empty(max(count, 0), dtype=A.OCCLUSION_DTYPE)
+        texels = np.empty(max(count, 0), dtype=A.BAKE_TEXEL_DTYPE)
+        self._check(self._lib.hala_rt_bake_atlas_occlusion_host(self._h, C.byref(d), C.c_void_p(table.ctypes.data), C.c_uint32(rays), C.c_uint32(seed),
+                                                                C.c_void_p(rec.ctypes.data), C.c_void_p(texels.ctypes.data)))
+        return rec.reshape(int(height), int(width)), texels.reshape(int(height), int(width))
+
     def bvh_info(self) -> A.BvhInfo:
         i = A.BvhInfo()
         self._check(self._lib.hala_rt_get_bvh_info(self._h, C.byref(i)))

@@ -1000,7 +1000,9 @@ int hala_rt_occlusion_host(hala_rt_renderer* r, const hala_occlusion_sample* sam
  * or output, no committed scene, a two-level tree (the records of instanced primitives are in object space: commit with instancing =
  * 0), `instance` out of range, a dimension of 0 or above HALA_MAX_BAKE_DIM, `margin` above HALA_MAX_BAKE_MARGIN, an unknown flag bit,
  * a non-finite bias, rays outside 1..256, width * height * rays >= 2^32.
- * Not built: compaction of empty texels, vertex baking, supersampled or conservative coverage, UV wrap, a second UV set, two-level trees. */
+ * hala_rt_bake_occlusion hands every texel of the map to the occlusion pass, covered or not: a map with much gutter is baked faster as
+ * an atlas of one chart (hala_rt_bake_atlas_occlusion below), which traces the covered texels only.
+ * Not built: vertex baking, supersampled or conservative coverage, UV wrap, a second UV set, two-level trees. */
 #define HALA_MAX_BAKE_DIM 4096
 #define HALA_MAX_BAKE_MARGIN 16
 #define HALA_BAKE_SHADING_NORMAL 1u
@@ -1020,6 +1022,45 @@ int hala_rt_bake_occlusion(hala_rt_renderer* r, const hala_bake_desc* desc, uint
                            hala_bake_texel* d_texels /* or NULL */, void* hip_stream);
 int hala_rt_bake_occlusion_host(hala_rt_renderer* r, const hala_bake_desc* desc, uint32_t rays, uint32_t seed, hala_occlusion* out,
                                 hala_bake_texel* texels /* or NULL */);
+
+/* Bake atlases (RENDER_SPEC 4.12): several instances in one map.  `charts` is a host array of desc->chart_count entries, read before the
+ * call returns; each places one instance of the scene: a triangle's texture coordinates go through uv * scale + offset (one fma per
+ * component) before they are scaled to texels, and everything behind that is the bake map above — the coverage rule, the sample, the
+ * texel record, with `flags` (HALA_BAKE_*) per chart since instances wind differently.  A texel that triangles of several charts cover
+ * belongs to the lowest global triangle id among all of them, as within one instance.  A negative scale mirrors a chart, a zero scale
+ * covers nothing.  An atlas of one chart with scale (1, 1) and offset (0, 0) is the bake map of that instance (bit for bit unless a
+ * texture coordinate is -0, which the fma turns into +0).
+ * hala_rt_bake_atlas_samples writes the samples and texel records (and ignores `margin`); hala_rt_bake_atlas_occlusion writes what
+ * hala_rt_occlusion answers for exactly that sample buffer with (rays, seed), sample i being texel i, then the dilation over the whole
+ * atlas.  Its occlusion pass traces only the texels that have a sample: their list is built on the device from the owner map, so a
+ * texel of the gutter costs one store.  The list stays inside the renderer.  Scratch, stream order, growing buffers and the optional
+ * d_texels are as for the bake maps.  Refused with a message and without touching anything: a null description, chart table or output,
+ * no committed scene, a two-level tree, chart_count 0 or above the scene's instance count, an instance out of range or named twice, an
+ * unknown flag bit, a non-finite scale, offset or bias, a dimension of 0 or above HALA_MAX_BAKE_DIM, `margin` above
+ * HALA_MAX_BAKE_MARGIN, rays outside 1..256, width * height * rays >= 2^32.
+ * Not built: packing charts into an atlas (the layout is the caller's), vertex baking, supersampled or conservative coverage, UV wrap, a
+ * second UV set, two-level trees, handing the list of owned texels to the caller, compaction inside plain hala_rt_occlusion. */
+typedef struct hala_bake_chart {
+  uint32_t instance; /* index in instance order (RENDER_SPEC 3); at most one chart per instance */
+  uint32_t flags;    /* HALA_BAKE_* */
+  float scale[2];    /* of (u, v) */
+  float offset[2];   /* of (u, v), in units of the atlas: [0, 1] is the map */
+} hala_bake_chart;   /* 24 B */
+typedef struct hala_bake_atlas_desc {
+  uint32_t width, height; /* 1 .. HALA_MAX_BAKE_DIM */
+  float bias, reach;      /* of every sample (RENDER_SPEC 4.10) */
+  uint32_t margin;        /* dilation reach in texels, 0 .. HALA_MAX_BAKE_MARGIN */
+  uint32_t chart_count;   /* 1 .. the scene's instances */
+} hala_bake_atlas_desc;   /* 24 B */
+int hala_rt_bake_atlas_samples(hala_rt_renderer* r, const hala_bake_atlas_desc* desc, const hala_bake_chart* charts,
+                               hala_occlusion_sample* d_samples /* width * height */, hala_bake_texel* d_texels /* width * height, or NULL */,
+                               void* hip_stream);
+int hala_rt_bake_atlas_samples_host(hala_rt_renderer* r, const hala_bake_atlas_desc* desc, const hala_bake_chart* charts, hala_occlusion_sample* samples,
+                                    hala_bake_texel* texels /* or NULL */);
+int hala_rt_bake_atlas_occlusion(hala_rt_renderer* r, const hala_bake_atlas_desc* desc, const hala_bake_chart* charts, uint32_t rays, uint32_t seed,
+                                 hala_occlusion* d_out /* width * height */, hala_bake_texel* d_texels /* or NULL */, void* hip_stream);
+int hala_rt_bake_atlas_occlusion_host(hala_rt_renderer* r, const hala_bake_atlas_desc* desc, const hala_bake_chart* charts, uint32_t rays, uint32_t seed,
+                                      hala_occlusion* out, hala_bake_texel* texels /* or NULL */);
 
 /* BVH introspection for the oracle cross-check: 64-B nodes + 48-B triangles as laid out in HBM.
  * node_width is 4: compressed 4-wide nodes (docs/RENDER_SPEC.md §4.1b). */

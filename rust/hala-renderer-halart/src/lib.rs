@@ -73,6 +73,9 @@ pub mod sys {
   /// hala_bake_desc (28 B) / hala_bake_texel (16 B): bake maps (include/halart.h, docs/RENDER_SPEC.md 4.11); flags: HALA_BAKE_*
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_bake_desc { pub instance: u32, pub width: u32, pub height: u32, pub flags: u32, pub bias: f32, pub reach: f32, pub margin: u32 }
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_bake_texel { pub u: f32, pub v: f32, pub prim: u32, pub source: u32 }
+  /// hala_bake_chart (24 B) / hala_bake_atlas_desc (24 B): bake atlases (include/halart.h, docs/RENDER_SPEC.md 4.12); flags: HALA_BAKE_*, per chart
+  #[repr(C)] #[derive(Clone, Copy)] pub struct hala_bake_chart { pub instance: u32, pub flags: u32, pub scale: [f32; 2], pub offset: [f32; 2] }
+  #[repr(C)] #[derive(Clone, Copy)] pub struct hala_bake_atlas_desc { pub width: u32, pub height: u32, pub bias: f32, pub reach: f32, pub margin: u32, pub chart_count: u32 }
   #[repr(C)] #[derive(Default)] pub struct hala_rt_info { pub width: u32, pub height: u32 }
 
   /// hala_rt_build_options (include/halart.h): every field 0 = the default
@@ -165,6 +168,14 @@ pub mod sys {
                                   d_texels: *mut hala_bake_texel, hip_stream: *mut c_void) -> c_int;
     pub fn hala_rt_bake_occlusion_host(r: *mut hala_rt_renderer, desc: *const hala_bake_desc, rays: u32, seed: u32, out: *mut hala_occlusion,
                                        texels: *mut hala_bake_texel) -> c_int;
+    pub fn hala_rt_bake_atlas_samples(r: *mut hala_rt_renderer, desc: *const hala_bake_atlas_desc, charts: *const hala_bake_chart,
+                                      d_samples: *mut hala_occlusion_sample, d_texels: *mut hala_bake_texel, hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_bake_atlas_samples_host(r: *mut hala_rt_renderer, desc: *const hala_bake_atlas_desc, charts: *const hala_bake_chart,
+                                           samples: *mut hala_occlusion_sample, texels: *mut hala_bake_texel) -> c_int;
+    pub fn hala_rt_bake_atlas_occlusion(r: *mut hala_rt_renderer, desc: *const hala_bake_atlas_desc, charts: *const hala_bake_chart, rays: u32, seed: u32,
+                                        d_out: *mut hala_occlusion, d_texels: *mut hala_bake_texel, hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_bake_atlas_occlusion_host(r: *mut hala_rt_renderer, desc: *const hala_bake_atlas_desc, charts: *const hala_bake_chart, rays: u32, seed: u32,
+                                             out: *mut hala_occlusion, texels: *mut hala_bake_texel) -> c_int;
     pub fn hala_rt_update_node_transform(r: *mut hala_rt_renderer, node_index: u32, local_transform: *const f32) -> c_int;
     pub fn hala_rt_update_material(r: *mut hala_rt_renderer, material_index: u32, material: *const hala_material_desc) -> c_int;
     pub fn hala_rt_update_vertices(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, vertices: *const hala_vertex, vertex_count: u32) -> c_int;
@@ -424,6 +435,37 @@ impl HalaRenderer {
   pub fn bake_occlusion_device(&self, desc: &sys::hala_bake_desc, rays: u32, seed: u32, d_out: *mut sys::hala_occlusion, d_texels: *mut sys::hala_bake_texel)
                                -> Result<(), HalaRendererError> {
     check(unsafe { sys::hala_rt_bake_occlusion(self.h, desc, rays, seed, d_out, d_texels, std::ptr::null_mut()) })
+  }
+  /// bake atlases (RENDER_SPEC 4.12) to host memory: the instances of `charts`, each through its scale and offset, in one map; `desc.chart_count`
+  /// is taken from the slice.  Only texels that a chart covers are traced by the occlusion form.
+  pub fn bake_atlas_samples(&self, desc: &sys::hala_bake_atlas_desc, charts: &[sys::hala_bake_chart])
+                            -> Result<(Vec<sys::hala_occlusion_sample>, Vec<sys::hala_bake_texel>), HalaRendererError> {
+    let d = sys::hala_bake_atlas_desc { chart_count: charts.len() as u32, ..*desc };
+    let n = d.width as usize * d.height as usize;
+    let mut samples = vec![sys::hala_occlusion_sample { point: [0.0; 3], bias: 0.0, normal: [0.0; 3], reach: 0.0 }; n];
+    let mut texels = vec![sys::hala_bake_texel { u: 0.0, v: 0.0, prim: u32::MAX, source: u32::MAX }; n];
+    check(unsafe { sys::hala_rt_bake_atlas_samples_host(self.h, &d, charts.as_ptr(), samples.as_mut_ptr(), texels.as_mut_ptr()) })?;
+    Ok((samples, texels))
+  }
+  pub fn bake_atlas_occlusion(&self, desc: &sys::hala_bake_atlas_desc, charts: &[sys::hala_bake_chart], rays: u32, seed: u32)
+                              -> Result<(Vec<sys::hala_occlusion>, Vec<sys::hala_bake_texel>), HalaRendererError> {
+    let d = sys::hala_bake_atlas_desc { chart_count: charts.len() as u32, ..*desc };
+    let n = d.width as usize * d.height as usize;
+    let mut out = vec![sys::hala_occlusion { visibility: -1.0, bent: [0.0; 3] }; n];
+    let mut texels = vec![sys::hala_bake_texel { u: 0.0, v: 0.0, prim: u32::MAX, source: u32::MAX }; n];
+    check(unsafe { sys::hala_rt_bake_atlas_occlusion_host(self.h, &d, charts.as_ptr(), rays, seed, out.as_mut_ptr(), texels.as_mut_ptr()) })?;
+    Ok((out, texels))
+  }
+  /// the device-pointer forms, on the renderer's stream; the chart table is read before they return; d_texels may be null
+  pub fn bake_atlas_samples_device(&self, desc: &sys::hala_bake_atlas_desc, charts: &[sys::hala_bake_chart], d_samples: *mut sys::hala_occlusion_sample,
+                                   d_texels: *mut sys::hala_bake_texel) -> Result<(), HalaRendererError> {
+    let d = sys::hala_bake_atlas_desc { chart_count: charts.len() as u32, ..*desc };
+    check(unsafe { sys::hala_rt_bake_atlas_samples(self.h, &d, charts.as_ptr(), d_samples, d_texels, std::ptr::null_mut()) })
+  }
+  pub fn bake_atlas_occlusion_device(&self, desc: &sys::hala_bake_atlas_desc, charts: &[sys::hala_bake_chart], rays: u32, seed: u32,
+                                     d_out: *mut sys::hala_occlusion, d_texels: *mut sys::hala_bake_texel) -> Result<(), HalaRendererError> {
+    let d = sys::hala_bake_atlas_desc { chart_count: charts.len() as u32, ..*desc };
+    check(unsafe { sys::hala_rt_bake_atlas_occlusion(self.h, &d, charts.as_ptr(), rays, seed, d_out, d_texels, std::ptr::null_mut()) })
   }
   /// binds an ordered node set (empty: unbinds); refit_nodes then takes one local transform per bound node, in that order
   pub fn bind_nodes(&mut self, node_indices: &[u32]) -> Result<(), HalaRendererError> {
