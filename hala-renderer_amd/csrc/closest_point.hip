@@ -71,21 +71,14 @@ k_closest_point(SceneView sv, const float4* __restrict__ queries, float4* __rest
   }
 }
 
-// The kernel's own LDS: the per-lane stacks, and a staged tree behind them
-static size_t point_lds_bytes(const SceneView& sv, TreeForm tree) {
-  const size_t stacks = (size_t)traverse_stack_lds_levels(tree) * kTraverseThreads * 8;
-  return tree == TreeForm::Staged ? stacks + (size_t)sv.lds_nodes * 64 + (size_t)sv.lds_tris * 48 : stacks;
-}
 bool launch_closest_point(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_count, const hala_point_query* queries, hala_closest_point* out,
                           uint32_t n, WorkCounters* work, unsigned long long* counters, hipStream_t s) {
   const TreeForm tree = tree_form(sv);
   if (tree == TreeForm::TwoLevel) return false;
-  const size_t smem = point_lds_bytes(sv, tree);
-  const uint32_t per_cu = counters ? tree_blocks_per_cu([](auto STAGED, auto) { return k_closest_point<STAGED, true>; }, tree, kTraverseThreads, smem)
-                                  : tree_blocks_per_cu([](auto STAGED, auto) { return k_closest_point<STAGED, false>; }, tree, kTraverseThreads, smem);
+  const size_t smem = query_lds_bytes(sv, tree, kTraverseThreads);
+  const uint32_t per_cu = counted_blocks_per_cu([](auto STAGED, auto COUNT) { return k_closest_point<STAGED, COUNT>; }, counters != nullptr, tree, kTraverseThreads, smem);
   if (per_cu == 0u) return false;
-  // the spill area holds one slice per lane of lc.persistent_blocks workgroups: never a larger grid than that
-  const uint32_t blocks = std::min(lc.persistent_blocks, cu_count * std::min(per_cu, 8u));
+  const uint32_t blocks = query_blocks(lc, cu_count, per_cu);
   with_flags([&](auto STAGED, auto COUNT) {
     hipLaunchKernelGGL((k_closest_point<STAGED, COUNT>), dim3(blocks), dim3(kTraverseThreads), smem, s, sv, reinterpret_cast<const float4*>(queries),
                        reinterpret_cast<float4*>(out), n, work, lc.spill, lc.refill, counters);

@@ -329,24 +329,15 @@ k_grid_rows(SceneView sv, GridView g, uint32_t* __restrict__ bits, WorkCounters*
   if (COUNT) grid_count(counters, 2, n_nodes, n_tris);
 }
 
-// The kernels' own LDS: the stacks, and a staged tree behind them
-static size_t grid_lds_bytes(const SceneView& sv, TreeForm tree) {
-  const size_t stacks = (size_t)traverse_stack_lds_levels(tree) * kTraverseThreads * 8;
-  return tree == TreeForm::Staged ? stacks + (size_t)sv.lds_nodes * 64 + (size_t)sv.lds_tris * 48 : stacks;
-}
-// a grid within lc.persistent_blocks: the spill area holds one slice per lane of that many workgroups
-static uint32_t grid_blocks(const LaunchCfg& lc, uint32_t cu_count, uint32_t per_cu) { return std::min(lc.persistent_blocks, cu_count * std::min(per_cu, 8u)); }
-
 bool launch_grid_rows(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_count, const GridView& g, uint32_t* bits, WorkCounters* work,
                       unsigned long long* counters, hipStream_t s) {
   const TreeForm tree = tree_form(sv);
   if (tree == TreeForm::TwoLevel) return false;
-  const size_t smem = grid_lds_bytes(sv, tree);
-  const uint32_t per_cu = counters ? tree_blocks_per_cu([](auto STAGED, auto) { return k_grid_rows<STAGED, true>; }, tree, kTraverseThreads, smem)
-                                  : tree_blocks_per_cu([](auto STAGED, auto) { return k_grid_rows<STAGED, false>; }, tree, kTraverseThreads, smem);
+  const size_t smem = query_lds_bytes(sv, tree, kTraverseThreads);
+  const uint32_t per_cu = counted_blocks_per_cu([](auto STAGED, auto COUNT) { return k_grid_rows<STAGED, COUNT>; }, counters != nullptr, tree, kTraverseThreads, smem);
   if (per_cu == 0u) return false;
   with_flags([&](auto STAGED, auto COUNT) {
-    hipLaunchKernelGGL((k_grid_rows<STAGED, COUNT>), dim3(grid_blocks(lc, cu_count, per_cu)), dim3(kTraverseThreads), smem, s, sv, g, bits, work, lc.spill,
+    hipLaunchKernelGGL((k_grid_rows<STAGED, COUNT>), dim3(query_blocks(lc, cu_count, per_cu)), dim3(kTraverseThreads), smem, s, sv, g, bits, work, lc.spill,
                        lc.refill, counters);
   }, tree == TreeForm::Staged, counters != nullptr);
   return true;
@@ -355,16 +346,12 @@ bool launch_distance_grid(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_
                           const uint32_t* inside, WorkCounters* work, unsigned long long* counters, hipStream_t s) {
   const TreeForm tree = tree_form(sv);
   if (tree == TreeForm::TwoLevel) return false;
-  const size_t smem = grid_lds_bytes(sv, tree);
-  uint32_t per_cu;
-  if (method == 2u)
-    per_cu = counters ? tree_blocks_per_cu([](auto STAGED, auto) { return k_grid_brick<STAGED, true>; }, tree, kTraverseThreads, smem)
-                      : tree_blocks_per_cu([](auto STAGED, auto) { return k_grid_brick<STAGED, false>; }, tree, kTraverseThreads, smem);
-  else
-    per_cu = counters ? tree_blocks_per_cu([](auto STAGED, auto) { return k_grid_lane<STAGED, true>; }, tree, kTraverseThreads, smem)
-                      : tree_blocks_per_cu([](auto STAGED, auto) { return k_grid_lane<STAGED, false>; }, tree, kTraverseThreads, smem);
+  const size_t smem = query_lds_bytes(sv, tree, kTraverseThreads);
+  const uint32_t per_cu =
+      method == 2u ? counted_blocks_per_cu([](auto STAGED, auto COUNT) { return k_grid_brick<STAGED, COUNT>; }, counters != nullptr, tree, kTraverseThreads, smem)
+                   : counted_blocks_per_cu([](auto STAGED, auto COUNT) { return k_grid_lane<STAGED, COUNT>; }, counters != nullptr, tree, kTraverseThreads, smem);
   if (per_cu == 0u) return false;
-  const uint32_t blocks = grid_blocks(lc, cu_count, per_cu);
+  const uint32_t blocks = query_blocks(lc, cu_count, per_cu);
   with_flags([&](auto STAGED, auto COUNT) {
     if (method == 2u)
       hipLaunchKernelGGL((k_grid_brick<STAGED, COUNT>), dim3(blocks), dim3(kTraverseThreads), smem, s, sv, g, distance, prim, inside, work, counters);

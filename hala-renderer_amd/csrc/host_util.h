@@ -49,6 +49,8 @@ struct DeviceArray {
     if (e == hipSuccess) count = n; else ptr = nullptr;
     return e;
   }
+  // resize, but never to fewer elements: for a buffer that is kept between calls and grown on demand
+  hipError_t grow(size_t n) { return count < n || !ptr ? resize(n) : hipSuccess; }
   hipError_t upload(const T* src, size_t n, hipStream_t s) {
     hipError_t e = resize(n);
     if (e != hipSuccess || n == 0) return e;

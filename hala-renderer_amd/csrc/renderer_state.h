@@ -1,6 +1,6 @@
 // renderer_state.h — the renderer object behind the C ABI (struct hala_rt_renderer), shared by the host units that implement it:
 // renderer.hip (life cycle, scene, update), rt_scene.hip (uploads, edits), rt_trees.hip (trees, refit sequence), rt_outputs.hip (views, AOVs, adaptive sampling, light
-// groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_deform.hip (deformers), rt_rig.hip (rigs and clips), rt_shutter.hip (shutter motion blur), rt_nodes.hip (node batches), rt_tiles.hip (tile shard and exchange) and rt_rays.hip.
+// groups), rt_cryptomatte.hip, rt_post.hip (denoise, temporal reprojection), rt_deform.hip (deformers), rt_rig.hip (rigs and clips), rt_shutter.hip (shutter motion blur), rt_nodes.hip (node batches), rt_tiles.hip (tile shard and exchange), rt_rays.hip (ray batches), rt_queries.hip and rt_bake.hip (the other query batches).
 // Each feature keeps its state in one struct that knows how to turn itself off.  What is indexed by path slot (per-path state, queues)
 // lives in the WavefrontSet of a frame slot (FrameSlots::slot[2]: two updates in flight), sized by WavefrontSet::fit to the one PathShape
 // that hala_rt_renderer::path_shape() computes: a feature with per-path state adds a field to the shape and an array to the set.
@@ -177,6 +177,44 @@ struct ScratchOrder {
     return HALA_OK;
   }
   void release() { if (batch_done) (void)hipEventDestroy(batch_done); }
+};
+// The scratch contract of a query batch's device form (ray batches, multi-hit, closest points, distance grids, occlusion, bakes), once:
+// the work runs on the caller's stream, ordered behind the scratch's previous user, without a host synchronisation, and batch_done is
+// recorded behind it for the next user.  hala_rt_renderer::batch(hip_stream) makes one; open() before the first launch or memset that
+// touches the scratch, close() as the entry point's result.  A scope left open — an RT_HIP or RT_FAIL return in between — still records
+// batch_done behind whatever the call queued, quietly: the call is failing already, and the message stays that of the first failure.
+struct BatchScope {
+  ScratchOrder& scratch;
+  WorkCounters* work;
+  hipStream_t s;
+  bool opened = false;
+  BatchScope(ScratchOrder& order, WorkCounters* counters, hipStream_t stream) : scratch(order), work(counters), s(stream) {}
+  BatchScope(const BatchScope&) = delete;
+  BatchScope& operator=(const BatchScope&) = delete;
+  ~BatchScope() {
+    if (!opened) return;
+    if (!scratch.batch_done && hipEventCreateWithFlags(&scratch.batch_done, hipEventDisableTiming) != hipSuccess) { scratch.batch_done = nullptr; return; }
+    if (hipEventRecord(scratch.batch_done, s) == hipSuccess) { scratch.event = scratch.batch_done; scratch.stream = s; }
+  }
+  int open() {
+    if (scratch.acquire(s) != HALA_OK) return HALA_ERR;
+    opened = true;
+    return HALA_OK;
+  }
+  int reset_work() {
+    RT_HIP(hipMemsetAsync(work, 0, sizeof(WorkCounters), s));
+    return HALA_OK;
+  }
+  // refusal: a launcher found that its kernel fits no compute unit — said once the event is recorded, as the result
+  int close(const char* refusal = nullptr) {
+    opened = false;
+    if (!scratch.batch_done) RT_HIP(hipEventCreateWithFlags(&scratch.batch_done, hipEventDisableTiming));
+    RT_HIP(hipEventRecord(scratch.batch_done, s));
+    scratch.event = scratch.batch_done; scratch.stream = s;
+    if (refusal) RT_FAIL(refusal);
+    RT_HIP(hipGetLastError());
+    return HALA_OK;
+  }
 };
 
 // multi-GPU exchange (C1 of SURVEY 2.1): one RCCL all-gather of the rank's tile buffer per AOV and frame, inside the library
@@ -586,6 +624,8 @@ struct hala_rt_renderer {
     if (lcfg.spill) lc.spill = slots.slot[slot].spill.ptr;
     return lc;
   }
+  // the scratch scope of a query batch on the caller's stream (null: the renderer's own)
+  BatchScope batch(void* hip_stream) { return BatchScope(scratch, d_batch_work.ptr, hip_stream ? static_cast<hipStream_t>(hip_stream) : stream); }
   // what a path slot holds with `capacity` paths per pixel slot in flight: the one place that says so
   PathShape path_shape(uint32_t capacity) const { return PathShape{(size_t)slot_count * capacity, (aov_mask & 1u) != 0u, wants_ids(), groups.count}; }
   PathShape path_shape() const { return path_shape(batch_capacity); }
@@ -724,6 +764,47 @@ int shutter_step(hala_rt_renderer* r, uint32_t j);
 int crypto_prepare(hala_rt_renderer* r);
 // rt_tiles.hip
 void compute_tiling(hala_rt_renderer* r);
+
+// ---- shared by the units that answer query batches (rt_rays.hip, rt_queries.hip, rt_bake.hip) ---------------------------------------------
+// The refusals they share.  one_level: what the feature calls itself, where it is built for one-level trees only
+inline int check_committed(const hala_rt_renderer* r, const char* one_level = nullptr) {
+  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");  // src/rt_renderer.rs:284
+  if (one_level && r->two_level) RT_FAIL(std::string(one_level) + " are not built for two-level trees: commit the scene flattened (instancing = 0).");
+  return HALA_OK;
+}
+inline int check_occlusion_rays(uint32_t rays) {
+  if (rays == 0 || rays > HALA_MAX_OCCLUSION_RAYS) RT_FAIL("The occlusion ray count must be 1.." + std::to_string(HALA_MAX_OCCLUSION_RAYS) + ".");
+  return HALA_OK;
+}
+inline int check_occlusion_size(uint64_t samples, uint32_t rays, const char* too_large) {  // a ray's index is 32 bits
+  if (samples * rays >= (1ull << 32)) RT_FAIL(too_large);
+  return HALA_OK;
+}
+// The device twin of an optional host output array, for the host form of a call: `n` records where the host pointer is given, none (and a
+// null device pointer) where it is not.  host_form below allocates the twins, makes the call and reads them back.
+template <class T>
+struct HostOut {
+  T* host;
+  size_t n;
+  DeviceArray<T> dev;
+  HostOut(T* host_ptr, size_t count) : host(host_ptr), n(count) {}
+  hipError_t stage() { return host ? dev.resize(n) : hipSuccess; }
+  hipError_t fetch(hipStream_t s) { return host ? hipMemcpyAsync(host, dev.ptr, n * sizeof(T), hipMemcpyDeviceToHost, s) : hipSuccess; }
+  T* ptr() const { return host ? dev.ptr : nullptr; }
+};
+// The host form of a call whose device form `call` runs on `s`: stage the outputs, call, read them back, wait — the one place that waits.
+// -> HALA_OK, or HALA_ERR with the message set (by `call`, where it refused)
+template <class Call, class... Outs>
+int host_form(hipStream_t s, Call call, Outs&... outs) {
+  hipError_t e = hipSuccess;
+  ((e = e == hipSuccess ? outs.stage() : e), ...);
+  RT_HIP(e);
+  if (call() != HALA_OK) return HALA_ERR;
+  ((e = e == hipSuccess ? outs.fetch(s) : e), ...);
+  RT_HIP(e);
+  RT_HIP(hipStreamSynchronize(s));
+  return HALA_OK;
+}
 
 // ---- shared by the units that edit and pose vertices (rt_scene.hip, rt_deform.hip, rt_shutter.hip, rt_rig.hip) ---------------------------
 inline int find_primitive(hala_rt_renderer* r, uint32_t mesh_index, uint32_t primitive_index, uint32_t* prim) {

@@ -51,7 +51,7 @@ int hala_rt_set_views(hala_rt_renderer* r, const uint32_t* camera_indices, uint3
     if (e != hipSuccess) { r->views = old_views; RT_HIP(e); }
   }
   if (r->groups.count) {  // light groups (RENDER_SPEC §14): every view's images, zero until its first update
-    hipError_t e = r->groups.img.count < n * r->groups.count ? r->groups.img.resize(n * r->groups.count) : hipSuccess;
+    hipError_t e = r->groups.img.grow(n * r->groups.count);
     if (e == hipSuccess) e = hipMemsetAsync(r->groups.img.ptr, 0, r->groups.img.bytes(), r->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
     if (e != hipSuccess) { r->views = old_views; RT_HIP(e); }

@@ -1,5 +1,6 @@
-// rt_rays.hip — what works without a frame: the ray-batch operator on the committed scene's tree, the hala_rtprog object over it,
-// and the stand-alone helpers of the C ABI (environment distribution, tonemap, hash, image files).
+// rt_rays.hip — what works without a frame: the ray-batch operators on the committed scene's tree (single-hit and multi-hit), the
+// hala_rtprog object over them, and the stand-alone helpers of the C ABI (environment distribution, tonemap, hash, image files).  The
+// other query batches are in rt_queries.hip and rt_bake.hip; all of them run inside a BatchScope (renderer_state.h).
 #include "renderer_state.h"
 
 extern "C" {
@@ -7,235 +8,58 @@ extern "C" {
 // ---- ray-batch operator ------------------------------------------------------------------------------------------------
 int hala_rt_trace_rays(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_hits, uint32_t count, int mode, uint64_t* d_counters, void* hip_stream) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
-  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");  // src/rt_renderer.rs:284
+  if (check_committed(r) != HALA_OK) return HALA_ERR;
   if (mode != 0 && mode != 1) RT_FAIL("Invalid trace mode.");
   if (count == 0) return HALA_OK;
   if (!d_rays || !d_hits) RT_FAIL("The ray batch is null!");
-  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : r->stream;
-  if (r->scratch.acquire(s) != HALA_OK) return HALA_ERR;  // stream-ordered behind the previous user of the renderer's scratch (include/halart.h)
-  RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
+  BatchScope scope = r->batch(hip_stream);
+  if (scope.open() != HALA_OK || scope.reset_work() != HALA_OK) return HALA_ERR;
+  hipStream_t s = scope.s;
   // counters: the kernel accumulates into the control block's 64-bit fields; copy them out if requested
   if (d_counters) RT_HIP(hipMemsetAsync(&r->d_ctl.ptr->totals.steps[mode][0], 0, 16, s));
   // RENDER_SPEC 4.2: far origins are re-based where the batch enters, and the distance comes back on the closest hits where it leaves —
   // the traversal launch in between sees ordinary rays.  (Growing the copy frees the old one, which waits for whoever still reads it.)
-  if (r->d_batch_rays.count < count) { RT_HIP(r->d_batch_rays.resize(count)); RT_HIP(r->d_batch_moved.resize(count)); }
+  RT_HIP(r->d_batch_rays.grow(count));
+  RT_HIP(r->d_batch_moved.grow(count));
   const SceneView sv = r->view();
   launch_rebase_batch(sv, d_rays, r->d_batch_rays.ptr, r->d_batch_moved.ptr, count, s);
   launch_trace_batch(r->lcfg, sv, r->d_batch_rays.ptr, d_hits, nullptr, count, r->d_batch_work.ptr, r->d_ctl.ptr, mode == 1, d_counters != nullptr, false, s);
   if (mode == 0) launch_unbase_hits(d_hits, r->d_batch_moved.ptr, count, s);
   if (d_counters) RT_HIP(hipMemcpyAsync(d_counters, &r->d_ctl.ptr->totals.steps[mode][0], 16, hipMemcpyDeviceToDevice, s));
-  if (!r->scratch.batch_done) RT_HIP(hipEventCreateWithFlags(&r->scratch.batch_done, hipEventDisableTiming));
-  RT_HIP(hipEventRecord(r->scratch.batch_done, s));
-  r->scratch.event = r->scratch.batch_done; r->scratch.stream = s;
-  RT_HIP(hipGetLastError());
-  return HALA_OK;
+  return scope.close();
 }
-// RENDER_SPEC 4.7: the contract of hala_rt_trace_rays (scratch, stream order, the renderer's own re-based copy of the batch) around the
-// multi-hit kernel; the distance a far ray was moved comes back on every record of its list
-int hala_rt_trace_rays_multi(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_hits, uint32_t* d_counts, uint32_t count, uint32_t k, void* hip_stream) {
+// RENDER_SPEC 4.7: the same (scope, the renderer's own re-based copy of the batch) around the multi-hit kernel; the distance a far ray was
+// moved comes back on every record of its list
+static int multi_check(hala_rt_renderer* r, const void* rays, const void* hits, uint32_t count, uint32_t k) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
-  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
-  if (k == 0 || k > HALA_MAX_MULTI_HITS) RT_FAIL("The multi-hit capacity must be 1.." + std::to_string(HALA_MAX_MULTI_HITS) + ".");
-  if (count == 0) return HALA_OK;
-  if (!d_rays || !d_hits) RT_FAIL("The ray batch is null!");
-  if ((uint64_t)count * k > (1ull << 32)) RT_FAIL("The multi-hit batch is too large.");
-  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : r->stream;
-  if (r->scratch.acquire(s) != HALA_OK) return HALA_ERR;
-  RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
-  if (r->d_batch_rays.count < count) { RT_HIP(r->d_batch_rays.resize(count)); RT_HIP(r->d_batch_moved.resize(count)); }
-  const SceneView sv = r->view();
-  launch_rebase_batch(sv, d_rays, r->d_batch_rays.ptr, r->d_batch_moved.ptr, count, s);
-  const bool fits = launch_trace_multi(r->lcfg, sv, r->cu_count, r->d_batch_rays.ptr, d_hits, d_counts, count, k, r->d_batch_work.ptr, s);
-  if (fits) launch_unbase_multi(d_hits, r->d_batch_moved.ptr, count, k, s);
-  if (!r->scratch.batch_done) RT_HIP(hipEventCreateWithFlags(&r->scratch.batch_done, hipEventDisableTiming));
-  RT_HIP(hipEventRecord(r->scratch.batch_done, s));
-  r->scratch.event = r->scratch.batch_done; r->scratch.stream = s;
-  if (!fits) RT_FAIL("The multi-hit traversal kernel does not fit on a compute unit.");
-  RT_HIP(hipGetLastError());
-  return HALA_OK;
-}
-int hala_rt_trace_rays_multi_host(hala_rt_renderer* r, const hala_ray* rays, hala_hit* hits, uint32_t* counts, uint32_t count, uint32_t k) {
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;
-  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
+  if (check_committed(r) != HALA_OK) return HALA_ERR;
   if (k == 0 || k > HALA_MAX_MULTI_HITS) RT_FAIL("The multi-hit capacity must be 1.." + std::to_string(HALA_MAX_MULTI_HITS) + ".");
   if (count == 0) return HALA_OK;
   if (!rays || !hits) RT_FAIL("The ray batch is null!");
   if ((uint64_t)count * k > (1ull << 32)) RT_FAIL("The multi-hit batch is too large.");
-  DeviceArray<hala_ray> d_rays;
-  DeviceArray<hala_hit> d_hits;
-  DeviceArray<uint32_t> d_counts;
-  RT_HIP(d_rays.upload(rays, count, r->stream));
-  RT_HIP(d_hits.resize((size_t)count * k));
-  if (counts) RT_HIP(d_counts.resize(count));
-  if (hala_rt_trace_rays_multi(r, d_rays.ptr, d_hits.ptr, counts ? d_counts.ptr : nullptr, count, k, r->stream) != HALA_OK) return HALA_ERR;
-  RT_HIP(hipMemcpyAsync(hits, d_hits.ptr, (size_t)count * k * sizeof(hala_hit), hipMemcpyDeviceToHost, r->stream));
-  if (counts) RT_HIP(hipMemcpyAsync(counts, d_counts.ptr, (size_t)count * 4, hipMemcpyDeviceToHost, r->stream));
-  RT_HIP(hipStreamSynchronize(r->stream));
   return HALA_OK;
 }
-// RENDER_SPEC 4.8: the contract of hala_rt_trace_rays (scratch, stream order) around the closest-point kernel.  Nothing is re-based: the
-// kernel reads the caller's queries.  d_counters (2 x uint64, or null): node visits and triangle tests of the batch.
-int hala_rt_closest_points_counted(hala_rt_renderer* r, const hala_point_query* d_queries, hala_closest_point* d_out, uint32_t count,
-                                   uint64_t* d_counters, void* hip_stream) {
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;
-  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
-  if (r->two_level) RT_FAIL("Closest-point queries are not built for two-level trees: commit the scene flattened (instancing = 0).");
+int hala_rt_trace_rays_multi(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_hits, uint32_t* d_counts, uint32_t count, uint32_t k, void* hip_stream) {
+  if (multi_check(r, d_rays, d_hits, count, k) != HALA_OK) return HALA_ERR;
   if (count == 0) return HALA_OK;
-  if (!d_queries || !d_out) RT_FAIL("The query batch is null!");
-  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : r->stream;
-  if (r->scratch.acquire(s) != HALA_OK) return HALA_ERR;
-  RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
-  if (d_counters) RT_HIP(hipMemsetAsync(d_counters, 0, 16, s));
-  const bool fits = launch_closest_point(r->lcfg, r->view(), r->cu_count, d_queries, d_out, count, r->d_batch_work.ptr,
-                                         reinterpret_cast<unsigned long long*>(d_counters), s);
-  if (!r->scratch.batch_done) RT_HIP(hipEventCreateWithFlags(&r->scratch.batch_done, hipEventDisableTiming));
-  RT_HIP(hipEventRecord(r->scratch.batch_done, s));
-  r->scratch.event = r->scratch.batch_done; r->scratch.stream = s;
-  if (!fits) RT_FAIL("The closest-point kernel does not fit on a compute unit.");
-  RT_HIP(hipGetLastError());
-  return HALA_OK;
-}
-int hala_rt_closest_points(hala_rt_renderer* r, const hala_point_query* d_queries, hala_closest_point* d_out, uint32_t count, void* hip_stream) {
-  return hala_rt_closest_points_counted(r, d_queries, d_out, count, nullptr, hip_stream);
-}
-int hala_rt_closest_points_host(hala_rt_renderer* r, const hala_point_query* queries, hala_closest_point* out, uint32_t count) {
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;
-  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
-  if (r->two_level) RT_FAIL("Closest-point queries are not built for two-level trees: commit the scene flattened (instancing = 0).");
-  if (count == 0) return HALA_OK;
-  if (!queries || !out) RT_FAIL("The query batch is null!");
-  DeviceArray<hala_point_query> d_queries;
-  DeviceArray<hala_closest_point> d_out;
-  RT_HIP(d_queries.upload(queries, count, r->stream));
-  RT_HIP(d_out.resize(count));
-  if (hala_rt_closest_points(r, d_queries.ptr, d_out.ptr, count, r->stream) != HALA_OK) return HALA_ERR;
-  RT_HIP(hipMemcpyAsync(out, d_out.ptr, (size_t)count * sizeof(hala_closest_point), hipMemcpyDeviceToHost, r->stream));
-  RT_HIP(hipStreamSynchronize(r->stream));
-  return HALA_OK;
-}
-// RENDER_SPEC 4.9.  Which distance kernel an automatic grid runs (DESIGN.md 28 has the measurements the rule rests on).  The per-wave
-// walk runs, in every lane, the union of what its 64 voxels need, and saves the wave its node and triangle fetches.  It wins where those
-// fetches come from memory (not a staged tree), where the band does not end a query early (it spans the scene box) and where the voxels
-// are fine against the scene: spacing * sqrt(triangles) <= 4.4 x the box's largest extent.  Everywhere else a voxel per lane.
-static uint32_t grid_auto_method(const SceneView& sv, const hala_distance_grid_desc* g) {
-  if (sv.staged) return 1u;
-  const float extent = std::max(sv.box_max[0] - sv.box_min[0], std::max(sv.box_max[1] - sv.box_min[1], sv.box_max[2] - sv.box_min[2]));
-  if (!(g->band >= extent)) return 1u;
-  return g->spacing * std::sqrt((float)sv.tri_count) <= 4.4f * extent ? 2u : 1u;
-}
-static int grid_check(hala_rt_renderer* r, const hala_distance_grid_desc* g, const void* distance) {
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;
-  if (!g) RT_FAIL("The distance grid description is null!");
-  if (!distance) RT_FAIL("The distance grid output is null!");
-  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
-  if (r->two_level) RT_FAIL("Distance grids are not built for two-level trees: commit the scene flattened (instancing = 0).");
-  for (int a = 0; a < 3; ++a)
-    if (g->dims[a] == 0 || g->dims[a] > 1024u) RT_FAIL("The distance grid's dims must be 1..1024 each.");
-  if (!(std::isfinite(g->spacing) && g->spacing > 0.0f)) RT_FAIL("The distance grid's spacing must be finite and positive.");
-  if (!(g->band >= 0.0f)) RT_FAIL("The distance grid's band must be >= 0 or +inf.");
-  if ((g->flags & ~7u) != 0u || ((g->flags >> HALA_GRID_METHOD_SHIFT) & 3u) == 3u) RT_FAIL("Unknown distance grid flags.");
-  return HALA_OK;
-}
-// The contract of hala_rt_trace_rays (scratch, stream order) around the row pass of a signed grid and the distance pass; the rows' bits
-// live in a buffer the renderer owns (growing it frees the old one, which waits for whoever still reads it).
-int hala_rt_distance_grid_counted(hala_rt_renderer* r, const hala_distance_grid_desc* desc, float* d_distance, uint32_t* d_prim, uint64_t* d_counters,
-                                  void* hip_stream) {
-  if (grid_check(r, desc, d_distance) != HALA_OK) return HALA_ERR;
-  GridView g{};
-  memcpy(g.origin, desc->origin, sizeof(g.origin));
-  g.spacing = desc->spacing; g.band = desc->band; g.nx = desc->dims[0]; g.ny = desc->dims[1]; g.nz = desc->dims[2];
-  g.words = (g.nx + 1u + 31u) / 32u;
-  const bool is_signed = (desc->flags & HALA_GRID_SIGNED) != 0u;
-  uint32_t method = (desc->flags >> HALA_GRID_METHOD_SHIFT) & 3u;
+  BatchScope scope = r->batch(hip_stream);
+  if (scope.open() != HALA_OK || scope.reset_work() != HALA_OK) return HALA_ERR;
+  RT_HIP(r->d_batch_rays.grow(count));
+  RT_HIP(r->d_batch_moved.grow(count));
   const SceneView sv = r->view();
-  if (method == 0u) method = grid_auto_method(sv, desc);
-  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : r->stream;
-  const size_t bit_words = (size_t)g.ny * g.nz * g.words;
-  if (is_signed && r->d_grid_bits.count < bit_words) RT_HIP(r->d_grid_bits.resize(bit_words));
-  if (r->scratch.acquire(s) != HALA_OK) return HALA_ERR;
-  unsigned long long* counters = reinterpret_cast<unsigned long long*>(d_counters);
-  if (d_counters) RT_HIP(hipMemsetAsync(d_counters, 0, 48, s));
-  bool fits = true;
-  if (is_signed) {
-    RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
-    RT_HIP(hipMemsetAsync(r->d_grid_bits.ptr, 0, bit_words * 4, s));
-    fits = launch_grid_rows(r->lcfg, sv, r->cu_count, g, r->d_grid_bits.ptr, r->d_batch_work.ptr, counters, s);
-  }
-  if (fits) {
-    RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
-    fits = launch_distance_grid(r->lcfg, sv, r->cu_count, g, method, d_distance, d_prim, is_signed ? r->d_grid_bits.ptr : nullptr, r->d_batch_work.ptr, counters, s);
-  }
-  if (!r->scratch.batch_done) RT_HIP(hipEventCreateWithFlags(&r->scratch.batch_done, hipEventDisableTiming));
-  RT_HIP(hipEventRecord(r->scratch.batch_done, s));
-  r->scratch.event = r->scratch.batch_done; r->scratch.stream = s;
-  if (!fits) RT_FAIL("The distance grid kernels do not fit on a compute unit.");
-  RT_HIP(hipGetLastError());
-  return HALA_OK;
+  launch_rebase_batch(sv, d_rays, r->d_batch_rays.ptr, r->d_batch_moved.ptr, count, scope.s);
+  const bool fits = launch_trace_multi(r->lcfg, sv, r->cu_count, r->d_batch_rays.ptr, d_hits, d_counts, count, k, r->d_batch_work.ptr, scope.s);
+  if (fits) launch_unbase_multi(d_hits, r->d_batch_moved.ptr, count, k, scope.s);
+  return scope.close(fits ? nullptr : "The multi-hit traversal kernel does not fit on a compute unit.");
 }
-int hala_rt_distance_grid(hala_rt_renderer* r, const hala_distance_grid_desc* desc, float* d_distance, uint32_t* d_prim, void* hip_stream) {
-  return hala_rt_distance_grid_counted(r, desc, d_distance, d_prim, nullptr, hip_stream);
-}
-int hala_rt_distance_grid_host(hala_rt_renderer* r, const hala_distance_grid_desc* desc, float* distance, uint32_t* prim) {
-  if (grid_check(r, desc, distance) != HALA_OK) return HALA_ERR;
-  const size_t n = (size_t)desc->dims[0] * desc->dims[1] * desc->dims[2];
-  DeviceArray<float> d_distance;
-  DeviceArray<uint32_t> d_prim;
-  RT_HIP(d_distance.resize(n));
-  if (prim) RT_HIP(d_prim.resize(n));
-  if (hala_rt_distance_grid(r, desc, d_distance.ptr, prim ? d_prim.ptr : nullptr, r->stream) != HALA_OK) return HALA_ERR;
-  RT_HIP(hipMemcpyAsync(distance, d_distance.ptr, n * 4, hipMemcpyDeviceToHost, r->stream));
-  if (prim) RT_HIP(hipMemcpyAsync(prim, d_prim.ptr, n * 4, hipMemcpyDeviceToHost, r->stream));
-  RT_HIP(hipStreamSynchronize(r->stream));
-  return HALA_OK;
-}
-// RENDER_SPEC 4.10: the contract of hala_rt_trace_rays (scratch, stream order) around the occlusion kernels.  Nothing is copied or
-// re-based ahead of the launch: the rays are made, far origins included, in the lanes that trace them.  Without the caller's mask array
-// the words live in a buffer the renderer owns (growing it frees the old one, which waits for whoever still reads it).
-static int occlusion_check(hala_rt_renderer* r, const void* samples, const void* out, uint32_t count, uint32_t rays) {
-  if (ensure_device(r) != HALA_OK) return HALA_ERR;
-  if (!r->committed) RT_FAIL("The top level acceleration structure is none!");
-  if (rays == 0 || rays > HALA_MAX_OCCLUSION_RAYS) RT_FAIL("The occlusion ray count must be 1.." + std::to_string(HALA_MAX_OCCLUSION_RAYS) + ".");
+int hala_rt_trace_rays_multi_host(hala_rt_renderer* r, const hala_ray* rays, hala_hit* hits, uint32_t* counts, uint32_t count, uint32_t k) {
+  if (multi_check(r, rays, hits, count, k) != HALA_OK) return HALA_ERR;
   if (count == 0) return HALA_OK;
-  if (!samples || !out) RT_FAIL("The occlusion batch is null!");
-  if ((uint64_t)count * rays >= (1ull << 32)) RT_FAIL("The occlusion batch is too large.");
-  return HALA_OK;
-}
-int hala_rt_occlusion(hala_rt_renderer* r, const hala_occlusion_sample* d_samples, hala_occlusion* d_out, uint32_t* d_masks, uint32_t count, uint32_t rays,
-                      uint32_t seed, void* hip_stream) {
-  if (occlusion_check(r, d_samples, d_out, count, rays) != HALA_OK) return HALA_ERR;
-  if (count == 0) return HALA_OK;
-  hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : r->stream;
-  const size_t mask_words = (size_t)count * ((rays + 31u) / 32u);
-  if (!d_masks) {
-    if (r->d_occlusion_masks.count < mask_words) RT_HIP(r->d_occlusion_masks.resize(mask_words));
-    d_masks = r->d_occlusion_masks.ptr;
-  }
-  if (r->scratch.acquire(s) != HALA_OK) return HALA_ERR;
-  RT_HIP(hipMemsetAsync(r->d_batch_work.ptr, 0, sizeof(WorkCounters), s));
-  RT_HIP(hipMemsetAsync(d_masks, 0, mask_words * 4, s));
-  launch_trace_occlusion(r->lcfg, r->view(), d_samples, d_out, d_masks, count, rays, seed, r->d_batch_work.ptr, s);
-  if (!r->scratch.batch_done) RT_HIP(hipEventCreateWithFlags(&r->scratch.batch_done, hipEventDisableTiming));
-  RT_HIP(hipEventRecord(r->scratch.batch_done, s));
-  r->scratch.event = r->scratch.batch_done; r->scratch.stream = s;
-  RT_HIP(hipGetLastError());
-  return HALA_OK;
-}
-int hala_rt_occlusion_host(hala_rt_renderer* r, const hala_occlusion_sample* samples, hala_occlusion* out, uint32_t* masks, uint32_t count, uint32_t rays,
-                           uint32_t seed) {
-  if (occlusion_check(r, samples, out, count, rays) != HALA_OK) return HALA_ERR;
-  if (count == 0) return HALA_OK;
-  const size_t mask_words = (size_t)count * ((rays + 31u) / 32u);
-  DeviceArray<hala_occlusion_sample> d_samples;
-  DeviceArray<hala_occlusion> d_out;
-  DeviceArray<uint32_t> d_masks;
-  RT_HIP(d_samples.upload(samples, count, r->stream));
-  RT_HIP(d_out.resize(count));
-  if (masks) RT_HIP(d_masks.resize(mask_words));
-  if (hala_rt_occlusion(r, d_samples.ptr, d_out.ptr, masks ? d_masks.ptr : nullptr, count, rays, seed, r->stream) != HALA_OK) return HALA_ERR;
-  RT_HIP(hipMemcpyAsync(out, d_out.ptr, (size_t)count * sizeof(hala_occlusion), hipMemcpyDeviceToHost, r->stream));
-  if (masks) RT_HIP(hipMemcpyAsync(masks, d_masks.ptr, mask_words * 4, hipMemcpyDeviceToHost, r->stream));
-  RT_HIP(hipStreamSynchronize(r->stream));
-  return HALA_OK;
+  DeviceArray<hala_ray> d_rays;
+  HostOut<hala_hit> d_hits(hits, (size_t)count * k);
+  HostOut<uint32_t> d_counts(counts, count);
+  RT_HIP(d_rays.upload(rays, count, r->stream));
+  return host_form(r->stream, [&] { return hala_rt_trace_rays_multi(r, d_rays.ptr, d_hits.ptr(), d_counts.ptr(), count, k, r->stream); }, d_hits, d_counts);
 }
 int hala_rt_trace_rays_indirect(hala_rt_renderer* r, const hala_ray* d_rays, hala_hit* d_hits, const uint32_t* d_indirect, int mode, void* hip_stream) {
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
@@ -252,17 +76,12 @@ int hala_rt_trace_rays_host(hala_rt_renderer* r, const hala_ray* rays, hala_hit*
   if (ensure_device(r) != HALA_OK) return HALA_ERR;
   if (count == 0) return HALA_OK;
   DeviceArray<hala_ray> d_rays;
-  DeviceArray<hala_hit> d_hits;
-  DeviceArray<uint64_t> d_ctr;
+  HostOut<hala_hit> d_hits(hits, count);
+  HostOut<uint64_t> d_ctr(counters, 2);
   RT_HIP(d_rays.upload(rays, count, r->stream));
-  RT_HIP(d_hits.resize(count));
-  if (counters) RT_HIP(d_ctr.resize(2));
-  if (hala_rt_trace_rays(r, d_rays.ptr, d_hits.ptr, count, mode, counters ? d_ctr.ptr : nullptr, r->stream) != HALA_OK) return HALA_ERR;
-  RT_HIP(hipMemcpyAsync(hits, d_hits.ptr, (size_t)count * sizeof(hala_hit), hipMemcpyDeviceToHost, r->stream));
-  if (counters) RT_HIP(hipMemcpyAsync(counters, d_ctr.ptr, 16, hipMemcpyDeviceToHost, r->stream));
-  RT_HIP(hipStreamSynchronize(r->stream));
-  return HALA_OK;
+  return host_form(r->stream, [&] { return hala_rt_trace_rays(r, d_rays.ptr, d_hits.ptr(), count, mode, d_ctr.ptr(), r->stream); }, d_hits, d_ctr);
 }
+
 
 // ---- stand-alone pieces ---------------------------------------------------------------------------------------------------
 int hala_envmap_build_distribution(int device_ordinal, const float* rgba32f, uint32_t width, uint32_t height, float* total_sum, float* marginal, float* conditional) {

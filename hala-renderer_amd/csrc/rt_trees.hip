@@ -342,8 +342,8 @@ static int quality_measure(hala_rt_renderer* r, const std::vector<uint32_t>& whi
   QualityState& q = r->quality;
   if (which.empty()) return HALA_OK;
   const size_t words = q.trees.size() * 3u;
-  if (q.d_out.count < words) RT_HIP(q.d_out.resize(words));
-  if (q.d_partials.count < kTreeCostPartialWords) RT_HIP(q.d_partials.resize(kTreeCostPartialWords));
+  RT_HIP(q.d_out.grow(words));
+  RT_HIP(q.d_partials.grow(kTreeCostPartialWords));
   if (q.h_words < words) {
     if (q.h_out) (void)hipHostFree(q.h_out);
     q.h_out = nullptr; q.h_words = 0;

@@ -176,19 +176,13 @@ __global__ void __launch_bounds__(256) k_unbase_multi(float4* __restrict__ hits,
   if (reinterpret_cast<const uint32_t*>(t)[3] != kAbsent) *t = *t + moved[i / k];
 }
 
-// The kernel's own LDS: the per-lane stacks, and a staged tree behind them
-static size_t multi_lds_bytes(const SceneView& sv, TreeForm tree) {
-  const size_t stacks = (size_t)traverse_stack_lds_levels(tree) * kTraverseThreads * 8;
-  return tree == TreeForm::Staged ? stacks + (size_t)sv.lds_nodes * 64 + (size_t)sv.lds_tris * 48 : stacks;
-}
 bool launch_trace_multi(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_count, const hala_ray* rays, hala_hit* hits, uint32_t* counts,
                         uint32_t n, uint32_t k, WorkCounters* work, hipStream_t s) {
   const TreeForm tree = tree_form(sv);
-  const size_t smem = multi_lds_bytes(sv, tree);
+  const size_t smem = query_lds_bytes(sv, tree, kTraverseThreads);
   const uint32_t per_cu = tree_blocks_per_cu([](auto STAGED, auto INST) { return k_trace_multi<STAGED, INST>; }, tree, kTraverseThreads, smem);
   if (per_cu == 0u) return false;
-  // the spill area holds one slice per lane of lc.persistent_blocks workgroups: never a larger grid than that
-  const uint32_t blocks = std::min(lc.persistent_blocks, cu_count * std::min(per_cu, 8u));
+  const uint32_t blocks = query_blocks(lc, cu_count, per_cu);
   with_flags([&](auto STAGED, auto INST) {
     if constexpr (!(STAGED && INST))
       hipLaunchKernelGGL((k_trace_multi<STAGED, INST>), dim3(blocks), dim3(kTraverseThreads), smem, s, sv, rays, reinterpret_cast<float4*>(hits), counts, n, k,

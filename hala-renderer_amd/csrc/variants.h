@@ -1,6 +1,7 @@
 // variants.h — how launch-time flags become kernel template arguments, for the launchers of the six flag-dispatched kernel families
 // (trace_closest.hip, trace_shadow.hip, shade.hip, resolve.hip), and what the variant ledger (variants.cpp) records of it.  Host code only.
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <tuple>
 #include <type_traits>
@@ -32,6 +33,21 @@ static uint32_t tree_blocks_per_cu(F&& kernel_of, TreeForm tree, int threads, si
   return e == hipSuccess && n > 0 ? (uint32_t)n : 0u;
 }
 uint32_t trace_shadow_blocks_per_cu(size_t dynamic_lds_bytes, TreeForm tree);
+
+// The launch shape of the query kernels that size themselves (trace_multi.hip, closest_point.hip, distance_grid.hip), unlike the ones that
+// run in lc's grid and LDS.  Their LDS: the per-lane stacks, and a staged tree behind them
+static size_t query_lds_bytes(const SceneView& sv, TreeForm tree, int threads) {
+  const size_t stacks = (size_t)traverse_stack_lds_levels(tree) * threads * 8;
+  return tree == TreeForm::Staged ? stacks + (size_t)sv.lds_nodes * 64 + (size_t)sv.lds_tris * 48 : stacks;
+}
+// Their grid: what is resident, within lc.persistent_blocks — the spill area holds one slice per lane of that many workgroups
+static uint32_t query_blocks(const LaunchCfg& lc, uint32_t cu_count, uint32_t per_cu) { return std::min(lc.persistent_blocks, cu_count * std::min(per_cu, 8u)); }
+// Their occupancy where counting is a template argument: that of kernel_of(STAGED, COUNT), the instantiation the launch will run
+template <class F>
+static uint32_t counted_blocks_per_cu(F&& kernel_of, bool count, TreeForm tree, int threads, size_t dynamic_lds_bytes) {
+  return count ? tree_blocks_per_cu([&](auto STAGED, auto) { return kernel_of(STAGED, std::true_type{}); }, tree, threads, dynamic_lds_bytes)
+               : tree_blocks_per_cu([&](auto STAGED, auto) { return kernel_of(STAGED, std::false_type{}); }, tree, threads, dynamic_lds_bytes);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // The variant ledger (hala_rt_variant_ledger): which instantiations of the six flag-dispatched kernel families exist and which of them

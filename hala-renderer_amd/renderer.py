@@ -533,6 +533,28 @@ class HalaRenderer:
         self._check(self._lib.hala_rt_trace_rays_multi(self._h, C.c_void_p(d_rays), C.c_void_p(d_hits), C.c_void_p(d_counts), C.c_uint32(count), C.c_uint32(k),
                                                        C.c_void_p(stream)))
 
+    # -- what the device forms of the query batches share: a tensor or a pointer in, a checked output, a count -----------
+    @staticmethod
+    def _device_address(x):
+        """the device address of a tensor, of a pointer, or 0 for None"""
+        return x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0)
+
+    @staticmethod
+    def _device_count(x, itemsize, count):
+        """the records of a device batch: `count` where given, else what the tensor holds"""
+        if count is not None:
+            return count
+        if not hasattr(x, "data_ptr"):
+            raise ValueError("a device pointer needs `count`")
+        return x.numel() * x.element_size() // itemsize
+
+    @staticmethod
+    def _device_out(x, nbytes, too_small):
+        """the device address of an output tensor (or pointer, or None), a tensor checked against the bytes the call writes"""
+        if hasattr(x, "data_ptr") and x.numel() * x.element_size() < nbytes:
+            raise ValueError(too_small)
+        return HalaRenderer._device_address(x)
+
     def closest_points(self, points, radius=np.inf, out=None, count=None, stream: int = 0, d_counters: int = 0):
         """RENDER_SPEC 4.8: the nearest surface point of every query point within `radius` (a scalar or one per point), as a structured
         array of A.CLOSEST_POINT_DTYPE (distance, u, v, prim, point, region; a miss has distance -1 and prim 0xffffffff).  `points` is
@@ -543,13 +565,9 @@ class HalaRenderer:
         if out is not None or isinstance(points, int) or hasattr(points, "data_ptr"):
             if out is None:
                 raise ValueError("the device form needs `out`")
-            d_q, d_o = (x.data_ptr() if hasattr(x, "data_ptr") else int(x) for x in (points, out))
-            if count is None:
-                if not hasattr(points, "data_ptr"):
-                    raise ValueError("a device pointer needs `count`")
-                count = points.numel() * points.element_size() // A.POINT_QUERY_DTYPE.itemsize
-            if hasattr(out, "data_ptr") and out.numel() * out.element_size() < count * A.CLOSEST_POINT_DTYPE.itemsize:
-                raise ValueError("`out` is too small for the batch")
+            d_q = self._device_address(points)
+            count = self._device_count(points, A.POINT_QUERY_DTYPE.itemsize, count)
+            d_o = self._device_out(out, count * A.CLOSEST_POINT_DTYPE.itemsize, "`out` is too small for the batch")
             if d_counters:
                 self._check(self._lib.hala_rt_closest_points_counted(self._h, C.c_void_p(d_q), C.c_void_p(d_o), C.c_uint32(count), C.c_void_p(d_counters),
                                                                      C.c_void_p(stream)))
@@ -581,10 +599,7 @@ class HalaRenderer:
         desc = A.DistanceGridDesc((C.c_float * 3)(*[float(x) for x in origin]), float(spacing), (C.c_uint32 * 3)(nx, ny, nz), float(band),
                                   (A.GRID_SIGNED if signed else 0) | (int(method or 0) << A.GRID_METHOD_SHIFT))
         if out is not None:
-            d_o, d_p = (x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0) for x in (out, out_prim))
-            for x in (out, out_prim):
-                if hasattr(x, "data_ptr") and x.numel() * x.element_size() < nx * ny * nz * 4:
-                    raise ValueError("the output is too small for the grid")
+            d_o, d_p = (self._device_out(x, nx * ny * nz * 4, "the output is too small for the grid") for x in (out, out_prim))
             if d_counters:
                 self._check(self._lib.hala_rt_distance_grid_counted(self._h, C.byref(desc), C.c_void_p(d_o), C.c_void_p(d_p), C.c_void_p(d_counters),
                                                                     C.c_void_p(stream)))
@@ -625,15 +640,10 @@ class HalaRenderer:
         if out is not None or isinstance(points, int) or hasattr(points, "data_ptr"):
             if out is None:
                 raise ValueError("the device form needs `out`")
-            d_s, d_o, d_m = (x.data_ptr() if hasattr(x, "data_ptr") else int(x or 0) for x in (points, out, out_masks))
-            if count is None:
-                if not hasattr(points, "data_ptr"):
-                    raise ValueError("a device pointer needs `count`")
-                count = points.numel() * points.element_size() // A.OCCLUSION_SAMPLE_DTYPE.itemsize
-            if hasattr(out, "data_ptr") and out.numel() * out.element_size() < count * A.OCCLUSION_DTYPE.itemsize:
-                raise ValueError("`out` is too small for the batch")
-            if hasattr(out_masks, "data_ptr") and out_masks.numel() * out_masks.element_size() < count * words * 4:
-                raise ValueError("`out_masks` is too small for the batch")
+            d_s = self._device_address(points)
+            count = self._device_count(points, A.OCCLUSION_SAMPLE_DTYPE.itemsize, count)
+            d_o = self._device_out(out, count * A.OCCLUSION_DTYPE.itemsize, "`out` is too small for the batch")
+            d_m = self._device_out(out_masks, count * words * 4, "`out_masks` is too small for the batch")
             self._check(self._lib.hala_rt_occlusion(self._h, C.c_void_p(d_s), C.c_void_p(d_o), C.c_void_p(d_m), C.c_uint32(count), C.c_uint32(rays),
                                                     C.c_uint32(seed), C.c_void_p(stream)))
             return None
@@ -659,14 +669,20 @@ class HalaRenderer:
         flags = (A.BAKE_SHADING_NORMAL if shading_normal else 0) | (A.BAKE_FLIP_NORMAL if flip else 0)
         return A.BakeDesc(int(instance), int(width), int(height), flags, float(self.ray_eps() if bias is None else bias), float(reach), int(margin))
 
-    @staticmethod
-    def _bake_device_out(x, count, itemsize, name):
-        """the device address of an output tensor (or pointer), checked against the map's size"""
-        if hasattr(x, "data_ptr"):
-            if x.numel() * x.element_size() < count * itemsize:
-                raise ValueError(f"`{name}` is too small for the map")
-            return x.data_ptr()
-        return int(x or 0)
+    def _bake(self, fn, args, record_dtype, width, height, out, out_texels, stream):
+        """What the four bake_* methods do once their description is made.  fn: the library's device form (its host form is fn +
+        "_host"); args: what both take between the handle and the outputs; record_dtype: of the first output.  Host form: (records,
+        texels) shaped (height, width); device form (out is not None): launched on `stream`, nothing returned."""
+        count = int(width) * int(height)
+        if out is not None:
+            d_o = self._device_out(out, count * record_dtype.itemsize, "`out` is too small for the map")
+            d_t = self._device_out(out_texels, count * A.BAKE_TEXEL_DTYPE.itemsize, "`out_texels` is too small for the map")
+            self._check(getattr(self._lib, fn)(self._h, *args, C.c_void_p(d_o), C.c_void_p(d_t), C.c_void_p(stream)))
+            return None
+        rec = np.empty(max(count, 0), dtype=record_dtype)
+        texels = np.empty(max(count, 0), dtype=A.BAKE_TEXEL_DTYPE)
+        self._check(getattr(self._lib, fn + "_host")(self._h, *args, C.c_void_p(rec.ctypes.data), C.c_void_p(texels.ctypes.data)))
+        return rec.reshape(int(height), int(width)), texels.reshape(int(height), int(width))
 
     def bake_samples(self, instance, width, height, *, shading_normal=False, flip=False, bias=None, reach=np.inf, out=None, out_texels=None,
                      stream: int = 0):
@@ -678,16 +694,7 @@ class HalaRenderer:
         Device form: `out` is a device tensor (or pointer) of width * height 32-B samples and `out_texels` one of 16-B records or None;
         the map is launched on `stream` and nothing is returned."""
         d = self._bake_desc(instance, width, height, shading_normal, flip, bias, reach, 0)
-        count = int(width) * int(height)
-        if out is not None:
-            d_s = self._bake_device_out(out, count, A.OCCLUSION_SAMPLE_DTYPE.itemsize, "out")
-            d_t = self._bake_device_out(out_texels, count, A.BAKE_TEXEL_DTYPE.itemsize, "out_texels")
-            self._check(self._lib.hala_rt_bake_samples(self._h, C.byref(d), C.c_void_p(d_s), C.c_void_p(d_t), C.c_void_p(stream)))
-            return None
-        samples = np.empty(max(count, 0), dtype=A.OCCLUSION_SAMPLE_DTYPE)
-        texels = np.empty(max(count, 0), dtype=A.BAKE_TEXEL_DTYPE)
-        self._check(self._lib.hala_rt_bake_samples_host(self._h, C.byref(d), C.c_void_p(samples.ctypes.data), C.c_void_p(texels.ctypes.data)))
-        return samples.reshape(int(height), int(width)), texels.reshape(int(height), int(width))
+        return self._bake("hala_rt_bake_samples", (C.byref(d),), A.OCCLUSION_SAMPLE_DTYPE, width, height, out, out_texels, stream)
 
     def bake_occlusion(self, instance, width, height, rays, seed=0, *, margin=0, shading_normal=False, flip=False, bias=None, reach=np.inf, out=None,
                        out_texels=None, stream: int = 0):
@@ -698,18 +705,7 @@ class HalaRenderer:
         Device form: `out` is a device tensor (or pointer) of width * height 16-B records and `out_texels` one of 16-B texel records or
         None; the bake is launched on `stream`, nothing leaves the device and nothing is returned."""
         d = self._bake_desc(instance, width, height, shading_normal, flip, bias, reach, margin)
-        count = int(width) * int(height)
-        if out is not None:
-            d_o = self._bake_device_out(out, count, A.OCCLUSION_DTYPE.itemsize, "out")
-            d_t = self._bake_device_out(out_texels, count, A.BAKE_TEXEL_DTYPE.itemsize, "out_texels")
-            self._check(self._lib.hala_rt_bake_occlusion(self._h, C.byref(d), C.c_uint32(rays), C.c_uint32(seed), C.c_void_p(d_o), C.c_void_p(d_t),
-                                                         C.c_void_p(stream)))
-            return None
-        rec = np.empty(max(count, 0), dtype=A.OCCLUSION_DTYPE)
-        texels = np.empty(max(count, 0), dtype=A.BAKE_TEXEL_DTYPE)
-        self._check(self._lib.hala_rt_bake_occlusion_host(self._h, C.byref(d), C.c_uint32(rays), C.c_uint32(seed), C.c_void_p(rec.ctypes.data),
-                                                          C.c_void_p(texels.ctypes.data)))
-        return rec.reshape(int(height), int(width)), texels.reshape(int(height), int(width))
+        return self._bake("hala_rt_bake_occlusion", (C.byref(d), C.c_uint32(rays), C.c_uint32(seed)), A.OCCLUSION_DTYPE, width, height, out, out_texels, stream)
 
     @staticmethod
     def _bake_charts(charts):
@@ -736,18 +732,8 @@ class HalaRenderer:
         the device form is bake_samples()'s."""
         table = self._bake_charts(charts)
         d = self._bake_atlas_desc(table, width, height, bias, reach, 0)
-        count = int(width) * int(height)
-        if out is not None:
-            d_s = self._bake_device_out(out, count, A.OCCLUSION_SAMPLE_DTYPE.itemsize, "out")
-            d_t = self._bake_device_out(out_texels, count, A.BAKE_TEXEL_DTYPE.itemsize, "out_texels")
-            self._check(self._lib.hala_rt_bake_atlas_samples(self._h, C.byref(d), C.c_void_p(table.ctypes.data), C.c_void_p(d_s), C.c_void_p(d_t),
-                                                             C.c_void_p(stream)))
-            return None
-        samples = np.empty(max(count, 0), dtype=A.OCCLUSION_SAMPLE_DTYPE)
-        texels = np.empty(max(count, 0), dtype=A.BAKE_TEXEL_DTYPE)
-        self._check(self._lib.hala_rt_bake_atlas_samples_host(self._h, C.byref(d), C.c_void_p(table.ctypes.data), C.c_void_p(samples.ctypes.data),
-                                                              C.c_void_p(texels.ctypes.data)))
-        return samples.reshape(int(height), int(width)), texels.reshape(int(height), int(width))
+        return self._bake("hala_rt_bake_atlas_samples", (C.byref(d), C.c_void_p(table.ctypes.data)), A.OCCLUSION_SAMPLE_DTYPE, width, height, out, out_texels,
+                          stream)
 
     def bake_atlas_occlusion(self, charts, width, height, rays, seed=0, *, margin=0, bias=None, reach=np.inf, out=None, out_texels=None, stream: int = 0):
         """RENDER_SPEC 4.12: the ambient-occlusion atlas of the charted instances: what occlusion() answers, with `rays` and `seed`, for
@@ -756,18 +742,8 @@ class HalaRenderer:
         (height, width) as bake_occlusion() does; the device form is bake_occlusion()'s."""
         table = self._bake_charts(charts)
         d = self._bake_atlas_desc(table, width, height, bias, reach, margin)
-        count = int(width) * int(height)
-        if out is not None:
-            d_o = self._bake_device_out(out, count, A.OCCLUSION_DTYPE.itemsize, "out")
-            d_t = self._bake_device_out(out_texels, count, A.BAKE_TEXEL_DTYPE.itemsize, "out_texels")
-            self._check(self._lib.hala_rt_bake_atlas_occlusion(self._h, C.byref(d), C.c_void_p(table.ctypes.data), C.c_uint32(rays), C.c_uint32(seed),
-                                                               C.c_void_p(d_o), C.c_void_p(d_t), C.c_void_p(stream)))
-            return None
-        rec = np.empty(max(count, 0), dtype=A.OCCLUSION_DTYPE)
-        texels = np.empty(max(count, 0), dtype=A.BAKE_TEXEL_DTYPE)
-        self._check(self._lib.hala_rt_bake_atlas_occlusion_host(self._h, C.byref(d), C.c_void_p(table.ctypes.data), C.c_uint32(rays), C.c_uint32(seed),
-                                                                C.c_void_p(rec.ctypes.data), C.c_void_p(texels.ctypes.data)))
-        return rec.reshape(int(height), int(width)), texels.reshape(int(height), int(width))
+        return self._bake("hala_rt_bake_atlas_occlusion", (C.byref(d), C.c_void_p(table.ctypes.data), C.c_uint32(rays), C.c_uint32(seed)), A.OCCLUSION_DTYPE,
+                          width, height, out, out_texels, stream)
 
     def bvh_info(self) -> A.BvhInfo:
         i = A.BvhInfo()
