@@ -174,6 +174,14 @@ class BakeAtlasDesc(C.Structure):  # hala_bake_atlas_desc, 24 B
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("bias", C.c_float), ("reach", C.c_float), ("margin", C.c_uint32), ("chart_count", C.c_uint32)]
 
 
+class BakeTransferDesc(C.Structure):  # hala_bake_transfer_desc, 16 B (RENDER_SPEC 4.13)
+    _fields_ = [("front", C.c_float), ("back", C.c_float), ("flags", C.c_uint32), ("target_count", C.c_uint32)]
+
+
+class BakeTransferHit(C.Structure):  # hala_bake_transfer_hit, 32 B
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("prim", C.c_uint32), ("normal", C.c_float * 3), ("height", C.c_float)]
+
+
 class RtInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32)]
 
@@ -369,6 +377,8 @@ PROTOTYPES = {
     "hala_rt_bake_atlas_samples_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "hala_rt_bake_atlas_occlusion": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "hala_rt_bake_atlas_occlusion_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
+    "hala_rt_bake_transfer": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "hala_rt_bake_transfer_host": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "hala_rtprog_trace_rays_multi": ([C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int),
     "hala_denoise_default_params": ([C.POINTER(DenoiseParams)], None),
     "hala_rt_denoise": ([C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(C.c_float)], C.c_int),
@@ -469,6 +479,8 @@ OCCLUSION_DTYPE = _np.dtype([("visibility", "<f4"), ("bent", "<f4", 3)])
 BAKE_TEXEL_DTYPE = _np.dtype([("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("source", "<u4")])
 # RENDER_SPEC 4.12: hala_bake_chart (24 B)
 BAKE_CHART_DTYPE = _np.dtype([("instance", "<u4"), ("flags", "<u4"), ("scale", "<f4", 2), ("offset", "<f4", 2)])
+# RENDER_SPEC 4.13: hala_bake_transfer_hit (32 B)
+BAKE_TRANSFER_HIT_DTYPE = _np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"), ("normal", "<f4", 3), ("height", "<f4")])
 VERTEX_DTYPE = _np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("tex_coord", "<f4", 2)])
 
 # every symbol include/halart.h declares (tests/test_abi.py checks the .so exports all of them)
@@ -521,6 +533,7 @@ EXPORTS = [
     "hala_rt_occlusion", "hala_rt_occlusion_host",
     "hala_rt_bake_samples", "hala_rt_bake_samples_host", "hala_rt_bake_occlusion", "hala_rt_bake_occlusion_host",
     "hala_rt_bake_atlas_samples", "hala_rt_bake_atlas_samples_host", "hala_rt_bake_atlas_occlusion", "hala_rt_bake_atlas_occlusion_host",
+    "hala_rt_bake_transfer", "hala_rt_bake_transfer_host",
 ]
 MAX_MULTI_HITS = 16  # HALA_MAX_MULTI_HITS (RENDER_SPEC 4.7)
 MAX_OCCLUSION_RAYS = 256  # HALA_MAX_OCCLUSION_RAYS (RENDER_SPEC 4.10)

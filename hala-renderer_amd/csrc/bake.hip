@@ -11,6 +11,7 @@
 // Bake atlases (RENDER_SPEC 4.12) put several instances into one map, each through a chart (scale, offset, flags): k_bake_atlas_count /
 // _cover / _sample are the first three kernels with the chart between the UVs and the corners, and k_bake_list_count / k_bake_list turn
 // the ownership words into the list of owned texels that the listed occlusion pass of occlusion.hip traces.
+// Transfer bakes (RENDER_SPEC 4.13) use the rasteriser as it is and k_bake_dilate_transfer, the dilation on their 32-B records.
 // The owner map is tiled 8 x 8 (a block is 256 B: two lines, one atomic instruction per wave step); its layout is not observable.
 // The library is built with -ffp-contract=off: the only fused operations are the ones written as __fmaf_rn, here the three of `point`
 // and those inside dot3 / cross3 / transform_normal (shading.h, rt_math.h), which the spec names.
@@ -386,6 +387,48 @@ __global__ void __launch_bounds__(256) k_bake_dilate(BakeView bv, const uint32_t
   if (texels) texels[i].w = best_i;
 }
 
+// RENDER_SPEC 4.13, dilation: k_bake_dilate's rule and search on the 32-B records of a transfer bake (both halves of the chosen texel's
+// record are copied).  A kernel of its own and not a template over the record: the 4.11 kernel is to compile as it did (the note above
+// k_bake_atlas_count).
+__global__ void __launch_bounds__(256) k_bake_dilate_transfer(BakeView bv, const uint32_t* __restrict__ owner, const unsigned long long* __restrict__ bits,
+                                                              float4* __restrict__ out, uint4* __restrict__ texels) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= bv.width * bv.height) return;
+  const int y = (int)(i / bv.width), x = (int)(i - (uint32_t)y * bv.width);
+  if (owner[bake_tiled(bv, (uint32_t)x, (uint32_t)y)] != kAbsent) return;
+  const int w = (int)bv.width, h = (int)bv.height, m = (int)bv.margin;
+  {
+    const int wx0 = max(x - m, 0), wx1 = min(x + m, w - 1), wy0 = max(y - m, 0), wy1 = min(y + m, h - 1);
+    bool any = false;
+    for (int by = wy0 >> 3; by <= wy1 >> 3; ++by) {
+      const int r0 = max(wy0 - (by << 3), 0), r1 = min(wy1 - (by << 3), 7);  // the block's rows inside the window
+      const unsigned long long rows = (r1 == 7 ? ~0ull : (1ull << ((r1 + 1) << 3)) - 1ull) & ~((1ull << (r0 << 3)) - 1ull);
+      for (int bx = wx0 >> 3; bx <= wx1 >> 3; ++bx) {
+        const int c0 = max(wx0 - (bx << 3), 0), c1 = min(wx1 - (bx << 3), 7);
+        const unsigned long long cols = (unsigned long long)(((1u << (c1 + 1)) - 1u) & ~((1u << c0) - 1u)) * 0x0101010101010101ull;
+        any = any || (bits[(size_t)by * bv.blocks_x + (size_t)bx] & rows & cols) != 0ull;
+      }
+    }
+    if (!any) return;
+  }
+  uint32_t best_d = 0xffffffffu, best_i = kAbsent;
+  const auto look = [&](int xx, int yy) {
+    if (xx < 0 || yy < 0 || xx >= w || yy >= h) return;
+    if (owner[bake_tiled(bv, (uint32_t)xx, (uint32_t)yy)] == kAbsent) return;
+    const uint32_t d = (uint32_t)((xx - x) * (xx - x) + (yy - y) * (yy - y)), idx = (uint32_t)yy * bv.width + (uint32_t)xx;
+    if (d < best_d || (d == best_d && idx < best_i)) { best_d = d; best_i = idx; }
+  };
+  for (int r = 1; r <= m; ++r) {
+    if (best_d < (uint32_t)(r * r)) break;
+    for (int k = -r; k <= r; ++k) { look(x + k, y - r); look(x + k, y + r); }
+    for (int k = -r + 1; k < r; ++k) { look(x - r, y + k); look(x + r, y + k); }
+  }
+  if (best_i == kAbsent) return;
+  const float4 a = out[(size_t)best_i * 2u], b = out[(size_t)best_i * 2u + 1u];
+  out[(size_t)i * 2u] = a; out[(size_t)i * 2u + 1u] = b;
+  if (texels) texels[i].w = best_i;
+}
+
 static BakeView bake_grid(BakeView bv) {
   bv.blocks_x = (bv.width + 7u) >> 3; bv.blocks_y = (bv.height + 7u) >> 3;
   return bv;
@@ -454,6 +497,13 @@ void launch_bake_dilate(const BakeView& view, const BakeScratch& sc, hala_occlus
   if (!bits_ready)
     hipLaunchKernelGGL(k_bake_blocks, dim3(blocks_for(bv.blocks_x * bv.blocks_y, 4)), dim3(256), 0, s, bv, sc.owner, sc.block_bits);
   hipLaunchKernelGGL(k_bake_dilate, dim3(blocks_for(bv.width * bv.height, 256)), dim3(256), 0, s, bv, sc.owner, sc.block_bits,
+                     reinterpret_cast<float4*>(out), reinterpret_cast<uint4*>(texels));
+}
+void launch_bake_dilate_transfer(const BakeView& view, const BakeScratch& sc, hala_bake_transfer_hit* out, hala_bake_texel* texels, hipStream_t s) {
+  const BakeView bv = bake_grid(view);
+  if (bv.margin == 0u) return;
+  hipLaunchKernelGGL(k_bake_blocks, dim3(blocks_for(bv.blocks_x * bv.blocks_y, 4)), dim3(256), 0, s, bv, sc.owner, sc.block_bits);
+  hipLaunchKernelGGL(k_bake_dilate_transfer, dim3(blocks_for(bv.width * bv.height, 256)), dim3(256), 0, s, bv, sc.owner, sc.block_bits,
                      reinterpret_cast<float4*>(out), reinterpret_cast<uint4*>(texels));
 }
 

@@ -116,6 +116,23 @@ hipError_t launch_bake_list(const BakeView& bv, const BakeScratch& sc, const Bak
 // are those of the unlisted pass.  One-level trees only.
 void launch_trace_occlusion_listed(const LaunchCfg& lc, const SceneView& sv, const hala_occlusion_sample* samples, const uint32_t* list, const uint32_t* count,
                                    uint32_t max_count, hala_occlusion* out, uint32_t* masks, uint32_t rays, uint32_t seed, WorkCounters* work, hipStream_t s);
+// trace_transfer.hip — RENDER_SPEC 4.13: texel i of a bake map (samples[i], as launch_bake_samples left it) projected from `front` ahead
+// of its surface along -normal onto the triangles whose global ids lie in `targets`, t in (0, tmax); out[i] gets the whole 32-B record
+// (the trace kernel its first half, then one lane per texel the normal and the height).  Launched like the multi-hit kernel (own LDS
+// size and occupancy, a grid within lc.persistent_blocks), on one-level trees.  false: the kernel fits no compute unit, or the tree is
+// a two-level one.
+// The target table: merged, sorted, disjoint [lo, hi) ranges of global triangle ids.  Up to two ranges travel as kernel arguments (an
+// unused one is [0, 0)); more are read from `table` (count entries of (lo, hi), device memory), which is then the only copy consulted.
+// A concept of its own: nothing in it knows about bake maps.
+struct TransferTargets {
+  uint32_t count;
+  uint32_t lo0, hi0, lo1, hi1;
+  const uint2* table;
+};
+bool launch_trace_transfer(const LaunchCfg& lc, const SceneView& sv, uint32_t cu_count, const hala_occlusion_sample* samples, const TransferTargets& targets,
+                           float front, float tmax, hala_bake_transfer_hit* out, uint32_t count, WorkCounters* work, hipStream_t s);
+// bake.hip — the dilation of RENDER_SPEC 4.11 on the 32-B records of 4.13 (the ownership words are made here: no bits_ready)
+void launch_bake_dilate_transfer(const BakeView& bv, const BakeScratch& sc, hala_bake_transfer_hit* out, hala_bake_texel* texels, hipStream_t s);
 // shade.hip
 void launch_shade(const FrameConst& fc, const SceneView& sv, const Queues& q, const PathState& ps, Control* ctl, uint32_t depth, hipStream_t s);
 // resolve.hip

@@ -549,6 +549,8 @@ struct hala_rt_renderer {
   // the per-block counts and offsets it is built from
   DeviceArray<BakeChartDev> d_bake_charts;
   DeviceArray<uint32_t> d_bake_list, d_bake_list_counts, d_bake_list_offsets;
+  // hala_rt_bake_transfer, RENDER_SPEC 4.13 (grown on demand): the target ranges of a call that has more than two
+  DeviceArray<uint2> d_bake_targets;
 
   uint64_t total_frames = 0;
   bool counting = false;

@@ -4,6 +4,7 @@
 // kernels read them there.  (Growing one of the renderer's buffers frees the old one, which waits for whoever still reads it.)
 // Bake atlases (RENDER_SPEC 4.12) follow: the same around the atlas kernels, the owned-texel list and the listed occlusion pass.
 // hala_rt_bake_occlusion keeps the plain pass: on a map without empty texels the listed one measured 0.5-3 % slower.
+// Transfer bakes (RENDER_SPEC 4.13) come last: the rasteriser, then the filtered closest-hit trace of trace_transfer.hip, then the dilation.
 #include "renderer_state.h"
 
 namespace {
@@ -98,7 +99,43 @@ int atlas_prepare(hala_rt_renderer* r, const hala_bake_atlas_desc* d, const hala
   RT_HIP(r->d_bake_charts.grow(table->size()));
   return HALA_OK;
 }
-// The host form of the four bakes: `call(d_out, d_texels)` is the device form on the renderer's stream
+// RENDER_SPEC 4.13: the refusals of a transfer — those of hala_rt_bake_samples first, with their texts, then its own in the order the
+// header lists them — and the target set as merged, sorted [lo, hi) ranges of global triangle ids (instances own contiguous ranges in
+// instance order; a target without triangles adds none; `ranges` null: the checks alone, for the host form).  `targets` is read here: the
+// caller's array is not needed once this returns.
+int transfer_check(hala_rt_renderer* r, const hala_bake_desc* d, const hala_bake_transfer_desc* t, const uint32_t* targets, const void* out,
+                   std::vector<uint2>* ranges) {
+  if (bake_check(r, d, out) != HALA_OK) return HALA_ERR;
+  if (!t) RT_FAIL("The bake transfer description is null!");
+  if (t->flags != 0u) RT_FAIL("Unknown bake transfer flags.");
+  if (!std::isfinite(t->front) || t->front < 0.0f) RT_FAIL("The front distance of a bake transfer must be finite and not negative.");
+  if (std::isnan(t->back) || t->back < 0.0f) RT_FAIL("The back distance of a bake transfer must be +inf or a number that is not negative.");
+  const size_t instances = r->hs.instances.size();
+  if (t->target_count > instances) RT_FAIL("The bake transfer target count must be 0.." + std::to_string(instances) + " (the scene's instances).");
+  if (t->target_count != 0u && !targets) RT_FAIL("The bake transfer target list is null!");
+  std::vector<uint8_t> is_target(instances, t->target_count == 0u ? 1 : 0);
+  if (t->target_count == 0u) {
+    if (instances < 2u) RT_FAIL("The bake transfer has no targets: the receiver is the scene's only instance.");
+    is_target[d->instance] = 0;
+  }
+  for (uint32_t k = 0; k < t->target_count; ++k) {
+    const uint32_t i = targets[k];
+    if (i >= instances) RT_FAIL("A bake transfer target is out of range (target " + std::to_string(k) + ").");
+    if (is_target[i]) RT_FAIL("A bake transfer names a target once: instance " + std::to_string(i) + " is named twice.");
+    if (i == d->instance) RT_FAIL("The receiver of a bake transfer cannot be one of its targets (instance " + std::to_string(i) + ").");
+    is_target[i] = 1;
+  }
+  if (!ranges) return HALA_OK;
+  ranges->clear();
+  for (size_t i = 0; i < instances; ++i) {
+    const uint32_t lo = r->hs.inst_first_tri[i], hi = r->hs.inst_first_tri[i + 1u];
+    if (!is_target[i] || lo == hi) continue;
+    if (!ranges->empty() && ranges->back().y == lo) ranges->back().y = hi;
+    else ranges->push_back(make_uint2(lo, hi));
+  }
+  return HALA_OK;
+}
+// The host form of the bakes: `call(d_out, d_texels)` is the device form on the renderer's stream
 template <class Rec, class Call>
 int bake_host(hala_rt_renderer* r, uint32_t width, uint32_t height, Rec* out, hala_bake_texel* texels, Call call) {
   const size_t n = (size_t)width * height;
@@ -210,6 +247,49 @@ int hala_rt_bake_atlas_occlusion_host(hala_rt_renderer* r, const hala_bake_atlas
   if (atlas_occlusion_check(r, desc, charts, out, rays) != HALA_OK) return HALA_ERR;
   return bake_host(r, desc->width, desc->height, out, texels, [&](hala_occlusion* d_out, hala_bake_texel* d_texels) {
     return hala_rt_bake_atlas_occlusion(r, desc, charts, rays, seed, d_out, d_texels, r->stream);
+  });
+}
+
+// ---- RENDER_SPEC 4.13: transfer bakes ----------------------------------------------------------------------------------------------------
+// One scope around the rasteriser (into the renderer's sample buffer), the transfer trace with its resolve, and the dilation.  Every
+// texel goes to the trace's queue: an ownerless one has the all-zero sample, which the ray load rejects at the cost of one 32-B load and
+// one 16-B store — a transfer traces ONE ray per texel, so the owned-texel list of 4.12 (three kernels and a scan ahead of the trace)
+// has nothing like the N rays per texel of an occlusion pass to win back.
+int hala_rt_bake_transfer(hala_rt_renderer* r, const hala_bake_desc* desc, const hala_bake_transfer_desc* transfer, const uint32_t* targets,
+                          hala_bake_transfer_hit* d_out, hala_bake_texel* d_texels, void* hip_stream) {
+  std::vector<uint2> ranges;
+  if (transfer_check(r, desc, transfer, targets, d_out, &ranges) != HALA_OK) return HALA_ERR;
+  rt::BakeView bv;
+  rt::BakeScratch sc;
+  if (bake_prepare(r, desc, &bv, &sc) != HALA_OK) return HALA_ERR;
+  const uint32_t count = desc->width * desc->height;
+  RT_HIP(r->d_bake_samples.grow(count));
+  rt::TransferTargets tg{(uint32_t)ranges.size(), 0u, 0u, 0u, 0u, nullptr};
+  if (ranges.size() > 2u) RT_HIP(r->d_bake_targets.grow(ranges.size()));
+  else {
+    if (ranges.size() > 0u) { tg.lo0 = ranges[0].x; tg.hi0 = ranges[0].y; }
+    if (ranges.size() > 1u) { tg.lo1 = ranges[1].x; tg.hi1 = ranges[1].y; }
+  }
+  BatchScope scope = r->batch(hip_stream);
+  if (scope.open() != HALA_OK) return HALA_ERR;
+  hipStream_t s = scope.s;
+  if (ranges.size() > 2u) {
+    RT_HIP(hipMemcpyAsync(r->d_bake_targets.ptr, ranges.data(), ranges.size() * sizeof(uint2), hipMemcpyHostToDevice, s));  // (pageable: read before it returns)
+    tg.table = r->d_bake_targets.ptr;
+  }
+  const rt::SceneView sv = r->view();
+  RT_HIP(rt::launch_bake_samples(sv, r->cu_count, bv, sc, r->d_bake_samples.ptr, d_texels, s));
+  if (scope.reset_work() != HALA_OK) return HALA_ERR;
+  const float tmax = transfer->front + transfer->back;  // one float add; +inf stays +inf
+  const bool fits = rt::launch_trace_transfer(r->lcfg, sv, r->cu_count, r->d_bake_samples.ptr, tg, transfer->front, tmax, d_out, count, r->d_batch_work.ptr, s);
+  if (fits) rt::launch_bake_dilate_transfer(bv, sc, d_out, d_texels, s);
+  return scope.close(fits ? nullptr : "The transfer traversal kernel does not fit on a compute unit.");
+}
+int hala_rt_bake_transfer_host(hala_rt_renderer* r, const hala_bake_desc* desc, const hala_bake_transfer_desc* transfer, const uint32_t* targets,
+                               hala_bake_transfer_hit* out, hala_bake_texel* texels) {
+  if (transfer_check(r, desc, transfer, targets, out, nullptr) != HALA_OK) return HALA_ERR;
+  return bake_host(r, desc->width, desc->height, out, texels, [&](hala_bake_transfer_hit* d_out, hala_bake_texel* d_texels) {
+    return hala_rt_bake_transfer(r, desc, transfer, targets, d_out, d_texels, r->stream);
   });
 }
 

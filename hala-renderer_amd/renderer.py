@@ -745,6 +745,23 @@ class HalaRenderer:
         return self._bake("hala_rt_bake_atlas_occlusion", (C.byref(d), C.c_void_p(table.ctypes.data), C.c_uint32(rays), C.c_uint32(seed)), A.OCCLUSION_DTYPE,
                           width, height, out, out_texels, stream)
 
+    def bake_transfer(self, instance, width, height, front, back=None, targets=None, *, margin=0, shading_normal=False, flip=False, out=None,
+                      out_texels=None, stream: int = 0):
+        """RENDER_SPEC 4.13: every texel of instance `instance`'s width x height bake map projected onto other instances.  The ray of a
+        texel starts `front` ahead of its surface point along the unit normal (the triangle's, or with shading_normal=True the
+        interpolated vertex normal; flip=True negates it) and runs against the normal for front + back (back=None: front; np.inf: no
+        end); it sees only the triangles of `targets`, a sequence of instance indices (None or empty: every instance but `instance`).
+        Returns (records, texels) shaped (height, width): A.BAKE_TRANSFER_HIT_DTYPE — the nearest target hit (t, u, v, prim), the
+        target's world-space shading normal there and height = front - t, the displacement along the normal; t = -1 where there is no
+        hit — and A.BAKE_TEXEL_DTYPE as bake_occlusion() gives it, with the same dilation by `margin`.
+        Device form: `out` is a device tensor (or pointer) of width * height 32-B records and `out_texels` one of 16-B texel records or
+        None; the bake is launched on `stream`, nothing leaves the device and nothing is returned."""
+        d = self._bake_desc(instance, width, height, shading_normal, flip, 0.0, np.inf, margin)
+        table = np.ascontiguousarray([] if targets is None else list(targets), dtype=np.uint32).reshape(-1)
+        t = A.BakeTransferDesc(float(front), float(front if back is None else back), 0, len(table))
+        return self._bake("hala_rt_bake_transfer", (C.byref(d), C.byref(t), C.c_void_p(table.ctypes.data) if len(table) else None), A.BAKE_TRANSFER_HIT_DTYPE,
+                          width, height, out, out_texels, stream)
+
     def bvh_info(self) -> A.BvhInfo:
         i = A.BvhInfo()
         self._check(self._lib.hala_rt_get_bvh_info(self._h, C.byref(i)))

@@ -1062,6 +1062,42 @@ int hala_rt_bake_atlas_occlusion(hala_rt_renderer* r, const hala_bake_atlas_desc
 int hala_rt_bake_atlas_occlusion_host(hala_rt_renderer* r, const hala_bake_atlas_desc* desc, const hala_bake_chart* charts, uint32_t rays, uint32_t seed,
                                       hala_occlusion* out, hala_bake_texel* texels /* or NULL */);
 
+/* Transfer bakes (RENDER_SPEC 4.13): every texel of one instance's bake map (the receiver: `desc` is the bake description above, with
+ * its coverage rule, texel record and normal flags; `bias` must be finite and is otherwise not read, like `reach`) is projected onto
+ * OTHER instances of the scene, the targets.  From the texel's surface point the ray starts `front` ahead along the unit normal n and
+ * runs against it: o = point + front * n, d = -n, t in (0, front + back).  Only triangles of target instances are seen — the receiver's
+ * own surface and every other instance let the ray through, whatever their materials — and the nearest of them by (t, triangle id)
+ * is the texel's record: the hit as hala_rt_trace_rays reports it (t, u, v, prim), the target's interpolated vertex normal at (u, v)
+ * in world space (unit length, as the shade path moves it there; not turned to face the ray, not affected by the receiver's flags) and
+ * height = front - t, the signed offset of the target's surface from the receiver's along n: the displacement value.  A texel without
+ * a sample, an invalid sample and a ray that meets no target all get {-1, 0, 0, ~0, {0, 0, 0}, 0}; d_texels (or NULL) tells them apart.
+ * Then the dilation of the bake maps, over the 32-B records: a texel without a sample takes the record of the nearest texel with one,
+ * hit or miss, within `margin`.
+ * `targets` is a host array of transfer->target_count instance indices in instance order (RENDER_SPEC 3), read before the call
+ * returns; their order does not matter.  target_count == 0 (then `targets` may be NULL) means every instance but the receiver.
+ * Scratch, stream order, growing buffers and the optional d_texels are as for the bake maps.  Refused with a message and without
+ * touching anything: everything hala_rt_bake_samples refuses, a null `transfer`, transfer->flags != 0, a negative or non-finite
+ * `front`, a negative or NaN `back` (+inf is allowed), target_count above the scene's instance count, NULL `targets` with a count, a
+ * target out of range or named twice, the receiver among the targets, a scene of one instance with target_count == 0.
+ * Not built: any rule but the first hit seen from the cage (no nearest-to-the-receiver, no two-sided search); tangent-space encoding of
+ * the normal (the texel record's (u, v, prim) and the world normal give a host what it needs); an atlas form; instance masks on plain
+ * ray batches (hala_rt_trace_rays, hala_rt_trace_rays_multi); supersampling; two-level trees. */
+typedef struct hala_bake_transfer_desc {
+  float front, back;     /* distances along the normal: finite front >= 0; back >= 0 or +inf */
+  uint32_t flags;        /* 0 */
+  uint32_t target_count; /* 0: every instance but the receiver */
+} hala_bake_transfer_desc; /* 16 B */
+typedef struct hala_bake_transfer_hit {
+  float t, u, v;
+  uint32_t prim;
+  float normal[3];
+  float height;
+} hala_bake_transfer_hit; /* 32 B; no hit: {-1, 0, 0, ~0, {0, 0, 0}, 0} */
+int hala_rt_bake_transfer(hala_rt_renderer* r, const hala_bake_desc* desc, const hala_bake_transfer_desc* transfer, const uint32_t* targets,
+                          hala_bake_transfer_hit* d_out /* width * height */, hala_bake_texel* d_texels /* or NULL */, void* hip_stream);
+int hala_rt_bake_transfer_host(hala_rt_renderer* r, const hala_bake_desc* desc, const hala_bake_transfer_desc* transfer, const uint32_t* targets,
+                               hala_bake_transfer_hit* out, hala_bake_texel* texels /* or NULL */);
+
 /* BVH introspection for the oracle cross-check: 64-B nodes + 48-B triangles as laid out in HBM.
  * node_width is 4: compressed 4-wide nodes (docs/RENDER_SPEC.md §4.1b). */
 typedef struct hala_bvh_info {

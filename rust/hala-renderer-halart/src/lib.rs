@@ -76,6 +76,9 @@ pub mod sys {
   /// hala_bake_chart (24 B) / hala_bake_atlas_desc (24 B): bake atlases (include/halart.h, docs/RENDER_SPEC.md 4.12); flags: HALA_BAKE_*, per chart
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_bake_chart { pub instance: u32, pub flags: u32, pub scale: [f32; 2], pub offset: [f32; 2] }
   #[repr(C)] #[derive(Clone, Copy)] pub struct hala_bake_atlas_desc { pub width: u32, pub height: u32, pub bias: f32, pub reach: f32, pub margin: u32, pub chart_count: u32 }
+  /// hala_bake_transfer_desc (16 B) / hala_bake_transfer_hit (32 B): transfer bakes (include/halart.h, docs/RENDER_SPEC.md 4.13); flags: 0
+  #[repr(C)] #[derive(Clone, Copy)] pub struct hala_bake_transfer_desc { pub front: f32, pub back: f32, pub flags: u32, pub target_count: u32 }
+  #[repr(C)] #[derive(Clone, Copy)] pub struct hala_bake_transfer_hit { pub t: f32, pub u: f32, pub v: f32, pub prim: u32, pub normal: [f32; 3], pub height: f32 }
   #[repr(C)] #[derive(Default)] pub struct hala_rt_info { pub width: u32, pub height: u32 }
 
   /// hala_rt_build_options (include/halart.h): every field 0 = the default
@@ -176,6 +179,10 @@ pub mod sys {
                                         d_out: *mut hala_occlusion, d_texels: *mut hala_bake_texel, hip_stream: *mut c_void) -> c_int;
     pub fn hala_rt_bake_atlas_occlusion_host(r: *mut hala_rt_renderer, desc: *const hala_bake_atlas_desc, charts: *const hala_bake_chart, rays: u32, seed: u32,
                                              out: *mut hala_occlusion, texels: *mut hala_bake_texel) -> c_int;
+    pub fn hala_rt_bake_transfer(r: *mut hala_rt_renderer, desc: *const hala_bake_desc, transfer: *const hala_bake_transfer_desc, targets: *const u32,
+                                 d_out: *mut hala_bake_transfer_hit, d_texels: *mut hala_bake_texel, hip_stream: *mut c_void) -> c_int;
+    pub fn hala_rt_bake_transfer_host(r: *mut hala_rt_renderer, desc: *const hala_bake_desc, transfer: *const hala_bake_transfer_desc, targets: *const u32,
+                                      out: *mut hala_bake_transfer_hit, texels: *mut hala_bake_texel) -> c_int;
     pub fn hala_rt_update_node_transform(r: *mut hala_rt_renderer, node_index: u32, local_transform: *const f32) -> c_int;
     pub fn hala_rt_update_material(r: *mut hala_rt_renderer, material_index: u32, material: *const hala_material_desc) -> c_int;
     pub fn hala_rt_update_vertices(r: *mut hala_rt_renderer, mesh_index: u32, primitive_index: u32, vertices: *const hala_vertex, vertex_count: u32) -> c_int;
@@ -466,6 +473,25 @@ impl HalaRenderer {
                                      d_out: *mut sys::hala_occlusion, d_texels: *mut sys::hala_bake_texel) -> Result<(), HalaRendererError> {
     let d = sys::hala_bake_atlas_desc { chart_count: charts.len() as u32, ..*desc };
     check(unsafe { sys::hala_rt_bake_atlas_occlusion(self.h, &d, charts.as_ptr(), rays, seed, d_out, d_texels, std::ptr::null_mut()) })
+  }
+  /// transfer bakes (RENDER_SPEC 4.13) to host memory: every texel of `desc.instance`'s map projected from `front` ahead of its surface to `back`
+  /// behind it onto the instances of `targets` (empty: every other instance); `transfer.target_count` is taken from the slice
+  pub fn bake_transfer(&self, desc: &sys::hala_bake_desc, transfer: &sys::hala_bake_transfer_desc, targets: &[u32])
+                       -> Result<(Vec<sys::hala_bake_transfer_hit>, Vec<sys::hala_bake_texel>), HalaRendererError> {
+    let t = sys::hala_bake_transfer_desc { target_count: targets.len() as u32, ..*transfer };
+    let n = desc.width as usize * desc.height as usize;
+    let mut out = vec![sys::hala_bake_transfer_hit { t: -1.0, u: 0.0, v: 0.0, prim: u32::MAX, normal: [0.0; 3], height: 0.0 }; n];
+    let mut texels = vec![sys::hala_bake_texel { u: 0.0, v: 0.0, prim: u32::MAX, source: u32::MAX }; n];
+    let list = if targets.is_empty() { std::ptr::null() } else { targets.as_ptr() };
+    check(unsafe { sys::hala_rt_bake_transfer_host(self.h, desc, &t, list, out.as_mut_ptr(), texels.as_mut_ptr()) })?;
+    Ok((out, texels))
+  }
+  /// the device-pointer form, on the renderer's stream; the target list is read before it returns; d_texels may be null
+  pub fn bake_transfer_device(&self, desc: &sys::hala_bake_desc, transfer: &sys::hala_bake_transfer_desc, targets: &[u32],
+                              d_out: *mut sys::hala_bake_transfer_hit, d_texels: *mut sys::hala_bake_texel) -> Result<(), HalaRendererError> {
+    let t = sys::hala_bake_transfer_desc { target_count: targets.len() as u32, ..*transfer };
+    let list = if targets.is_empty() { std::ptr::null() } else { targets.as_ptr() };
+    check(unsafe { sys::hala_rt_bake_transfer(self.h, desc, &t, list, d_out, d_texels, std::ptr::null_mut()) })
   }
   /// binds an ordered node set (empty: unbinds); refit_nodes then takes one local transform per bound node, in that order
   pub fn bind_nodes(&mut self, node_indices: &[u32]) -> Result<(), HalaRendererError> {
